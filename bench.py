@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GCUPS of the hw2.cpp DP hot path on MI355X (contract: one JSON line on rank 0).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c2|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c2|c5] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM.
 Default workload (BASELINE.json configs[2], the config the >=1 TCUPS target is quoted on):
@@ -116,6 +116,24 @@ def attach_traffic(roofline, workload):
         roofline["traffic_source"] = tj.get("source")
         if tj.get("kernel_avg_ms") is not None:
             roofline["traffic_note"] = "per dispatch of %s (rocprof avg %.4f ms per dispatch)" % (tj.get("kernel"), tj["kernel_avg_ms"])
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all files together
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one d/<name>.npy per array in float64 (exact for every score,
+    count and position the paths return).  An array larger than its equal share of DUMP_LIMIT_BYTES is written as a fixed seeded
+    sample of its elements, with their flat positions in d/<name>_index.npy, so that two builds still compare element for element."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays) - 256   # room for the .npy headers
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size * 8 > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // 16, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
 
 
 # ----------------------------------------------------------------------------- CPU baseline leg
@@ -302,9 +320,14 @@ def main():
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="launcher / sharding / collective rehearsal without a GPU: gloo + the CPU oracle as compute "
                          "(needs --small; the line is marked invalid)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64, at most 64 MB in all: "
+                         "larger outputs as a fixed seeded sample)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.rehearse_cpu and not args.small:
         raise SystemExit("--rehearse-cpu is a functional rehearsal: it needs --small")
 
@@ -459,6 +482,12 @@ def main():
         step()
     sync()
     elapsed = time.perf_counter() - t0
+    last = None
+    if args.dump_outputs and rank == 0:   # copied now: the host-call leg below fetches into `scores` again
+        name = "distances" if mode == "nwdist" else "scores"
+        last = {name: scores.copy()}
+        if use_dist:
+            last["gathered_" + name] = state["gathered"].cpu().numpy()
     kernel_ms = batch.run_times(min(args.steps, 64))   # HIP events on the launch stream, per step
     cells = info["cells"]
     if use_dist:
@@ -483,6 +512,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
 
     ms_per_step = elapsed / args.steps * 1e3
     gcups = cells_total * args.steps / elapsed / 1e9
@@ -658,6 +689,12 @@ def bench_global_batch(args, pkg, ctx, rank=0, world=1, dist=None, torch=None, d
             return
     res = [dict(score=int(out["scores"][k]), ops=out["ops"][int(out["ops_off"][k]):int(out["ops_off"][k]) + int(out["n_ops"][k])])
            for k in range(n_pairs)]
+    if args.dump_outputs:
+        arrays = {k: out[k][:n_pairs] for k in ("scores", "n_ops", "end", "start")}
+        arrays["ops"] = np.concatenate([r["ops"] for r in res])   # the op lists back to back, without the buffer's slack
+        if dist is not None:
+            arrays["gathered"] = state["gathered"].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     # a seeded sample of the batch against the CPU oracle, op for op (after the timed region)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import oracle_lib as O
@@ -749,6 +786,9 @@ def bench_single_pair(args, pkg, ctx, rank, world, dist, torch):
     if rank != 0:
         dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"score": [r["score"]], "ops": np.frombuffer(r["ops"], dtype=np.uint8),
+                                         "end": r["end"], "start": r["start"]})
     st = ctx.align_stats()
     cells = float(n) * m
     k_ms = float(np.mean(fill))

@@ -100,6 +100,15 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+def ref_vectors(key):
+    """What the compiled reference returned for the seeded inputs of one differential test (tests/golden/differential.json.gz,
+    written by tests/golden/make_golden_differential.py): the tests need no oracle/_ref."""
+    import gzip
+    import json
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "differential.json.gz"), "rt") as f:
+        return json.load(f)[key]
+
+
 def ref():
     global _ref
     if _ref is None:

@@ -75,7 +75,8 @@ class RehearsalContext:
             ops[int(ops_off[k]):int(ops_off[k]) + len(r["ops"])] = np.frombuffer(r["ops"], dtype=np.uint8)
         self._ms = (time.perf_counter() - t0) * 1e3
         return dict(scores=np.array([r["score"] for r in res], dtype=np.int32), n_ops=np.array([len(r["ops"]) for r in res], dtype=np.uint64),
-                    ops=ops, ops_off=ops_off)
+                    ops=ops, ops_off=ops_off, end=np.array([r["end"] for r in res], dtype=np.uint64).reshape(-1, 2),
+                    start=np.array([r["start"] for r in res], dtype=np.uint64).reshape(-1, 2))
 
     def align_stats(self):
         return dict(fill_ms=self._ms, traceback_ms=0.0, band_bytes=0)

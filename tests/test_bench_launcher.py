@@ -79,3 +79,51 @@ def test_a_failing_rank_fails_the_launch():
     pr = _run(["--gpus", "2", "--small", "--rehearse-cpu", "--workload", "c3"], {"BENCH_TEST_FAIL_RANK": "1"}, timeout=120)
     assert pr.returncode != 0
     assert not [l for l in pr.stdout.decode().splitlines() if l.startswith("{")]
+
+
+@pytest.mark.parametrize("workload", ["c3", "g"])
+def test_dump_outputs_hold_what_the_last_step_returned(workload, tmp_path):
+    """--dump-outputs DIR: rank 0 writes the arrays the timed path returned, as float .npy files that match the CPU oracle."""
+    import numpy as np
+    pr = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--small", "--rehearse-cpu",
+               "--dump-outputs", str(tmp_path)])
+    assert pr.returncode == 0, pr.stderr.decode()[-2000:]
+    assert json.loads([l for l in pr.stdout.decode().splitlines() if l.startswith("{")][0])["steps"] == 3
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    if workload == "c3":   # rank r: 24 patterns x its own 4 texts, pattern-major
+        assert sorted(got) == ["gathered_scores", "scores"]
+        want = [O.score("sw", O.gen(1, 0, k // 4, 150), O.gen(1, 1, r * 4 + k % 4, 300), 1, -1, -1)[0] for r in range(2) for k in range(96)]
+        assert got["scores"].tolist() == want[:96] and got["gathered_scores"].tolist() == want
+    else:                  # rank 0's block: 8 patterns against texts k % 4, full alignments
+        assert sorted(got) == ["end", "gathered", "n_ops", "ops", "scores", "start"]
+        want = [O.align("nw", O.gen(1, 0, k, 40), O.gen(1, 1, k % 4, 200), 1, -1, -1, compact=True) for k in range(8)]
+        assert got["scores"].tolist() == [w["score"] for w in want]
+        assert got["n_ops"].tolist() == [len(w["ops"]) for w in want]
+        assert bytes(got["ops"].astype(np.uint8)) == b"".join(w["ops"] for w in want)
+        assert got["end"].tolist() == [list(w["end"]) for w in want] and got["start"].tolist() == [list(w["start"]) for w in want]
+
+
+def test_dump_outputs_stay_within_64_mb(tmp_path):
+    """an output past its share of the 64 MB is written as a seeded sample plus the sample's positions"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big, small = np.arange(12_000_000, dtype=np.int32)[::-1].copy(), np.arange(5, dtype=np.int32)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"big": big, "small": small})
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 10**6
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "big_index.npy", "small.npy"]
+    idx = np.load(tmp_path / "a" / "big_index.npy").astype(np.int64)
+    assert len(idx) > 1_000_000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+    for f in os.listdir(tmp_path / "a"):   # the same sample every run
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+
+
+def test_steps_must_be_positive():
+    pr = _run(["--gpus", "1", "--steps", "0", "--small", "--rehearse-cpu"])
+    assert pr.returncode != 0 and b"--steps must be >= 1" in pr.stderr

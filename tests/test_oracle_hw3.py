@@ -1,8 +1,5 @@
 """The hw3 affine checker checked against fixtures generated from the unmodified hw3.cpp.  CPU only."""
 import os
-import random
-
-import pytest
 
 import oracle_lib as O
 from conftest import B, GOLDEN, load_golden
@@ -39,14 +36,11 @@ def test_center_of_reference_known_answer():
     assert seqs[c][0] == first
 
 
-@pytest.mark.skipif(not O.have_ref3(), reason="oracle/_ref only exists in the dev container")
 def test_affine_oracle_differential():
-    rng = random.Random(8)
-    for it in range(1500):
-        a = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 50)))
-        b = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 50)))
-        sc = rng.choice([(5, -4, -16, -4), (1, -1, -2, -1), (1, 1, 1, 1), (0, 0, 0, 0), (4, -5, 2, -1), (2, -1, -3, 1)])
-        assert O.affine_score(a, b, *sc) == O.ref_affine_score(a, b, *sc), (a, b, sc)
+    """1500 seeded random pairs against the compiled reference's scores (tests/golden/differential.json.gz)"""
+    for rec in O.ref_vectors("hw3_scores"):
+        a, b, sc = B(rec["a"]), B(rec["b"]), rec["scoring"]
+        assert O.affine_score(a, b, *sc) == rec["score"], (a, b, sc)
 
 
 def _ops_from_strings(a1, a2):
@@ -63,16 +57,12 @@ def test_affine_alignment_oracle_matches_reference_vectors():
         assert got["ops"] == _ops_from_strings(B(rec["a1"]), B(rec["a2"]))
 
 
-@pytest.mark.skipif(not O.have_ref3(), reason="oracle/_ref only exists in the dev container")
 def test_affine_alignment_oracle_differential():
-    rng = random.Random(18)
-    for it in range(600):
-        alpha = rng.choice([b"AC", b"ACGT", b"ACDEFGHIKLMNPQRSTVWY"])
-        a = bytes(rng.choice(alpha) for _ in range(rng.randint(0, 45)))
-        b = bytes(rng.choice(alpha) for _ in range(rng.randint(0, 45)))
-        sc = rng.choice([(5, -4, -16, -4), (1, -1, -2, -1), (1, -1, 0, -1), (0, 0, 0, 0), (2, -1, -3, 1), (1, 1, 1, 1)])
-        r, o = O.ref_affine_align(a, b, *sc), O.affine_align(a, b, *sc)
-        assert (o["score"], o["a1"], o["a2"]) == (r["score"], r["a1"], r["a2"]), (a, b, sc)
+    """600 seeded random pairs against the compiled reference's gapped strings (tests/golden/differential.json.gz)"""
+    for rec in O.ref_vectors("hw3_alignments"):
+        a, b, sc = B(rec["a"]), B(rec["b"]), rec["scoring"]
+        o = O.affine_align(a, b, *sc)
+        assert (o["score"], o["a1"], o["a2"]) == (rec["score"], B(rec["a1"]), B(rec["a2"])), (a, b, sc)
 
 
 def run_hw3_cases(exe, tmp_path, name="hw3"):

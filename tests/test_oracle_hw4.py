@@ -1,9 +1,6 @@
 """The hw4 checker (NW distance, UPGMA, CLI) against fixtures generated from the unmodified hw4.cpp.  CPU only."""
 import os
-import random
 import subprocess
-
-import pytest
 
 import oracle_lib as O
 from conftest import B, GOLDEN, load_golden
@@ -44,11 +41,8 @@ def test_hw4_oracle_cli(tmp_path):
     assert (tmp_path / "t.txt").read_bytes() == open(os.path.join(GOLDEN, "hw4_tree.txt"), "rb").read()
 
 
-@pytest.mark.skipif(not O.have_ref4(), reason="oracle/_ref only exists in the dev container")
 def test_hw4_distance_differential():
-    rng = random.Random(44)
-    for it in range(1500):
-        a = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 50)))
-        b = bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 50)))
-        sc = rng.choice([(1, -1, -1), (2, -3, -5), (1, 1, 1), (0, 0, 0), (-1, 2, 1), (1, -1, 0)])
-        assert O.nw_distance(a, b, *sc)[0] == O.ref_nw_distance(a, b, *sc), (a, b, sc)
+    """1500 seeded random pairs against the compiled reference's distances (tests/golden/differential.json.gz)"""
+    for rec in O.ref_vectors("hw4"):
+        a, b, sc = B(rec["a"]), B(rec["b"]), rec["scoring"]
+        assert O.nw_distance(a, b, *sc)[0] == rec["dist"], (a, b, sc)
