@@ -537,6 +537,7 @@ struct PairLaunch {
     bool perm = false;   // sequences are coded 0..6 (pad 7) and the key constants fit a byte: table-scoring fill kernels
     bool keyed = true;   // traceback fills keep H * 4 + priority (needs |H| < 2^28); false: plain int32 compare-and-select form
     bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
+    bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;
@@ -558,7 +559,7 @@ struct PairLaunch {
             pd[q].n_stripes = (uint32_t)ns;
             pd[q].row_stride = (uint32_t)align_up((uint64_t)pd[q].m + 64, 64);
             for (uint64_t st = 0; st < nsup; ++st) tl.push_back({(uint32_t)q, (uint32_t)st});
-            rows_i32 += (nsup - 1) * pd[q].row_stride;
+            rows_i32 += (nsup - 1) * pd[q].row_stride * (dist ? 2 : 1);
             n_stripes_total += ns;
         }
         row_bytes = rows_i32 * sizeof(int32_t);
@@ -567,7 +568,7 @@ struct PairLaunch {
         for (auto& d : pd) {
             d.rows = static_cast<int32_t*>(p_rows) + ro;
             const uint64_t nsup = ((uint64_t)d.n_stripes + g.w - 1) / g.w;
-            ro += (nsup - 1) * d.row_stride;
+            ro += (nsup - 1) * d.row_stride * (dist ? 2 : 1);
         }
         HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
         HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
@@ -678,6 +679,17 @@ struct PairLaunch {
             G.stamps = stamps.as<unsigned long long>();
             G.trace_base = (uint32_t)(n_stripes * 4);
             G.trace_stripe = ctx->knobs.trace_stripe;
+        }
+        if (dist) {   // hw4 distances: the fill writes D[n][m] into the score vector itself
+            const pair_kernel_t fill = pair_dist_kernel_for(geom.rl, geom.w);
+            if (!fill) return fail(ctx, PWA_E_INVALID, "internal: no distance kernel for this geometry");
+            size_t pad_lds = 0;   // (one multi-stripe workgroup per CU when they are few: as below)
+            if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;
+            if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+            hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
+            HIPC(ctx, hipGetLastError());
+            if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+            return PWA_OK;
         }
         // (scores / end cells only over a coded arena, keys in range: the keyed chunk without a band -- batch_create_impl sets perm for that)
         const bool noband = !tb && perm && keyed && !sband;
@@ -897,6 +909,10 @@ int pwa_ctx_set_score_band(pwa_ctx* c, int on) {
 // ---------------------------------------------------------------------------- batch: create
 } // extern "C" (reopened below): the shared implementation has C++ linkage
 enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2 };
+// Route estimates of the stripe engine's distance fill (pair_dist.hip.h), in the units of the estimate (stripes of choose_geom's
+// geometry): ns per stripe step and SIMD with the chip full, us of pipeline lag per stripe, ns per step of a pair alone.  [gpu]
+// profiles/hw4_long_route_probe.txt: 496 pairs 10k x 10k 29.9 ms; one pair 10k x 10k 2.66 ms, 20k x 20k 5.29 ms.
+constexpr double kDistStepNs = 80.0, kDistLagUs = 13.0, kDistLoneStepNs = 162.0;
 static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, int kind, int gap_extend,
                              const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
                              const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
@@ -1113,6 +1129,9 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             arena_bytes += align_up(slen(s) + 1, 16);
         }
     arena_bytes += 512;   // slack: strips and text words are over-read, never over-used
+    // (a strip task loads its lanes' pattern words for every strip of its LONGEST pattern and masks them after the load: a short pattern
+    // is read up to that length past its start -- past the end of the arena when it lies last, which faulted on the device)
+    if (b->use_strips) arena_bytes += align_up(max_n, 16);
     if (arena_bytes >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "sequence arena exceeds 4 GiB");
     // (a scores pass that wants end cells runs wholly off the strips: its arena is coded whenever the alphabet allows, for the mini-stripe
     // kernels -- the stripe engine's compare form is the same on codes, a pattern-only symbol is code 7 and equals no text code)
@@ -1278,14 +1297,23 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         // the split with the smallest estimated total -- the two launches run one after the other on the run's stream -- wins.
         // Pairs are independent (hw2.cpp:328-338) and both engines are exact, so a split changes no result.
         std::vector<uint32_t> pair_list;   // pair indices routed to the stripe engine
-        if (!affine && !nwdist && ctx->knobs.scores_route != 0) {
+        // hw4 distances take the same split when the batch is in the two-value form (some n + m > 4000, or PWA_NO_PACKED_DIST): coded arena,
+        // keys H * 4 + prio inside int32 (pair_dist.hip.h).  Packed-form lists, other byte alphabets and larger scores stay on the strips.
+        bool dist_route = false;
+        if (nwdist && kmode == BM_DIST && score_path == SC_PERM) {
+            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap), 1});
+            dist_route = (int64_t)(max_n + max_m + 2) * amax < (1ll << 28);
+        }
+        if (((!affine && !nwdist) || dist_route) && ctx->knobs.scores_route != 0) {
             const size_t nt0 = ht.size();
-            const double vpc = (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
-            constexpr double kLoneNs = 1.9, kSimdNs = 1.63, kSimds = 1024.0;                // ns per wave instruction: one wave alone / a SIMD with two
+            const double vpc = nwdist ? 10.75 : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
+            constexpr double kLoneNs = 1.9, kSimdNs = 1.63;                                 // ns per wave instruction: one wave alone / a SIMD with two
+            const double kSimds = nwdist ? 4.0 * ctx->num_cu : 1024.0;
             // stripe engine: per step and SIMD; per stripe of pipeline lag; per step of a pair alone -- the keyed chunk without a band (coded
-            // arena, keys in range) or the plain step ([gpu] r03_route_probe.txt: one 10k x 10k pair 1.26 / 1.01 ms, 64 pairs 3.45 / 2.05 ms)
-            const double step_ns = mini_scores ? (local ? 70.0 : 42.0) : (local ? 105.0 : 75.0), lag_us = 9.0,
-                         lone_step_ns = mini_scores ? (local ? 55.0 : 30.0) : 100.0;
+            // arena, keys in range) or the plain step ([gpu] r03_route_probe.txt: one 10k x 10k pair 1.26 / 1.01 ms, 64 pairs 3.45 / 2.05 ms);
+            // the distance fill (profiles/hw4_long_route_probe.txt)
+            const double step_ns = nwdist ? kDistStepNs : mini_scores ? (local ? 70.0 : 42.0) : (local ? 105.0 : 75.0), lag_us = nwdist ? kDistLagUs : 9.0,
+                         lone_step_ns = nwdist ? kDistLoneStepNs : mini_scores ? (local ? 55.0 : 30.0) : 100.0;
             std::vector<double> I(nt0), S(nt0), L(nt0);   // strip instructions / stripe-side work (ns x SIMD) / longest single-pair latency (us) of a task
             double I_total = 0, I_max = 0;
             uint64_t filled = 0;
@@ -1351,7 +1379,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             const double tA = strips_fit ? 0.0 : evaluate(ordA, kA), tB = strips_fit ? 0.0 : evaluate(ordB, kB);
             const std::vector<uint32_t>& ord = tA <= tB ? ordA : ordB;
             size_t kmove = strips_fit ? 0 : (tA <= tB ? kA : kB);
-            if (ctx->knobs.scores_route == 1) kmove = nt0;   // tests: everything on the stripe engine
+            if (ctx->knobs.scores_route == 1) kmove = nt0;   // tests: everything (eligible) on the stripe engine
             if (dbg) std::fprintf(stderr, "[pwa] route: %zu of %zu wave tasks to the stripe engine (estimates: all on strips %.1f us, split %.1f us)\n",
                                   kmove, nt0, std::max(*std::max_element(I.begin(), I.end()) * kLoneNs, I_total / kSimds * kSimdNs) * 1e-3, std::min(tA, tB));
             if (kmove) {
@@ -1637,7 +1665,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             // a coded arena with keys in range (what the band-less mini kernels ask for as well): the keyed chunk without a band -- table
             // scoring, one v_max3 per cell, global fills gap-shifted -- instead of the plain compare-and-select step: [gpu, r03] SW scores of
             // 64 pairs 10k x 10k 4.8 -> 3.45 ms, NW 4.06 -> 2.05 ms; one pair 1.67 -> 1.26 / 1.55 -> 1.01 ms
-            const bool keyed_scores = mini_scores && !ctx->knobs.no_keyed_tb && !ctx->knobs.no_pair_table;
+            const bool keyed_scores = !nwdist && mini_scores && !ctx->knobs.no_keyed_tb && !ctx->knobs.no_pair_table;
             const bool gap0_scores = keyed_scores && mini_gap0 && !ctx->knobs.no_gap_shift;
             for (const uint32_t k : plist) {
                 PairDesc d = describe(k, q_next++);
@@ -1648,10 +1676,12 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             b->pl.perm = keyed_scores;
             b->pl.keyed = true;
             b->pl.gap0 = gap0_scores;
+            b->pl.dist = nwdist;
             const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom);
             if (rc != PWA_OK) return rc;
             b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
-            names = std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
+            names = nwdist ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
+                           : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
         }
         for (auto& cls : mini_lists) {
             const int rl = cls.first;

@@ -36,7 +36,8 @@
  * consults the environment, so a process that wants another setting creates another context.  (pwa_fasta_read, which has no context,
  * reads PWA_FASTA_MIN_CHUNK -- bytes per parser chunk -- on every call.)
  *   PWA_DEBUG, PWA_PROBE          host-side phase times / nop-kernel probes on stderr
- *   PWA_SCORES_ROUTE=0|1          scores passes: 0 every pair on the strip engine, 1 every pair on the stripe engine (default: by cost)
+ *   PWA_SCORES_ROUTE=0|1          scores passes: 0 every pair on the strip engine, 1 every pair on the stripe engine (default: by cost);
+ *                                 distance passes in the two-value form likewise, for the pairs the stripe engine's distance fill takes
  *   PWA_TB_ENGINE=0|2             traceback fills and scores off the strips: 0 the stripe engine's plain forms only, 2 mini-stripe kernels
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
@@ -181,6 +182,11 @@ int pwa_align_affine_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, 
  * for pair k (pair_a = sequence1 = rows, pair_b = sequence2 = columns).  No traceback is stored: the
  * kernel carries the distance of the chosen path through the DP.  The batch object behaves like any
  * other (run / d_scores / fetch / info / destroy; no end cells).
+ * Engines: the strip kernels (lane = pair) take every list; a list in the two-value form (some pair with
+ * n + m > 4000, or PWA_NO_PACKED_DIST) over at most 7 symbols with (n + m + 2) * max|score| < 2^28 is split
+ * by estimated cost between them and the stripe engine's distance fill (a pair over many waves: few long
+ * sequences), like a scores pass; PWA_SCORES_ROUTE=0 keeps every pair on the strips, =1 moves every such
+ * pair.  A split batch reports "<strip kernel> + <stripe kernel>".  pwa_distances inherits the routing.
  */
 int pwa_nwdist_batch_create(pwa_ctx *ctx, int match, int mismatch, int gap, const uint8_t *seq_bytes,
                             const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
