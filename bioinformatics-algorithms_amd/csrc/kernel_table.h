@@ -36,6 +36,9 @@ pair_kernel_t pair_traceback_kernel_for(int rl, bool local, int walk);   // walk
 // pair_dist_kernels.hip -- hw4's NW distance on the stripe engine (rl = 2 | 4, w = 1 | 4): no band, no walk, D[n][m] straight into
 // PairParams::scores_out
 pair_kernel_t pair_dist_kernel_for(int rl, int w);
+// pair_affine_kernels.hip -- hw3's affine score on the stripe engine (rl = 2 | 4, w = 1 | 4): no band, no walk, M[n][m] straight
+// into PairParams::scores_out; PairParams::gap = gap opening, gap_extend = gap extension
+pair_kernel_t pair_affine_kernel_for(int rl, int w);
 // mini_kernels*.hip -- the mini-stripe engine (16 lanes per pair, 4 pairs per wave; keyed cells, table scoring): fills for
 // rl in kMiniRL; gap0 only global without score band; the walks over its band geometry (BandGeo<16, rl>)
 constexpr int kMiniRL[] = {4, 6, 8, 10, 12, 16};

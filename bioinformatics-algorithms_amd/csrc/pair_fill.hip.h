@@ -117,6 +117,7 @@ struct PairParams {
     unsigned long long* stamps;   // debugging (PWA_STAMPS): per stripe {start, first interior chunk, end, -} in s_memrealtime ticks (10 ns), or nullptr
     int32_t dash;           // WALK_OVERLAP: the arena's symbol for a literal '-' (its code when the arena is coded), or a
                             // value no symbol has when no sequence contains one (hw2.cpp:269 skips such columns)
+    int32_t gap_extend;     // affine scores (pair_affine.hip.h): hw3's gap extension; gap is then the gap opening
 };
 
 __device__ __forceinline__ int p_addw(int a, int b) { return (int)((unsigned)a + (unsigned)b); }

@@ -538,13 +538,14 @@ struct PairLaunch {
     bool keyed = true;   // traceback fills keep H * 4 + priority (needs |H| < 2^28); false: plain int32 compare-and-select form
     bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
     bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
+    bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;
     DevBuf stamps;   // PWA_STAMPS=<file>: per-stripe time stamps of the fill (debugging the stripe pipeline)
 
     // pd[q].{pat,txt,n,m,tb,sband,res,ops,ops_cap} filled by the caller; this adds the pipeline fields
-    int build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g) {
+    int build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g, int gap_extend = 0) {
         geom = g;
         const uint64_t rows_per_stripe = 64ull * g.rl;
         std::vector<StripeTask> tl;
@@ -559,7 +560,7 @@ struct PairLaunch {
             pd[q].n_stripes = (uint32_t)ns;
             pd[q].row_stride = (uint32_t)align_up((uint64_t)pd[q].m + 64, 64);
             for (uint64_t st = 0; st < nsup; ++st) tl.push_back({(uint32_t)q, (uint32_t)st});
-            rows_i32 += (nsup - 1) * pd[q].row_stride * (dist ? 2 : 1);
+            rows_i32 += (nsup - 1) * pd[q].row_stride * (dist || aff ? 2 : 1);
             n_stripes_total += ns;
         }
         row_bytes = rows_i32 * sizeof(int32_t);
@@ -568,7 +569,7 @@ struct PairLaunch {
         for (auto& d : pd) {
             d.rows = static_cast<int32_t*>(p_rows) + ro;
             const uint64_t nsup = ((uint64_t)d.n_stripes + g.w - 1) / g.w;
-            ro += (nsup - 1) * d.row_stride * (dist ? 2 : 1);
+            ro += (nsup - 1) * d.row_stride * (dist || aff ? 2 : 1);
         }
         HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
         HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
@@ -592,6 +593,7 @@ struct PairLaunch {
         G.match = match;
         G.mismatch = mismatch;
         G.gap = gap;
+        G.gap_extend = gap_extend;
         G.dash = 0x100;   // no symbol: set by the callers that walk for overlaps
         G.stamps = nullptr;
         G.trace_stripe = -1;
@@ -680,9 +682,9 @@ struct PairLaunch {
             G.trace_base = (uint32_t)(n_stripes * 4);
             G.trace_stripe = ctx->knobs.trace_stripe;
         }
-        if (dist) {   // hw4 distances: the fill writes D[n][m] into the score vector itself
-            const pair_kernel_t fill = pair_dist_kernel_for(geom.rl, geom.w);
-            if (!fill) return fail(ctx, PWA_E_INVALID, "internal: no distance kernel for this geometry");
+        if (dist || aff) {   // hw4 distances / hw3 affine scores: the fill writes D[n][m] / M[n][m] into the score vector itself
+            const pair_kernel_t fill = dist ? pair_dist_kernel_for(geom.rl, geom.w) : pair_affine_kernel_for(geom.rl, geom.w);
+            if (!fill) return fail(ctx, PWA_E_INVALID, "internal: no distance / affine kernel for this geometry");
             size_t pad_lds = 0;   // (one multi-stripe workgroup per CU when they are few: as below)
             if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;
             if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
@@ -913,6 +915,9 @@ enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2 };
 // geometry): ns per stripe step and SIMD with the chip full, us of pipeline lag per stripe, ns per step of a pair alone.  [gpu]
 // profiles/hw4_long_route_probe.txt: 496 pairs 10k x 10k 29.9 ms; one pair 10k x 10k 2.66 ms, 20k x 20k 5.29 ms.
 constexpr double kDistStepNs = 80.0, kDistLagUs = 13.0, kDistLoneStepNs = 162.0;
+// ... and of the affine score fill (pair_affine.hip.h), [gpu] profiles/hw3_long_route_probe.txt: 496 pairs 10k x 10k 23.4 ms; one pair
+// 10k x 10k 1.62 ms, 20k x 20k 3.21 ms.
+constexpr double kAffStepNs = 62.0, kAffLagUs = 8.0, kAffLoneStepNs = 99.0;
 static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, int kind, int gap_extend,
                              const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
                              const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
@@ -1304,16 +1309,26 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap), 1});
             dist_route = (int64_t)(max_n + max_m + 2) * amax < (1ll << 28);
         }
-        if (((!affine && !nwdist) || dist_route) && ctx->knobs.scores_route != 0) {
+        // hw3 affine scores likewise: coded arena, every real value inside +-2^28 so that the -2^29 sentinels never win (pair_affine.hip.h).
+        // Raw-byte alphabets and scorings large enough for the reference's own wrap-around to matter stay on the strips.
+        bool aff_route = false;
+        if (affine && score_path == SC_PERM) {
+            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
+                                                    std::llabs((long long)gap) + std::llabs((long long)gap_extend), 1});
+            aff_route = (int64_t)(max_n + max_m + 2) * amax < (1ll << 28);
+        }
+        if (((!affine && !nwdist) || dist_route || aff_route) && ctx->knobs.scores_route != 0) {
             const size_t nt0 = ht.size();
-            const double vpc = nwdist ? 10.75 : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
+            // (affine strips: 5.6 VALU per cell, PMC of profiles/r03_hw3_rocprof_summary.md)
+            const double vpc = nwdist ? 10.75 : affine ? 5.6 : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
             constexpr double kLoneNs = 1.9, kSimdNs = 1.63;                                 // ns per wave instruction: one wave alone / a SIMD with two
-            const double kSimds = nwdist ? 4.0 * ctx->num_cu : 1024.0;
+            const double kSimds = nwdist || affine ? 4.0 * ctx->num_cu : 1024.0;
             // stripe engine: per step and SIMD; per stripe of pipeline lag; per step of a pair alone -- the keyed chunk without a band (coded
             // arena, keys in range) or the plain step ([gpu] r03_route_probe.txt: one 10k x 10k pair 1.26 / 1.01 ms, 64 pairs 3.45 / 2.05 ms);
-            // the distance fill (profiles/hw4_long_route_probe.txt)
-            const double step_ns = nwdist ? kDistStepNs : mini_scores ? (local ? 70.0 : 42.0) : (local ? 105.0 : 75.0), lag_us = nwdist ? kDistLagUs : 9.0,
-                         lone_step_ns = nwdist ? kDistLoneStepNs : mini_scores ? (local ? 55.0 : 30.0) : 100.0;
+            // the distance fill (profiles/hw4_long_route_probe.txt); the affine fill (profiles/hw3_long_route_probe.txt)
+            const double step_ns = nwdist ? kDistStepNs : affine ? kAffStepNs : mini_scores ? (local ? 70.0 : 42.0) : (local ? 105.0 : 75.0),
+                         lag_us = nwdist ? kDistLagUs : affine ? kAffLagUs : 9.0,
+                         lone_step_ns = nwdist ? kDistLoneStepNs : affine ? kAffLoneStepNs : mini_scores ? (local ? 55.0 : 30.0) : 100.0;
             std::vector<double> I(nt0), S(nt0), L(nt0);   // strip instructions / stripe-side work (ns x SIMD) / longest single-pair latency (us) of a task
             double I_total = 0, I_max = 0;
             uint64_t filled = 0;
@@ -1677,11 +1692,14 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             b->pl.keyed = true;
             b->pl.gap0 = gap0_scores;
             b->pl.dist = nwdist;
-            const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom);
+            b->pl.aff = affine;   // (go travels as the gap, ge beside it)
+            const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom,
+                                       affine ? gap_extend : 0);
             if (rc != PWA_OK) return rc;
             b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
-            names = nwdist ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
-                           : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
+            names = nwdist   ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
+                    : affine ? std::string("pair_affine_kernel<RL=") + std::to_string(geom.rl) + ",AFF,no-band>"
+                             : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
         }
         for (auto& cls : mini_lists) {
             const int rl = cls.first;

@@ -37,7 +37,8 @@
  * reads PWA_FASTA_MIN_CHUNK -- bytes per parser chunk -- on every call.)
  *   PWA_DEBUG, PWA_PROBE          host-side phase times / nop-kernel probes on stderr
  *   PWA_SCORES_ROUTE=0|1          scores passes: 0 every pair on the strip engine, 1 every pair on the stripe engine (default: by cost);
- *                                 distance passes in the two-value form likewise, for the pairs the stripe engine's distance fill takes
+ *                                 distance passes in the two-value form likewise, for the pairs the stripe engine's distance fill takes;
+ *                                 affine score passes likewise, for the lists the stripe engine's affine fill takes
  *   PWA_TB_ENGINE=0|2             traceback fills and scores off the strips: 0 the stripe engine's plain forms only, 2 mini-stripe kernels
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
@@ -152,6 +153,11 @@ void pwa_batch_destroy(pwa_batch *b);
  * pair (a, b): string1 = sequence a (rows), string2 = sequence b (columns).
  * The returned batch object works with pwa_batch_run / _d_scores / _set_d_scores / _fetch / _info /
  * _run_times / _destroy exactly like a linear-gap batch (no end cells).
+ * Engines: the strip kernels (lane = pair) take every list; a list over at most 7 symbols (coded arena)
+ * with (n + m + 2) * max(|M|, |Mm|, |Go| + |Ge|) < 2^28 is split by estimated cost between them and the
+ * stripe engine's affine fill (a pair over many waves: few long sequences), like a scores pass;
+ * PWA_SCORES_ROUTE=0 keeps every pair on the strips, =1 moves every pair of such a list.  A split batch
+ * reports "<strip kernel> + <stripe kernel>".  pwa_scores_affine inherits the routing.
  */
 int pwa_affine_batch_create(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
                             const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
