@@ -66,6 +66,10 @@ struct BatchParams {
     uint32_t tab_hi, tab_lo;     // SC_PERM: byte table, selector 0 -> match, 1..7 -> mismatch
     uint32_t pad_word;           // symbol that matches nothing in any text, x4
     uint32_t tpad_word;          // LANES: symbol that matches nothing in any pattern and differs from pad_word, x4
+    // CELL16 (packed f16 cells, two pairs per lane): scores as f16 bit patterns of s * 2^-11.  The per-column table's low /
+    // high bytes are {lo,hi}16_base ^ ({lo,hi}16_diff << 8c) for text code c (bytes 0..3 = pattern codes 0..3)
+    uint32_t lo16_base, lo16_diff, hi16_base, hi16_diff;
+    uint32_t gap16x2;            // f16x2 of gap * 2^-11, both halves
 };
 
 __device__ __forceinline__ int addw(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
@@ -153,6 +157,201 @@ constexpr int strip_waves_per_simd(int R, int MODE) {
     return (MODE == BM_SWS) ? (R > 48 ? 2 : 3) : (R > 104 ? 2 : (R > 80 ? 3 : 4));
 }
 
+// ---------------------------------------------------------------------------------------------------
+// CELL16: the saturating SW form (BM_SWS, SC_PERM) with TWO pairs per lane in packed f16 cells.  Every score is stored as
+// k * 2^-11 with k an integer: the host admits a batch only when |match|, |mismatch|, |gap| <= 127 and
+// longest pattern * max(match, 0) <= 2047, so every H, t = d + s and h + g is k * 2^-11 with |k| <= 2047 -- exact in f16
+// (normal or zero, no rounding) -- and the clamp of v_pk_add_f16 to [0, 1] is the floor at 0 (h + g never exceeds 1).
+// One row of BOTH pairs is then
+//   s  = v_perm_b32(table of the column, selector of the row)    both pairs' f16 scores in one dword
+//   t  = d + s                  v_pk_add_f16
+//   h  = max3(t, Hs_up, Hs_left) v_pk_maximum3_f16              = max(0, diag, up + g, left + g), hw2.cpp:211
+//   Hs = clamp(h + g)           v_pk_add_f16 ... clamp
+//   best = max3(best, h, h')    (half a v_pk_maximum3_f16 per row)
+// = 4.5 VALU per row and two pairs against 2 x 4.06 for the int32 cells.  The text symbol c of a column is wave-uniform, so the
+// 8-byte v_perm table is built per column on the scalar unit: bytes 0..3 hold the low bytes of f16(s(p, c)) for pattern codes
+// p = 0..3, bytes 4..7 the high bytes; a row's selector is (pA, pA + 4, pB, pB + 4), and 12 (-> 0x00 = +0.0) for pad rows.
+// A score of 0 below a pattern's end keeps every padded value <= a real one (g <= 0), as the int32 pad rows do.
+// Register state: H, Hs and the selector per row, 3R VGPRs; the hand-off keeps the [column/4][lane][4] layout, each dword the
+// two pairs' f16 values.
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ half2_t h2_bits(uint32_t v) { return __builtin_bit_cast(half2_t, v); }
+__device__ __forceinline__ uint32_t h2_u32(half2_t v) { return __builtin_bit_cast(uint32_t, v); }
+// max(h + g, 0) for both halves: v_pk_add_f16 with the output clamp to [0, 1] (the compiler emits a separate clamping max for the
+// builtin form, hence the asm; not volatile, so it schedules like any other instruction)
+__device__ __forceinline__ half2_t h2_add_clamp(half2_t h, uint32_t g) {
+    uint32_t r;
+    asm("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(r) : "v"(h2_u32(h)), "s"(g));
+    return h2_bits(r);
+}
+
+template <int R, int C>
+__device__ __forceinline__ void dp_block16(half2_t (&H)[R], half2_t (&Hs)[R], const uint32_t (&sel)[R], const uint32_t (&tlo)[C],
+                                           const uint32_t (&thi)[C], const half2_t (&top)[C], half2_t& topprev, half2_t (&bot)[C],
+                                           half2_t& best, uint32_t g) {
+    half2_t d[C], u[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        d[k] = (k == 0) ? topprev : top[k - 1];
+        u[k] = h2_add_clamp(top[k], g);
+    }
+    topprev = top[C - 1];
+    // skewed order as dp_block: column k runs one quad (4 rows) behind column k-1
+#pragma unroll
+    for (int step = 0; step < R / 4 + C - 1; ++step) {
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            const int q = step - k;
+            if (q >= 0 && q < R / 4) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int r = 4 * q + b;
+                    // one ordered asm block per row: with the four instructions free to move, hipcc computes the diagonal
+                    // candidates of whole columns ahead (they do not depend on the chain) and needs ~45 VGPRs more than
+                    // 3R + the skew's d / u, which at R = 76 spill inside the column loop
+                    uint32_t hv, hsv = h2_u32(Hs[r]), sv, tv;
+                    asm volatile("v_perm_b32 %[s], %[thi], %[tlo], %[sel]\n\t"
+                                 "v_pk_add_f16 %[t], %[d], %[s]\n\t"
+                                 "v_pk_maximum3_f16 %[h], %[t], %[u], %[hs]\n\t"
+                                 "v_pk_add_f16 %[hs], %[h], %[g] clamp"
+                                 : [h] "=&v"(hv), [hs] "+v"(hsv), [s] "=&v"(sv), [t] "=&v"(tv)
+                                 : [d] "v"(h2_u32(d[k])), [u] "v"(h2_u32(u[k])), [thi] "s"(thi[k]), [tlo] "v"(tlo[k]), [sel] "v"(sel[r]), [g] "s"(g));
+                    const half2_t h = h2_bits(hv), hs = h2_bits(hsv);
+                    d[k] = H[r];
+                    best = __builtin_elementwise_maximum(best, h);
+                    Hs[r] = hs;
+                    H[r] = h;
+                    u[k] = hs;
+                    if (r == R - 1) bot[k] = h;
+                }
+            }
+        }
+    }
+}
+
+// Task = 128 lane slots of one text: lane l runs slot0 + l (pair A, low halves) and slot0 + 64 + l (pair B, high halves).
+template <int R, bool MULTI>
+__device__ __forceinline__ void scores16_body(const BatchParams& P) {
+    static_assert(R % 4 == 0, "a strip is whole quads of rows");
+    const int lane = threadIdx.x & 63;
+    int32_t* const hand = P.hand + ((size_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * P.hand_stride;
+    const uint32_t g = P.gap16x2;
+
+    for (;;) {
+        uint32_t tid = 0;
+        {
+            int elect = lane;   // (opaque, see batch_scores_kernel)
+            asm volatile("" : "+v"(elect));
+            if (elect == 0) tid = atomicAdd(P.queue, 1u);
+        }
+        tid = __builtin_amdgcn_readfirstlane(tid);
+        if (tid >= P.n_tasks) break;
+
+        const BatchTask task = P.tasks[tid];
+        const int m = (int)task.text_len;
+        const uint32_t* tx = reinterpret_cast<const uint32_t*>(P.arena + task.text_off);
+        const uint32_t slot_a = task.slot0 + lane, slot_b = slot_a + 64;
+        const uint32_t poff_a = P.slot_poff[slot_a], poff_b = P.slot_poff[slot_b];
+        const int n_a = (int)P.slot_plen[slot_a], n_b = (int)P.slot_plen[slot_b];
+        const uint32_t out_a = P.slot_out[slot_a], out_b = P.slot_out[slot_b];
+        const int nblk = m >> 2, rem = m & 3;
+        // the per-column v_perm table of text code c (codes 4..7 match no pattern code: every byte the mismatch's)
+        auto table = [&](uint32_t c, uint32_t& lo, uint32_t& hi) {
+            lo = P.lo16_base ^ (uint32_t)((uint64_t)P.lo16_diff << (8 * c));
+            hi = P.hi16_base ^ (uint32_t)((uint64_t)P.hi16_diff << (8 * c));
+        };
+
+        half2_t best = h2_bits(0u);
+        for (int s = 0; s < (int)task.n_strips; ++s) {
+            const int row0 = s * R;
+            // ---- the strip's row selectors (pA, pA + 4, pB, pB + 4); 12 past a pattern's end (byte 0x00: score +0.0)
+            uint32_t sel[R];
+            {
+                const uint32_t* pa = reinterpret_cast<const uint32_t*>(P.arena + poff_a + row0);
+                const uint32_t* pb = reinterpret_cast<const uint32_t*>(P.arena + poff_b + row0);
+#pragma unroll
+                for (int q = 0; q < R / 4; ++q) {
+                    const uint32_t wa = pa[q], wb = pb[q];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const int i = row0 + 4 * q + b;
+                        const uint32_t ca = (wa >> (8 * b)) & 0xffu, cb = (wb >> (8 * b)) & 0xffu;
+                        const uint32_t sa = i < n_a ? ca * 0x0101u + 0x0400u : 0x0c0cu;
+                        const uint32_t sb = i < n_b ? cb * 0x0101u + 0x0400u : 0x0c0cu;
+                        sel[4 * q + b] = sa | (sb << 16);
+                    }
+                }
+            }
+            half2_t H[R], Hs[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) H[r] = Hs[r] = h2_bits(0u);
+            half2_t topprev = h2_bits(0u);
+
+            // hand-off rows through a buffer descriptor per 4-column block (SGPRs): the lane's byte offset is the one VGPR of every
+            // access -- no 64-bit VGPR addresses in the column loop.  The descriptor is rebuilt from a 64-bit wave-uniform block
+            // pointer that advances block by block, so no offset grows with the text (a half is m * 256 bytes: a 32-bit block offset
+            // would overflow from m = 2^23 on)
+            auto rsrc = [](const char* p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), (short)0, 0x7fffffff, 0x00020000); };
+            const char* hin_blk = reinterpret_cast<const char*>(hand + (size_t)((s + 1) & 1) * P.hand_half);   // block jb + 1 of strip s-1's row
+            char* hout_blk = reinterpret_cast<char*>(hand + (size_t)(s & 1) * P.hand_half);                   // block jb of this strip's row
+            const bool has_top = s > 0;
+            const bool has_bot = s + 1 < (int)task.n_strips;
+            const size_t in_stride = has_top ? 1024 : 0, out_stride = has_bot ? 1024 : 0;   // bytes per 4-column block; 0 parks on block 0
+            const int lane16 = lane * 16;
+            int4 tnext = make_int4(0, 0, 0, 0);
+            if (MULTI) tnext = __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(rsrc(hin_blk), lane16, 0, 0));
+            hin_blk += in_stride;
+            uint32_t cwn = tx[0];
+            // row 0 of the strip above the first is +0.0 (kept opaque like the int32 form's zero)
+            uint32_t zero = 0;
+            asm volatile("" : "+v"(zero));
+            for (int jb = 0; jb < nblk; ++jb) {
+                const uint32_t cw = __builtin_amdgcn_readfirstlane(cwn);   // (uniform: the tables below are scalar work)
+                const int4 tcur = tnext;
+                cwn = tx[jb + 1];   // arena slack makes the over-read safe
+                if (MULTI) tnext = __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(rsrc(hin_blk), lane16, 0, 0));
+                hin_blk += in_stride;
+                uint32_t tlo[4], thi[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) table((cw >> (8 * k)) & 0xffu, tlo[k], thi[k]);
+                half2_t top[4], bot[4];
+                {
+                    const uint32_t tl[4] = {(uint32_t)tcur.x, (uint32_t)tcur.y, (uint32_t)tcur.z, (uint32_t)tcur.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) top[k] = h2_bits(has_top ? tl[k] : (MULTI ? 0u : zero));
+                }
+                dp_block16<R, 4>(H, Hs, sel, tlo, thi, top, topprev, bot, best, g);
+                if (MULTI) {
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 v = {h2_u32(bot[0]), h2_u32(bot[1]), h2_u32(bot[2]), h2_u32(bot[3])};
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc(hout_blk), lane16, 0, 0);
+                }
+                hout_blk += out_stride;
+            }
+            if (rem > 0) {
+                uint32_t cw = __builtin_amdgcn_readfirstlane(cwn);
+                uint32_t t0 = (uint32_t)tnext.x, t1 = (uint32_t)tnext.y, t2 = (uint32_t)tnext.z;
+#pragma unroll 1
+                for (int k = 0; k < rem; ++k) {
+                    uint32_t tlo[1], thi[1];
+                    table(cw & 0xffu, tlo[0], thi[0]);
+                    cw >>= 8;
+                    const half2_t top1[1] = {h2_bits(has_top ? t0 : (MULTI ? 0u : zero))};
+                    t0 = t1;
+                    t1 = t2;
+                    half2_t bot1[1];
+                    dp_block16<R, 1>(H, Hs, sel, tlo, thi, top1, topprev, bot1, best, g);
+                    if (MULTI) __builtin_amdgcn_raw_buffer_store_b32(h2_u32(bot1[0]), rsrc(hout_blk), lane16 + 4 * k, 0, 0);   // (block nblk)
+                }
+            }
+        }
+        // best = k * 2^-11, exact: back to int32 once per task
+        if (out_a != 0xffffffffu) P.scores[out_a] = (int)((float)best.x * 2048.0f);
+        if (out_b != 0xffffffffu) P.scores[out_b] = (int)((float)best.y * 2048.0f);
+    }
+}
+
 // MULTI = false: every task of the launch is a single strip -- the hand-off row accesses are compiled out
 // (with them, each wave parks an unconditional 1 KiB load + store per 4 columns on an L2-resident dummy
 // block: harmless for speed, but it shows up as ~45 MB of HBM traffic per C3 launch).
@@ -167,8 +366,15 @@ constexpr int strip_waves_per_simd(int R, int MODE) {
 // Four-wave workgroups that each ask for a share of the CU's LDS are how the host gets a BALANCED placement -- the same number of
 // waves on every SIMD -- whatever kernel ran before ([gpu, r03] tools/probes/simd_place2.hip: single-wave workgroups launched after
 // another kernel double up on some SIMDs and leave others empty).
-template <int R, int MODE, int SCORE, bool MULTI, bool LANES = false>
+//
+// CELL16 = true (BM_SWS, SC_PERM only): two pairs per lane in packed f16 cells (scores16_body above), 128 lane slots per task.
+template <int R, int MODE, int SCORE, bool MULTI, bool LANES = false, bool CELL16 = false>
 __global__ __launch_bounds__(256, strip_waves_per_simd(R, MODE)) void batch_scores_kernel(const BatchParams P) {
+    static_assert(!CELL16 || (MODE == BM_SWS && SCORE == SC_PERM && !LANES), "packed f16 cells: the saturating SW form, shared texts");
+    if constexpr (CELL16) {
+        scores16_body<R, MULTI>(P);
+        return;
+    }
     // Global alignment, gap-shifted form, coded alphabets of <= 4 symbols: the texts of a task are RIGHT-aligned.  The
     // host stores every lane's text as a row of M = 4*ceil(max m / 4) codes, front-padded with code 4, which the
     // table scores like a gap (H-space g, here -g): with g <= 0 such a column reproduces column 0 exactly

@@ -97,6 +97,8 @@ struct Knobs {
     int pipe_runs = 0;                          // PWA_PIPE_RUNS=N: cut a list that fits one arena into N pipelined runs (experiment; measured slower)
     int scores_route = -1;                      // PWA_SCORES_ROUTE: 0 = every pair on the strip engine, 1 = every pair on the stripe
                                                 // engine, unset = by estimated cost (batch_create_impl)
+    int cell16 = -1;                            // PWA_CELL16: 0 = never the packed f16 cells (two pairs per lane), 1 = always where the batch
+                                                // admits them, unset = by estimated cost (batch_create_impl)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
     void read() {
@@ -128,6 +130,7 @@ struct Knobs {
         strip_wg1 = flag("PWA_STRIP_WG1");
         scores_route = num("PWA_SCORES_ROUTE", -1);
         tb_engine = num("PWA_TB_ENGINE", -1);
+        cell16 = num("PWA_CELL16", -1);
     }
 };
 
@@ -175,6 +178,18 @@ struct pwa_ctx {
 constexpr size_t kBandCacheMax = 64ull << 30;   // (288 GB of HBM per GPU: a 4096-pair batch with both bands is 33 GB)
 
 namespace {
+
+// Packed f16 strip cells (batch_scores.hip.h, CELL16): VALU per lane row and column, both pairs together -- perm, pk_add,
+// pk_maximum3, pk_add clamp, 1/2 pk_maximum3 for the running best, + the hand-off share ([gpu] PMC on C3: 4.56)
+constexpr double kCell16Vpr = 4.6;
+// f16 bit pattern of k * 2^-11 for |k| <= 1023: a normal number (exponent k's leading bit + 4), exact
+uint32_t f16_bits_scaled(int k) {
+    if (k == 0) return 0;
+    const uint32_t sign = k < 0 ? 0x8000u : 0u, a = (uint32_t)std::abs(k);
+    int e = 0;
+    while ((a >> (e + 1)) != 0) ++e;
+    return sign | ((uint32_t)(e + 4) << 10) | ((a - (1u << e)) << (10 - e));
+}
 
 constexpr size_t kFreeListMaxBytes = 24ull << 30, kFreeListMaxCount = 64;
 struct DevBuf {   // RAII device allocation; with `pool` set, released buffers go to the context's free list and come back from it
@@ -753,6 +768,7 @@ struct pwa_batch {
     const BatchKernelEntry* kern = nullptr;
     BatchParams bp{};
     bool affine = false, nwdist = false, single_strip = false, paired = false, lanes = false;
+    bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
     int32_t aff_go = 0, aff_ge = 0, aff_neg = 0;
     uint32_t grid = 0;
     DevBuf arena, tasks, slot_poff, slot_plen, slot_out, slot_toff, slot_tlen, lane_text, hand, queue, scores;
@@ -1033,23 +1049,10 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         for (int t = 0; t < 16; ++t)
             for (int v = 0; v < 256; ++v) present[v] |= part[t][v];
     }
-    int n_alpha = 0;
-    int code_of[256];
-    int absent_byte = -1;
-    for (int v = 0; v < 256; ++v) {
-        if (present[v]) code_of[v] = n_alpha++;
-        else {
-            code_of[v] = -1;
-            if (absent_byte < 0) absent_byte = v;
-        }
-    }
-
     // LANES kernels also pad TEXTS (columns past a lane's own text): that symbol must match no pattern symbol and
     // must differ from the pattern pad, or padded rows would "match" padded columns.
     bool pattern_has[256] = {false};
-    int text_pad_byte = -1;   // raw-byte (SC_CMP) form; the coded (SC_PERM) form uses code 6 when the alphabet leaves it free
     {
-        bool in_pattern[256] = {false};
         std::vector<uint8_t> is_pat(n_seq, 0);
         for (uint64_t k = 0; k < n_pairs; ++k) is_pat[pair_a[k]] = 1;
         bool part[16][256] = {};
@@ -1060,11 +1063,23 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
                     for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
         });
         for (int t = 0; t < 16; ++t)
-            for (int v = 0; v < 256; ++v) in_pattern[v] |= part[t][v];
-        for (int v = 255; v >= 0 && text_pad_byte < 0; --v)
-            if (!in_pattern[v] && v != absent_byte) text_pad_byte = v;
-        for (int v = 0; v < 256; ++v) pattern_has[v] = in_pattern[v];
+            for (int v = 0; v < 256; ++v) pattern_has[v] |= part[t][v];
     }
+    // codes: the text symbols that patterns use first, then the text-only ones (an N in the texts does not push a pattern symbol
+    // past code 3, which the packed f16 cells need); symbols compare by equality only, so any order gives the same scores
+    int n_alpha = 0;
+    int code_of[256];
+    int absent_byte = -1;
+    for (int v = 0; v < 256; ++v) {
+        code_of[v] = -1;
+        if (!present[v] && absent_byte < 0) absent_byte = v;
+    }
+    for (int pass = 0; pass < 2; ++pass)
+        for (int v = 0; v < 256; ++v)
+            if (present[v] && pattern_has[v] == (pass == 0)) code_of[v] = n_alpha++;
+    int text_pad_byte = -1;   // raw-byte (SC_CMP) form; the coded (SC_PERM) form uses code 6 when the alphabet leaves it free
+    for (int v = 255; v >= 0 && text_pad_byte < 0; --v)
+        if (!pattern_has[v] && v != absent_byte) text_pad_byte = v;
 
     // ---- engine choice.  The strip engine pads short patterns with rows that match nothing; for SW
     // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
@@ -1205,13 +1220,17 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             uint64_t maxlen;   // longest pattern of the task
             uint64_t m;        // text length (LANES: the longest text of the task)
         };
-        std::vector<HostTask> ht;
-        for (size_t p = 0; p < order.size();) {
-            size_t q = p;
-            while (q < order.size() && q - p < 64 && pair_b[order[q]] == pair_b[order[p]]) ++q;
-            ht.push_back({pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), slen(pair_a[order[p]]), slen(pair_b[order[p]])});
-            p = q;
-        }
+        auto group_by_text = [&](size_t lanes_per_task) {   // up to lanes_per_task patterns of one text per wave task
+            std::vector<HostTask> g;
+            for (size_t p = 0; p < order.size();) {
+                size_t q = p;
+                while (q < order.size() && q - p < lanes_per_task && pair_b[order[q]] == pair_b[order[p]]) ++q;
+                g.push_back({pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), slen(pair_a[order[p]]), slen(pair_b[order[p]])});
+                p = q;
+            }
+            return g;
+        };
+        std::vector<HostTask> ht = group_by_text(64);
         // ---- lists whose pairs share few texts (the reference's own loop pairs pattern i with reference i,
         // hw2.cpp:328-338) would leave most lanes of a text-grouped wave empty: give every lane its own text
         // instead (LANES kernels, local alignment only).  Pairs are sorted so that a wave's 64 pairs need about
@@ -1256,7 +1275,8 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         // ---- strip height: least padded work, ties to the taller strip
         int bestR = 0, best_mode = kmode;
         const int kmode_asked = kmode;
-        auto choose_strip_height = [&]() {
+        // c16: the packed f16 form (two pairs per lane, 128-slot tasks), priced per lane row at kCell16Vpr VALU for both pairs
+        auto choose_strip_height = [&](const std::vector<HostTask>& tl, bool c16) -> long double {
         bestR = 0;
         best_mode = kmode_asked;
         long double best_cost = -1;
@@ -1267,17 +1287,18 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             const bool mode_ok = e.mode == kmode_asked || (kmode_asked == BM_SW && e.mode == BM_SWS);
             if (!mode_ok || e.score != score_path) continue;
             if (b->lanes && !e.fn_lanes) continue;
+            if (c16 && !e.fn_cell16) continue;
             const int R = e.R;
             if (force && force != R) continue;
             if (force_mode >= 0 && force_mode != e.mode) continue;
-            long double w = e.mode == BM_SWS ? 4.06L : (e.mode == BM_SW ? 5.02L : 1.0L);   // VALU per cell
+            long double w = c16 ? (long double)kCell16Vpr : e.mode == BM_SWS ? 4.06L : (e.mode == BM_SW ? 5.02L : 1.0L);   // VALU per lane row
             // affine strips of more than 40 rows run 2 instead of 3 waves per SIMD: [gpu] all pairs of 1024 x 1000 take
             // 93.2 ms at R = 52 against 89.2 ms at R = 32 for the same padded cells
             if ((e.mode == BM_AFF || e.mode == BM_AFFS) && R > 40) w *= 1.045L;
             // evaluated cells + the strip hand-off priced at ~2 cells per column and strip boundary ([gpu]: the
             // 1000-row affine pass is equally fast at R = 32 and 52 but moves 37 % fewer HBM bytes at 52)
             long double cost = 0;
-            for (const auto& t : ht) {
+            for (const auto& t : tl) {
                 const uint64_t strips = (t.maxlen + R - 1) / R;
                 cost += (long double)(strips * R + 2 * (strips - 1)) * (long double)t.m * 64.0L;
             }
@@ -1288,9 +1309,34 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
                 best_mode = e.mode;
             }
         }
+        return best_cost;
         };
-        choose_strip_height();
+        const long double cost32 = choose_strip_height(ht, false);
         if (bestR == 0) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
+        // ---- packed f16 cells (batch_scores.hip.h, CELL16): local scores over a coded arena whose pattern symbols all have codes 0..3,
+        // pad rules of the int32 strips (mismatch, gap <= 0), scores in a byte, and every value k * 2^-11 with |k| <= 2047 exact in f16:
+        // H <= longest pattern * max(match, 0) bounds all of them.  Everything else keeps the int32 kernels, bit for bit.
+        {
+            bool pats_low = true;
+            for (int v = 0; v < 256; ++v) pats_low = pats_low && (!pattern_has[v] || (present[v] && code_of[v] <= 3));
+            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap)});
+            const bool cell16_ok = local && kmode_asked == BM_SW && !affine && !nwdist && score_path == SC_PERM && !b->lanes && pats_low &&
+                                   mismatch <= 0 && gap <= 0 && amax <= 127 && (int64_t)max_n * std::max(match, 0) <= 2047 &&
+                                   ctx->knobs.cell16 != 0 && ctx->knobs.paired < 0 && (ctx->knobs.force_mode < 0 || ctx->knobs.force_mode == BM_SWS);
+            if (cell16_ok) {
+                const int R32 = bestR, mode32 = best_mode;
+                std::vector<HostTask> ht16 = group_by_text(128);
+                const long double cost16 = choose_strip_height(ht16, true);
+                if (bestR != 0 && (ctx->knobs.cell16 == 1 || cost16 < cost32)) {
+                    b->cell16 = true;
+                    ht.swap(ht16);
+                } else {
+                    bestR = R32;
+                    best_mode = mode32;
+                }
+            }
+        }
+        const uint64_t kTaskLanes = b->cell16 ? 128 : 64;   // lane slots per wave task
 
         // ---- work-aware routing (r03).  The strip engine is the cheaper one per cell (lane = pair, 2.5 - 5 VALU per cell) but a wave
         // task is one wave running strips x columns on its own: a list of few long pairs -- ONE 10k x 10k pair is 105 strips x 2500
@@ -1320,7 +1366,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         if (((!affine && !nwdist) || dist_route || aff_route) && ctx->knobs.scores_route != 0) {
             const size_t nt0 = ht.size();
             // (affine strips: 5.6 VALU per cell, PMC of profiles/r03_hw3_rocprof_summary.md)
-            const double vpc = nwdist ? 10.75 : affine ? 5.6 : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
+            const double vpc = nwdist ? 10.75 : affine ? 5.6 : b->cell16 ? kCell16Vpr : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
             constexpr double kLoneNs = 1.9, kSimdNs = 1.63;                                 // ns per wave instruction: one wave alone / a SIMD with two
             const double kSimds = nwdist || affine ? 4.0 * ctx->num_cu : 1024.0;
             // stripe engine: per step and SIMD; per stripe of pipeline lag; per step of a pair alone -- the keyed chunk without a band (coded
@@ -1341,7 +1387,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             }
             // nothing to route when the strips' waves are many, full, and none of them dominates: per cell the strips are the cheapest engine
             // by 2x and more, so no task can gain by leaving (and the per-pair estimates below cost ~3 ms for a million pairs)
-            const bool strips_fit = nt0 >= 4096 && filled * 10 >= (uint64_t)nt0 * 64 * 9 && I_max * kLoneNs * 4 < I_total / kSimds * kSimdNs &&
+            const bool strips_fit = nt0 >= 4096 && filled * 10 >= (uint64_t)nt0 * kTaskLanes * 9 && I_max * kLoneNs * 4 < I_total / kSimds * kSimdNs &&
                                     ctx->knobs.scores_route < 0;
             for (size_t t = 0; t < nt0 && !strips_fit; ++t) {
                 double steps = 0, lat = 0;
@@ -1410,7 +1456,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
                 }
                 ht.swap(keep);
                 std::sort(pair_list.begin(), pair_list.end());
-                if (!ht.empty()) choose_strip_height();   // the strips that stay may prefer another height
+                if (!ht.empty()) choose_strip_height(ht, b->cell16);   // the strips that stay may prefer another height
             }
         }
         if (ht.empty()) b->use_strips = false;
@@ -1418,7 +1464,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
       if (b->use_strips) {
         kmode = best_mode;
         const int R = bestR;
-        for (const auto& t : ht) b->padded_cells += (t.maxlen + bestR - 1) / bestR * bestR * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * 64;
+        for (const auto& t : ht) b->padded_cells += (t.maxlen + bestR - 1) / bestR * bestR * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
         b->kern = find_batch_kernel(R, kmode, score_path);
         if (!b->kern) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
         b->kernel_name = b->kern->name;
@@ -1430,7 +1476,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         const size_t nt = ht.size();
         // task list and lane slots are built in page-locked buffers of the context and uploaded from there (see PinnedBuf)
         HIPC(ctx, ctx->pin[pwa_ctx::PIN_TASKS].reserve(nt * sizeof(BatchTask)));
-        for (int q = 0; q < (b->lanes ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * 64 * sizeof(uint32_t)));
+        for (int q = 0; q < (b->lanes ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * kTaskLanes * sizeof(uint32_t)));
         BatchTask* const tasks = ctx->pin[pwa_ctx::PIN_TASKS].as<BatchTask>();
         uint32_t* const spoff = ctx->pin[pwa_ctx::PIN_SLOT0].as<uint32_t>();
         uint32_t* const splen = ctx->pin[pwa_ctx::PIN_SLOT1].as<uint32_t>();
@@ -1438,12 +1484,12 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         uint32_t* const stoff = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT3].as<uint32_t>() : nullptr;   // empty lanes: no text, no pattern
         uint32_t* const stlen = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT4].as<uint32_t>() : nullptr;
         std::memset(tasks, 0, nt * sizeof(BatchTask));
-        std::memset(spoff, 0, nt * 64 * sizeof(uint32_t));
-        std::memset(splen, 0, nt * 64 * sizeof(uint32_t));
-        std::memset(sout, 0xff, nt * 64 * sizeof(uint32_t));
+        std::memset(spoff, 0, nt * kTaskLanes * sizeof(uint32_t));
+        std::memset(splen, 0, nt * kTaskLanes * sizeof(uint32_t));
+        std::memset(sout, 0xff, nt * kTaskLanes * sizeof(uint32_t));
         if (b->lanes) {
-            std::memset(stoff, 0, nt * 64 * sizeof(uint32_t));
-            std::memset(stlen, 0, nt * 64 * sizeof(uint32_t));
+            std::memset(stoff, 0, nt * kTaskLanes * sizeof(uint32_t));
+            std::memset(stlen, 0, nt * kTaskLanes * sizeof(uint32_t));
         }
         uint32_t max_strips = 1;
         size_t two_strip_tasks = 0;
@@ -1456,18 +1502,18 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
                 for (size_t t = a; t < z; ++t) {
                     tasks[t].text_off = (uint32_t)aoff[ht[t].text];
                     tasks[t].text_len = (uint32_t)ht[t].m;
-                    tasks[t].slot0 = (uint32_t)(t * 64);
+                    tasks[t].slot0 = (uint32_t)(t * kTaskLanes);
                     tasks[t].n_strips = (uint32_t)((ht[t].maxlen + R - 1) / R);
                     part_max[(size_t)th] = std::max(part_max[(size_t)th], tasks[t].n_strips);
                     part_two[(size_t)th] += tasks[t].n_strips == 2;
                     for (uint32_t l = 0; l < ht[t].count; ++l) {
                         const uint32_t k = order[ht[t].first + l];
-                        spoff[t * 64 + l] = (uint32_t)aoff[pair_a[k]];
-                        splen[t * 64 + l] = (uint32_t)slen(pair_a[k]);
-                        sout[t * 64 + l] = k;
+                        spoff[t * kTaskLanes + l] = (uint32_t)aoff[pair_a[k]];
+                        splen[t * kTaskLanes + l] = (uint32_t)slen(pair_a[k]);
+                        sout[t * kTaskLanes + l] = k;
                         if (b->lanes) {
-                            stoff[t * 64 + l] = (uint32_t)aoff[pair_b[k]];
-                            stlen[t * 64 + l] = (uint32_t)slen(pair_b[k]);
+                            stoff[t * kTaskLanes + l] = (uint32_t)aoff[pair_b[k]];
+                            stlen[t * kTaskLanes + l] = (uint32_t)slen(pair_b[k]);
                         }
                     }
                 }
@@ -1544,12 +1590,12 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         mark("choose R + slot arrays");
         HIPC(ctx, b->tasks.alloc(nt * sizeof(BatchTask)));
         HIPC(ctx, hipMemcpy(b->tasks.p, tasks, nt * sizeof(BatchTask), hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_poff.alloc(nt * 64 * 4));
-        HIPC(ctx, hipMemcpy(b->slot_poff.p, spoff, nt * 64 * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_plen.alloc(nt * 64 * 4));
-        HIPC(ctx, hipMemcpy(b->slot_plen.p, splen, nt * 64 * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_out.alloc(nt * 64 * 4));
-        HIPC(ctx, hipMemcpy(b->slot_out.p, sout, nt * 64 * 4, hipMemcpyHostToDevice));
+        HIPC(ctx, b->slot_poff.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, hipMemcpy(b->slot_poff.p, spoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+        HIPC(ctx, b->slot_plen.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, hipMemcpy(b->slot_plen.p, splen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+        HIPC(ctx, b->slot_out.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, hipMemcpy(b->slot_out.p, sout, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
 
         b->single_strip = !affine && !nwdist && max_strips == 1 && b->kern->fn_single != nullptr;
         // Opt-in (PWA_PAIRED=1): two-strip tasks (the C3 shape: 150-row patterns in 76-row strips) as two waves of one
@@ -1564,7 +1610,8 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             b->paired = false;
             b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
         }
-        const void* kfn = b->lanes        ? reinterpret_cast<const void*>(max_strips == 1 ? b->kern->fn_lanes_single : b->kern->fn_lanes)
+        const void* kfn = b->cell16       ? reinterpret_cast<const void*>(max_strips == 1 ? b->kern->fn_cell16_single : b->kern->fn_cell16)
+                          : b->lanes      ? reinterpret_cast<const void*>(max_strips == 1 ? b->kern->fn_lanes_single : b->kern->fn_lanes)
                           : b->single_strip ? reinterpret_cast<const void*>(b->kern->fn_single)
                           : b->paired     ? reinterpret_cast<const void*>(b->kern->fn_pair)
                           : nwdist        ? reinterpret_cast<const void*>(b->kern->dfn)
@@ -1627,6 +1674,14 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         P.tpad_word = ((score_path == SC_PERM) ? 6u : (uint32_t)std::max(text_pad_byte, 0)) * 0x01010101u;
         P.lane_text = b->lane_text.as<uint8_t>();
         if (b->lanes && kmode == BM_NWG) P.tab_hi = (uint32_t)(uint8_t)(int8_t)(-gap) * 0x01010101u;   // selectors 4..7: front pad = a gap column
+        if (b->cell16) {   // f16 bit patterns of s * 2^-11 (exact: |s| <= 127)
+            const uint32_t m16 = f16_bits_scaled(match), x16 = f16_bits_scaled(mismatch), g16 = f16_bits_scaled(gap);
+            P.lo16_base = (x16 & 0xffu) * 0x01010101u;
+            P.lo16_diff = (m16 ^ x16) & 0xffu;
+            P.hi16_base = (x16 >> 8) * 0x01010101u;
+            P.hi16_diff = ((m16 ^ x16) >> 8) & 0xffu;
+            P.gap16x2 = g16 | (g16 << 16);
+        }
         P.slot_toff = b->slot_toff.as<uint32_t>();
         P.slot_tlen = b->slot_tlen.as<uint32_t>();
       }   // strips that stay
@@ -2017,7 +2072,9 @@ int pwa_batch_run(pwa_batch* b, void* stream_v) {
                 } else {
                     // b->grid waves as workgroups of four, with an LDS request that admits exactly their share per CU: a balanced
                     // placement whatever ran before (batch_scores.hip.h); PWA_STRIP_WG1: single-wave workgroups (A/B)
-                    const batch_kernel_t fn = b->lanes ? (b->single_strip ? b->kern->fn_lanes_single : b->kern->fn_lanes) : (b->single_strip ? b->kern->fn_single : b->kern->fn);
+                    const batch_kernel_t fn = b->cell16  ? (b->single_strip ? b->kern->fn_cell16_single : b->kern->fn_cell16)
+                                              : b->lanes ? (b->single_strip ? b->kern->fn_lanes_single : b->kern->fn_lanes)
+                                                         : (b->single_strip ? b->kern->fn_single : b->kern->fn);
                     if (ctx->knobs.strip_wg1) {
                         hipLaunchKernelGGL(fn, dim3(b->grid), dim3(64), 0, st, b->bp);
                     } else {
@@ -2110,6 +2167,11 @@ int pwa_batch_info(const pwa_batch* b, uint64_t* cells, uint64_t* padded_cells, 
     }
     if (kernel_name) *kernel_name = b->kernel_name.c_str();
     return PWA_OK;
+}
+
+int pwa_batch_cell_bits(const pwa_batch* b) {
+    if (!b) return PWA_E_INVALID;
+    return b->use_strips ? (b->cell16 ? 16 : 32) : 0;
 }
 
 int pwa_batch_fetch(pwa_batch* b, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out) try {

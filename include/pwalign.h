@@ -39,6 +39,8 @@
  *   PWA_SCORES_ROUTE=0|1          scores passes: 0 every pair on the strip engine, 1 every pair on the stripe engine (default: by cost);
  *                                 distance passes in the two-value form likewise, for the pairs the stripe engine's distance fill takes;
  *                                 affine score passes likewise, for the lists the stripe engine's affine fill takes
+ *   PWA_CELL16=0|1                local strip scores: 0 never / 1 always (where the batch admits it) the packed f16 cells, two pairs per
+ *                                 lane (default: by estimated cost; pwa_batch_cell_bits says which form a batch runs)
  *   PWA_TB_ENGINE=0|2             traceback fills and scores off the strips: 0 the stripe engine's plain forms only, 2 mini-stripe kernels
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
@@ -135,6 +137,11 @@ int pwa_batch_fetch(pwa_batch *b, int32_t *score_out, uint32_t *end_i_out, uint3
  * actually evaluate (register-tile padding); kernel_name = the dominant kernel instantiation. */
 int pwa_batch_info(const pwa_batch *b, uint64_t *cells, uint64_t *padded_cells, uint64_t *n_tasks,
                    const char **kernel_name);
+/* Cell form of the batch's register-strip launch: 16 = two pairs per lane in packed f16 cells, 32 = int32 cells (one pair per
+ * lane), 0 = no pair runs on the strips.  The packed form is taken for local scores over patterns whose symbols are four of the
+ * texts' (codes 0..3), with mismatch <= 0, gap <= 0, |scores| <= 127 and longest pattern * max(match, 0) <= 2047, when the cost
+ * model prefers it; PWA_CELL16=0|1 forces either form where it applies. */
+int pwa_batch_cell_bits(const pwa_batch *b);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);

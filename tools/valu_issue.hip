@@ -113,6 +113,14 @@ OP(k_andor, "v_and_or_b32 %0, %1, %2, %3")
 OPX(k_idx4, "s_set_gpr_idx_on 0, 1\n\tv_add_u32 %0, %2, %3\n\tv_add_u32 %0, %2, %4\n\tv_add_u32 %0, %3, %4\n\tv_add_u32 %0, %4, %3\n\ts_set_gpr_idx_off")
 OPX(k_cell4, "s_bfe_u32 %1, %1, 0x80008\n\ts_set_gpr_idx_on 0, 1\n\tv_add_u32 %0, %2, %3\n\tv_add_u32 %0, %2, %4\n\tv_add_u32 %0, %3, %4\n\tv_add_u32 %0, %4, %3\n\ts_set_gpr_idx_off\n\tv_max3_i32 %0, %2, %3, %4\n\tv_sub_u32_e64 %0, %2, %3 clamp\n\tv_max3_i32 %0, %2, %3, %4\n\tv_sub_u32_e64 %0, %2, %4 clamp\n\tv_max3_i32 %0, %4, %3, %2\n\tv_sub_u32_e64 %0, %3, %2 clamp\n\tv_max3_i32 %0, %2, %4, %3\n\tv_sub_u32_e64 %0, %4, %2 clamp\n\tv_max3_i32 %0, %3, %4, %2\n\tv_max3_i32 %0, %3, %2, %4")
 OPX(k_cell4old, "v_add_u32_sdwa %0, %2, sext(%3) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\tv_add_u32_sdwa %0, %2, sext(%4) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\tv_add_u32_sdwa %0, %3, sext(%4) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\tv_add_u32_sdwa %0, %4, sext(%3) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\tv_xor_b32 %0, %2, %3\n\tv_perm_b32 %0, %2, %3, %4\n\tv_max3_i32 %0, %2, %3, %4\n\tv_sub_u32_e64 %0, %2, %3 clamp\n\tv_max3_i32 %0, %2, %3, %4\n\tv_sub_u32_e64 %0, %2, %4 clamp\n\tv_max3_i32 %0, %4, %3, %2\n\tv_sub_u32_e64 %0, %3, %2 clamp\n\tv_max3_i32 %0, %2, %4, %3\n\tv_sub_u32_e64 %0, %4, %2 clamp\n\tv_max3_i32 %0, %3, %4, %2\n\tv_max3_i32 %0, %3, %2, %4")
+// packed f16 / u16 forms of the SW cell (two pairs per lane; r04)
+OP(k_pkmaximum3f16, "v_pk_maximum3_f16 %0, %1, %2, %3")
+OP(k_pkaddf16, "v_pk_add_f16 %0, %1, %2")
+OP(k_pkaddf16c, "v_pk_add_f16 %0, %1, %2 clamp")
+OP(k_pkmaxf16, "v_pk_max_f16 %0, %1, %2")
+OP(k_pkaddu16, "v_pk_add_u16 %0, %1, %2")
+OP(k_permsgpr, "v_perm_b32 %0, s2, %2, %3")   // the kernarg pointer's low word as an arbitrary SGPR table half
+OPX(k_cell16, "v_perm_b32 %0, s2, %2, %3\n\tv_pk_add_f16 %0, %3, %4\n\tv_pk_maximum3_f16 %0, %2, %3, %4\n\tv_pk_add_f16 %0, %2, %4 clamp\n\tv_perm_b32 %0, s2, %3, %4\n\tv_pk_add_f16 %0, %2, %4\n\tv_pk_maximum3_f16 %0, %3, %2, %4\n\tv_pk_add_f16 %0, %3, %4 clamp\n\tv_pk_maximum3_f16 %0, %4, %3, %2")
 OP(k_nop, "s_nop 0")
 
 // dependent chains (every instruction reads the result of the one before it) and chains diluted with independent fillers:
@@ -156,6 +164,9 @@ int main(int argc, char** argv) {
         {"v_and_or_b32", k_andor, 1}, {"idx_on+4 v_add+idx_off /add", k_idx4, 1},
         {"v_dot4_i32_i8", k_dot4i8, 1}, {"v_dot4_u32_u8", k_dot4u8, 1}, {"v_dot8_i32_i4", k_dot8i4, 1}, {"v_dot2_i32_i16", k_dot2i16, 1},
         {"v_sad_u8", k_sad8, 1}, {"v_bfe_i32", k_bfei, 1},
+        {"v_pk_maximum3_f16", k_pkmaximum3f16, 1}, {"v_pk_add_f16", k_pkaddf16, 1}, {"v_pk_add_f16 clamp", k_pkaddf16c, 1},
+        {"v_pk_max_f16", k_pkmaxf16, 1}, {"v_pk_add_u16", k_pkaddu16, 1}, {"v_perm_b32 (sgpr table)", k_permsgpr, 1},
+        {"SW cell16, 2 rows x 2 pairs /cell", k_cell16, 1},
         {"SW cell, profile form /cell", k_cell4, 1}, {"SW cell, table form   /cell", k_cell4old, 1}, {"s_nop 0", k_nop, 1}};
     struct { const char* n; kfn f; int chain, total; } dt_[] = {
         {"v_add_u32 chain", d_add, 4, 4}, {"v_and/v_or chain", d_and, 4, 4}, {"v_max3_i32 chain", d_max3, 4, 4}, {"v_add_u32_sdwa chain", d_sdwa, 4, 4},
