@@ -21,7 +21,6 @@ struct BatchKernelEntry {
     affine_kernel_t afn = nullptr;
     nwdist_kernel_t dfn = nullptr;
     batch_kernel_t fn_single = nullptr;   // every task a single strip: no hand-off accesses at all
-    batch_kernel_t fn_pair = nullptr;     // every task at most two strips: two waves per task, hand-off through an LDS ring
     batch_kernel_t fn_lanes = nullptr;         // every lane its own text (index-paired lists), multi-strip
     batch_kernel_t fn_lanes_single = nullptr;  // ... every task a single strip
     batch_kernel_t fn_cell16 = nullptr;        // two pairs per lane in packed f16 cells (BM_SWS, SC_PERM), multi-strip

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <new>
 #include <numeric>
@@ -81,7 +82,6 @@ struct Knobs {
     std::string stamps;                         // PWA_STAMPS=<file>: per-stripe time stamps of the fill
     int trace_stripe = -1;                      // PWA_TRACE_STRIPE
     bool no_packed_dist = false;                // PWA_NO_PACKED_DIST: hw4 pass in its two-value form
-    int paired = -1;                            // PWA_PAIRED: two-strip tasks as two waves with an LDS hand-off (opt-in)
     int force_lanes = -1;                       // PWA_FORCE_LANES=0: never the per-lane-text kernels
     int force_r = 0, force_mode = -1;           // PWA_FORCE_R, PWA_FORCE_MODE: strip height / kernel form of the strip engine
     uint64_t arena_limit = 0;                   // PWA_ARENA_LIMIT: bytes of sequence arena per run of the one-shot calls (tests)
@@ -92,7 +92,6 @@ struct Knobs {
     bool no_keyed_tb = false;                   // PWA_NO_KEYED_TB: traceback fills in the plain int32 form
     bool no_gap_shift = false;                  // PWA_NO_GAP_SHIFT: global traceback fills in H, not G = H - gap (i + j)
     bool no_tiled_ops = false;                  // PWA_NO_TILED_OPS: op lists through the staging copy
-    bool strip_wg1 = false;                     // PWA_STRIP_WG1: strip kernels as single-wave workgroups (r02 form; A/B of the placement effect)
     bool no_pipeline = false;                   // PWA_NO_PIPELINE: the runs of a one-shot score call are processed strictly one after the other
     int pipe_runs = 0;                          // PWA_PIPE_RUNS=N: cut a list that fits one arena into N pipelined runs (experiment; measured slower)
     int scores_route = -1;                      // PWA_SCORES_ROUTE: 0 = every pair on the strip engine, 1 = every pair on the stripe
@@ -113,7 +112,6 @@ struct Knobs {
         if (const char* e = std::getenv("PWA_STAMPS")) stamps = e;
         trace_stripe = num("PWA_TRACE_STRIPE", -1);
         no_packed_dist = flag("PWA_NO_PACKED_DIST");
-        paired = num("PWA_PAIRED", -1);
         force_lanes = num("PWA_FORCE_LANES", -1);
         force_r = num("PWA_FORCE_R", 0);
         force_mode = num("PWA_FORCE_MODE", -1);
@@ -127,7 +125,6 @@ struct Knobs {
         no_tiled_ops = flag("PWA_NO_TILED_OPS");
         no_pipeline = flag("PWA_NO_PIPELINE");
         pipe_runs = num("PWA_PIPE_RUNS", 0);
-        strip_wg1 = flag("PWA_STRIP_WG1");
         scores_route = num("PWA_SCORES_ROUTE", -1);
         tb_engine = num("PWA_TB_ENGINE", -1);
         cell16 = num("PWA_CELL16", -1);
@@ -360,13 +357,65 @@ void for_seq_ranges(const uint64_t* seq_off, uint32_t n_seq, F&& fn, int* n_thre
     for (auto& x : th) x.join();
 }
 
+// out[v]: does byte v occur in a sequence s with in[s] != 0?  One pass over those sequences, on a thread per bytes_per_thread of input
+void scan_bytes(const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& in, bool out[256],
+                uint64_t bytes_per_thread) {
+    bool part[16][256] = {};
+    for_seq_ranges(seq_off, n_seq, [&](uint32_t s0, uint32_t s1, int t) {
+        bool* mine = part[t];
+        for (uint32_t s = s0; s < s1; ++s)
+            if (in[s])
+                for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
+    }, nullptr, bytes_per_thread);
+    for (int v = 0; v < 256; ++v) {
+        out[v] = false;
+        for (int t = 0; t < 16; ++t) out[v] |= part[t][v];
+    }
+}
+
+// the largest magnitude among scoring values (a trailing 1 where the result divides)
+int64_t max_abs(std::initializer_list<int64_t> vals) {
+    int64_t r = 0;
+    for (const int64_t v : vals) r = std::max<int64_t>(r, std::llabs((long long)v));
+    return r;
+}
+
 // The traceback kernels keep H * 4 + priority in int32 (pair_fill.hip.h): |H| has to stay below 2^28.
 // (bits = 26: local fills of the mini-stripe kernels, whose first-maximum records hold H * 16 + a step index, mini_fill.hip.h)
 bool tb_range_ok(uint64_t n_plus_m, int match, int mismatch, int gap, int bits = 28) {
-    const uint64_t amax = (uint64_t)std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
-                                                       std::llabs((long long)gap), 1});
-    return (n_plus_m + 2) <= (1ull << bits) / amax;
+    return (n_plus_m + 2) <= (1ull << bits) / (uint64_t)max_abs({match, mismatch, gap, 1});
 }
+
+// The keyed fills score four rows with one byte-table lookup (pair_fill.hip.h, PERM): the table holds the two diagonal key
+// constants, and both must fit a signed byte.
+bool key_byte(int64_t k) { return k <= 127 && k >= -126; }
+bool diag_keys_fit(int match, int mismatch, int gap) {
+    return key_byte(((int64_t)match - gap) * 4 + 2) && key_byte(((int64_t)mismatch - gap) * 4 + 2);
+}
+// Global fills in gap-shifted coordinates G = H - gap (i + j) (GAP0): |G| <= |H| + |gap| (n + m), twice the range, and both shifted
+// diagonal constants (s - 2 gap) * 4 + prio(diag) - prio(left) in the byte table
+bool gap0_ok(uint64_t n_plus_m, int match, int mismatch, int gap) {
+    return key_byte(((int64_t)match - 2 * (int64_t)gap) * 4 + 1) && key_byte(((int64_t)mismatch - 2 * (int64_t)gap) * 4 + 1) &&
+           tb_range_ok(n_plus_m, match, mismatch, gap, 27);
+}
+// Alphabets of at most 7 symbols (DNA, DNA + N, ...) are stored as codes 0..6 -- equality is all the recurrence ever asks of a symbol
+// (hw2.cpp:142, 208) -- so that the fill can score four rows with one byte-table lookup.  Fills code_of; true when the fills may use it.
+bool code_alphabet(const bool seen[256], uint8_t code_of[256], int match, int mismatch, int gap, const Knobs& knobs) {
+    int n_alpha = 0;
+    for (int v = 0; v < 256; ++v) {
+        code_of[v] = (uint8_t)std::min(n_alpha, 7);
+        if (seen[v]) ++n_alpha;
+    }
+    return n_alpha <= 7 && diag_keys_fit(match, mismatch, gap) && !knobs.no_pair_table;
+}
+// rows per lane of the four-pair mini-stripe class that holds an n-row pattern, 0: none (n > 256)
+int mini_rl_for(uint64_t n) {
+    for (const int rl : kMiniRL)
+        if (n <= (uint64_t)(16 * rl)) return rl;
+    return 0;
+}
+// ... and of the one-pair-per-wave class (64 lanes) for 257 .. 1024 rows
+int wide_rl_for(uint64_t n) { return n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16; }
 
 // A workspace of `bytes` from the context's cache slot (see pwa_ctx): reused when big enough, regrown otherwise;
 // requests beyond kBandCacheMax are served by `fallback` and freed with it.
@@ -767,7 +816,8 @@ struct pwa_batch {
     bool use_pairs = false;         // some (or, with end cells / scorings the strips cannot pad for, all) pairs run on the stripe engine
     const BatchKernelEntry* kern = nullptr;
     BatchParams bp{};
-    bool affine = false, nwdist = false, single_strip = false, paired = false, lanes = false;
+    bool affine = false, nwdist = false, lanes = false;
+    void* strip_fn = nullptr;         // the strip kernel this batch launches (strip_kernel_fn)
     bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
     int32_t aff_go = 0, aff_ge = 0, aff_neg = 0;
     uint32_t grid = 0;
@@ -927,13 +977,839 @@ int pwa_ctx_set_score_band(pwa_ctx* c, int on) {
 // ---------------------------------------------------------------------------- batch: create
 } // extern "C" (reopened below): the shared implementation has C++ linkage
 enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2 };
-// Route estimates of the stripe engine's distance fill (pair_dist.hip.h), in the units of the estimate (stripes of choose_geom's
-// geometry): ns per stripe step and SIMD with the chip full, us of pipeline lag per stripe, ns per step of a pair alone.  [gpu]
-// profiles/hw4_long_route_probe.txt: 496 pairs 10k x 10k 29.9 ms; one pair 10k x 10k 2.66 ms, 20k x 20k 5.29 ms.
-constexpr double kDistStepNs = 80.0, kDistLagUs = 13.0, kDistLoneStepNs = 162.0;
-// ... and of the affine score fill (pair_affine.hip.h), [gpu] profiles/hw3_long_route_probe.txt: 496 pairs 10k x 10k 23.4 ms; one pair
-// 10k x 10k 1.62 ms, 20k x 20k 3.21 ms.
-constexpr double kAffStepNs = 62.0, kAffLagUs = 8.0, kAffLoneStepNs = 99.0;
+
+namespace {
+
+// The caller's sequences, pair list and scoring, as the stages of batch_create_impl see them
+struct BatchInput {
+    const uint8_t* seq_bytes;
+    const uint64_t* seq_off;
+    uint32_t n_seq;
+    const uint32_t* pair_a;
+    const uint32_t* pair_b;
+    uint64_t n_pairs;
+    int kind, match, mismatch, gap, gap_extend;
+    bool local, want_end;
+    bool affine() const { return kind == KIND_AFFINE; }
+    bool nwdist() const { return kind == KIND_NWDIST; }
+    uint64_t len(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
+};
+
+// PWA_DEBUG: host-side time between the phases of a batch's creation
+struct CreateClock {
+    pwa_ctx* ctx;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    void mark(const char* what) {
+        if (!ctx->knobs.debug) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[pwa] create: %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+        if (ctx->knobs.probe) {   // how long does a kernel submission take at this point?
+            hipLaunchKernelGGL(pwa_nop_kernel, dim3(1), dim3(64), 0, ctx->stream, (int*)nullptr);
+            (void)hipStreamSynchronize(ctx->stream);
+            const auto t2 = std::chrono::steady_clock::now();
+            std::fprintf(stderr, "[pwa]     probe after it: nop kernel + sync %8.3f ms\n", std::chrono::duration<double, std::milli>(t2 - now).count());
+            t_last = t2;
+        }
+    }
+};
+
+struct LivePairs {
+    std::vector<uint32_t> live;   // the pairs that reach a kernel (n > 0 and m > 0), ascending
+    uint64_t max_n = 0, max_m = 0;
+    bool any_trivial_score = false;
+};
+
+// One pass over the pair list: index check, and pairs with an empty side never reach a kernel (hw2.cpp: loops 138/205 do not
+// run) -- they are resolved here, into b's host scores and end cells
+int scan_pairs(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, LivePairs& lp) {
+    b->host_scores.assign(in.n_pairs, 0);
+    if (b->want_end) {
+        b->host_end_i.assign(in.n_pairs, 0);
+        b->host_end_j.assign(in.n_pairs, 0);
+    }
+    lp.live.resize(in.n_pairs);
+    uint64_t n_live = 0;
+    for (uint64_t k = 0; k < in.n_pairs; ++k) {
+        if (in.pair_a[k] >= in.n_seq || in.pair_b[k] >= in.n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
+        const uint64_t n = in.len(in.pair_a[k]), m = in.len(in.pair_b[k]);
+        if (n == 0 || m == 0) {
+            if (in.nwdist()) {   // hw4.cpp:21-28 + 146-152: an all-gap alignment, every column counts
+                b->host_scores[k] = (int32_t)(n + m);
+            } else if (in.affine()) {   // hw3.cpp:39-52: V[0][0] = 0, F[n][0] = Go + Ge(n-1), E[0][m] = Go + Ge(m-1)
+                b->host_scores[k] = (n + m == 0) ? 0 : (int32_t)((uint32_t)in.gap + (uint32_t)wrap_mul((int64_t)(n + m - 1), in.gap_extend));
+            } else if (!in.local) b->host_scores[k] = wrap_mul((int64_t)(n + m), in.gap);   // dp[n][0] / dp[0][m], hw2.cpp:125-136
+            lp.any_trivial_score = lp.any_trivial_score || b->host_scores[k] != 0;
+            if (b->want_end && !in.local) {
+                b->host_end_i[k] = (uint32_t)n;
+                b->host_end_j[k] = (uint32_t)m;
+            }
+            continue;
+        }
+        if (n > 0x7fffffc0ull || m > 0x7fffffc0ull) return fail(ctx, PWA_E_CAPACITY, "sequence longer than 2^31");
+        lp.live[n_live++] = (uint32_t)k;
+        b->cells += n * m;
+        lp.max_n = std::max(lp.max_n, n);
+        lp.max_m = std::max(lp.max_m, m);
+    }
+    lp.live.resize(n_live);
+    return PWA_OK;
+}
+
+struct Alphabet {
+    bool present[256];       // text symbols
+    bool pattern_has[256];   // pattern symbols
+    int code_of[256];        // -1: not a text symbol
+    int n_alpha = 0;
+    int absent_byte = -1;    // the smallest byte no text holds
+    int text_pad_byte = -1;  // raw-byte (SC_CMP) form; the coded (SC_PERM) form uses code 6 when the alphabet leaves it free
+};
+
+Alphabet scan_alphabet(const BatchInput& in, const std::vector<uint8_t>& is_text) {
+    Alphabet al;
+    scan_bytes(in.seq_bytes, in.seq_off, in.n_seq, is_text, al.present, 8ull << 20);
+    // LANES kernels also pad TEXTS (columns past a lane's own text): that symbol must match no pattern symbol and
+    // must differ from the pattern pad, or padded rows would "match" padded columns.
+    {
+        std::vector<uint8_t> is_pat(in.n_seq, 0);
+        for (uint64_t k = 0; k < in.n_pairs; ++k) is_pat[in.pair_a[k]] = 1;
+        scan_bytes(in.seq_bytes, in.seq_off, in.n_seq, is_pat, al.pattern_has, 8ull << 20);
+    }
+    // codes: the text symbols that patterns use first, then the text-only ones (an N in the texts does not push a pattern symbol
+    // past code 3, which the packed f16 cells need); symbols compare by equality only, so any order gives the same scores
+    for (int v = 0; v < 256; ++v) {
+        al.code_of[v] = -1;
+        if (!al.present[v] && al.absent_byte < 0) al.absent_byte = v;
+    }
+    for (int pass = 0; pass < 2; ++pass)
+        for (int v = 0; v < 256; ++v)
+            if (al.present[v] && al.pattern_has[v] == (pass == 0)) al.code_of[v] = al.n_alpha++;
+    for (int v = 255; v >= 0 && al.text_pad_byte < 0; --v)
+        if (!al.pattern_has[v] && v != al.absent_byte) al.text_pad_byte = v;
+    return al;
+}
+
+bool fits8(int v) { return v >= -128 && v <= 127; }
+
+// How a batch's cells are stored and scored
+struct CellForm {
+    bool strips = false;              // the strip kernels can serve the list
+    int kmode = BM_NW, score_path = SC_CMP;
+    int tab_match = 0, tab_mismatch = 0;
+    int32_t aff_go = 0, aff_ge = 0, aff_neg = 0;
+    bool coded = false;               // the arena holds codes, not bytes
+    bool mini_scores = false, mini_gap0 = false;
+};
+
+int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, const Alphabet& al, CellForm& f) {
+    const int match = in.match, mismatch = in.mismatch, gap = in.gap, gap_extend = in.gap_extend;
+    const bool local = in.local, affine = in.affine(), nwdist = in.nwdist();
+    const uint64_t max_n = lp.max_n, max_m = lp.max_m;
+    // ---- engine choice.  The strip engine pads short patterns with rows that match nothing; for SW
+    // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
+    f.strips = affine || nwdist || (!in.want_end && (!local || (mismatch <= 0 && gap <= 0)));
+    f.kmode = local ? BM_SW : BM_NW;
+    f.tab_match = match;
+    f.tab_mismatch = mismatch;
+    if (nwdist) {
+        f.kmode = BM_DIST;
+        f.tab_match = match - gap;       // the rows store H + gap: the diagonal consumer takes the gap back out
+        f.tab_mismatch = mismatch - gap;
+        if (al.n_alpha <= 7 && fits8(f.tab_match) && fits8(f.tab_mismatch)) f.score_path = SC_PERM;
+        if (f.score_path == SC_CMP && al.absent_byte < 0)
+            return fail(ctx, PWA_E_INVALID, "distance pass: the texts use all 256 byte values, no padding symbol left");
+        // packed (H, dist) keys: dist in 12 bits, H in the 18 above (batch_nwdist.hip.h)
+        if (max_n + max_m <= 4000 && (int64_t)(max_n + max_m + 2) * max_abs({match, mismatch, gap}) < 65536 && !ctx->knobs.no_packed_dist) {
+            f.kmode = BM_DISTP;
+            f.tab_match = match;       // the packed kernel takes hw4's own three scores
+            f.tab_mismatch = mismatch;
+        }
+    } else if (affine) {
+        // Ge(i+j)-shifted form when every value stays far inside int32 (the sentinels are -2^29 there)
+        const bool shift_ok = (int64_t)(max_n + max_m + 4) * max_abs({match, mismatch, gap, gap_extend}) * 4 < (1ll << 27);
+        f.kmode = shift_ok ? BM_AFFS : BM_AFF;
+        f.aff_go = gap;
+        f.aff_ge = gap_extend;
+        f.aff_neg = shift_ok ? -(1 << 29) : std::numeric_limits<int32_t>::min() / 2;   // hw3.cpp:16
+        if (shift_ok) {
+            f.tab_match = match - 2 * gap_extend;
+            f.tab_mismatch = mismatch - 2 * gap_extend;
+        }
+        if (al.n_alpha <= 7 && fits8(f.tab_match) && fits8(f.tab_mismatch)) f.score_path = SC_PERM;
+        if (f.score_path == SC_CMP && al.absent_byte < 0)
+            return fail(ctx, PWA_E_INVALID, "affine pass: the texts use all 256 byte values, no padding symbol left");
+    } else if (f.strips) {
+        if (!local) {
+            // gap-shifted NW: G = H - g(i+j) needs every |value| to stay far inside int32
+            const int64_t s_match = (int64_t)match - 2 * (int64_t)gap, s_mis = (int64_t)mismatch - 2 * (int64_t)gap;
+            if ((int64_t)(max_n + max_m + 4) * max_abs({match, mismatch, gap}) * 4 < (1ll << 30) && fits8((int)s_match) && fits8((int)s_mis)) {
+                f.kmode = BM_NWG;
+                f.tab_match = (int)s_match;
+                f.tab_mismatch = (int)s_mis;
+            }
+        }
+        // (an alphabet of more than 7 symbols takes the compare path, which works in G space too)
+        if (al.n_alpha <= 7 && fits8(f.tab_match) && fits8(f.tab_mismatch)) f.score_path = SC_PERM;
+        if (f.score_path == SC_CMP && al.absent_byte < 0) f.strips = false;   // no byte left to pad with
+    }
+    // (a scores pass that wants end cells runs wholly off the strips: its arena is coded whenever the alphabet allows, for the mini-stripe
+    // kernels -- the stripe engine's compare form is the same on codes, a pattern-only symbol is code 7 and equals no text code)
+    const bool code_for_end_cells = in.want_end && !affine && !nwdist && al.n_alpha <= 7 && ctx->knobs.tb_engine != 0;
+    f.coded = (f.strips && f.score_path == SC_PERM) || code_for_end_cells;
+    // Short patterns that a scores pass routes away from the strips run on the mini-stripe engine WITHOUT a band (mini_fill.hip.h,
+    // BAND = false: four pairs per wave) where it applies: coded arena, keyed cells in range, table constants in a byte.
+    if (f.coded && !affine && !nwdist && ctx->knobs.tb_engine != 0 && tb_range_ok(max_n + max_m, match, mismatch, gap, local ? 26 : 28)) {
+        f.mini_scores = diag_keys_fit(match, mismatch, gap);
+        f.mini_gap0 = f.mini_scores && !local && gap0_ok(max_n + max_m, match, mismatch, gap);
+    }
+    return PWA_OK;
+}
+
+// Device arena: every used sequence, 16-byte aligned, as symbols of the chosen coding; aoff[s]: where sequence s starts
+int upload_arena(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std::vector<uint8_t>& is_used, uint64_t max_n, const CellForm& f,
+                 const Alphabet& al, std::vector<uint64_t>& aoff) {
+    aoff.assign(in.n_seq, 0);
+    uint64_t arena_bytes = 0;
+    for (uint32_t s = 0; s < in.n_seq; ++s)
+        if (is_used[s]) {
+            aoff[s] = arena_bytes;
+            arena_bytes += align_up(in.len(s) + 1, 16);
+        }
+    arena_bytes += 512;   // slack: strips and text words are over-read, never over-used
+    // (a strip task loads its lanes' pattern words for every strip of its LONGEST pattern and masks them after the load: a short pattern
+    // is read up to that length past its start -- past the end of the arena when it lies last, which faulted on the device)
+    if (f.strips) arena_bytes += align_up(max_n, 16);
+    if (arena_bytes >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "sequence arena exceeds 4 GiB");
+    uint8_t code8[256];
+    for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)(al.code_of[v] >= 0 ? al.code_of[v] : 7);
+    HIPC(ctx, b->arena.alloc(arena_bytes));
+    HIPC(ctx, build_arena(ctx, b->arena.p, arena_bytes, in.seq_bytes, in.seq_off, in.n_seq, is_used, aoff, f.coded ? code8 : nullptr,
+                          !al.present[0] && !al.pattern_has[0]));
+    return PWA_OK;
+}
+
+struct HostTask {
+    uint32_t text, first, count;
+    uint64_t maxlen;   // longest pattern of the task
+    uint64_t m;        // text length (LANES: the longest text of the task)
+};
+
+// up to lanes_per_task patterns of one text per wave task
+std::vector<HostTask> group_by_text(const BatchInput& in, const std::vector<uint32_t>& order, size_t lanes_per_task) {
+    std::vector<HostTask> g;
+    for (size_t p = 0; p < order.size();) {
+        size_t q = p;
+        while (q < order.size() && q - p < lanes_per_task && in.pair_b[order[q]] == in.pair_b[order[p]]) ++q;
+        g.push_back({in.pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), in.len(in.pair_a[order[p]]), in.len(in.pair_b[order[p]])});
+        p = q;
+    }
+    return g;
+}
+
+struct StripTasks {
+    std::vector<uint32_t> order;   // pair indices, task by task
+    std::vector<HostTask> ht;
+    bool lanes = false;            // every lane its own text (LANES kernels)
+};
+
+// ---- wave tasks: pairs grouped by text, patterns sorted by length, 64 per wave
+StripTasks plan_strip_tasks(pwa_ctx* ctx, const BatchInput& in, const std::vector<uint32_t>& live, const CellForm& f, const Alphabet& al) {
+    StripTasks st;
+    std::vector<uint32_t>& order = st.order;
+    order = live;   // ascending pair index: the stable sorts below keep it as the last key
+    {
+        // text ascending, pattern length descending.  Stable counting sorts, least significant key first: two linear passes
+        // per key, and the length pass is skipped when every pattern has the same length (a million-pair cross product:
+        // ~3 ms [gpu box] against 14 ms for the 64-bit radix sort, which stays as the fallback for huge key ranges)
+        uint64_t lmin = ~0ull, lmax = 0;
+        for (const uint32_t k : order) {
+            const uint64_t l = in.len(in.pair_a[k]);
+            lmin = std::min(lmin, l);
+            lmax = std::max(lmax, l);
+        }
+        // (the histograms have n_seq + 1 and lmax - lmin + 1 entries whatever the list's size: a short list over a large
+        // FASTA index, or with one outlier length, is cheaper through the radix sort)
+        if (lmax - lmin < (1u << 22) && in.n_seq <= (1u << 24) && (uint64_t)in.n_seq <= 4 * (uint64_t)order.size() + 65536 &&
+            lmax - lmin <= 4 * (uint64_t)order.size() + 65536) {
+            std::vector<uint32_t> tmp;
+            if (lmax != lmin) counting_sort(order, tmp, (size_t)(lmax - lmin + 1), [&](uint32_t k) { return (size_t)(lmax - in.len(in.pair_a[k])); });
+            counting_sort(order, tmp, (size_t)in.n_seq, [&](uint32_t k) { return (size_t)in.pair_b[k]; });
+        } else {
+            std::vector<uint64_t> key(order.size());   // text ascending, pattern length descending (lengths < 2^31)
+            for (size_t o = 0; o < order.size(); ++o)
+                key[o] = ((uint64_t)in.pair_b[order[o]] << 32) | (uint64_t)(0x7fffffffu - (uint32_t)in.len(in.pair_a[order[o]]));
+            radix_sort_by_key(key, order);
+        }
+    }
+    st.ht = group_by_text(in, order, 64);
+    // ---- lists whose pairs share few texts (the reference's own loop pairs pattern i with reference i,
+    // hw2.cpp:328-338) would leave most lanes of a text-grouped wave empty: give every lane its own text
+    // instead (LANES kernels, local alignment only).  Pairs are sorted so that a wave's 64 pairs need about
+    // the same number of strips and columns; a wave runs max(strips) x max(columns) of its lanes.
+    bool kernels_have_lanes = false;
+    size_t n_kernels = 0;
+    const BatchKernelEntry* const kernels = batch_kernel_table(&n_kernels);
+    for (size_t ki = 0; ki < n_kernels; ++ki) kernels_have_lanes |= (kernels[ki].fn_lanes != nullptr && kernels[ki].score == f.score_path);
+    const bool text_pad_ok = f.score_path == SC_PERM ? al.n_alpha <= 6 : al.text_pad_byte >= 0;
+    const bool underfilled = st.ht.size() * 64 > order.size() * 3 / 2 + 64;
+    st.lanes = f.kmode == BM_SW && !in.affine() && !in.nwdist() && kernels_have_lanes && text_pad_ok && underfilled;
+    // global alignment: right-aligned texts, front-padded with a code the table scores like a gap (batch_scores.hip.h).
+    // Needs the gap-shifted form, a coded alphabet with codes 4..7 free, every pattern symbol inside it (a
+    // pattern-only symbol shares code 7 with the pad rows), g <= 0 and -g in a table byte.
+    bool patterns_inside = true;
+    for (int v = 0; v < 256; ++v) patterns_inside = patterns_inside && (!al.pattern_has[v] || al.present[v]);
+    const bool lanes_nw = f.kmode == BM_NWG && !in.affine() && !in.nwdist() && f.score_path == SC_PERM && al.n_alpha <= 4 && patterns_inside &&
+                          in.gap <= 0 && fits8(-in.gap) && underfilled;
+    st.lanes = st.lanes || lanes_nw;
+    if (ctx->knobs.force_lanes >= 0) st.lanes = st.lanes && ctx->knobs.force_lanes != 0;   // experiments only
+    if (st.lanes) {
+        order = live;
+        std::vector<uint64_t> key(order.size());   // nominal strips descending, then text length descending
+        for (size_t o = 0; o < order.size(); ++o) {
+            const uint64_t strips = (in.len(in.pair_a[order[o]]) + 75) / 76;
+            key[o] = ((0x7fffffffull - strips) << 32) | (uint64_t)(0x7fffffffu - (uint32_t)in.len(in.pair_b[order[o]]));
+        }
+        radix_sort_by_key(key, order);
+        st.ht.clear();
+        for (size_t p = 0; p < order.size(); p += 64) {
+            const size_t q = std::min(order.size(), p + 64);
+            uint64_t mn = 0, mm = 0;
+            for (size_t o = p; o < q; ++o) {
+                mn = std::max(mn, in.len(in.pair_a[order[o]]));
+                mm = std::max(mm, in.len(in.pair_b[order[o]]));
+            }
+            st.ht.push_back({in.pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), mn, mm});
+        }
+    }
+    return st;
+}
+
+struct StripHeight {
+    int R = 0, mode = 0;      // R = 0: no kernel instantiation
+    long double cost = -1;
+};
+
+// ---- strip height: least padded work, ties to the taller strip.  c16: the packed f16 form (two pairs per lane, 128-slot tasks),
+// priced per lane row at kCell16Vpr VALU for both pairs
+StripHeight choose_strip_height(const std::vector<HostTask>& tl, const CellForm& f, bool lanes, bool c16, const Knobs& knobs) {
+    StripHeight best;
+    best.mode = f.kmode;
+    size_t n_kernels = 0;
+    const BatchKernelEntry* const kernels = batch_kernel_table(&n_kernels);
+    const int force = knobs.force_r, force_mode = knobs.force_mode;   // experiments only
+    for (size_t ki = 0; ki < n_kernels; ++ki) {
+        const BatchKernelEntry& e = kernels[ki];
+        // SW has two forms: BM_SW (R registers per lane, 5.0 VALU per cell) and BM_SWS (2R registers, 4.06)
+        const bool mode_ok = e.mode == f.kmode || (f.kmode == BM_SW && e.mode == BM_SWS);
+        if (!mode_ok || e.score != f.score_path) continue;
+        if (lanes && !e.fn_lanes) continue;
+        if (c16 && !e.fn_cell16) continue;
+        const int R = e.R;
+        if (force && force != R) continue;
+        if (force_mode >= 0 && force_mode != e.mode) continue;
+        long double w = c16 ? (long double)kCell16Vpr : e.mode == BM_SWS ? 4.06L : (e.mode == BM_SW ? 5.02L : 1.0L);   // VALU per lane row
+        // affine strips of more than 40 rows run 2 instead of 3 waves per SIMD: [gpu] all pairs of 1024 x 1000 take
+        // 93.2 ms at R = 52 against 89.2 ms at R = 32 for the same padded cells
+        if ((e.mode == BM_AFF || e.mode == BM_AFFS) && R > 40) w *= 1.045L;
+        // evaluated cells + the strip hand-off priced at ~2 cells per column and strip boundary ([gpu]: the
+        // 1000-row affine pass is equally fast at R = 32 and 52 but moves 37 % fewer HBM bytes at 52)
+        long double cost = 0;
+        for (const auto& t : tl) {
+            const uint64_t strips = (t.maxlen + R - 1) / R;
+            cost += (long double)(strips * R + 2 * (strips - 1)) * (long double)t.m * 64.0L;
+        }
+        cost *= w;
+        if (best.cost < 0 || cost < best.cost || (cost == best.cost && R > best.R)) {
+            best.cost = cost;
+            best.R = R;
+            best.mode = e.mode;
+        }
+    }
+    return best;
+}
+
+// ---- packed f16 cells (batch_scores.hip.h, CELL16): local scores over a coded arena whose pattern symbols all have codes 0..3,
+// pad rules of the int32 strips (mismatch, gap <= 0), scores in a byte, and every value k * 2^-11 with |k| <= 2047 exact in f16:
+// H <= longest pattern * max(match, 0) bounds all of them.  Everything else keeps the int32 kernels, bit for bit.
+bool cell16_admitted(const Knobs& knobs, const BatchInput& in, const CellForm& f, const Alphabet& al, bool lanes, uint64_t max_n) {
+    bool pats_low = true;
+    for (int v = 0; v < 256; ++v) pats_low = pats_low && (!al.pattern_has[v] || (al.present[v] && al.code_of[v] <= 3));
+    return in.local && f.kmode == BM_SW && !in.affine() && !in.nwdist() && f.score_path == SC_PERM && !lanes && pats_low &&
+           in.mismatch <= 0 && in.gap <= 0 && max_abs({in.match, in.mismatch, in.gap}) <= 127 && (int64_t)max_n * std::max(in.match, 0) <= 2047 &&
+           knobs.cell16 != 0 && (knobs.force_mode < 0 || knobs.force_mode == BM_SWS);
+}
+
+// Whether the cost-based split below applies.  Linear scores always.  hw4 distances take it when the batch is in the two-value form
+// (some n + m > 4000, or PWA_NO_PACKED_DIST): coded arena, keys H * 4 + prio inside int32 (pair_dist.hip.h).  Packed-form lists, other
+// byte alphabets and larger scores stay on the strips.  hw3 affine scores likewise: coded arena, every real value inside +-2^28 so that
+// the -2^29 sentinels never win (pair_affine.hip.h).  Raw-byte alphabets and scorings large enough for the reference's own
+// wrap-around to matter stay on the strips.
+bool route_eligible(const BatchInput& in, const CellForm& f, uint64_t max_n, uint64_t max_m) {
+    if (in.nwdist())
+        return f.kmode == BM_DIST && f.score_path == SC_PERM && (int64_t)(max_n + max_m + 2) * max_abs({in.match, in.mismatch, in.gap, 1}) < (1ll << 28);
+    if (in.affine())
+        return f.score_path == SC_PERM &&
+               (int64_t)(max_n + max_m + 2) * max_abs({in.match, in.mismatch, std::llabs((long long)in.gap) + std::llabs((long long)in.gap_extend), 1}) < (1ll << 28);
+    return true;
+}
+
+// Route estimates of a pass kind: the strips' VALU per cell; and the stripe engine's, in the units of the estimate (stripes of
+// choose_geom's geometry): ns per stripe step and SIMD with the chip full, us of pipeline lag per stripe, ns per step of a pair alone
+struct RouteCost {
+    double valu_per_cell, step_ns, lag_us, lone_step_ns;
+};
+
+RouteCost route_cost(const BatchInput& in, const CellForm& f, bool cell16, int strip_mode) {
+    // the distance fill (pair_dist.hip.h), [gpu] profiles/hw4_long_route_probe.txt: 496 pairs 10k x 10k 29.9 ms; one pair 10k x 10k
+    // 2.66 ms, 20k x 20k 5.29 ms
+    if (in.nwdist()) return {10.75, 80.0, 13.0, 162.0};
+    // the affine score fill (pair_affine.hip.h), [gpu] profiles/hw3_long_route_probe.txt: 496 pairs 10k x 10k 23.4 ms; one pair
+    // 10k x 10k 1.62 ms, 20k x 20k 3.21 ms; affine strips: 5.6 VALU per cell, PMC of profiles/r03_hw3_rocprof_summary.md
+    if (in.affine()) return {5.6, 62.0, 8.0, 99.0};
+    // linear scores: the keyed chunk without a band (coded arena, keys in range) or the plain step ([gpu] r03_route_probe.txt: one
+    // 10k x 10k pair 1.26 / 1.01 ms, 64 pairs 3.45 / 2.05 ms)
+    const double vpc = cell16 ? kCell16Vpr : (strip_mode == BM_SWS ? 4.06 : strip_mode == BM_SW ? 5.02 : strip_mode == BM_NWG ? 2.53 : 4.5) + (f.score_path == SC_CMP ? 2.0 : 0.0);
+    if (f.mini_scores) return {vpc, in.local ? 70.0 : 42.0, 9.0, in.local ? 55.0 : 30.0};
+    return {vpc, in.local ? 105.0 : 75.0, 9.0, 100.0};
+}
+
+// ---- work-aware routing (r03).  The strip engine is the cheaper one per cell (lane = pair, 2.5 - 5 VALU per cell) but a wave
+// task is one wave running strips x columns on its own: a list of few long pairs -- ONE 10k x 10k pair is 105 strips x 2500
+// column blocks x 1560 instructions on one lane of one wave, [gpu] 779 ms against 1.67 ms on the stripe engine -- or of few
+// wave tasks (4096 pairs 150 x 10k = 64 tasks: 11.6 ms against 4.3 ms) leaves the chip idle.  The stripe engine spreads a
+// pair over ceil(n / (64 RL)) waves that sweep anti-diagonals (~100 ns per step of 64 RL cells per SIMD).  Both costs are
+// estimated from the task list with constants measured on the GPU (profiles/r03_route_probe.txt), tasks are moved to the
+// stripe engine in two candidate orders (largest strip task first; cheapest-to-move per unit of strip work first) and
+// the split with the smallest estimated total -- the two launches run one after the other on the run's stream -- wins.
+// Pairs are independent (hw2.cpp:328-338) and both engines are exact, so a split changes no result.
+// Returns the tasks (indices into st.ht) to move to the stripe engine.
+std::vector<uint32_t> tasks_to_move(const pwa_ctx* ctx, const BatchInput& in, const StripTasks& st, int R, uint64_t task_lanes,
+                                    const RouteCost& rc, bool mini_scores) {
+    const std::vector<HostTask>& ht = st.ht;
+    const size_t nt0 = ht.size();
+    constexpr double kLoneNs = 1.9, kSimdNs = 1.63;                                 // ns per wave instruction: one wave alone / a SIMD with two
+    const double kSimds = 4.0 * ctx->num_cu;
+    std::vector<double> I(nt0), S(nt0), L(nt0);   // strip instructions / stripe-side work (ns x SIMD) / longest single-pair latency (us) of a task
+    double I_total = 0, I_max = 0;
+    uint64_t filled = 0;
+    for (size_t t = 0; t < nt0; ++t) {
+        const uint64_t strips = (ht[t].maxlen + R - 1) / R;
+        I[t] = (double)strips * (double)((ht[t].m + 3) / 4) * (4.0 * R * rc.valu_per_cell);
+        I_total += I[t];
+        I_max = std::max(I_max, I[t]);
+        filled += ht[t].count;
+    }
+    // nothing to route when the strips' waves are many, full, and none of them dominates: per cell the strips are the cheapest engine
+    // by 2x and more, so no task can gain by leaving (and the per-pair estimates below cost ~3 ms for a million pairs)
+    const bool strips_fit = (double)nt0 >= 4 * kSimds && filled * 10 >= (uint64_t)nt0 * task_lanes * 9 && I_max * kLoneNs * 4 < I_total / kSimds * kSimdNs &&
+                            ctx->knobs.scores_route < 0;
+    for (size_t t = 0; t < nt0 && !strips_fit; ++t) {
+        double steps = 0, lat = 0;
+        for (uint32_t l = 0; l < ht[t].count; ++l) {
+            const uint32_t k = st.order[ht[t].first + l];
+            const uint64_t n = in.len(in.pair_a[k]), m = in.len(in.pair_b[k]);
+            if (const int mrl = mini_scores ? mini_rl_for(n) : 0) {   // mini-stripe engine, no band: a quarter of a wave, (17 + 5 | 7.3 RL) instructions per step
+                const double mstep = (17.0 + (in.local ? 7.3 : 5.0) * mrl) * 1.37;   // [gpu] 92 ns per step for RL = 10, global (tools/probes/mini_mix.hip)
+                steps += (double)(m + 15) * mstep / 4.0 / 1.5;                    // (two waves per SIMD: ~1.9 x one wave's throughput)
+                lat = std::max(lat, (double)(m + 15) * mstep * 1e-3);
+                continue;
+            }
+            const PairGeom g = choose_geom(ctx->knobs, n);
+            const double stripes = (double)((n + 64 * g.rl - 1) / (64 * g.rl));
+            steps += stripes * (double)(m + 63) * rc.step_ns;
+            lat = std::max(lat, stripes * rc.lag_us + (double)(m + 63) * rc.lone_step_ns * 1e-3);
+        }
+        S[t] = steps;
+        L[t] = lat;
+    }
+    auto evaluate = [&](const std::vector<uint32_t>& ord, size_t& best_k) -> double {
+        // tasks ord[0 .. k-1] move; suffix maxima of I over the tasks that stay
+        std::vector<double> sufmax(nt0 + 1, 0.0);
+        for (size_t k = nt0; k-- > 0;) sufmax[k] = std::max(sufmax[k + 1], I[ord[k]]);
+        double best_t = -1, moved_I = 0, moved_S = 0, moved_L = 0;
+        for (size_t k = 0; k <= nt0; ++k) {
+            const double ts = std::max(sufmax[k] * kLoneNs, (I_total - moved_I) / kSimds * kSimdNs) * 1e-3;              // us
+            const double tp = k ? std::max(moved_L, moved_S / kSimds * 1e-3) + 15.0 : 0.0;                                 // us (+ two more launches)
+            const double tt = ts + tp;
+            if (best_t < 0 || tt < best_t) {
+                best_t = tt;
+                best_k = k;
+            }
+            if (k < nt0) {
+                moved_I += I[ord[k]];
+                moved_S += S[ord[k]];
+                moved_L = std::max(moved_L, L[ord[k]]);
+            }
+        }
+        return best_t;
+    };
+    std::vector<uint32_t> ordA(nt0), ordB(nt0);
+    std::iota(ordA.begin(), ordA.end(), 0u);
+    ordB = ordA;
+    if (!strips_fit) {
+        std::stable_sort(ordA.begin(), ordA.end(), [&](uint32_t x, uint32_t y) { return I[x] > I[y]; });
+        std::stable_sort(ordB.begin(), ordB.end(), [&](uint32_t x, uint32_t y) { return S[x] * I[y] < S[y] * I[x]; });   // S / I ascending
+    }
+    size_t kA = 0, kB = 0;
+    const double tA = strips_fit ? 0.0 : evaluate(ordA, kA), tB = strips_fit ? 0.0 : evaluate(ordB, kB);
+    std::vector<uint32_t>& ord = tA <= tB ? ordA : ordB;
+    size_t kmove = strips_fit ? 0 : (tA <= tB ? kA : kB);
+    if (ctx->knobs.scores_route == 1) kmove = nt0;   // tests: everything (eligible) on the stripe engine
+    if (ctx->knobs.debug) std::fprintf(stderr, "[pwa] route: %zu of %zu wave tasks to the stripe engine (estimates: all on strips %.1f us, split %.1f us)\n",
+                                       kmove, nt0, std::max(*std::max_element(I.begin(), I.end()) * kLoneNs, I_total / kSimds * kSimdNs) * 1e-3, std::min(tA, tB));
+    ord.resize(kmove);
+    return std::move(ord);
+}
+
+// Takes the moved tasks out of st.ht; returns their pairs, ascending
+std::vector<uint32_t> split_tasks(StripTasks& st, const std::vector<uint32_t>& move) {
+    std::vector<uint8_t> moved(st.ht.size(), 0);
+    for (const uint32_t t : move) moved[t] = 1;
+    std::vector<HostTask> keep;
+    std::vector<uint32_t> pair_list;
+    for (size_t t = 0; t < st.ht.size(); ++t) {
+        if (!moved[t]) {
+            keep.push_back(st.ht[t]);
+            continue;
+        }
+        for (uint32_t l = 0; l < st.ht[t].count; ++l) pair_list.push_back(st.order[st.ht[t].first + l]);
+    }
+    st.ht.swap(keep);
+    std::sort(pair_list.begin(), pair_list.end());
+    return pair_list;
+}
+
+// The strip kernel a batch launches, chosen once: the occupancy query and pwa_batch_run both take this one
+void* strip_kernel_fn(const BatchKernelEntry& e, const BatchInput& in, bool cell16, bool lanes, bool single) {
+    if (in.nwdist()) return reinterpret_cast<void*>(e.dfn);
+    if (in.affine()) return reinterpret_cast<void*>(e.afn);
+    const batch_kernel_t fn = cell16  ? (single ? e.fn_cell16_single : e.fn_cell16)
+                              : lanes ? (single ? e.fn_lanes_single : e.fn_lanes)
+                                      : (single && e.fn_single ? e.fn_single : e.fn);
+    return reinterpret_cast<void*>(fn);
+}
+
+// Right-aligned, front-padded (code 4) text rows of a LANES global batch: task t, lane l at t_base + l * M_t, M_t = 4 * ceil(max m / 4)
+int upload_lane_rows(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Alphabet& al, const StripTasks& st, BatchTask* tasks, uint32_t* stoff) {
+    const std::vector<HostTask>& ht = st.ht;
+    const size_t nt = ht.size();
+    uint64_t total = 0;
+    std::vector<uint64_t> tbase(nt);
+    for (size_t t = 0; t < nt; ++t) {
+        tbase[t] = total;
+        total += 64ull * ((ht[t].m + 3) / 4 * 4);
+    }
+    if (total + 64 >= (ctx->knobs.lane_rows_limit ? ctx->knobs.lane_rows_limit : 0xffffffffull))
+        return fail(ctx, PWA_E_CAPACITY, "per-lane text rows exceed 4 GiB");   // (one-shot calls halve the run and retry)
+    // The rows are built straight in the context's two page-locked arena buffers, in pieces of whole tasks (~32 MiB), by several host
+    // threads, while the previous piece is on its way (copy stream) -- like build_arena.  (Until r03: one thread, byte by byte into a
+    // heap buffer, then through the bounce buffer: 156 ms of a 159 ms call for 131 072 pairs 150 x 2000.)
+    HIPC(ctx, b->lane_text.alloc(total + 64));
+    uint8_t code8[256];
+    for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)al.code_of[v];
+    constexpr uint64_t kPiece = 32ull << 20;
+    auto task_end = [&](size_t t) { return t + 1 < nt ? tbase[t + 1] : total + 64; };   // (the slack after the last task is pad as well)
+    int piece = 0;
+    for (size_t t0 = 0; t0 < nt; ++piece) {
+        size_t t1 = t0 + 1;
+        while (t1 < nt && task_end(t1) - tbase[t0] <= kPiece) ++t1;
+        const uint64_t base = tbase[t0], bytes = task_end(t1 - 1) - base;
+        PinnedBuf& pb = ctx->pin[pwa_ctx::PIN_ARENA + (piece & 1)];
+        if (piece >= 2) HIPC(ctx, hipEventSynchronize(ctx->copy_ev[piece & 1]));   // the copy that last read this buffer
+        HIPC(ctx, pb.reserve(bytes));
+        uint8_t* const host = pb.as<uint8_t>();
+        const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>({16, bytes / (1ull << 20) + 1, std::max(1u, std::thread::hardware_concurrency()), (uint64_t)(t1 - t0)}));
+        auto work = [&](int th) {
+            const size_t a = t0 + (t1 - t0) * (size_t)th / (size_t)T, z = t0 + (t1 - t0) * (size_t)(th + 1) / (size_t)T;
+            for (size_t t = a; t < z; ++t) {
+                const uint64_t M = (ht[t].m + 3) / 4 * 4;
+                std::memset(host + (tbase[t] - base), 4, task_end(t) - tbase[t]);
+                tasks[t].text_len = (uint32_t)M;
+                for (uint32_t l = 0; l < ht[t].count; ++l) {
+                    const uint32_t k = st.order[ht[t].first + l];
+                    const uint8_t* src = in.seq_bytes + in.seq_off[in.pair_b[k]];
+                    const uint64_t len = in.len(in.pair_b[k]);
+                    uint8_t* dst = host + (tbase[t] - base) + (uint64_t)l * M + (M - len);
+                    for (uint64_t o = 0; o < len; ++o) dst[o] = code8[src[o]];
+                    stoff[t * 64 + l] = (uint32_t)(tbase[t] + (uint64_t)l * M);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int th = 1; th < T; ++th) pool.emplace_back(work, th);
+        work(0);
+        for (auto& x : pool) x.join();
+        HIPC(ctx, hipMemcpyAsync(b->lane_text.as<uint8_t>() + base, host, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+        HIPC(ctx, hipEventRecord(ctx->copy_ev[piece & 1], ctx->copy_stream));
+        t0 = t1;
+    }
+    HIPC(ctx, hipStreamSynchronize(ctx->copy_stream));
+    return PWA_OK;
+}
+
+// The strips that stay: slot arrays, lane text rows, the kernel, the hand-off workspace and BatchParams
+int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellForm& f, const Alphabet& al, const std::vector<uint64_t>& aoff,
+                 StripTasks& st, const StripHeight& h, uint64_t max_m, CreateClock& clock) {
+    std::vector<HostTask>& ht = st.ht;
+    const int kmode = h.mode, R = h.R;
+    const uint64_t kTaskLanes = b->cell16 ? 128 : 64;   // lane slots per wave task
+    for (const auto& t : ht) b->padded_cells += (t.maxlen + R - 1) / R * R * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
+    b->kern = find_batch_kernel(R, kmode, f.score_path);
+    if (!b->kern) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
+    b->kernel_name = b->kern->name;
+    std::sort(ht.begin(), ht.end(), [&](const HostTask& x, const HostTask& y) {   // longest first
+        const uint64_t cx = (x.maxlen + R - 1) / R * x.m, cy = (y.maxlen + R - 1) / R * y.m;
+        if (cx != cy) return cx > cy;
+        return x.first < y.first;
+    });
+    const size_t nt = ht.size();
+    // task list and lane slots are built in page-locked buffers of the context and uploaded from there (see PinnedBuf)
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_TASKS].reserve(nt * sizeof(BatchTask)));
+    for (int q = 0; q < (b->lanes ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * kTaskLanes * sizeof(uint32_t)));
+    BatchTask* const tasks = ctx->pin[pwa_ctx::PIN_TASKS].as<BatchTask>();
+    uint32_t* const spoff = ctx->pin[pwa_ctx::PIN_SLOT0].as<uint32_t>();
+    uint32_t* const splen = ctx->pin[pwa_ctx::PIN_SLOT1].as<uint32_t>();
+    uint32_t* const sout = ctx->pin[pwa_ctx::PIN_SLOT2].as<uint32_t>();
+    uint32_t* const stoff = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT3].as<uint32_t>() : nullptr;   // empty lanes: no text, no pattern
+    uint32_t* const stlen = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT4].as<uint32_t>() : nullptr;
+    std::memset(tasks, 0, nt * sizeof(BatchTask));
+    std::memset(spoff, 0, nt * kTaskLanes * sizeof(uint32_t));
+    std::memset(splen, 0, nt * kTaskLanes * sizeof(uint32_t));
+    std::memset(sout, 0xff, nt * kTaskLanes * sizeof(uint32_t));
+    if (b->lanes) {
+        std::memset(stoff, 0, nt * kTaskLanes * sizeof(uint32_t));
+        std::memset(stlen, 0, nt * kTaskLanes * sizeof(uint32_t));
+    }
+    uint32_t max_strips = 1;
+    {   // (a million slots through three indirections each: on a few threads for long task lists)
+        const int T = (int)std::max<size_t>(1, std::min<size_t>({8, std::max(1u, std::thread::hardware_concurrency()), nt >> 11}));
+        std::vector<uint32_t> part_max((size_t)T, 1);
+        auto work = [&](int th) {
+            const size_t a = nt * (size_t)th / (size_t)T, z = nt * (size_t)(th + 1) / (size_t)T;
+            for (size_t t = a; t < z; ++t) {
+                tasks[t].text_off = (uint32_t)aoff[ht[t].text];
+                tasks[t].text_len = (uint32_t)ht[t].m;
+                tasks[t].slot0 = (uint32_t)(t * kTaskLanes);
+                tasks[t].n_strips = (uint32_t)((ht[t].maxlen + R - 1) / R);
+                part_max[(size_t)th] = std::max(part_max[(size_t)th], tasks[t].n_strips);
+                for (uint32_t l = 0; l < ht[t].count; ++l) {
+                    const uint32_t k = st.order[ht[t].first + l];
+                    spoff[t * kTaskLanes + l] = (uint32_t)aoff[in.pair_a[k]];
+                    splen[t * kTaskLanes + l] = (uint32_t)in.len(in.pair_a[k]);
+                    sout[t * kTaskLanes + l] = k;
+                    if (b->lanes) {
+                        stoff[t * kTaskLanes + l] = (uint32_t)aoff[in.pair_b[k]];
+                        stlen[t * kTaskLanes + l] = (uint32_t)in.len(in.pair_b[k]);
+                    }
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        for (int th = 1; th < T; ++th) pool.emplace_back(work, th);
+        work(0);
+        for (auto& x : pool) x.join();
+        for (int th = 0; th < T; ++th) max_strips = std::max(max_strips, part_max[(size_t)th]);
+    }
+    if (b->lanes && kmode == BM_NWG) {
+        const int rc = upload_lane_rows(ctx, b, in, al, st, tasks, stoff);
+        if (rc != PWA_OK) return rc;
+    }
+    if (b->lanes) {
+        HIPC(ctx, b->slot_toff.alloc(nt * 64 * 4));
+        HIPC(ctx, hipMemcpy(b->slot_toff.p, stoff, nt * 64 * 4, hipMemcpyHostToDevice));
+        HIPC(ctx, b->slot_tlen.alloc(nt * 64 * 4));
+        HIPC(ctx, hipMemcpy(b->slot_tlen.p, stlen, nt * 64 * 4, hipMemcpyHostToDevice));
+    }
+    clock.mark("choose R + slot arrays");
+    HIPC(ctx, b->tasks.alloc(nt * sizeof(BatchTask)));
+    HIPC(ctx, hipMemcpy(b->tasks.p, tasks, nt * sizeof(BatchTask), hipMemcpyHostToDevice));
+    HIPC(ctx, b->slot_poff.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, hipMemcpy(b->slot_poff.p, spoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+    HIPC(ctx, b->slot_plen.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, hipMemcpy(b->slot_plen.p, splen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+    HIPC(ctx, b->slot_out.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, hipMemcpy(b->slot_out.p, sout, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+
+    if (b->lanes) b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
+    b->strip_fn = strip_kernel_fn(*b->kern, in, b->cell16, b->lanes, max_strips == 1);
+    int per_cu = 0;
+    HIPC(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, b->strip_fn, 64, 0));
+    per_cu = std::max(1, std::min(per_cu, 32));
+    b->grid = (uint32_t)std::min<uint64_t>(nt, (uint64_t)ctx->num_cu * per_cu);
+    // int32 per half: one (affine: two) int4 per lane per 4-column block
+    const int hand_vals = (in.affine() || (in.nwdist() && kmode != BM_DISTP)) ? 2 : 1;   // int4 per lane per 4-column block
+    const uint64_t half = (max_strips > 1 ? ((max_m + 3) / 4 + 1) * 256 : 256) * hand_vals;
+    // Strip s reads the half written by strip s-1 and writes the other one.  With at most two strips per task
+    // the second half is only ever the parked dummy block (stride 0), so it is one block long: for C3 that
+    // turns a 10.5 GB workspace (0.24 s of hipMalloc, profiles/r01_malloc_probe.txt) into 5.2 GB (0.3 ms).
+    const uint64_t block_ints = 256 * hand_vals;
+    const uint64_t second = max_strips > 2 ? half : block_ints;
+    {   // very long texts: fewer workgroups rather than a workspace that does not fit (tasks come off a queue,
+        // any grid is correct)
+        size_t free_b = 0, total_b = 0;
+        HIPC(ctx, hipMemGetInfo(&free_b, &total_b));
+        const uint64_t per_wg = (half + second) * sizeof(int32_t);
+        const uint64_t fit = std::max<uint64_t>(1, (uint64_t)(free_b * 0.6) / per_wg);
+        b->grid = (uint32_t)std::min<uint64_t>(b->grid, fit);
+        b->grid = (b->grid + 3u) & ~3u;   // whole four-wave workgroups (pwa_batch_run): every wave has a hand-off region of its own
+    }
+    {
+        const size_t hand_bytes = (size_t)b->grid * (half + second) * sizeof(int32_t);
+        if (ctx->hand_cache && ctx->hand_cache_bytes >= hand_bytes) {   // left behind by an earlier batch of this context
+            b->hand.p = ctx->hand_cache;
+            b->hand.bytes = ctx->hand_cache_bytes;
+            ctx->hand_cache = nullptr;
+            ctx->hand_cache_bytes = 0;
+        } else {
+            HIPC(ctx, b->hand.alloc(hand_bytes));
+        }
+    }
+
+    clock.mark("uploads + workspace");
+    BatchParams& P = b->bp;
+    P.arena = b->arena.as<uint8_t>();
+    P.tasks = b->tasks.as<BatchTask>();
+    P.slot_poff = b->slot_poff.as<uint32_t>();
+    P.slot_plen = b->slot_plen.as<uint32_t>();
+    P.slot_out = b->slot_out.as<uint32_t>();
+    P.scores = b->scores.as<int32_t>();
+    P.hand = b->hand.as<int32_t>();
+    P.hand_stride = half + second;
+    P.hand_half = (uint32_t)half;
+    P.queue = b->queue.as<uint32_t>();
+    P.n_tasks = (uint32_t)nt;
+    P.match = f.tab_match;
+    P.mismatch = f.tab_mismatch;
+    P.gap = in.gap;
+    const uint32_t bm = (uint8_t)(int8_t)f.tab_match, bx = (uint8_t)(int8_t)f.tab_mismatch;
+    P.tab_lo = bm | (bx << 8) | (bx << 16) | (bx << 24);   // selector 0 -> match
+    P.tab_hi = bx * 0x01010101u;                           // selectors 4..7 -> mismatch
+    const uint32_t pad = (f.score_path == SC_PERM) ? 7u : (uint32_t)al.absent_byte;
+    P.pad_word = pad * 0x01010101u;
+    P.tpad_word = ((f.score_path == SC_PERM) ? 6u : (uint32_t)std::max(al.text_pad_byte, 0)) * 0x01010101u;
+    P.lane_text = b->lane_text.as<uint8_t>();
+    if (b->lanes && kmode == BM_NWG) P.tab_hi = (uint32_t)(uint8_t)(int8_t)(-in.gap) * 0x01010101u;   // selectors 4..7: front pad = a gap column
+    if (b->cell16) {   // f16 bit patterns of s * 2^-11 (exact: |s| <= 127)
+        const uint32_t m16 = f16_bits_scaled(in.match), x16 = f16_bits_scaled(in.mismatch), g16 = f16_bits_scaled(in.gap);
+        P.lo16_base = (x16 & 0xffu) * 0x01010101u;
+        P.lo16_diff = (m16 ^ x16) & 0xffu;
+        P.hi16_base = (x16 >> 8) * 0x01010101u;
+        P.hi16_diff = ((m16 ^ x16) >> 8) & 0xffu;
+        P.gap16x2 = g16 | (g16 << 16);
+    }
+    P.slot_toff = b->slot_toff.as<uint32_t>();
+    P.slot_tlen = b->slot_tlen.as<uint32_t>();
+    return PWA_OK;
+}
+
+// ---- the pairs that do not run on strips: short patterns over a coded arena on the mini-stripe engine (no band, four pairs per
+// wave, one launch per row class), everything else on the stripe engine (no band: exact first-maximum end cells, any scoring)
+int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellForm& f, const std::vector<uint64_t>& aoff,
+                     const std::vector<uint32_t>& pairs) {
+    const int match = in.match, mismatch = in.mismatch, gap = in.gap;
+    const bool local = in.local, mini_gap0 = f.mini_gap0;
+    std::vector<uint32_t> plist;
+    std::vector<std::pair<int, std::vector<uint32_t>>> mini_lists;   // (rows per lane, pairs)
+    for (const uint32_t k : pairs) {
+        const int mrl = f.mini_scores ? mini_rl_for(in.len(in.pair_a[k])) : 0;
+        if (!mrl) {
+            plist.push_back(k);
+            continue;
+        }
+        size_t c = 0;
+        while (c < mini_lists.size() && mini_lists[c].first != mrl) ++c;
+        if (c == mini_lists.size()) mini_lists.emplace_back(mrl, std::vector<uint32_t>());
+        mini_lists[c].second.push_back(k);
+    }
+    const size_t nl = pairs.size();
+    HIPC(ctx, b->pair_res.alloc(nl * sizeof(PairResult)));
+    HIPC(ctx, hipMemset(b->pair_res.p, 0, nl * sizeof(PairResult)));
+    size_t q_next = 0;
+    auto describe = [&](uint32_t k, size_t q) {
+        PairDesc d;
+        std::memset(&d, 0, sizeof d);
+        d.pat = b->arena.as<uint8_t>() + aoff[in.pair_a[k]];
+        d.txt = b->arena.as<uint8_t>() + aoff[in.pair_b[k]];
+        d.n = (int32_t)in.len(in.pair_a[k]);
+        d.m = (int32_t)in.len(in.pair_b[k]);
+        d.res = b->pair_res.as<PairResult>() + q;
+        d.out_index = k;
+        return d;
+    };
+    std::string names;
+    if (!plist.empty()) {
+        b->use_pairs = true;
+        b->live_idx = plist;
+        std::vector<PairDesc> pd;
+        pd.reserve(plist.size());
+        uint64_t pe_max_n = 0;
+        for (const uint32_t k : plist) pe_max_n = std::max(pe_max_n, in.len(in.pair_a[k]));
+        PairGeom geom = choose_geom(ctx->knobs, pe_max_n);
+        {   // RL = 2 buys a pair more waves in flight -- which a list that fills the chip anyway does not need: [gpu, r03] SW scores of
+            // 10k x 10k pairs, RL = 2 / RL = 4: 8 pairs 1.73 / 1.79 ms, 64 pairs 5.35 / 4.93 ms, 256 pairs 17.3 / 12.8 ms
+            uint64_t stripes2 = 0;
+            for (const uint32_t k : plist) stripes2 += (in.len(in.pair_a[k]) + 127) / 128;
+            if (geom.rl == 2 && geom.w == 4 && !ctx->knobs.force_rl && stripes2 >= 2048) geom.rl = 4;
+        }
+        // a coded arena with keys in range (what the band-less mini kernels ask for as well): the keyed chunk without a band -- table
+        // scoring, one v_max3 per cell, global fills gap-shifted -- instead of the plain compare-and-select step: [gpu, r03] SW scores of
+        // 64 pairs 10k x 10k 4.8 -> 3.45 ms, NW 4.06 -> 2.05 ms; one pair 1.67 -> 1.26 / 1.55 -> 1.01 ms
+        const bool keyed_scores = !in.nwdist() && f.mini_scores && !ctx->knobs.no_keyed_tb && !ctx->knobs.no_pair_table;
+        const bool gap0_scores = keyed_scores && mini_gap0 && !ctx->knobs.no_gap_shift;
+        for (const uint32_t k : plist) {
+            PairDesc d = describe(k, q_next++);
+            d.score_bias = gap0_scores ? wrap_mul((int64_t)(in.len(in.pair_a[k]) + in.len(in.pair_b[k])), gap) : 0;
+            pd.push_back(d);
+            b->padded_cells += (in.len(in.pair_a[k]) + 64 * geom.rl - 1) / (64 * geom.rl) * (64 * geom.rl) * in.len(in.pair_b[k]);
+        }
+        b->pl.perm = keyed_scores;
+        b->pl.keyed = true;
+        b->pl.gap0 = gap0_scores;
+        b->pl.dist = in.nwdist();
+        b->pl.aff = in.affine();   // (go travels as the gap, ge beside it)
+        const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom,
+                                   in.affine() ? in.gap_extend : 0);
+        if (rc != PWA_OK) return rc;
+        b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
+        names = in.nwdist()   ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
+                : in.affine() ? std::string("pair_affine_kernel<RL=") + std::to_string(geom.rl) + ",AFF,no-band>"
+                              : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
+    }
+    for (auto& cls : mini_lists) {
+        const int rl = cls.first;
+        std::vector<uint32_t>& lst = cls.second;
+        sort_by_length_desc(lst, [&](uint32_t x) { return in.len(in.pair_b[x]); });   // a wave's four texts about equally long
+        std::vector<PairDesc> pd;
+        pd.reserve(lst.size() + 3);
+        for (const uint32_t k : lst) {
+            PairDesc d = describe(k, q_next++);
+            b->live_idx.push_back(k);
+            d.score_bias = mini_gap0 ? wrap_mul((int64_t)(in.len(in.pair_a[k]) + in.len(in.pair_b[k])), gap) : 0;
+            pd.push_back(d);
+            b->padded_cells += (uint64_t)(16 * rl) * in.len(in.pair_b[k]);
+        }
+        const uint32_t n_real = (uint32_t)pd.size();
+        while (pd.size() % 4) {   // empty patterns fill the last wave (their results go nowhere: no row of theirs is row n)
+            PairDesc d = pd[n_real - 1];
+            d.n = 0;
+            pd.push_back(d);
+        }
+        b->mini.emplace_back(new PairLaunch());
+        PairLaunch& ml = *b->mini.back();
+        for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
+        ml.perm = ml.keyed = true;
+        ml.gap0 = mini_gap0;
+        const int rc = ml.build_mini(ctx, pd, n_real, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap, rl);
+        if (rc != PWA_OK) return rc;
+        ml.G.scores_out = b->scores.as<int32_t>();
+        names += std::string(names.empty() ? "" : " + ") + "mini_fill_kernel<RL=" + std::to_string(rl) + (local ? ",SW" : (mini_gap0 ? ",NW,GAP0" : ",NW")) + ",no-band>";
+    }
+    b->kernel_name = b->use_strips ? b->kernel_name + " + " + names : names;   // (the strip kernel first: bench.py prices its instruction mix)
+    return PWA_OK;
+}
+
+}  // namespace
+
 static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, int kind, int gap_extend,
                              const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
                              const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
@@ -948,21 +1824,9 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
     for (uint32_t s = 0; s < n_seq; ++s)
         if (seq_off[s + 1] < seq_off[s]) return fail(ctx, PWA_E_INVALID, "seq_off not monotone");
     HIPC(ctx, hipSetDevice(ctx->device));
-    const bool dbg = ctx->knobs.debug;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {   // PWA_DEBUG: host-side time between marks
-        if (!dbg) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[pwa] create: %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-        if (ctx->knobs.probe) {   // how long does a kernel submission take at this point?
-            hipLaunchKernelGGL(pwa_nop_kernel, dim3(1), dim3(64), 0, ctx->stream, (int*)nullptr);
-            (void)hipStreamSynchronize(ctx->stream);
-            const auto t2 = std::chrono::steady_clock::now();
-            std::fprintf(stderr, "[pwa]     probe after it: nop kernel + sync %8.3f ms\n", std::chrono::duration<double, std::milli>(t2 - now).count());
-            t_last = t2;
-        }
-    };
+    CreateClock clock{ctx};
+    const BatchInput in{seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, kind, match, mismatch, gap, gap_extend,
+                        mode == PWA_MODE_SW, want_end_cells != 0};
 
     pwa_batch* b = new (std::nothrow) pwa_batch();
     if (!b) return fail(ctx, PWA_E_NOMEM, "host allocation");
@@ -976,827 +1840,85 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
         d->pool = ctx;   // released buffers are kept for the next batch of this context
     b->mode = mode;
     b->n_pairs = n_pairs;
-    b->want_end = want_end_cells != 0;
-    const bool local = mode == PWA_MODE_SW;
+    b->want_end = in.want_end;
+    b->affine = affine;
+    b->nwdist = nwdist;
 
-    auto slen = [&](uint32_t s) -> uint64_t { return seq_off[s + 1] - seq_off[s]; };
-
-    // ---- one pass over the pair list: index check, and pairs with an empty side never reach a kernel (hw2.cpp: loops
-    // 138/205 do not run) -- they are resolved here
-    b->host_scores.assign(n_pairs, 0);
-    if (b->want_end) {
-        b->host_end_i.assign(n_pairs, 0);
-        b->host_end_j.assign(n_pairs, 0);
-    }
-    std::vector<uint32_t> live(n_pairs);
-    uint64_t max_n = 0, max_m = 0, n_live = 0;
-    bool any_trivial_score = false;
-    for (uint64_t k = 0; k < n_pairs; ++k) {
-        if (pair_a[k] >= n_seq || pair_b[k] >= n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
-        const uint64_t n = slen(pair_a[k]), m = slen(pair_b[k]);
-        if (n == 0 || m == 0) {
-            if (nwdist) {   // hw4.cpp:21-28 + 146-152: an all-gap alignment, every column counts
-                b->host_scores[k] = (int32_t)(n + m);
-            } else if (affine) {   // hw3.cpp:39-52: V[0][0] = 0, F[n][0] = Go + Ge(n-1), E[0][m] = Go + Ge(m-1)
-                b->host_scores[k] = (n + m == 0) ? 0 : (int32_t)((uint32_t)gap + (uint32_t)wrap_mul((int64_t)(n + m - 1), gap_extend));
-            } else if (!local) b->host_scores[k] = wrap_mul((int64_t)(n + m), gap);   // dp[n][0] / dp[0][m], hw2.cpp:125-136
-            any_trivial_score = any_trivial_score || b->host_scores[k] != 0;
-            if (b->want_end && !local) {
-                b->host_end_i[k] = (uint32_t)n;
-                b->host_end_j[k] = (uint32_t)m;
-            }
-            continue;
-        }
-        if (n > 0x7fffffc0ull || m > 0x7fffffc0ull) return fail(ctx, PWA_E_CAPACITY, "sequence longer than 2^31");
-        live[n_live++] = (uint32_t)k;
-        b->cells += n * m;
-        max_n = std::max(max_n, n);
-        max_m = std::max(max_m, m);
-    }
-    live.resize(n_live);
-    b->n_live = live.size();
-
+    LivePairs lp;
+    int rc = scan_pairs(ctx, b, in, lp);
+    if (rc != PWA_OK) return rc;
+    b->n_live = lp.live.size();
     HIPC(ctx, b->scores.alloc(std::max<uint64_t>(n_pairs, 1) * sizeof(int32_t)));
-    if (any_trivial_score) HIPC(ctx, upload_via_bounce(ctx, b->scores.p, b->host_scores.data(), n_pairs * sizeof(int32_t)));
+    if (lp.any_trivial_score) HIPC(ctx, upload_via_bounce(ctx, b->scores.p, b->host_scores.data(), n_pairs * sizeof(int32_t)));
     else {   // (on the copy stream and waited for: a run may be enqueued on any stream afterwards -- and the context's own stream may be
              // busy with the previous batch's run, which preparing this one must not wait for)
         HIPC(ctx, hipMemsetAsync(b->scores.p, 0, std::max<uint64_t>(n_pairs, 1) * sizeof(int32_t), ctx->copy_stream));
         HIPC(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
     HIPC(ctx, b->queue.alloc(64));   // (the event ring of the runs is created run by run: pwa_batch_run)
-    if (live.empty()) {
+    if (lp.live.empty()) {
         b->kernel_name = "none";
         guard.b = nullptr;
         *out = b;
         return PWA_OK;
     }
 
-    // ---- which sequences play which role; text alphabet
+    // ---- which sequences play which role; the alphabet, the cell form, the arena
     std::vector<uint8_t> is_text(n_seq, 0), is_used(n_seq, 0);
-    for (uint32_t k : live) {
+    for (uint32_t k : lp.live) {
         is_text[pair_b[k]] = 1;
         is_used[pair_a[k]] = is_used[pair_b[k]] = 1;
     }
-    bool present[256] = {false};
-    {
-        bool part[16][256] = {};
-        for_seq_ranges(seq_off, n_seq, [&](uint32_t s0, uint32_t s1, int t) {
-            bool* mine = part[t];
-            for (uint32_t s = s0; s < s1; ++s)
-                if (is_text[s])
-                    for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
-        });
-        for (int t = 0; t < 16; ++t)
-            for (int v = 0; v < 256; ++v) present[v] |= part[t][v];
-    }
-    // LANES kernels also pad TEXTS (columns past a lane's own text): that symbol must match no pattern symbol and
-    // must differ from the pattern pad, or padded rows would "match" padded columns.
-    bool pattern_has[256] = {false};
-    {
-        std::vector<uint8_t> is_pat(n_seq, 0);
-        for (uint64_t k = 0; k < n_pairs; ++k) is_pat[pair_a[k]] = 1;
-        bool part[16][256] = {};
-        for_seq_ranges(seq_off, n_seq, [&](uint32_t s0, uint32_t s1, int t) {
-            bool* mine = part[t];
-            for (uint32_t s = s0; s < s1; ++s)
-                if (is_pat[s])
-                    for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
-        });
-        for (int t = 0; t < 16; ++t)
-            for (int v = 0; v < 256; ++v) pattern_has[v] |= part[t][v];
-    }
-    // codes: the text symbols that patterns use first, then the text-only ones (an N in the texts does not push a pattern symbol
-    // past code 3, which the packed f16 cells need); symbols compare by equality only, so any order gives the same scores
-    int n_alpha = 0;
-    int code_of[256];
-    int absent_byte = -1;
-    for (int v = 0; v < 256; ++v) {
-        code_of[v] = -1;
-        if (!present[v] && absent_byte < 0) absent_byte = v;
-    }
-    for (int pass = 0; pass < 2; ++pass)
-        for (int v = 0; v < 256; ++v)
-            if (present[v] && pattern_has[v] == (pass == 0)) code_of[v] = n_alpha++;
-    int text_pad_byte = -1;   // raw-byte (SC_CMP) form; the coded (SC_PERM) form uses code 6 when the alphabet leaves it free
-    for (int v = 255; v >= 0 && text_pad_byte < 0; --v)
-        if (!pattern_has[v] && v != absent_byte) text_pad_byte = v;
+    const Alphabet al = scan_alphabet(in, is_text);
+    CellForm form;
+    if ((rc = choose_cell_form(ctx, in, lp, al, form)) != PWA_OK) return rc;
+    b->use_strips = form.strips;
+    b->aff_go = form.aff_go;
+    b->aff_ge = form.aff_ge;
+    b->aff_neg = form.aff_neg;
+    std::vector<uint64_t> aoff;
+    if ((rc = upload_arena(ctx, b, in, is_used, lp.max_n, form, al, aoff)) != PWA_OK) return rc;
+    clock.mark("validate + arena upload");
 
-    // ---- engine choice.  The strip engine pads short patterns with rows that match nothing; for SW
-    // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
-    const bool strips_ok = affine || nwdist || (!b->want_end && (!local || (mismatch <= 0 && gap <= 0)));
-    b->affine = affine;
-    b->nwdist = nwdist;
-    auto fits8 = [](int v) { return v >= -128 && v <= 127; };
-    b->use_strips = strips_ok;
-
-    // ---- device arena: every used sequence, 16-byte aligned, as symbols of the chosen coding
-    int score_path = SC_CMP;
-    int kmode = local ? BM_SW : BM_NW;
-    int tab_match = match, tab_mismatch = mismatch;
-    if (nwdist) {
-        kmode = BM_DIST;
-        tab_match = match - gap;       // the rows store H + gap: the diagonal consumer takes the gap back out
-        tab_mismatch = mismatch - gap;
-        if (n_alpha <= 7 && fits8(tab_match) && fits8(tab_mismatch)) score_path = SC_PERM;
-        if (score_path == SC_CMP && absent_byte < 0)
-            return fail(ctx, PWA_E_INVALID, "distance pass: the texts use all 256 byte values, no padding symbol left");
-        // packed (H, dist) keys: dist in 12 bits, H in the 18 above (batch_nwdist.hip.h)
-        const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
-                                                std::llabs((long long)gap)});
-        if (max_n + max_m <= 4000 && (int64_t)(max_n + max_m + 2) * amax < 65536 && !ctx->knobs.no_packed_dist) {
-            kmode = BM_DISTP;
-            tab_match = match;       // the packed kernel takes hw4's own three scores
-            tab_mismatch = mismatch;
-        }
-    } else if (affine) {
-        // Ge(i+j)-shifted form when every value stays far inside int32 (the sentinels are -2^29 there)
-        const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
-                                                std::llabs((long long)gap), std::llabs((long long)gap_extend)});
-        const bool shift_ok = (int64_t)(max_n + max_m + 4) * amax * 4 < (1ll << 27);
-        kmode = shift_ok ? BM_AFFS : BM_AFF;
-        b->aff_go = gap;
-        b->aff_ge = gap_extend;
-        b->aff_neg = shift_ok ? -(1 << 29) : std::numeric_limits<int32_t>::min() / 2;   // hw3.cpp:16
-        if (shift_ok) {
-            tab_match = match - 2 * gap_extend;
-            tab_mismatch = mismatch - 2 * gap_extend;
-        }
-        if (n_alpha <= 7 && fits8(tab_match) && fits8(tab_mismatch)) score_path = SC_PERM;
-        if (score_path == SC_CMP && absent_byte < 0)
-            return fail(ctx, PWA_E_INVALID, "affine pass: the texts use all 256 byte values, no padding symbol left");
-    } else if (b->use_strips) {
-        if (!local) {
-            // gap-shifted NW: G = H - g(i+j) needs every |value| to stay far inside int32
-            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
-                                                    std::llabs((long long)gap)});
-            const int64_t s_match = (int64_t)match - 2 * (int64_t)gap, s_mis = (int64_t)mismatch - 2 * (int64_t)gap;
-            if ((int64_t)(max_n + max_m + 4) * amax * 4 < (1ll << 30) && fits8((int)s_match) && fits8((int)s_mis)) {
-                kmode = BM_NWG;
-                tab_match = (int)s_match;
-                tab_mismatch = (int)s_mis;
-            }
-        }
-        if (n_alpha <= 7 && fits8(tab_match) && fits8(tab_mismatch)) score_path = SC_PERM;
-        else if (kmode == BM_NWG && n_alpha > 7) { /* compare path works in G space too */ }
-        if (score_path == SC_CMP && absent_byte < 0) b->use_strips = false;   // no byte left to pad with
-    }
-
-    std::vector<uint64_t> aoff(n_seq, 0);
-    uint64_t arena_bytes = 0;
-    for (uint32_t s = 0; s < n_seq; ++s)
-        if (is_used[s]) {
-            aoff[s] = arena_bytes;
-            arena_bytes += align_up(slen(s) + 1, 16);
-        }
-    arena_bytes += 512;   // slack: strips and text words are over-read, never over-used
-    // (a strip task loads its lanes' pattern words for every strip of its LONGEST pattern and masks them after the load: a short pattern
-    // is read up to that length past its start -- past the end of the arena when it lies last, which faulted on the device)
-    if (b->use_strips) arena_bytes += align_up(max_n, 16);
-    if (arena_bytes >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "sequence arena exceeds 4 GiB");
-    // (a scores pass that wants end cells runs wholly off the strips: its arena is coded whenever the alphabet allows, for the mini-stripe
-    // kernels -- the stripe engine's compare form is the same on codes, a pattern-only symbol is code 7 and equals no text code)
-    const bool code_for_end_cells = b->want_end && !affine && !nwdist && n_alpha <= 7 && ctx->knobs.tb_engine != 0;
-    const bool arena_coded = (b->use_strips && score_path == SC_PERM) || code_for_end_cells;
-    // Short patterns that a scores pass routes away from the strips run on the mini-stripe engine WITHOUT a band (mini_fill.hip.h,
-    // BAND = false: four pairs per wave) where it applies: coded arena, keyed cells in range, table constants in a byte.
-    bool mini_scores = false, mini_gap0 = false;
-    if (arena_coded && !affine && !nwdist && ctx->knobs.tb_engine != 0 && tb_range_ok(max_n + max_m, match, mismatch, gap, local ? 26 : 28)) {
-        const int64_t kdm = ((int64_t)match - gap) * 4 + 2, kdx = ((int64_t)mismatch - gap) * 4 + 2;
-        mini_scores = kdm <= 127 && kdm >= -126 && kdx <= 127 && kdx >= -126;
-        if (mini_scores && !local) {
-            const int64_t km = ((int64_t)match - 2 * (int64_t)gap) * 4 + 1, kx = ((int64_t)mismatch - 2 * (int64_t)gap) * 4 + 1;
-            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap), 1});
-            mini_gap0 = km <= 127 && km >= -126 && kx <= 127 && kx >= -126 && (max_n + max_m + 2) <= (1ull << 27) / (uint64_t)amax;
-        }
-    }
-    auto mini_rl_of = [&](uint64_t n) -> int {   // rows per lane of the mini-stripe class that holds an n-row pattern, 0: none
-        if (mini_scores && n <= 256)
-            for (const int rl : kMiniRL)
-                if (n <= (uint64_t)(16 * rl)) return rl;
-        return 0;
-    };
-    {
-        const bool coded = arena_coded;
-        uint8_t code8[256];
-        for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)(code_of[v] >= 0 ? code_of[v] : 7);
-        HIPC(ctx, b->arena.alloc(arena_bytes));
-        HIPC(ctx, build_arena(ctx, b->arena.p, arena_bytes, seq_bytes, seq_off, n_seq, is_used, aoff, coded ? code8 : nullptr,
-                              !present[0] && !pattern_has[0]));
-    }
-
-    mark("validate + arena upload");
     b->padded_cells = 0;
-    std::vector<uint32_t> live_pairs_engine;   // the pairs that run on the stripe engine (all of them when the strips cannot serve the list)
-    if (!b->use_strips) live_pairs_engine = live;
+    std::vector<uint32_t> off_strips;   // the pairs that run off the strips (all of them when the strips cannot serve the list)
+    if (!b->use_strips) off_strips = lp.live;
     if (b->use_strips) {
-        // ---- wave tasks: pairs grouped by text, patterns sorted by length, 64 per wave
-        std::vector<uint32_t> order(live);   // ascending pair index: the stable sorts below keep it as the last key
-        {
-            // text ascending, pattern length descending.  Stable counting sorts, least significant key first: two linear passes
-            // per key, and the length pass is skipped when every pattern has the same length (a million-pair cross product:
-            // ~3 ms [gpu box] against 14 ms for the 64-bit radix sort, which stays as the fallback for huge key ranges)
-            uint64_t lmin = ~0ull, lmax = 0;
-            for (const uint32_t k : order) {
-                const uint64_t l = slen(pair_a[k]);
-                lmin = std::min(lmin, l);
-                lmax = std::max(lmax, l);
-            }
-            // (the histograms have n_seq + 1 and lmax - lmin + 1 entries whatever the list's size: a short list over a large
-            // FASTA index, or with one outlier length, is cheaper through the radix sort)
-            if (lmax - lmin < (1u << 22) && n_seq <= (1u << 24) && (uint64_t)n_seq <= 4 * (uint64_t)order.size() + 65536 &&
-                lmax - lmin <= 4 * (uint64_t)order.size() + 65536) {
-                std::vector<uint32_t> tmp;
-                if (lmax != lmin) counting_sort(order, tmp, (size_t)(lmax - lmin + 1), [&](uint32_t k) { return (size_t)(lmax - slen(pair_a[k])); });
-                counting_sort(order, tmp, (size_t)n_seq, [&](uint32_t k) { return (size_t)pair_b[k]; });
-            } else {
-                std::vector<uint64_t> key(order.size());   // text ascending, pattern length descending (lengths < 2^31)
-                for (size_t o = 0; o < order.size(); ++o)
-                    key[o] = ((uint64_t)pair_b[order[o]] << 32) | (uint64_t)(0x7fffffffu - (uint32_t)slen(pair_a[order[o]]));
-                radix_sort_by_key(key, order);
+        StripTasks st = plan_strip_tasks(ctx, in, lp.live, form, al);
+        b->lanes = st.lanes;
+        clock.mark("sort + group pairs");
+        StripHeight h = choose_strip_height(st.ht, form, st.lanes, false, ctx->knobs);
+        if (h.R == 0) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
+        if (cell16_admitted(ctx->knobs, in, form, al, st.lanes, lp.max_n)) {
+            std::vector<HostTask> ht16 = group_by_text(in, st.order, 128);
+            const StripHeight h16 = choose_strip_height(ht16, form, st.lanes, true, ctx->knobs);
+            if (h16.R != 0 && (ctx->knobs.cell16 == 1 || h16.cost < h.cost)) {
+                b->cell16 = true;
+                st.ht.swap(ht16);
+                h = h16;
             }
         }
-        struct HostTask {
-            uint32_t text, first, count;
-            uint64_t maxlen;   // longest pattern of the task
-            uint64_t m;        // text length (LANES: the longest text of the task)
-        };
-        auto group_by_text = [&](size_t lanes_per_task) {   // up to lanes_per_task patterns of one text per wave task
-            std::vector<HostTask> g;
-            for (size_t p = 0; p < order.size();) {
-                size_t q = p;
-                while (q < order.size() && q - p < lanes_per_task && pair_b[order[q]] == pair_b[order[p]]) ++q;
-                g.push_back({pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), slen(pair_a[order[p]]), slen(pair_b[order[p]])});
-                p = q;
-            }
-            return g;
-        };
-        std::vector<HostTask> ht = group_by_text(64);
-        // ---- lists whose pairs share few texts (the reference's own loop pairs pattern i with reference i,
-        // hw2.cpp:328-338) would leave most lanes of a text-grouped wave empty: give every lane its own text
-        // instead (LANES kernels, local alignment only).  Pairs are sorted so that a wave's 64 pairs need about
-        // the same number of strips and columns; a wave runs max(strips) x max(columns) of its lanes.
-        bool kernels_have_lanes = false;
-        size_t n_kernels = 0;
-        const BatchKernelEntry* const kernels = batch_kernel_table(&n_kernels);
-        for (size_t ki = 0; ki < n_kernels; ++ki) kernels_have_lanes |= (kernels[ki].fn_lanes != nullptr && kernels[ki].score == score_path);
-        const bool text_pad_ok = score_path == SC_PERM ? n_alpha <= 6 : text_pad_byte >= 0;
-        const bool underfilled = ht.size() * 64 > order.size() * 3 / 2 + 64;
-        b->lanes = kmode == BM_SW && !affine && !nwdist && kernels_have_lanes && text_pad_ok && underfilled &&
-                   ctx->knobs.paired < 0;   // (the opt-in experiment wins)
-        // global alignment: right-aligned texts, front-padded with a code the table scores like a gap (batch_scores.hip.h).
-        // Needs the gap-shifted form, a coded alphabet with codes 4..7 free, every pattern symbol inside it (a
-        // pattern-only symbol shares code 7 with the pad rows), g <= 0 and -g in a table byte.
-        bool patterns_inside = true;
-        for (int v = 0; v < 256; ++v) patterns_inside = patterns_inside && (!pattern_has[v] || present[v]);
-        const bool lanes_nw = kmode == BM_NWG && !affine && !nwdist && score_path == SC_PERM && n_alpha <= 4 && patterns_inside &&
-                              gap <= 0 && fits8(-gap) && underfilled;
-        b->lanes = b->lanes || lanes_nw;
-        if (ctx->knobs.force_lanes >= 0) b->lanes = b->lanes && ctx->knobs.force_lanes != 0;   // experiments only
-        if (b->lanes) {
-            order = live;
-            std::vector<uint64_t> key(order.size());   // nominal strips descending, then text length descending
-            for (size_t o = 0; o < order.size(); ++o) {
-                const uint64_t strips = (slen(pair_a[order[o]]) + 75) / 76;
-                key[o] = ((0x7fffffffull - strips) << 32) | (uint64_t)(0x7fffffffu - (uint32_t)slen(pair_b[order[o]]));
-            }
-            radix_sort_by_key(key, order);
-            ht.clear();
-            for (size_t p = 0; p < order.size(); p += 64) {
-                const size_t q = std::min(order.size(), p + 64);
-                uint64_t mn = 0, mm = 0;
-                for (size_t o = p; o < q; ++o) {
-                    mn = std::max(mn, slen(pair_a[order[o]]));
-                    mm = std::max(mm, slen(pair_b[order[o]]));
-                }
-                ht.push_back({pair_b[order[p]], (uint32_t)p, (uint32_t)(q - p), mn, mm});
+        if (route_eligible(in, form, lp.max_n, lp.max_m) && ctx->knobs.scores_route != 0) {
+            const std::vector<uint32_t> move = tasks_to_move(ctx, in, st, h.R, b->cell16 ? 128 : 64, route_cost(in, form, b->cell16, h.mode), form.mini_scores);
+            if (!move.empty()) {
+                off_strips = split_tasks(st, move);
+                if (!st.ht.empty()) h = choose_strip_height(st.ht, form, st.lanes, b->cell16, ctx->knobs);   // the strips that stay may prefer another height
             }
         }
-        mark("sort + group pairs");
-        // ---- strip height: least padded work, ties to the taller strip
-        int bestR = 0, best_mode = kmode;
-        const int kmode_asked = kmode;
-        // c16: the packed f16 form (two pairs per lane, 128-slot tasks), priced per lane row at kCell16Vpr VALU for both pairs
-        auto choose_strip_height = [&](const std::vector<HostTask>& tl, bool c16) -> long double {
-        bestR = 0;
-        best_mode = kmode_asked;
-        long double best_cost = -1;
-        const int force = ctx->knobs.force_r, force_mode = ctx->knobs.force_mode;   // experiments only
-        for (size_t ki = 0; ki < n_kernels; ++ki) {
-            const BatchKernelEntry& e = kernels[ki];
-            // SW has two forms: BM_SW (R registers per lane, 5.0 VALU per cell) and BM_SWS (2R registers, 4.06)
-            const bool mode_ok = e.mode == kmode_asked || (kmode_asked == BM_SW && e.mode == BM_SWS);
-            if (!mode_ok || e.score != score_path) continue;
-            if (b->lanes && !e.fn_lanes) continue;
-            if (c16 && !e.fn_cell16) continue;
-            const int R = e.R;
-            if (force && force != R) continue;
-            if (force_mode >= 0 && force_mode != e.mode) continue;
-            long double w = c16 ? (long double)kCell16Vpr : e.mode == BM_SWS ? 4.06L : (e.mode == BM_SW ? 5.02L : 1.0L);   // VALU per lane row
-            // affine strips of more than 40 rows run 2 instead of 3 waves per SIMD: [gpu] all pairs of 1024 x 1000 take
-            // 93.2 ms at R = 52 against 89.2 ms at R = 32 for the same padded cells
-            if ((e.mode == BM_AFF || e.mode == BM_AFFS) && R > 40) w *= 1.045L;
-            // evaluated cells + the strip hand-off priced at ~2 cells per column and strip boundary ([gpu]: the
-            // 1000-row affine pass is equally fast at R = 32 and 52 but moves 37 % fewer HBM bytes at 52)
-            long double cost = 0;
-            for (const auto& t : tl) {
-                const uint64_t strips = (t.maxlen + R - 1) / R;
-                cost += (long double)(strips * R + 2 * (strips - 1)) * (long double)t.m * 64.0L;
-            }
-            cost *= w;
-            if (best_cost < 0 || cost < best_cost || (cost == best_cost && R > bestR)) {
-                best_cost = cost;
-                bestR = R;
-                best_mode = e.mode;
-            }
-        }
-        return best_cost;
-        };
-        const long double cost32 = choose_strip_height(ht, false);
-        if (bestR == 0) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
-        // ---- packed f16 cells (batch_scores.hip.h, CELL16): local scores over a coded arena whose pattern symbols all have codes 0..3,
-        // pad rules of the int32 strips (mismatch, gap <= 0), scores in a byte, and every value k * 2^-11 with |k| <= 2047 exact in f16:
-        // H <= longest pattern * max(match, 0) bounds all of them.  Everything else keeps the int32 kernels, bit for bit.
-        {
-            bool pats_low = true;
-            for (int v = 0; v < 256; ++v) pats_low = pats_low && (!pattern_has[v] || (present[v] && code_of[v] <= 3));
-            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap)});
-            const bool cell16_ok = local && kmode_asked == BM_SW && !affine && !nwdist && score_path == SC_PERM && !b->lanes && pats_low &&
-                                   mismatch <= 0 && gap <= 0 && amax <= 127 && (int64_t)max_n * std::max(match, 0) <= 2047 &&
-                                   ctx->knobs.cell16 != 0 && ctx->knobs.paired < 0 && (ctx->knobs.force_mode < 0 || ctx->knobs.force_mode == BM_SWS);
-            if (cell16_ok) {
-                const int R32 = bestR, mode32 = best_mode;
-                std::vector<HostTask> ht16 = group_by_text(128);
-                const long double cost16 = choose_strip_height(ht16, true);
-                if (bestR != 0 && (ctx->knobs.cell16 == 1 || cost16 < cost32)) {
-                    b->cell16 = true;
-                    ht.swap(ht16);
-                } else {
-                    bestR = R32;
-                    best_mode = mode32;
-                }
-            }
-        }
-        const uint64_t kTaskLanes = b->cell16 ? 128 : 64;   // lane slots per wave task
-
-        // ---- work-aware routing (r03).  The strip engine is the cheaper one per cell (lane = pair, 2.5 - 5 VALU per cell) but a wave
-        // task is one wave running strips x columns on its own: a list of few long pairs -- ONE 10k x 10k pair is 105 strips x 2500
-        // column blocks x 1560 instructions on one lane of one wave, [gpu] 779 ms against 1.67 ms on the stripe engine -- or of few
-        // wave tasks (4096 pairs 150 x 10k = 64 tasks: 11.6 ms against 4.3 ms) leaves the chip idle.  The stripe engine spreads a
-        // pair over ceil(n / (64 RL)) waves that sweep anti-diagonals (~100 ns per step of 64 RL cells per SIMD).  Both costs are
-        // estimated from the task list with constants measured on the GPU (profiles/r03_route_probe.txt), tasks are moved to the
-        // stripe engine in two candidate orders (largest strip task first; cheapest-to-move per unit of strip work first) and
-        // the split with the smallest estimated total -- the two launches run one after the other on the run's stream -- wins.
-        // Pairs are independent (hw2.cpp:328-338) and both engines are exact, so a split changes no result.
-        std::vector<uint32_t> pair_list;   // pair indices routed to the stripe engine
-        // hw4 distances take the same split when the batch is in the two-value form (some n + m > 4000, or PWA_NO_PACKED_DIST): coded arena,
-        // keys H * 4 + prio inside int32 (pair_dist.hip.h).  Packed-form lists, other byte alphabets and larger scores stay on the strips.
-        bool dist_route = false;
-        if (nwdist && kmode == BM_DIST && score_path == SC_PERM) {
-            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap), 1});
-            dist_route = (int64_t)(max_n + max_m + 2) * amax < (1ll << 28);
-        }
-        // hw3 affine scores likewise: coded arena, every real value inside +-2^28 so that the -2^29 sentinels never win (pair_affine.hip.h).
-        // Raw-byte alphabets and scorings large enough for the reference's own wrap-around to matter stay on the strips.
-        bool aff_route = false;
-        if (affine && score_path == SC_PERM) {
-            const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch),
-                                                    std::llabs((long long)gap) + std::llabs((long long)gap_extend), 1});
-            aff_route = (int64_t)(max_n + max_m + 2) * amax < (1ll << 28);
-        }
-        if (((!affine && !nwdist) || dist_route || aff_route) && ctx->knobs.scores_route != 0) {
-            const size_t nt0 = ht.size();
-            // (affine strips: 5.6 VALU per cell, PMC of profiles/r03_hw3_rocprof_summary.md)
-            const double vpc = nwdist ? 10.75 : affine ? 5.6 : b->cell16 ? kCell16Vpr : (best_mode == BM_SWS ? 4.06 : best_mode == BM_SW ? 5.02 : best_mode == BM_NWG ? 2.53 : 4.5) + (score_path == SC_CMP ? 2.0 : 0.0);
-            constexpr double kLoneNs = 1.9, kSimdNs = 1.63;                                 // ns per wave instruction: one wave alone / a SIMD with two
-            const double kSimds = nwdist || affine ? 4.0 * ctx->num_cu : 1024.0;
-            // stripe engine: per step and SIMD; per stripe of pipeline lag; per step of a pair alone -- the keyed chunk without a band (coded
-            // arena, keys in range) or the plain step ([gpu] r03_route_probe.txt: one 10k x 10k pair 1.26 / 1.01 ms, 64 pairs 3.45 / 2.05 ms);
-            // the distance fill (profiles/hw4_long_route_probe.txt); the affine fill (profiles/hw3_long_route_probe.txt)
-            const double step_ns = nwdist ? kDistStepNs : affine ? kAffStepNs : mini_scores ? (local ? 70.0 : 42.0) : (local ? 105.0 : 75.0),
-                         lag_us = nwdist ? kDistLagUs : affine ? kAffLagUs : 9.0,
-                         lone_step_ns = nwdist ? kDistLoneStepNs : affine ? kAffLoneStepNs : mini_scores ? (local ? 55.0 : 30.0) : 100.0;
-            std::vector<double> I(nt0), S(nt0), L(nt0);   // strip instructions / stripe-side work (ns x SIMD) / longest single-pair latency (us) of a task
-            double I_total = 0, I_max = 0;
-            uint64_t filled = 0;
-            for (size_t t = 0; t < nt0; ++t) {
-                const uint64_t strips = (ht[t].maxlen + bestR - 1) / bestR;
-                I[t] = (double)strips * (double)((ht[t].m + 3) / 4) * (4.0 * bestR * vpc);
-                I_total += I[t];
-                I_max = std::max(I_max, I[t]);
-                filled += ht[t].count;
-            }
-            // nothing to route when the strips' waves are many, full, and none of them dominates: per cell the strips are the cheapest engine
-            // by 2x and more, so no task can gain by leaving (and the per-pair estimates below cost ~3 ms for a million pairs)
-            const bool strips_fit = nt0 >= 4096 && filled * 10 >= (uint64_t)nt0 * kTaskLanes * 9 && I_max * kLoneNs * 4 < I_total / kSimds * kSimdNs &&
-                                    ctx->knobs.scores_route < 0;
-            for (size_t t = 0; t < nt0 && !strips_fit; ++t) {
-                double steps = 0, lat = 0;
-                for (uint32_t l = 0; l < ht[t].count; ++l) {
-                    const uint32_t k = order[ht[t].first + l];
-                    const uint64_t n = slen(pair_a[k]), m = slen(pair_b[k]);
-                    if (const int mrl = mini_rl_of(n)) {   // mini-stripe engine, no band: a quarter of a wave, (17 + 5 | 7.3 RL) instructions per step
-                        const double mstep = (17.0 + (local ? 7.3 : 5.0) * mrl) * 1.37;   // [gpu] 92 ns per step for RL = 10, global (tools/probes/mini_mix.hip)
-                        steps += (double)(m + 15) * mstep / 4.0 / 1.5;                    // (two waves per SIMD: ~1.9 x one wave's throughput)
-                        lat = std::max(lat, (double)(m + 15) * mstep * 1e-3);
-                        continue;
-                    }
-                    const PairGeom g = choose_geom(ctx->knobs, n);
-                    const double stripes = (double)((n + 64 * g.rl - 1) / (64 * g.rl));
-                    steps += stripes * (double)(m + 63) * step_ns;
-                    lat = std::max(lat, stripes * lag_us + (double)(m + 63) * lone_step_ns * 1e-3);
-                }
-                S[t] = steps;
-                L[t] = lat;
-            }
-            auto evaluate = [&](const std::vector<uint32_t>& ord, size_t& best_k) -> double {
-                // tasks ord[0 .. k-1] move; suffix maxima of I over the tasks that stay
-                std::vector<double> sufmax(nt0 + 1, 0.0);
-                for (size_t k = nt0; k-- > 0;) sufmax[k] = std::max(sufmax[k + 1], I[ord[k]]);
-                double best_t = -1, moved_I = 0, moved_S = 0, moved_L = 0;
-                for (size_t k = 0; k <= nt0; ++k) {
-                    const double ts = std::max(sufmax[k] * kLoneNs, (I_total - moved_I) / kSimds * kSimdNs) * 1e-3;              // us
-                    const double tp = k ? std::max(moved_L, moved_S / kSimds * 1e-3) + 15.0 : 0.0;                                 // us (+ two more launches)
-                    const double tt = ts + tp;
-                    if (best_t < 0 || tt < best_t) {
-                        best_t = tt;
-                        best_k = k;
-                    }
-                    if (k < nt0) {
-                        moved_I += I[ord[k]];
-                        moved_S += S[ord[k]];
-                        moved_L = std::max(moved_L, L[ord[k]]);
-                    }
-                }
-                return best_t;
-            };
-            std::vector<uint32_t> ordA(nt0), ordB(nt0);
-            std::iota(ordA.begin(), ordA.end(), 0u);
-            ordB = ordA;
-            if (!strips_fit) {
-                std::stable_sort(ordA.begin(), ordA.end(), [&](uint32_t x, uint32_t y) { return I[x] > I[y]; });
-                std::stable_sort(ordB.begin(), ordB.end(), [&](uint32_t x, uint32_t y) { return S[x] * I[y] < S[y] * I[x]; });   // S / I ascending
-            }
-            size_t kA = 0, kB = 0;
-            const double tA = strips_fit ? 0.0 : evaluate(ordA, kA), tB = strips_fit ? 0.0 : evaluate(ordB, kB);
-            const std::vector<uint32_t>& ord = tA <= tB ? ordA : ordB;
-            size_t kmove = strips_fit ? 0 : (tA <= tB ? kA : kB);
-            if (ctx->knobs.scores_route == 1) kmove = nt0;   // tests: everything (eligible) on the stripe engine
-            if (dbg) std::fprintf(stderr, "[pwa] route: %zu of %zu wave tasks to the stripe engine (estimates: all on strips %.1f us, split %.1f us)\n",
-                                  kmove, nt0, std::max(*std::max_element(I.begin(), I.end()) * kLoneNs, I_total / kSimds * kSimdNs) * 1e-3, std::min(tA, tB));
-            if (kmove) {
-                std::vector<uint8_t> moved(nt0, 0);
-                for (size_t k = 0; k < kmove; ++k) moved[ord[k]] = 1;
-                std::vector<HostTask> keep;
-                for (size_t t = 0; t < nt0; ++t) {
-                    if (!moved[t]) {
-                        keep.push_back(ht[t]);
-                        continue;
-                    }
-                    for (uint32_t l = 0; l < ht[t].count; ++l) pair_list.push_back(order[ht[t].first + l]);
-                }
-                ht.swap(keep);
-                std::sort(pair_list.begin(), pair_list.end());
-                if (!ht.empty()) choose_strip_height(ht, b->cell16);   // the strips that stay may prefer another height
-            }
-        }
-        if (ht.empty()) b->use_strips = false;
-        live_pairs_engine.swap(pair_list);
-      if (b->use_strips) {
-        kmode = best_mode;
-        const int R = bestR;
-        for (const auto& t : ht) b->padded_cells += (t.maxlen + bestR - 1) / bestR * bestR * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
-        b->kern = find_batch_kernel(R, kmode, score_path);
-        if (!b->kern) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
-        b->kernel_name = b->kern->name;
-        std::sort(ht.begin(), ht.end(), [&](const HostTask& x, const HostTask& y) {   // longest first
-            const uint64_t cx = (x.maxlen + R - 1) / R * x.m, cy = (y.maxlen + R - 1) / R * y.m;
-            if (cx != cy) return cx > cy;
-            return x.first < y.first;
-        });
-        const size_t nt = ht.size();
-        // task list and lane slots are built in page-locked buffers of the context and uploaded from there (see PinnedBuf)
-        HIPC(ctx, ctx->pin[pwa_ctx::PIN_TASKS].reserve(nt * sizeof(BatchTask)));
-        for (int q = 0; q < (b->lanes ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * kTaskLanes * sizeof(uint32_t)));
-        BatchTask* const tasks = ctx->pin[pwa_ctx::PIN_TASKS].as<BatchTask>();
-        uint32_t* const spoff = ctx->pin[pwa_ctx::PIN_SLOT0].as<uint32_t>();
-        uint32_t* const splen = ctx->pin[pwa_ctx::PIN_SLOT1].as<uint32_t>();
-        uint32_t* const sout = ctx->pin[pwa_ctx::PIN_SLOT2].as<uint32_t>();
-        uint32_t* const stoff = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT3].as<uint32_t>() : nullptr;   // empty lanes: no text, no pattern
-        uint32_t* const stlen = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT4].as<uint32_t>() : nullptr;
-        std::memset(tasks, 0, nt * sizeof(BatchTask));
-        std::memset(spoff, 0, nt * kTaskLanes * sizeof(uint32_t));
-        std::memset(splen, 0, nt * kTaskLanes * sizeof(uint32_t));
-        std::memset(sout, 0xff, nt * kTaskLanes * sizeof(uint32_t));
-        if (b->lanes) {
-            std::memset(stoff, 0, nt * kTaskLanes * sizeof(uint32_t));
-            std::memset(stlen, 0, nt * kTaskLanes * sizeof(uint32_t));
-        }
-        uint32_t max_strips = 1;
-        size_t two_strip_tasks = 0;
-        {   // (a million slots through three indirections each: on a few threads for long task lists)
-            const int T = (int)std::max<size_t>(1, std::min<size_t>({8, std::max(1u, std::thread::hardware_concurrency()), nt >> 11}));
-            std::vector<uint32_t> part_max((size_t)T, 1);
-            std::vector<size_t> part_two((size_t)T, 0);
-            auto work = [&](int th) {
-                const size_t a = nt * (size_t)th / (size_t)T, z = nt * (size_t)(th + 1) / (size_t)T;
-                for (size_t t = a; t < z; ++t) {
-                    tasks[t].text_off = (uint32_t)aoff[ht[t].text];
-                    tasks[t].text_len = (uint32_t)ht[t].m;
-                    tasks[t].slot0 = (uint32_t)(t * kTaskLanes);
-                    tasks[t].n_strips = (uint32_t)((ht[t].maxlen + R - 1) / R);
-                    part_max[(size_t)th] = std::max(part_max[(size_t)th], tasks[t].n_strips);
-                    part_two[(size_t)th] += tasks[t].n_strips == 2;
-                    for (uint32_t l = 0; l < ht[t].count; ++l) {
-                        const uint32_t k = order[ht[t].first + l];
-                        spoff[t * kTaskLanes + l] = (uint32_t)aoff[pair_a[k]];
-                        splen[t * kTaskLanes + l] = (uint32_t)slen(pair_a[k]);
-                        sout[t * kTaskLanes + l] = k;
-                        if (b->lanes) {
-                            stoff[t * kTaskLanes + l] = (uint32_t)aoff[pair_b[k]];
-                            stlen[t * kTaskLanes + l] = (uint32_t)slen(pair_b[k]);
-                        }
-                    }
-                }
-            };
-            std::vector<std::thread> pool;
-            for (int th = 1; th < T; ++th) pool.emplace_back(work, th);
-            work(0);
-            for (auto& x : pool) x.join();
-            for (int th = 0; th < T; ++th) {
-                max_strips = std::max(max_strips, part_max[(size_t)th]);
-                two_strip_tasks += part_two[(size_t)th];
-            }
-        }
-        if (b->lanes && kmode == BM_NWG) {
-            // right-aligned, front-padded (code 4) text rows: task t, lane l at t_base + l * M_t, M_t = 4 * ceil(max m / 4)
-            uint64_t total = 0;
-            std::vector<uint64_t> tbase(nt);
-            for (size_t t = 0; t < nt; ++t) {
-                tbase[t] = total;
-                total += 64ull * ((ht[t].m + 3) / 4 * 4);
-            }
-            if (total + 64 >= (ctx->knobs.lane_rows_limit ? ctx->knobs.lane_rows_limit : 0xffffffffull))
-                return fail(ctx, PWA_E_CAPACITY, "per-lane text rows exceed 4 GiB");   // (one-shot calls halve the run and retry)
-            // The rows are built straight in the context's two page-locked arena buffers, in pieces of whole tasks (~32 MiB), by several host
-            // threads, while the previous piece is on its way (copy stream) -- like build_arena.  (Until r03: one thread, byte by byte into a
-            // heap buffer, then through the bounce buffer: 156 ms of a 159 ms call for 131 072 pairs 150 x 2000.)
-            HIPC(ctx, b->lane_text.alloc(total + 64));
-            uint8_t code8[256];
-            for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)code_of[v];
-            constexpr uint64_t kPiece = 32ull << 20;
-            auto task_end = [&](size_t t) { return t + 1 < nt ? tbase[t + 1] : total + 64; };   // (the slack after the last task is pad as well)
-            int piece = 0;
-            for (size_t t0 = 0; t0 < nt; ++piece) {
-                size_t t1 = t0 + 1;
-                while (t1 < nt && task_end(t1) - tbase[t0] <= kPiece) ++t1;
-                const uint64_t base = tbase[t0], bytes = task_end(t1 - 1) - base;
-                PinnedBuf& pb = ctx->pin[pwa_ctx::PIN_ARENA + (piece & 1)];
-                if (piece >= 2) HIPC(ctx, hipEventSynchronize(ctx->copy_ev[piece & 1]));   // the copy that last read this buffer
-                HIPC(ctx, pb.reserve(bytes));
-                uint8_t* const host = pb.as<uint8_t>();
-                const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>({16, bytes / (1ull << 20) + 1, std::max(1u, std::thread::hardware_concurrency()), (uint64_t)(t1 - t0)}));
-                auto work = [&](int th) {
-                    const size_t a = t0 + (t1 - t0) * (size_t)th / (size_t)T, z = t0 + (t1 - t0) * (size_t)(th + 1) / (size_t)T;
-                    for (size_t t = a; t < z; ++t) {
-                        const uint64_t M = (ht[t].m + 3) / 4 * 4;
-                        std::memset(host + (tbase[t] - base), 4, task_end(t) - tbase[t]);
-                        tasks[t].text_len = (uint32_t)M;
-                        for (uint32_t l = 0; l < ht[t].count; ++l) {
-                            const uint32_t k = order[ht[t].first + l];
-                            const uint8_t* src = seq_bytes + seq_off[pair_b[k]];
-                            const uint64_t len = slen(pair_b[k]);
-                            uint8_t* dst = host + (tbase[t] - base) + (uint64_t)l * M + (M - len);
-                            for (uint64_t o = 0; o < len; ++o) dst[o] = code8[src[o]];
-                            stoff[t * 64 + l] = (uint32_t)(tbase[t] + (uint64_t)l * M);
-                        }
-                    }
-                };
-                std::vector<std::thread> pool;
-                for (int th = 1; th < T; ++th) pool.emplace_back(work, th);
-                work(0);
-                for (auto& x : pool) x.join();
-                HIPC(ctx, hipMemcpyAsync(b->lane_text.as<uint8_t>() + base, host, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-                HIPC(ctx, hipEventRecord(ctx->copy_ev[piece & 1], ctx->copy_stream));
-                t0 = t1;
-            }
-            HIPC(ctx, hipStreamSynchronize(ctx->copy_stream));
-        }
-        if (b->lanes) {
-            HIPC(ctx, b->slot_toff.alloc(nt * 64 * 4));
-            HIPC(ctx, hipMemcpy(b->slot_toff.p, stoff, nt * 64 * 4, hipMemcpyHostToDevice));
-            HIPC(ctx, b->slot_tlen.alloc(nt * 64 * 4));
-            HIPC(ctx, hipMemcpy(b->slot_tlen.p, stlen, nt * 64 * 4, hipMemcpyHostToDevice));
-        }
-        mark("choose R + slot arrays");
-        HIPC(ctx, b->tasks.alloc(nt * sizeof(BatchTask)));
-        HIPC(ctx, hipMemcpy(b->tasks.p, tasks, nt * sizeof(BatchTask), hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_poff.alloc(nt * kTaskLanes * 4));
-        HIPC(ctx, hipMemcpy(b->slot_poff.p, spoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_plen.alloc(nt * kTaskLanes * 4));
-        HIPC(ctx, hipMemcpy(b->slot_plen.p, splen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_out.alloc(nt * kTaskLanes * 4));
-        HIPC(ctx, hipMemcpy(b->slot_out.p, sout, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-
-        b->single_strip = !affine && !nwdist && max_strips == 1 && b->kern->fn_single != nullptr;
-        // Opt-in (PWA_PAIRED=1): two-strip tasks (the C3 shape: 150-row patterns in 76-row strips) as two waves of one
-        // workgroup that pass the boundary row through an LDS ring instead of HBM.  It removes the hand-off traffic
-        // (84 GB per C3 launch -> none) but couples the two waves' progress: [gpu] 172.5 ms against 161.9 ms for the
-        // HBM hand-off form, which already runs at the VALU issue limit -- hence not the default.
-        b->paired = false;
-        if (ctx->knobs.paired >= 0)
-            b->paired = ctx->knobs.paired != 0 && !affine && !nwdist && max_strips == 2 && b->kern->fn_pair != nullptr &&
-                        two_strip_tasks * 8 >= nt * 7;   // at most 1 task in 8 may leave the second wave idle
-        if (b->lanes) {
-            b->paired = false;
-            b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
-        }
-        const void* kfn = b->cell16       ? reinterpret_cast<const void*>(max_strips == 1 ? b->kern->fn_cell16_single : b->kern->fn_cell16)
-                          : b->lanes      ? reinterpret_cast<const void*>(max_strips == 1 ? b->kern->fn_lanes_single : b->kern->fn_lanes)
-                          : b->single_strip ? reinterpret_cast<const void*>(b->kern->fn_single)
-                          : b->paired     ? reinterpret_cast<const void*>(b->kern->fn_pair)
-                          : nwdist        ? reinterpret_cast<const void*>(b->kern->dfn)
-                                 : (affine ? reinterpret_cast<const void*>(b->kern->afn) : reinterpret_cast<const void*>(b->kern->fn));
-        if (b->paired) b->kernel_name = std::string("batch_scores_pair_kernel") + (b->kernel_name.c_str() + std::strlen("batch_scores_kernel"));
-        int per_cu = 0;
-        HIPC(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, b->paired ? 128 : 64, 0));
-        per_cu = std::max(1, std::min(per_cu, 32));
-        b->grid = (uint32_t)std::min<uint64_t>(nt, (uint64_t)ctx->num_cu * per_cu);
-        // int32 per half: one (affine: two) int4 per lane per 4-column block
-        const int hand_vals = (affine || (nwdist && kmode != BM_DISTP)) ? 2 : 1;   // int4 per lane per 4-column block
-        const uint64_t half = ((max_strips > 1 && !b->paired) ? ((max_m + 3) / 4 + 1) * 256 : 256) * hand_vals;
-        // Strip s reads the half written by strip s-1 and writes the other one.  With at most two strips per task
-        // the second half is only ever the parked dummy block (stride 0), so it is one block long: for C3 that
-        // turns a 10.5 GB workspace (0.24 s of hipMalloc, profiles/r01_malloc_probe.txt) into 5.2 GB (0.3 ms).
-        const uint64_t block_ints = 256 * hand_vals;
-        const uint64_t second = (max_strips > 2 || b->paired) ? half : block_ints;
-        {   // very long texts: fewer workgroups rather than a workspace that does not fit (tasks come off a queue,
-            // any grid is correct)
-            size_t free_b = 0, total_b = 0;
-            HIPC(ctx, hipMemGetInfo(&free_b, &total_b));
-            const uint64_t per_wg = (half + second) * sizeof(int32_t);
-            const uint64_t fit = std::max<uint64_t>(1, (uint64_t)(free_b * 0.6) / per_wg);
-            b->grid = (uint32_t)std::min<uint64_t>(b->grid, fit);
-            b->grid = (b->grid + 3u) & ~3u;   // whole four-wave workgroups (pwa_batch_run): every wave has a hand-off region of its own
-        }
-        {
-            const size_t hand_bytes = (size_t)b->grid * (half + second) * sizeof(int32_t);
-            if (ctx->hand_cache && ctx->hand_cache_bytes >= hand_bytes) {   // left behind by an earlier batch of this context
-                b->hand.p = ctx->hand_cache;
-                b->hand.bytes = ctx->hand_cache_bytes;
-                ctx->hand_cache = nullptr;
-                ctx->hand_cache_bytes = 0;
-            } else {
-                HIPC(ctx, b->hand.alloc(hand_bytes));
-            }
-        }
-
-        mark("uploads + workspace");
-        BatchParams& P = b->bp;
-        P.arena = b->arena.as<uint8_t>();
-        P.tasks = b->tasks.as<BatchTask>();
-        P.slot_poff = b->slot_poff.as<uint32_t>();
-        P.slot_plen = b->slot_plen.as<uint32_t>();
-        P.slot_out = b->slot_out.as<uint32_t>();
-        P.scores = b->scores.as<int32_t>();
-        P.hand = b->hand.as<int32_t>();
-        P.hand_stride = half + second;
-        P.hand_half = (uint32_t)half;
-        P.queue = b->queue.as<uint32_t>();
-        P.n_tasks = (uint32_t)nt;
-        P.match = tab_match;
-        P.mismatch = tab_mismatch;
-        P.gap = gap;
-        const uint32_t bm = (uint8_t)(int8_t)tab_match, bx = (uint8_t)(int8_t)tab_mismatch;
-        P.tab_lo = bm | (bx << 8) | (bx << 16) | (bx << 24);   // selector 0 -> match
-        P.tab_hi = bx * 0x01010101u;                           // selectors 4..7 -> mismatch
-        const uint32_t pad = (score_path == SC_PERM) ? 7u : (uint32_t)absent_byte;
-        P.pad_word = pad * 0x01010101u;
-        P.tpad_word = ((score_path == SC_PERM) ? 6u : (uint32_t)std::max(text_pad_byte, 0)) * 0x01010101u;
-        P.lane_text = b->lane_text.as<uint8_t>();
-        if (b->lanes && kmode == BM_NWG) P.tab_hi = (uint32_t)(uint8_t)(int8_t)(-gap) * 0x01010101u;   // selectors 4..7: front pad = a gap column
-        if (b->cell16) {   // f16 bit patterns of s * 2^-11 (exact: |s| <= 127)
-            const uint32_t m16 = f16_bits_scaled(match), x16 = f16_bits_scaled(mismatch), g16 = f16_bits_scaled(gap);
-            P.lo16_base = (x16 & 0xffu) * 0x01010101u;
-            P.lo16_diff = (m16 ^ x16) & 0xffu;
-            P.hi16_base = (x16 >> 8) * 0x01010101u;
-            P.hi16_diff = ((m16 ^ x16) >> 8) & 0xffu;
-            P.gap16x2 = g16 | (g16 << 16);
-        }
-        P.slot_toff = b->slot_toff.as<uint32_t>();
-        P.slot_tlen = b->slot_tlen.as<uint32_t>();
-      }   // strips that stay
+        if (st.ht.empty()) b->use_strips = false;
+        if (b->use_strips && (rc = setup_strips(ctx, b, in, form, al, aoff, st, h, lp.max_m, clock)) != PWA_OK) return rc;
     }
-    if (!live_pairs_engine.empty()) {
-        // ---- the pairs that do not run on strips: short patterns over a coded arena on the mini-stripe engine (no band, four pairs per
-        // wave, one launch per row class), everything else on the stripe engine (no band: exact first-maximum end cells, any scoring)
-        std::vector<uint32_t> plist;
-        std::vector<std::pair<int, std::vector<uint32_t>>> mini_lists;   // (rows per lane, pairs)
-        for (const uint32_t k : live_pairs_engine) {
-            const int mrl = mini_rl_of(slen(pair_a[k]));
-            if (!mrl) {
-                plist.push_back(k);
-                continue;
-            }
-            size_t c = 0;
-            while (c < mini_lists.size() && mini_lists[c].first != mrl) ++c;
-            if (c == mini_lists.size()) mini_lists.emplace_back(mrl, std::vector<uint32_t>());
-            mini_lists[c].second.push_back(k);
-        }
-        const size_t nl = live_pairs_engine.size();
-        HIPC(ctx, b->pair_res.alloc(nl * sizeof(PairResult)));
-        HIPC(ctx, hipMemset(b->pair_res.p, 0, nl * sizeof(PairResult)));
-        size_t q_next = 0;
-        auto describe = [&](uint32_t k, size_t q) {
-            PairDesc d;
-            std::memset(&d, 0, sizeof d);
-            d.pat = b->arena.as<uint8_t>() + aoff[pair_a[k]];
-            d.txt = b->arena.as<uint8_t>() + aoff[pair_b[k]];
-            d.n = (int32_t)slen(pair_a[k]);
-            d.m = (int32_t)slen(pair_b[k]);
-            d.res = b->pair_res.as<PairResult>() + q;
-            d.out_index = k;
-            return d;
-        };
-        std::string names;
-        if (!plist.empty()) {
-            b->use_pairs = true;
-            b->live_idx = plist;
-            std::vector<PairDesc> pd;
-            pd.reserve(plist.size());
-            uint64_t pe_max_n = 0;
-            for (const uint32_t k : plist) pe_max_n = std::max(pe_max_n, slen(pair_a[k]));
-            PairGeom geom = choose_geom(ctx->knobs, pe_max_n);
-            {   // RL = 2 buys a pair more waves in flight -- which a list that fills the chip anyway does not need: [gpu, r03] SW scores of
-                // 10k x 10k pairs, RL = 2 / RL = 4: 8 pairs 1.73 / 1.79 ms, 64 pairs 5.35 / 4.93 ms, 256 pairs 17.3 / 12.8 ms
-                uint64_t stripes2 = 0;
-                for (const uint32_t k : plist) stripes2 += (slen(pair_a[k]) + 127) / 128;
-                if (geom.rl == 2 && geom.w == 4 && !ctx->knobs.force_rl && stripes2 >= 2048) geom.rl = 4;
-            }
-            // a coded arena with keys in range (what the band-less mini kernels ask for as well): the keyed chunk without a band -- table
-            // scoring, one v_max3 per cell, global fills gap-shifted -- instead of the plain compare-and-select step: [gpu, r03] SW scores of
-            // 64 pairs 10k x 10k 4.8 -> 3.45 ms, NW 4.06 -> 2.05 ms; one pair 1.67 -> 1.26 / 1.55 -> 1.01 ms
-            const bool keyed_scores = !nwdist && mini_scores && !ctx->knobs.no_keyed_tb && !ctx->knobs.no_pair_table;
-            const bool gap0_scores = keyed_scores && mini_gap0 && !ctx->knobs.no_gap_shift;
-            for (const uint32_t k : plist) {
-                PairDesc d = describe(k, q_next++);
-                d.score_bias = gap0_scores ? wrap_mul((int64_t)(slen(pair_a[k]) + slen(pair_b[k])), gap) : 0;
-                pd.push_back(d);
-                b->padded_cells += (slen(pair_a[k]) + 64 * geom.rl - 1) / (64 * geom.rl) * (64 * geom.rl) * slen(pair_b[k]);
-            }
-            b->pl.perm = keyed_scores;
-            b->pl.keyed = true;
-            b->pl.gap0 = gap0_scores;
-            b->pl.dist = nwdist;
-            b->pl.aff = affine;   // (go travels as the gap, ge beside it)
-            const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom,
-                                       affine ? gap_extend : 0);
-            if (rc != PWA_OK) return rc;
-            b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
-            names = nwdist   ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
-                    : affine ? std::string("pair_affine_kernel<RL=") + std::to_string(geom.rl) + ",AFF,no-band>"
-                             : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
-        }
-        for (auto& cls : mini_lists) {
-            const int rl = cls.first;
-            std::vector<uint32_t>& lst = cls.second;
-            sort_by_length_desc(lst, [&](uint32_t x) { return slen(pair_b[x]); });   // a wave's four texts about equally long
-            std::vector<PairDesc> pd;
-            pd.reserve(lst.size() + 3);
-            for (const uint32_t k : lst) {
-                PairDesc d = describe(k, q_next++);
-                b->live_idx.push_back(k);
-                d.score_bias = mini_gap0 ? wrap_mul((int64_t)(slen(pair_a[k]) + slen(pair_b[k])), gap) : 0;
-                pd.push_back(d);
-                b->padded_cells += (uint64_t)(16 * rl) * slen(pair_b[k]);
-            }
-            const uint32_t n_real = (uint32_t)pd.size();
-            while (pd.size() % 4) {   // empty patterns fill the last wave (their results go nowhere: no row of theirs is row n)
-                PairDesc d = pd[n_real - 1];
-                d.n = 0;
-                pd.push_back(d);
-            }
-            b->mini.emplace_back(new PairLaunch());
-            PairLaunch& ml = *b->mini.back();
-            for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
-            ml.perm = ml.keyed = true;
-            ml.gap0 = mini_gap0;
-            const int rc = ml.build_mini(ctx, pd, n_real, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap, rl);
-            if (rc != PWA_OK) return rc;
-            ml.G.scores_out = b->scores.as<int32_t>();
-            names += std::string(names.empty() ? "" : " + ") + "mini_fill_kernel<RL=" + std::to_string(rl) + (local ? ",SW" : (mini_gap0 ? ",NW,GAP0" : ",NW")) + ",no-band>";
-        }
-        b->kernel_name = b->use_strips ? b->kernel_name + " + " + names : names;   // (the strip kernel first: bench.py prices its instruction mix)
-    }
-    if (dbg) {
-        mark("engine setup");
+    if (!off_strips.empty() && (rc = setup_off_strips(ctx, b, in, form, aoff, off_strips)) != PWA_OK) return rc;
+    if (ctx->knobs.debug) {
+        clock.mark("engine setup");
         HIPC(ctx, hipDeviceSynchronize());
-        mark("hipDeviceSynchronize");
+        clock.mark("hipDeviceSynchronize");
         hipLaunchKernelGGL(pwa_nop_kernel, dim3(1), dim3(64), 0, ctx->stream, (int*)nullptr);
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        mark("nop kernel + sync");
+        clock.mark("nop kernel + sync");
         hipLaunchKernelGGL(pwa_nop_kernel, dim3(1), dim3(64), 0, ctx->stream, (int*)nullptr);
         HIPC(ctx, hipStreamSynchronize(ctx->stream));
-        mark("nop kernel + sync again");
+        clock.mark("nop kernel + sync again");
     }
     guard.b = nullptr;
     *out = b;
@@ -2058,33 +2180,22 @@ int pwa_batch_run(pwa_batch* b, void* stream_v) {
                 dp.tab2_lo = 0x000000ffu;   // selector 0 (symbols equal) -> -1, every other selector -> 0
                 dp.tab2_hi = 0u;
                 dp.scores2 = nullptr;
-                hipLaunchKernelGGL(b->kern->dfn, dim3(b->grid), dim3(64), 0, st, dp);
+                hipLaunchKernelGGL(reinterpret_cast<nwdist_kernel_t>(b->strip_fn), dim3(b->grid), dim3(64), 0, st, dp);
             } else if (b->affine) {
                 AffineParams ap;
                 ap.b = b->bp;
                 ap.go = b->aff_go;
                 ap.ge = b->aff_ge;
                 ap.neg = b->aff_neg;
-                hipLaunchKernelGGL(b->kern->afn, dim3(b->grid), dim3(64), 0, st, ap);
+                hipLaunchKernelGGL(reinterpret_cast<affine_kernel_t>(b->strip_fn), dim3(b->grid), dim3(64), 0, st, ap);
             } else {
-                if (b->paired) {
-                    hipLaunchKernelGGL(b->kern->fn_pair, dim3(b->grid), dim3(128), 0, st, b->bp);
-                } else {
-                    // b->grid waves as workgroups of four, with an LDS request that admits exactly their share per CU: a balanced
-                    // placement whatever ran before (batch_scores.hip.h); PWA_STRIP_WG1: single-wave workgroups (A/B)
-                    const batch_kernel_t fn = b->cell16  ? (b->single_strip ? b->kern->fn_cell16_single : b->kern->fn_cell16)
-                                              : b->lanes ? (b->single_strip ? b->kern->fn_lanes_single : b->kern->fn_lanes)
-                                                         : (b->single_strip ? b->kern->fn_single : b->kern->fn);
-                    if (ctx->knobs.strip_wg1) {
-                        hipLaunchKernelGGL(fn, dim3(b->grid), dim3(64), 0, st, b->bp);
-                    } else {
-                        const uint32_t n_wg = (b->grid + 3) / 4, per_cu = (n_wg + (uint32_t)ctx->num_cu - 1) / (uint32_t)ctx->num_cu;
-                        static const uint32_t kPadKiB[6] = {0, 96, 64, 48, 36, 30};
-                        const size_t pad_lds = per_cu <= 5 ? (size_t)kPadKiB[per_cu] * 1024 : 0;
-                        HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
-                        hipLaunchKernelGGL(fn, dim3(n_wg), dim3(256), pad_lds, st, b->bp);
-                    }
-                }
+                // b->grid waves as workgroups of four, with an LDS request that admits exactly their share per CU: a balanced
+                // placement whatever ran before (batch_scores.hip.h)
+                const uint32_t n_wg = (b->grid + 3) / 4, per_cu = (n_wg + (uint32_t)ctx->num_cu - 1) / (uint32_t)ctx->num_cu;
+                static const uint32_t kPadKiB[6] = {0, 96, 64, 48, 36, 30};
+                const size_t pad_lds = per_cu <= 5 ? (size_t)kPadKiB[per_cu] * 1024 : 0;
+                HIPC(ctx, hipFuncSetAttribute(b->strip_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+                hipLaunchKernelGGL(reinterpret_cast<batch_kernel_t>(b->strip_fn), dim3(n_wg), dim3(256), pad_lds, st, b->bp);
             }
             HIPC(ctx, hipGetLastError());
         }
@@ -2186,11 +2297,6 @@ int pwa_batch_fetch(pwa_batch* b, int32_t* score_out, uint32_t* end_i_out, uint3
         if (rc != PWA_OK) return rc;
     }
     if (!b->want_end || b->n_live == 0) {   // both engines write their pairs' scores into the device score vector
-        if (b->paired && b->n_live) {   // the LDS hand-off spins are bounded; a wave that gave up says so here
-            uint32_t q[2] = {0, 0};
-            HIPC(ctx, hipMemcpy(q, b->queue.p, sizeof q, hipMemcpyDeviceToHost));
-            if (q[1] != 0) return fail(ctx, PWA_E_HIP, "strip hand-off timed out inside batch_scores_pair_kernel");
-        }
         HIPC(ctx, hipMemcpy(score_out, pwa_batch_d_scores(b), b->n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
         if (b->want_end) {   // only reachable with no live pairs
             if (end_i_out) std::memcpy(end_i_out, b->host_end_i.data(), b->n_pairs * 4);
@@ -2427,36 +2533,12 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             arena_bytes += align_up(slen(s) + 1, 16);
         }
     arena_bytes += 256;
-    // Alphabets of at most 7 symbols (DNA, DNA + N, ...) are stored as codes 0..6 -- equality is all the recurrence
-    // ever asks of a symbol (hw2.cpp:142, 208) -- so that the fill can score four rows with one byte-table lookup
-    // (pair_fill.hip.h, PERM).  The table holds the two diagonal key constants: both must fit a signed byte.
-    bool coded = false;
+    // alphabets of at most 7 symbols as codes (code_alphabet); one pass over every used byte, on a few threads once the input reaches megabytes
+    bool seen[256];
+    scan_bytes(seq_bytes, seq_off, n_seq, is_used, seen, 1ull << 20);
     uint8_t code_of[256];
-    bool dash_seen = false, nul_seen = false;
-    {
-        bool seen[256] = {false};
-        {   // one pass over every used byte: on a few threads once the input reaches megabytes
-            bool part[16][256] = {};
-            for_seq_ranges(seq_off, n_seq, [&](uint32_t s0, uint32_t s1, int t) {
-                bool* mine = part[t];
-                for (uint32_t s = s0; s < s1; ++s)
-                    if (is_used[s])
-                        for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
-            }, nullptr, 1ull << 20);
-            for (int t = 0; t < 16; ++t)
-                for (int v = 0; v < 256; ++v) seen[v] |= part[t][v];
-        }
-        int n_alpha = 0;
-        for (int v = 0; v < 256; ++v) {
-            code_of[v] = (uint8_t)std::min(n_alpha, 7);
-            if (seen[v]) ++n_alpha;
-        }
-        const int64_t kd_match = ((int64_t)match - gap) * 4 + 2, kd_mismatch = ((int64_t)mismatch - gap) * 4 + 2;
-        coded = n_alpha <= 7 && kd_match <= 127 && kd_match >= -126 && kd_mismatch <= 127 && kd_mismatch >= -126 &&
-                !ctx->knobs.no_pair_table;
-        dash_seen = seen[(unsigned char)'-'];
-        nul_seen = seen[0];
-    }
+    const bool coded = code_alphabet(seen, code_of, match, mismatch, gap, ctx->knobs);
+    const bool dash_seen = seen[(unsigned char)'-'], nul_seen = seen[0];
     // overlapLongestExactMatch (hw2.cpp:269) does not count a column whose symbols are '-' -- also when the '-' is part
     // of the input sequence itself: the walk needs the arena's value for that byte
     const int32_t dash_sym = !dash_seen ? 0x100 : (coded ? (int32_t)code_of[(unsigned char)'-'] : (int32_t)'-');
@@ -2475,15 +2557,8 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     // scores x lengths beyond the packed keys' 2^28: the plain int32 form, exact for anything the reference's int holds
     const bool keyed = tb_range_ok(longest_sum, match, mismatch, gap, local ? 26 : 28) && !ctx->knobs.no_keyed_tb;   // (local: H * 16 in the first-maximum records)
     // Global alignments with table scoring run in gap-shifted coordinates G = H - gap (i + j): the same recurrence with gap 0 and
-    // scores s - 2 gap, identical comparisons and codes, one instruction less per cell (pair_fill.hip.h, GAP0).  |G| <= |H| +
-    // |gap| (n + m): twice the range; both shifted diagonal constants must fit the byte table.
-    bool gap0 = false;
-    if (!local && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift) {
-        const int64_t sm = (int64_t)match - 2 * (int64_t)gap, sx = (int64_t)mismatch - 2 * (int64_t)gap;
-        const int64_t km = sm * 4 + 1, kx = sx * 4 + 1;   // (s' - 0) * 4 + prio(diag) - prio(left)
-        const int64_t amax = std::max<int64_t>({std::llabs((long long)match), std::llabs((long long)mismatch), std::llabs((long long)gap), 1});
-        gap0 = km <= 127 && km >= -126 && kx <= 127 && kx >= -126 && (longest_sum + 2) <= (1ull << 27) / (uint64_t)amax;
-    }
+    // scores s - 2 gap, identical comparisons and codes, one instruction less per cell (pair_fill.hip.h, GAP0: gap0_ok)
+    const bool gap0 = !local && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift && gap0_ok(longest_sum, match, mismatch, gap);
     const int k_match = gap0 ? match - 2 * gap : match, k_mismatch = gap0 ? mismatch - 2 * gap : mismatch, k_gap = gap0 ? 0 : gap;
     // the mini-stripe engine exists for keyed cells with table scoring; PWA_FORCE_RL / PWA_FORCE_W address the stripe engine
     const bool mini_ok = coded && keyed && ctx->knobs.tb_engine != 0 && !ctx->knobs.force_rl && !ctx->knobs.force_w &&
@@ -2507,10 +2582,8 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     }
     const bool tall_stripes = stripes2 >= 1024 && !ctx->knobs.force_rl;
     auto class_of = [&](uint64_t n) -> TbClass {   // (w of a mini class = its lanes per pair)
-        if (mini_ok && n <= 256)
-            for (const int rl : kMiniRL)
-                if (n <= (uint64_t)(16 * rl)) return TbClass{true, rl, 16};
-        if (wide_ok && n <= 1024) return TbClass{true, n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16, 64};
+        if (mini_ok && n <= 256) return TbClass{true, mini_rl_for(n), 16};
+        if (wide_ok && n <= 1024) return TbClass{true, wide_rl_for(n), 64};
         PairGeom g = choose_geom(ctx->knobs, n, keyed, true);
         if (tall_stripes && g.rl == 2 && g.w == 4) g.rl = 4;
         return TbClass{false, g.rl, g.w};
@@ -2849,27 +2922,15 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
     // patterns of up to 256 rows over an alphabet of <= 7 symbols: the mini-stripe engine, as pwa_align_batch would pick it (so that
     // the whole-matrix comparison covers that engine's cells too); everything else: the stripe engine on raw bytes
     uint8_t code_of[256];
-    int n_alpha = 0;
-    {
-        bool seen[256] = {false};
-        for (uint64_t o = 0; o < n; ++o) seen[pattern[o]] = true;
-        for (uint64_t o = 0; o < m; ++o) seen[text[o]] = true;
-        for (int v = 0; v < 256; ++v) {
-            code_of[v] = (uint8_t)std::min(n_alpha, 7);
-            if (seen[v]) ++n_alpha;
-        }
-    }
-    const int64_t kd_match = ((int64_t)match - gap) * 4 + 2, kd_mismatch = ((int64_t)mismatch - gap) * 4 + 2;
-    const bool coded = n_alpha <= 7 && kd_match <= 127 && kd_match >= -126 && kd_mismatch <= 127 && kd_mismatch >= -126 && !ctx->knobs.no_pair_table;
+    bool seen[256] = {false};
+    for (uint64_t o = 0; o < n; ++o) seen[pattern[o]] = true;
+    for (uint64_t o = 0; o < m; ++o) seen[text[o]] = true;
+    const bool coded = code_alphabet(seen, code_of, match, mismatch, gap, ctx->knobs);
     int mini_rl = 0, wide_rl = 0;   // wide: one pair per wave (PWA_TB_ENGINE=2 here: a single pair would normally take pipelined stripes)
     if (coded && keyed && ctx->knobs.tb_engine != 0 && !ctx->knobs.force_rl && !ctx->knobs.force_w &&
         (mode != PWA_MODE_SW || tb_range_ok(n + m, match, mismatch, gap, 26))) {
-        if (n <= 256) {
-            for (const int rl : kMiniRL)
-                if (!mini_rl && n <= (uint64_t)(16 * rl)) mini_rl = rl;
-        } else if (n <= 1024 && ctx->knobs.tb_engine == 2) {
-            wide_rl = n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16;
-        }
+        mini_rl = mini_rl_for(n);
+        if (!mini_rl && n <= 1024 && ctx->knobs.tb_engine == 2) wide_rl = wide_rl_for(n);
     }
     const PairGeom geom = mini_rl ? PairGeom{mini_rl, 1} : wide_rl ? PairGeom{wide_rl, 1} : choose_geom(ctx->knobs, n, keyed, true);
     const uint64_t kRL = (uint64_t)geom.rl;

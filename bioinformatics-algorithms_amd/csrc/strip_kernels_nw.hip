@@ -5,11 +5,8 @@ namespace pwa {
 
 #define BK(R, M, S) {R, M, S, batch_scores_kernel<R, M, S, true>, "batch_scores_kernel<R=" #R "," #M "," #S ">", nullptr, nullptr, \
                      batch_scores_kernel<R, M, S, false>}
-#define BKP(R, M, S) {R, M, S, batch_scores_kernel<R, M, S, true>, "batch_scores_kernel<R=" #R "," #M "," #S ">", nullptr, nullptr, \
-                      batch_scores_kernel<R, M, S, false>, batch_scores_pair_kernel<R, M, S>, \
-                      batch_scores_kernel<R, M, S, true, true>, batch_scores_kernel<R, M, S, false, true>}
 #define BKL(R, M, S) {R, M, S, batch_scores_kernel<R, M, S, true>, "batch_scores_kernel<R=" #R "," #M "," #S ">", nullptr, nullptr, \
-                      batch_scores_kernel<R, M, S, false>, nullptr, \
+                      batch_scores_kernel<R, M, S, false>, \
                       batch_scores_kernel<R, M, S, true, true>, batch_scores_kernel<R, M, S, false, true>}
 extern const BatchKernelEntry kStripKernelsNW[] = {
     BK(64, BM_NW, SC_PERM),   BK(128, BM_NW, SC_PERM),  BK(152, BM_NW, SC_PERM),

@@ -330,10 +330,10 @@ def test_scores_many_strips_and_long_texts(sctx):
             assert got == want, (mode, sc)
 
 
-def test_two_strip_tasks_through_the_lds_paired_kernel(ctx):
-    """opt-in form (PWA_PAIRED=1): local-alignment batches whose tasks have one or two strips run as two waves per task
-    with the strip boundary row in an LDS ring (batch_scores_pair_kernel): every text length residue mod 4, texts shorter than
-    one block, longer than the ring, a few single-strip tasks, ragged lanes, many more tasks than workgroups."""
+def test_two_strip_tasks_on_the_hbm_hand_off(ctx):
+    """local-alignment batches whose tasks have one or two strips, on the strips' HBM hand-off, in int32 cells (PWA_CELL16=0) and in
+    the form the cost model picks: every text length residue mod 4, texts shorter than one block, longer than 16 blocks, a few
+    single-strip tasks, ragged lanes, many more tasks than workgroups."""
     rng = random.Random(4242)
     txt_lens = [1, 2, 3, 4, 5, 6, 7, 61, 62, 63, 64, 65, 66, 67, 68, 69, 255, 256, 257, 1000, 1001, 1002, 1003]
     txts = [O.gen(11, 1, i, m) for i, m in enumerate(txt_lens)]
@@ -348,16 +348,19 @@ def test_two_strip_tasks_through_the_lds_paired_kernel(ctx):
                 if (i >= 90) == short_text and rng.random() < 0.9:
                     pa.append(i)
                     pb.append(len(pats) + j)
-        with switched_context(PWA_PAIRED="1", PWA_SCORES_ROUTE="0") as c:   # opt-in form (a switch of the context)
-            b = c.batch("sw", seqs, pa, pb, *scoring)
-            assert "pair_kernel" in b.info()["kernel"], b.info()
-            for _ in range(2):
-                b.run()
-                got = b.fetch()
-            b.close()
         want = [O.score("sw", seqs[a], seqs[c], *scoring)[0] for a, c in zip(pa, pb)]
-        bad = [k for k in range(len(pa)) if got[k] != want[k]]
-        assert not bad, (scoring, bad[:5], [(len(seqs[pa[k]]), len(seqs[pb[k]]), got[k], want[k]) for k in bad[:5]])
+        for env in ({"PWA_CELL16": "0"}, {}):
+            with switched_context(PWA_SCORES_ROUTE="0", **env) as c:   # every pair on the strips
+                b = c.batch("sw", seqs, pa, pb, *scoring)
+                kernel = b.info()["kernel"]
+                assert kernel.startswith("batch_scores_kernel<") and " + " not in kernel, kernel
+                assert b.cell_bits() == 32 or not env, env
+                for _ in range(2):
+                    b.run()
+                    got = b.fetch()
+                b.close()
+            bad = [k for k in range(len(pa)) if got[k] != want[k]]
+            assert not bad, (scoring, env, bad[:5], [(len(seqs[pa[k]]), len(seqs[pb[k]]), got[k], want[k]) for k in bad[:5]])
 
 
 @pytest.mark.parametrize("alphabet,expect_lanes", [(b"ACGT", True), (b"ACGTN", True), (b"ACGTNXY", False),
