@@ -27,7 +27,7 @@ MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1}
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_scores",
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits",
-    "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_batch", "pwa_overlaps",
+    "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_overlaps",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
 ]
@@ -83,6 +83,7 @@ def lib():
                             C.c_uint64, u64p, u64p, u64p]
     L.pwa_align_matrices.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
     L.pwa_align_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
+    L.pwa_align_affine_last_stats.argtypes = [vp, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_align_batch.argtypes = batch_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_overlaps.argtypes = batch_in + [i32p, i32p]
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
@@ -403,6 +404,12 @@ class Context:
         f, t, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
         self._L.pwa_align_last_stats(self._h, C.byref(f), C.byref(t), C.byref(b))
         return dict(fill_ms=f.value, traceback_ms=t.value, band_bytes=b.value)
+
+    def align_affine_stats(self):
+        """The last align_affine_batch: pairs on the stripe engine, device ms of their fills / walks, band bytes written."""
+        p, f, w, b = C.c_uint64(0), C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_align_affine_last_stats(self._h, C.byref(p), C.byref(f), C.byref(w), C.byref(b)), "pwa_align_affine_last_stats")
+        return dict(stripe_pairs=p.value, fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
 
 
 class Batch:

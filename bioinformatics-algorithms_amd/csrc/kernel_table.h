@@ -40,6 +40,11 @@ pair_kernel_t pair_dist_kernel_for(int rl, int w);
 // pair_affine_kernels.hip -- hw3's affine score on the stripe engine (rl = 2 | 4, w = 1 | 4): no band, no walk, M[n][m] straight
 // into PairParams::scores_out; PairParams::gap = gap opening, gap_extend = gap extension
 pair_kernel_t pair_affine_kernel_for(int rl, int w);
+// pair_affine_tb_kernels.hip -- hw3's affine alignment on the stripe engine (rl = 4, w = 1 | 4): the fill writes the traceback band
+// (one code byte per cell, batch_affine_tb.hip.h's code) and M[n][m] into PairParams::scores_out; the walk (one wave per pair) the
+// op list into PairDesc::ops and its length into PairResult::n_ops
+pair_kernel_t pair_affine_tb_kernel_for(int rl, int w);
+pair_kernel_t pair_affine_walk_kernel_for(int rl);
 // mini_kernels*.hip -- the mini-stripe engine (16 lanes per pair, 4 pairs per wave; keyed cells, table scoring): fills for
 // rl in kMiniRL; gap0 only global without score band; the walks over its band geometry (BandGeo<16, rl>)
 constexpr int kMiniRL[] = {4, 6, 8, 10, 12, 16};

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <cmath>
+#include <functional>
 #include <initializer_list>
 #include <limits>
 #include <new>
@@ -96,6 +98,8 @@ struct Knobs {
     int pipe_runs = 0;                          // PWA_PIPE_RUNS=N: cut a list that fits one arena into N pipelined runs (experiment; measured slower)
     int scores_route = -1;                      // PWA_SCORES_ROUTE: 0 = every pair on the strip engine, 1 = every pair on the stripe
                                                 // engine, unset = by estimated cost (batch_create_impl)
+    int affine_tb_route = -1;                   // PWA_AFFINE_TB_ROUTE: pwa_align_affine_batch: 0 = every pair on the strips, 1 = every eligible
+                                                // pair on the stripe engine, unset = by estimated cost and band size
     int cell16 = -1;                            // PWA_CELL16: 0 = never the packed f16 cells (two pairs per lane), 1 = always where the batch
                                                 // admits them, unset = by estimated cost (batch_create_impl)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
@@ -128,6 +132,7 @@ struct Knobs {
         scores_route = num("PWA_SCORES_ROUTE", -1);
         tb_engine = num("PWA_TB_ENGINE", -1);
         cell16 = num("PWA_CELL16", -1);
+        affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
     }
 };
 
@@ -140,6 +145,9 @@ struct pwa_ctx {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     std::string err;
     float fill_ms = 0.f, tb_ms = 0.f;
+    // the last pwa_align_affine_batch: pairs it ran on the stripe engine, device ms of their fills / walks, band bytes written
+    uint64_t aff_stripe_pairs = 0, aff_band_bytes = 0;
+    float aff_fill_ms = 0.f, aff_walk_ms = 0.f;
     uint64_t band_bytes = 0;
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
@@ -603,6 +611,7 @@ struct PairLaunch {
     bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
     bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
     bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
+    bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;
@@ -747,14 +756,20 @@ struct PairLaunch {
             G.trace_stripe = ctx->knobs.trace_stripe;
         }
         if (dist || aff) {   // hw4 distances / hw3 affine scores: the fill writes D[n][m] / M[n][m] into the score vector itself
-            const pair_kernel_t fill = dist ? pair_dist_kernel_for(geom.rl, geom.w) : pair_affine_kernel_for(geom.rl, geom.w);
-            if (!fill) return fail(ctx, PWA_E_INVALID, "internal: no distance / affine kernel for this geometry");
+            const pair_kernel_t fill = dist ? pair_dist_kernel_for(geom.rl, geom.w)
+                                       : aff_tb ? pair_affine_tb_kernel_for(geom.rl, geom.w) : pair_affine_kernel_for(geom.rl, geom.w);
+            const pair_kernel_t walk_fn = aff_tb ? pair_affine_walk_kernel_for(geom.rl) : nullptr;
+            if (!fill || (aff_tb && !walk_fn)) return fail(ctx, PWA_E_INVALID, "internal: no distance / affine kernel for this geometry");
             size_t pad_lds = 0;   // (one multi-stripe workgroup per CU when they are few: as below)
             if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;
             if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
             hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
             HIPC(ctx, hipGetLastError());
             if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+            if (aff_tb) {
+                hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+                HIPC(ctx, hipGetLastError());
+            }
             return PWA_OK;
         }
         // (scores / end cells only over a coded arena, keys in range: the keyed chunk without a band -- batch_create_impl sets perm for that)
@@ -1929,6 +1944,171 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
     return fail(ctx, PWA_E_HIP, "unexpected C++ exception");   // nothing may propagate across the C ABI
 }
 
+namespace {
+
+// A wave task of the affine alignment strips (batch_affine_tb_kernel): `count` pairs order[first ..] sharing string1 (m columns),
+// their string2 over `strips` 32-row strips, the task's code band tb_dwords
+struct AffTbTask {
+    uint32_t first, count;
+    uint64_t strips, m, tb_dwords;
+};
+
+// ---- pwa_align_affine_batch: which strip wave tasks move to the stripe engine (pair_affine_tb.hip.h).  A strip wave task is one
+// wave running strips x m columns of 32 rows on its own: [gpu] the 15 center pairs of 16 x 10 kb are ONE task, 313 strips x 10 000
+// columns in 5.47 s, 55 ns per row and column.  The stripe engine spreads each pair over ceil(n / 256) waves that sweep anti-diagonals,
+// then walks every pair with one wave.  As in tasks_to_move, tasks are moved in order of decreasing strip cost and the count with
+// the smallest estimated total -- the strip launch and the stripe launches run one after the other -- wins; a task whose strip band
+// does not fit the budget moves whatever the estimate (the strips cannot run it at all).  Constants: profiles/hw3_align_route_probe.txt.
+std::vector<uint8_t> affine_tb_route(const pwa_ctx* ctx, const std::vector<AffTbTask>& ht, const std::vector<uint32_t>& order,
+                                     const std::function<uint64_t(uint32_t)>& n_of, const std::function<uint64_t(uint32_t)>& m_of,
+                                     uint64_t strip_budget_bytes, bool eligible) {
+    const size_t nt = ht.size();
+    std::vector<uint8_t> move(nt, 0);
+    const int route = ctx->knobs.affine_tb_route;
+    if (!eligible || route == 0) return move;
+    if (route == 1) {
+        std::fill(move.begin(), move.end(), 1);
+        return move;
+    }
+    // [gpu] profiles/hw3_align_route_probe.txt: strips 55 ns per row and column of a task (one wave alone); stripe engine, a pair
+    // alone: 32.5 us per 256-row stripe + 134 ns per step; chip full (16 x 100 kb): 340 ns per stripe step and SIMD; walks ~50 ns per op
+    constexpr double kStripNs = 55.0;
+    constexpr double kStepNs = 340.0, kLagUs = 32.5, kLoneStepNs = 134.0, kWalkNsPerOp = 50.0, kLaunchUs = 30.0;
+    const double kSimds = 4.0 * ctx->num_cu;
+    std::vector<double> I(nt), S(nt), L(nt);   // strip ns / stripe fill ns x SIMD / longest stripe fill + walk (ns) of a task
+    std::vector<uint32_t> ord(nt);
+    for (size_t t = 0; t < nt; ++t) {
+        ord[t] = (uint32_t)t;
+        I[t] = (double)ht[t].strips * 32.0 * (double)ht[t].m * kStripNs;
+        double steps = 0, lat = 0;
+        for (uint32_t l = 0; l < ht[t].count; ++l) {
+            const uint32_t k = order[ht[t].first + l];
+            const double n = (double)n_of(k), m = (double)m_of(k), stripes = std::ceil(n / 256.0);
+            steps += stripes * (m + 63) * kStepNs;
+            lat = std::max(lat, stripes * kLagUs * 1e3 + (m + 63) * kLoneStepNs + (n + m) * kWalkNsPerOp);
+        }
+        S[t] = steps;
+        L[t] = lat;
+    }
+    // tasks that cannot stay first, then by decreasing strip cost
+    auto must = [&](size_t t) { return ht[t].tb_dwords * 4 > strip_budget_bytes; };
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return must(x) != must(y) ? must(x) : I[x] > I[y]; });
+    size_t n_must = 0;
+    while (n_must < nt && must(ord[n_must])) ++n_must;
+    std::vector<double> sufmax(nt + 1, 0.0), sufsum(nt + 1, 0.0);
+    for (size_t k = nt; k-- > 0;) {
+        sufmax[k] = std::max(sufmax[k + 1], I[ord[k]]);
+        sufsum[k] = sufsum[k + 1] + I[ord[k]];
+    }
+    double best = -1, mS = 0, mL = 0;
+    size_t best_k = n_must;
+    for (size_t k = 0; k <= nt; ++k) {
+        const double ts = std::max(sufmax[k], sufsum[k] / kSimds);                                    // ns
+        const double tp = k ? std::max(mL, mS / kSimds) + kLaunchUs * 1e3 : 0.0;
+        if (k >= n_must && (best < 0 || ts + tp < best)) {
+            best = ts + tp;
+            best_k = k;
+        }
+        if (k < nt) {
+            mS += S[ord[k]];
+            mL = std::max(mL, L[ord[k]]);
+        }
+    }
+    for (size_t k = 0; k < best_k; ++k) move[ord[k]] = 1;
+    if (ctx->knobs.debug)
+        std::fprintf(stderr, "[pwa] align_affine route: %zu of %zu wave tasks to the stripe engine (%zu whose strip band exceeds %.2f GB; estimates: "
+                             "all on strips %.1f ms, split %.1f ms)\n", best_k, nt, n_must, (double)strip_budget_bytes / 1e9,
+                     std::max(sufmax[0], sufsum[0] / kSimds) * 1e-6, best * 1e-6);
+    return move;
+}
+
+// ---- pwa_align_affine_batch on the stripe engine: the pairs `pairs` (caller indices, ascending) in consecutive chunks whose bands fit
+// the budget (min(0.6 free, 48 GiB), or PWA_RANGE_BYTES), one fill + walk launch per chunk.  Scores go to d_scores[k], op lists to
+// d_ops + dev_ops_off[k]; n_ops[k] is filled on the host.  Band, results and launch buffers come from the context's caches.
+int affine_tb_on_stripes(pwa_ctx* ctx, const std::vector<uint32_t>& pairs, const uint32_t* pair_a, const uint32_t* pair_b,
+                         const std::function<uint64_t(uint32_t)>& slen, const uint8_t* arena, const std::vector<uint64_t>& aoff,
+                         int match, int mismatch, int gap_open, int gap_extend, int32_t* d_scores, uint8_t* d_ops,
+                         const std::vector<uint64_t>& dev_ops_off, size_t free_b, std::vector<uint32_t>& n_ops) {
+    if (pairs.empty()) return PWA_OK;
+    const uint64_t cap = ctx->knobs.range_bytes ? ctx->knobs.range_bytes : std::min<uint64_t>((uint64_t)(free_b * 0.6), 48ull << 30);
+    constexpr uint64_t kWalkPad = 32768;   // the walk stages whole 16 KiB windows: one may run past the last band
+    auto band = [&](uint32_t k) { return align_up(tb_band_bytes(slen(pair_a[k]), slen(pair_b[k]), 4), 256); };
+    std::vector<std::pair<size_t, size_t>> chunks;
+    uint64_t band_cap = 0, nc_cap = 0;
+    for (size_t p0 = 0; p0 < pairs.size();) {
+        size_t p1 = p0;
+        uint64_t b = 0;
+        while (p1 < pairs.size() && (p1 == p0 || b + band(pairs[p1]) <= cap)) b += band(pairs[p1++]);
+        if (b + kWalkPad > (uint64_t)(free_b * 0.97)) return fail(ctx, PWA_E_NOMEM, "traceback band of a single pair exceeds free HBM");
+        chunks.emplace_back(p0, p1);
+        band_cap = std::max(band_cap, b);
+        nc_cap = std::max<uint64_t>(nc_cap, p1 - p0);
+        p0 = p1;
+    }
+    if (ctx->knobs.debug)
+        std::fprintf(stderr, "[pwa] align_affine stripes: %zu pairs in %zu chunk(s) of <= %.2f GB of band (cap %.2f GB)\n", pairs.size(), chunks.size(),
+                     (double)band_cap / 1e9, (double)cap / 1e9);
+    DevBuf d_band, d_res_own;
+    void *p_band = nullptr, *p_res = nullptr;
+    HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, band_cap + kWalkPad, d_band, &p_band));
+    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
+    PairResult* const d_res = static_cast<PairResult*>(p_res);
+    for (const auto& ch : chunks) {
+        const size_t nc = ch.second - ch.first;
+        std::vector<PairDesc> pd(nc);
+        uint64_t bo = 0, max_n = 0;
+        for (size_t q = 0; q < nc; ++q) {
+            const uint32_t k = pairs[ch.first + q];
+            PairDesc& d = pd[q];
+            std::memset(&d, 0, sizeof d);
+            d.pat = arena + aoff[pair_a[k]];   // rows: string1 (hw3's i), columns: string2 (j)
+            d.txt = arena + aoff[pair_b[k]];
+            d.n = (int32_t)slen(pair_a[k]);
+            d.m = (int32_t)slen(pair_b[k]);
+            d.tb = static_cast<uint8_t*>(p_band) + bo;
+            d.res = d_res + q;
+            d.ops = d_ops + dev_ops_off[k];
+            d.ops_cap = (uint32_t)(d.n + d.m);
+            d.out_index = k;
+            bo += band(k);
+            max_n = std::max<uint64_t>(max_n, (uint64_t)d.n);
+            ctx->aff_band_bytes += tb_band_bytes((uint64_t)d.n, (uint64_t)d.m, 4);
+        }
+        HIPC(ctx, hipMemsetAsync(d_res, 0, nc * sizeof(PairResult), ctx->stream));
+        PairLaunch pl;
+        pl.from_pool = true;
+        pl.aff = pl.aff_tb = true;
+        int rc = pl.build(ctx, pd, match, mismatch, gap_open, PairGeom{4, max_n <= 256 ? 1 : 4}, gap_extend);
+        if (rc != PWA_OK) return rc;
+        pl.G.scores_out = d_scores;
+        if (ctx->knobs.debug)
+            std::fprintf(stderr, "[pwa] align_affine chunk: pairs %zu .. %zu, W=%d grid=%u tasks=%u band %.2f GB rows %llu B\n", ch.first, ch.second - 1,
+                         pl.geom.w, pl.grid, pl.G.n_tasks, (double)bo / 1e9, (unsigned long long)pl.row_bytes);
+        HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        rc = pl.launch(ctx, ctx->stream, false, true, WALK_OPS, ctx->ev[1]);
+        if (rc != PWA_OK) return rc;
+        HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+        HIPC(ctx, hipStreamSynchronize(ctx->stream));
+        rc = pl.check(ctx);
+        if (rc != PWA_OK) return rc;
+        float a = 0, c = 0;
+        HIPC(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
+        HIPC(ctx, hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]));
+        ctx->aff_fill_ms += a;
+        ctx->aff_walk_ms += c;
+        std::vector<PairResult> res(nc);
+        HIPC(ctx, hipMemcpy(res.data(), d_res, nc * sizeof(PairResult), hipMemcpyDeviceToHost));
+        for (size_t q = 0; q < nc; ++q) {
+            if (res[q].overflow) return fail(ctx, PWA_E_CAPACITY, "internal: traceback longer than n+m");
+            n_ops[pairs[ch.first + q]] = res[q].n_ops;
+        }
+    }
+    ctx->aff_stripe_pairs += pairs.size();
+    return PWA_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int pwa_batch_create(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes,
@@ -1954,7 +2134,8 @@ int pwa_nwdist_batch_create(pwa_ctx* ctx, int match, int mismatch, int gap, cons
 // hw3.cpp:261-283: full affine-gap alignments (score + op list) of a pair list.  Pairs are grouped by string1 (for
 // the center-star step every pair has the center there): it becomes the wave's shared text and every lane runs its
 // own string2 down the rows (batch_affine_tb.hip.h).  Raw bytes, compare path, 32-row strips: the pass covers N-1
-// pairs next to the all-pairs score pass over N(N-1)/2, so it is built for exactness, not for speed.
+// pairs next to the all-pairs score pass over N(N-1)/2, so it is built for exactness, not for speed.  Wave tasks that would leave the chip
+// idle -- few long pairs -- or whose band does not fit run on the stripe engine instead (pair_affine_tb.hip.h, affine_tb_route).
 int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
                            const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                            uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops) try {
@@ -1968,10 +2149,12 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
     HIPC(ctx, hipSetDevice(ctx->device));
     constexpr int R = 32, Q = R / 4;
     auto slen = [&](uint32_t s) -> uint64_t { return seq_off[s + 1] - seq_off[s]; };
+    ctx->aff_stripe_pairs = ctx->aff_band_bytes = 0;
+    ctx->aff_fill_ms = ctx->aff_walk_ms = 0.f;
 
     // ---- pairs with an empty side: the reference's boundary walk (hw3.cpp:42-53, 105-131) -- all 'D' or all 'I'
     std::vector<uint32_t> live;
-    uint64_t max_m = 0;
+    uint64_t max_m = 0, max_n2 = 0;
     for (uint64_t k = 0; k < n_pairs; ++k) {
         const uint64_t n1 = slen(pair_a[k]), n2 = slen(pair_b[k]);
         if (n1 > 0x3fffffffull || n2 > 0x3fffffffull) return fail(ctx, PWA_E_CAPACITY, "sequence longer than 2^30");
@@ -1983,6 +2166,7 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
         }
         live.push_back((uint32_t)k);
         max_m = std::max(max_m, n1);
+        max_n2 = std::max(max_n2, n2);
     }
     if (live.empty()) return PWA_OK;
 
@@ -2029,10 +2213,7 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
             key[o] = ((uint64_t)pair_a[order[o]] << 32) | (uint64_t)(0x7fffffffu - (uint32_t)slen(pair_b[order[o]]));
         radix_sort_by_key(key, order);
     }
-    struct HostTask {
-        uint32_t first, count;
-        uint64_t strips, m, tb_dwords;
-    };
+    typedef AffTbTask HostTask;
     std::vector<HostTask> ht;
     for (size_t p = 0; p < order.size();) {
         size_t q = p;
@@ -2045,6 +2226,26 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
     size_t free_b = 0, total_b = 0;
     HIPC(ctx, hipMemGetInfo(&free_b, &total_b));
     const uint64_t tb_budget_dw = std::max<uint64_t>(std::min<uint64_t>((uint64_t)(free_b * 0.6), 6ull << 30) / 4, 1);
+
+    // ---- wave tasks that leave the strips for the stripe engine (pair_affine_tb.hip.h): by estimated cost, and every task whose
+    // strip band exceeds the budget.  Only lists whose keys stay inside int32 (the kernel's guard, 2^26 on the values) qualify.
+    std::vector<uint32_t> stripe_pairs;
+    {
+        const bool eligible = (int64_t)(max_m + max_n2 + 2) *
+                                  max_abs({match, mismatch, std::llabs((long long)gap_open) + std::llabs((long long)gap_extend), 1}) < (1ll << 26);
+        const std::vector<uint8_t> move = affine_tb_route(ctx, ht, order, [&](uint32_t k) { return slen(pair_a[k]); },
+                                                          [&](uint32_t k) { return slen(pair_b[k]); }, tb_budget_dw * 4, eligible);
+        std::vector<HostTask> keep;
+        for (size_t t = 0; t < ht.size(); ++t) {
+            if (!move[t]) {
+                keep.push_back(ht[t]);
+                continue;
+            }
+            for (uint32_t l = 0; l < ht[t].count; ++l) stripe_pairs.push_back(order[ht[t].first + l]);
+        }
+        ht.swap(keep);
+        std::sort(stripe_pairs.begin(), stripe_pairs.end());
+    }
     DevBuf d_scores, d_ops, d_nops, d_queue, d_hand;
     HIPC(ctx, d_scores.alloc(n_pairs * sizeof(int32_t)));
     HIPC(ctx, d_nops.alloc(n_pairs * sizeof(uint32_t)));
@@ -2058,7 +2259,13 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
     HIPC(ctx, d_ops.alloc(ops_total));
     const uint64_t half = ((max_m + 3) / 4 + 1) * 192 * 4;   // int32 per half: three int4 per lane per 4-column block
     const uint32_t grid_cap = (uint32_t)std::min<uint64_t>(ht.size(), (uint64_t)ctx->num_cu * 2);
-    HIPC(ctx, d_hand.alloc((size_t)grid_cap * 2 * half * sizeof(int32_t)));
+    if (grid_cap) HIPC(ctx, d_hand.alloc((size_t)grid_cap * 2 * half * sizeof(int32_t)));
+    std::vector<uint32_t> h_nops(n_pairs, 0);
+    {
+        const int rc = affine_tb_on_stripes(ctx, stripe_pairs, pair_a, pair_b, slen, arena.as<uint8_t>(), aoff, match, mismatch, gap_open,
+                                            gap_extend, d_scores.as<int32_t>(), d_ops.as<uint8_t>(), dev_ops_off, free_b, h_nops);
+        if (rc != PWA_OK) return rc;
+    }
 
     // ---- chunks of tasks whose code bands fit the budget
     for (size_t t0 = 0; t0 < ht.size();) {
@@ -2139,10 +2346,16 @@ int pwa_align_affine_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, 
         t0 = t1;
     }
     std::vector<int32_t> h_scores(n_pairs);
-    std::vector<uint32_t> h_nops(n_pairs);
     std::vector<uint8_t> h_ops(ops_total);
     HIPC(ctx, hipMemcpy(h_scores.data(), d_scores.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPC(ctx, hipMemcpy(h_nops.data(), d_nops.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    {   // the strip walk's counts; the stripe pairs' came back with their results
+        std::vector<uint32_t> strip_nops(n_pairs);
+        HIPC(ctx, hipMemcpy(strip_nops.data(), d_nops.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> on_stripes(n_pairs, 0);
+        for (uint32_t k : stripe_pairs) on_stripes[k] = 1;
+        for (uint32_t k : live)
+            if (!on_stripes[k]) h_nops[k] = strip_nops[k];
+    }
     HIPC(ctx, hipMemcpy(h_ops.data(), d_ops.p, ops_total, hipMemcpyDeviceToHost));
     for (uint32_t k : live) {
         score_out[k] = h_scores[k];
@@ -3024,6 +3237,15 @@ int pwa_align_last_stats(const pwa_ctx* ctx, float* fill_ms, float* traceback_ms
     if (fill_ms) *fill_ms = ctx->fill_ms;
     if (traceback_ms) *traceback_ms = ctx->tb_ms;
     if (band_bytes) *band_bytes = ctx->band_bytes;
+    return PWA_OK;
+}
+
+int pwa_align_affine_last_stats(const pwa_ctx* ctx, uint64_t* stripe_pairs, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
+    if (!ctx) return PWA_E_INVALID;
+    if (stripe_pairs) *stripe_pairs = ctx->aff_stripe_pairs;
+    if (fill_ms) *fill_ms = ctx->aff_fill_ms;
+    if (walk_ms) *walk_ms = ctx->aff_walk_ms;
+    if (band_bytes) *band_bytes = ctx->aff_band_bytes;
     return PWA_OK;
 }
 

@@ -45,7 +45,10 @@
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
- *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list)
+ *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
+ *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
+ *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
+ *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
  *   PWA_NO_PAIR_TABLE, PWA_NO_KEYED_TB, PWA_NO_GAP_SHIFT, PWA_NO_TILED_OPS, PWA_NO_PACKED_DIST, PWA_FORCE_LANES,
  *   PWA_FORCE_R, PWA_FORCE_MODE, PWA_FORCE_RL, PWA_FORCE_W, PWA_WG_PER_CU, PWA_MINI_PER_CU, PWA_NO_LDS_PAD, PWA_STAMPS,
  *   PWA_TRACE_STRIPE
@@ -177,8 +180,14 @@ int pwa_scores_affine(pwa_ctx *ctx, int match, int mismatch, int gap_open, int g
  * The alignments hw3.cpp builds against the center of the star (hw3.cpp:261-283): affine_alignment(string1, string2,
  * ..., &alignedString1, &alignedString2), i.e. hw3.cpp:23-135 with its three trace matrices, its tie-breaks (V,
  * then F if strictly greater, then E if strictly greater; a gap is extended only if that is strictly better than
- * opening one) and its walk.  pair (a, b): string1 = sequence a, string2 = sequence b.  Pairs that share string1
- * (the center) are processed 64 to a wavefront.
+ * opening one) and its walk.  pair (a, b): string1 = sequence a, string2 = sequence b.
+ * Engines: pairs that share string1 (the center) form wave tasks of up to 64 pairs, one lane each, on the strip kernels
+ * (batch_affine_tb.hip.h); a task moves to the stripe engine (pair_affine_tb.hip.h: each pair over ceil(n / 256) waves, then one
+ * wave walks it) when that is estimated to be faster -- few long pairs -- or when its strip band would not fit the HBM budget.
+ * Only lists with (n + m + 2) * max(|M|, |Mm|, |Go| + |Ge|) < 2^26 qualify; every other list stays on the strips.  The stripe
+ * pairs run in consecutive chunks whose bands (~n * (m + 80) bytes per pair) fit min(0.6 free HBM, 48 GiB); a single pair whose
+ * band exceeds free HBM fails with PWA_E_NOMEM.  Both engines give the reference's op lists byte for byte.
+ * PWA_AFFINE_TB_ROUTE=0 keeps every pair on the strips, =1 moves every task of a qualifying list.
  *   score_out[k] : max(V, F, E)[n][m] as pwa_scores_affine
  *   ops          : one byte per alignment column in TRACEBACK order (end -> start), pair k at ops[ops_off[k] ..):
  *                  'M' both symbols, 'D' string1 symbol against '-', 'I' '-' against string2 symbol; the caller
@@ -187,6 +196,9 @@ int pwa_scores_affine(pwa_ctx *ctx, int match, int mismatch, int gap_open, int g
 int pwa_align_affine_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
                            const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
                            uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off, uint64_t *n_ops);
+/* The last pwa_align_affine_batch on ctx: pairs it ran on the stripe engine, device ms of their fills and of their walks
+ * (event-timed, summed over chunks), and the bytes of traceback band those fills wrote. */
+int pwa_align_affine_last_stats(const pwa_ctx *ctx, uint64_t *stripe_pairs, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
 
 /*
  * The all-pairs step of the sibling program /root/reference/hw4/hw4.cpp (138-159): per pair a
