@@ -21,6 +21,8 @@ LIB_PATH = os.environ.get("PWA_LIB") or os.path.join(_HERE, "libpwalign.so")   #
 CLI_PATH = os.path.join(_HERE, "host", "hw2_amd")
 HW3_CLI_PATH = os.path.join(_HERE, "host", "hw3_amd")
 CLI4_PATH = os.path.join(_HERE, "host", "hw4_amd")
+HW1_CLI_PATH = os.path.join(_HERE, "host", "hw1_amd")
+HW1_HOST_PATH = os.path.join(_HERE, "libhw1_host.so")   # hw1's reader and DOT writer (host only, host/hw1_host.h)
 
 MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1}
 
@@ -30,11 +32,76 @@ EXPORTS = [
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_overlaps",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
+    "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
 ]
 
 
 class PwaError(RuntimeError):
     pass
+
+
+_hw1 = None
+
+
+def hw1_host():
+    """libhw1_host.so: hw1's readSequences and DOT writer (host code only; loads without a GPU)."""
+    global _hw1
+    if _hw1 is None:
+        H = C.CDLL(HW1_HOST_PATH)
+        vp, u32p, u64p = C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        H.hw1_read_sequences.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+        H.hw1_read_sequences.restype = vp
+        H.hw1_records_count.argtypes = [vp]
+        H.hw1_records_count.restype = C.c_uint32
+        for f in (H.hw1_records_header, H.hw1_records_sequence):
+            f.argtypes = [vp, C.c_uint32, u64p]
+            f.restype = vp
+        H.hw1_records_free.argtypes = [vp]
+        H.hw1_records_free.restype = None
+        H.hw1_terminator.argtypes = [C.c_uint32, C.c_uint32]
+        H.hw1_write_dot.argtypes = [C.c_char_p, vp, C.c_uint32, u32p, C.c_uint32, u32p, C.POINTER(C.c_char_p), u64p]
+        _hw1 = H
+    return _hw1
+
+
+def hw1_read_sequences(path):
+    """readSequences of the hw1 reference -> (list of (header bytes, sequence bytes), opened)"""
+    H = hw1_host()
+    ok = C.c_int(0)
+    h = H.hw1_read_sequences(os.fsencode(path), C.byref(ok))
+    try:
+        out = []
+        for i in range(H.hw1_records_count(h)):
+            rec = []
+            for f in (H.hw1_records_header, H.hw1_records_sequence):
+                n = C.c_uint64(0)
+                p = f(h, i, C.byref(n))
+                rec.append(C.string_at(p, n.value) if n.value else b"")
+            out.append(tuple(rec))
+        return out, bool(ok.value)
+    finally:
+        H.hw1_records_free(h)
+
+
+def hw1_text(refs):
+    """(T, ref_start, headers) of hw1: each reference's sequence followed by its terminator"""
+    H = hw1_host()
+    text, starts = bytearray(), []
+    for i, (_, seq) in enumerate(refs):
+        starts.append(len(text))
+        text += seq + bytes([H.hw1_terminator(len(refs), i)])
+    starts.append(len(text))
+    return bytes(text), starts, [h for h, _ in refs]
+
+
+def hw1_write_dot(path, text, sa, ref_start, headers):
+    H = hw1_host()
+    n_ref = len(headers)
+    sa_a = (C.c_uint32 * max(len(sa), 1))(*sa)
+    rs = (C.c_uint32 * len(ref_start))(*ref_start)
+    hp = (C.c_char_p * max(n_ref, 1))(*headers)
+    hl = (C.c_uint64 * max(n_ref, 1))(*[len(h) for h in headers])
+    return H.hw1_write_dot(os.fsencode(path), text, len(text), sa_a, n_ref, rs, hp, hl)
 
 
 _lib = None
@@ -105,6 +172,13 @@ def lib():
     L.pwa_fasta_first_seq.restype = u32p
     L.pwa_fasta_free.argtypes = [vp]
     L.pwa_fasta_free.restype = None
+    L.pwa_sa_create.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
+    L.pwa_sa_fetch.argtypes = [vp, u32p]
+    L.pwa_sa_find.argtypes = [vp, vp, u64p, C.c_uint32, u32p]
+    L.pwa_sa_occurrences.argtypes = [vp, vp, u64p, C.c_uint32, u32p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
+    L.pwa_sa_last_stats.argtypes = [vp, u32p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pwa_sa_destroy.argtypes = [vp]
+    L.pwa_sa_destroy.restype = None
     _lib = L
     return L
 
@@ -410,6 +484,58 @@ class Context:
         p, f, w, b = C.c_uint64(0), C.c_float(0), C.c_float(0), C.c_uint64(0)
         self._check(self._L.pwa_align_affine_last_stats(self._h, C.byref(p), C.byref(f), C.byref(w), C.byref(b)), "pwa_align_affine_last_stats")
         return dict(stripe_pairs=p.value, fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
+
+
+    # -- hw1: suffix array of one text, exact pattern search (include/pwalign.h, pwa_sa_*)
+    def _sa_index(self, text):
+        text = _b(text)
+        ix = C.c_void_p()
+        self._check(self._L.pwa_sa_create(self._h, text, len(text), C.byref(ix)), "pwa_sa_create")
+        return ix
+
+    def _sa_stats(self, ix):
+        r, b, s = C.c_uint32(0), C.c_float(0), C.c_float(0)
+        self._L.pwa_sa_last_stats(ix, C.byref(r), C.byref(b), C.byref(s))
+        self.sa_stats = dict(rounds=r.value, build_ms=b.value, search_ms=s.value)
+
+    def suffix_array(self, text):
+        """The suffixes of text in signed-char order, as a list of start positions (built on the device)."""
+        ix = self._sa_index(text)
+        try:
+            n = len(text)
+            out = (C.c_uint32 * max(n, 1))()
+            self._check(self._L.pwa_sa_fetch(ix, out), "pwa_sa_fetch")
+            self._sa_stats(ix)
+            return list(out[:n])
+        finally:
+            self._L.pwa_sa_destroy(ix)
+
+    def find(self, text, patterns, refs=None):
+        """refs None: per pattern, the number of its occurrences anywhere in text.  refs = (ref_start, header_rank): reference r is
+        text[ref_start[r]:ref_start[r + 1]] with its terminator last; per pattern, the sorted list of (header_rank, local position)
+        of its occurrences that do not start on a terminator."""
+        blob, off, pats = pack_sequences(patterns)
+        n_pat = len(pats)
+        ix = self._sa_index(text)
+        try:
+            cnt = (C.c_uint32 * max(n_pat, 1))()
+            self._check(self._L.pwa_sa_find(ix, blob, off, n_pat, cnt), "pwa_sa_find")
+            if refs is None:
+                self._sa_stats(ix)
+                return list(cnt[:n_pat])
+            ref_start, header_rank = refs
+            rs = (C.c_uint32 * len(ref_start))(*ref_start)
+            hr = (C.c_uint32 * max(len(header_rank), 1))(*header_rank)
+            cap = sum(cnt[:n_pat])
+            occ_off = (C.c_uint64 * (n_pat + 1))()
+            occ = (C.c_uint64 * max(cap, 1))()
+            need = C.c_uint64(0)
+            self._check(self._L.pwa_sa_occurrences(ix, blob, off, n_pat, rs, len(ref_start) - 1, hr, occ_off, occ, cap, C.byref(need)),
+                        "pwa_sa_occurrences")
+            self._sa_stats(ix)
+            return [[(occ[e] >> 32, occ[e] & 0xffffffff) for e in range(occ_off[k], occ_off[k + 1])] for k in range(n_pat)]
+        finally:
+            self._L.pwa_sa_destroy(ix)
 
 
 class Batch:

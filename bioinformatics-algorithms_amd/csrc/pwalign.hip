@@ -22,6 +22,7 @@
 
 #include "kernel_table.h"
 #include "batch_affine_tb.hip.h"
+#include "sufarr_ctx.h"
 
 using namespace pwa;
 
@@ -102,6 +103,7 @@ struct Knobs {
                                                 // pair on the stripe engine, unset = by estimated cost and band size
     int cell16 = -1;                            // PWA_CELL16: 0 = never the packed f16 cells (two pairs per lane), 1 = always where the batch
                                                 // admits them, unset = by estimated cost (batch_create_impl)
+    uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
     void read() {
@@ -133,6 +135,7 @@ struct Knobs {
         tb_engine = num("PWA_TB_ENGINE", -1);
         cell16 = num("PWA_CELL16", -1);
         affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
+        if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     }
 };
 
@@ -180,7 +183,17 @@ struct pwa_ctx {
     enum { PIN_ARENA, PIN_ARENA2, PIN_TASKS, PIN_SLOT0, PIN_SLOT1, PIN_SLOT2, PIN_SLOT3, PIN_SLOT4, PIN_DESC, PIN_TL, PIN_RES, PIN_BOUNCE, PIN_N };
     PinnedBuf pin[PIN_N];
 };
-constexpr size_t kBandCacheMax = 64ull << 30;   // (288 GB of HBM per GPU: a 4096-pair batch with both bands is 33 GB)
+constexpr size_t kBandCacheMax = 64ull << 30;
+
+pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
+    SaCtxView v;
+    v.device = c->device;
+    v.stream = c->stream;
+    v.debug = c->knobs.debug;
+    v.occ_chunk_hits = c->knobs.occ_chunk_hits;
+    v.err = &c->err;
+    return v;
+}   // (288 GB of HBM per GPU: a 4096-pair batch with both bands is 33 GB)
 
 namespace {
 

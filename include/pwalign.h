@@ -47,6 +47,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
+ *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
  *   PWA_NO_PAIR_TABLE, PWA_NO_KEYED_TB, PWA_NO_GAP_SHIFT, PWA_NO_TILED_OPS, PWA_NO_PACKED_DIST, PWA_FORCE_LANES,
@@ -297,6 +298,36 @@ const uint8_t *pwa_fasta_bytes(const pwa_fasta *f);
 const uint64_t *pwa_fasta_offsets(const pwa_fasta *f);   /* n_seq + 1 */
 const uint32_t *pwa_fasta_first_seq(const pwa_fasta *f); /* n_paths + 1 */
 void pwa_fasta_free(pwa_fasta *f);
+
+/*
+ * Suffix-array index of one text (hw1, multiple_pattern_matching.cpp): the sorted suffixes that the reference's Ukkonen
+ * tree (50-281) encodes, built on the device by prefix doubling over a device radix sort, then searched by many patterns
+ * at once.  Suffixes are ordered by bytes as SIGNED char (the reference's std::map<char, ...>, 40), a suffix before every
+ * longer one it is a prefix of.
+ *   pwa_sa_create       uploads text[0 .. n) and builds its suffix array on the context's GPU; n < 2^31 (positions are
+ *                       int32 in the reference), PWA_E_CAPACITY otherwise;
+ *   pwa_sa_fetch        sa_out[n]: the suffix array (start positions in sorted order);
+ *   pwa_sa_find         counts_out[n_pat]: exact occurrences of each pattern anywhere in the text (pattern k is
+ *                       pat_bytes[pat_off[k] .. pat_off[k + 1])); an empty pattern occurs at every position;
+ *   pwa_sa_occurrences  the occurrences the reference reports (search 168-200 + the grouping at 390-431): reference r is
+ *                       text[ref_start[r] .. ref_start[r + 1]) whose LAST byte is its terminator (ref_start[0] = 0,
+ *                       ref_start[n_ref] = n, strictly increasing); hits on a terminator are dropped, every other hit p of
+ *                       reference r is the key header_rank[r] << 32 | (p - ref_start[r]).  Pattern k's keys are
+ *                       occ[occ_off[k] .. occ_off[k + 1]) in ascending order (occ_off: n_pat + 1 entries).  Patterns are
+ *                       processed in chunks whose raw hits fit a device budget.  PWA_E_CAPACITY with *needed set when
+ *                       cap < the number of keys (the sum of pwa_sa_find's counts always suffices);
+ *   pwa_sa_last_stats   rounds of the build (the first sort included), device ms of the build (events), host ms of the
+ *                       last find / occurrences call.
+ * The text's positions are searched on the device only: there is no CPU path.
+ */
+typedef struct pwa_sa_index pwa_sa_index;
+int pwa_sa_create(pwa_ctx *ctx, const uint8_t *text, uint64_t n, pwa_sa_index **out);
+int pwa_sa_fetch(pwa_sa_index *ix, uint32_t *sa_out);
+int pwa_sa_find(pwa_sa_index *ix, const uint8_t *pat_bytes, const uint64_t *pat_off, uint32_t n_pat, uint32_t *counts_out);
+int pwa_sa_occurrences(pwa_sa_index *ix, const uint8_t *pat_bytes, const uint64_t *pat_off, uint32_t n_pat, const uint32_t *ref_start,
+                       uint32_t n_ref, const uint32_t *header_rank, uint64_t *occ_off, uint64_t *occ, uint64_t cap, uint64_t *needed);
+int pwa_sa_last_stats(const pwa_sa_index *ix, uint32_t *rounds, float *build_ms, float *search_ms);
+void pwa_sa_destroy(pwa_sa_index *ix);
 
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
