@@ -29,7 +29,7 @@ MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1}
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_scores",
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits",
-    "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_overlaps",
+    "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
@@ -152,6 +152,7 @@ def lib():
     L.pwa_align_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_align_affine_last_stats.argtypes = [vp, u64p, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_align_batch.argtypes = batch_in + [i32p, vp, u64p, u64p, u64p, u64p]
+    L.pwa_align_batch_cigar.argtypes = batch_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
     L.pwa_overlaps.argtypes = batch_in + [i32p, i32p]
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
@@ -416,6 +417,35 @@ class Context:
             res.append(dict(score=sc[k], ops=o, end=(endc[2 * k], endc[2 * k + 1]),
                             start=(startc[2 * k], startc[2 * k + 1])))
         return res
+
+    def align_batch_cigar(self, mode, seqs, pair_a, pair_b, match, mismatch, gap):
+        """pwa_align_batch_cigar: the alignments of align_batch as the reference's CIGAR and MD:Z strings, built on the device ->
+        [dict(score, cigar, mdz, end, start)] (cigar / mdz: bytes).  The buffers are sized by pwa_cigar_bound / pwa_mdz_bound of every
+        pair, which always fit: one call, no retry."""
+        import numpy as np
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        lens = np.array([len(x) for x in seqs] or [0], dtype=np.uint64)
+        nm = lens[np.asarray(pair_a, dtype=np.int64)] + lens[np.asarray(pair_b, dtype=np.int64)] if n else np.zeros(0, np.uint64)
+        cap_c, cap_m = int((2 * nm + 24).sum()), int((3 * nm + 24).sum())   # pwa_cigar_bound / pwa_mdz_bound (host/postprocess.cpp)
+        cg = np.empty(max(cap_c, 1), dtype=np.uint8)
+        md = np.empty(max(cap_m, 1), dtype=np.uint8)
+        cg_off = np.zeros(n + 1, dtype=np.uint64)
+        md_off = np.zeros(n + 1, dtype=np.uint64)
+        sc = (C.c_int32 * max(n, 1))()
+        endc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint64 * (2 * max(n, 1)))()
+        u64p = C.POINTER(C.c_uint64)
+        rc = self._L.pwa_align_batch_cigar(self._h, MODE[mode], match, mismatch, gap, blob, off, len(seqs), pa, pb, n, sc,
+                                           cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
+                                           md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None)
+        self._check(rc, "pwa_align_batch_cigar")
+        co, mo = cg_off.tolist(), md_off.tolist()
+        cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
+        return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
+                     start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
     def align_batch_arrays(self, mode, packed, pair_a, pair_b, match, mismatch, gap, out=None):
         """pwa_align_batch on caller-held buffers, the way a compiled host calls it: `packed` = pack_sequences(seqs) done once,

@@ -22,7 +22,12 @@
 
 #include "kernel_table.h"
 #include "batch_affine_tb.hip.h"
+#include "cigar.hip.h"
 #include "sufarr_ctx.h"
+
+namespace pwa {
+hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
+}
 
 using namespace pwa;
 
@@ -165,8 +170,9 @@ struct pwa_ctx {
     size_t hand_cache_bytes = 0;
     // pwa_align* work buffers (sequence arena, op lists, results, pair descriptors, task list, hand-off rows, progress words,
     // per-stripe bests, queue): grow-only, reused by the next call -- a call that aligns a batch costs no hipMalloc / hipFree
-    // (each of which also synchronises the device) once the context has seen a batch of that size
-    enum { POOL_ARENA, POOL_OPS, POOL_RES, POOL_DESC, POOL_TASKS, POOL_ROWS, POOL_PROGRESS, POOL_BEST, POOL_QUEUE, POOL_N };
+    // (each of which also synchronises the device) once the context has seen a batch of that size; pwa_align_batch_cigar's
+    // strings and their pair list / lengths / scan partials
+    enum { POOL_ARENA, POOL_OPS, POOL_RES, POOL_DESC, POOL_TASKS, POOL_ROWS, POOL_PROGRESS, POOL_BEST, POOL_QUEUE, POOL_STR, POOL_STR_AUX, POOL_N };
     void* pool[POOL_N] = {};
     size_t pool_bytes[POOL_N] = {};
     // page-locked staging of everything the library itself uploads or reads back (see PinnedBuf)
@@ -180,7 +186,7 @@ struct pwa_ctx {
     // overlap of preparing run k + 1 with computing run k would be gone (scores_in_arena_chunks).
     std::vector<std::pair<void*, size_t>> free_list;
     size_t free_list_bytes = 0;
-    enum { PIN_ARENA, PIN_ARENA2, PIN_TASKS, PIN_SLOT0, PIN_SLOT1, PIN_SLOT2, PIN_SLOT3, PIN_SLOT4, PIN_DESC, PIN_TL, PIN_RES, PIN_BOUNCE, PIN_N };
+    enum { PIN_ARENA, PIN_ARENA2, PIN_TASKS, PIN_SLOT0, PIN_SLOT1, PIN_SLOT2, PIN_SLOT3, PIN_SLOT4, PIN_DESC, PIN_TL, PIN_RES, PIN_BOUNCE, PIN_STR, PIN_N };
     PinnedBuf pin[PIN_N];
 };
 constexpr size_t kBandCacheMax = 64ull << 30;
@@ -2719,16 +2725,27 @@ struct TbClass {
     int rl, w;   // mini: rows per lane (w unused); stripe engine: its PairGeom
     bool operator==(const TbClass& o) const { return mini == o.mini && rl == o.rl && w == o.w; }
 };
+// pwa_align_batch_cigar: the walks' op lists stay on the device; per range the CIGAR / MD:Z passes (cigar.hip.h) pack the strings and
+// only those come back, at the running offsets
+struct StrOut {
+    char *cigar, *mdz;
+    uint64_t cigar_cap, mdz_cap;
+    uint64_t *cigar_off, *mdz_off, *needed;
+};
+// bytes a pair's two strings can take: the range's string buffer is sized by this, and a range's total stays below 2^32 (the scan is 32-bit)
+uint64_t str_bound(uint64_t n_plus_m) { return pwa_cigar_bound(n_plus_m) + pwa_mdz_bound(n_plus_m); }
 }  // namespace
 
 static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes,
                             const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                             uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops,
-                            uint64_t* end_cells, uint64_t* start_cells, int32_t* overlap_out) try {
+                            uint64_t* end_cells, uint64_t* start_cells, int32_t* overlap_out, const StrOut* str) try {
     if (!ctx) return PWA_E_INVALID;
     if (mode != PWA_MODE_NW && mode != PWA_MODE_SW) return fail(ctx, PWA_E_INVALID, "unknown mode");
-    const bool want_ops = ops != nullptr;
-    if (!seq_off || !score_out || (want_ops && (!ops_off || !n_ops)) || (!want_ops && !overlap_out) ||
+    const bool want_ops = ops != nullptr, want_str = str != nullptr;
+    const bool walk_ops = want_ops || want_str;   // WALK_OPS; the op lists come back (want_ops) or are formatted on the device (want_str)
+    if (!seq_off || !score_out || (want_ops && (!ops_off || !n_ops)) || (!walk_ops && !overlap_out) ||
+        (want_str && (!str->cigar_off || !str->mdz_off || (str->cigar_cap && !str->cigar) || (str->mdz_cap && !str->mdz))) ||
         (n_pairs && (!pair_a || !pair_b)))
         return fail(ctx, PWA_E_INVALID, "null input");
     if (n_pairs >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "more than 2^32-2 pairs in one batch");
@@ -2875,26 +2892,31 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
         uint32_t n_dummy = 0;
     };
     struct Range {
-        uint64_t k0, k1, band, opsb;
+        uint64_t k0, k1, band, opsb, strb;   // strb: string bound of the range (pwa_align_batch_cigar)
         bool tiled;      // the caller's op regions ops_off[k] .. + n_k + m_k of the range's pairs follow one another without a gap:
         uint64_t span;   // the device op buffer then mirrors that range and comes back with ONE copy, straight into `ops`
         std::vector<Launch> launches;
     };
     std::vector<Range> ranges;
-    uint64_t band_cap = 0, ops_cap_b = 0, nc_cap = 0;
+    uint64_t band_cap = 0, ops_cap_b = 0, nc_cap = 0, str_cap = 0;
     for (uint64_t k0 = 0; k0 < n_pairs;) {
-        uint64_t k1 = k0, est = 0, opsb = 0, live_in = 0;
+        uint64_t k1 = k0, est = 0, opsb = 0, live_in = 0, strb = 0;
         while (k1 < n_pairs) {
             const uint64_t n = slen(pair_a[k1]), m = slen(pair_b[k1]);
             if (n > 0x7fffffc0ull || m > 0x7fffffc0ull) return fail(ctx, PWA_E_CAPACITY, "sequence longer than 2^31");
             const uint64_t need = (n && m) ? align_up(band_of(class_of(n), n, m), 256) : 0;
-            if (k1 > k0 && ((est + need) * band_mult + opsb + n + m > chunk_target || (need && live_in >= pairs_target))) break;
+            const uint64_t sneed = want_str ? str_bound(n + m) : 0;
+            if (sneed > 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "strings of one pair may exceed 2^32 bytes");
+            if (k1 > k0 && ((est + need) * band_mult + opsb + n + m > chunk_target || (need && live_in >= pairs_target) ||
+                            strb + sneed > 0xffffffffull))
+                break;
             live_in += need != 0;
             est += need;
             opsb += align_up(n + m + 1, 16);
+            strb += sneed;
             ++k1;
         }
-        Range rg{k0, k1, 0, opsb, want_ops, 0, {}};
+        Range rg{k0, k1, 0, opsb, strb, want_ops, 0, {}};
         // the range's launches: one per class present, pairs in caller order (mini: by text length, so that the four pairs of a
         // wave run about the same number of steps; the band of each is sized for its task's longest text)
         for (uint64_t k = k0; k < k1; ++k) {
@@ -2943,20 +2965,30 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
         band_cap = std::max(band_cap, rg.band);
         ops_cap_b = std::max(ops_cap_b, std::max(opsb, rg.tiled ? rg.span + 16 : 0));
         nc_cap = std::max(nc_cap, k1 - k0);
+        str_cap = std::max(str_cap, rg.strb);
         ranges.push_back(std::move(rg));
         k0 = k1;
     }
     mark("plan: ranges + launches");
-    DevBuf d_band, d_sband, d_ops_own, d_res_own;
-    void *p_band = nullptr, *p_sband = nullptr, *p_ops = nullptr, *p_res = nullptr;
+    DevBuf d_band, d_sband, d_ops_own, d_res_own, d_str_own, d_aux_own;
+    void *p_band = nullptr, *p_sband = nullptr, *p_ops = nullptr, *p_res = nullptr, *p_str = nullptr, *p_aux = nullptr;
+    // pwa_align_batch_cigar's device side per range: the pair list, the 2 nc + 2 string lengths (then offsets), the scan's partials
+    const uint64_t len_words = 2 * nc_cap + 2, aux_len_at = nc_cap * sizeof(CigarPair), aux_part_at = aux_len_at + align_up(len_words * 4, 256);
     if (!ranges.empty()) {
         // + one traceback window: the walk stages whole windows
         HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, band_cap + 32768, d_band, &p_band));
         if (ctx->score_band)
             HIPC(ctx, cached_workspace(ctx->sband_cache, ctx->sband_cache_bytes, band_cap * sizeof(int32_t), d_sband, &p_sband));
-        HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], want_ops ? ops_cap_b : 16, d_ops_own, &p_ops));
+        HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], walk_ops ? ops_cap_b : 16, d_ops_own, &p_ops));
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
+        if (want_str) {
+            HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], str_cap, d_str_own, &p_str));
+            HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR_AUX], ctx->pool_bytes[pwa_ctx::POOL_STR_AUX],
+                                       aux_part_at + pwa::scan_part_words(len_words) * 4, d_aux_own, &p_aux));
+        }
     }
+    uint64_t str_at[2] = {0, 0};   // bytes of CIGAR / MD:Z so far (the output offsets of the next range)
+    float fmt_ms[2] = {0.f, 0.f};
     mark("band / ops allocation");
     if (dbg) std::fprintf(stderr, "[pwa] bands at %p (codes, %.2f GB) %p (scores)\n", p_band, (double)band_cap / 1e9, p_sband);
     uint8_t* const d_ops = static_cast<uint8_t*>(p_ops);
@@ -2968,6 +3000,13 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
         const uint64_t nc = k1 - k0;
         HIPC(ctx, ctx->pin[pwa_ctx::PIN_RES].reserve(nc * sizeof(PairResult)));
         PairResult* const res = ctx->pin[pwa_ctx::PIN_RES].as<PairResult>();   // page-locked: uploaded, and read back after the walk
+        CigarPair* cpairs = nullptr;   // pwa_align_batch_cigar: the range's pair list, then (same page-locked buffer) its string offsets
+        uint32_t* clen = nullptr;
+        if (want_str) {
+            HIPC(ctx, ctx->pin[pwa_ctx::PIN_STR].reserve(nc * sizeof(CigarPair) + (2 * nc + 2) * 4));
+            cpairs = ctx->pin[pwa_ctx::PIN_STR].as<CigarPair>();
+            clen = reinterpret_cast<uint32_t*>(cpairs + nc);
+        }
         std::vector<uint64_t> ooff(nc);
         uint64_t oo = 0;
         const uint64_t ops_lo = (want_ops && nc) ? ops_off[k0] : 0;
@@ -2981,9 +3020,11 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
                 res[q].end_i = (uint32_t)n;
                 res[q].end_j = (uint32_t)m;
             }
+            if (want_str) cpairs[q] = CigarPair{aoff[pair_a[k]], aoff[pair_b[k]], ooff[q], (uint32_t)n, (uint32_t)m};
             oo += align_up(n + m + 1, 16);
         }
         HIPC(ctx, hipMemcpy(d_res, res, nc * sizeof(PairResult), hipMemcpyHostToDevice));
+        if (want_str) HIPC(ctx, hipMemcpyAsync(p_aux, cpairs, nc * sizeof(CigarPair), hipMemcpyHostToDevice, ctx->stream));
         mark("range results init");
         for (const Launch& L : rg.launches) {
             const size_t np = L.q.size();
@@ -3000,7 +3041,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
                 d.tb = static_cast<uint8_t*>(p_band) + L.bo[p];
                 if (ctx->score_band) d.sband = static_cast<int32_t*>(p_sband) + L.bo[p];
                 d.res = d_res + q;
-                d.ops = want_ops ? d_ops + ooff[q] : d_ops;   // WALK_OVERLAP never writes ops
+                d.ops = walk_ops ? d_ops + ooff[q] : d_ops;   // WALK_OVERLAP never writes ops
                 d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
                 d.score_bias = gap0 ? wrap_mul((int64_t)(n + m), gap) : 0;
                 pd.push_back(d);
@@ -3026,7 +3067,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             if (dbg) std::fprintf(stderr, "[pwa] fill launch %s RL=%d W|LN=%d grid=%u pairs=%u tasks=%u rows=%llu\n", L.cls.mini ? "mini" : "stripes", L.cls.rl,
                                   L.cls.w, pl.grid, pl.G.n_pairs, pl.G.n_tasks, (unsigned long long)pl.row_bytes);
             HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-            rc = pl.launch(ctx, ctx->stream, local, true, want_ops ? WALK_OPS : WALK_OVERLAP, ctx->ev[1], ctx->score_band);
+            rc = pl.launch(ctx, ctx->stream, local, true, walk_ops ? WALK_OPS : WALK_OVERLAP, ctx->ev[1], ctx->score_band);
             if (rc != PWA_OK) return rc;
             HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
             HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -3038,6 +3079,49 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             HIPC(ctx, hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]));
             ctx->fill_ms += a;
             ctx->tb_ms += c;
+        }
+        if (want_str) {
+            // the strings of the range: lengths, their exclusive scan (= offsets in the string buffer: every CIGAR, then every MD:Z),
+            // the bytes; then the offsets come back and, when they fit the caller's buffers, the two packed blocks
+            CigarParams cp;
+            cp.arena = arena_base;
+            cp.ops = d_ops;
+            cp.res = d_res;
+            cp.pairs = static_cast<const CigarPair*>(p_aux);
+            cp.len = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(p_aux) + aux_len_at);
+            cp.out = static_cast<uint8_t*>(p_str);
+            cp.decode = 0;
+            if (coded)
+                for (int v = 255; v >= 0; --v)
+                    if (seen[v]) cp.decode = cp.decode << 8 | (uint64_t)v;   // code c = the c-th symbol seen, in byte order
+            cp.nc = (uint32_t)nc;
+            cp.coded = coded;
+            cp.local = local;
+            HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+            HIPC(ctx, pwa::cigar_launch(cp, false, ctx->stream));
+            pwa::scan_excl(ctx->stream, cp.len, 2 * nc + 2, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(p_aux) + aux_part_at));
+            HIPC(ctx, hipGetLastError());
+            HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+            HIPC(ctx, pwa::cigar_launch(cp, true, ctx->stream));
+            HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+            HIPC(ctx, hipMemcpyAsync(clen, cp.len, (2 * nc + 2) * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPC(ctx, hipStreamSynchronize(ctx->stream));
+            float a = 0, c = 0;
+            HIPC(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
+            HIPC(ctx, hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]));
+            fmt_ms[0] += a;
+            fmt_ms[1] += c;
+            const uint64_t tot_c = clen[nc], tot_m = (uint64_t)clen[2 * nc + 1] - tot_c;
+            for (uint64_t q = 0; q < nc; ++q) {
+                str->cigar_off[k0 + q] = str_at[0] + clen[q];
+                str->mdz_off[k0 + q] = str_at[1] + (clen[nc + 1 + q] - tot_c);
+            }
+            if (tot_c && str_at[0] + tot_c <= str->cigar_cap) HIPC(ctx, hipMemcpy(str->cigar + str_at[0], p_str, tot_c, hipMemcpyDeviceToHost));
+            if (tot_m && str_at[1] + tot_m <= str->mdz_cap)
+                HIPC(ctx, hipMemcpy(str->mdz + str_at[1], static_cast<uint8_t*>(p_str) + tot_c, tot_m, hipMemcpyDeviceToHost));
+            str_at[0] += tot_c;
+            str_at[1] += tot_m;
+            mark("strings (device) + copy back");
         }
         HIPC(ctx, hipMemcpy(res, d_res, nc * sizeof(PairResult), hipMemcpyDeviceToHost));
         if (want_ops && rg.tiled && rg.span) HIPC(ctx, hipMemcpy(ops + ops_lo, d_ops, rg.span, hipMemcpyDeviceToHost));   // straight into the caller's list
@@ -3077,8 +3161,20 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
         }
         mark("scatter to caller buffers");
     }
-    if (dbg) std::fprintf(stderr, "[pwa] %s: %llu pairs in %zu range(s): fills %.3f ms, walks %.3f ms (device), %.2f GB of band written\n", want_ops ? "align_batch" : "overlaps",
-                          (unsigned long long)n_pairs, ranges.size(), ctx->fill_ms, ctx->tb_ms, (double)ctx->band_bytes / 1e9);
+    if (dbg) std::fprintf(stderr, "[pwa] %s: %llu pairs in %zu range(s): fills %.3f ms, walks %.3f ms (device), %.2f GB of band written\n",
+                          want_ops ? "align_batch" : want_str ? "align_batch_cigar" : "overlaps", (unsigned long long)n_pairs, ranges.size(), ctx->fill_ms,
+                          ctx->tb_ms, (double)ctx->band_bytes / 1e9);
+    if (want_str) {
+        if (dbg) std::fprintf(stderr, "[pwa] strings: count + scan %.3f ms, write %.3f ms (device); %llu B of CIGAR, %llu B of MD:Z\n", fmt_ms[0], fmt_ms[1],
+                              (unsigned long long)str_at[0], (unsigned long long)str_at[1]);
+        str->cigar_off[n_pairs] = str_at[0];
+        str->mdz_off[n_pairs] = str_at[1];
+        if (str->needed) {
+            str->needed[0] = str_at[0];
+            str->needed[1] = str_at[1];
+        }
+        if (str_at[0] > str->cigar_cap || str_at[1] > str->mdz_cap) return fail(ctx, PWA_E_CAPACITY, "CIGAR / MD:Z strings exceed the buffers");
+    }
     return PWA_OK;
 } catch (const std::bad_alloc&) {
     return fail(ctx, PWA_E_NOMEM, "host allocation failed");
@@ -3094,7 +3190,16 @@ int pwa_align_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, co
                     uint64_t* end_cells, uint64_t* start_cells) {
     if (ctx && !ops) return fail(ctx, PWA_E_INVALID, "null input");
     return align_batch_impl(ctx, mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, ops,
-                            ops_off, n_ops, end_cells, start_cells, nullptr);
+                            ops_off, n_ops, end_cells, start_cells, nullptr, nullptr);
+}
+
+int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
+                          uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
+                          uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
+                          uint64_t* start_cells, uint64_t needed[2]) {
+    const StrOut str{cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed};
+    return align_batch_impl(ctx, mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, nullptr,
+                            nullptr, nullptr, end_cells, start_cells, nullptr, &str);
 }
 
 int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
@@ -3102,7 +3207,7 @@ int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const
                  int32_t* overlap_out) {
     if (ctx && !overlap_out) return fail(ctx, PWA_E_INVALID, "null input");
     return align_batch_impl(ctx, mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, overlap_out);
+                            nullptr, nullptr, nullptr, nullptr, overlap_out, nullptr);
 }
 
 int pwa_align(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* pattern, uint64_t n,

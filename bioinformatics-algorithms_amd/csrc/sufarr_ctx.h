@@ -1,4 +1,5 @@
-// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign.hip.
+// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign.hip, and the
+// scan of that unit that pwalign.hip borrows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,4 +17,8 @@ struct SaCtxView {
     std::string* err = nullptr;      // the context's last-error text
 };
 SaCtxView sa_ctx_view(pwa_ctx* c);
+// The suffix-array unit's reduce-then-scan over uint32 (sufarr_kernels.hip), enqueued on s: x[0 .. len) := its exclusive prefix
+// sums, in place; part is a device workspace of scan_part_words(len) words.
+void scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part);
+size_t scan_part_words(size_t len);
 }  // namespace pwa

@@ -55,14 +55,20 @@ void check(hipError_t e, const char* what) {
 
 inline uint32_t blocks_for(size_t n, size_t per) { return (uint32_t)((n + per - 1) / per); }
 
-// x[0 .. len) := exclusive prefix sums, in place (reduce, scan of the chunk sums, apply); part: len / kTile + 1 words
-void scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part) {
+}  // namespace
+
+// x[0 .. len) := exclusive prefix sums, in place (reduce, scan of the chunk sums, apply); part: scan_part_words(len) words.
+// Also the scan of pwa_align_batch_cigar's string lengths (pwalign.hip), hence outside this unit's anonymous namespace.
+size_t pwa::scan_part_words(size_t len) { return len / kTile + 1; }
+void pwa::scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part) {
     if (!len) return;
     const uint32_t nb = blocks_for(len, kTile);
     scan_reduce_kernel<<<nb, kThreads, 0, s>>>(x, len, part);
     scan_partials_kernel<<<1, kThreads, 0, s>>>(part, nb);
     scan_apply_kernel<<<nb, kThreads, 0, s>>>(x, len, part);
 }
+
+namespace {
 
 // Buffers of a stable LSD radix sort of n (key, value) pairs: k[cur] / v[cur] hold the input and, afterwards, the result.
 template <class K, class V>
@@ -101,7 +107,7 @@ int radix_sort(hipStream_t s, SortBufs<K, V>& b, size_t n, SortScratch& sc) {
         if (((vary >> sh) & (K)(kBuckets - 1)) == 0) continue;
         uint32_t* hist = sc.hist.as<uint32_t>();
         radix_hist_kernel<K><<<tiles, kThreads, 0, s>>>(b.k[b.cur], n, sh, hist, tiles);
-        scan_excl(s, hist, (size_t)tiles * kBuckets, sc.part.as<uint32_t>());
+        pwa::scan_excl(s, hist, (size_t)tiles * kBuckets, sc.part.as<uint32_t>());
         radix_scatter_kernel<K, V><<<tiles, kThreads, 0, s>>>(b.k[b.cur], b.v[b.cur], b.k[b.cur ^ 1], b.v[b.cur ^ 1], n, sh, hist, tiles);
         b.cur ^= 1;
         ++passes;
@@ -215,7 +221,7 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
             uint32_t h = (uint32_t)k;
             for (;;) {
                 sa_heads_kernel<<<blocks_for(n + 1, kThreads), kThreads, 0, v.stream>>>(b.k[b.cur], nn, head.as<uint32_t>());
-                scan_excl(v.stream, head.as<uint32_t>(), n + 1, sc.part.as<uint32_t>());
+                pwa::scan_excl(v.stream, head.as<uint32_t>(), n + 1, sc.part.as<uint32_t>());
                 uint32_t groups = 0;
                 SA_CHECK(hipMemcpyAsync(&groups, head.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, v.stream));
                 SA_CHECK(hipStreamSynchronize(v.stream));
@@ -325,7 +331,7 @@ int pwa_sa_occurrences(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_
                 uint32_t* d_off = off.as<uint32_t>();
                 SA_CHECK(hipMemcpyAsync(d_off, r.cnt.as<uint32_t>() + p0, (size_t)np * 4, hipMemcpyDeviceToDevice, v.stream));
                 SA_CHECK(hipMemsetAsync(d_off + np, 0, 4, v.stream));
-                scan_excl(v.stream, d_off, (size_t)np + 1, sc.part.as<uint32_t>());
+                pwa::scan_excl(v.stream, d_off, (size_t)np + 1, sc.part.as<uint32_t>());
                 SortBufs<uint64_t, uint32_t> s1{{key.as<uint64_t>(), key.as<uint64_t>() + max_hits}, {pid.as<uint32_t>(), pid.as<uint32_t>() + max_hits}, 0};
                 occ_gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->d_sa, r.lo.as<uint32_t>() + p0, d_off, np, (uint32_t)total,
                                                                                           d_ref.as<uint32_t>(), n_ref, d_rank.as<uint32_t>(), s1.k[0], s1.v[0]);

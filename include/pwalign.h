@@ -271,6 +271,25 @@ int pwa_align_batch(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, co
                     uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */);
 
 /*
+ * The same alignments as pwa_align_batch (same arguments, same score_out / end_cells / start_cells), returned as the two
+ * strings the reference derives from each walk -- prepareCigarString (hw2.cpp:59-78) and prepareMDZString (80-116) -- instead
+ * of the op lists.  The strings are built on the device right after each range's walks, and only they cross to the host.
+ *   pair k's CIGAR is cigar[cigar_off[k] .. cigar_off[k + 1]), its MD:Z mdz[mdz_off[k] .. mdz_off[k + 1]) (n_pairs + 1 offsets each,
+ *   written by the library); the strings are packed back to back in pair order, without NUL terminators, and are exactly the
+ *   bytes pwa_format_alignment gives for that pair's op list (any byte value may appear, '-' and NUL included).  A pair with
+ *   one side empty: NW "nD" / "0^<pattern>0" (empty text), "mI" / "0" (empty pattern); SW: "" / "0", as for a zero score.
+ *   PWA_E_CAPACITY when the strings exceed cigar_cap / mdz_cap: needed (when not NULL) receives the two totals, and the string
+ *   buffers are undefined.  The sums over the pairs of pwa_cigar_bound(n_k + m_k) and pwa_mdz_bound(n_k + m_k) always suffice.
+ */
+int pwa_align_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, const uint8_t *seq_bytes,
+                          const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                          uint64_t n_pairs, int32_t *score_out,
+                          char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                          char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                          uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                          uint64_t needed[2] /* or NULL */);
+
+/*
  * The -g selection without the op lists: hw2.cpp:342-350 keeps, of every pair's global alignment, only
  * overlapLongestExactMatch(alignedPattern, alignedReference) (hw2.cpp:267-278) and the score.  Same fill and
  * traceback band as pwa_align_batch; the device walk looks at the symbols under each run of diagonal moves
