@@ -24,7 +24,7 @@ CLI4_PATH = os.path.join(_HERE, "host", "hw4_amd")
 HW1_CLI_PATH = os.path.join(_HERE, "host", "hw1_amd")
 HW1_HOST_PATH = os.path.join(_HERE, "libhw1_host.so")   # hw1's reader and DOT writer (host only, host/hw1_host.h)
 
-MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1}
+MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1, "sg": 2, "semiglobal": 2}   # sg: semi-global (pwalign.h, PWA_MODE_SG)
 
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_scores",

@@ -40,6 +40,7 @@ struct CigarParams {
     uint64_t decode;          // coded arena: byte c = the symbol of code c
     uint32_t nc;
     int coded, local;
+    int semi;                 // semi-global (PWA_MODE_SG): a pair with an empty side is all D (m = 0) or nothing (n = 0)
 };
 
 namespace cigar {
@@ -80,10 +81,10 @@ __global__ __launch_bounds__(256) void cigar_kernel(const CigarParams a) {
     const uint64_t lt = (1ull << lane) - 1;
     const CigarPair P = a.pairs[q];
     const PairResult R = a.res[q];
-    const bool one_side = !(P.n && P.m);   // NW: the boundary walk (all D or all I), SW: nothing; the walk never saw the pair
+    const bool one_side = !(P.n && P.m);   // NW: the boundary walk (all D or all I), SW: nothing, SG: column 0 (all D); the walk never saw the pair
     uint32_t n_ops, i, j;
     if (one_side) {
-        n_ops = a.local ? 0u : P.n + P.m;
+        n_ops = a.local ? 0u : a.semi ? P.n : P.n + P.m;
         i = j = 0;
     } else {
         n_ops = (R.overflow || R.n_ops > P.n + P.m) ? 0u : R.n_ops;   // an overflowed walk: nothing read, the host fails the call

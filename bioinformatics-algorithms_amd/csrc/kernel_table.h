@@ -32,8 +32,10 @@ const BatchKernelEntry* find_batch_kernel(int R, int mode, int score);
 // pair_kernels.hip
 // perm: coded sequences, table scoring (keyed tb only); keyed = false: the plain int32 traceback form (RL = 4 only)
 // gap0: global fill in gap-shifted coordinates (the host passes gap 0 and scores s - 2 gap): perm && keyed && !sband only
-pair_kernel_t pair_fill_kernel_for(int rl, int w, bool local, bool tb, bool sband, bool perm, bool keyed = true, bool gap0 = false, bool band = true);   // band = false: keyed, table scoring, no band at all
-pair_kernel_t pair_traceback_kernel_for(int rl, bool local, int walk);   // walk: WALK_NONE / WALK_OPS / WALK_OVERLAP
+// semi = true: the semi-global form of the same fills and walks (local = false, no gap0, no overlap walk; pair_fill.hip.h, SEMI)
+pair_kernel_t pair_fill_kernel_for(int rl, int w, bool local, bool tb, bool sband, bool perm, bool keyed = true, bool gap0 = false, bool band = true,
+                                   bool semi = false);   // band = false: keyed, table scoring, no band at all
+pair_kernel_t pair_traceback_kernel_for(int rl, bool local, int walk, bool semi = false);   // walk: WALK_NONE / WALK_OPS / WALK_OVERLAP
 // pair_dist_kernels.hip -- hw4's NW distance on the stripe engine (rl = 2 | 4, w = 1 | 4): no band, no walk, D[n][m] straight into
 // PairParams::scores_out
 pair_kernel_t pair_dist_kernel_for(int rl, int w);
@@ -49,7 +51,7 @@ pair_kernel_t pair_affine_walk_kernel_for(int rl);
 // rl in kMiniRL; gap0 only global without score band; the walks over its band geometry (BandGeo<16, rl>)
 constexpr int kMiniRL[] = {4, 6, 8, 10, 12, 16};
 // ln = 16: four pairs per wave (rl in kMiniRL); ln = 64: one pair per wave, rl = 8 | 16 (single stripes of 512 / 1024 rows; band only)
-pair_kernel_t mini_fill_kernel_for(int rl, bool local, bool sband, bool gap0, bool band = true, int ln = 16);   // band = false: scores (+ end cells) only
-pair_kernel_t mini_traceback_kernel_for(int rl, bool local, int walk, int ln = 16);
+pair_kernel_t mini_fill_kernel_for(int rl, bool local, bool sband, bool gap0, bool band = true, int ln = 16, bool semi = false);   // band = false: scores (+ end cells) only
+pair_kernel_t mini_traceback_kernel_for(int rl, bool local, int walk, int ln = 16, bool semi = false);
 
 }  // namespace pwa

@@ -57,15 +57,18 @@ __device__ __forceinline__ int mini_pick_lane0(int dst, int v) {
 
 // 16 steps of four pairs.  GUARD: some lane of the wave is outside its matrix at some step of the chunk (the first 15
 // steps, and from the shortest text's last column on): that lane's state is frozen (pair_fill.hip.h, keyed_chunk).
-template <int RL, bool LOCAL, bool SBAND, bool GUARD, bool GAP0, bool BAND = true, int LN = 16>
+// SEMI (semi-global): the lane that owns row n keeps the first maximum of that row (sg_v: its stored value, sg_t: the step) -- see
+// sg_track in pair_fill.hip.h.
+template <int RL, bool LOCAL, bool SBAND, bool GUARD, bool GAP0, bool BAND = true, int LN = 16, bool SEMI = false>
 __device__ __forceinline__ void mini_chunk(const int t0, const int k, const int m, const uint32_t (&pk)[(RL + 3) / 4], int (&hl)[RL], int& diag0,
                                            int& bottom, int& tch, const int tcv, const int top0, const int top_inc, int (&bs)[RL], int (&bj)[RL],
                                            const uint32_t tab_lo, const uint32_t tab_hi, const int cl, g_u8* const tba, g_u8* const tbb,
-                                           g_i32* const sb) {
+                                           g_i32* const sb, const int (&own)[RL], int& sg_v, int& sg_t) {
     typedef BandGeo<LN, RL> Geo;
     constexpr int NQ = (RL + 3) / 4;
     constexpr int PU = TbCode<LOCAL>::UP, PL = TbCode<LOCAL>::LEFT;
     static_assert(!GAP0 || (!LOCAL && !SBAND && PU == 0), "gap-shifted fills: global, no score band");
+    static_assert(!SEMI || (!LOCAL && !GAP0), "semi-global fills: global cells in plain coordinates");
     static_assert(LN == 16 || (LN == 64 && (RL == 6 || RL == 8 || RL == 12 || RL == 16)), "one pair per wave: single stripes of 384 .. 1024 rows");
     const int cu = p_addw(cl, PU - PL);
     // LOCAL: the first maximum of every row (hw2.cpp:225-229).  Inside the chunk a row keeps ONE running maximum over keys H * 16 + (15 - q)
@@ -86,7 +89,7 @@ __device__ __forceinline__ void mini_chunk(const int t0, const int k, const int 
         const int up_in = mini_row_shr1<LN>(top0 + q * top_inc, bottom);
         int dg = diag0, up = up_in;
         uint32_t codes[NQ];
-        int hsb[RL];
+        int hsb[RL], hst[RL];
 #pragma unroll
         for (int r = 0; r < RL; ++r) {
             const int kd = p_addw(dg, (int)(int8_t)(s4[r / 4] >> (8 * (r % 4))));   // hw2.cpp:142 / 208-211: diag + s, as a key
@@ -111,10 +114,12 @@ __device__ __forceinline__ void mini_chunk(const int t0, const int k, const int 
                 }
             }
             if (SBAND) hsb[r] = kk >> 2;
+            if (SEMI) hst[r] = hn;
             dg = kl;
             up = GAP0 ? base : p_addw(base, cu);                                    // what the row below / the lane below takes
             hl[r] = act ? hn : kl;
         }
+        if constexpr (SEMI) sg_track<RL, GUARD>(hst, own, act, t0 + q, sg_v, sg_t);
         const int d0 = p_addw(up_in, PL - PU);                                      // dp[i_first - 1][j] in the left form: next step's diagonal of row 0
         diag0 = act ? d0 : diag0;
         bottom = act ? up : bottom;
@@ -157,7 +162,9 @@ constexpr int kMiniWaves = 4;
 // LN = 64 (r03): ONE pair per wave, lane k owns RL = 6 | 8 | 12 | 16 rows -- a single stripe of 384 .. 1024 rows (BandGeo<64, RL>: for RL = 8
 // and 16 the stripe engine's own layout [step][64 lanes][RL]), for batches of mid-sized patterns: one wave and 17 + 5 RL instructions per
 // step where the stripe engine runs 3 - 8 pipelined stripes of 33 with their hand-offs.
-template <int RL, bool LOCAL, bool SBAND, bool GAP0, bool BAND = true, int LN = 16>
+// SEMI (semi-global, PWA_MODE_SG): row 0 is the constant 0, and the lane that owns row n records the first maximum of that row --
+// the fill's end record (res->score, res->end_j), which the walk starts from.
+template <int RL, bool LOCAL, bool SBAND, bool GAP0, bool BAND = true, int LN = 16, bool SEMI = false>
 __global__ __launch_bounds__(64 * kMiniWaves) void mini_fill_kernel(const PairParams G) {
     static_assert(BAND || !SBAND, "no score band without the code band");
     typedef BandGeo<LN, RL> Geo;
@@ -208,8 +215,12 @@ __global__ __launch_bounds__(64 * kMiniWaves) void mini_fill_kernel(const PairPa
             bj[r] = 0;
         }
         int diag0 = tb_stored(LOCAL || GAP0 ? 0 : p_mulw(i_first - 1, gap), gap, PL);   // dp[i_first-1][0]
-        // row 0 in the form `bottom` travels in (the up-candidate of the row below): global H = j * gap, G and local 0
-        const int top_inc = (LOCAL || GAP0) ? 0 : (int)((unsigned)gap * 4u);
+        // row 0 in the form `bottom` travels in (the up-candidate of the row below): global H = j * gap, G, local and semi-global 0
+        const int top_inc = (LOCAL || GAP0 || SEMI) ? 0 : (int)((unsigned)gap * 4u);
+        // SEMI: the end record starts at column 0, dp[n][0] = n * gap (step k - 1 is column 0 of lane k)
+        int own[RL] = {};
+        if (SEMI) sg_own(own, i_first, n);
+        int sg_v = tb_stored(p_mulw(n, gap), gap, PL), sg_t = k - 1;
         g_u8* const tb = (g_u8*)P->tb;
         g_i32* const sband = SBAND ? (g_i32*)P->sband : nullptr;
         const int offa = k * Geo::PA, offb = LN * Geo::PA + k * Geo::PB;
@@ -245,19 +256,25 @@ __global__ __launch_bounds__(64 * kMiniWaves) void mini_fill_kernel(const PairPa
             for (int x = 1; x < 4 * PPW; ++x) wv = (wsel == x) ? wnext[x >> 2][x & 3] : wv;
             const int tcv = (int)__builtin_amdgcn_perm(wv, wv, bsel);   // lane q of a row: its pair's column t0 + q, splatted (the symbol travels down the lanes that way)
             stage(t0 + 16, wnext);                                       // a chunk ahead
-            const int top0 = tb_stored(LOCAL || GAP0 ? 0 : p_mulw(t0 + 1, gap), gap, PU);
+            const int top0 = tb_stored(LOCAL || GAP0 || SEMI ? 0 : p_mulw(t0 + 1, gap), gap, PU);
             g_u8* const tbs = tb + (size_t)t0 * Geo::SR;
             g_i32* const sbs = SBAND ? sband + (size_t)t0 * Geo::SR : nullptr;
             const bool interior = t0 >= LN - 1 && t0 + 16 <= mmin;   // every lane of every pair inside its matrix
             if (interior)
-                mini_chunk<RL, LOCAL, SBAND, false, GAP0, BAND, LN>(t0, k, m, pk, hl, diag0, bottom, tch, tcv, top0, top_inc, bs, bj, tab_lo, tab_hi, cl,
-                                                                    tbs + offa, tbs + offb, sbs);
+                mini_chunk<RL, LOCAL, SBAND, false, GAP0, BAND, LN, SEMI>(t0, k, m, pk, hl, diag0, bottom, tch, tcv, top0, top_inc, bs, bj, tab_lo, tab_hi,
+                                                                          cl, tbs + offa, tbs + offb, sbs, own, sg_v, sg_t);
             else
-                mini_chunk<RL, LOCAL, SBAND, true, GAP0, BAND, LN>(t0, k, m, pk, hl, diag0, bottom, tch, tcv, top0, top_inc, bs, bj, tab_lo, tab_hi, cl,
-                                                                   tbs + offa, tbs + offb, sbs);
+                mini_chunk<RL, LOCAL, SBAND, true, GAP0, BAND, LN, SEMI>(t0, k, m, pk, hl, diag0, bottom, tch, tcv, top0, top_inc, bs, bj, tab_lo, tab_hi,
+                                                                         cl, tbs + offa, tbs + offb, sbs, own, sg_v, sg_t);
         }
         PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
-        if (!LOCAL) {
+        if (SEMI) {
+            // the first maximum of row n (its lane's record): the walk starts at (n, j*)
+            if (n >= i_first && n < i_first + RL) {
+                res->score = (int)((unsigned)sg_v - (unsigned)cl) >> 2;
+                res->end_j = (uint32_t)(sg_t - k + 1);
+            }
+        } else if (!LOCAL) {
             // dp[n][m] (hw2.cpp:186): a lane's state freezes when it leaves the matrix, so the lane that holds row n still has its last
             // column's stored value H * 4 + gap * 4 + prio(left)
 #pragma unroll

@@ -159,11 +159,36 @@ __device__ __forceinline__ size_t tb_index(int i, int j, int m) {   // i, j >= 1
 
 // One anti-diagonal step of a stripe.  EDGE = some lanes of this step may lie outside the matrix
 // or compute the matrix's last column.
-template <int RL, bool LOCAL, bool TB, bool SBAND, bool EDGE, bool PERM = false, bool KEYED = true>
+// SEMI (semi-global): the end cell is the FIRST maximum of row n (pwalign.h, PWA_MODE_SG).  The lane that owns row n keeps a running
+// record of it: per step it picks its row-n slot's value out of the step's RL values -- own[r] is -1 for that slot and 0 elsewhere, fixed
+// for a task, so the pick is one v_and_or per row slot, on no dependency chain of the fill -- and takes it if strictly larger: columns
+// reach the lane in increasing order, so ties keep the smallest j.  sg_t: the step (keyed fills) or the column (plain fills) of the record.
+// sg_own builds the masks; they are opaque to the compiler, which would otherwise see that exactly one is set and turn the pick into a
+// dynamically indexed private array -- a scratch store of every row value per step.
+template <int RL>
+__device__ __forceinline__ void sg_own(int (&own)[RL], const int i_first, const int n) {
+#pragma unroll
+    for (int r = 0; r < RL; ++r) {
+        own[r] = i_first + r == n ? -1 : 0;
+        asm volatile("" : "+v"(own[r]));
+    }
+}
+template <int RL, bool GUARD>
+__device__ __forceinline__ void sg_track(const int (&hs)[RL], const int (&own)[RL], const bool act, const int t, int& sg_v, int& sg_t) {
+    int v = hs[0] & own[0];
+#pragma unroll
+    for (int r = 1; r < RL; ++r) v |= hs[r] & own[r];
+    bool better = v > sg_v;
+    if (GUARD) better = better && act;   // (a lane outside the matrix records nothing)
+    sg_v = better ? v : sg_v;
+    sg_t = better ? t : sg_t;
+}
+
+template <int RL, bool LOCAL, bool TB, bool SBAND, bool EDGE, bool PERM = false, bool KEYED = true, bool SEMI = false>
 __device__ __forceinline__ void stripe_step(int t, int lane, int m, int n, int i_first, const int (&pc)[RL], int (&hl)[RL],
                                             int& diag0, int& bottom, int& tch, int& topv, int& tcv, int& coll,
                                             int (&bs)[RL], int (&bj)[RL], int match, int mismatch, int gap,
-                                            g_u8* tbs, g_i32* sbs, PWA_GLOBAL PairResult* res) {
+                                            g_u8* tbs, g_i32* sbs, PWA_GLOBAL PairResult* res, const int (&own)[RL], int& sg_v, int& sg_j) {
     const int up_in = wave_shr1(topv, bottom);   // dp[i_first-1][j]; lane 0: the staged row above the stripe
     tch = wave_shr1(tcv, tch);                   // text char of column c; lane 0: the staged text
     topv = wave_shl1(topv, topv);                // rotate the staged vectors: lane 0 sees the next column next step
@@ -206,7 +231,7 @@ __device__ __forceinline__ void stripe_step(int t, int lane, int m, int n, int i
                         h = ug;
                         code = PU;
                     }
-                    if (EDGE && (i_first + r) == n && j == m) res->score = h;                              // 186
+                    if (!SEMI && EDGE && (i_first + r) == n && j == m) res->score = h;                     // 186
                 }
                 codes |= (uint32_t)code << (8 * r);
                 dg = lf;
@@ -230,7 +255,7 @@ __device__ __forceinline__ void stripe_step(int t, int lane, int m, int n, int i
                     }
                 } else {
                     h = max(tdiag, max(lg, ug));                                                           // 142-153
-                    if (EDGE && (i_first + r) == n && j == m) res->score = h;                              // 186
+                    if (!SEMI && EDGE && (i_first + r) == n && j == m) res->score = h;                     // 186
                 }
                 dg = lf;
                 up = h;
@@ -238,6 +263,7 @@ __device__ __forceinline__ void stripe_step(int t, int lane, int m, int n, int i
                 hnew[r] = h;
             }
         }
+        if constexpr (SEMI) sg_track<RL, false>(hnew, own, true, j, sg_v, sg_j);
         // keyed form: `bottom` (and with it the rings and hand-off rows) carries the UP-candidate form H*4 + gap*4 + prio(up),
         // what the row below feeds straight into its v_max3; diag0 stays in the left-candidate form the tables are built for
         diag0 = up_in;
@@ -320,12 +346,15 @@ __device__ __forceinline__ int dpp_fill_shr1(int dst, int v) { return __builtin_
 // 2 instead of 3 instructions behind each v_max3, 2 instead of 3 on the chain.
 // BAND = false (r03): the same chunk with no band at all -- scores (and end cells) of long pairs that a scores pass keeps off the strips:
 // no code bytes, no stores, one instruction per cell less.
-template <int RL, bool LOCAL, bool SBAND, bool PERM, bool GUARD, bool GAP0 = false, bool BAND = true>
+// SEMI (semi-global): sg_track after every step, on the stored values (H * 4 + gap * 4 + prio(left): ordered as H is).
+template <int RL, bool LOCAL, bool SBAND, bool PERM, bool GUARD, bool GAP0 = false, bool BAND = true, bool SEMI = false>
 __device__ __forceinline__ void keyed_chunk(const int t0, const int lane, const int m, const int (&pc)[RL], int (&hl)[RL], int& diag0, int& bottom,
                                             int& tch, const int topv, const int tcv, int (&bs)[RL], int (&bj)[RL], const int tab_lo,
-                                            const int tab_hi, const int cl, g_u8* tbs, g_i32* sbs, int* ring_out) {
+                                            const int tab_hi, const int cl, g_u8* tbs, g_i32* sbs, int* ring_out, const int (&own)[RL], int& sg_v,
+                                            int& sg_t) {
     constexpr int PU = TbCode<LOCAL>::UP, PL = TbCode<LOCAL>::LEFT;
     static_assert(!GAP0 || (!LOCAL && PERM && !SBAND && PU == 0), "gap-shifted fills: global, table scoring, no score band");
+    static_assert(!SEMI || (!LOCAL && !GAP0), "semi-global fills: global cells in plain coordinates");
     static_assert(BAND || !SBAND, "no score band without the code band");
     const int cu = p_addw(cl, PU - PL);
     // band pointers of this lane at step t0: the unrolled steps store at immediate offsets from them
@@ -414,6 +443,7 @@ __device__ __forceinline__ void keyed_chunk(const int t0, const int lane, const 
             }
             PWA_SB();
         }
+        if constexpr (SEMI) sg_track<RL, GUARD>(hn, own, act, t0 + q, sg_v, sg_t);
         bottom = act ? up : bottom;
         if constexpr (more && PERM) {
             if (!have_x) xn = (uint32_t)pc[0] ^ (uint32_t)tn2;
@@ -484,7 +514,9 @@ struct WgShared {
     uint32_t task;
 };
 
-template <int RL, int W, bool LOCAL, bool TB, bool SBAND, bool PERM = false, bool KEYED = true, bool GAP0 = false, bool BAND = true>
+// SEMI (semi-global, PWA_MODE_SG): row 0 is the constant 0, and the lane that owns row n records the first maximum of that row into
+// res->score / res->end_j (the walk starts there)
+template <int RL, int W, bool LOCAL, bool TB, bool SBAND, bool PERM = false, bool KEYED = true, bool GAP0 = false, bool BAND = true, bool SEMI = false>
 __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParams G) {
     static_assert(!PERM || (TB && KEYED), "table scoring exists for the keyed (traceback) form only");
     static_assert(BAND || (TB && KEYED && PERM && !SBAND), "the band-less keyed form: scores / end cells of coded sequences");
@@ -548,7 +580,7 @@ __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParam
                             v[u] = tc[u] = 0;
                             if (c < hi) {
                                 if (top_global) v[u] = __hip_atomic_load(rin + c, PWA_RLX_AGENT);   // sc1: issued after the poll's value is known
-                                else v[u] = LOCAL ? 0 : p_mulw(c + 1, gap);                         // dp[0][j], hw2.cpp:131-136
+                                else v[u] = LOCAL || SEMI ? 0 : p_mulw(c + 1, gap);                 // dp[0][j], hw2.cpp:131-136
                                 tc[u] = txt[c];
                             }
                         }
@@ -612,6 +644,10 @@ __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParam
             }
             int diag0 = LOCAL ? 0 : p_mulw(i_first - 1, gap);           // dp[i_first-1][0]
             if (TBK) diag0 = tb_stored(diag0, gap, TbCode<LOCAL>::LEFT);
+            // SEMI: the end record starts at column 0, dp[n][0] = n * gap (keyed: step lane - 1 is column 0 of this lane)
+            int own[RL] = {};
+            if (SEMI) sg_own(own, i_first, n);
+            int sg_v = TBK ? tb_stored(p_mulw(n, gap), gap, TbCode<LOCAL>::LEFT) : p_mulw(n, gap), sg_t = TBK ? lane - 1 : 0;
             const size_t Tb = band_steps((size_t)m);
             g_u8* tbs = (TB && BAND) ? (g_u8*)(P.tb + (size_t)s * Tb * 64 * RL) : nullptr;
             g_i32* sbs = SBAND ? (g_i32*)(P.sband + (size_t)s * Tb * 64 * RL) : nullptr;
@@ -690,11 +726,11 @@ __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParam
                     }
                     int* const ring_out = (has_out && lane == 63) ? rout + ring_slot(t0 - 63) : sh.dump[wave] + lane;
                     if (interior)
-                        keyed_chunk<RL, LOCAL, SBAND, PERM, false, GAP0, BAND>(t0, lane, m, pc, hl, diag0, bottom, tch, topv, tcv, bs, bj, a_match, a_mismatch,
-                                                                   a_gap, tbs, sbs, ring_out);
+                        keyed_chunk<RL, LOCAL, SBAND, PERM, false, GAP0, BAND, SEMI>(t0, lane, m, pc, hl, diag0, bottom, tch, topv, tcv, bs, bj, a_match,
+                                                                         a_mismatch, a_gap, tbs, sbs, ring_out, own, sg_v, sg_t);
                     else
-                        keyed_chunk<RL, LOCAL, SBAND, PERM, true, GAP0, BAND>(t0, lane, m, pc, hl, diag0, bottom, tch, topv, tcv, bs, bj, a_match, a_mismatch,
-                                                                  a_gap, tbs, sbs, ring_out);
+                        keyed_chunk<RL, LOCAL, SBAND, PERM, true, GAP0, BAND, SEMI>(t0, lane, m, pc, hl, diag0, bottom, tch, topv, tcv, bs, bj, a_match,
+                                                                        a_mismatch, a_gap, tbs, sbs, ring_out, own, sg_v, sg_t);
                     const int hi = min(m, t0 - 63 + CH);
                     if (has_out && hi > 0) lds_post_after_writes(&sh.ready[wave + 1], (uint32_t)hi);   // after the chunk's ring writes (one wave: in order)
                     continue;
@@ -702,14 +738,14 @@ __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParam
                     if (interior) {
 #pragma unroll PWA_STEP_UNROLL
                         for (int q = 0; q < CH; ++q)
-                            stripe_step<RL, LOCAL, TB, SBAND, false, PERM, KEYED>(t0 + q, lane, m, n, i_first, pc, hl, diag0, bottom, tch, topv,
-                                                                     tcv, coll, bs, bj, a_match, a_mismatch, a_gap, tbs, sbs, res);
+                            stripe_step<RL, LOCAL, TB, SBAND, false, PERM, KEYED, SEMI>(t0 + q, lane, m, n, i_first, pc, hl, diag0, bottom, tch, topv,
+                                                                           tcv, coll, bs, bj, a_match, a_mismatch, a_gap, tbs, sbs, res, own, sg_v, sg_t);
                     } else {
                         const int qn = min(CH, T - t0);
 #pragma unroll 1
                         for (int q = 0; q < qn; ++q)
-                            stripe_step<RL, LOCAL, TB, SBAND, true, PERM, KEYED>(t0 + q, lane, m, n, i_first, pc, hl, diag0, bottom, tch, topv,
-                                                                    tcv, coll, bs, bj, a_match, a_mismatch, a_gap, tbs, sbs, res);
+                            stripe_step<RL, LOCAL, TB, SBAND, true, PERM, KEYED, SEMI>(t0 + q, lane, m, n, i_first, pc, hl, diag0, bottom, tch, topv,
+                                                                          tcv, coll, bs, bj, a_match, a_mismatch, a_gap, tbs, sbs, res, own, sg_v, sg_t);
 #pragma unroll 1
                         for (int q = qn; q < CH; ++q) coll = wave_shl1(bottom, coll);   // keep the collector aligned
                     }
@@ -730,12 +766,16 @@ __global__ __launch_bounds__(64 * (W + 1)) void pair_fill_kernel(const PairParam
             }
             if (failed && lane == 0) __hip_atomic_store((g_u32*)(G.queue + 1), 1u, PWA_RLX_AGENT);
             if (G.stamps && lane == 0) G.stamps[(size_t)(P.first_stripe + s) * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-            if (TBK && !LOCAL) {
+            if (TBK && !LOCAL && !SEMI) {
                 // dp[n][m] (hw2.cpp:186): a lane's state freezes when it leaves the matrix, so the row that holds row n still has
                 // its last column's stored value: H * 4 + gap * 4 + prio(left)
 #pragma unroll
                 for (int r = 0; r < RL; ++r)
                     if (i_first + r == n) res->score = (int)((unsigned)hl[r] - (unsigned)a_gap) >> 2;
+            }
+            if (SEMI && n >= i_first && n < i_first + RL) {   // the first maximum of row n: the walk starts at (n, j*)
+                res->score = TBK ? (int)((unsigned)sg_v - (unsigned)a_gap) >> 2 : sg_v;
+                res->end_j = (uint32_t)(TBK ? sg_t - lane + 1 : sg_t);
             }
 
             if (LOCAL) {
@@ -815,8 +855,11 @@ struct BandGeo {
 #ifndef PWA_WALK_WIN_WIDE_DIV
 #define PWA_WALK_WIN_WIDE_DIV 1   // (experiment builds: 2 halves the window of the one-pair-per-wave classes)
 #endif
-template <int RL, bool LOCAL, int WALK, int LN = 64>
+// SEMI (semi-global): the walk starts at the fill's end record (n, j*) and stops at row 0 -- only a walk that reaches column 0 first
+// goes on down it ('D'); start_j is where it reached row 0.
+template <int RL, bool LOCAL, int WALK, int LN = 64, bool SEMI = false>
 __global__ __launch_bounds__(64) void pair_traceback_kernel(const PairParams G) {
+    static_assert(!SEMI || (!LOCAL && WALK != WALK_OVERLAP), "semi-global walks: global codes, op list or end cell");
     typedef BandGeo<LN, RL> Geo;
     // steps per LDS window.  Stripe engine (LN = 64, RL = 2 | 4: few, long walks): 64 steps, <= 16 KiB.  Mini-stripe classes (many short
     // walks, LDS decides how many run per CU): 32 steps -- [gpu, r03] 65 536 walks over 150 x 2000 bands 4.7 -> 3.05 ms, the `g` batch
@@ -851,6 +894,10 @@ __global__ __launch_bounds__(64) void pair_traceback_kernel(const PairParams G) 
         }
         if (lane == 0) res->score = sb;
         if (lane == 0 && G.scores_out) ((g_i32*)G.scores_out)[P.out_index] = sb;
+    } else if (SEMI) {
+        i = P.n;
+        j = min((int)res->end_j, P.m);   // the fill's record: the first maximum of row n, and its score (never past column m)
+        if (lane == 0 && G.scores_out) ((g_i32*)G.scores_out)[P.out_index] = res->score;
     } else {
         i = P.n;
         j = P.m;
@@ -1259,15 +1306,18 @@ __global__ __launch_bounds__(64) void pair_traceback_kernel(const PairParams G) 
         }
     }
     if (!LOCAL) {
-        // hw2.cpp:170-179 with j == 0 or i == 0: column 0 is all 'u', row 0 all 'l' (125-136)
+        // hw2.cpp:170-179 with j == 0 or i == 0: column 0 is all 'u', row 0 all 'l' (125-136); semi-global: row 0 is free, the walk
+        // ends where it meets it
         if (OPS)
             for (int o = lane; o < i; o += 64) ops[cnt + o] = 'D';
         cnt += i;
         i = 0;
-        if (OPS)
-            for (int o = lane; o < j; o += 64) ops[cnt + o] = 'I';
-        cnt += j;
-        j = 0;
+        if (!SEMI) {
+            if (OPS)
+                for (int o = lane; o < j; o += 64) ops[cnt + o] = 'I';
+            cnt += j;
+            j = 0;
+        }
     }
     (void)stopped;
     if (lane == 0) {

@@ -597,10 +597,6 @@ PairGeom choose_geom(const Knobs& kn, uint64_t max_n, bool keyed = true, bool ke
     if (kn.force_w) g.w = kn.force_w == 1 ? 1 : 4;
     return g;
 }
-pair_kernel_t pair_fill_fn(PairGeom g, bool local, bool tb, bool sband, bool perm, bool keyed, bool gap0) {
-    return pair_fill_kernel_for(g.rl, g.w, local, tb, sband, perm, keyed, gap0);
-}
-pair_kernel_t pair_tb_fn(PairGeom g, bool local, int walk) { return pair_traceback_kernel_for(g.rl, local, walk); }
 
 size_t tb_band_bytes(uint64_t n, uint64_t m, int rl) {
     const uint64_t stripes = (n + 64 * rl - 1) / (64 * rl);
@@ -628,6 +624,7 @@ struct PairLaunch {
     bool perm = false;   // sequences are coded 0..6 (pad 7) and the key constants fit a byte: table-scoring fill kernels
     bool keyed = true;   // traceback fills keep H * 4 + priority (needs |H| < 2^28); false: plain int32 compare-and-select form
     bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
+    bool semi = false;   // semi-global (PWA_MODE_SG) fills and walks: row 0 free, the end record of row n (never with gap0)
     bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
     bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
     bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
@@ -743,8 +740,8 @@ struct PairLaunch {
     int launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband = false) {
         HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
         if (mini) {
-            const pair_kernel_t fill = mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln);   // tb = false: no band at all
-            const pair_kernel_t walk_fn = mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln);
+            const pair_kernel_t fill = mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
+            const pair_kernel_t walk_fn = mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
             if (!fill || !walk_fn || !perm || !keyed) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
             // Workgroups of four waves (one task each per round); `per_cu` of them per CU, enforced through the dynamic LDS request, so
             // that no CU gets more than its share whatever ran before (mini_fill.hip.h): with ceil(tasks / 4) workgroups for 256 CUs,
@@ -793,9 +790,11 @@ struct PairLaunch {
         }
         // (scores / end cells only over a coded arena, keys in range: the keyed chunk without a band -- batch_create_impl sets perm for that)
         const bool noband = !tb && perm && keyed && !sband;
-        const pair_kernel_t fill = noband ? pair_fill_kernel_for(geom.rl, geom.w, local, true, false, true, true, gap0 && !local, false)
-                                          : pair_fill_fn(geom, local, tb, sband, perm && tb && keyed, keyed, gap0 && tb && keyed && perm && !sband && !local);
-        if (!fill) return fail(ctx, PWA_E_INVALID, "internal: no fill kernel for this geometry");
+        const pair_kernel_t fill = noband ? pair_fill_kernel_for(geom.rl, geom.w, local, true, false, true, true, gap0 && !local, false, semi)
+                                          : pair_fill_kernel_for(geom.rl, geom.w, local, tb, sband, perm && tb && keyed, keyed,
+                                                                 gap0 && tb && keyed && perm && !sband && !local, true, semi);
+        const pair_kernel_t walk_fn = pair_traceback_kernel_for(geom.rl, local, walk, semi);
+        if (!fill || !walk_fn) return fail(ctx, PWA_E_INVALID, "internal: no fill kernel for this geometry");
         // A launch with no more multi-stripe workgroups than CUs asks for enough (unused) dynamic LDS that only ONE workgroup
         // fits a CU: a stripe is one wave alone on its SIMD, and every stripe of a pair moves at the pace of the slowest --
         // two workgroups sharing a CU's four SIMDs would slow the whole pipeline
@@ -805,7 +804,7 @@ struct PairLaunch {
         hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
         HIPC(ctx, hipGetLastError());
         if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
-        hipLaunchKernelGGL(pair_tb_fn(geom, local, walk), dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+        hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
         HIPC(ctx, hipGetLastError());
         return PWA_OK;
     }
@@ -1024,6 +1023,7 @@ struct BatchInput {
     uint64_t n_pairs;
     int kind, match, mismatch, gap, gap_extend;
     bool local, want_end;
+    bool semi;   // PWA_MODE_SG: every pair runs off the strips (band-less mini-stripe / stripe fills + the end-cell walk)
     bool affine() const { return kind == KIND_AFFINE; }
     bool nwdist() const { return kind == KIND_NWDIST; }
     uint64_t len(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
@@ -1072,11 +1072,13 @@ int scan_pairs(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, LivePairs& lp) 
                 b->host_scores[k] = (int32_t)(n + m);
             } else if (in.affine()) {   // hw3.cpp:39-52: V[0][0] = 0, F[n][0] = Go + Ge(n-1), E[0][m] = Go + Ge(m-1)
                 b->host_scores[k] = (n + m == 0) ? 0 : (int32_t)((uint32_t)in.gap + (uint32_t)wrap_mul((int64_t)(n + m - 1), in.gap_extend));
+            } else if (in.semi) {
+                b->host_scores[k] = wrap_mul((int64_t)n, in.gap);   // dp[n][0]; an empty pattern ends at (0, 0) with score 0
             } else if (!in.local) b->host_scores[k] = wrap_mul((int64_t)(n + m), in.gap);   // dp[n][0] / dp[0][m], hw2.cpp:125-136
             lp.any_trivial_score = lp.any_trivial_score || b->host_scores[k] != 0;
             if (b->want_end && !in.local) {
                 b->host_end_i[k] = (uint32_t)n;
-                b->host_end_j[k] = (uint32_t)m;
+                b->host_end_j[k] = in.semi ? 0u : (uint32_t)m;
             }
             continue;
         }
@@ -1141,7 +1143,8 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
     const uint64_t max_n = lp.max_n, max_m = lp.max_m;
     // ---- engine choice.  The strip engine pads short patterns with rows that match nothing; for SW
     // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
-    f.strips = affine || nwdist || (!in.want_end && (!local || (mismatch <= 0 && gap <= 0)));
+    // (semi-global: no strip form yet -- every pair takes the route of a pass with end cells)
+    f.strips = affine || nwdist || (!in.want_end && !in.semi && (!local || (mismatch <= 0 && gap <= 0)));
     f.kmode = local ? BM_SW : BM_NW;
     f.tab_match = match;
     f.tab_mismatch = mismatch;
@@ -1188,13 +1191,13 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
     }
     // (a scores pass that wants end cells runs wholly off the strips: its arena is coded whenever the alphabet allows, for the mini-stripe
     // kernels -- the stripe engine's compare form is the same on codes, a pattern-only symbol is code 7 and equals no text code)
-    const bool code_for_end_cells = in.want_end && !affine && !nwdist && al.n_alpha <= 7 && ctx->knobs.tb_engine != 0;
+    const bool code_for_end_cells = (in.want_end || in.semi) && !affine && !nwdist && al.n_alpha <= 7 && ctx->knobs.tb_engine != 0;
     f.coded = (f.strips && f.score_path == SC_PERM) || code_for_end_cells;
     // Short patterns that a scores pass routes away from the strips run on the mini-stripe engine WITHOUT a band (mini_fill.hip.h,
     // BAND = false: four pairs per wave) where it applies: coded arena, keyed cells in range, table constants in a byte.
     if (f.coded && !affine && !nwdist && ctx->knobs.tb_engine != 0 && tb_range_ok(max_n + max_m, match, mismatch, gap, local ? 26 : 28)) {
         f.mini_scores = diag_keys_fit(match, mismatch, gap);
-        f.mini_gap0 = f.mini_scores && !local && gap0_ok(max_n + max_m, match, mismatch, gap);
+        f.mini_gap0 = f.mini_scores && !local && !in.semi && gap0_ok(max_n + max_m, match, mismatch, gap);
     }
     return PWA_OK;
 }
@@ -1789,7 +1792,7 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         // scoring, one v_max3 per cell, global fills gap-shifted -- instead of the plain compare-and-select step: [gpu, r03] SW scores of
         // 64 pairs 10k x 10k 4.8 -> 3.45 ms, NW 4.06 -> 2.05 ms; one pair 1.67 -> 1.26 / 1.55 -> 1.01 ms
         const bool keyed_scores = !in.nwdist() && f.mini_scores && !ctx->knobs.no_keyed_tb && !ctx->knobs.no_pair_table;
-        const bool gap0_scores = keyed_scores && mini_gap0 && !ctx->knobs.no_gap_shift;
+        const bool gap0_scores = keyed_scores && mini_gap0 && !ctx->knobs.no_gap_shift;   // (never semi-global: mini_gap0 is false)
         for (const uint32_t k : plist) {
             PairDesc d = describe(k, q_next++);
             d.score_bias = gap0_scores ? wrap_mul((int64_t)(in.len(in.pair_a[k]) + in.len(in.pair_b[k])), gap) : 0;
@@ -1799,6 +1802,7 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         b->pl.perm = keyed_scores;
         b->pl.keyed = true;
         b->pl.gap0 = gap0_scores;
+        b->pl.semi = in.semi;
         b->pl.dist = in.nwdist();
         b->pl.aff = in.affine();   // (go travels as the gap, ge beside it)
         const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom,
@@ -1807,7 +1811,7 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
         names = in.nwdist()   ? std::string("pair_dist_kernel<RL=") + std::to_string(geom.rl) + ",NW,DIST,no-band>"
                 : in.affine() ? std::string("pair_affine_kernel<RL=") + std::to_string(geom.rl) + ",AFF,no-band>"
-                              : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
+                              : std::string("pair_fill_kernel<RL=") + std::to_string(geom.rl) + (local ? ",SW" : in.semi ? ",SG" : (gap0_scores ? ",NW,GAP0" : ",NW")) + (keyed_scores ? ",keyed,no-band>" : ",no-traceback>");
     }
     for (auto& cls : mini_lists) {
         const int rl = cls.first;
@@ -1833,10 +1837,11 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
         ml.perm = ml.keyed = true;
         ml.gap0 = mini_gap0;
+        ml.semi = in.semi;
         const int rc = ml.build_mini(ctx, pd, n_real, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap, rl);
         if (rc != PWA_OK) return rc;
         ml.G.scores_out = b->scores.as<int32_t>();
-        names += std::string(names.empty() ? "" : " + ") + "mini_fill_kernel<RL=" + std::to_string(rl) + (local ? ",SW" : (mini_gap0 ? ",NW,GAP0" : ",NW")) + ",no-band>";
+        names += std::string(names.empty() ? "" : " + ") + "mini_fill_kernel<RL=" + std::to_string(rl) + (local ? ",SW" : in.semi ? ",SG" : (mini_gap0 ? ",NW,GAP0" : ",NW")) + ",no-band>";
     }
     b->kernel_name = b->use_strips ? b->kernel_name + " + " + names : names;   // (the strip kernel first: bench.py prices its instruction mix)
     return PWA_OK;
@@ -1851,7 +1856,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
     *out = nullptr;
     const bool affine = kind == KIND_AFFINE, nwdist = kind == KIND_NWDIST;
     if ((affine || nwdist) && want_end_cells) return fail(ctx, PWA_E_INVALID, "end cells are not defined for this pass");
-    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && (mode != PWA_MODE_SG || affine || nwdist)) return fail(ctx, PWA_E_INVALID, "unknown mode");
     if (!seq_off || (n_pairs && (!pair_a || !pair_b))) return fail(ctx, PWA_E_INVALID, "null input");
     if (n_seq && !seq_bytes && seq_off[n_seq] != 0) return fail(ctx, PWA_E_INVALID, "null seq_bytes");
     if (n_pairs >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "more than 2^32-2 pairs in one batch");
@@ -1860,7 +1865,7 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
     HIPC(ctx, hipSetDevice(ctx->device));
     CreateClock clock{ctx};
     const BatchInput in{seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, kind, match, mismatch, gap, gap_extend,
-                        mode == PWA_MODE_SW, want_end_cells != 0};
+                        mode == PWA_MODE_SW, want_end_cells != 0, mode == PWA_MODE_SG};
 
     pwa_batch* b = new (std::nothrow) pwa_batch();
     if (!b) return fail(ctx, PWA_E_NOMEM, "host allocation");
@@ -2741,9 +2746,10 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
                             uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops,
                             uint64_t* end_cells, uint64_t* start_cells, int32_t* overlap_out, const StrOut* str) try {
     if (!ctx) return PWA_E_INVALID;
-    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW) return fail(ctx, PWA_E_INVALID, "unknown mode");
     const bool want_ops = ops != nullptr, want_str = str != nullptr;
     const bool walk_ops = want_ops || want_str;   // WALK_OPS; the op lists come back (want_ops) or are formatted on the device (want_str)
+    // (pwa_overlaps is hw2 -g's selection over global or local alignments: no semi-global form)
+    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && (mode != PWA_MODE_SG || !walk_ops)) return fail(ctx, PWA_E_INVALID, "unknown mode");
     if (!seq_off || !score_out || (want_ops && (!ops_off || !n_ops)) || (!walk_ops && !overlap_out) ||
         (want_str && (!str->cigar_off || !str->mdz_off || (str->cigar_cap && !str->cigar) || (str->mdz_cap && !str->mdz))) ||
         (n_pairs && (!pair_a || !pair_b)))
@@ -2752,7 +2758,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     for (uint64_t k = 0; k < n_pairs; ++k)
         if (pair_a[k] >= n_seq || pair_b[k] >= n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
     HIPC(ctx, hipSetDevice(ctx->device));
-    const bool local = mode == PWA_MODE_SW;
+    const bool local = mode == PWA_MODE_SW, semi = mode == PWA_MODE_SG;   // (semi-global: NW's classes, guards and codes; no gap shift)
     auto slen = [&](uint32_t s) -> uint64_t { return seq_off[s + 1] - seq_off[s]; };
     ctx->fill_ms = ctx->tb_ms = 0.f;
     ctx->band_bytes = 0;
@@ -2801,7 +2807,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     const bool keyed = tb_range_ok(longest_sum, match, mismatch, gap, local ? 26 : 28) && !ctx->knobs.no_keyed_tb;   // (local: H * 16 in the first-maximum records)
     // Global alignments with table scoring run in gap-shifted coordinates G = H - gap (i + j): the same recurrence with gap 0 and
     // scores s - 2 gap, identical comparisons and codes, one instruction less per cell (pair_fill.hip.h, GAP0: gap0_ok)
-    const bool gap0 = !local && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift && gap0_ok(longest_sum, match, mismatch, gap);
+    const bool gap0 = !local && !semi && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift && gap0_ok(longest_sum, match, mismatch, gap);
     const int k_match = gap0 ? match - 2 * gap : match, k_mismatch = gap0 ? mismatch - 2 * gap : mismatch, k_gap = gap0 ? 0 : gap;
     // the mini-stripe engine exists for keyed cells with table scoring; PWA_FORCE_RL / PWA_FORCE_W address the stripe engine
     const bool mini_ok = coded && keyed && ctx->knobs.tb_engine != 0 && !ctx->knobs.force_rl && !ctx->knobs.force_w &&
@@ -3015,10 +3021,10 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             const uint64_t k = k0 + q, n = slen(pair_a[k]), m = slen(pair_b[k]);
             std::memset(&res[q], 0, sizeof(PairResult));
             ooff[q] = rg.tiled ? ops_off[k] - ops_lo : oo;
-            if (!(n && m) && !local) {
-                res[q].score = wrap_mul((int64_t)(n + m), gap);
+            if (!(n && m) && !local) {   // (semi-global: column 0, or nothing for an empty pattern)
+                res[q].score = wrap_mul((int64_t)(semi ? n : n + m), gap);
                 res[q].end_i = (uint32_t)n;
-                res[q].end_j = (uint32_t)m;
+                res[q].end_j = semi ? 0u : (uint32_t)m;
             }
             if (want_str) cpairs[q] = CigarPair{aoff[pair_a[k]], aoff[pair_b[k]], ooff[q], (uint32_t)n, (uint32_t)m};
             oo += align_up(n + m + 1, 16);
@@ -3059,6 +3065,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             pl.perm = coded && keyed;
             pl.keyed = keyed;
             pl.gap0 = gap0;
+            pl.semi = semi;
             int rc = L.cls.mini ? pl.build_mini(ctx, pd, (uint32_t)np, k_match, k_mismatch, k_gap, L.cls.rl, L.cls.w)
                                 : pl.build(ctx, pd, k_match, k_mismatch, k_gap, PairGeom{L.cls.rl, L.cls.w});
             if (rc != PWA_OK) return rc;
@@ -3097,6 +3104,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             cp.nc = (uint32_t)nc;
             cp.coded = coded;
             cp.local = local;
+            cp.semi = semi;
             HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
             HIPC(ctx, pwa::cigar_launch(cp, false, ctx->stream));
             pwa::scan_excl(ctx->stream, cp.len, 2 * nc + 2, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(p_aux) + aux_part_at));
@@ -3136,9 +3144,9 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             const uint64_t k = k0 + q, n = slen(pair_a[k]), m = slen(pair_b[k]);
             uint64_t cnt = res[q].n_ops;
             if (!(n && m)) {
-                // one side empty: NW walks the boundary (hw2.cpp:170-179), SW emits nothing (239); no column
-                // without a gap, so the overlap is 0 (hw2.cpp:267-278)
-                cnt = local ? 0 : n + m;
+                // one side empty: NW walks the boundary (hw2.cpp:170-179), SW emits nothing (239), SG walks column 0; no
+                // column without a gap, so the overlap is 0 (hw2.cpp:267-278)
+                cnt = local ? 0 : semi ? n : n + m;
                 if (want_ops)
                     for (uint64_t o = 0; o < cnt; ++o) ops[ops_off[k] + o] = n ? 'D' : 'I';
                 if (start_cells) start_cells[2 * k] = start_cells[2 * k + 1] = 0;
@@ -3233,11 +3241,11 @@ int pwa_align(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const ui
 int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* pattern, uint64_t n,
                        const uint8_t* text, uint64_t m, int32_t* dp_out, char* tb_out) try {
     if (!ctx) return PWA_E_INVALID;
-    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
     if ((n && !pattern) || (m && !text) || (!dp_out && !tb_out)) return fail(ctx, PWA_E_INVALID, "null input");
     if (n > 0x7fffffc0ull || m > 0x7fffffc0ull) return fail(ctx, PWA_E_CAPACITY, "sequence longer than 2^31");
     const bool keyed = tb_range_ok(n + m, match, mismatch, gap, mode == PWA_MODE_SW ? 26 : 28) && !ctx->knobs.no_keyed_tb;
-    const bool local = mode == PWA_MODE_SW;
+    const bool local = mode == PWA_MODE_SW, semi = mode == PWA_MODE_SG;
     const uint64_t W = m + 1;
     // row 0 and column 0 exactly as the reference initialises them (hw2.cpp:119-136 / 193-194)
     for (uint64_t i = 0; i <= n; ++i) {
@@ -3245,8 +3253,8 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
         if (tb_out) tb_out[i * W] = (!local && i > 0) ? 'u' : ' ';
     }
     for (uint64_t j = 0; j <= m; ++j) {
-        if (dp_out) dp_out[j] = local ? 0 : wrap_mul((int64_t)j, gap);
-        if (tb_out) tb_out[j] = (!local && j > 0) ? 'l' : ' ';
+        if (dp_out) dp_out[j] = local || semi ? 0 : wrap_mul((int64_t)j, gap);   // (semi-global: row 0 is free)
+        if (tb_out) tb_out[j] = (!local && !semi && j > 0) ? 'l' : ' ';
     }
     if (n == 0 || m == 0) return PWA_OK;
     HIPC(ctx, hipSetDevice(ctx->device));
@@ -3294,6 +3302,7 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
     pd[0].res = d_res.as<PairResult>();
     PairLaunch pl;
     pl.keyed = keyed;
+    pl.semi = semi;
     int rc;
     if (mini_rl) {
         for (int d = 1; d < 4; ++d) {   // three empty patterns fill the wave; their padding goes behind the pair's bands

@@ -67,6 +67,14 @@ extern "C" {
 
 #define PWA_MODE_NW 0 /* global, hw2.cpp:118-190 (tie-break diag >= left >= up, 145-153)      */
 #define PWA_MODE_SW 1 /* local,  hw2.cpp:192-265 (tie-break zero > diag > up > left, 214-222) */
+/* Semi-global ("fitting", "glocal"): the WHOLE pattern against any substring of the text; the text's unaligned prefix and suffix
+ * cost nothing.  An extension of the library: hw2.cpp has no such mode.  NW's recurrence and tie-break (diag >= left >= up) with
+ *   dp[0][j] = 0 for all j (traceback ' '), dp[i][0] = i * gap for i > 0 ('u');
+ *   end cell (n, j*): j* the SMALLEST j in 0..m with maximal dp[n][j]; score = dp[n][j*];
+ *   the walk (NW's rules) runs from (n, j*) while i > 0 -- down column 0 ('D') if it reaches j = 0 first -- and stops at (0, j0):
+ *   start_cell = (0, j0), text [j0, j*) is aligned.  n = 0: score 0, end = start = (0, 0), no ops; m = 0 < n: n * gap, n 'D'.
+ * Scores of this mode run on the stripe / mini-stripe engines (never the strip kernels); pwa_overlaps does not take it. */
+#define PWA_MODE_SG 2
 
 #define PWA_OK 0
 #define PWA_E_INVALID (-1)     /* bad argument (null pointer, unknown mode, index out of range) */
@@ -103,9 +111,10 @@ int pwa_ctx_set_score_band(pwa_ctx *ctx, int on);
  *   seq_bytes/seq_off : n_seq sequences, sequence s = seq_bytes[seq_off[s] .. seq_off[s+1])
  *   pair_a/pair_b     : pair k aligns pattern = sequence pair_a[k] (rows, hw2 "patterns")
  *                       against reference/text = sequence pair_b[k] (columns, hw2 "references")
- *   score_out[k]      : NW: dp[n][m] (hw2.cpp:186);  SW: max cell (hw2.cpp:225-229)
+ *   score_out[k]      : NW: dp[n][m] (hw2.cpp:186);  SW: max cell (hw2.cpp:225-229);  SG: max of row n (PWA_MODE_SG)
  *   end_i_out/end_j_out (each may be NULL): the cell the reference's traceback starts from --
- *                       NW (n, m); SW the FIRST maximum in row-major order, (0,0) if all zero.
+ *                       NW (n, m); SW the FIRST maximum in row-major order, (0,0) if all zero; SG (n, j*), the first
+ *                       maximum of row n.
  * Pair lists of any size: a batch object addresses its sequence arena with 32-bit offsets (4 GiB of distinct sequences),
  * so this call (like pwa_distances and pwa_scores_affine) cuts the list into runs of consecutive pairs whose sequences
  * fit one arena and PIPELINES them: run k + 1 is scheduled, coded and uploaded while the kernels of run k execute.  Remaining limits: a sequence < 2^31 - 64 symbols; pattern +
@@ -233,8 +242,9 @@ int pwa_upgma_newick(const double *dist, const char *const *names, uint32_t n, c
  *              'I' (left: '-' vs text char) in TRACEBACK order, i.e. exactly the contents of
  *              the reference's `tracebacks` vector (hw2.cpp:161, 237) before any reversal;
  *   ops_cap  : capacity of ops; n + m always suffices (PWA_E_CAPACITY otherwise);
- *   end_cell : {i, j} the walk starts from (NW: n, m; SW: first row-major maximum);
- *   start_cell: {i, j} where it stops (NW: 0,0).   Either may be NULL.
+ *   end_cell : {i, j} the walk starts from (NW: n, m; SW: first row-major maximum; SG: n, j* = first maximum of row n);
+ *   start_cell: {i, j} where it stops (NW: 0,0; SG: 0, j0).   Either may be NULL.
+ *   score    : NW dp[n][m]; SW the maximum cell; SG dp[n][j*].
  */
 int pwa_align(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, const uint8_t *pattern, uint64_t n,
               const uint8_t *text, uint64_t m, int32_t *score, uint8_t *ops, uint64_t ops_cap, uint64_t *n_ops,
@@ -245,6 +255,7 @@ int pwa_align(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, const ui
  * inspection and whole-matrix parity tests; sizes are the caller's problem: 5 B per cell):
  *   dp_out : int32 (n+1) x (m+1) = `dp`        (hw2.cpp:119 / 193), or NULL
  *   tb_out : char  (n+1) x (m+1) = `traceback` (hw2.cpp:120 / 194): ' ', 'd', 'u', 'l', '0', or NULL
+ *            (SG: row 0 is 0 / ' ', column 0 i * gap / 'u', the interior NW's)
  * On the device both are written as skewed bands (int32 score band + 1 B/cell traceback band, one
  * coalesced wave store per anti-diagonal step); the host un-skews them.
  */
@@ -277,7 +288,8 @@ int pwa_align_batch(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, co
  *   pair k's CIGAR is cigar[cigar_off[k] .. cigar_off[k + 1]), its MD:Z mdz[mdz_off[k] .. mdz_off[k + 1]) (n_pairs + 1 offsets each,
  *   written by the library); the strings are packed back to back in pair order, without NUL terminators, and are exactly the
  *   bytes pwa_format_alignment gives for that pair's op list (any byte value may appear, '-' and NUL included).  A pair with
- *   one side empty: NW "nD" / "0^<pattern>0" (empty text), "mI" / "0" (empty pattern); SW: "" / "0", as for a zero score.
+ *   one side empty: NW "nD" / "0^<pattern>0" (empty text), "mI" / "0" (empty pattern); SW: "" / "0", as for a zero score; SG: as NW
+ *   for an empty text, "" / "0" for an empty pattern.  score_out / end_cells / start_cells: as pwa_align, per pair.
  *   PWA_E_CAPACITY when the strings exceed cigar_cap / mdz_cap: needed (when not NULL) receives the two totals, and the string
  *   buffers are undefined.  The sums over the pairs of pwa_cigar_bound(n_k + m_k) and pwa_mdz_bound(n_k + m_k) always suffice.
  */
@@ -296,6 +308,7 @@ int pwa_align_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch, int g
  * and returns the longest run of equal, gap-free columns -- no op list is written or copied back.  The
  * caller then asks pwa_align for the ONE winning pair (first strictly larger overlap, hw2.cpp:346).
  *   score_out[k]   : as pwa_align_batch;   overlap_out[k] : as pwa_alignment_overlap on that pair's walk
+ * Modes NW and SW only (PWA_MODE_SG: PWA_E_INVALID).
  */
 int pwa_overlaps(pwa_ctx *ctx, int mode, int match, int mismatch, int gap, const uint8_t *seq_bytes,
                  const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs,
