@@ -350,6 +350,174 @@ __device__ __forceinline__ void scores16_body(const BatchParams& P) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// PROF16: the profile form of the packed f16 local cells.  Same admission as CELL16, plus every text code in 0..3.  A wave task is
+// ONE pattern (wave-uniform) against 128 texts: lane l runs text slot slot0 + l in the low halves and slot0 + 64 + l in the high
+// halves, each lane streaming its own two texts (pad code 12 past a text's end, the LANES argument: local scores only decay).  The
+// whole pattern is ONE strip of R rows: no hand-off.  Task fields: text_off / n_strips = the pattern's arena offset / length,
+// text_len = the longest text of the task.
+// Stored value per row: G = h + g (one register instead of CELL16's H and Hs).  With s' = s - g the cell is
+//   t' = clamp(G_diag + s')         = max(0, h_diag + s)          v_pk_add_f16 clamp, s' read through VGPR index mode
+//   h  = max3(t', G_up, G_left)      = max(0, diag, up + g, left + g), hw2.cpp:211
+//   G  = h + g                                                     v_pk_add_f16
+//   best = max3(best, h, h')         (half a v_pk_maximum3_f16 per row)
+// = 3.5 VALU per lane row of two pairs (CELL16: 4.5).  Exactness as CELL16: every h, t' and G is k * 2^-11 with |k| <= 2047
+// (G >= g >= -127), and h_diag + s <= longest pattern * match <= 2047 keeps t' below the clamp's 1.
+// Per block of 8 columns the lane builds the profile: register 8 sigma + k holds f16x2(s'(sigma, c_A,k), s'(sigma, c_B,k)) (one
+// v_perm per register from the pattern code's byte tables), sigma = 4 is +0.0 for the pad rows past the pattern's end (s = g: pad
+// rows only decay).  The 40 registers are pinned (v216..v255) because a row step reads them relative to the row's code x 8: the 8
+// diagonal adds sit between s_set_gpr_idx_on (SRC1) and s_set_gpr_idx_off, and nothing else does.  Then the 8 maxima and gap adds
+// of the row step, a chain across the block's columns that the second wave on the SIMD covers ([gpu] tools/valu_issue.hip, rows
+// "SW pk16 profile").
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+
+template <int R>
+__device__ __forceinline__ void scores16p_body(const BatchParams& P) {
+    constexpr int C = 8, NW = (R + 3) / 4;
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = P.gap16x2;
+    // the pattern code sigma's byte tables (s' = s - g): bytes 0..3 = low / high bytes of f16(s'(sigma, c)) for text codes c = 0..3
+    uint32_t tlo[4], thi[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        tlo[s] = P.lo16_base ^ (P.lo16_diff << (8 * s));
+        thi[s] = P.hi16_base ^ (P.hi16_diff << (8 * s));
+    }
+    u32x8 pz = {0, 0, 0, 0, 0, 0, 0, 0};   // sigma = 4: the pad rows' +0.0
+    asm volatile("" : "+v"(pz));
+
+    for (;;) {
+        uint32_t tid = 0;
+        {
+            int elect = lane;   // (opaque, see batch_scores_kernel)
+            asm volatile("" : "+v"(elect));
+            if (elect == 0) tid = atomicAdd(P.queue, 1u);
+        }
+        tid = __builtin_amdgcn_readfirstlane(tid);
+        if (tid >= P.n_tasks) break;
+
+        const BatchTask task = P.tasks[tid];
+        const int m = (int)task.text_len;
+        const int n = (int)task.n_strips;
+        // the pattern's codes x 8 (the row's profile offset), 4 to a word, 32 past the pattern's end; wave-uniform (SGPRs).  The
+        // arena's slack covers the over-read of a pattern shorter than R.
+        uint32_t pw[NW];
+        {
+            const uint32_t* pp = reinterpret_cast<const uint32_t*>(P.arena + task.text_off);
+#pragma unroll
+            for (int q = 0; q < NW; ++q) {
+                const int valid = n - 4 * q;
+                const uint32_t keep = valid >= 4 ? 0xffffffffu : (valid <= 0 ? 0u : ((1u << (8 * valid)) - 1u));
+                pw[q] = __builtin_amdgcn_readfirstlane(((pp[q] & keep) | (0x04040404u & ~keep)) << 3);
+            }
+        }
+        const uint32_t slot_a = task.slot0 + lane, slot_b = slot_a + 64;
+        const uint32_t toff_a = P.slot_toff[slot_a], toff_b = P.slot_toff[slot_b];
+        const int ma = (int)P.slot_tlen[slot_a], mb = (int)P.slot_tlen[slot_b];
+        // the lane's text word w (4 columns from column 4w), codes past the text's end replaced by the pad code 12; the load never
+        // leaves the text (the arena's slack covers the rounding to whole dwords)
+        auto word = [&](uint32_t toff, int ml, int w) -> uint32_t {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(P.arena + toff + 4u * (uint32_t)min(w, max((ml - 1) >> 2, 0)));
+            const int valid = ml - 4 * w;
+            const uint32_t keep = valid >= 4 ? 0xffffffffu : (valid <= 0 ? 0u : ((1u << (8 * valid)) - 1u));
+            return (v & keep) | (0x0c0c0c0cu & ~keep);
+        };
+
+        // G of the left boundary column (H = 0): g in every row
+        uint32_t col[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) col[r] = g;
+        uint32_t best[4] = {0, 0, 0, 0};
+        const int nblk = (m + C - 1) / C;
+        uint32_t na0 = word(toff_a, ma, 0), na1 = word(toff_a, ma, 1);
+        uint32_t nb0 = word(toff_b, mb, 0), nb1 = word(toff_b, mb, 1);
+        for (int jb = 0; jb < nblk; ++jb) {
+            const uint32_t wa[2] = {na0, na1}, wb[2] = {nb0, nb1};
+            na0 = word(toff_a, ma, 2 * jb + 2);
+            na1 = word(toff_a, ma, 2 * jb + 3);
+            nb0 = word(toff_b, mb, 2 * jb + 2);
+            nb1 = word(toff_b, mb, 2 * jb + 3);
+            // the block's profile: selector (cA, cA | 4, cB, cB | 4) per column, then one v_perm per code
+            u32x8 p0, p1, p2, p3;
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                const uint32_t kk = (uint32_t)(k & 3);
+                const uint32_t sel = __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk * 0x00000101u + (4u + kk) * 0x01010000u) | 0x04000400u;
+                p0[k] = __builtin_amdgcn_perm(thi[0], tlo[0], sel);
+                p1[k] = __builtin_amdgcn_perm(thi[1], tlo[1], sel);
+                p2[k] = __builtin_amdgcn_perm(thi[2], tlo[2], sel);
+                p3[k] = __builtin_amdgcn_perm(thi[3], tlo[3], sel);
+            }
+            // row -1 (H = 0): G_up = g in every column, and the diagonal of row 0's first column
+            uint32_t u[C];
+#pragma unroll
+            for (int k = 0; k < C; ++k) u[k] = g;
+            uint32_t dprev = g;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                // the row's profile offset on the scalar unit, right before its row step (left to the compiler, all 152 are
+                // computed ahead and spill to VGPR lanes: one v_readlane_b32 per row)
+                uint32_t idx;
+                asm volatile("s_bfe_u32 %0, %1, %2" : "=s"(idx) : "s"(pw[r >> 2]), "i"((8 * (r & 3)) | (8 << 16)) : "scc");
+                const uint32_t left = col[r];
+                uint32_t t[C];
+                asm volatile(
+                    "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
+                    "v_pk_add_f16 %[t0], %[d], v216 clamp\n\t"
+                    "v_pk_add_f16 %[t1], %[u0], v217 clamp\n\t"
+                    "v_pk_add_f16 %[t2], %[u1], v218 clamp\n\t"
+                    "v_pk_add_f16 %[t3], %[u2], v219 clamp\n\t"
+                    "v_pk_add_f16 %[t4], %[u3], v220 clamp\n\t"
+                    "v_pk_add_f16 %[t5], %[u4], v221 clamp\n\t"
+                    "v_pk_add_f16 %[t6], %[u5], v222 clamp\n\t"
+                    "v_pk_add_f16 %[t7], %[u6], v223 clamp\n\t"
+                    "s_set_gpr_idx_off\n\t"
+                    "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l]\n\t"
+                    "v_pk_add_f16 %[u0], %[t0], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                    "v_pk_add_f16 %[u1], %[t1], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                    "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                    "v_pk_add_f16 %[u2], %[t2], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                    "v_pk_add_f16 %[u3], %[t3], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                    "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                    "v_pk_add_f16 %[u4], %[t4], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                    "v_pk_add_f16 %[u5], %[t5], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                    "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                    "v_pk_add_f16 %[u6], %[t6], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
+                    "v_pk_add_f16 %[u7], %[t7], %[g]\n\t"
+                    "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
+                    : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
+                      [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
+                      [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
+                      [b2] "+v"(best[2]), [b3] "+v"(best[3])
+                    : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
+                      "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                    : "m0", "scc");
+                dprev = left;
+                col[r] = u[C - 1];
+            }
+        }
+        // best = k * 2^-11, exact: back to int32 once per task
+        const half2_t b = __builtin_elementwise_maximum(__builtin_elementwise_maximum(h2_bits(best[0]), h2_bits(best[1])),
+                                                        __builtin_elementwise_maximum(h2_bits(best[2]), h2_bits(best[3])));
+        const uint32_t out_a = P.slot_out[slot_a], out_b = P.slot_out[slot_b];   // (read here: no VGPRs held over the column loop)
+        if (out_a != 0xffffffffu) P.scores[out_a] = (int)((float)b.x * 2048.0f);
+        if (out_b != 0xffffffffu) P.scores[out_b] = (int)((float)b.y * 2048.0f);
+    }
+}
+
+// R = 152 rows at two waves per SIMD: R + 40 profile + the block's columns and temporaries fit in 256 VGPRs
+template <int R>
+__global__ __launch_bounds__(256, 2) void batch_scores16p_kernel(const BatchParams P) {
+    scores16p_body<R>(P);
+}
+
 // MULTI = false: every task of the launch is a single strip -- the hand-off row accesses are compiled out
 // (with them, each wave parks an unconditional 1 KiB load + store per 4 columns on an L2-resident dummy
 // block: harmless for speed, but it shows up as ~45 MB of HBM traffic per C3 launch).

@@ -108,6 +108,8 @@ struct Knobs {
                                                 // pair on the stripe engine, unset = by estimated cost and band size
     int cell16 = -1;                            // PWA_CELL16: 0 = never the packed f16 cells (two pairs per lane), 1 = always where the batch
                                                 // admits them, unset = by estimated cost (batch_create_impl)
+    int prof16 = -1;                            // PWA_PROF16: 0 = never the profile form of the packed cells (one pattern against 128
+                                                // texts), 1 = always where the batch admits it, unset = by estimated cost
     uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
@@ -139,6 +141,7 @@ struct Knobs {
         scores_route = num("PWA_SCORES_ROUTE", -1);
         tb_engine = num("PWA_TB_ENGINE", -1);
         cell16 = num("PWA_CELL16", -1);
+        prof16 = num("PWA_PROF16", -1);
         affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
         if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     }
@@ -206,6 +209,10 @@ namespace {
 // Packed f16 strip cells (batch_scores.hip.h, CELL16): VALU per lane row and column, both pairs together -- perm, pk_add,
 // pk_maximum3, pk_add clamp, 1/2 pk_maximum3 for the running best, + the hand-off share ([gpu] PMC on C3: 4.56)
 constexpr double kCell16Vpr = 4.6;
+// The profile form (PROF16): 3.5 VALU per lane row -- indexed pk_add clamp, pk_maximum3, pk_add, 1/2 pk_maximum3 -- + the row's
+// v_mov and the per-block profile ([gpu] tools/valu_issue.hip: 6.43 against CELL16's 7.62 cycles per cell at two waves per SIMD)
+constexpr double kProf16Vpr = 3.8;
+constexpr int kProf16R = 152;   // the rows of its single strip (batch_scores16p_kernel<152>)
 // f16 bit pattern of k * 2^-11 for |k| <= 1023: a normal number (exponent k's leading bit + 4), exact
 uint32_t f16_bits_scaled(int k) {
     if (k == 0) return 0;
@@ -852,6 +859,7 @@ struct pwa_batch {
     bool affine = false, nwdist = false, lanes = false;
     void* strip_fn = nullptr;         // the strip kernel this batch launches (strip_kernel_fn)
     bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
+    bool prof16 = false;            // ... in their profile form: one pattern per wave task (batch_scores.hip.h, PROF16)
     int32_t aff_go = 0, aff_ge = 0, aff_neg = 0;
     uint32_t grid = 0;
     DevBuf arena, tasks, slot_poff, slot_plen, slot_out, slot_toff, slot_tlen, lane_text, hand, queue, scores;
@@ -1376,6 +1384,36 @@ bool cell16_admitted(const Knobs& knobs, const BatchInput& in, const CellForm& f
            knobs.cell16 != 0 && (knobs.force_mode < 0 || knobs.force_mode == BM_SWS);
 }
 
+// ---- the profile form of the packed cells (PROF16): CELL16's admission, patterns of at most kProf16R rows, and every code of the
+// arena in 0..3 (its profile tables have four text codes; 12 is the text pad).  Pairs are grouped by pattern, 128 to a wave task,
+// texts longest first so that a task's columns are about its lanes' own.
+bool prof16_admitted(const Knobs& knobs, const Alphabet& al, uint64_t max_n) {
+    bool codes_low = true;
+    for (int v = 0; v < 256; ++v) codes_low = codes_low && (!al.present[v] || al.code_of[v] <= 3);
+    return knobs.prof16 != 0 && codes_low && max_n <= (uint64_t)kProf16R;
+}
+
+std::vector<HostTask> group_by_pattern(const BatchInput& in, std::vector<uint32_t>& order) {
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        if (in.pair_a[x] != in.pair_a[y]) return in.pair_a[x] < in.pair_a[y];
+        return in.len(in.pair_b[x]) > in.len(in.pair_b[y]);
+    });
+    std::vector<HostTask> g;
+    for (size_t p = 0; p < order.size();) {
+        size_t q = p;
+        while (q < order.size() && q - p < 128 && in.pair_a[order[q]] == in.pair_a[order[p]]) ++q;
+        g.push_back({in.pair_a[order[p]], (uint32_t)p, (uint32_t)(q - p), in.len(in.pair_a[order[p]]), in.len(in.pair_b[order[p]])});
+        p = q;
+    }
+    return g;
+}
+
+long double prof16_cost(const std::vector<HostTask>& tl) {   // in choose_strip_height's units
+    long double cost = 0;
+    for (const auto& t : tl) cost += (long double)kProf16R * (long double)((t.m + 7) / 8 * 8) * 64.0L;
+    return cost * (long double)kProf16Vpr;
+}
+
 // Whether the cost-based split below applies.  Linear scores always.  hw4 distances take it when the batch is in the two-value form
 // (some n + m > 4000, or PWA_NO_PACKED_DIST): coded arena, keys H * 4 + prio inside int32 (pair_dist.hip.h).  Packed-form lists, other
 // byte alphabets and larger scores stay on the strips.  hw3 affine scores likewise: coded arena, every real value inside +-2^28 so that
@@ -1590,30 +1628,33 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
     std::vector<HostTask>& ht = st.ht;
     const int kmode = h.mode, R = h.R;
     const uint64_t kTaskLanes = b->cell16 ? 128 : 64;   // lane slots per wave task
-    for (const auto& t : ht) b->padded_cells += (t.maxlen + R - 1) / R * R * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
+    const bool own_texts = b->lanes || b->prof16;   // per-slot text arrays
+    for (const auto& t : ht)
+        b->padded_cells += b->prof16 ? (uint64_t)kProf16R * ((t.m + 7) / 8 * 8) * kTaskLanes
+                                     : (t.maxlen + R - 1) / R * R * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
     b->kern = find_batch_kernel(R, kmode, f.score_path);
     if (!b->kern) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");
     b->kernel_name = b->kern->name;
     std::sort(ht.begin(), ht.end(), [&](const HostTask& x, const HostTask& y) {   // longest first
-        const uint64_t cx = (x.maxlen + R - 1) / R * x.m, cy = (y.maxlen + R - 1) / R * y.m;
+        const uint64_t cx = b->prof16 ? x.m : (x.maxlen + R - 1) / R * x.m, cy = b->prof16 ? y.m : (y.maxlen + R - 1) / R * y.m;
         if (cx != cy) return cx > cy;
         return x.first < y.first;
     });
     const size_t nt = ht.size();
     // task list and lane slots are built in page-locked buffers of the context and uploaded from there (see PinnedBuf)
     HIPC(ctx, ctx->pin[pwa_ctx::PIN_TASKS].reserve(nt * sizeof(BatchTask)));
-    for (int q = 0; q < (b->lanes ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * kTaskLanes * sizeof(uint32_t)));
+    for (int q = 0; q < (own_texts ? 5 : 3); ++q) HIPC(ctx, ctx->pin[pwa_ctx::PIN_SLOT0 + q].reserve(nt * kTaskLanes * sizeof(uint32_t)));
     BatchTask* const tasks = ctx->pin[pwa_ctx::PIN_TASKS].as<BatchTask>();
     uint32_t* const spoff = ctx->pin[pwa_ctx::PIN_SLOT0].as<uint32_t>();
     uint32_t* const splen = ctx->pin[pwa_ctx::PIN_SLOT1].as<uint32_t>();
     uint32_t* const sout = ctx->pin[pwa_ctx::PIN_SLOT2].as<uint32_t>();
-    uint32_t* const stoff = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT3].as<uint32_t>() : nullptr;   // empty lanes: no text, no pattern
-    uint32_t* const stlen = b->lanes ? ctx->pin[pwa_ctx::PIN_SLOT4].as<uint32_t>() : nullptr;
+    uint32_t* const stoff = own_texts ? ctx->pin[pwa_ctx::PIN_SLOT3].as<uint32_t>() : nullptr;   // empty lanes: no text, no pattern
+    uint32_t* const stlen = own_texts ? ctx->pin[pwa_ctx::PIN_SLOT4].as<uint32_t>() : nullptr;
     std::memset(tasks, 0, nt * sizeof(BatchTask));
     std::memset(spoff, 0, nt * kTaskLanes * sizeof(uint32_t));
     std::memset(splen, 0, nt * kTaskLanes * sizeof(uint32_t));
     std::memset(sout, 0xff, nt * kTaskLanes * sizeof(uint32_t));
-    if (b->lanes) {
+    if (own_texts) {
         std::memset(stoff, 0, nt * kTaskLanes * sizeof(uint32_t));
         std::memset(stlen, 0, nt * kTaskLanes * sizeof(uint32_t));
     }
@@ -1629,12 +1670,16 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
                 tasks[t].slot0 = (uint32_t)(t * kTaskLanes);
                 tasks[t].n_strips = (uint32_t)((ht[t].maxlen + R - 1) / R);
                 part_max[(size_t)th] = std::max(part_max[(size_t)th], tasks[t].n_strips);
+                if (b->prof16) {   // PROF16's task: the pattern's arena offset and length, the longest text
+                    tasks[t].n_strips = (uint32_t)ht[t].maxlen;
+                    part_max[(size_t)th] = 1;
+                }
                 for (uint32_t l = 0; l < ht[t].count; ++l) {
                     const uint32_t k = st.order[ht[t].first + l];
                     spoff[t * kTaskLanes + l] = (uint32_t)aoff[in.pair_a[k]];
                     splen[t * kTaskLanes + l] = (uint32_t)in.len(in.pair_a[k]);
                     sout[t * kTaskLanes + l] = k;
-                    if (b->lanes) {
+                    if (own_texts) {
                         stoff[t * kTaskLanes + l] = (uint32_t)aoff[in.pair_b[k]];
                         stlen[t * kTaskLanes + l] = (uint32_t)in.len(in.pair_b[k]);
                     }
@@ -1651,11 +1696,11 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
         const int rc = upload_lane_rows(ctx, b, in, al, st, tasks, stoff);
         if (rc != PWA_OK) return rc;
     }
-    if (b->lanes) {
-        HIPC(ctx, b->slot_toff.alloc(nt * 64 * 4));
-        HIPC(ctx, hipMemcpy(b->slot_toff.p, stoff, nt * 64 * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_tlen.alloc(nt * 64 * 4));
-        HIPC(ctx, hipMemcpy(b->slot_tlen.p, stlen, nt * 64 * 4, hipMemcpyHostToDevice));
+    if (own_texts) {
+        HIPC(ctx, b->slot_toff.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, hipMemcpy(b->slot_toff.p, stoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
+        HIPC(ctx, b->slot_tlen.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, hipMemcpy(b->slot_tlen.p, stlen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
     }
     clock.mark("choose R + slot arrays");
     HIPC(ctx, b->tasks.alloc(nt * sizeof(BatchTask)));
@@ -1669,6 +1714,7 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
 
     if (b->lanes) b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
     b->strip_fn = strip_kernel_fn(*b->kern, in, b->cell16, b->lanes, max_strips == 1);
+    if (b->prof16) b->strip_fn = reinterpret_cast<void*>(b->kern->fn_prof16);   // (the reported name stays the CELL16 entry's)
     int per_cu = 0;
     HIPC(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, b->strip_fn, 64, 0));
     per_cu = std::max(1, std::min(per_cu, 32));
@@ -1733,6 +1779,13 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
         P.hi16_base = (x16 >> 8) * 0x01010101u;
         P.hi16_diff = ((m16 ^ x16) >> 8) & 0xffu;
         P.gap16x2 = g16 | (g16 << 16);
+        if (b->prof16) {   // the profile form's tables hold s' = s - g (|s'| <= 254: exact)
+            const uint32_t mp = f16_bits_scaled(in.match - in.gap), xp = f16_bits_scaled(in.mismatch - in.gap);
+            P.lo16_base = (xp & 0xffu) * 0x01010101u;
+            P.lo16_diff = (mp ^ xp) & 0xffu;
+            P.hi16_base = (xp >> 8) * 0x01010101u;
+            P.hi16_diff = ((mp ^ xp) >> 8) & 0xffu;
+        }
     }
     P.slot_toff = b->slot_toff.as<uint32_t>();
     P.slot_tlen = b->slot_tlen.as<uint32_t>();
@@ -1942,6 +1995,17 @@ static int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, in
             if (!move.empty()) {
                 off_strips = split_tasks(st, move);
                 if (!st.ht.empty()) h = choose_strip_height(st.ht, form, st.lanes, b->cell16, ctx->knobs);   // the strips that stay may prefer another height
+            }
+        }
+        if (b->cell16 && !st.ht.empty() && prof16_admitted(ctx->knobs, al, lp.max_n)) {   // the strips that stay, one pattern per task
+            std::vector<uint32_t> porder;
+            for (const auto& t : st.ht)
+                for (uint32_t l = 0; l < t.count; ++l) porder.push_back(st.order[t.first + l]);
+            std::vector<HostTask> htp = group_by_pattern(in, porder);
+            if (ctx->knobs.prof16 == 1 || prof16_cost(htp) < h.cost) {
+                b->prof16 = true;
+                st.order.swap(porder);
+                st.ht.swap(htp);
             }
         }
         if (st.ht.empty()) b->use_strips = false;
@@ -2515,6 +2579,11 @@ int pwa_batch_info(const pwa_batch* b, uint64_t* cells, uint64_t* padded_cells, 
     }
     if (kernel_name) *kernel_name = b->kernel_name.c_str();
     return PWA_OK;
+}
+
+int pwa_batch_profile_form(const pwa_batch* b) {
+    if (!b) return PWA_E_INVALID;
+    return b->use_strips && b->prof16 ? 1 : 0;
 }
 
 int pwa_batch_cell_bits(const pwa_batch* b) {

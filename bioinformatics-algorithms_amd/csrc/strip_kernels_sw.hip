@@ -8,11 +8,12 @@ namespace pwa {
 #define BKL(R, M, S) {R, M, S, batch_scores_kernel<R, M, S, true>, "batch_scores_kernel<R=" #R "," #M "," #S ">", nullptr, nullptr, \
                       batch_scores_kernel<R, M, S, false>, \
                       batch_scores_kernel<R, M, S, true, true>, batch_scores_kernel<R, M, S, false, true>}
-// BKL + the packed f16 form (CELL16): the reported name stays the int32 form's, like fn_single's
+// BKL + the packed f16 form (CELL16) and its profile form (PROF16): the reported name stays the int32 form's, like fn_single's
 #define BKL16(R, M, S) {R, M, S, batch_scores_kernel<R, M, S, true>, "batch_scores_kernel<R=" #R "," #M "," #S ">", nullptr, nullptr, \
                         batch_scores_kernel<R, M, S, false>, \
                         batch_scores_kernel<R, M, S, true, true>, batch_scores_kernel<R, M, S, false, true>, \
-                        batch_scores_kernel<R, M, S, true, false, true>, batch_scores_kernel<R, M, S, false, false, true>}
+                        batch_scores_kernel<R, M, S, true, false, true>, batch_scores_kernel<R, M, S, false, false, true>, \
+                        batch_scores16p_kernel<152>}
 extern const BatchKernelEntry kStripKernelsSW[] = {
     BK(76, BM_SW, SC_PERM),   BK(104, BM_SW, SC_PERM),
     BKL(40, BM_SWS, SC_PERM), BKL16(52, BM_SWS, SC_PERM), BKL16(76, BM_SWS, SC_PERM), BKL(96, BM_SWS, SC_PERM),

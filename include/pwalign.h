@@ -41,6 +41,8 @@
  *                                 affine score passes likewise, for the lists the stripe engine's affine fill takes
  *   PWA_CELL16=0|1                local strip scores: 0 never / 1 always (where the batch admits it) the packed f16 cells, two pairs per
  *                                 lane (default: by estimated cost; pwa_batch_cell_bits says which form a batch runs)
+ *   PWA_PROF16=0|1                packed f16 local strip scores: 0 never / 1 always (where the batch admits it) their profile form, one
+ *                                 pattern against 128 texts per wave task (default: by estimated cost; pwa_batch_profile_form says which)
  *   PWA_TB_ENGINE=0|2             traceback fills and scores off the strips: 0 the stripe engine's plain forms only, 2 mini-stripe kernels
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
@@ -155,6 +157,9 @@ int pwa_batch_info(const pwa_batch *b, uint64_t *cells, uint64_t *padded_cells, 
  * texts' (codes 0..3), with mismatch <= 0, gap <= 0, |scores| <= 127 and longest pattern * max(match, 0) <= 2047, when the cost
  * model prefers it; PWA_CELL16=0|1 forces either form where it applies. */
 int pwa_batch_cell_bits(const pwa_batch *b);
+/* 1 when the batch's strips run the profile form of the packed f16 cells (one pattern against 128 texts per wave task; PWA_PROF16=0|1
+ * forces either form where it applies), 0 otherwise. */
+int pwa_batch_profile_form(const pwa_batch *b);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);
