@@ -30,6 +30,7 @@ EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_scores",
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
+    "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
@@ -155,6 +156,10 @@ def lib():
     L.pwa_align_batch.argtypes = batch_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_align_batch_cigar.argtypes = batch_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
     L.pwa_overlaps.argtypes = batch_in + [i32p, i32p]
+    gotoh_in = batch_in[:5] + [C.c_int] + batch_in[5:]   # ctx, mode, match, mismatch, gap_open, gap_extend, sequences, pairs
+    L.pwa_align_gotoh_batch.argtypes = gotoh_in + [i32p, vp, u64p, u64p, u64p, u64p]
+    L.pwa_align_gotoh_batch_cigar.argtypes = gotoh_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
+    L.pwa_align_gotoh_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
     L.pwa_cigar_bound.argtypes = [C.c_uint64]
@@ -447,6 +452,64 @@ class Context:
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+
+    def align_gotoh_batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
+        """pwa_align_gotoh_batch: affine-gap alignments (a gap of length L scores gap_open + L * gap_extend; include/pwalign.h) ->
+        [dict(score, ops, end, start)] as align_batch returns them."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        ooff = (C.c_uint64 * max(n, 1))()
+        tot = 0
+        for k in range(n):
+            ooff[k] = tot
+            tot += len(seqs[pair_a[k]]) + len(seqs[pair_b[k]])
+        ops = C.create_string_buffer(tot + 1)
+        sc = (C.c_int32 * max(n, 1))()
+        nops = (C.c_uint64 * max(n, 1))()
+        endc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint64 * (2 * max(n, 1)))()
+        rc = self._L.pwa_align_gotoh_batch(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc,
+                                           ops, ooff, nops, endc, startc)
+        self._check(rc, "pwa_align_gotoh_batch")
+        raw = memoryview(ops)
+        return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
+                     start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+
+    def align_gotoh_batch_cigar(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
+        """pwa_align_gotoh_batch_cigar: the alignments of align_gotoh_batch as CIGAR and MD:Z strings built on the device ->
+        [dict(score, cigar, mdz, end, start)] as align_batch_cigar returns them."""
+        import numpy as np
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        lens = np.array([len(x) for x in seqs] or [0], dtype=np.uint64)
+        nm = lens[np.asarray(pair_a, dtype=np.int64)] + lens[np.asarray(pair_b, dtype=np.int64)] if n else np.zeros(0, np.uint64)
+        cap_c, cap_m = int((2 * nm + 24).sum()), int((3 * nm + 24).sum())   # pwa_cigar_bound / pwa_mdz_bound
+        cg = np.empty(max(cap_c, 1), dtype=np.uint8)
+        md = np.empty(max(cap_m, 1), dtype=np.uint8)
+        cg_off = np.zeros(n + 1, dtype=np.uint64)
+        md_off = np.zeros(n + 1, dtype=np.uint64)
+        sc = (C.c_int32 * max(n, 1))()
+        endc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint64 * (2 * max(n, 1)))()
+        u64p = C.POINTER(C.c_uint64)
+        rc = self._L.pwa_align_gotoh_batch_cigar(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n,
+                                                 sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
+                                                 md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None)
+        self._check(rc, "pwa_align_gotoh_batch_cigar")
+        co, mo = cg_off.tolist(), md_off.tolist()
+        cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
+        return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
+                     start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+
+    def align_gotoh_stats(self):
+        """The last align_gotoh_batch(_cigar): device ms of its fills and walks, band bytes written."""
+        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_align_gotoh_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_gotoh_last_stats")
+        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
 
     def align_batch_arrays(self, mode, packed, pair_a, pair_b, match, mismatch, gap, out=None):
         """pwa_align_batch on caller-held buffers, the way a compiled host calls it: `packed` = pack_sequences(seqs) done once,

@@ -27,6 +27,9 @@
 
 namespace pwa {
 hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
+// gotoh_kernels.hip: the affine-gap (Gotoh) fills and walks, mode = PWA_MODE_NW | SW | SG; ln = 16 (rl in kMiniRL) or 64 (rl = 8 | 16)
+void (*gotoh_fill_kernel_for(int rl, int mode, int ln))(const PairParams);
+void (*gotoh_walk_kernel_for(int rl, int mode, int ln))(const PairParams);
 }
 
 using namespace pwa;
@@ -160,6 +163,9 @@ struct pwa_ctx {
     uint64_t aff_stripe_pairs = 0, aff_band_bytes = 0;
     float aff_fill_ms = 0.f, aff_walk_ms = 0.f;
     uint64_t band_bytes = 0;
+    // the last pwa_align_gotoh_batch(_cigar): device ms of its fills / walks, band bytes written
+    float gotoh_fill_ms = 0.f, gotoh_walk_ms = 0.f;
+    uint64_t gotoh_band_bytes = 0;
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
     // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the
@@ -635,6 +641,7 @@ struct PairLaunch {
     bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
     bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
     bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
+    int gotoh = -1;      // >= 0 (a PWA_MODE_*): the affine-gap mini-stripe kernels (gotoh_fill.hip.h); build_mini takes gap_open as gap
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;
@@ -747,9 +754,11 @@ struct PairLaunch {
     int launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband = false) {
         HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
         if (mini) {
-            const pair_kernel_t fill = mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
-            const pair_kernel_t walk_fn = mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
-            if (!fill || !walk_fn || !perm || !keyed) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
+            const pair_kernel_t fill = gotoh >= 0 ? gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln)
+                                                  : mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
+            const pair_kernel_t walk_fn = gotoh >= 0 ? gotoh_walk_kernel_for(geom.rl, gotoh, mini_ln)
+                                                     : mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
+            if (!fill || !walk_fn || (gotoh < 0 && (!perm || !keyed))) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
             // Workgroups of four waves (one task each per round); `per_cu` of them per CU, enforced through the dynamic LDS request, so
             // that no CU gets more than its share whatever ran before (mini_fill.hip.h): with ceil(tasks / 4) workgroups for 256 CUs,
             // per_cu = ceil(workgroups / CUs), at most 2; longer task lists run in rounds ([gpu] pairs 150 x 10k: 8192 of them at two
@@ -2808,12 +2817,35 @@ struct StrOut {
 };
 // bytes a pair's two strings can take: the range's string buffer is sized by this, and a range's total stays below 2^32 (the scan is 32-bit)
 uint64_t str_bound(uint64_t n_plus_m) { return pwa_cigar_bound(n_plus_m) + pwa_mdz_bound(n_plus_m); }
+// pwa_align_gotoh_batch(_cigar): affine gaps on the gotoh mini-stripe kernels (align_batch_impl takes gap = gap_open)
+struct GotohSpec {
+    int gap_open, gap_extend;
+};
+constexpr uint64_t kGotohMaxN = 1024;   // patterns of the gotoh classes: 16 x kMiniRL rows, then 64 x 8 | 16 rows
+// The gotoh calls report their device times through pwa_align_gotoh_last_stats: whatever they add to the linear calls' counters
+// moves there when the call returns, and those counters get their values back.
+struct GotohStatsScope {
+    pwa_ctx* ctx;
+    float fill_ms, tb_ms;
+    uint64_t band_bytes;
+    explicit GotohStatsScope(pwa_ctx* c) : ctx(c), fill_ms(c ? c->fill_ms : 0.f), tb_ms(c ? c->tb_ms : 0.f), band_bytes(c ? c->band_bytes : 0) {}
+    ~GotohStatsScope() {
+        if (!ctx) return;
+        ctx->gotoh_fill_ms = ctx->fill_ms;
+        ctx->gotoh_walk_ms = ctx->tb_ms;
+        ctx->gotoh_band_bytes = ctx->band_bytes;
+        ctx->fill_ms = fill_ms;
+        ctx->tb_ms = tb_ms;
+        ctx->band_bytes = band_bytes;
+    }
+};
 }  // namespace
 
 static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes,
                             const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                             uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops,
-                            uint64_t* end_cells, uint64_t* start_cells, int32_t* overlap_out, const StrOut* str) try {
+                            uint64_t* end_cells, uint64_t* start_cells, int32_t* overlap_out, const StrOut* str,
+                            const GotohSpec* gt = nullptr) try {
     if (!ctx) return PWA_E_INVALID;
     const bool want_ops = ops != nullptr, want_str = str != nullptr;
     const bool walk_ops = want_ops || want_str;   // WALK_OPS; the op lists come back (want_ops) or are formatted on the device (want_str)
@@ -2826,9 +2858,19 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     if (n_pairs >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "more than 2^32-2 pairs in one batch");
     for (uint64_t k = 0; k < n_pairs; ++k)
         if (pair_a[k] >= n_seq || pair_b[k] >= n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
+    auto slen = [&](uint32_t s) -> uint64_t { return seq_off[s + 1] - seq_off[s]; };
+    if (gt) {   // the gotoh classes' shape limit, and the range every key of theirs stays exact in
+        const int64_t mx = max_abs({match, mismatch, (int64_t)std::llabs((long long)gt->gap_open) + std::llabs((long long)gt->gap_extend)});
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const uint64_t n = slen(pair_a[k]), m = slen(pair_b[k]);
+            if (n > kGotohMaxN) return fail(ctx, PWA_E_CAPACITY, "gotoh alignments take patterns of at most 1024 symbols");
+            if (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)mx >= (long double)(1u << 28))
+                return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
+        }
+    }
     HIPC(ctx, hipSetDevice(ctx->device));
     const bool local = mode == PWA_MODE_SW, semi = mode == PWA_MODE_SG;   // (semi-global: NW's classes, guards and codes; no gap shift)
-    auto slen = [&](uint32_t s) -> uint64_t { return seq_off[s + 1] - seq_off[s]; };
+    const bool sband_on = ctx->score_band && !gt;   // (the gotoh kernels write no score band)
     ctx->fill_ms = ctx->tb_ms = 0.f;
     ctx->band_bytes = 0;
     const bool dbg = ctx->knobs.debug;
@@ -2855,7 +2897,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     bool seen[256];
     scan_bytes(seq_bytes, seq_off, n_seq, is_used, seen, 1ull << 20);
     uint8_t code_of[256];
-    const bool coded = code_alphabet(seen, code_of, match, mismatch, gap, ctx->knobs);
+    const bool coded = !gt && code_alphabet(seen, code_of, match, mismatch, gap, ctx->knobs);   // (gotoh: raw bytes, compared)
     const bool dash_seen = seen[(unsigned char)'-'], nul_seen = seen[0];
     // overlapLongestExactMatch (hw2.cpp:269) does not count a column whose symbols are '-' -- also when the '-' is part
     // of the input sequence itself: the walk needs the arena's value for that byte
@@ -2876,7 +2918,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     const bool keyed = tb_range_ok(longest_sum, match, mismatch, gap, local ? 26 : 28) && !ctx->knobs.no_keyed_tb;   // (local: H * 16 in the first-maximum records)
     // Global alignments with table scoring run in gap-shifted coordinates G = H - gap (i + j): the same recurrence with gap 0 and
     // scores s - 2 gap, identical comparisons and codes, one instruction less per cell (pair_fill.hip.h, GAP0: gap0_ok)
-    const bool gap0 = !local && !semi && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift && gap0_ok(longest_sum, match, mismatch, gap);
+    const bool gap0 = !gt && !local && !semi && coded && keyed && !ctx->score_band && !ctx->knobs.no_gap_shift && gap0_ok(longest_sum, match, mismatch, gap);
     const int k_match = gap0 ? match - 2 * gap : match, k_mismatch = gap0 ? mismatch - 2 * gap : mismatch, k_gap = gap0 ? 0 : gap;
     // the mini-stripe engine exists for keyed cells with table scoring; PWA_FORCE_RL / PWA_FORCE_W address the stripe engine
     const bool mini_ok = coded && keyed && ctx->knobs.tb_engine != 0 && !ctx->knobs.force_rl && !ctx->knobs.force_w &&
@@ -2900,6 +2942,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     }
     const bool tall_stripes = stripes2 >= 1024 && !ctx->knobs.force_rl;
     auto class_of = [&](uint64_t n) -> TbClass {   // (w of a mini class = its lanes per pair)
+        if (gt) return n <= 256 ? TbClass{true, mini_rl_for(n), 16} : TbClass{true, n <= 512 ? 8 : 16, 64};
         if (mini_ok && n <= 256) return TbClass{true, mini_rl_for(n), 16};
         if (wide_ok && n <= 1024) return TbClass{true, wide_rl_for(n), 64};
         PairGeom g = choose_geom(ctx->knobs, n, keyed, true);
@@ -2929,7 +2972,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     // waves on a chip of 1024 SIMDs.  So: a range should hold ~8192 pairs where the list has them (2048+ waves), it may use up to
     // 48 GiB for that (the workspace is kept in the context: the slow hipMalloc is paid once), and a list that needs several ranges is
     // cut into EQUAL ones, not into full ones and a remainder.
-    const uint64_t band_mult = ctx->score_band ? 5 : 1;
+    const uint64_t band_mult = sband_on ? 5 : 1;
     uint64_t chunk_target = std::min<uint64_t>(budget, 8ull << 30);
     uint64_t pairs_target = ~0ull;   // live pairs per range, when the list is cut into several
     {
@@ -3052,7 +3095,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
     if (!ranges.empty()) {
         // + one traceback window: the walk stages whole windows
         HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, band_cap + 32768, d_band, &p_band));
-        if (ctx->score_band)
+        if (sband_on)
             HIPC(ctx, cached_workspace(ctx->sband_cache, ctx->sband_cache_bytes, band_cap * sizeof(int32_t), d_sband, &p_sband));
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], walk_ops ? ops_cap_b : 16, d_ops_own, &p_ops));
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
@@ -3092,6 +3135,10 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             ooff[q] = rg.tiled ? ops_off[k] - ops_lo : oo;
             if (!(n && m) && !local) {   // (semi-global: column 0, or nothing for an empty pattern)
                 res[q].score = wrap_mul((int64_t)(semi ? n : n + m), gap);
+                if (gt) {   // one gap of length L: gap_open + L * gap_extend
+                    const uint64_t L = semi ? n : n + m;
+                    res[q].score = L ? (int32_t)((uint32_t)gt->gap_open + (uint32_t)wrap_mul((int64_t)L, gt->gap_extend)) : 0;
+                }
                 res[q].end_i = (uint32_t)n;
                 res[q].end_j = semi ? 0u : (uint32_t)m;
             }
@@ -3114,7 +3161,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
                 d.n = (int32_t)n;
                 d.m = (int32_t)m;
                 d.tb = static_cast<uint8_t*>(p_band) + L.bo[p];
-                if (ctx->score_band) d.sband = static_cast<int32_t*>(p_sband) + L.bo[p];
+                if (sband_on) d.sband = static_cast<int32_t*>(p_sband) + L.bo[p];
                 d.res = d_res + q;
                 d.ops = walk_ops ? d_ops + ooff[q] : d_ops;   // WALK_OVERLAP never writes ops
                 d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
@@ -3126,7 +3173,7 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
                 PairDesc d = pd[np - 1];
                 d.n = 0;
                 d.tb = static_cast<uint8_t*>(p_band) + L.dummy_bo[dmy];
-                if (ctx->score_band) d.sband = static_cast<int32_t*>(p_sband) + L.dummy_bo[dmy];
+                if (sband_on) d.sband = static_cast<int32_t*>(p_sband) + L.dummy_bo[dmy];
                 pd.push_back(d);
             }
             PairLaunch pl;
@@ -3135,15 +3182,17 @@ static int align_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int
             pl.keyed = keyed;
             pl.gap0 = gap0;
             pl.semi = semi;
+            pl.gotoh = gt ? mode : -1;
             int rc = L.cls.mini ? pl.build_mini(ctx, pd, (uint32_t)np, k_match, k_mismatch, k_gap, L.cls.rl, L.cls.w)
                                 : pl.build(ctx, pd, k_match, k_mismatch, k_gap, PairGeom{L.cls.rl, L.cls.w});
             if (rc != PWA_OK) return rc;
             pl.G.dash = dash_sym;
+            if (gt) pl.G.gap_extend = gt->gap_extend;
             mark("task list build + upload");
             if (dbg) std::fprintf(stderr, "[pwa] fill launch %s RL=%d W|LN=%d grid=%u pairs=%u tasks=%u rows=%llu\n", L.cls.mini ? "mini" : "stripes", L.cls.rl,
                                   L.cls.w, pl.grid, pl.G.n_pairs, pl.G.n_tasks, (unsigned long long)pl.row_bytes);
             HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-            rc = pl.launch(ctx, ctx->stream, local, true, walk_ops ? WALK_OPS : WALK_OVERLAP, ctx->ev[1], ctx->score_band);
+            rc = pl.launch(ctx, ctx->stream, local, true, walk_ops ? WALK_OPS : WALK_OVERLAP, ctx->ev[1], sband_on);
             if (rc != PWA_OK) return rc;
             HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
             HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -3277,6 +3326,46 @@ int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int g
     const StrOut str{cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed};
     return align_batch_impl(ctx, mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, nullptr,
                             nullptr, nullptr, end_cells, start_cells, nullptr, &str);
+}
+
+static int gotoh_batch_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                            const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                            int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells,
+                            const StrOut* str) {
+    if (!ctx) return PWA_E_INVALID;
+    if (gap_open > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
+    if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    const GotohSpec gs{gap_open, gap_extend};
+    GotohStatsScope scope(ctx);
+    ctx->fill_ms = ctx->tb_ms = 0.f;
+    ctx->band_bytes = 0;
+    return align_batch_impl(ctx, mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, ops, ops_off,
+                            n_ops, end_cells, start_cells, nullptr, str, &gs);
+}
+
+int pwa_align_gotoh_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                          const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                          int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells) {
+    if (ctx && !ops) return fail(ctx, PWA_E_INVALID, "null input");
+    return gotoh_batch_impl(ctx, mode, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, ops,
+                            ops_off, n_ops, end_cells, start_cells, nullptr);
+}
+
+int pwa_align_gotoh_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                                const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                                int32_t* score_out, char* cigar, uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap,
+                                uint64_t* mdz_off, uint64_t* end_cells, uint64_t* start_cells, uint64_t needed[2]) {
+    const StrOut str{cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed};
+    return gotoh_batch_impl(ctx, mode, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out,
+                            nullptr, nullptr, nullptr, end_cells, start_cells, &str);
+}
+
+int pwa_align_gotoh_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
+    if (!ctx) return PWA_E_INVALID;
+    if (fill_ms) *fill_ms = ctx->gotoh_fill_ms;
+    if (walk_ms) *walk_ms = ctx->gotoh_walk_ms;
+    if (band_bytes) *band_bytes = ctx->gotoh_band_bytes;
+    return PWA_OK;
 }
 
 int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,

@@ -307,6 +307,49 @@ int pwa_align_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch, int g
                           uint64_t needed[2] /* or NULL */);
 
 /*
+ * Affine-gap ("gotoh") alignments of many pairs: pwa_align_batch / pwa_align_batch_cigar with a gap open and a gap extend.  Named
+ * gotoh, not affine, to keep them apart from hw3's drop-in (pwa_scores_affine, pwa_align_affine_batch), whose quirks they do not share.
+ * Scoring: match, mismatch, gap_open, gap_extend (signed, the usual sign convention); a gap of length L scores gap_open + L * gap_extend.
+ * gap_open <= 0 and gap_extend <= 0, else PWA_E_INVALID.  s(i,j) = match when p[i-1] == t[j-1] as raw bytes (any byte value, NUL and
+ * '-' included), mismatch otherwise; oe = gap_open + gap_extend.
+ *   E[i][j] = max(H[i][j-1] + oe, E[i][j-1] + gap_extend)   'I' (left);  a tie OPENS
+ *   F[i][j] = max(H[i-1][j] + oe, F[i-1][j] + gap_extend)   'D' (up);    a tie OPENS
+ *   H[i][j] = max(H[i-1][j-1] + s(i,j), E[i][j], F[i][j])    SW: and 0
+ *   H tie-break  NW, SG: diag >= E >= F  (hw2's NW: diag >= left >= up);  SW: zero > diag > F > E  (hw2's SW: zero > diag > up > left)
+ *   E[i][0] = F[0][j] = -inf
+ *   NW: H[0][0] = 0, H[0][j] = gap_open + j * gap_extend, H[i][0] = gap_open + i * gap_extend
+ *   SW: H[0][j] = H[i][0] = 0
+ *   SG: H[0][j] = 0, H[i][0] = gap_open + i * gap_extend
+ * End cells and scores follow the linear modes: NW ends at (n, m); SW at the first row-major maximum of H, or at (0, 0) with no ops
+ * when every H is 0; SG at (n, j*), j* the smallest j with maximal H[n][j].
+ * The walk starts in state H at the end cell.  In H the cell's source decides: diag emits 'M' and goes to (i-1, j-1); E or F switch to
+ * that state on the same cell; SW stops on a zero cell.  In E: 'I', then (i, j-1) in H when E[i][j] opened, in E when it extended; F
+ * likewise with 'D' and (i-1, j).  Boundaries as in the linear modes: NW and SG emit the 'D' run down column 0, NW the 'I' run along
+ * row 0; SG stops at row 0 with start_cell = (0, j0); SW stops in state H at i = 0, at j = 0 or on a zero cell.  Ops are written in
+ * traceback order ('M' / 'D' / 'I'), as pwa_align_batch writes them; a pair with an empty side follows pwa_align_batch_cigar's
+ * conventions per mode (its one gap scores gap_open + L * gap_extend, an empty pair 0).
+ * With gap_open = 0, the H matrix, every code choice and every op list equal the linear mode's with gap = gap_extend.
+ * Range: every result is exact while (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) < 2^28; a pair beyond that is
+ * PWA_E_CAPACITY.  Shape: patterns of at most 1024 symbols (0..256 rows: 16 lanes per pair, 257..1024: one pair per wave), else
+ * PWA_E_CAPACITY; texts of any length the linear calls take.
+ * Arguments, op-region layout, range splitting (PWA_RANGE_BYTES) and string buffers (pwa_cigar_bound / pwa_mdz_bound) are exactly
+ * pwa_align_batch's and pwa_align_batch_cigar's.  An empty pair list is PWA_OK.
+ */
+int pwa_align_gotoh_batch(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mismatch, int gap_open, int gap_extend,
+                          const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                          const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off,
+                          uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */);
+int pwa_align_gotoh_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch, int gap_open, int gap_extend,
+                                const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                                const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                                uint64_t needed[2] /* or NULL */);
+/* Device ms of the fills and walks of the last pwa_align_gotoh_batch(_cigar) on ctx, and the band bytes they wrote. */
+int pwa_align_gotoh_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
+
+/*
  * The -g selection without the op lists: hw2.cpp:342-350 keeps, of every pair's global alignment, only
  * overlapLongestExactMatch(alignedPattern, alignedReference) (hw2.cpp:267-278) and the score.  Same fill and
  * traceback band as pwa_align_batch; the device walk looks at the symbols under each run of diagonal moves
