@@ -10,6 +10,11 @@ import oracle_lib as O
 import sg_oracle as SG
 
 SCORINGS = [(1, -4, -6, -1), (2, -3, -5, -2), (5, -4, -16, -4), (1, -1, -1, -1), (0, 0, 0, 0), (3, -1, 0, -2)]
+# the edges the device kernels are tested at too (test_gpu_gotoh_edges.py): gap_extend = 0 (every open / extend choice ties), match <=
+# mismatch, a positive mismatch (pad rows past n then outgrow the real ones), match = 0 with gaps, a gap open that never pays off,
+# an extension dearer than the opening, a negative match
+EDGE_SCORINGS = [(1, -4, -6, 0), (3, -2, -7, 0), (-1, 2, -3, 0), (-1, 2, -3, -1), (0, 1, -2, -1), (1, -1, -20, -1), (4, -1, -1, -3),
+                 (-2, -1, -1, -1)]
 
 
 def _rand(rng, n, alpha=b"ACGT"):
@@ -17,7 +22,7 @@ def _rand(rng, n, alpha=b"ACGT"):
 
 
 @pytest.mark.parametrize("mode", ["nw", "sw", "sg"])
-@pytest.mark.parametrize("sc", SCORINGS)
+@pytest.mark.parametrize("sc", SCORINGS + EDGE_SCORINGS)
 def test_oracle_matches_scalar_dp(mode, sc):
     rng = random.Random(hash((mode, sc)) & 0xffff)
     match, mismatch, go, ge = sc
@@ -35,7 +40,7 @@ def test_oracle_matches_scalar_dp(mode, sc):
 
 
 @pytest.mark.parametrize("mode", ["nw", "sw", "sg"])
-@pytest.mark.parametrize("sc", SCORINGS)
+@pytest.mark.parametrize("sc", SCORINGS + EDGE_SCORINGS)
 def test_op_scores_equal_scores(mode, sc):
     rng = random.Random(7 + len(mode))
     match, mismatch, go, ge = sc
@@ -89,3 +94,87 @@ def test_one_event_is_one_gap():
     ops = bytes(reversed(r["ops"]))
     assert b"I" * 12 in ops and ops.count(b"I") == 12 and b"D" not in ops
     assert r["score"] == len(read) - 6 - 12
+
+
+def _rule_walk(p, t, mode, match, mismatch, go, ge):
+    """pwalign.h's end cell and three-state walk, written from the stated rules over scalar_dp's H alone: E and F are recomputed
+    from H, every choice is made from values (no source or open codes) -> (score, end, start, ops)"""
+    n, m = len(p), len(t)
+    H = GO.scalar_dp(p, t, mode, match, mismatch, go, ge)[0]
+    oe, inf = go + ge, float("-inf")
+    E = [[inf] * (m + 1) for _ in range(n + 1)]
+    F = [[inf] * (m + 1) for _ in range(n + 1)]
+    for i in range(1, n + 1):
+        for j in range(1, m + 1):
+            E[i][j] = max(H[i][j - 1] + oe, E[i][j - 1] + ge)
+            F[i][j] = max(H[i - 1][j] + oe, F[i - 1][j] + ge)
+    if mode == "nw":
+        end = (n, m)
+    elif mode == "sg":
+        end = (n, min(j for j in range(m + 1) if H[n][j] == max(H[n])))
+    else:
+        best = max(max(r) for r in H)
+        end = (0, 0) if best <= 0 else next((i, j) for i in range(n + 1) for j in range(m + 1) if H[i][j] == best)
+    i, j = end
+    ops, st = [], "H"
+    while i > 0 and j > 0:
+        if st == "H":
+            d = H[i - 1][j - 1] + (match if p[i - 1] == t[j - 1] else mismatch)
+            h = H[i][j]
+            if mode == "sw" and h == 0:
+                break
+            order = ["D", "F", "E"] if mode == "sw" else ["D", "E", "F"]   # SW: zero > diag > F > E; NW, SG: diag >= E >= F
+            st = next(s for s in order if {"D": d, "E": E[i][j], "F": F[i][j]}[s] == h)
+            if st == "D":
+                ops.append("M")
+                i, j, st = i - 1, j - 1, "H"
+                continue
+        if st == "E":   # a tie opens
+            ops.append("I")
+            st = "H" if H[i][j - 1] + oe >= E[i][j - 1] + ge else "E"
+            j -= 1
+        else:
+            ops.append("D")
+            st = "H" if H[i - 1][j] + oe >= F[i - 1][j] + ge else "F"
+            i -= 1
+    if mode != "sw":
+        ops += ["D"] * i
+        i = 0
+        if mode == "nw":
+            ops += ["I"] * j
+            j = 0
+    return H[end[0]][end[1]], end, (i, j), "".join(ops).encode()
+
+
+def _homopolymer_cases():
+    """runs with one gap that can sit at any of several places (all of them tie), on both sides and in the middle"""
+    out = []
+    for a, b in [(b"ACG", b"CA"), (b"", b"GC"), (b"TG", b""), (b"G", b"C")]:
+        for run, d in [(b"T", 5), (b"TT", 3), (b"A", 4)]:
+            for k in (1, 2, 3):
+                short, long_ = a + run * d + b, a + run * (d + k) + b
+                out += [(short, long_), (long_, short)]
+    out += [(b"AAAA", b"AA"), (b"AA", b"AAAA"), (b"A", b"AAAAA"), (b"CAAAC", b"CAC"), (b"ACACAC", b"ACAC"), (b"ACAC", b"ACACAC")]
+    return out
+
+
+@pytest.mark.parametrize("mode", ["nw", "sw", "sg"])
+@pytest.mark.parametrize("sc", [(1, -4, -6, -1), (2, -3, -5, -2), (1, -4, -6, 0), (1, -1, -1, -1), (-1, 2, -3, 0), (0, 1, -2, -1)])
+def test_walk_tie_breaks_follow_the_stated_rules(mode, sc):
+    """gap placement in homopolymer and tandem runs, open vs extend (gap_extend = 0 ties them), first maxima: the oracle's walk equals
+    the rule walk above, field for field"""
+    match, mismatch, go, ge = sc
+    for p, t in _homopolymer_cases():
+        r = GO.align(p, t, mode, match, mismatch, go, ge)
+        score, end, start, ops = _rule_walk(p, t, mode, match, mismatch, go, ge)
+        assert (r["score"], r["end"], r["start"], r["ops"]) == (score, end, start, ops), (p, t)
+
+
+def test_homopolymer_gap_sits_at_the_run_start():
+    """the walk runs backwards and prefers the diagonal, so a gap in a run lands at its first base (forward order); global and
+    semi-global (a local alignment of these drops the gap)"""
+    for mode in ("nw", "sg"):
+        r = GO.align(b"ACGTTTTTCA", b"ACGTTTTTTTCA", mode, 1, -4, -6, -1)
+        assert bytes(reversed(r["ops"])) == b"MMMIIMMMMMMM", mode
+        r = GO.align(b"ACGTTTTTTTCA", b"ACGTTTTTCA", mode, 1, -4, -6, -1)
+        assert bytes(reversed(r["ops"])) == b"MMMDDMMMMMMM", mode

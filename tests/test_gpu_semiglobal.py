@@ -253,3 +253,47 @@ def test_errors(ctx, pkg):
     dp = np.zeros((5, 6), dtype=np.int32)
     assert L.pwa_align_matrices(h, 3, 1, -1, -1, b"ACGT", 4, b"ACGTT", 5, dp.ctypes.data_as(C.c_void_p), None) == -1
     assert ctx.align("sg", b"ACGT", b"TTACGTT", 1, -1, -1)["score"] == 4   # the context is usable afterwards
+
+
+@pytest.mark.parametrize("engine,n_class", [("stripes", (1, 63, 64)), ("stripes", (65, 127, 128)), ("stripes", (129, 200, 256)),
+                                            ("stripes", (257, 300, 511, 512, 513)), ("stripes", (700, 1025, 1100, 1537)),
+                                            ("mini", (1, 15, 16, 17, 63, 64)), ("mini", (65, 95, 96, 97, 127, 128)),
+                                            ("mini", (129, 150, 159, 160, 161)), ("mini", (191, 192, 193, 255, 256, 257)),
+                                            ("wide", (257, 300, 384, 385, 511, 512, 513)), ("wide", (700, 768, 769, 1023, 1024, 1025))])
+def test_sg_shapes_around_every_boundary(engine, n_class):
+    """test_gpu_parity.py's boundary grid in semi-global mode: pattern lengths around every stripe, mini-stripe (16 lanes x RL = 4 .. 16)
+    and one-pair-per-wave (64 lanes x RL = 6, 8, 12, 16) class edge x text lengths around the 16-step chunks, the 15- and 63-step lane
+    ramps and the 512-column LDS ring; table and compare scoring, with and without the score band: op lists, end and start cells and
+    scores against sg_oracle (one fill per pattern, the texts are prefixes of one)."""
+    rng = random.Random(sum(n_class) * 11 + len(n_class))
+    ms = [0, 1, 2, 15, 16, 17, 31, 47, 48, 49, 62, 63, 64, 65, 79, 80, 81, 95, 127, 128, 129, 191, 255, 256, 257, 383, 384, 385, 511, 512,
+          513, 520, 767, 768, 769, 1030]
+    groups = []
+    for n in n_class:
+        p = bytes(rng.choice(b"ACGT") for _ in range(n))
+        core = _mutate(rng, p, b"ACGT", 0.1)
+        t = bytearray(rng.choice(b"ACGT") for _ in range(max(ms)))
+        off = rng.randint(0, 60)
+        t[off:off + len(core)] = core[:max(ms) - off]
+        groups.append((p, bytes(t)))
+    seqs, pa, pb = [], [], []
+    for p, t in groups:
+        for m in ms:
+            seqs += [p, t[:m]]
+            pa.append(len(seqs) - 2)
+            pb.append(len(seqs) - 1)
+    scorings = [(1, -1, -1), (2, -3, -5)]
+    want = {sc: [w for p, t in groups for w in SG.prefixes(p, t, ms, *sc)] for sc in scorings}
+    variants = [({}, False), ({"PWA_NO_PAIR_TABLE": "1"}, False), ({}, True)]
+    for env, band in variants:
+        if engine == "stripes":
+            env = dict(env, PWA_TB_ENGINE="0")
+        if engine == "wide":
+            env = dict(env, PWA_TB_ENGINE="2")
+        with switched_context(**env) as c:
+            c.set_score_band(band)
+            for sc in scorings:
+                res = c.align_batch("sg", seqs, pa, pb, *sc)
+                for k, (r, w) in enumerate(zip(res, want[sc])):
+                    assert (r["score"], r["ops"], tuple(r["end"]), tuple(r["start"])) == \
+                        (w["score"], w["ops"], tuple(w["end"]), tuple(w["start"])), (env, band, sc, len(seqs[pa[k]]), len(seqs[pb[k]]))
