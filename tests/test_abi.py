@@ -54,7 +54,8 @@ def test_dropin_library_exports_the_reference_signatures():
 
 def test_host_sorting_helpers_selftest():
     """The scheduler's stable sorts (counting sort incl. its multi-threaded form, length sort, radix sort) against std::stable_sort on
-    lists of up to 2^20 elements -- inside the library, no GPU involved."""
+    lists of up to 2^20 elements, and the range planner of the alignment batches on random length lists (all three classes, empty sides,
+    linear and gotoh, several ranges, score band, gapped op regions) against the invariants of a plan -- inside the library, no GPU involved."""
     L = load_pkg().lib()
     L.pwa_selftest_host.argtypes = [C.c_uint32]
     L.pwa_selftest_host.restype = C.c_int
