@@ -1,5 +1,5 @@
 // cigar_kernels.hip -- the count and write passes of pwa_align_batch_cigar (cigar.hip.h), launched by align_batch_impl
-// (pwalign.hip) between a range's walks and its copy back.  Own translation unit.
+// (pwalign_align.hip) between a range's walks and its copy back.  Own translation unit.
 #include "cigar.hip.h"
 
 namespace pwa {

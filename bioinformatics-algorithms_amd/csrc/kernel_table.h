@@ -1,5 +1,5 @@
 // kernel_table.h -- the instantiated strip kernels (strip_kernels.hip) and pair-engine kernels (pair_kernels.hip) as
-// seen by the host scheduler (pwalign.hip).  Three translation units so that the device code compiles in parallel.
+// seen by the host units (pwalign*.hip).  Three translation units so that the device code compiles in parallel.
 #pragma once
 #include "batch_scores.hip.h"
 #include "batch_affine.hip.h"

@@ -24,7 +24,7 @@
 //   G = max(kvo, kf - 1)                 likewise (70-75);  xF of (i+1, j) = G & 1
 // xF of a lane's first row thus crosses lanes inside G's low bits, with the same DPP shift, ring slot and HBM word that carry G.
 //
-// Range (the host's guard, pwalign.hip: (n + m + 2) * max(|match|, |mismatch|, |go| + |ge|) < 2^26).  Every real value (a path's score,
+// Range (the host's guard, pwalign_affine_tb.hip: (n + m + 2) * max(|match|, |mismatch|, |go| + |ge|) < 2^26).  Every real value (a path's score,
 // + go once for G / X) is then inside +-2^26, its key inside +-2^28.  The sentinel key kAffTbNeg = -2^30 (value -2^28) enters only as
 // G[0][j] and X[i][0]; one + 4 ge later it is beaten by a real value (kvo), so no key leaves (-2^30 - 2^28, 2^28): no int32 wraps, and a
 // sentinel-derived candidate never wins a max against a real one, exactly as the reference's INT_MIN/2 never does inside the same range.

@@ -1,0 +1,750 @@
+// pwalign_ctx.hip -- contexts, device memory management (buffers, workspaces, uploads, the sequence arena) and the launches of
+// the wavefront (pair) engine.  The schedulers of the entry points are in pwalign.hip (score batches), pwalign_affine_tb.hip and
+// pwalign_align.hip.  gfx950 only; there is no CPU path.
+#include "pwalign_internal.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "sufarr_ctx.h"
+
+using namespace pwa;
+
+namespace pwa {
+// gotoh_kernels.hip: the affine-gap (Gotoh) fills and walks, mode = PWA_MODE_NW | SW | SG; ln = 16 (rl in kMiniRL) or 64 (rl = 8 | 16)
+void (*gotoh_fill_kernel_for(int rl, int mode, int ln))(const PairParams);
+void (*gotoh_walk_kernel_for(int rl, int mode, int ln))(const PairParams);
+}
+
+__global__ void pwa_nop_kernel(int* p) {
+    if (p && threadIdx.x == 12345) *p = 0;
+}
+
+// Symbols -> codes on the device (build_arena): n16 blocks of 16 bytes at p, every byte through the 256-entry table.  The host then only
+// copies raw bytes into the upload buffers (a memcpy instead of a table lookup per byte, which was what bounded a 570 MB arena).
+struct RecodeTable {
+    uint8_t t[256];
+};
+__global__ __launch_bounds__(256) void pwa_recode_kernel(uint8_t* p, size_t n16, const RecodeTable tab) {
+    __shared__ uint8_t lut[256];
+    lut[threadIdx.x] = tab.t[threadIdx.x];
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
+        uint4 v = reinterpret_cast<const uint4*>(p)[i];
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            w[d] = (uint32_t)lut[w[d] & 0xffu] | (uint32_t)lut[(w[d] >> 8) & 0xffu] << 8 | (uint32_t)lut[(w[d] >> 16) & 0xffu] << 16 | (uint32_t)lut[w[d] >> 24] << 24;
+        reinterpret_cast<uint4*>(p)[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+void Knobs::read() {
+    auto flag = [](const char* n) { return std::getenv(n) != nullptr; };
+    auto num = [](const char* n, int dflt) { const char* e = std::getenv(n); return e ? std::atoi(e) : dflt; };
+    debug = flag("PWA_DEBUG");
+    probe = flag("PWA_PROBE");
+    force_rl = num("PWA_FORCE_RL", 0);
+    force_w = num("PWA_FORCE_W", 0);
+    wg_per_cu = num("PWA_WG_PER_CU", 0);
+    no_lds_pad = flag("PWA_NO_LDS_PAD");
+    if (const char* e = std::getenv("PWA_STAMPS")) stamps = e;
+    trace_stripe = num("PWA_TRACE_STRIPE", -1);
+    no_packed_dist = flag("PWA_NO_PACKED_DIST");
+    force_lanes = num("PWA_FORCE_LANES", -1);
+    force_r = num("PWA_FORCE_R", 0);
+    force_mode = num("PWA_FORCE_MODE", -1);
+    if (const char* e = std::getenv("PWA_ARENA_LIMIT")) arena_limit = std::max<uint64_t>(1024, std::strtoull(e, nullptr, 10));
+    if (const char* e = std::getenv("PWA_LANE_ROWS_LIMIT")) lane_rows_limit = std::max<uint64_t>(1024, std::strtoull(e, nullptr, 10));
+    mini_per_cu = num("PWA_MINI_PER_CU", 0);
+    if (const char* e = std::getenv("PWA_RANGE_BYTES")) range_bytes = std::max<uint64_t>(4096, std::strtoull(e, nullptr, 10));
+    no_pair_table = flag("PWA_NO_PAIR_TABLE");
+    no_keyed_tb = flag("PWA_NO_KEYED_TB");
+    no_gap_shift = flag("PWA_NO_GAP_SHIFT");
+    no_tiled_ops = flag("PWA_NO_TILED_OPS");
+    no_pipeline = flag("PWA_NO_PIPELINE");
+    pipe_runs = num("PWA_PIPE_RUNS", 0);
+    scores_route = num("PWA_SCORES_ROUTE", -1);
+    tb_engine = num("PWA_TB_ENGINE", -1);
+    cell16 = num("PWA_CELL16", -1);
+    prof16 = num("PWA_PROF16", -1);
+    affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
+    if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+}
+
+pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
+    SaCtxView v;
+    v.device = c->device;
+    v.stream = c->stream;
+    v.debug = c->knobs.debug;
+    v.occ_chunk_hits = c->knobs.occ_chunk_hits;
+    v.err = &c->err;
+    return v;
+}
+
+namespace {
+
+constexpr size_t kFreeListMaxBytes = 24ull << 30, kFreeListMaxCount = 64;   // (DevBuf)
+bool key_byte(int64_t k) { return k <= 127 && k >= -126; }   // (diag_keys_fit, gap0_ok)
+
+// Runs fn(first_seq, last_seq, thread) over the sequences, split into byte-balanced contiguous ranges, on up to
+// 16 host threads (one per >= 8 MiB): the host passes over the input (alphabet scan, symbol coding into the
+// arena) are memory-bound loops that otherwise dominate the call for inputs of hundreds of MB.
+template <class F>
+void for_seq_ranges(const uint64_t* seq_off, uint32_t n_seq, F&& fn, int* n_threads_out = nullptr, uint64_t bytes_per_thread = 8ull << 20) {
+    const uint64_t total = n_seq ? seq_off[n_seq] - seq_off[0] : 0;
+    int T = (int)std::min<uint64_t>({16, total / bytes_per_thread + 1, std::max(1u, std::thread::hardware_concurrency())});
+    T = std::max(1, std::min<int>(T, (int)std::max<uint32_t>(n_seq, 1)));
+    if (n_threads_out) *n_threads_out = T;
+    std::vector<uint32_t> cut((size_t)T + 1, n_seq);
+    cut[0] = 0;
+    for (int t = 1; t < T; ++t) {
+        const uint64_t want = seq_off[0] + total / (uint64_t)T * (uint64_t)t;
+        cut[(size_t)t] = (uint32_t)(std::lower_bound(seq_off, seq_off + n_seq, want) - seq_off);
+    }
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t) th.emplace_back([&, t] { fn(cut[(size_t)t], cut[(size_t)t + 1], t); });
+    fn(cut[0], cut[1], 0);
+    for (auto& x : th) x.join();
+}
+
+}  // namespace
+
+namespace pwa {
+
+void DevBuf::release() {
+    if (p) {
+        if (pool && pool->free_list.size() < kFreeListMaxCount && pool->free_list_bytes + bytes <= kFreeListMaxBytes) {
+            pool->free_list.emplace_back(p, bytes);
+            pool->free_list_bytes += bytes;
+        } else {
+            (void)hipFree(p);
+        }
+    }
+    p = nullptr;
+    bytes = 0;
+}
+hipError_t DevBuf::alloc(size_t n) {
+    release();
+    if (n == 0) n = 16;
+    if (pool) {   // best fit among the kept buffers: at least n, at most 2 n + 1 MiB (a 5 GB block is not spent on a 1 KB request)
+        size_t best = pool->free_list.size();
+        for (size_t i = 0; i < pool->free_list.size(); ++i) {
+            const size_t have = pool->free_list[i].second;
+            if (have >= n && have <= 2 * n + (1u << 20) && (best == pool->free_list.size() || have < pool->free_list[best].second)) best = i;
+        }
+        if (best < pool->free_list.size()) {
+            p = pool->free_list[best].first;
+            bytes = pool->free_list[best].second;
+            pool->free_list_bytes -= bytes;
+            pool->free_list.erase(pool->free_list.begin() + (long)best);
+            return hipSuccess;
+        }
+    }
+    hipError_t e = hipMalloc(&p, n);
+    if (e != hipSuccess && pool && !pool->free_list.empty()) {   // out of memory with buffers parked: give them back and try again
+        for (auto& f : pool->free_list) (void)hipFree(f.first);
+        pool->free_list.clear();
+        pool->free_list_bytes = 0;
+        (void)hipGetLastError();
+        e = hipMalloc(&p, n);
+    }
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+}
+
+// Stable LSD radix sort of `idx` by 64-bit keys (16-bit digits; passes whose digit is constant are skipped).
+// Sorting a million pairs with std::sort and a comparator that looks lengths up cost ~95 ms per batch [gpu box].
+void radix_sort_by_key(std::vector<uint64_t>& key, std::vector<uint32_t>& idx) {
+    const size_t n = idx.size();
+    std::vector<uint64_t> key2(n);
+    std::vector<uint32_t> idx2(n);
+    std::vector<size_t> cnt(65536);
+    for (int pass = 0; pass < 4; ++pass) {
+        const int sh = 16 * pass;
+        std::fill(cnt.begin(), cnt.end(), 0);
+        for (size_t i = 0; i < n; ++i) ++cnt[(key[i] >> sh) & 0xffff];
+        if (n && cnt[(key[0] >> sh) & 0xffff] == n) continue;
+        size_t run = 0;
+        for (size_t d = 0; d < 65536; ++d) {
+            const size_t c = cnt[d];
+            cnt[d] = run;
+            run += c;
+        }
+        for (size_t i = 0; i < n; ++i) {
+            const size_t o = cnt[(key[i] >> sh) & 0xffff]++;
+            key2[o] = key[i];
+            idx2[o] = idx[i];
+        }
+        key.swap(key2);
+        idx.swap(idx2);
+    }
+}
+
+// out[v]: does byte v occur in a sequence s with in[s] != 0?  One pass over those sequences, on a thread per bytes_per_thread of input
+void scan_bytes(const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& in, bool out[256],
+                uint64_t bytes_per_thread) {
+    bool part[16][256] = {};
+    for_seq_ranges(seq_off, n_seq, [&](uint32_t s0, uint32_t s1, int t) {
+        bool* mine = part[t];
+        for (uint32_t s = s0; s < s1; ++s)
+            if (in[s])
+                for (uint64_t o = seq_off[s]; o < seq_off[s + 1]; ++o) mine[seq_bytes[o]] = true;
+    }, nullptr, bytes_per_thread);
+    for (int v = 0; v < 256; ++v) {
+        out[v] = false;
+        for (int t = 0; t < 16; ++t) out[v] |= part[t][v];
+    }
+}
+
+// the largest magnitude among scoring values (a trailing 1 where the result divides)
+int64_t max_abs(std::initializer_list<int64_t> vals) {
+    int64_t r = 0;
+    for (const int64_t v : vals) r = std::max<int64_t>(r, std::llabs((long long)v));
+    return r;
+}
+
+// The traceback kernels keep H * 4 + priority in int32 (pair_fill.hip.h): |H| has to stay below 2^28.
+// (bits = 26: local fills of the mini-stripe kernels, whose first-maximum records hold H * 16 + a step index, mini_fill.hip.h)
+bool tb_range_ok(uint64_t n_plus_m, int match, int mismatch, int gap, int bits) {
+    return (n_plus_m + 2) <= (1ull << bits) / (uint64_t)max_abs({match, mismatch, gap, 1});
+}
+
+// The keyed fills score four rows with one byte-table lookup (pair_fill.hip.h, PERM): the table holds the two diagonal key
+// constants, and both must fit a signed byte (key_byte).
+bool diag_keys_fit(int match, int mismatch, int gap) {
+    return key_byte(((int64_t)match - gap) * 4 + 2) && key_byte(((int64_t)mismatch - gap) * 4 + 2);
+}
+// Global fills in gap-shifted coordinates G = H - gap (i + j) (GAP0): |G| <= |H| + |gap| (n + m), twice the range, and both shifted
+// diagonal constants (s - 2 gap) * 4 + prio(diag) - prio(left) in the byte table
+bool gap0_ok(uint64_t n_plus_m, int match, int mismatch, int gap) {
+    return key_byte(((int64_t)match - 2 * (int64_t)gap) * 4 + 1) && key_byte(((int64_t)mismatch - 2 * (int64_t)gap) * 4 + 1) &&
+           tb_range_ok(n_plus_m, match, mismatch, gap, 27);
+}
+// Alphabets of at most 7 symbols (DNA, DNA + N, ...) are stored as codes 0..6 -- equality is all the recurrence ever asks of a symbol
+// (hw2.cpp:142, 208) -- so that the fill can score four rows with one byte-table lookup.  Fills code_of; true when the fills may use it.
+bool code_alphabet(const bool seen[256], uint8_t code_of[256], int match, int mismatch, int gap, const Knobs& knobs) {
+    int n_alpha = 0;
+    for (int v = 0; v < 256; ++v) {
+        code_of[v] = (uint8_t)std::min(n_alpha, 7);
+        if (seen[v]) ++n_alpha;
+    }
+    return n_alpha <= 7 && diag_keys_fit(match, mismatch, gap) && !knobs.no_pair_table;
+}
+// rows per lane of the four-pair mini-stripe class that holds an n-row pattern, 0: none (n > 256)
+int mini_rl_for(uint64_t n) {
+    for (const int rl : kMiniRL)
+        if (n <= (uint64_t)(16 * rl)) return rl;
+    return 0;
+}
+// ... and of the one-pair-per-wave class (64 lanes) for 257 .. 1024 rows
+int wide_rl_for(uint64_t n) { return n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16; }
+
+// A workspace of `bytes` from the context's cache slot (see pwa_ctx): reused when big enough, regrown otherwise;
+// requests beyond kBandCacheMax are served by `fallback` and freed with it.
+hipError_t cached_workspace(void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out) {
+    if (bytes > kBandCacheMax) {
+        const hipError_t e = fallback.alloc(bytes);
+        *out = fallback.p;
+        return e;
+    }
+    if (slot_bytes < bytes) {
+        if (slot) (void)hipFree(slot);
+        slot = nullptr;
+        slot_bytes = 0;
+        const hipError_t e = hipMalloc(&slot, bytes);
+        if (e != hipSuccess) {
+            slot = nullptr;
+            return e;
+        }
+        slot_bytes = bytes;
+    }
+    *out = slot;
+    return hipSuccess;
+}
+
+// pageable memory that the library does not own (or that is too large to mirror in page-locked memory): through a bounce buffer
+hipError_t upload_via_bounce(pwa_ctx* c, void* dst, const void* src, size_t bytes) {
+    constexpr size_t kChunk = 8u << 20;
+    hipError_t e = c->pin[pwa_ctx::PIN_BOUNCE].reserve(std::min(bytes, kChunk));
+    for (size_t o = 0; e == hipSuccess && o < bytes; o += kChunk) {
+        const size_t n = std::min(kChunk, bytes - o);
+        std::memcpy(c->pin[pwa_ctx::PIN_BOUNCE].p, static_cast<const uint8_t*>(src) + o, n);
+        e = hipMemcpy(static_cast<uint8_t*>(dst) + o, c->pin[pwa_ctx::PIN_BOUNCE].p, n, hipMemcpyHostToDevice);
+    }
+    return e;
+}
+
+// The device arena of a call: every used sequence s at aoff[s] (16-byte aligned) as symbols -- through `table` (256 entries) or
+// copied when table == nullptr -- and zeros everywhere else.  It goes up in pieces of ~32 MiB: while piece k is on its way
+// (copy stream, from one of two page-locked buffers of the context) piece k + 1 is being coded by several host threads into the
+// other -- readFasta's blob is never repacked into a second host copy, and a 570 MB arena costs 2 x 32 MiB of pinned memory.
+// r03: arenas of a MiB and more are coded ON THE DEVICE when no sequence holds a NUL byte (`nul_free`: the padding between sequences is
+// zeros and has to stay zeros, so the device table maps 0 to 0): the host threads then only copy raw bytes into the pieces and a small
+// kernel behind every piece's copy turns them into codes in place.
+hipError_t build_arena(pwa_ctx* c, void* d_arena, uint64_t arena_bytes, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                       const std::vector<uint8_t>& is_used, const std::vector<uint64_t>& aoff, const uint8_t* table, bool nul_free) {
+    constexpr uint64_t kPiece = 32ull << 20;
+    const bool on_device = table && nul_free && arena_bytes >= (1ull << 20) && arena_bytes % 16 == 0;
+    RecodeTable rt;
+    if (on_device) {
+        std::memcpy(rt.t, table, 256);
+        rt.t[0] = 0;
+        table = nullptr;   // the pieces take raw bytes
+    }
+    std::vector<uint32_t> used;
+    for (uint32_t s = 0; s < n_seq; ++s)
+        if (is_used[s]) used.push_back(s);
+    if (used.empty()) return hipMemset(d_arena, 0, arena_bytes);
+    hipError_t e = hipSuccess;
+    int piece = 0;
+    for (size_t u0 = 0; u0 < used.size() && e == hipSuccess; ++piece) {
+        size_t u1 = u0 + 1;
+        const uint64_t a0 = u0 == 0 ? 0 : aoff[used[u0]];
+        auto end_of = [&](size_t u) { return u < used.size() ? aoff[used[u]] : arena_bytes; };
+        while (u1 < used.size() && end_of(u1 + 1) - a0 <= kPiece) ++u1;
+        const uint64_t a1 = end_of(u1), bytes = a1 - a0;
+        PinnedBuf& pb = c->pin[pwa_ctx::PIN_ARENA + (piece & 1)];
+        if (piece >= 2) e = hipEventSynchronize(c->copy_ev[piece & 1]);   // the copy that last read this buffer
+        if (e == hipSuccess) e = pb.reserve(bytes);
+        if (e != hipSuccess) break;
+        uint8_t* const host = pb.as<uint8_t>();
+        // sequences u0 .. u1-1 of the piece over a few threads, byte-balanced
+        const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>({16, bytes / (1ull << 20) + 1, std::max(1u, std::thread::hardware_concurrency()), (uint64_t)(u1 - u0)}));
+        auto work = [&](int t) {
+            const uint64_t lo = a0 + bytes / T * t, hi = t + 1 == T ? a1 : a0 + bytes / T * (t + 1);
+            // first sequence whose region starts at or after lo (regions are [aoff[s], aoff[next]))
+            size_t u = std::lower_bound(used.begin() + u0, used.begin() + u1, lo, [&](uint32_t sidx, uint64_t v) { return aoff[sidx] < v; }) - used.begin();
+            if (t == 0) {
+                u = u0;
+                if (a0 < aoff[used[u0]]) std::memset(host, 0, aoff[used[u0]] - a0);
+            }
+            for (; u < u1 && aoff[used[u]] < hi; ++u) {
+                const uint32_t sidx = used[u];
+                const uint64_t len = seq_off[sidx + 1] - seq_off[sidx], r0 = aoff[sidx], r1 = end_of(u + 1);
+                uint8_t* dst = host + (r0 - a0);
+                const uint8_t* src = seq_bytes + seq_off[sidx];
+                if (table)
+                    for (uint64_t o = 0; o < len; ++o) dst[o] = table[src[o]];
+                else if (len)
+                    std::memcpy(dst, src, len);
+                std::memset(dst + len, 0, r1 - r0 - len);
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < T; ++t) th.emplace_back(work, t);
+        work(0);
+        for (auto& x : th) x.join();
+        e = hipMemcpyAsync(static_cast<uint8_t*>(d_arena) + a0, host, bytes, hipMemcpyHostToDevice, c->copy_stream);
+        if (e == hipSuccess) e = hipEventRecord(c->copy_ev[piece & 1], c->copy_stream);
+        if (e == hipSuccess && on_device && a0 % 16 == 0 && bytes % 16 == 0) {   // (pieces start and end on sequence regions: multiples of 16)
+            const size_t n16 = (size_t)(bytes / 16);
+            hipLaunchKernelGGL(pwa_recode_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 4096)), dim3(256), 0, c->copy_stream,
+                               static_cast<uint8_t*>(d_arena) + a0, n16, rt);
+            e = hipGetLastError();
+        } else if (e == hipSuccess && on_device) {
+            e = hipErrorInvalidValue;   // cannot happen: regions are 16-byte aligned
+        }
+        u0 = u1;
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->copy_stream);
+    return e != hipSuccess ? e : e2;
+}
+
+int fail(pwa_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    return code;
+}
+
+PairGeom choose_geom(const Knobs& kn, uint64_t max_n, bool keyed, bool keyed_tb) {
+    // (W = 3 -- three stripes + the helper = one wave per SIMD -- was measured in r02: no gain over W = 4, the stripes behind the
+    // first workgroup run ~5-9 % slower than the first either way: they run at the edge of what their producer has posted.)
+    // RL = 2 up to 32k rows (twice the stripes = twice the waves of a pair in flight), RL = 4 beyond.  (The choice was measured in r01 --
+    // 10k x 10k: RL = 2 10 % ahead; 100k x 100k: RL = 4 5 % ahead -- and has held since; today's fills: 1.65 ms / 11.8 - 12.2 ms)
+    PairGeom g{max_n <= 32768 ? 2 : 4, 4};
+    // 129..256 rows: ONE 256-row stripe (W = 1) instead of two 128-row stripes in a 4-stripe workgroup with two idle waves.  (Since r03
+    // only what the mini-stripe engine cannot take comes here with such patterns: alphabets of more than 7 symbols, scores beyond the keys.)
+    if (max_n > 128 && max_n <= 256) g.rl = 4;
+    if (kn.force_rl) g.rl = kn.force_rl == 2 ? 2 : 4;   // experiments only
+    if (!keyed) g.rl = 4;   // the plain int32 traceback form exists for RL = 4 only (pair_kernels.hip)
+    if ((max_n + 64 * g.rl - 1) / (64 * g.rl) <= 1) g.w = 1;
+    // (W = 8 was built and measured in r02: nine waves on a CU's four SIMDs share issue slots, a step goes from 197 to 317
+    // cycles -- a workgroup lives on one CU, so four compute waves is the most that keeps one stripe per SIMD)
+    (void)keyed_tb;
+    if (kn.force_w) g.w = kn.force_w == 1 ? 1 : 4;
+    return g;
+}
+
+size_t tb_band_bytes(uint64_t n, uint64_t m, int rl) {
+    const uint64_t stripes = (n + 64 * rl - 1) / (64 * rl);
+    return (size_t)(stripes * band_steps(m) * 64 * rl);
+}
+
+// ---- PairLaunch (pwalign_internal.h)
+// pd[q].{pat,txt,n,m,tb,sband,res,ops,ops_cap} filled by the caller; this adds the pipeline fields
+int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g, int gap_extend) {
+    geom = g;
+    const uint64_t rows_per_stripe = 64ull * g.rl;
+    std::vector<StripeTask> tl;
+    uint64_t rows_i32 = 0, n_stripes_total = 0;
+    for (size_t q = 0; q < pd.size(); ++q) {
+        const uint64_t ns = ((uint64_t)pd[q].n + rows_per_stripe - 1) / rows_per_stripe;
+        const uint64_t nsup = (ns + g.w - 1) / g.w;
+        if (tl.size() + nsup >= 0xffffffffull || n_stripes_total + ns >= 0xffffffffull)
+            return fail(ctx, PWA_E_CAPACITY, "too many stripe tasks in one launch");
+        pd[q].first_task = (uint32_t)tl.size();
+        pd[q].first_stripe = (uint32_t)n_stripes_total;
+        pd[q].n_stripes = (uint32_t)ns;
+        pd[q].row_stride = (uint32_t)align_up((uint64_t)pd[q].m + 64, 64);
+        for (uint64_t st = 0; st < nsup; ++st) tl.push_back({(uint32_t)q, (uint32_t)st});
+        rows_i32 += (nsup - 1) * pd[q].row_stride * (dist || aff ? 2 : 1);
+        n_stripes_total += ns;
+    }
+    row_bytes = rows_i32 * sizeof(int32_t);
+    HIPC(ctx, take(ctx, rows, pwa_ctx::POOL_ROWS, row_bytes, &p_rows));
+    uint64_t ro = 0;
+    for (auto& d : pd) {
+        d.rows = static_cast<int32_t*>(p_rows) + ro;
+        const uint64_t nsup = ((uint64_t)d.n_stripes + g.w - 1) / g.w;
+        ro += (nsup - 1) * d.row_stride * (dist || aff ? 2 : 1);
+    }
+    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
+    std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), pd.size() * sizeof(PairDesc));
+    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, pd.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
+    HIPC(ctx, take(ctx, tasks, pwa_ctx::POOL_TASKS, tl.size() * sizeof(StripeTask), &p_tasks));
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_TL].reserve(tl.size() * sizeof(StripeTask)));
+    std::memcpy(ctx->pin[pwa_ctx::PIN_TL].p, tl.data(), tl.size() * sizeof(StripeTask));
+    HIPC(ctx, hipMemcpy(p_tasks, ctx->pin[pwa_ctx::PIN_TL].p, tl.size() * sizeof(StripeTask), hipMemcpyHostToDevice));
+    progress_bytes = align_up(tl.size() * sizeof(uint32_t), 16);
+    HIPC(ctx, take(ctx, progress, pwa_ctx::POOL_PROGRESS, progress_bytes, &p_progress));
+    HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, std::max<uint64_t>(n_stripes_total, 1) * sizeof(StripeBest), &p_best));
+    HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
+    G.pairs = static_cast<PairDesc*>(p_desc);
+    G.tasks = static_cast<StripeTask*>(p_tasks);
+    G.n_pairs = (uint32_t)pd.size();
+    G.n_tasks = (uint32_t)tl.size();
+    G.queue = static_cast<uint32_t*>(p_queue);
+    G.progress = static_cast<uint32_t*>(p_progress);
+    G.best = static_cast<StripeBest*>(p_best);
+    G.match = match;
+    G.mismatch = mismatch;
+    G.gap = gap;
+    G.gap_extend = gap_extend;
+    G.dash = 0x100;   // no symbol: set by the callers that walk for overlaps
+    G.stamps = nullptr;
+    G.trace_stripe = -1;
+    G.trace_base = 0;
+    n_stripes = n_stripes_total;
+    // Tasks come off the queue in global order, so correctness does not depend on how many workgroups
+    // are resident.  One workgroup = W compute waves + 1 helper wave.
+    // [gpu] single-stripe batches (4096 pairs 150 x 10k, NW + band): 8 workgroups per CU 4.11 ms, 12 or 16: 3.76 ms (three
+    // compute waves per SIMD fill the issue slots two leave open); the HBM-bound SW + score-band batch does not care
+    int per_cu = g.w == 1 ? 12 : 3;
+    if (ctx->knobs.wg_per_cu > 0) per_cu = ctx->knobs.wg_per_cu;   // experiments only
+    grid = (uint32_t)std::min<uint64_t>(tl.size(), (uint64_t)ctx->num_cu * per_cu);
+    return PWA_OK;
+}
+// mini-stripe engine: pd = the real pairs first (n_real of them), then empty patterns up to a multiple of four; task t = the
+// pairs 4t .. 4t+3 (the caller orders them so that a task's texts are about equally long)
+int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, int match, int mismatch, int gap, int rl, int ln) {
+    mini = true;
+    mini_ln = ln;
+    geom = PairGeom{rl, 1};
+    const size_t ppw = (size_t)(64 / ln);   // pairs per wave: 4, or 1 (one pair per wave: 512- / 1024-row single stripes)
+    if (pd.empty() || pd.size() % ppw || pd.size() >= 0xffffffffull || n_real > pd.size() || n_real + ppw - 1 < pd.size())
+        return fail(ctx, PWA_E_INVALID, "internal: mini-stripe task list");
+    for (size_t q = 0; q < pd.size(); ++q) {
+        pd[q].first_task = (uint32_t)(q / ppw);
+        pd[q].first_stripe = (uint32_t)q;
+        pd[q].n_stripes = 1;
+        pd[q].row_stride = 0;
+        pd[q].rows = nullptr;
+    }
+    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
+    std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), pd.size() * sizeof(PairDesc));
+    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, pd.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
+    HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, pd.size() * sizeof(StripeBest), &p_best));
+    HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
+    progress_bytes = 0;
+    row_bytes = 0;
+    G = PairParams{};
+    G.pairs = static_cast<PairDesc*>(p_desc);
+    G.n_pairs = n_real;
+    G.n_tasks = (uint32_t)(pd.size() / ppw);
+    G.queue = static_cast<uint32_t*>(p_queue);
+    G.best = static_cast<StripeBest*>(p_best);
+    G.match = match;
+    G.mismatch = mismatch;
+    G.gap = gap;
+    G.dash = 0x100;
+    G.trace_stripe = -1;
+    n_stripes = pd.size();
+    grid = G.n_tasks;   // (clamped to what the chip holds at launch time, where the kernel is known)
+    return PWA_OK;
+}
+// enqueue: zero the queue / progress words, fill, then the walk (or only the end-cell pick)
+int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband) {
+    HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
+    if (mini) {
+        const pair_kernel_t fill = gotoh >= 0 ? gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln)
+                                              : mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
+        const pair_kernel_t walk_fn = gotoh >= 0 ? gotoh_walk_kernel_for(geom.rl, gotoh, mini_ln)
+                                                 : mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
+        if (!fill || !walk_fn || (gotoh < 0 && (!perm || !keyed))) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
+        // Workgroups of four waves (one task each per round); `per_cu` of them per CU, enforced through the dynamic LDS request, so
+        // that no CU gets more than its share whatever ran before (mini_fill.hip.h): with ceil(tasks / 4) workgroups for 256 CUs,
+        // per_cu = ceil(workgroups / CUs), at most 2; longer task lists run in rounds ([gpu] pairs 150 x 10k: 8192 of them at two
+        // waves per SIMD 2.68 ms, 16384 at four 6.61 ms -- 16 k concurrent write streams get 4.0 instead of 4.9 TB/s out of HBM).
+        const uint32_t n_wg = (G.n_tasks + kMiniWaves - 1) / kMiniWaves;
+        // (band-less fills have no write streams to thin out: four per CU -- [gpu] scores with end cells 2 - 3 % faster than at two)
+        const uint32_t cap_per_cu = ctx->knobs.mini_per_cu > 0 ? (uint32_t)std::min(ctx->knobs.mini_per_cu, 5) : (tb ? 2u : 4u);
+        const uint32_t per_cu = std::min<uint32_t>(cap_per_cu, (n_wg + (uint32_t)ctx->num_cu - 1) / (uint32_t)ctx->num_cu);
+        static const uint32_t kPadKiB[6] = {0, 96, 64, 48, 36, 30};   // more than 160 KiB / (per_cu + 1), at most 160 KiB / per_cu
+        const size_t pad_lds = (size_t)kPadKiB[per_cu] * 1024;
+        HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+        const uint32_t g = std::min<uint32_t>(n_wg, (uint32_t)ctx->num_cu * per_cu);
+        if (ctx->knobs.debug) std::fprintf(stderr, "[pwa] mini fill: %u tasks, %u workgroups of %d waves, %u per CU (%zu KiB of LDS each)\n", G.n_tasks, g, kMiniWaves, per_cu, pad_lds >> 10);
+        hipLaunchKernelGGL(fill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G);
+        HIPC(ctx, hipGetLastError());
+        if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+        hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+        HIPC(ctx, hipGetLastError());
+        return PWA_OK;
+    }
+    HIPC(ctx, hipMemsetAsync(p_progress, 0, progress_bytes, st));
+    if (!ctx->knobs.stamps.empty()) {
+        HIPC(ctx, stamps.alloc(n_stripes * 32 + 4 * 8192 * 8));
+        HIPC(ctx, hipMemsetAsync(stamps.p, 0, n_stripes * 32 + 4 * 8192 * 8, st));
+        G.stamps = stamps.as<unsigned long long>();
+        G.trace_base = (uint32_t)(n_stripes * 4);
+        G.trace_stripe = ctx->knobs.trace_stripe;
+    }
+    if (dist || aff) {   // hw4 distances / hw3 affine scores: the fill writes D[n][m] / M[n][m] into the score vector itself
+        const pair_kernel_t fill = dist ? pair_dist_kernel_for(geom.rl, geom.w)
+                                   : aff_tb ? pair_affine_tb_kernel_for(geom.rl, geom.w) : pair_affine_kernel_for(geom.rl, geom.w);
+        const pair_kernel_t walk_fn = aff_tb ? pair_affine_walk_kernel_for(geom.rl) : nullptr;
+        if (!fill || (aff_tb && !walk_fn)) return fail(ctx, PWA_E_INVALID, "internal: no distance / affine kernel for this geometry");
+        size_t pad_lds = 0;   // (one multi-stripe workgroup per CU when they are few: as below)
+        if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;
+        if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+        hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
+        HIPC(ctx, hipGetLastError());
+        if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+        if (aff_tb) {
+            hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+            HIPC(ctx, hipGetLastError());
+        }
+        return PWA_OK;
+    }
+    // (scores / end cells only over a coded arena, keys in range: the keyed chunk without a band -- batch_create_impl sets perm for that)
+    const bool noband = !tb && perm && keyed && !sband;
+    const pair_kernel_t fill = noband ? pair_fill_kernel_for(geom.rl, geom.w, local, true, false, true, true, gap0 && !local, false, semi)
+                                      : pair_fill_kernel_for(geom.rl, geom.w, local, tb, sband, perm && tb && keyed, keyed,
+                                                             gap0 && tb && keyed && perm && !sband && !local, true, semi);
+    const pair_kernel_t walk_fn = pair_traceback_kernel_for(geom.rl, local, walk, semi);
+    if (!fill || !walk_fn) return fail(ctx, PWA_E_INVALID, "internal: no fill kernel for this geometry");
+    // A launch with no more multi-stripe workgroups than CUs asks for enough (unused) dynamic LDS that only ONE workgroup
+    // fits a CU: a stripe is one wave alone on its SIMD, and every stripe of a pair moves at the pace of the slowest --
+    // two workgroups sharing a CU's four SIMDs would slow the whole pipeline
+    size_t pad_lds = 0;
+    if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;   // static (<= 16 KiB) + 96 KiB > half of the CU's 160 KiB
+    if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+    hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
+    HIPC(ctx, hipGetLastError());
+    if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+    hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+    HIPC(ctx, hipGetLastError());
+    return PWA_OK;
+}
+// after the stream has been synchronised: did a bounded spin give up?
+int PairLaunch::check(pwa_ctx* ctx) {
+    if (const char* path = ctx->knobs.stamps.c_str(); !ctx->knobs.stamps.empty() && stamps.p) {
+        std::vector<unsigned long long> h(n_stripes * 4);
+        HIPC(ctx, hipMemcpy(h.data(), stamps.p, n_stripes * 32, hipMemcpyDeviceToHost));
+        if (FILE* f = std::fopen(path, "w")) {
+            for (uint64_t k = 0; k < n_stripes; ++k)
+                std::fprintf(f, "%llu %llu %llu %llu %llu\n", (unsigned long long)k, h[4 * k] - h[0], h[4 * k + 3] - h[0], h[4 * k + 1] - h[0], h[4 * k + 2] - h[0]);
+            std::fclose(f);
+        }
+        if (G.trace_stripe >= 0) {
+            std::vector<unsigned long long> tr(4 * 8192);
+            HIPC(ctx, hipMemcpy(tr.data(), stamps.as<unsigned long long>() + G.trace_base, tr.size() * 8, hipMemcpyDeviceToHost));
+            if (FILE* f = std::fopen((std::string(path) + ".trace").c_str(), "w")) {
+                for (int c = 0; c < 8192; ++c)
+                    std::fprintf(f, "%d %llu %llu %llu %llu\n", c, tr[c] - h[0], tr[8192 + c] - h[0], tr[2 * 8192 + c] - h[0], tr[3 * 8192 + c] - h[0]);
+                std::fclose(f);
+            }
+        }
+    }
+    uint32_t q[2] = {0, 0};
+    HIPC(ctx, hipMemcpy(q, p_queue, sizeof q, hipMemcpyDeviceToHost));
+    if (q[1] != 0) return fail(ctx, PWA_E_HIP, "stripe pipeline timed out waiting for the stripe above");
+    return PWA_OK;
+}
+
+// the pair-list checks of the alignment batches
+int check_pair_list(pwa_ctx* ctx, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint32_t n_seq) {
+    if (n_pairs >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "more than 2^32-2 pairs in one batch");
+    for (uint64_t k = 0; k < n_pairs; ++k)
+        if (pair_a[k] >= n_seq || pair_b[k] >= n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
+    return PWA_OK;
+}
+
+// Arena layout of the used sequences: s at aoff[s], 16-byte aligned, at least one byte of padding behind each and tail_pad bytes behind
+// the last; returns the arena's size
+uint64_t layout_arena(const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& is_used, uint64_t tail_pad, std::vector<uint64_t>& aoff) {
+    aoff.assign(n_seq, 0);
+    uint64_t arena_bytes = 0;
+    for (uint32_t s = 0; s < n_seq; ++s)
+        if (is_used[s]) {
+            aoff[s] = arena_bytes;
+            arena_bytes += align_up(seq_off[s + 1] - seq_off[s] + 1, 16);
+        }
+    return arena_bytes + tail_pad;
+}
+
+}  // namespace pwa
+
+extern "C" {
+
+const char* pwa_version(void) { return "pwalign 0.1 gfx950"; }
+
+// Host-only checks of the scheduler's sorting helpers and of the alignment batches' range planner (include/pwalign.h): tests call this on
+// machines without a GPU.
+int pwa_selftest_host(uint32_t seed) try {
+    uint64_t x = 0x9e3779b97f4a7c15ull ^ seed;
+    auto rnd = [&]() {
+        x ^= x << 13;
+        x ^= x >> 7;
+        x ^= x << 17;
+        return x;
+    };
+    int check = 0;
+    for (const size_t n : {size_t(0), size_t(1), size_t(2), size_t(1000), size_t(70000), size_t(300000), size_t(1) << 20}) {
+        for (const size_t buckets : {size_t(1), size_t(3), size_t(4352), size_t(65536), size_t(200000)}) {
+            ++check;
+            std::vector<uint32_t> key(n), idx(n), tmp, want(n);
+            for (size_t i = 0; i < n; ++i) {
+                key[i] = (uint32_t)(rnd() % buckets);
+                idx[i] = (uint32_t)i;
+            }
+            want = idx;
+            std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+            counting_sort(idx, tmp, buckets, [&](uint32_t v) { return (size_t)key[v]; });   // (threaded from 2^18 elements, <= 2^16 buckets)
+            if (idx != want) return check;
+        }
+        for (const uint64_t span : {uint64_t(1), uint64_t(7), uint64_t(3000), uint64_t(1) << 33}) {   // the last one takes the radix path
+            ++check;
+            std::vector<uint64_t> len(n);
+            std::vector<uint32_t> idx(n), want(n);
+            for (size_t i = 0; i < n; ++i) {
+                len[i] = 5 + rnd() % span;
+                idx[i] = (uint32_t)i;
+            }
+            want = idx;
+            std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return len[a] > len[b]; });
+            sort_by_length_desc(idx, [&](uint32_t v) { return len[v]; });
+            if (idx != want) return check;
+        }
+        {
+            ++check;
+            std::vector<uint64_t> key(n);
+            std::vector<uint32_t> idx(n), want(n);
+            for (size_t i = 0; i < n; ++i) {
+                key[i] = rnd() >> (rnd() % 50);
+                idx[i] = (uint32_t)i;
+            }
+            want = idx;
+            const std::vector<uint64_t> key0 = key;
+            std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return key0[a] < key0[b]; });
+            radix_sort_by_key(key, idx);
+            if (idx != want) return check;
+        }
+    }
+    return selftest_align_plan(x, check);
+} catch (...) {
+    return -1;
+}
+
+const char* pwa_strerror(int code) {
+    switch (code) {
+        case PWA_OK: return "ok";
+        case PWA_E_INVALID: return "invalid argument";
+        case PWA_E_NODEVICE: return "no usable gfx950 device";
+        case PWA_E_HIP: return "HIP runtime error";
+        case PWA_E_NOMEM: return "out of memory";
+        case PWA_E_CAPACITY: return "capacity exceeded";
+        case PWA_E_IO: return "cannot open or read file";
+        default: return "unknown error";
+    }
+}
+
+int pwa_ctx_create(int device, pwa_ctx** out) {
+    if (!out) return PWA_E_INVALID;
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return PWA_E_NODEVICE;
+    if (device < 0 || device >= count) return PWA_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return PWA_E_NODEVICE;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return PWA_E_NODEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PWA_E_NODEVICE;   // kernels exist for gfx950 only
+    pwa_ctx* c = new (std::nothrow) pwa_ctx();
+    if (!c) return PWA_E_NOMEM;
+    c->knobs.read();   // the only place the library's switches are read from the environment
+    c->device = device;
+    c->num_cu = prop.multiProcessorCount;
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete c;
+        return PWA_E_HIP;
+    }
+    for (auto& e : c->ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            pwa_ctx_destroy(c);
+            return PWA_E_HIP;
+        }
+    if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->copy_ev[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->copy_ev[1], hipEventDisableTiming) != hipSuccess || hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->aux_ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->aux_ev[1], hipEventDisableTiming) != hipSuccess) {
+        pwa_ctx_destroy(c);
+        return PWA_E_HIP;
+    }
+    *out = c;
+    return PWA_OK;
+}
+
+void pwa_ctx_destroy(pwa_ctx* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    for (auto& e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (auto& e : c->copy_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    for (auto& e : c->aux_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
+    if (c->band_cache) (void)hipFree(c->band_cache);
+    if (c->sband_cache) (void)hipFree(c->sband_cache);
+    if (c->hand_cache) (void)hipFree(c->hand_cache);
+    for (void* q : c->pool)
+        if (q) (void)hipFree(q);
+    for (auto& f : c->free_list) (void)hipFree(f.first);
+    delete c;
+}
+
+const char* pwa_last_error(const pwa_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+int pwa_ctx_set_score_band(pwa_ctx* c, int on) {
+    if (!c) return PWA_E_INVALID;
+    c->score_band = on != 0;
+    return PWA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,307 @@
+// pwalign_internal.h -- what the host units of libpwalign.so share (pwalign_ctx.hip: context and memory; pwalign.hip: score
+// batches; pwalign_affine_tb.hip: hw3's affine alignments; pwalign_align.hip: alignment batches), declared once.  Not installed; the
+// functions of namespace pwa are defined in pwalign_ctx.hip unless noted and have hidden visibility: the library exports the C ABI only.
+#pragma once
+#include "../../include/pwalign.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "kernel_table.h"
+
+// Host-side source / destination of the library's own host <-> device copies: page-locked, grow-only, kept in the context.
+// hipMemcpy from a short-lived pageable vector works, but the runtime registers its pages with the driver for the DMA, and
+// when the vector is freed the unmap notifier evicts the process's GPU queues: the NEXT kernel submission then takes 14-24 ms
+// [gpu, r02: tools/cold_start.py, PWA_PROBE] -- which is what made the first run of every fresh batch 25 ms late.
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t reserve(size_t n) {   // contents are NOT kept
+        if (n <= cap) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        n = (n + (n >> 2) + 4095) & ~(size_t)4095;   // 25 % headroom: few regrowths
+        const hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
+        if (e == hipSuccess) cap = n;
+        else p = nullptr;
+        return e;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// Test / diagnostic switches (include/pwalign.h, "Environment switches"): environment variables read ONCE, by
+// pwa_ctx_create, into the context.  No entry point consults the environment afterwards; a test that wants another
+// setting creates a fresh context.
+struct Knobs {
+    bool debug = false, probe = false;          // PWA_DEBUG, PWA_PROBE: host-side phase times on stderr, nop-kernel probes
+    int force_rl = 0, force_w = 0;              // PWA_FORCE_RL (2 | 3 | 4), PWA_FORCE_W (1 | 4): geometry of the stripe engine
+    int wg_per_cu = 0;                          // PWA_WG_PER_CU: workgroups per CU of a stripe-engine launch
+    bool no_lds_pad = false;                    // PWA_NO_LDS_PAD
+    std::string stamps;                         // PWA_STAMPS=<file>: per-stripe time stamps of the fill
+    int trace_stripe = -1;                      // PWA_TRACE_STRIPE
+    bool no_packed_dist = false;                // PWA_NO_PACKED_DIST: hw4 pass in its two-value form
+    int force_lanes = -1;                       // PWA_FORCE_LANES=0: never the per-lane-text kernels
+    int force_r = 0, force_mode = -1;           // PWA_FORCE_R, PWA_FORCE_MODE: strip height / kernel form of the strip engine
+    uint64_t arena_limit = 0;                   // PWA_ARENA_LIMIT: bytes of sequence arena per run of the one-shot calls (tests)
+    uint64_t lane_rows_limit = 0;               // PWA_LANE_ROWS_LIMIT: bytes of per-lane text rows per batch object (tests)
+    int mini_per_cu = 0;                        // PWA_MINI_PER_CU: most four-wave workgroups of a mini-stripe fill per CU (experiments; default 2)
+    uint64_t range_bytes = 0;                   // PWA_RANGE_BYTES: band + op bytes per range of pwa_align_batch / pwa_overlaps (tests: several ranges on small lists)
+    bool no_pair_table = false;                 // PWA_NO_PAIR_TABLE: traceback fills on raw bytes (compare + select)
+    bool no_keyed_tb = false;                   // PWA_NO_KEYED_TB: traceback fills in the plain int32 form
+    bool no_gap_shift = false;                  // PWA_NO_GAP_SHIFT: global traceback fills in H, not G = H - gap (i + j)
+    bool no_tiled_ops = false;                  // PWA_NO_TILED_OPS: op lists through the staging copy
+    bool no_pipeline = false;                   // PWA_NO_PIPELINE: the runs of a one-shot score call are processed strictly one after the other
+    int pipe_runs = 0;                          // PWA_PIPE_RUNS=N: cut a list that fits one arena into N pipelined runs (experiment; measured slower)
+    int scores_route = -1;                      // PWA_SCORES_ROUTE: 0 = every pair on the strip engine, 1 = every pair on the stripe
+                                                // engine, unset = by estimated cost (batch_create_impl)
+    int affine_tb_route = -1;                   // PWA_AFFINE_TB_ROUTE: pwa_align_affine_batch: 0 = every pair on the strips, 1 = every eligible
+                                                // pair on the stripe engine, unset = by estimated cost and band size
+    int cell16 = -1;                            // PWA_CELL16: 0 = never the packed f16 cells (two pairs per lane), 1 = always where the batch
+                                                // admits them, unset = by estimated cost (batch_create_impl)
+    int prof16 = -1;                            // PWA_PROF16: 0 = never the profile form of the packed cells (one pattern against 128
+                                                // texts), 1 = always where the batch admits it, unset = by estimated cost
+    uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
+    int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
+                                                // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
+    void read();   // (pwalign_ctx.hip)
+};
+
+// Device ms of the fills / walks of a batch of full alignments (event-timed, summed over its launches) and the band bytes they wrote
+struct AlignStats {
+    float fill_ms = 0.f, tb_ms = 0.f;
+    uint64_t band_bytes = 0;
+};
+
+// pwa_align_affine_batch: pairs it ran on the stripe engine, device ms of their fills / walks, band bytes written
+struct AffineAlignStats {
+    uint64_t stripe_pairs = 0, band_bytes = 0;
+    float fill_ms = 0.f, walk_ms = 0.f;
+};
+
+// ------------------------------------------------------------------------------------ context
+struct pwa_ctx {
+    Knobs knobs;
+    int device = 0;
+    int num_cu = 256;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::string err;
+    AlignStats align_stats, gotoh_stats;   // the last pwa_align_batch / _cigar / pwa_overlaps, the last pwa_align_gotoh_batch(_cigar)
+    AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
+    bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
+    // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
+    // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the
+    // device's memory, and a caller that aligns batch after batch should pay it once.
+    void* band_cache = nullptr;
+    size_t band_cache_bytes = 0;
+    void* sband_cache = nullptr;
+    size_t sband_cache_bytes = 0;
+    // the strip hand-off workspace of the last destroyed batch (5.2 GB for C3): the next batch takes it over
+    void* hand_cache = nullptr;
+    size_t hand_cache_bytes = 0;
+    // pwa_align* work buffers (sequence arena, op lists, results, pair descriptors, task list, hand-off rows, progress words,
+    // per-stripe bests, queue): grow-only, reused by the next call -- a call that aligns a batch costs no hipMalloc / hipFree
+    // (each of which also synchronises the device) once the context has seen a batch of that size; pwa_align_batch_cigar's
+    // strings and their pair list / lengths / scan partials
+    enum { POOL_ARENA, POOL_OPS, POOL_RES, POOL_DESC, POOL_TASKS, POOL_ROWS, POOL_PROGRESS, POOL_BEST, POOL_QUEUE, POOL_STR, POOL_STR_AUX, POOL_N };
+    void* pool[POOL_N] = {};
+    size_t pool_bytes[POOL_N] = {};
+    // page-locked staging of everything the library itself uploads or reads back (see PinnedBuf)
+    hipStream_t aux_stream = nullptr;                  // pwa_batch_run: the mini-stripe launches of a split batch run next to its stripe launch
+    hipEvent_t aux_ev[2] = {nullptr, nullptr};         // fork / join of that
+    hipStream_t copy_stream = nullptr;                 // uploads that overlap host work (build_arena)
+    hipEvent_t copy_ev[2] = {nullptr, nullptr};
+    // Device buffers of destroyed batch objects, kept for the next one (DevBuf below): a steady stream of batches -- the runs of a
+    // one-shot call over a large list, a caller that builds batch after batch -- costs no hipMalloc and, more to the point, no
+    // hipFree: hipFree waits for ALL work on the device, i.e. for the kernels of the batch that is still running, and with it the
+    // overlap of preparing run k + 1 with computing run k would be gone (scores_in_arena_chunks).
+    std::vector<std::pair<void*, size_t>> free_list;
+    size_t free_list_bytes = 0;
+    enum { PIN_ARENA, PIN_ARENA2, PIN_TASKS, PIN_SLOT0, PIN_SLOT1, PIN_SLOT2, PIN_SLOT3, PIN_SLOT4, PIN_DESC, PIN_TL, PIN_RES, PIN_BOUNCE, PIN_STR, PIN_N };
+    PinnedBuf pin[PIN_N];
+};
+constexpr size_t kBandCacheMax = 64ull << 30;   // (288 GB of HBM per GPU: a 4096-pair batch with both bands is 33 GB)
+
+__global__ void pwa_nop_kernel(int* p);   // (pwalign_ctx.hip; PWA_PROBE / PWA_DEBUG launch it to time a submission)
+
+#pragma GCC visibility push(hidden)
+namespace pwa {
+
+struct DevBuf {   // RAII device allocation; with `pool` set, released buffers go to the context's free list and come back from it
+    void* p = nullptr;
+    size_t bytes = 0;
+    pwa_ctx* pool = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release();
+    hipError_t alloc(size_t n);
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// ---- defined in pwalign_ctx.hip (the comments are at the definitions)
+void radix_sort_by_key(std::vector<uint64_t>& key, std::vector<uint32_t>& idx);
+void scan_bytes(const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& in, bool out[256],
+                uint64_t bytes_per_thread);
+int64_t max_abs(std::initializer_list<int64_t> vals);
+bool tb_range_ok(uint64_t n_plus_m, int match, int mismatch, int gap, int bits = 28);
+bool diag_keys_fit(int match, int mismatch, int gap);
+bool gap0_ok(uint64_t n_plus_m, int match, int mismatch, int gap);
+bool code_alphabet(const bool seen[256], uint8_t code_of[256], int match, int mismatch, int gap, const Knobs& knobs);
+int mini_rl_for(uint64_t n);
+int wide_rl_for(uint64_t n);
+hipError_t cached_workspace(void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out);
+hipError_t upload_via_bounce(pwa_ctx* c, void* dst, const void* src, size_t bytes);
+hipError_t build_arena(pwa_ctx* c, void* d_arena, uint64_t arena_bytes, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                       const std::vector<uint8_t>& is_used, const std::vector<uint64_t>& aoff, const uint8_t* table, bool nul_free = false);
+int fail(pwa_ctx* c, int code, const std::string& msg);
+int check_pair_list(pwa_ctx* ctx, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, uint32_t n_seq);
+uint64_t layout_arena(const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& is_used, uint64_t tail_pad, std::vector<uint64_t>& aoff);
+// ---- defined in pwalign_align.hip, behind the planner it checks; pwa_selftest_host ends with it
+int selftest_align_plan(uint64_t x, int check);
+
+// Stable counting sort of `idx` by key(idx[i]) in [0, n_buckets): two linear passes.
+template <class KeyFn>
+void counting_sort(std::vector<uint32_t>& idx, std::vector<uint32_t>& tmp, size_t n_buckets, KeyFn key) {
+    const size_t n = idx.size();
+    if (n >= (1u << 18) && n_buckets <= (1u << 16)) {
+        // a million pairs: both passes are scattered memory accesses -- on a few threads, each with its own histogram over its own
+        // contiguous part of idx (thread t's elements of a bucket go behind those of the threads before it: still stable)
+        const int T = (int)std::min<size_t>({8, std::max(1u, std::thread::hardware_concurrency()), n >> 16});
+        std::vector<std::vector<uint32_t>> cnt((size_t)T, std::vector<uint32_t>(n_buckets, 0));
+        auto part = [&](int t) { return std::make_pair(n * (size_t)t / (size_t)T, n * (size_t)(t + 1) / (size_t)T); };
+        auto run = [&](auto&& fn) {
+            std::vector<std::thread> th;
+            for (int t = 1; t < T; ++t) th.emplace_back(fn, t);
+            fn(0);
+            for (auto& x : th) x.join();
+        };
+        run([&](int t) {
+            const auto [a, z] = part(t);
+            uint32_t* const c = cnt[(size_t)t].data();
+            for (size_t o = a; o < z; ++o) ++c[key(idx[o])];
+        });
+        uint32_t at = 0;
+        for (size_t bkt = 0; bkt < n_buckets; ++bkt)
+            for (int t = 0; t < T; ++t) {
+                const uint32_t c = cnt[(size_t)t][bkt];
+                cnt[(size_t)t][bkt] = at;
+                at += c;
+            }
+        tmp.resize(n);
+        run([&](int t) {
+            const auto [a, z] = part(t);
+            uint32_t* const c = cnt[(size_t)t].data();
+            for (size_t o = a; o < z; ++o) tmp[c[key(idx[o])]++] = idx[o];
+        });
+        idx.swap(tmp);
+        return;
+    }
+    std::vector<uint32_t> cnt(n_buckets + 1, 0);
+    for (const uint32_t v : idx) ++cnt[key(v) + 1];
+    for (size_t b = 0; b < n_buckets; ++b) cnt[b + 1] += cnt[b];
+    tmp.resize(idx.size());
+    for (const uint32_t v : idx) tmp[cnt[key(v)]++] = v;
+    idx.swap(tmp);
+}
+
+// idx by DESCENDING length, stable (equal lengths keep their order): linear passes instead of std::stable_sort's n log n compares
+// through two indirections ([cpu] 16 384 pairs of random lengths: 0.95 ms for the merge sort)
+template <class LenFn>
+void sort_by_length_desc(std::vector<uint32_t>& idx, LenFn len_of) {
+    if (idx.size() < 2) return;
+    uint64_t lmin = ~0ull, lmax = 0;
+    for (const uint32_t v : idx) {
+        const uint64_t l = len_of(v);
+        lmin = std::min(lmin, l);
+        lmax = std::max(lmax, l);
+    }
+    if (lmin == lmax) return;
+    if (lmax - lmin <= 4 * (uint64_t)idx.size() + 65536) {
+        std::vector<uint32_t> tmp;
+        counting_sort(idx, tmp, (size_t)(lmax - lmin + 1), [&](uint32_t v) { return (size_t)(lmax - len_of(v)); });
+    } else {
+        std::vector<uint64_t> key(idx.size());
+        for (size_t o = 0; o < idx.size(); ++o) key[o] = lmax - len_of(idx[o]);
+        radix_sort_by_key(key, idx);
+    }
+}
+
+#define HIPC(ctx, call)                                                                              \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            return fail((ctx), e_ == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP,                  \
+                        std::string(#call) + ": " + hipGetErrorString(e_));                          \
+        }                                                                                            \
+    } while (0)
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+inline int32_t wrap_mul(int64_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
+
+// Geometry of the wavefront (pair) engine: RL rows per lane (stripe = 64*RL rows) and W compute waves
+// per workgroup (a workgroup task = W consecutive stripes + one helper wave).  Pairs of a single
+// stripe use W = 1; short multi-stripe pairs get RL = 2 (twice the stripes = twice the waves in flight).
+struct PairGeom {
+    int rl, w;
+};
+PairGeom choose_geom(const Knobs& kn, uint64_t max_n, bool keyed = true, bool keyed_tb = false);
+size_t tb_band_bytes(uint64_t n, uint64_t m, int rl);
+
+// Device-side state of one launch of the wavefront (pair) engine: pair descriptors, the global
+// stripe-task list, hand-off rows, progress counters, per-stripe bests.
+struct PairLaunch {
+    DevBuf desc, tasks, rows, progress, best, queue;
+    bool from_pool = false;   // take the six buffers from the context's pool (one launch at a time per context: pwa_align*)
+    void *p_desc = nullptr, *p_tasks = nullptr, *p_rows = nullptr, *p_progress = nullptr, *p_best = nullptr, *p_queue = nullptr;
+    size_t progress_bytes = 0;
+    hipError_t take(pwa_ctx* ctx, DevBuf& own, int slot, size_t bytes, void** out) {
+        if (bytes == 0) bytes = 16;
+        if (from_pool) return cached_workspace(ctx->pool[slot], ctx->pool_bytes[slot], bytes, own, out);
+        const hipError_t e = own.alloc(bytes);
+        *out = own.p;
+        return e;
+    }
+    PairParams G{};
+    PairGeom geom{4, 4};
+    bool mini = false;   // the mini-stripe engine (mini_fill.hip.h): mini_ln lanes per pair, geom.rl rows per lane, 64 / mini_ln pairs per wave
+    int mini_ln = 16;
+    bool perm = false;   // sequences are coded 0..6 (pad 7) and the key constants fit a byte: table-scoring fill kernels
+    bool keyed = true;   // traceback fills keep H * 4 + priority (needs |H| < 2^28); false: plain int32 compare-and-select form
+    bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
+    bool semi = false;   // semi-global (PWA_MODE_SG) fills and walks: row 0 free, the end record of row n (never with gap0)
+    bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
+    bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
+    bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
+    int gotoh = -1;      // >= 0 (a PWA_MODE_*): the affine-gap mini-stripe kernels (gotoh_fill.hip.h); build_mini takes gap_open as gap
+    uint32_t grid = 0;
+    uint64_t row_bytes = 0;
+    uint64_t n_stripes = 0;
+    DevBuf stamps;   // PWA_STAMPS=<file>: per-stripe time stamps of the fill (debugging the stripe pipeline)
+
+    // pd[q].{pat,txt,n,m,tb,sband,res,ops,ops_cap} filled by the caller; this adds the pipeline fields
+    int build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g, int gap_extend = 0);
+    int build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, int match, int mismatch, int gap, int rl, int ln = 16);
+    // enqueue: zero the queue / progress words, fill, then the walk (or only the end-cell pick)
+    int launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband = false);
+    // after the stream has been synchronised: did a bounded spin give up?
+    int check(pwa_ctx* ctx);
+};
+
+}  // namespace pwa
+#pragma GCC visibility pop

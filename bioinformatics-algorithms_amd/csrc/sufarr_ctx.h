@@ -1,5 +1,5 @@
-// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign.hip, and the
-// scan of that unit that pwalign.hip borrows.
+// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign_internal.h, and the
+// scan of that unit that pwalign_align.hip borrows.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -58,7 +58,7 @@ inline uint32_t blocks_for(size_t n, size_t per) { return (uint32_t)((n + per - 
 }  // namespace
 
 // x[0 .. len) := exclusive prefix sums, in place (reduce, scan of the chunk sums, apply); part: scan_part_words(len) words.
-// Also the scan of pwa_align_batch_cigar's string lengths (pwalign.hip), hence outside this unit's anonymous namespace.
+// Also the scan of pwa_align_batch_cigar's string lengths (pwalign_align.hip), hence outside this unit's anonymous namespace.
 size_t pwa::scan_part_words(size_t len) { return len / kTile + 1; }
 void pwa::scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part) {
     if (!len) return;

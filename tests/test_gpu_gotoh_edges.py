@@ -33,7 +33,7 @@ POS_MISMATCH = (2, 1, -3, -1)   # rows past n (never-equal pad symbol) then grow
 
 
 def gotoh_class(n):
-    """(lanes per pair, rows per lane) of the class a pattern of n symbols runs in (pwalign.hip: class_of for gotoh)"""
+    """(lanes per pair, rows per lane) of the class a pattern of n symbols runs in (pwalign_align.hip: class_of for gotoh)"""
     if n <= 256:
         return 16, next(rl for rl in (4, 6, 8, 10, 12, 16) if n <= 16 * rl)
     return 64, 8 if n <= 512 else 16

@@ -1166,7 +1166,7 @@ def test_local_alignments_with_many_equal_maxima(engine):
 
 def test_arenas_of_a_mebibyte_are_coded_on_the_device(ctx):
     """An arena of >= 1 MiB over a small alphabet goes up as raw bytes and is turned into codes by a kernel behind every piece's copy
-    (pwalign.hip, build_arena); a NUL byte inside a sequence keeps the host's table pass (the padding between sequences is zeros).
+    (pwalign_ctx.hip, build_arena); a NUL byte inside a sequence keeps the host's table pass (the padding between sequences is zeros).
     Alignments and scores of a 1.2 MB list, with and without a NUL, against the oracle on a sample."""
     rng = random.Random(1 << 20)
     for with_nul in (False, True):

@@ -37,7 +37,7 @@ __global__ void alu_clock(unsigned long long* out, int iters) {   // pure VALU; 
     }
 }
 
-static void launch_fill(const PairParams& G) {   // as pwalign.hip launches it: 4-wave workgroups, LDS request = one share of a CU
+static void launch_fill(const PairParams& G) {   // as pwalign_ctx.hip launches it: 4-wave workgroups, LDS request = one share of a CU
     const uint32_t n_wg = (G.n_tasks + 3) / 4, per_cu = std::min<uint32_t>(5, (n_wg + 255) / 256);
     static const uint32_t pad_kib[6] = {0, 96, 64, 48, 36, 30};
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mini_fill_kernel<10, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(pad_kib[per_cu] * 1024));
