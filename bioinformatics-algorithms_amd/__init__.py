@@ -31,6 +31,7 @@ EXPORTS = [
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
+    "pwa_gotoh_batch_create", "pwa_scores_gotoh",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
@@ -160,6 +161,8 @@ def lib():
     L.pwa_align_gotoh_batch.argtypes = gotoh_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_align_gotoh_batch_cigar.argtypes = gotoh_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
     L.pwa_align_gotoh_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
+    L.pwa_gotoh_batch_create.argtypes = gotoh_in + [C.c_int, C.POINTER(vp)]
+    L.pwa_scores_gotoh.argtypes = gotoh_in + [i32p, u32p, u32p]
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
     L.pwa_cigar_bound.argtypes = [C.c_uint64]
@@ -358,6 +361,32 @@ class Context:
     def scores_affine_oneshot(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
         """pwa_scores_affine: the one-call form."""
         return self._oneshot(self._L.pwa_scores_affine, "pwa_scores_affine", seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend)
+
+    # -- affine-gap (gotoh) scores: the semantics of align_gotoh_batch without the alignments (include/pwalign.h)
+    def scores_gotoh(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, want_end=False):
+        b = Batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, want_end, gap_extend=gap_extend, gotoh=True)
+        b.run()
+        out = b.fetch()
+        b.close()
+        return out
+
+    def scores_gotoh_oneshot(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, want_end=False):
+        """pwa_scores_gotoh: the one-call form (pair lists of any size: cut into arena-sized runs by the library)."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei = (C.c_uint32 * max(n, 1))() if want_end else None
+        ej = (C.c_uint32 * max(n, 1))() if want_end else None
+        rc = self._L.pwa_scores_gotoh(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ei, ej)
+        self._check(rc, "pwa_scores_gotoh")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n])
+        return list(sc[:n])
+
+    def batch_gotoh(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, want_end=False):
+        return Batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, want_end, gap_extend=gap_extend, gotoh=True)
 
     def batch_distances(self, seqs, pair_a, pair_b, match, mismatch, gap):
         return Batch(self, "nwdist", seqs, pair_a, pair_b, match, mismatch, gap)
@@ -635,7 +664,7 @@ class Context:
 class Batch:
     """Prepared scores-only batch: inputs resident in HBM, run() only enqueues kernels."""
 
-    def __init__(self, ctx, mode, seqs, pair_a, pair_b, match, mismatch, gap, want_end=False, gap_extend=0):
+    def __init__(self, ctx, mode, seqs, pair_a, pair_b, match, mismatch, gap, want_end=False, gap_extend=0, gotoh=False):
         self._ctx, self._L = ctx, ctx._L
         blob, off, seqs = pack_sequences(seqs)
         self.n_pairs = len(pair_a)
@@ -648,7 +677,10 @@ class Batch:
             pa = (C.c_uint32 * max(n, 1))(*pair_a)
             pb = (C.c_uint32 * max(n, 1))(*pair_b)
         h = C.c_void_p()
-        if mode == "nwdist":
+        if gotoh:   # affine-gap scores of `mode` (nw / sw / sg): gap = gap_open
+            rc = self._L.pwa_gotoh_batch_create(ctx._h, MODE[mode], match, mismatch, gap, gap_extend, blob, off, len(seqs), pa, pb, n,
+                                                1 if want_end else 0, C.byref(h))
+        elif mode == "nwdist":
             rc = self._L.pwa_nwdist_batch_create(ctx._h, match, mismatch, gap, blob, off, len(seqs), pa, pb, n, C.byref(h))
         elif mode == "affine":
             rc = self._L.pwa_affine_batch_create(ctx._h, match, mismatch, gap, gap_extend, blob, off, len(seqs), pa, pb, n,

@@ -43,7 +43,8 @@ struct GotohConst {
 };
 
 // 16 steps of 64 / LN pairs.  GUARD: some lane is outside its matrix at some step of the chunk -- its state is frozen there.
-template <int RL, int MODE, bool GUARD, int LN>
+// BAND = false: no code is stored (tba, tbb unused): the scores form, gotoh_scores_kernel.
+template <int RL, int MODE, bool GUARD, int LN, bool BAND = true>
 __device__ __forceinline__ void gotoh_chunk(const int t0, const int k, const int m, const int (&pc)[RL], int (&hl)[RL], int (&el)[RL], int& diag0,
                                             int& bot_h, int& bot_f, int& tch, const int tcv, const int top0, const int top_inc, const GotohConst& K,
                                             int (&bs)[RL], int (&bj)[RL], const int (&own)[RL], int& sg_v, int& sg_t, g_u8* const tba, g_u8* const tbb) {
@@ -100,11 +101,13 @@ __device__ __forceinline__ void gotoh_chunk(const int t0, const int k, const int
         bot_h = act ? uh : bot_h;
         bot_f = act ? uf : bot_f;
         tch = tn;
-        if constexpr (Geo::PA == 4) PWA_BAND_STORE((g_u32*)(tba + q * Geo::SR), codes[0]);
-        if constexpr (Geo::PA == 8) PWA_BAND_STORE((PWA_GLOBAL mu32x2*)(tba + q * Geo::SR), (mu32x2{codes[0], codes[1]}));
-        if constexpr (Geo::PA == 16) PWA_BAND_STORE((PWA_GLOBAL mu32x4*)(tba + q * Geo::SR), (mu32x4{codes[0], codes[1], codes[2], codes[3]}));
-        if constexpr (Geo::PB == 2) PWA_BAND_STORE((PWA_GLOBAL uint16_t*)(tbb + q * Geo::SR), (uint16_t)codes[Geo::PA / 4]);
-        if constexpr (Geo::PB == 4) PWA_BAND_STORE((g_u32*)(tbb + q * Geo::SR), codes[Geo::PA / 4]);
+        if constexpr (BAND) {
+            if constexpr (Geo::PA == 4) PWA_BAND_STORE((g_u32*)(tba + q * Geo::SR), codes[0]);
+            if constexpr (Geo::PA == 8) PWA_BAND_STORE((PWA_GLOBAL mu32x2*)(tba + q * Geo::SR), (mu32x2{codes[0], codes[1]}));
+            if constexpr (Geo::PA == 16) PWA_BAND_STORE((PWA_GLOBAL mu32x4*)(tba + q * Geo::SR), (mu32x4{codes[0], codes[1], codes[2], codes[3]}));
+            if constexpr (Geo::PB == 2) PWA_BAND_STORE((PWA_GLOBAL uint16_t*)(tbb + q * Geo::SR), (uint16_t)codes[Geo::PA / 4]);
+            if constexpr (Geo::PB == 4) PWA_BAND_STORE((g_u32*)(tbb + q * Geo::SR), codes[Geo::PA / 4]);
+        }
     });
     if (SW) {
 #pragma unroll
@@ -252,6 +255,152 @@ __global__ __launch_bounds__(64 * kMiniWaves) void gotoh_fill_kernel(const PairP
         }
     }
 }
+
+// The band-less form of the fill above for pwa_gotoh_batch_create (scores, and end cells, without alignments): the same cells and
+// first-maximum records, no code byte is built or stored and PairDesc::tb is not read; score and end cell go into PairResult as above,
+// and the score also into PairParams::scores_out at the pair's out_index.  It is a copy of gotoh_fill_kernel's body with the band taken
+// out rather than a shared body: gotoh_fill_kernel's instantiations are held byte-identical to the previous build,
+// and a shared body function changed their register allocation.
+template <int RL, int MODE, int LN>
+__global__ __launch_bounds__(64 * kMiniWaves) void gotoh_scores_kernel(const PairParams G) {
+    constexpr bool BAND = false;
+    static_assert(LN == 16 || (LN == 64 && (RL == 8 || RL == 16)), "gotoh classes: 16 lanes x kMiniRL, or 64 lanes x 8 | 16 rows");
+    typedef BandGeo<LN, RL> Geo;
+    typedef GotohPrio<MODE> PR;
+    constexpr int PPW = 64 / LN;
+    constexpr bool NW = MODE == 0, SG = MODE == 2;
+    const int lane = threadIdx.x & 63, k = lane & (LN - 1), grp = lane / LN;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int go = G.gap, ge = G.gap_extend, oe = p_addw(go, ge);
+    GotohConst K;
+    K.cE = p_addw(p_mulw(oe, 8), 2 * PR::E + 1);
+    K.cF = p_addw(p_mulw(oe, 8), 2 * PR::F + 1);
+    K.sM = p_addw(p_mulw(G.match, 8), 2 * PR::D - K.cE);
+    K.sX = p_addw(p_mulw(G.mismatch, 8), 2 * PR::D - K.cE);
+    K.ge8 = p_mulw(ge, 8);
+    auto h0 = [&](int i) { return NW || SG ? (i ? p_addw(go, p_mulw(i, ge)) : 0) : 0; };   // H[i][0] (and H[0][j] for NW)
+    for (uint32_t tid = blockIdx.x * kMiniWaves + wave; tid < G.n_tasks; tid += gridDim.x * kMiniWaves) {
+        const PWA_GLOBAL PairDesc* const P = (const PWA_GLOBAL PairDesc*)(G.pairs + (size_t)tid * PPW + grp);
+        const int n = P->n, m = P->m;
+        g_cu8* const pat = (g_cu8*)P->pat;
+        int mmax = m, mmin = m;
+        if (PPW == 4) {
+            mmax = max(m, __shfl_xor(m, 16));
+            mmin = min(m, __shfl_xor(m, 16));
+            mmax = max(mmax, __shfl_xor(mmax, 32));
+            mmin = min(mmin, __shfl_xor(mmin, 32));
+        }
+        mmax = __builtin_amdgcn_readfirstlane(mmax);
+        mmin = __builtin_amdgcn_readfirstlane(mmin);
+        const int n_chunks = (mmax + (LN - 1) + 15) / 16;
+        const int i_first = k * RL + 1;
+        int pc[RL], hl[RL], el[RL], bs[RL], bj[RL];
+#pragma unroll
+        for (int r = 0; r < RL; ++r) {
+            const int i = i_first + r;
+            pc[r] = i <= n ? (int)((uint32_t)pat[i - 1] * 0x01010101u) : 0x100;   // splatted byte; rows past n: never equal
+            const int h = h0(i);
+            hl[r] = p_addw(p_mulw(h, 8), K.cE);
+            el[r] = p_addw(p_mulw(p_addw(h, go), 8), 2 * PR::E);                 // E[i][0] = H[i][0] + gap_open: its extension ties the opening
+            bs[r] = 0;
+            bj[r] = 0;
+        }
+        int diag0 = K.cE;   // H[i_first - 1][0] = H[0][0] = 0 ... for lane 0; lane k: H[i_first - 1][0]
+        diag0 = p_addw(p_mulw(h0(i_first - 1), 8), K.cE);
+        const int top_inc = NW ? K.ge8 : 0;
+        int own[RL] = {};
+        if (SG) sg_own(own, i_first, n);
+        int sg_v = p_addw(p_mulw(h0(n), 8), K.cE), sg_t = k - 1;   // SG: the record starts at column 0
+        g_u8* const tb = BAND ? (g_u8*)P->tb : nullptr;
+        const int offa = k * Geo::PA, offb = LN * Geo::PA + k * Geo::PB;
+        int bot_h = 0, bot_f = 0, tch = 0;
+        // text staging with scalar loads, a chunk ahead (mini_fill_kernel: no vector load may sit among the band stores)
+        const uint32_t* tg[PPW];
+        int mg[PPW];
+#pragma unroll
+        for (int x = 0; x < PPW; ++x) {
+            const uint64_t tp = (uint64_t)(uintptr_t)P->txt;
+            const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)tp, LN * x), hi = __builtin_amdgcn_readlane((uint32_t)(tp >> 32), LN * x);
+            tg[x] = (const uint32_t*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+            mg[x] = __builtin_amdgcn_readlane(m, LN * x);
+        }
+        auto stage = [&](int t0s, mu32x4 (&w)[PPW]) {
+#pragma unroll
+            for (int x = 0; x < PPW; ++x) {
+                const int tc = min(t0s, (mg[x] + 15) & ~15);
+                w[x] = *(const __attribute__((address_space(4))) mu32x4*)((uintptr_t)tg[x] + (size_t)tc);
+            }
+        };
+        const uint32_t bsel = (uint32_t)(k & 3) * 0x01010101u;
+        const int wsel = lane >> 2;
+        mu32x4 wnext[PPW];
+        stage(0, wnext);
+        for (int ch = 0; ch < n_chunks; ++ch) {
+            const int t0 = ch * 16;
+            uint32_t wv = wnext[0][0];
+#pragma unroll
+            for (int x = 1; x < 4 * PPW; ++x) wv = (wsel == x) ? wnext[x >> 2][x & 3] : wv;
+            const int tcv = (int)__builtin_amdgcn_perm(wv, wv, bsel);
+            stage(t0 + 16, wnext);
+            const int top0 = p_addw(p_mulw(h0(NW ? t0 + 1 : 0), 8), K.cF);   // H[0][t0 + 1] as an F-open candidate
+            g_u8* const tbs = tb + (size_t)t0 * Geo::SR;
+            const bool interior = t0 >= LN - 1 && t0 + 16 <= mmin;
+            if (interior)
+                gotoh_chunk<RL, MODE, false, LN, BAND>(t0, k, m, pc, hl, el, diag0, bot_h, bot_f, tch, tcv, top0, top_inc, K, bs, bj, own, sg_v, sg_t,
+                                                       tbs + offa, tbs + offb);
+            else
+                gotoh_chunk<RL, MODE, true, LN, BAND>(t0, k, m, pc, hl, el, diag0, bot_h, bot_f, tch, tcv, top0, top_inc, K, bs, bj, own, sg_v, sg_t,
+                                                      tbs + offa, tbs + offb);
+        }
+        PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
+        g_i32* const sco = BAND ? nullptr : (g_i32*)G.scores_out + P->out_index;
+        if (SG) {
+            if (n >= i_first && n < i_first + RL) {
+                res->score = (int)((unsigned)sg_v - (unsigned)K.cE) >> 3;
+                res->end_i = (uint32_t)n;
+                res->end_j = (uint32_t)(sg_t - k + 1);
+                if (!BAND) *sco = (int)((unsigned)sg_v - (unsigned)K.cE) >> 3;
+            }
+        } else if (NW) {
+#pragma unroll
+            for (int r = 0; r < RL; ++r)
+                if (i_first + r == n) {   // the lane's state froze at column m
+                    res->score = (int)((unsigned)hl[r] - (unsigned)K.cE) >> 3;
+                    res->end_i = (uint32_t)n;
+                    res->end_j = (uint32_t)m;
+                    if (!BAND) *sco = (int)((unsigned)hl[r] - (unsigned)K.cE) >> 3;
+                }
+        } else {
+            int s_best = 0, i_best = 0, j_best = 0;
+#pragma unroll
+            for (int r = 0; r < RL; ++r) {
+                const int i = i_first + r, h = bs[r] >> 4;
+                if (i <= n && h > s_best) {
+                    s_best = h;
+                    i_best = i;
+                    j_best = bj[r] + (15 - (bs[r] & 15)) - k + 1;
+                }
+            }
+#pragma unroll
+            for (int off = LN / 2; off >= 1; off >>= 1) {
+                const int so = __shfl_xor(s_best, off), io = __shfl_xor(i_best, off), jo = __shfl_xor(j_best, off);
+                const bool better = so > s_best || (so == s_best && so > 0 && io < i_best);
+                if (better) {
+                    s_best = so;
+                    i_best = io;
+                    j_best = jo;
+                }
+            }
+            if (k == 0 && n > 0) {   // (the padding pairs of the last task share a real pair's result slot)
+                res->score = s_best;
+                res->end_i = (uint32_t)i_best;
+                res->end_j = (uint32_t)j_best;
+                if (!BAND) *sco = s_best;
+            }
+        }
+    }
+}
+
 
 // The walk: one wave per pair, a three-state machine (H, E, F) over the band, one op per iteration.  The band is staged into LDS in
 // windows of WIN steps by LDS-DMA (pair_traceback_kernel's scheme): the window of the current cell and, in flight behind it, the one

@@ -3,6 +3,7 @@
 #pragma once
 #include "batch_scores.hip.h"
 #include "batch_affine.hip.h"
+#include "batch_gotoh.hip.h"
 #include "batch_nwdist.hip.h"
 #include "pair_fill.hip.h"
 #include "mini_fill.hip.h"
@@ -13,12 +14,12 @@ typedef void (*batch_kernel_t)(const BatchParams);
 typedef void (*affine_kernel_t)(const AffineParams);
 typedef void (*nwdist_kernel_t)(const NwDistParams);
 typedef void (*pair_kernel_t)(const PairParams);
-enum { BM_AFF = 3, BM_AFFS = 4, BM_DIST = 5, BM_DISTP = 7 };   // affine (hw3) plain / shifted, hw4 NW + distance, its packed-key form; 0..2, 6: batch_scores.hip.h
+enum { BM_AFF = 3, BM_AFFS = 4, BM_DIST = 5, BM_DISTP = 7 };   // affine (hw3) plain / shifted, hw4 NW + distance, its packed-key form; 0..2, 6: batch_scores.hip.h; 8..10: batch_gotoh.hip.h
 struct BatchKernelEntry {
     int R, mode, score;
     batch_kernel_t fn;       // multi-strip form (strip hand-off rows through HBM)
     const char* name;
-    affine_kernel_t afn = nullptr;
+    affine_kernel_t afn = nullptr;            // hw3's affine kernels, and the gotoh score kernels (BM_GNW, BM_GNWS, BM_GSW)
     nwdist_kernel_t dfn = nullptr;
     batch_kernel_t fn_single = nullptr;   // every task a single strip: no hand-off accesses at all
     batch_kernel_t fn_lanes = nullptr;         // every lane its own text (index-paired lists), multi-strip

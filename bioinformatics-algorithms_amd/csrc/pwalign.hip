@@ -1,5 +1,5 @@
 // pwalign.hip -- score batches: pwa_*batch_create (the strip / stripe / mini-stripe scheduler of a pair list), pwa_batch_run ..
-// pwa_batch_destroy, and the one-shot calls over lists of any size (pwa_scores, pwa_distances, pwa_scores_affine).  The rest of the
+// pwa_batch_destroy, and the one-shot calls over lists of any size (pwa_scores, pwa_distances, pwa_scores_affine, pwa_scores_gotoh).  The rest of the
 // C ABI of include/pwalign.h: pwalign_ctx.hip (contexts, memory), pwalign_affine_tb.hip, pwalign_align.hip.  gfx950 only; no CPU path.
 #include "pwalign_internal.h"
 
@@ -27,6 +27,7 @@ struct pwa_batch {
     const BatchKernelEntry* kern = nullptr;
     BatchParams bp{};
     bool affine = false, nwdist = false, lanes = false;
+    bool gotoh = false;             // affine-gap (gotoh) scores: batch_gotoh_kernel strips, or the band-less gotoh mini-stripe fills in `mini`
     void* strip_fn = nullptr;         // the strip kernel this batch launches (strip_kernel_fn)
     bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
     bool prof16 = false;            // ... in their profile form: one pattern per wave task (batch_scores.hip.h, PROF16)
@@ -68,7 +69,8 @@ uint32_t f16_bits_scaled(int k) {
 }
 
 // ---------------------------------------------------------------------------- batch: create
-enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2 };
+enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2, KIND_GOTOH = 3 };
+constexpr uint64_t kGotohMiniMaxN = 1024;   // patterns of the band-less gotoh fills: 16 lanes x kMiniRL rows, then 64 lanes x 8 | 16 rows
 
 // The caller's sequences, pair list and scoring, as the stages of batch_create_impl see them
 struct BatchInput {
@@ -83,6 +85,7 @@ struct BatchInput {
     bool semi;   // PWA_MODE_SG: every pair runs off the strips (band-less mini-stripe / stripe fills + the end-cell walk)
     bool affine() const { return kind == KIND_AFFINE; }
     bool nwdist() const { return kind == KIND_NWDIST; }
+    bool gotoh() const { return kind == KIND_GOTOH; }   // gap = gap_open, beside gap_extend; any mode, end cells allowed
     uint64_t len(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
 };
 
@@ -121,11 +124,17 @@ int scan_pairs(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, LivePairs& lp) 
     }
     lp.live.resize(in.n_pairs);
     uint64_t n_live = 0;
+    const int64_t gotoh_mx = max_abs({in.match, in.mismatch, (int64_t)std::llabs((long long)in.gap) + std::llabs((long long)in.gap_extend)});
     for (uint64_t k = 0; k < in.n_pairs; ++k) {
         if (in.pair_a[k] >= in.n_seq || in.pair_b[k] >= in.n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
         const uint64_t n = in.len(in.pair_a[k]), m = in.len(in.pair_b[k]);
+        if (in.gotoh() && (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)gotoh_mx >= (long double)(1u << 28)))
+            return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
         if (n == 0 || m == 0) {
-            if (in.nwdist()) {   // hw4.cpp:21-28 + 146-152: an all-gap alignment, every column counts
+            if (in.gotoh()) {   // one gap of the whole other side: gap_open + L * gap_extend (SG: only the pattern's rows cost)
+                const uint64_t L = in.local ? 0 : in.semi ? (m == 0 ? n : 0) : n + m;
+                b->host_scores[k] = L == 0 ? 0 : (int32_t)((uint32_t)in.gap + (uint32_t)wrap_mul((int64_t)L, in.gap_extend));
+            } else if (in.nwdist()) {   // hw4.cpp:21-28 + 146-152: an all-gap alignment, every column counts
                 b->host_scores[k] = (int32_t)(n + m);
             } else if (in.affine()) {   // hw3.cpp:39-52: V[0][0] = 0, F[n][0] = Go + Ge(n-1), E[0][m] = Go + Ge(m-1)
                 b->host_scores[k] = (n + m == 0) ? 0 : (int32_t)((uint32_t)in.gap + (uint32_t)wrap_mul((int64_t)(n + m - 1), in.gap_extend));
@@ -196,11 +205,12 @@ struct CellForm {
 
 int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, const Alphabet& al, CellForm& f) {
     const int match = in.match, mismatch = in.mismatch, gap = in.gap, gap_extend = in.gap_extend;
-    const bool local = in.local, affine = in.affine(), nwdist = in.nwdist();
+    const bool local = in.local, affine = in.affine(), nwdist = in.nwdist(), gotoh = in.gotoh();
     const uint64_t max_n = lp.max_n, max_m = lp.max_m;
     // ---- engine choice.  The strip engine pads short patterns with rows that match nothing; for SW
     // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
     // (semi-global: no strip form yet -- every pair takes the route of a pass with end cells)
+    // (gotoh lists follow the linear rule, as a rule: NW and SW without end cells on the strips, gap terms are <= 0 there)
     f.strips = affine || nwdist || (!in.want_end && !in.semi && (!local || (mismatch <= 0 && gap <= 0)));
     f.kmode = local ? BM_SW : BM_NW;
     f.tab_match = match;
@@ -232,6 +242,23 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
         if (al.n_alpha <= 7 && fits8(f.tab_match) && fits8(f.tab_mismatch)) f.score_path = SC_PERM;
         if (f.score_path == SC_CMP && al.absent_byte < 0)
             return fail(ctx, PWA_E_INVALID, "affine pass: the texts use all 256 byte values, no padding symbol left");
+    } else if (gotoh) {
+        if (f.strips) {
+            // NW in ge (i + j)-shifted coordinates when every value stays far inside int32, as the hw3 form above; SW keeps the zero floor
+            const bool shift_ok = !local && (int64_t)(max_n + max_m + 4) * max_abs({match, mismatch, gap, gap_extend}) * 4 < (1ll << 27);
+            f.kmode = local ? BM_GSW : shift_ok ? BM_GNWS : BM_GNW;
+            f.aff_go = gap;
+            f.aff_ge = gap_extend;
+            if (shift_ok) {
+                f.tab_match = match - 2 * gap_extend;
+                f.tab_mismatch = mismatch - 2 * gap_extend;
+            }
+            if (al.n_alpha <= 7 && fits8(f.tab_match) && fits8(f.tab_mismatch)) f.score_path = SC_PERM;
+            if (f.score_path == SC_CMP && al.absent_byte < 0) f.strips = false;   // no byte left to pad with
+        }
+        // everything else: the band-less gotoh mini-stripe fills, on raw bytes, with their shape limit
+        if (!f.strips && max_n > kGotohMiniMaxN)
+            return fail(ctx, PWA_E_CAPACITY, "gotoh scores off the strip kernels (semi-global, end cells, SW with mismatch > 0, texts with all 256 byte values) take patterns of at most 1024 symbols");
     } else if (f.strips) {
         if (!local) {
             // gap-shifted NW: G = H - g(i+j) needs every |value| to stay far inside int32
@@ -248,11 +275,11 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
     }
     // (a scores pass that wants end cells runs wholly off the strips: its arena is coded whenever the alphabet allows, for the mini-stripe
     // kernels -- the stripe engine's compare form is the same on codes, a pattern-only symbol is code 7 and equals no text code)
-    const bool code_for_end_cells = (in.want_end || in.semi) && !affine && !nwdist && al.n_alpha <= 7 && ctx->knobs.tb_engine != 0;
+    const bool code_for_end_cells = (in.want_end || in.semi) && !affine && !nwdist && !gotoh && al.n_alpha <= 7 && ctx->knobs.tb_engine != 0;
     f.coded = (f.strips && f.score_path == SC_PERM) || code_for_end_cells;
     // Short patterns that a scores pass routes away from the strips run on the mini-stripe engine WITHOUT a band (mini_fill.hip.h,
     // BAND = false: four pairs per wave) where it applies: coded arena, keyed cells in range, table constants in a byte.
-    if (f.coded && !affine && !nwdist && ctx->knobs.tb_engine != 0 && tb_range_ok(max_n + max_m, match, mismatch, gap, local ? 26 : 28)) {
+    if (f.coded && !affine && !nwdist && !gotoh && ctx->knobs.tb_engine != 0 && tb_range_ok(max_n + max_m, match, mismatch, gap, local ? 26 : 28)) {
         f.mini_scores = diag_keys_fit(match, mismatch, gap);
         f.mini_gap0 = f.mini_scores && !local && !in.semi && gap0_ok(max_n + max_m, match, mismatch, gap);
     }
@@ -404,7 +431,8 @@ StripHeight choose_strip_height(const std::vector<HostTask>& tl, const CellForm&
         long double w = c16 ? (long double)kCell16Vpr : e.mode == BM_SWS ? 4.06L : (e.mode == BM_SW ? 5.02L : 1.0L);   // VALU per lane row
         // affine strips of more than 40 rows run 2 instead of 3 waves per SIMD: [gpu] all pairs of 1024 x 1000 take
         // 93.2 ms at R = 52 against 89.2 ms at R = 32 for the same padded cells
-        if ((e.mode == BM_AFF || e.mode == BM_AFFS) && R > 40) w *= 1.045L;
+        // (the gotoh strips hold three values per row like them and share affine_waves_per_simd: the same height table)
+        if ((e.mode == BM_AFF || e.mode == BM_AFFS || e.mode == BM_GNW || e.mode == BM_GNWS || e.mode == BM_GSW) && R > 40) w *= 1.045L;
         // evaluated cells + the strip hand-off priced at ~2 cells per column and strip boundary ([gpu]: the
         // 1000-row affine pass is equally fast at R = 32 and 52 but moves 37 % fewer HBM bytes at 52)
         long double cost = 0;
@@ -469,6 +497,7 @@ long double prof16_cost(const std::vector<HostTask>& tl) {   // in choose_strip_
 // the -2^29 sentinels never win (pair_affine.hip.h).  Raw-byte alphabets and scorings large enough for the reference's own
 // wrap-around to matter stay on the strips.
 bool route_eligible(const BatchInput& in, const CellForm& f, uint64_t max_n, uint64_t max_m) {
+    if (in.gotoh()) return false;   // routing is a rule for them (choose_cell_form); work-aware routing: DESIGN.md §9
     if (in.nwdist())
         return f.kmode == BM_DIST && f.score_path == SC_PERM && (int64_t)(max_n + max_m + 2) * max_abs({in.match, in.mismatch, in.gap, 1}) < (1ll << 28);
     if (in.affine())
@@ -606,7 +635,7 @@ std::vector<uint32_t> split_tasks(StripTasks& st, const std::vector<uint32_t>& m
 // The strip kernel a batch launches, chosen once: the occupancy query and pwa_batch_run both take this one
 void* strip_kernel_fn(const BatchKernelEntry& e, const BatchInput& in, bool cell16, bool lanes, bool single) {
     if (in.nwdist()) return reinterpret_cast<void*>(e.dfn);
-    if (in.affine()) return reinterpret_cast<void*>(e.afn);
+    if (in.affine() || in.gotoh()) return reinterpret_cast<void*>(e.afn);
     const batch_kernel_t fn = cell16  ? (single ? e.fn_cell16_single : e.fn_cell16)
                               : lanes ? (single ? e.fn_lanes_single : e.fn_lanes)
                                       : (single && e.fn_single ? e.fn_single : e.fn);
@@ -769,7 +798,7 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
     per_cu = std::max(1, std::min(per_cu, 32));
     b->grid = (uint32_t)std::min<uint64_t>(nt, (uint64_t)ctx->num_cu * per_cu);
     // int32 per half: one (affine: two) int4 per lane per 4-column block
-    const int hand_vals = (in.affine() || (in.nwdist() && kmode != BM_DISTP)) ? 2 : 1;   // int4 per lane per 4-column block
+    const int hand_vals = (in.affine() || in.gotoh() || (in.nwdist() && kmode != BM_DISTP)) ? 2 : 1;   // int4 per lane per 4-column block
     const uint64_t half = (max_strips > 1 ? ((max_m + 3) / 4 + 1) * 256 : 256) * hand_vals;
     // Strip s reads the half written by strip s-1 and writes the other one.  With at most two strips per task
     // the second half is only ever the parked dummy block (stride 0), so it is one block long: for C3 that
@@ -949,14 +978,77 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
     return PWA_OK;
 }
 
+// ---- gotoh pairs off the strips (every SG list, every list with end cells, SW with mismatch > 0, no pad byte): the band-less form of
+// the gotoh mini-stripe fill (gotoh_fill.hip.h, gotoh_scores_kernel), one launch per row class -- 16 lanes per pair up to 256 rows,
+// one pair per wave up to 1024.  The fill itself writes PairResult and the device score vector: no walk follows.
+int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std::vector<uint64_t>& aoff, const std::vector<uint32_t>& pairs) {
+    struct Cls {
+        int rl, ln;
+        std::vector<uint32_t> lst;
+    };
+    std::vector<Cls> classes;
+    for (const uint32_t k : pairs) {
+        const uint64_t n = in.len(in.pair_a[k]);
+        const int ln = n <= 256 ? 16 : 64, rl = n <= 256 ? mini_rl_for(n) : n <= 512 ? 8 : 16;
+        size_t c = 0;
+        while (c < classes.size() && (classes[c].rl != rl || classes[c].ln != ln)) ++c;
+        if (c == classes.size()) classes.push_back({rl, ln, {}});
+        classes[c].lst.push_back(k);
+    }
+    HIPC(ctx, b->pair_res.alloc(pairs.size() * sizeof(PairResult)));
+    HIPC(ctx, hipMemset(b->pair_res.p, 0, pairs.size() * sizeof(PairResult)));
+    static const char* const kModeName[3] = {"NW", "SW", "SG"};
+    size_t q_next = 0;
+    std::string names;
+    for (Cls& cls : classes) {
+        sort_by_length_desc(cls.lst, [&](uint32_t x) { return in.len(in.pair_b[x]); });   // a wave's four texts about equally long
+        const size_t ppw = (size_t)(64 / cls.ln);
+        std::vector<PairDesc> pd;
+        pd.reserve(cls.lst.size() + 3);
+        for (const uint32_t k : cls.lst) {
+            PairDesc d;
+            std::memset(&d, 0, sizeof d);
+            d.pat = b->arena.as<uint8_t>() + aoff[in.pair_a[k]];
+            d.txt = b->arena.as<uint8_t>() + aoff[in.pair_b[k]];
+            d.n = (int32_t)in.len(in.pair_a[k]);
+            d.m = (int32_t)in.len(in.pair_b[k]);
+            d.res = b->pair_res.as<PairResult>() + q_next++;
+            d.out_index = k;
+            b->live_idx.push_back(k);
+            pd.push_back(d);
+            b->padded_cells += (uint64_t)(cls.ln * cls.rl) * in.len(in.pair_b[k]);
+        }
+        const uint32_t n_real = (uint32_t)pd.size();
+        while (pd.size() % ppw) {   // empty patterns fill the last wave (no row of theirs is row n, no cell of theirs a maximum: nothing is written)
+            PairDesc d = pd[n_real - 1];
+            d.n = 0;
+            pd.push_back(d);
+        }
+        b->mini.emplace_back(new PairLaunch());
+        PairLaunch& ml = *b->mini.back();
+        for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
+        ml.gotoh = b->mode;
+        ml.gotoh_scores = true;
+        const int rc = ml.build_mini(ctx, pd, n_real, in.match, in.mismatch, in.gap, cls.rl, cls.ln);
+        if (rc != PWA_OK) return rc;
+        ml.G.gap_extend = in.gap_extend;
+        ml.G.scores_out = b->scores.as<int32_t>();
+        names += std::string(names.empty() ? "" : " + ") + "gotoh_scores_kernel<RL=" + std::to_string(cls.rl) + ",LN=" + std::to_string(cls.ln) + "," +
+                 kModeName[b->mode] + ",no-band>";
+    }
+    b->kernel_name = names;
+    return PWA_OK;
+}
+
 int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, int kind, int gap_extend,
                       const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
                       const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
     if (!ctx || !out) return PWA_E_INVALID;
     *out = nullptr;
-    const bool affine = kind == KIND_AFFINE, nwdist = kind == KIND_NWDIST;
+    const bool affine = kind == KIND_AFFINE, nwdist = kind == KIND_NWDIST, gotoh = kind == KIND_GOTOH;
     if ((affine || nwdist) && want_end_cells) return fail(ctx, PWA_E_INVALID, "end cells are not defined for this pass");
     if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && (mode != PWA_MODE_SG || affine || nwdist)) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    if (gotoh && (gap > 0 || gap_extend > 0)) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
     if (!seq_off || (n_pairs && (!pair_a || !pair_b))) return fail(ctx, PWA_E_INVALID, "null input");
     if (n_seq && !seq_bytes && seq_off[n_seq] != 0) return fail(ctx, PWA_E_INVALID, "null seq_bytes");
     if (n_pairs >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "more than 2^32-2 pairs in one batch");
@@ -982,6 +1074,7 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
     b->want_end = in.want_end;
     b->affine = affine;
     b->nwdist = nwdist;
+    b->gotoh = gotoh;
 
     LivePairs lp;
     int rc = scan_pairs(ctx, b, in, lp);
@@ -1058,7 +1151,7 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
         if (st.ht.empty()) b->use_strips = false;
         if (b->use_strips && (rc = setup_strips(ctx, b, in, form, al, aoff, st, h, lp.max_m, clock)) != PWA_OK) return rc;
     }
-    if (!off_strips.empty() && (rc = setup_off_strips(ctx, b, in, form, aoff, off_strips)) != PWA_OK) return rc;
+    if (!off_strips.empty() && (rc = gotoh ? setup_gotoh_mini(ctx, b, in, aoff, off_strips) : setup_off_strips(ctx, b, in, form, aoff, off_strips)) != PWA_OK) return rc;
     if (ctx->knobs.debug) {
         clock.mark("engine setup");
         HIPC(ctx, hipDeviceSynchronize());
@@ -1197,6 +1290,13 @@ int pwa_nwdist_batch_create(pwa_ctx* ctx, int match, int mismatch, int gap, cons
                              n_pairs, 0, out);
 }
 
+int pwa_gotoh_batch_create(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                           const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                           int want_end_cells, pwa_batch** out) {
+    return batch_create_impl(ctx, mode, match, mismatch, gap_open, KIND_GOTOH, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                             want_end_cells, out);
+}
+
 int pwa_batch_run(pwa_batch* b, void* stream_v) {
     if (!b) return PWA_E_INVALID;
     pwa_ctx* ctx = b->ctx;
@@ -1221,7 +1321,7 @@ int pwa_batch_run(pwa_batch* b, void* stream_v) {
                 dp.tab2_hi = 0u;
                 dp.scores2 = nullptr;
                 hipLaunchKernelGGL(reinterpret_cast<nwdist_kernel_t>(b->strip_fn), dim3(b->grid), dim3(64), 0, st, dp);
-            } else if (b->affine) {
+            } else if (b->affine || b->gotoh) {   // (the gotoh strips take go and ge the same way; neg is hw3's alone)
                 AffineParams ap;
                 ap.b = b->bp;
                 ap.go = b->aff_go;
@@ -1422,6 +1522,17 @@ int pwa_scores_affine(pwa_ctx* ctx, int match, int mismatch, int gap_open, int g
                                   [&](const uint32_t* a, const uint32_t* b, uint64_t n, pwa_batch** out) {
                                       return pwa_affine_batch_create(ctx, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq,
                                                                      a, b, n, out);
+                                  });
+}
+
+int pwa_scores_gotoh(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                     const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                     int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out) {
+    if (!ctx || !score_out) return PWA_E_INVALID;
+    return scores_in_arena_chunks(ctx, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, end_i_out, end_j_out,
+                                  [&](const uint32_t* a, const uint32_t* b, uint64_t n, pwa_batch** out) {
+                                      return pwa_gotoh_batch_create(ctx, mode, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq,
+                                                                    a, b, n, (end_i_out || end_j_out) ? 1 : 0, out);
                                   });
 }
 

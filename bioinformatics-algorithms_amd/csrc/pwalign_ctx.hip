@@ -16,6 +16,7 @@ namespace pwa {
 // gotoh_kernels.hip: the affine-gap (Gotoh) fills and walks, mode = PWA_MODE_NW | SW | SG; ln = 16 (rl in kMiniRL) or 64 (rl = 8 | 16)
 void (*gotoh_fill_kernel_for(int rl, int mode, int ln))(const PairParams);
 void (*gotoh_walk_kernel_for(int rl, int mode, int ln))(const PairParams);
+void (*gotoh_scores_kernel_for(int rl, int mode, int ln))(const PairParams);   // the fills without a band (no walk follows)
 }
 
 __global__ void pwa_nop_kernel(int* p) {
@@ -491,7 +492,7 @@ int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_r
 int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband) {
     HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
     if (mini) {
-        const pair_kernel_t fill = gotoh >= 0 ? gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln)
+        const pair_kernel_t fill = gotoh >= 0 ? (gotoh_scores ? gotoh_scores_kernel_for(geom.rl, gotoh, mini_ln) : gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln))
                                               : mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
         const pair_kernel_t walk_fn = gotoh >= 0 ? gotoh_walk_kernel_for(geom.rl, gotoh, mini_ln)
                                                  : mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
@@ -512,6 +513,7 @@ int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int wa
         hipLaunchKernelGGL(fill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G);
         HIPC(ctx, hipGetLastError());
         if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
+        if (gotoh_scores) return PWA_OK;
         hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
         HIPC(ctx, hipGetLastError());
         return PWA_OK;

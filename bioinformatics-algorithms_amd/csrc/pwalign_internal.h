@@ -289,6 +289,7 @@ struct PairLaunch {
     bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
     bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
     int gotoh = -1;      // >= 0 (a PWA_MODE_*): the affine-gap mini-stripe kernels (gotoh_fill.hip.h); build_mini takes gap_open as gap
+    bool gotoh_scores = false;   // ... their band-less form (gotoh_scores_kernel): score and end cell from the fill itself, no walk
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;

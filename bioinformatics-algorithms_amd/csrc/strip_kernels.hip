@@ -6,8 +6,8 @@
 
 namespace pwa {
 
-extern const BatchKernelEntry kStripKernelsSW[], kStripKernelsNW[], kStripKernelsAff[];
-extern const size_t kStripKernelsSWCount, kStripKernelsNWCount, kStripKernelsAffCount;
+extern const BatchKernelEntry kStripKernelsSW[], kStripKernelsNW[], kStripKernelsAff[], kStripKernelsGotoh[];
+extern const size_t kStripKernelsSWCount, kStripKernelsNWCount, kStripKernelsAffCount, kStripKernelsGotohCount;
 
 static const std::vector<BatchKernelEntry>& merged_table() {
     static const std::vector<BatchKernelEntry> t = [] {
@@ -15,6 +15,7 @@ static const std::vector<BatchKernelEntry>& merged_table() {
         v.insert(v.end(), kStripKernelsSW, kStripKernelsSW + kStripKernelsSWCount);
         v.insert(v.end(), kStripKernelsNW, kStripKernelsNW + kStripKernelsNWCount);
         v.insert(v.end(), kStripKernelsAff, kStripKernelsAff + kStripKernelsAffCount);
+        v.insert(v.end(), kStripKernelsGotoh, kStripKernelsGotoh + kStripKernelsGotohCount);
         return v;
     }();
     return t;

@@ -352,6 +352,28 @@ int pwa_align_gotoh_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch,
 int pwa_align_gotoh_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
 
 /*
+ * Affine-gap ("gotoh") SCORES of many pairs: what pwa_scores / pwa_batch_create are to pwa_align_batch.  Recurrence, boundaries, raw-byte
+ * equality, sign rule (gap_open <= 0 and gap_extend <= 0, else PWA_E_INVALID), score and end cell per mode, pairs with an empty side,
+ * the range rule (a pair beyond it is PWA_E_CAPACITY) and the empty list (PWA_OK) are exactly those of the comment block of
+ * pwa_align_gotoh_batch above: score_out[k] (and the end cell) equal what that call returns for pair k wherever both accept the pair.
+ *   pwa_gotoh_batch_create  a batch object like every other: pwa_batch_run (asynchronous, on the caller's stream) / _d_scores /
+ *                     _set_d_scores / _fetch / _info / _last_ms / _run_times / _destroy; end cells when want_end_cells was set;
+ *                     pwa_batch_cell_bits is 32 or 0, pwa_batch_profile_form 0;
+ *   pwa_scores_gotoh  the one-call form over lists of any size (cut into arena-sized pipelined runs, as pwa_scores); end cells when
+ *                     end_i_out or end_j_out is given.
+ * Engines, chosen by rule: PWA_MODE_NW, and PWA_MODE_SW with mismatch <= 0, without end cells run on register-strip kernels of their own
+ * (lane = pair, patterns of ANY length) as long as some byte value occurs in no text (the strips pad short patterns with it).  Every
+ * other list -- PWA_MODE_SG, end cells wanted, SW with mismatch > 0, texts that use all 256 byte values -- runs on the band-less form of
+ * pwa_align_gotoh_batch's fills, whose shape rule then holds for the whole list: patterns of at most 1024 symbols, else PWA_E_CAPACITY.
+ */
+int pwa_gotoh_batch_create(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mismatch, int gap_open, int gap_extend,
+                           const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                           const uint32_t *pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch **out);
+int pwa_scores_gotoh(pwa_ctx *ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                     const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs,
+                     int32_t *score_out, uint32_t *end_i_out, uint32_t *end_j_out);
+
+/*
  * The -g selection without the op lists: hw2.cpp:342-350 keeps, of every pair's global alignment, only
  * overlapLongestExactMatch(alignedPattern, alignedReference) (hw2.cpp:267-278) and the score.  Same fill and
  * traceback band as pwa_align_batch; the device walk looks at the symbols under each run of diagonal moves
