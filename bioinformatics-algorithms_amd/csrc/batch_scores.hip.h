@@ -369,19 +369,33 @@ __device__ __forceinline__ void scores16_body(const BatchParams& P) {
 // diagonal adds sit between s_set_gpr_idx_on (SRC1) and s_set_gpr_idx_off, and nothing else does.  Then the 8 maxima and gap adds
 // of the row step, a chain across the block's columns that the second wave on the SIMD covers ([gpu] tools/valu_issue.hip, rows
 // "SW pk16 profile").
+//
+// INT = true, the integer-coded row (the host admits it when mismatch - gap >= 0 and match - gap >= 0, pwalign.hip): the stored
+// value is H itself (>= 0) as the INTEGER k in each 16-bit half.  For 0 <= k < 0x7c00 the pattern k read as f16 is a non-negative
+// finite number (a denormal below 0x0400; the kernel's mode keeps f16 denormals) whose f16 order is the integer order, so
+// v_pk_maximum3_f16 is an exact packed unsigned max3 and the only f16 instruction left.  With gamma = -gap >= 0, s' = s + gamma:
+//   t = H_diag + s'                   v_add_u32: ONE 32-bit add for both halves (t <= 2047 + 254: no carry), s' through index mode
+//   m = max3(t, H_up, H_left)         = gamma + max(diag + s, up + g, left + g)
+//   H = max(m - gamma, 0)             v_pk_sub_u16 clamp          = max(0, diag + s, up + g, left + g), hw2.cpp:211
+//   best = max3(best, m, m')          score = max(best - gamma, 0) once per task, in integers
+// Boundary row and column are 0, pad rows and pad columns take s' = 0 (s = g: they only decay; their m never exceeds a real
+// cell's).  s' <= 254 is one byte: a profile register is one v_perm from the code's 4-byte table, the high byte of each half 0x00.
+// The 8 adds issue at the full rate, the other 20 of the row step's 28 at the packed rate ([gpu] tools/valu_issue.hip, row
+// "SW pk16 profile C=8 int"; that row has no v_mov, the kernel keeps the row's v_mov of the block's last H: DESIGN.md r05).
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
-template <int R>
+template <int R, bool INT>
 __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
     constexpr int C = 8, NW = (R + 3) / 4;
     const int lane = threadIdx.x & 63;
-    const uint32_t g = P.gap16x2;
+    const uint32_t g = P.gap16x2;   // INT: gamma | gamma << 16
     // the pattern code sigma's byte tables (s' = s - g): bytes 0..3 = low / high bytes of f16(s'(sigma, c)) for text codes c = 0..3
+    // (INT: the byte s' itself in tlo; no high bytes)
     uint32_t tlo[4], thi[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         tlo[s] = P.lo16_base ^ (P.lo16_diff << (8 * s));
-        thi[s] = P.hi16_base ^ (P.hi16_diff << (8 * s));
+        thi[s] = INT ? 0u : P.hi16_base ^ (P.hi16_diff << (8 * s));
     }
     u32x8 pz = {0, 0, 0, 0, 0, 0, 0, 0};   // sigma = 4: the pad rows' +0.0
     asm volatile("" : "+v"(pz));
@@ -423,10 +437,11 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
             return (v & keep) | (0x0c0c0c0cu & ~keep);
         };
 
-        // G of the left boundary column (H = 0): g in every row
+        // G of the left boundary column (H = 0): g in every row (INT: H = 0)
+        const uint32_t edge = INT ? 0u : g;
         uint32_t col[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) col[r] = g;
+        for (int r = 0; r < R; ++r) col[r] = edge;
         uint32_t best[4] = {0, 0, 0, 0};
         const int nblk = (m + C - 1) / C;
         uint32_t na0 = word(toff_a, ma, 0), na1 = word(toff_a, ma, 1);
@@ -438,11 +453,13 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
             nb0 = word(toff_b, mb, 2 * jb + 2);
             nb1 = word(toff_b, mb, 2 * jb + 3);
             // the block's profile: selector (cA, cA | 4, cB, cB | 4) per column, then one v_perm per code
+            // (INT: selector (cA, 12, cB, 12) -- byte 12 selects 0x00 -- into the one table)
             u32x8 p0, p1, p2, p3;
 #pragma unroll
             for (int k = 0; k < C; ++k) {
                 const uint32_t kk = (uint32_t)(k & 3);
-                const uint32_t sel = __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk * 0x00000101u + (4u + kk) * 0x01010000u) | 0x04000400u;
+                const uint32_t sel = INT ? __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk + ((4u + kk) << 16) + 0x0c000c00u) | 0x0c000c00u
+                                         : __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk * 0x00000101u + (4u + kk) * 0x01010000u) | 0x04000400u;
                 p0[k] = __builtin_amdgcn_perm(thi[0], tlo[0], sel);
                 p1[k] = __builtin_amdgcn_perm(thi[1], tlo[1], sel);
                 p2[k] = __builtin_amdgcn_perm(thi[2], tlo[2], sel);
@@ -451,8 +468,8 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
             // row -1 (H = 0): G_up = g in every column, and the diagonal of row 0's first column
             uint32_t u[C];
 #pragma unroll
-            for (int k = 0; k < C; ++k) u[k] = g;
-            uint32_t dprev = g;
+            for (int k = 0; k < C; ++k) u[k] = edge;
+            uint32_t dprev = edge;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 // the row's profile offset on the scalar unit, right before its row step (left to the compiler, all 152 are
@@ -461,61 +478,111 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
                 asm volatile("s_bfe_u32 %0, %1, %2" : "=s"(idx) : "s"(pw[r >> 2]), "i"((8 * (r & 3)) | (8 << 16)) : "scc");
                 const uint32_t left = col[r];
                 uint32_t t[C];
-                asm volatile(
-                    "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
-                    "v_pk_add_f16 %[t0], %[d], v216 clamp\n\t"
-                    "v_pk_add_f16 %[t1], %[u0], v217 clamp\n\t"
-                    "v_pk_add_f16 %[t2], %[u1], v218 clamp\n\t"
-                    "v_pk_add_f16 %[t3], %[u2], v219 clamp\n\t"
-                    "v_pk_add_f16 %[t4], %[u3], v220 clamp\n\t"
-                    "v_pk_add_f16 %[t5], %[u4], v221 clamp\n\t"
-                    "v_pk_add_f16 %[t6], %[u5], v222 clamp\n\t"
-                    "v_pk_add_f16 %[t7], %[u6], v223 clamp\n\t"
-                    "s_set_gpr_idx_off\n\t"
-                    "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l]\n\t"
-                    "v_pk_add_f16 %[u0], %[t0], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                    "v_pk_add_f16 %[u1], %[t1], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                    "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                    "v_pk_add_f16 %[u2], %[t2], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                    "v_pk_add_f16 %[u3], %[t3], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                    "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                    "v_pk_add_f16 %[u4], %[t4], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                    "v_pk_add_f16 %[u5], %[t5], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                    "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                    "v_pk_add_f16 %[u6], %[t6], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
-                    "v_pk_add_f16 %[u7], %[t7], %[g]\n\t"
-                    "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
-                    : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
-                      [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
-                      [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
-                      [b2] "+v"(best[2]), [b3] "+v"(best[3])
-                    : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
-                      "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
-                    : "m0", "scc");
+                if constexpr (INT) {
+                    asm volatile(
+                        "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
+                        "v_add_u32 %[t0], %[d], v216\n\t"
+                        "v_add_u32 %[t1], %[u0], v217\n\t"
+                        "v_add_u32 %[t2], %[u1], v218\n\t"
+                        "v_add_u32 %[t3], %[u2], v219\n\t"
+                        "v_add_u32 %[t4], %[u3], v220\n\t"
+                        "v_add_u32 %[t5], %[u4], v221\n\t"
+                        "v_add_u32 %[t6], %[u5], v222\n\t"
+                        "v_add_u32 %[t7], %[u6], v223\n\t"
+                        "s_set_gpr_idx_off\n\t"
+                        "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l]\n\t"
+                        "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                        "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                        "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                        "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                        "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                        "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                        "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                        "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                        "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                        "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
+                        "v_pk_sub_u16 %[u7], %[t7], %[g] clamp\n\t"
+                        "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
+                        : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
+                          [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
+                          [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
+                          [b2] "+v"(best[2]), [b3] "+v"(best[3])
+                        : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
+                          "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                        : "m0", "scc");
+                } else {
+                    asm volatile(
+                        "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
+                        "v_pk_add_f16 %[t0], %[d], v216 clamp\n\t"
+                        "v_pk_add_f16 %[t1], %[u0], v217 clamp\n\t"
+                        "v_pk_add_f16 %[t2], %[u1], v218 clamp\n\t"
+                        "v_pk_add_f16 %[t3], %[u2], v219 clamp\n\t"
+                        "v_pk_add_f16 %[t4], %[u3], v220 clamp\n\t"
+                        "v_pk_add_f16 %[t5], %[u4], v221 clamp\n\t"
+                        "v_pk_add_f16 %[t6], %[u5], v222 clamp\n\t"
+                        "v_pk_add_f16 %[t7], %[u6], v223 clamp\n\t"
+                        "s_set_gpr_idx_off\n\t"
+                        "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l]\n\t"
+                        "v_pk_add_f16 %[u0], %[t0], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                        "v_pk_add_f16 %[u1], %[t1], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                        "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                        "v_pk_add_f16 %[u2], %[t2], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                        "v_pk_add_f16 %[u3], %[t3], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                        "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                        "v_pk_add_f16 %[u4], %[t4], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                        "v_pk_add_f16 %[u5], %[t5], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                        "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                        "v_pk_add_f16 %[u6], %[t6], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
+                        "v_pk_add_f16 %[u7], %[t7], %[g]\n\t"
+                        "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
+                        : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
+                          [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
+                          [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
+                          [b2] "+v"(best[2]), [b3] "+v"(best[3])
+                        : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
+                          "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                        : "m0", "scc");
+                }
                 dprev = left;
                 col[r] = u[C - 1];
             }
         }
-        // best = k * 2^-11, exact: back to int32 once per task
-        const half2_t b = __builtin_elementwise_maximum(__builtin_elementwise_maximum(h2_bits(best[0]), h2_bits(best[1])),
-                                                        __builtin_elementwise_maximum(h2_bits(best[2]), h2_bits(best[3])));
         const uint32_t out_a = P.slot_out[slot_a], out_b = P.slot_out[slot_b];   // (read here: no VGPRs held over the column loop)
-        if (out_a != 0xffffffffu) P.scores[out_a] = (int)((float)b.x * 2048.0f);
-        if (out_b != 0xffffffffu) P.scores[out_b] = (int)((float)b.y * 2048.0f);
+        if constexpr (INT) {
+            // best = gamma + the score (or less than gamma where no cell is positive), an integer per half
+            const int gamma = (int)(g & 0xffffu);
+            const int ba = (int)max(max(best[0] & 0xffffu, best[1] & 0xffffu), max(best[2] & 0xffffu, best[3] & 0xffffu));
+            const int bb = (int)max(max(best[0] >> 16, best[1] >> 16), max(best[2] >> 16, best[3] >> 16));
+            if (out_a != 0xffffffffu) P.scores[out_a] = max(ba - gamma, 0);
+            if (out_b != 0xffffffffu) P.scores[out_b] = max(bb - gamma, 0);
+        } else {
+            // best = k * 2^-11, exact: back to int32 once per task
+            const half2_t b = __builtin_elementwise_maximum(__builtin_elementwise_maximum(h2_bits(best[0]), h2_bits(best[1])),
+                                                            __builtin_elementwise_maximum(h2_bits(best[2]), h2_bits(best[3])));
+            if (out_a != 0xffffffffu) P.scores[out_a] = (int)((float)b.x * 2048.0f);
+            if (out_b != 0xffffffffu) P.scores[out_b] = (int)((float)b.y * 2048.0f);
+        }
     }
 }
 
 // R = 152 rows at two waves per SIMD: R + 40 profile + the block's columns and temporaries fit in 256 VGPRs
-template <int R>
+template <int R, bool INT = false>
 __global__ __launch_bounds__(256, 2) void batch_scores16p_kernel(const BatchParams P) {
-    scores16p_body<R>(P);
+    scores16p_body<R, INT>(P);
 }
 
 // MULTI = false: every task of the launch is a single strip -- the hand-off row accesses are compiled out

@@ -27,6 +27,7 @@ struct BatchKernelEntry {
     batch_kernel_t fn_cell16 = nullptr;        // two pairs per lane in packed f16 cells (BM_SWS, SC_PERM), multi-strip
     batch_kernel_t fn_cell16_single = nullptr; // ... every task a single strip
     batch_kernel_t fn_prof16 = nullptr;        // ... their profile form: one pattern against 128 texts per task (PROF16, single strip)
+    batch_kernel_t fn_prof16_int = nullptr;    // ... with the integer-coded row (mismatch >= gap and match >= gap)
 };
 // strip_kernels.hip
 const BatchKernelEntry* batch_kernel_table(size_t* count);

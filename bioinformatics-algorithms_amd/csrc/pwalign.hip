@@ -31,6 +31,7 @@ struct pwa_batch {
     void* strip_fn = nullptr;         // the strip kernel this batch launches (strip_kernel_fn)
     bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
     bool prof16 = false;            // ... in their profile form: one pattern per wave task (batch_scores.hip.h, PROF16)
+    bool prof16_int = false;        // ... with the integer-coded row step (H as an integer per half; prof16_int_admitted)
     int32_t aff_go = 0, aff_ge = 0, aff_neg = 0;
     uint32_t grid = 0;
     DevBuf arena, tasks, slot_poff, slot_plen, slot_out, slot_toff, slot_tlen, lane_text, hand, queue, scores;
@@ -56,7 +57,8 @@ namespace {
 // pk_maximum3, pk_add clamp, 1/2 pk_maximum3 for the running best, + the hand-off share ([gpu] PMC on C3: 4.56)
 constexpr double kCell16Vpr = 4.6;
 // The profile form (PROF16): 3.5 VALU per lane row -- indexed pk_add clamp, pk_maximum3, pk_add, 1/2 pk_maximum3 -- + the row's
-// v_mov and the per-block profile ([gpu] tools/valu_issue.hip: 6.43 against CELL16's 7.62 cycles per cell at two waves per SIMD)
+// v_mov and the per-block profile ([gpu] tools/valu_issue.hip: 6.43 against CELL16's 7.62 cycles per cell at two waves per SIMD;
+// its integer-coded row 6.00 in the same table: the same instruction count, priced alike)
 constexpr double kProf16Vpr = 3.8;
 constexpr int kProf16R = 152;   // the rows of its single strip (batch_scores16p_kernel<152>)
 // f16 bit pattern of k * 2^-11 for |k| <= 1023: a normal number (exponent k's leading bit + 4), exact
@@ -470,6 +472,14 @@ bool prof16_admitted(const Knobs& knobs, const Alphabet& al, uint64_t max_n) {
     return knobs.prof16 != 0 && codes_low && max_n <= (uint64_t)kProf16R;
 }
 
+// ---- PROF16's integer-coded row: H >= 0 stored as an integer per half and s' = s - gap added with one 32-bit add, which needs every
+// s' >= 0 (mismatch <= match is not assumed).  Everything else is PROF16's own admission: H <= 2047 and s' <= 254 keep a half below
+// 2^16 (no carry into the other pair) and below 0x7c00 (ordered like its f16 reading).  Priced like the f16 row (kProf16Vpr): the
+// same 3.5 instructions per lane row, and no routing decision sits near enough to move.
+bool prof16_int_admitted(const Knobs& knobs, const BatchInput& in) {
+    return knobs.prof16_int != 0 && in.mismatch - in.gap >= 0 && in.match - in.gap >= 0;
+}
+
 std::vector<HostTask> group_by_pattern(const BatchInput& in, std::vector<uint32_t>& order) {
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
         if (in.pair_a[x] != in.pair_a[y]) return in.pair_a[x] < in.pair_a[y];
@@ -792,7 +802,7 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
 
     if (b->lanes) b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
     b->strip_fn = strip_kernel_fn(*b->kern, in, b->cell16, b->lanes, max_strips == 1);
-    if (b->prof16) b->strip_fn = reinterpret_cast<void*>(b->kern->fn_prof16);   // (the reported name stays the CELL16 entry's)
+    if (b->prof16) b->strip_fn = reinterpret_cast<void*>(b->prof16_int ? b->kern->fn_prof16_int : b->kern->fn_prof16);   // (the reported name stays the CELL16 entry's)
     int per_cu = 0;
     HIPC(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, b->strip_fn, 64, 0));
     per_cu = std::max(1, std::min(per_cu, 32));
@@ -857,12 +867,18 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
         P.hi16_base = (x16 >> 8) * 0x01010101u;
         P.hi16_diff = ((m16 ^ x16) >> 8) & 0xffu;
         P.gap16x2 = g16 | (g16 << 16);
-        if (b->prof16) {   // the profile form's tables hold s' = s - g (|s'| <= 254: exact)
+        if (b->prof16 && !b->prof16_int) {   // the profile form's tables hold s' = s - g (|s'| <= 254: exact)
             const uint32_t mp = f16_bits_scaled(in.match - in.gap), xp = f16_bits_scaled(in.mismatch - in.gap);
             P.lo16_base = (xp & 0xffu) * 0x01010101u;
             P.lo16_diff = (mp ^ xp) & 0xffu;
             P.hi16_base = (xp >> 8) * 0x01010101u;
             P.hi16_diff = ((mp ^ xp) >> 8) & 0xffu;
+        } else if (b->prof16) {   // its integer row: the bytes s' = s - g (0..254) themselves, and gamma = -g in both halves
+            const uint32_t mp = (uint32_t)(in.match - in.gap), xp = (uint32_t)(in.mismatch - in.gap), gamma = (uint32_t)(-in.gap);
+            P.lo16_base = xp * 0x01010101u;
+            P.lo16_diff = mp ^ xp;
+            P.hi16_base = P.hi16_diff = 0;
+            P.gap16x2 = gamma | (gamma << 16);
         }
     }
     P.slot_toff = b->slot_toff.as<uint32_t>();
@@ -1144,6 +1160,7 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
             std::vector<HostTask> htp = group_by_pattern(in, porder);
             if (ctx->knobs.prof16 == 1 || prof16_cost(htp) < h.cost) {
                 b->prof16 = true;
+                b->prof16_int = prof16_int_admitted(ctx->knobs, in);
                 st.order.swap(porder);
                 st.ht.swap(htp);
             }
@@ -1423,6 +1440,11 @@ int pwa_batch_info(const pwa_batch* b, uint64_t* cells, uint64_t* padded_cells, 
 int pwa_batch_profile_form(const pwa_batch* b) {
     if (!b) return PWA_E_INVALID;
     return b->use_strips && b->prof16 ? 1 : 0;
+}
+
+int pwa_batch_profile_int(const pwa_batch* b) {
+    if (!b) return PWA_E_INVALID;
+    return b->use_strips && b->prof16 && b->prof16_int ? 1 : 0;
 }
 
 int pwa_batch_cell_bits(const pwa_batch* b) {

@@ -71,6 +71,7 @@ void Knobs::read() {
     tb_engine = num("PWA_TB_ENGINE", -1);
     cell16 = num("PWA_CELL16", -1);
     prof16 = num("PWA_PROF16", -1);
+    prof16_int = num("PWA_PROF16_INT", -1);
     affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
     if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
 }

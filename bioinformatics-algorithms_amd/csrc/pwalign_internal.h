@@ -73,6 +73,8 @@ struct Knobs {
                                                 // admits them, unset = by estimated cost (batch_create_impl)
     int prof16 = -1;                            // PWA_PROF16: 0 = never the profile form of the packed cells (one pattern against 128
                                                 // texts), 1 = always where the batch admits it, unset = by estimated cost
+    int prof16_int = -1;                        // PWA_PROF16_INT: 0 = never the profile form's integer-coded row, 1 or unset = wherever the
+                                                // scoring admits it (mismatch >= gap and match >= gap)
     uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count

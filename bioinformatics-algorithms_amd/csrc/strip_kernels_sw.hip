@@ -13,7 +13,7 @@ namespace pwa {
                         batch_scores_kernel<R, M, S, false>, \
                         batch_scores_kernel<R, M, S, true, true>, batch_scores_kernel<R, M, S, false, true>, \
                         batch_scores_kernel<R, M, S, true, false, true>, batch_scores_kernel<R, M, S, false, false, true>, \
-                        batch_scores16p_kernel<152>}
+                        batch_scores16p_kernel<152>, batch_scores16p_kernel<152, true>}
 extern const BatchKernelEntry kStripKernelsSW[] = {
     BK(76, BM_SW, SC_PERM),   BK(104, BM_SW, SC_PERM),
     BKL(40, BM_SWS, SC_PERM), BKL16(52, BM_SWS, SC_PERM), BKL16(76, BM_SWS, SC_PERM), BKL(96, BM_SWS, SC_PERM),

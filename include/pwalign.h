@@ -43,6 +43,8 @@
  *                                 lane (default: by estimated cost; pwa_batch_cell_bits says which form a batch runs)
  *   PWA_PROF16=0|1                packed f16 local strip scores: 0 never / 1 always (where the batch admits it) their profile form, one
  *                                 pattern against 128 texts per wave task (default: by estimated cost; pwa_batch_profile_form says which)
+ *   PWA_PROF16_INT=0|1            the profile form's row step: 0 always the f16 row, 1 (and by default) the integer-coded row wherever the
+ *                                 scoring admits it (mismatch >= gap and match >= gap; pwa_batch_profile_int says which)
  *   PWA_TB_ENGINE=0|2             traceback fills and scores off the strips: 0 the stripe engine's plain forms only, 2 mini-stripe kernels
  *                                 wherever they exist (default: by the list -- patterns of <= 256 rows, and of <= 1024 rows in batches)
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
@@ -162,6 +164,9 @@ int pwa_batch_cell_bits(const pwa_batch *b);
 /* 1 when the batch's strips run the profile form of the packed f16 cells (one pattern against 128 texts per wave task; PWA_PROF16=0|1
  * forces either form where it applies), 0 otherwise. */
 int pwa_batch_profile_form(const pwa_batch *b);
+/* 1 when that profile form runs its integer-coded row step (scores stored as integers, one 32-bit add per two cells; taken when
+ * mismatch - gap >= 0 and match - gap >= 0 unless PWA_PROF16_INT=0), 0 otherwise.  Scores are the same either way. */
+int pwa_batch_profile_int(const pwa_batch *b);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);

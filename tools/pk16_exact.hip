@@ -5,6 +5,10 @@
 //   (2) v_pk_maximum3_f16 of every pair (a, b) against c in {-0.0, +0.0, -2^-11, 2^-11, -1, 1}: the larger value, and +0.0 when the
 //       largest value is a zero of either sign that meets +0.0
 //   (3) v_perm_b32 selector bytes 12 and 13: 0x00 and 0xff whatever the sources
+//   (4) the integer-coded profile cell (PROF16, integer form): bit patterns k in [0, 2304] read as f16 (k < 0x0400 are denormals):
+//       v_pk_maximum3_f16 of every pair (a, b) against c in {0, 1, a, b, 2304, 0x3c00} must be the integer maximum in both halves, and
+//       v_pk_sub_u16 ... clamp of every pair must be max(a - b, 0) / max(b - a, 0); under the mode register a HIP kernel starts with,
+//       which is printed
 //   hipcc --offload-arch=gfx950 -O2 -o tools/pk16_exact tools/pk16_exact.hip && tools/pk16_exact
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -57,6 +61,39 @@ __global__ void probe(uint32_t s_any) {
     }
 }
 
+#define KI 2304
+__device__ unsigned long long ifails[8];
+__device__ uint32_t mode_reg;
+
+__global__ void probe_int() {
+    const uint32_t a = blockIdx.x;
+    if (a == 0 && threadIdx.x == 0) {
+        uint32_t m;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_MODE)" : "=s"(m));
+        mode_reg = m;
+    }
+    for (uint32_t b = threadIdx.x; b <= KI; b += blockDim.x) {
+        const uint32_t x = a | (b << 16), y = b | (a << 16);
+        const uint32_t c3[6] = {0u, 1u, a, b, (uint32_t)KI, 0x3c00u};
+        const uint32_t mab = a > b ? a : b;
+        uint32_t r;
+        for (int i = 0; i < 6; ++i) {
+            asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(c3[i] | (c3[i] << 16)));
+            const uint32_t want = mab > c3[i] ? mab : c3[i];
+            if (r != (want | (want << 16))) {
+                atomicAdd(&ifails[0], 1ull);
+                if (want < 0x0400u) atomicAdd(&ifails[1], 1ull);   // the expected maximum is a denormal pattern
+            }
+        }
+        asm volatile("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(x), "v"(y));
+        if (r != ((a > b ? a - b : 0u) | ((b > a ? b - a : 0u) << 16))) atomicAdd(&ifails[2], 1ull);
+        // the row step's one 32-bit add for both halves: no carry out of the low half below 2^16
+        asm volatile("v_add_u32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+        if (r != ((a + b) | ((a + b) << 16))) atomicAdd(&ifails[3], 1ull);
+        atomicAdd(&ifails[4], 1ull);
+    }
+}
+
 int main() {
     unsigned long long z[8] = {}, h[8];
     (void)hipMemcpyToSymbol(HIP_SYMBOL(fails), z, sizeof z);
@@ -68,5 +105,19 @@ int main() {
     printf("v_pk_add_f16        == (a+b) * 2^-11 for |a+b| <= 2048:            %llu mismatches\n", h[1]);
     printf("v_pk_maximum3_f16   == max(a, b, c), c in {-0,+0,-2^-11,2^-11,-1,1}, +0 over -0: %llu mismatches (of %llu)\n", h[2], 6 * h[5]);
     printf("v_perm_b32 selector 12 -> 0x00: %llu mismatches; selector 13 -> 0xff: %llu mismatches\n", h[3], h[4]);
-    return (h[0] | h[1] | h[2] | h[3] | h[4]) ? 2 : 0;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(ifails), z, sizeof z);
+    hipLaunchKernelGGL(probe_int, dim3(KI + 1), dim3(256), 0, 0);
+    if (hipDeviceSynchronize() != hipSuccess) { printf("launch failed\n"); return 1; }
+    unsigned long long hi[8];
+    uint32_t mode = 0;
+    (void)hipMemcpyFromSymbol(hi, HIP_SYMBOL(ifails), sizeof hi);
+    (void)hipMemcpyFromSymbol(&mode, HIP_SYMBOL(mode_reg), sizeof mode);
+    printf("integer patterns (a, b), a, b in [0, %d]: %llu pairs; MODE = 0x%08x (FP_DENORM bits 7:4 = 0x%x: f32 = %u, f64/f16 = %u; 3 = denormals kept)\n", KI,
+           hi[4], mode, (mode >> 4) & 0xfu, (mode >> 4) & 3u, (mode >> 6) & 3u);
+    printf("v_pk_maximum3_f16   == integer max(a, b, c), c in {0, 1, a, b, %d, 0x3c00} (both halves): %llu mismatches (of %llu), %llu of them with a\n"
+           "                       denormal pattern (< 0x0400) expected%s\n", KI, hi[0], 6 * hi[4], hi[1],
+           hi[1] ? ": THE MAXIMUM FLUSHES F16 DENORMALS IN THIS MODE" : " -- f16 denormals are not flushed");
+    printf("v_pk_sub_u16 clamp  == max(a - b, 0), max(b - a, 0):                                      %llu mismatches\n", hi[2]);
+    printf("v_add_u32           == (a + b) in both halves, no carry between them:                    %llu mismatches\n", hi[3]);
+    return (h[0] | h[1] | h[2] | h[3] | h[4] | hi[0] | hi[2] | hi[3]) ? 2 : 0;
 }

@@ -126,11 +126,11 @@ OPX(k_cell16, "v_perm_b32 %0, s2, %2, %3\n\tv_pk_add_f16 %0, %3, %4\n\tv_pk_maxi
 // diagonal adds read it through index mode (SRC1) -- or, in the movrels row, through one v_movrels_b32 per column (M0 = code x C).
 // Then per column the chain h = max3(t', G_up, G_left), G = h + g, and half a running-best max3; one v_mov hands the block's last
 // G to the next block.  All registers are physical (clobbered), so the compiler only supplies the loop.  Counted per CELL (2C per step).
-#define PROF_CLOBBERS "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106"
+#define PROF_CLOBBERS "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107"
 #define OPP(name, txt)                                                                                                 \
     __global__ __launch_bounds__(64) void name(int* out, unsigned long long* ticks, int seed) {                        \
         int st = 0;                                                                                                    \
-        asm volatile("v_mov_b32 v32, 0x10001000\n\tv_mov_b32 v33, 0x10401040\n\tv_mov_b32 v34, 0x10801080\n\tv_mov_b32 v35, 0x10c010c0\n\tv_mov_b32 v36, 0x11001100\n\tv_mov_b32 v37, 0x11401140\n\tv_mov_b32 v38, 0x11801180\n\tv_mov_b32 v39, 0x11c011c0\n\tv_mov_b32 v40, 0x10001000\n\tv_mov_b32 v41, 0x10401040\n\tv_mov_b32 v42, 0x10801080\n\tv_mov_b32 v43, 0x10c010c0\n\tv_mov_b32 v44, 0x11001100\n\tv_mov_b32 v45, 0x11401140\n\tv_mov_b32 v46, 0x11801180\n\tv_mov_b32 v47, 0x11c011c0\n\tv_mov_b32 v48, 0x10001000\n\tv_mov_b32 v49, 0x10401040\n\tv_mov_b32 v50, 0x10801080\n\tv_mov_b32 v51, 0x10c010c0\n\tv_mov_b32 v52, 0x11001100\n\tv_mov_b32 v53, 0x11401140\n\tv_mov_b32 v54, 0x11801180\n\tv_mov_b32 v55, 0x11c011c0\n\tv_mov_b32 v56, 0x10001000\n\tv_mov_b32 v57, 0x10401040\n\tv_mov_b32 v58, 0x10801080\n\tv_mov_b32 v59, 0x10c010c0\n\tv_mov_b32 v60, 0x11001100\n\tv_mov_b32 v61, 0x11401140\n\tv_mov_b32 v62, 0x11801180\n\tv_mov_b32 v63, 0x11c011c0\n\tv_mov_b32 v64, 0x10001000\n\tv_mov_b32 v65, 0x10401040\n\tv_mov_b32 v66, 0x10801080\n\tv_mov_b32 v67, 0x10c010c0\n\tv_mov_b32 v68, 0x11001100\n\tv_mov_b32 v69, 0x11401140\n\tv_mov_b32 v70, 0x11801180\n\tv_mov_b32 v71, 0x11c011c0\n\tv_mov_b32 v72, 0x10001000\n\tv_mov_b32 v73, 0x10401040\n\tv_mov_b32 v74, 0x10801080\n\tv_mov_b32 v75, 0x10c010c0\n\tv_mov_b32 v76, 0x11001100\n\tv_mov_b32 v77, 0x11401140\n\tv_mov_b32 v78, 0x11801180\n\tv_mov_b32 v79, 0x11c011c0\n\tv_mov_b32 v80, 0x10001000\n\tv_mov_b32 v81, 0x10401040\n\tv_mov_b32 v82, 0x10801080\n\tv_mov_b32 v83, 0x10c010c0\n\tv_mov_b32 v84, 0x11001100\n\tv_mov_b32 v85, 0x11401140\n\tv_mov_b32 v86, 0x11801180\n\tv_mov_b32 v87, 0x11c011c0\n\tv_mov_b32 v88, 0x10001000\n\tv_mov_b32 v89, 0x10401040\n\tv_mov_b32 v90, 0x10801080\n\tv_mov_b32 v91, 0x10c010c0\n\tv_mov_b32 v92, 0x11001100\n\tv_mov_b32 v93, 0x11401140\n\tv_mov_b32 v94, 0x11801180\n\tv_mov_b32 v95, 0x11c011c0\n\tv_mov_b32 v96, 0x10001000\n\tv_mov_b32 v97, 0x10401040\n\tv_mov_b32 v98, 0x10801080\n\tv_mov_b32 v99, 0x10c010c0\n\tv_mov_b32 v100, 0x11001100\n\tv_mov_b32 v101, 0x11401140\n\tv_mov_b32 v102, 0x11801180\n\tv_mov_b32 v103, 0x11c011c0\n\tv_mov_b32 v104, 0x10001000\n\tv_mov_b32 v105, 0x10401040\n\tv_mov_b32 v106, 0x10801080" ::: PROF_CLOBBERS);                                                                          \
+        asm volatile("v_mov_b32 v32, 0x10001000\n\tv_mov_b32 v33, 0x10401040\n\tv_mov_b32 v34, 0x10801080\n\tv_mov_b32 v35, 0x10c010c0\n\tv_mov_b32 v36, 0x11001100\n\tv_mov_b32 v37, 0x11401140\n\tv_mov_b32 v38, 0x11801180\n\tv_mov_b32 v39, 0x11c011c0\n\tv_mov_b32 v40, 0x10001000\n\tv_mov_b32 v41, 0x10401040\n\tv_mov_b32 v42, 0x10801080\n\tv_mov_b32 v43, 0x10c010c0\n\tv_mov_b32 v44, 0x11001100\n\tv_mov_b32 v45, 0x11401140\n\tv_mov_b32 v46, 0x11801180\n\tv_mov_b32 v47, 0x11c011c0\n\tv_mov_b32 v48, 0x10001000\n\tv_mov_b32 v49, 0x10401040\n\tv_mov_b32 v50, 0x10801080\n\tv_mov_b32 v51, 0x10c010c0\n\tv_mov_b32 v52, 0x11001100\n\tv_mov_b32 v53, 0x11401140\n\tv_mov_b32 v54, 0x11801180\n\tv_mov_b32 v55, 0x11c011c0\n\tv_mov_b32 v56, 0x10001000\n\tv_mov_b32 v57, 0x10401040\n\tv_mov_b32 v58, 0x10801080\n\tv_mov_b32 v59, 0x10c010c0\n\tv_mov_b32 v60, 0x11001100\n\tv_mov_b32 v61, 0x11401140\n\tv_mov_b32 v62, 0x11801180\n\tv_mov_b32 v63, 0x11c011c0\n\tv_mov_b32 v64, 0x10001000\n\tv_mov_b32 v65, 0x10401040\n\tv_mov_b32 v66, 0x10801080\n\tv_mov_b32 v67, 0x10c010c0\n\tv_mov_b32 v68, 0x11001100\n\tv_mov_b32 v69, 0x11401140\n\tv_mov_b32 v70, 0x11801180\n\tv_mov_b32 v71, 0x11c011c0\n\tv_mov_b32 v72, 0x10001000\n\tv_mov_b32 v73, 0x10401040\n\tv_mov_b32 v74, 0x10801080\n\tv_mov_b32 v75, 0x10c010c0\n\tv_mov_b32 v76, 0x11001100\n\tv_mov_b32 v77, 0x11401140\n\tv_mov_b32 v78, 0x11801180\n\tv_mov_b32 v79, 0x11c011c0\n\tv_mov_b32 v80, 0x10001000\n\tv_mov_b32 v81, 0x10401040\n\tv_mov_b32 v82, 0x10801080\n\tv_mov_b32 v83, 0x10c010c0\n\tv_mov_b32 v84, 0x11001100\n\tv_mov_b32 v85, 0x11401140\n\tv_mov_b32 v86, 0x11801180\n\tv_mov_b32 v87, 0x11c011c0\n\tv_mov_b32 v88, 0x10001000\n\tv_mov_b32 v89, 0x10401040\n\tv_mov_b32 v90, 0x10801080\n\tv_mov_b32 v91, 0x10c010c0\n\tv_mov_b32 v92, 0x11001100\n\tv_mov_b32 v93, 0x11401140\n\tv_mov_b32 v94, 0x11801180\n\tv_mov_b32 v95, 0x11c011c0\n\tv_mov_b32 v96, 0x10001000\n\tv_mov_b32 v97, 0x10401040\n\tv_mov_b32 v98, 0x10801080\n\tv_mov_b32 v99, 0x10c010c0\n\tv_mov_b32 v100, 0x11001100\n\tv_mov_b32 v101, 0x11401140\n\tv_mov_b32 v102, 0x11801180\n\tv_mov_b32 v103, 0x11c011c0\n\tv_mov_b32 v104, 0x10001000\n\tv_mov_b32 v105, 0x10401040\n\tv_mov_b32 v106, 0x10801080\n\tv_mov_b32 v107, 0x10c010c0" ::: PROF_CLOBBERS);                                                                          \
         unsigned long long t0, t1;                                                                                     \
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");           \
         for (int it = 0; it < N_ITER; ++it) {                                                                          \
@@ -144,6 +144,10 @@ OPX(k_cell16, "v_perm_b32 %0, s2, %2, %3\n\tv_pk_add_f16 %0, %3, %4\n\tv_pk_maxi
     }
 OPP(k_prof8, "s_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_pk_add_f16 v80, v100, v32 clamp\n\tv_pk_add_f16 v81, v72, v33 clamp\n\tv_pk_add_f16 v82, v73, v34 clamp\n\tv_pk_add_f16 v83, v74, v35 clamp\n\tv_pk_add_f16 v84, v75, v36 clamp\n\tv_pk_add_f16 v85, v76, v37 clamp\n\tv_pk_add_f16 v86, v77, v38 clamp\n\tv_pk_add_f16 v87, v78, v39 clamp\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v101\n\tv_pk_add_f16 v72, v88, v102\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_add_f16 v73, v89, v102\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_add_f16 v74, v90, v102\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_add_f16 v75, v91, v102\n\tv_pk_maximum3_f16 v92, v84, v76, v75\n\tv_pk_add_f16 v76, v92, v102\n\tv_pk_maximum3_f16 v93, v85, v77, v76\n\tv_pk_add_f16 v77, v93, v102\n\tv_pk_maximum3_f16 v94, v86, v78, v77\n\tv_pk_add_f16 v78, v94, v102\n\tv_pk_maximum3_f16 v95, v87, v79, v78\n\tv_pk_add_f16 v79, v95, v102\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_pk_maximum3_f16 v105, v105, v92, v93\n\tv_pk_maximum3_f16 v106, v106, v94, v95\n\tv_mov_b32 v101, v79")
 OPP(k_prof4, "s_add_u32 %0, %0, 4\n\ts_and_b32 %0, %0, 15\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_pk_add_f16 v80, v100, v32 clamp\n\tv_pk_add_f16 v81, v72, v33 clamp\n\tv_pk_add_f16 v82, v73, v34 clamp\n\tv_pk_add_f16 v83, v74, v35 clamp\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v101\n\tv_pk_add_f16 v72, v88, v102\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_add_f16 v73, v89, v102\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_add_f16 v74, v90, v102\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_add_f16 v75, v91, v102\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_mov_b32 v101, v75")
+// integer-coded profile form: H stored as the integer k in each half, v_pk_maximum3_f16 only orders.  8 indexed v_add_u32 (one 32-bit add
+// for both halves), 8 max3, 8 v_pk_sub_u16 clamp, 4 best max3; no v_mov -- the last column's subtract writes the row's col register, which
+// the next row reads as its column-7 up (two row steps per asm text, v101 / v107 alternating as col[r] / col[r + 1])
+OPP(k_prof8i, "s_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v100, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v101\n\tv_pk_sub_u16 v72, v88, v102 clamp\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_sub_u16 v73, v89, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_sub_u16 v74, v90, v102 clamp\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_sub_u16 v75, v91, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_pk_maximum3_f16 v92, v84, v76, v75\n\tv_pk_sub_u16 v76, v92, v102 clamp\n\tv_pk_maximum3_f16 v93, v85, v77, v76\n\tv_pk_sub_u16 v77, v93, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v92, v93\n\tv_pk_maximum3_f16 v94, v86, v78, v77\n\tv_pk_sub_u16 v78, v94, v102 clamp\n\tv_pk_maximum3_f16 v95, v87, v107, v78\n\tv_pk_sub_u16 v101, v95, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v94, v95\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v100, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v107\n\tv_pk_sub_u16 v72, v88, v102 clamp\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_sub_u16 v73, v89, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_sub_u16 v74, v90, v102 clamp\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_sub_u16 v75, v91, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_pk_maximum3_f16 v92, v84, v76, v75\n\tv_pk_sub_u16 v76, v92, v102 clamp\n\tv_pk_maximum3_f16 v93, v85, v77, v76\n\tv_pk_sub_u16 v77, v93, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v92, v93\n\tv_pk_maximum3_f16 v94, v86, v78, v77\n\tv_pk_sub_u16 v78, v94, v102 clamp\n\tv_pk_maximum3_f16 v95, v87, v101, v78\n\tv_pk_sub_u16 v107, v95, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v94, v95")
 // (a v_movrels_b32 variant, one per column with M0 = code x C, does not exist here: gfx950 has no v_movrel* -- the assembler
 // rejects it as "instruction not supported on this GPU"; index mode is the only indexed VGPR read)
 OP(k_nop, "s_nop 0")
@@ -192,7 +196,7 @@ int main(int argc, char** argv) {
         {"v_pk_maximum3_f16", k_pkmaximum3f16, 1}, {"v_pk_add_f16", k_pkaddf16, 1}, {"v_pk_add_f16 clamp", k_pkaddf16c, 1},
         {"v_pk_max_f16", k_pkmaxf16, 1}, {"v_pk_add_u16", k_pkaddu16, 1}, {"v_perm_b32 (sgpr table)", k_permsgpr, 1},
         {"SW cell16, 2 rows x 2 pairs /cell", k_cell16, 1},
-        {"SW pk16 profile C=8 idx /cell", k_prof8, 4}, {"SW pk16 profile C=4 idx /cell", k_prof4, 2},
+        {"SW pk16 profile C=8 idx /cell", k_prof8, 4}, {"SW pk16 profile C=4 idx /cell", k_prof4, 2}, {"SW pk16 profile C=8 int /cell", k_prof8i, 8},
         {"SW cell, profile form /cell", k_cell4, 1}, {"SW cell, table form   /cell", k_cell4old, 1}, {"s_nop 0", k_nop, 1}};
     struct { const char* n; kfn f; int chain, total; } dt_[] = {
         {"v_add_u32 chain", d_add, 4, 4}, {"v_and/v_or chain", d_and, 4, 4}, {"v_max3_i32 chain", d_max3, 4, 4}, {"v_add_u32_sdwa chain", d_sdwa, 4, 4},
