@@ -32,6 +32,7 @@ EXPORTS = [
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
+    "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
@@ -164,6 +165,12 @@ def lib():
     L.pwa_align_gotoh_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_gotoh_batch_create.argtypes = gotoh_in + [C.c_int, C.POINTER(vp)]
     L.pwa_scores_gotoh.argtypes = gotoh_in + [i32p, u32p, u32p]
+    subst_in = batch_in[:2] + [vp, C.c_int, i32p] + gotoh_in[4:]   # ctx, mode, code[256], n_sym, submat, gap_open, gap_extend, sequences, pairs
+    L.pwa_align_subst_batch.argtypes = subst_in + [i32p, vp, u64p, u64p, u64p, u64p]
+    L.pwa_align_subst_batch_cigar.argtypes = subst_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
+    L.pwa_align_subst_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
+    L.pwa_subst_batch_create.argtypes = subst_in + [C.c_int, C.POINTER(vp)]
+    L.pwa_scores_subst.argtypes = subst_in + [i32p, u32p, u32p]
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
     L.pwa_cigar_bound.argtypes = [C.c_uint64]
@@ -211,6 +218,54 @@ def pack_sequences(seqs):
         tot += len(s)
     off[len(seqs)] = tot
     return b"".join(seqs), off, seqs
+
+
+_SUBST_NO_CODE = 255   # subst_table(unknown=None): a byte outside the alphabet (no code is that large: n_sym <= 32)
+
+
+def subst_table(alphabet, matrix, unknown=None, fold_case=False):
+    """The scoring of the align_subst_* / scores_subst* calls: symbol k of `alphabet` (bytes or str, at most 32 distinct symbols) gets
+    code k, and matrix[a][b] (any nested sequence or array of len(alphabet) x len(alphabet) integers, possibly asymmetric) scores
+    pattern symbol a against text symbol b.  Bytes outside the alphabet score as alphabet[unknown] (an index: a wildcard row and column
+    the caller put into the matrix); with unknown=None a call whose sequences hold such a byte raises PwaError.  fold_case also maps
+    the other case of every letter of the alphabet to the letter's code.  -> (code, n_sym, submat): a 256-entry uint8 map and the flat
+    int32 matrix, row = pattern code."""
+    import numpy as np
+    alpha = _b(alphabet)
+    n_sym = len(alpha)
+    if not 1 <= n_sym <= 32 or len(set(alpha)) != n_sym:
+        raise ValueError("subst_table: an alphabet of 1..32 distinct symbols")
+    m = np.asarray(matrix)
+    if m.shape != (n_sym, n_sym) or m.dtype.kind not in "iu" or np.abs(m.astype(np.int64)).max() > 0x7fffffff:
+        raise ValueError("subst_table: matrix must be %d x %d integers that fit int32" % (n_sym, n_sym))
+    if unknown is not None and not 0 <= unknown < n_sym:
+        raise ValueError("subst_table: unknown must be an index into the alphabet")
+    code = np.full(256, _SUBST_NO_CODE if unknown is None else unknown, dtype=np.uint8)
+    if fold_case:
+        for k, v in enumerate(alpha):
+            other = bytes([v]).swapcase()[0]
+            if other not in alpha:
+                code[other] = k
+    for k, v in enumerate(alpha):
+        code[v] = k
+    return code, n_sym, np.ascontiguousarray(m, dtype=np.int32).reshape(-1)
+
+
+def _subst_args(table, blob):
+    """(code, n_sym, submat) as the C ABI takes them; raises when the sequences hold a byte that subst_table left without a code"""
+    import numpy as np
+    code, n_sym, submat = table
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    submat = np.ascontiguousarray(submat, dtype=np.int32)
+    if code.shape != (256,) or submat.shape != (n_sym * n_sym,):
+        raise ValueError("a substitution table is (code[256], n_sym, submat[n_sym * n_sym]), as subst_table returns it")
+    if n_sym <= _SUBST_NO_CODE and (code == _SUBST_NO_CODE).any():
+        seen = np.bincount(np.frombuffer(blob, dtype=np.uint8), minlength=256) > 0
+        bad = np.flatnonzero(seen & (code == _SUBST_NO_CODE))
+        if bad.size:
+            raise PwaError("substitution table: byte 0x%02x of the sequences is outside the alphabet and no `unknown` code was given" % bad[0])
+        code = np.where(code == _SUBST_NO_CODE, 0, code).astype(np.uint8)   # (bytes that do not occur: any valid code)
+    return code, int(n_sym), submat, code.ctypes.data_as(C.c_void_p), submat.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def read_fasta(paths, n_threads=0):
@@ -483,9 +538,8 @@ class Context:
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def align_gotoh_batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
-        """pwa_align_gotoh_batch: affine-gap alignments (a gap of length L scores gap_open + L * gap_extend; include/pwalign.h) ->
-        [dict(score, ops, end, start)] as align_batch returns them."""
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b):
+        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs"""
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -500,16 +554,14 @@ class Context:
         nops = (C.c_uint64 * max(n, 1))()
         endc = (C.c_uint64 * (2 * max(n, 1)))()
         startc = (C.c_uint64 * (2 * max(n, 1)))()
-        rc = self._L.pwa_align_gotoh_batch(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc,
-                                           ops, ooff, nops, endc, startc)
-        self._check(rc, "pwa_align_gotoh_batch")
+        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc)
+        self._check(rc, name)
         raw = memoryview(ops)
         return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def align_gotoh_batch_cigar(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
-        """pwa_align_gotoh_batch_cigar: the alignments of align_gotoh_batch as CIGAR and MD:Z strings built on the device ->
-        [dict(score, cigar, mdz, end, start)] as align_batch_cigar returns them."""
+    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b):
+        """... and one that returns CIGAR and MD:Z strings built on the device"""
         import numpy as np
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
@@ -526,14 +578,73 @@ class Context:
         endc = (C.c_uint64 * (2 * max(n, 1)))()
         startc = (C.c_uint64 * (2 * max(n, 1)))()
         u64p = C.POINTER(C.c_uint64)
-        rc = self._L.pwa_align_gotoh_batch_cigar(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n,
-                                                 sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
-                                                 md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None)
-        self._check(rc, "pwa_align_gotoh_batch_cigar")
+        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
+                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None)
+        self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+
+    def align_gotoh_batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
+        """pwa_align_gotoh_batch: affine-gap alignments (a gap of length L scores gap_open + L * gap_extend; include/pwalign.h) ->
+        [dict(score, ops, end, start)] as align_batch returns them."""
+        return self._align_ops(self._L.pwa_align_gotoh_batch, "pwa_align_gotoh_batch",
+                               (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b)
+
+    def align_gotoh_batch_cigar(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
+        """pwa_align_gotoh_batch_cigar: the alignments of align_gotoh_batch as CIGAR and MD:Z strings built on the device ->
+        [dict(score, cigar, mdz, end, start)] as align_batch_cigar returns them."""
+        return self._align_strings(self._L.pwa_align_gotoh_batch_cigar, "pwa_align_gotoh_batch_cigar",
+                                   (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b)
+
+    # -- substitution-matrix scoring (table = subst_table(...)): the gotoh calls with s(i, j) = submat[code[p], code[t]]
+    def _subst_head(self, mode, table, gap_open, gap_extend, blob):
+        code, n_sym, submat, code_p, submat_p = _subst_args(table, blob)
+        return (self._h, MODE[mode], code_p, n_sym, submat_p, gap_open, gap_extend), (code, submat)
+
+    def align_subst_batch(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend):
+        """pwa_align_subst_batch -> [dict(score, ops, end, start)] as align_gotoh_batch returns them."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._align_ops(self._L.pwa_align_subst_batch, "pwa_align_subst_batch", head, packed, pair_a, pair_b)
+
+    def align_subst_batch_cigar(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend):
+        """pwa_align_subst_batch_cigar -> [dict(score, cigar, mdz, end, start)]; MD:Z reports byte identity, not score sign."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._align_strings(self._L.pwa_align_subst_batch_cigar, "pwa_align_subst_batch_cigar", head, packed, pair_a, pair_b)
+
+    def scores_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):
+        b = self.batch_subst(mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end)
+        b.run()
+        out = b.fetch()
+        b.close()
+        return out
+
+    def scores_subst_oneshot(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):
+        """pwa_scores_subst: the one-call form (pair lists of any size: cut into arena-sized runs by the library)."""
+        blob, off, seqs = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, blob)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei = (C.c_uint32 * max(n, 1))() if want_end else None
+        ej = (C.c_uint32 * max(n, 1))() if want_end else None
+        self._check(self._L.pwa_scores_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej), "pwa_scores_subst")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n])
+        return list(sc[:n])
+
+    def batch_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):
+        return Batch(self, mode, seqs, pair_a, pair_b, 0, 0, gap_open, want_end, gap_extend=gap_extend, subst=table)
+
+    def align_subst_stats(self):
+        """The last align_subst_batch(_cigar): device ms of its fills and walks, band bytes written."""
+        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_align_subst_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_subst_last_stats")
+        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
 
     def align_gotoh_stats(self):
         """The last align_gotoh_batch(_cigar): device ms of its fills and walks, band bytes written."""
@@ -665,7 +776,7 @@ class Context:
 class Batch:
     """Prepared scores-only batch: inputs resident in HBM, run() only enqueues kernels."""
 
-    def __init__(self, ctx, mode, seqs, pair_a, pair_b, match, mismatch, gap, want_end=False, gap_extend=0, gotoh=False):
+    def __init__(self, ctx, mode, seqs, pair_a, pair_b, match, mismatch, gap, want_end=False, gap_extend=0, gotoh=False, subst=None):
         self._ctx, self._L = ctx, ctx._L
         blob, off, seqs = pack_sequences(seqs)
         self.n_pairs = len(pair_a)
@@ -678,7 +789,11 @@ class Batch:
             pa = (C.c_uint32 * max(n, 1))(*pair_a)
             pb = (C.c_uint32 * max(n, 1))(*pair_b)
         h = C.c_void_p()
-        if gotoh:   # affine-gap scores of `mode` (nw / sw / sg): gap = gap_open
+        if subst is not None:   # ... under a substitution table (subst_table): the library copies code and matrix during the call
+            _code, n_sym, _submat, code_p, submat_p = _subst_args(subst, blob)
+            rc = self._L.pwa_subst_batch_create(ctx._h, MODE[mode], code_p, n_sym, submat_p, gap, gap_extend, blob, off, len(seqs), pa, pb, n,
+                                                1 if want_end else 0, C.byref(h))
+        elif gotoh:   # affine-gap scores of `mode` (nw / sw / sg): gap = gap_open
             rc = self._L.pwa_gotoh_batch_create(ctx._h, MODE[mode], match, mismatch, gap, gap_extend, blob, off, len(seqs), pa, pb, n,
                                                 1 if want_end else 0, C.byref(h))
         elif mode == "nwdist":

@@ -1,5 +1,5 @@
 // pwalign.hip -- score batches: pwa_*batch_create (the strip / stripe / mini-stripe scheduler of a pair list), pwa_batch_run ..
-// pwa_batch_destroy, and the one-shot calls over lists of any size (pwa_scores, pwa_distances, pwa_scores_affine, pwa_scores_gotoh).  The rest of the
+// pwa_batch_destroy, and the one-shot calls over lists of any size (pwa_scores, pwa_distances, pwa_scores_affine, pwa_scores_gotoh, pwa_scores_subst).  The rest of the
 // C ABI of include/pwalign.h: pwalign_ctx.hip (contexts, memory), pwalign_affine_tb.hip, pwalign_align.hip.  gfx950 only; no CPU path.
 #include "pwalign_internal.h"
 
@@ -28,6 +28,7 @@ struct pwa_batch {
     BatchParams bp{};
     bool affine = false, nwdist = false, lanes = false;
     bool gotoh = false;             // affine-gap (gotoh) scores: batch_gotoh_kernel strips, or the band-less gotoh mini-stripe fills in `mini`
+    SubstTable subst;               // pwa_subst_batch_create: the batch's own copy of the caller's table, host and device (n_sym = 0: none)
     void* strip_fn = nullptr;         // the strip kernel this batch launches (strip_kernel_fn)
     bool cell16 = false;            // the strips run two pairs per lane in packed f16 cells (batch_scores.hip.h, CELL16)
     bool prof16 = false;            // ... in their profile form: one pattern per wave task (batch_scores.hip.h, PROF16)
@@ -71,7 +72,7 @@ uint32_t f16_bits_scaled(int k) {
 }
 
 // ---------------------------------------------------------------------------- batch: create
-enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2, KIND_GOTOH = 3 };
+enum { KIND_LINEAR = 0, KIND_AFFINE = 1, KIND_NWDIST = 2, KIND_GOTOH = 3, KIND_SUBST = 4 };   // KIND_SUBST: gotoh under a substitution table
 constexpr uint64_t kGotohMiniMaxN = 1024;   // patterns of the band-less gotoh fills: 16 lanes x kMiniRL rows, then 64 lanes x 8 | 16 rows
 
 // The caller's sequences, pair list and scoring, as the stages of batch_create_impl see them
@@ -87,7 +88,8 @@ struct BatchInput {
     bool semi;   // PWA_MODE_SG: every pair runs off the strips (band-less mini-stripe / stripe fills + the end-cell walk)
     bool affine() const { return kind == KIND_AFFINE; }
     bool nwdist() const { return kind == KIND_NWDIST; }
-    bool gotoh() const { return kind == KIND_GOTOH; }   // gap = gap_open, beside gap_extend; any mode, end cells allowed
+    const SubstTable* subst;   // KIND_SUBST: the checked table (match / mismatch unused), else null
+    bool gotoh() const { return kind == KIND_GOTOH || kind == KIND_SUBST; }   // gap = gap_open, beside gap_extend; any mode, end cells allowed
     uint64_t len(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
 };
 
@@ -126,10 +128,13 @@ int scan_pairs(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, LivePairs& lp) 
     }
     lp.live.resize(in.n_pairs);
     uint64_t n_live = 0;
-    const int64_t gotoh_mx = max_abs({in.match, in.mismatch, (int64_t)std::llabs((long long)in.gap) + std::llabs((long long)in.gap_extend)});
+    const int64_t gotoh_gaps = (int64_t)std::llabs((long long)in.gap) + std::llabs((long long)in.gap_extend);
+    const int64_t gotoh_mx = in.subst ? std::max(in.subst->max_abs, gotoh_gaps) : max_abs({in.match, in.mismatch, gotoh_gaps});
     for (uint64_t k = 0; k < in.n_pairs; ++k) {
         if (in.pair_a[k] >= in.n_seq || in.pair_b[k] >= in.n_seq) return fail(ctx, PWA_E_INVALID, "pair index out of range");
         const uint64_t n = in.len(in.pair_a[k]), m = in.len(in.pair_b[k]);
+        if (in.subst && (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)gotoh_mx >= (long double)(1u << 28)))
+            return fail(ctx, PWA_E_CAPACITY, "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|) must stay below 2^28");
         if (in.gotoh() && (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)gotoh_mx >= (long double)(1u << 28)))
             return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
         if (n == 0 || m == 0) {
@@ -213,7 +218,8 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
     // those rows can only hold values <= real rows if mismatch <= 0 and gap <= 0.
     // (semi-global: no strip form yet -- every pair takes the route of a pass with end cells)
     // (gotoh lists follow the linear rule, as a rule: NW and SW without end cells on the strips, gap terms are <= 0 there)
-    f.strips = affine || nwdist || (!in.want_end && !in.semi && (!local || (mismatch <= 0 && gap <= 0)));
+    // (a substitution table: always the band-less mini form -- the strips score by byte compare or a two-value table)
+    f.strips = affine || nwdist || (!in.subst && !in.want_end && !in.semi && (!local || (mismatch <= 0 && gap <= 0)));
     f.kmode = local ? BM_SW : BM_NW;
     f.tab_match = match;
     f.tab_mismatch = mismatch;
@@ -259,6 +265,7 @@ int choose_cell_form(pwa_ctx* ctx, const BatchInput& in, const LivePairs& lp, co
             if (f.score_path == SC_CMP && al.absent_byte < 0) f.strips = false;   // no byte left to pad with
         }
         // everything else: the band-less gotoh mini-stripe fills, on raw bytes, with their shape limit
+        if (in.subst && max_n > kGotohMiniMaxN) return fail(ctx, PWA_E_CAPACITY, "substitution-matrix scores take patterns of at most 1024 symbols");
         if (!f.strips && max_n > kGotohMiniMaxN)
             return fail(ctx, PWA_E_CAPACITY, "gotoh scores off the strip kernels (semi-global, end cells, SW with mismatch > 0, texts with all 256 byte values) take patterns of at most 1024 symbols");
     } else if (f.strips) {
@@ -1049,7 +1056,12 @@ int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std
         if (rc != PWA_OK) return rc;
         ml.G.gap_extend = in.gap_extend;
         ml.G.scores_out = b->scores.as<int32_t>();
-        names += std::string(names.empty() ? "" : " + ") + "gotoh_scores_kernel<RL=" + std::to_string(cls.rl) + ",LN=" + std::to_string(cls.ln) + "," +
+        if (in.subst) {
+            ml.subst = b->subst.dev.as<uint32_t>();
+            ml.subst_n_sym = b->subst.n_sym;
+            ml.subst_stride = b->subst.stride;
+        }
+        names += std::string(names.empty() ? "" : " + ") + (in.subst ? "subst_scores_kernel<RL=" : "gotoh_scores_kernel<RL=") + std::to_string(cls.rl) + ",LN=" + std::to_string(cls.ln) + "," +
                  kModeName[b->mode] + ",no-band>";
     }
     b->kernel_name = names;
@@ -1058,10 +1070,11 @@ int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std
 
 int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, int kind, int gap_extend,
                       const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
-                      const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
+                      const uint32_t* pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch** out, SubstTable* subst = nullptr) try {
     if (!ctx || !out) return PWA_E_INVALID;
     *out = nullptr;
-    const bool affine = kind == KIND_AFFINE, nwdist = kind == KIND_NWDIST, gotoh = kind == KIND_GOTOH;
+    const bool affine = kind == KIND_AFFINE, nwdist = kind == KIND_NWDIST, gotoh = kind == KIND_GOTOH || kind == KIND_SUBST;
+    if ((kind == KIND_SUBST) != (subst != nullptr)) return fail(ctx, PWA_E_INVALID, "internal: substitution table");
     if ((affine || nwdist) && want_end_cells) return fail(ctx, PWA_E_INVALID, "end cells are not defined for this pass");
     if (mode != PWA_MODE_NW && mode != PWA_MODE_SW && (mode != PWA_MODE_SG || affine || nwdist)) return fail(ctx, PWA_E_INVALID, "unknown mode");
     if (gotoh && (gap > 0 || gap_extend > 0)) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
@@ -1072,8 +1085,8 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
         if (seq_off[s + 1] < seq_off[s]) return fail(ctx, PWA_E_INVALID, "seq_off not monotone");
     HIPC(ctx, hipSetDevice(ctx->device));
     CreateClock clock{ctx};
-    const BatchInput in{seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, kind, match, mismatch, gap, gap_extend,
-                        mode == PWA_MODE_SW, want_end_cells != 0, mode == PWA_MODE_SG};
+    BatchInput in{seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, kind, match, mismatch, gap, gap_extend,
+                  mode == PWA_MODE_SW, want_end_cells != 0, mode == PWA_MODE_SG, nullptr};
 
     pwa_batch* b = new (std::nothrow) pwa_batch();
     if (!b) return fail(ctx, PWA_E_NOMEM, "host allocation");
@@ -1091,6 +1104,13 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
     b->affine = affine;
     b->nwdist = nwdist;
     b->gotoh = gotoh;
+    if (subst) {   // the batch keeps the table: the caller's arrays are free after this call
+        b->subst.blob.swap(subst->blob);
+        b->subst.n_sym = subst->n_sym;
+        b->subst.stride = subst->stride;
+        b->subst.max_abs = subst->max_abs;
+        in.subst = &b->subst;
+    }
 
     LivePairs lp;
     int rc = scan_pairs(ctx, b, in, lp);
@@ -1117,6 +1137,7 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
         is_text[pair_b[k]] = 1;
         is_used[pair_a[k]] = is_used[pair_b[k]] = 1;
     }
+    if (subst && (rc = subst_upload(ctx, b->subst)) != PWA_OK) return rc;
     const Alphabet al = scan_alphabet(in, is_text);
     CellForm form;
     if ((rc = choose_cell_form(ctx, in, lp, al, form)) != PWA_OK) return rc;
@@ -1312,6 +1333,20 @@ int pwa_gotoh_batch_create(pwa_ctx* ctx, int mode, int match, int mismatch, int 
                            int want_end_cells, pwa_batch** out) {
     return batch_create_impl(ctx, mode, match, mismatch, gap_open, KIND_GOTOH, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
                              want_end_cells, out);
+}
+
+int pwa_subst_batch_create(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                           const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                           uint64_t n_pairs, int want_end_cells, pwa_batch** out) try {
+    if (!ctx || !out) return PWA_E_INVALID;
+    *out = nullptr;
+    SubstTable tab;
+    const int rc = subst_prepare(ctx, code, n_sym, submat, tab);
+    if (rc != PWA_OK) return rc;
+    return batch_create_impl(ctx, mode, 0, 0, gap_open, KIND_SUBST, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, want_end_cells, out,
+                             &tab);
+} catch (const std::bad_alloc&) {
+    return fail(ctx, PWA_E_NOMEM, "host allocation failed");
 }
 
 int pwa_batch_run(pwa_batch* b, void* stream_v) {
@@ -1554,6 +1589,23 @@ int pwa_scores_gotoh(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_op
     return scores_in_arena_chunks(ctx, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, end_i_out, end_j_out,
                                   [&](const uint32_t* a, const uint32_t* b, uint64_t n, pwa_batch** out) {
                                       return pwa_gotoh_batch_create(ctx, mode, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq,
+                                                                    a, b, n, (end_i_out || end_j_out) ? 1 : 0, out);
+                                  });
+}
+
+int pwa_scores_subst(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                     const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                     uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out) {
+    if (!ctx || !score_out) return PWA_E_INVALID;
+    {   // (an empty list creates no batch: the table and the gaps are checked all the same)
+        SubstTable tab;
+        const int rc = subst_prepare(ctx, code, n_sym, submat, tab);
+        if (rc != PWA_OK) return rc;
+        if (gap_open > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
+    }
+    return scores_in_arena_chunks(ctx, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out, end_i_out, end_j_out,
+                                  [&](const uint32_t* a, const uint32_t* b, uint64_t n, pwa_batch** out) {
+                                      return pwa_subst_batch_create(ctx, mode, code, n_sym, submat, gap_open, gap_extend, seq_bytes, seq_off, n_seq,
                                                                     a, b, n, (end_i_out || end_j_out) ? 1 : 0, out);
                                   });
 }

@@ -1,5 +1,5 @@
-// pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_overlaps (the range planner and
-// its stages), pwa_align and pwa_align_matrices.
+// pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_align_subst_batch(_cigar),
+// pwa_overlaps (the range planner and its stages), pwa_align and pwa_align_matrices.
 #include "pwalign_internal.h"
 
 #include <chrono>
@@ -49,6 +49,12 @@ uint64_t str_bound(uint64_t n_plus_m) { return pwa_cigar_bound(n_plus_m) + pwa_m
 struct GotohSpec {
     int gap_open, gap_extend;
 };
+// pwa_align_subst_batch(_cigar): the gotoh classes with the diagonal score from the caller's table (always beside a GotohSpec)
+struct SubstSpec {
+    const uint32_t* d_tab;   // SubstTable::dev
+    int n_sym, stride;
+    int64_t max_abs;         // max |submat|: the range rule's score term
+};
 constexpr uint64_t kGotohMaxN = 1024;   // patterns of the gotoh classes: 16 x kMiniRL rows, then 64 x 8 | 16 rows
 
 // What a call hands back next to the scores: the op lists (pwa_align_batch), the strings the device formats from them
@@ -68,6 +74,7 @@ struct AlignOut {
 struct AlignRequest {
     int mode, match, mismatch, gap;
     const GotohSpec* gt;   // null: linear gaps
+    const SubstSpec* sb;   // null: match / mismatch on raw bytes
     const uint8_t* seq_bytes;
     const uint64_t* seq_off;
     uint32_t n_seq;
@@ -105,10 +112,13 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
     const int rc = check_pair_list(ctx, rq.pair_a, rq.pair_b, rq.n_pairs, rq.n_seq);
     if (rc != PWA_OK || !rq.gt) return rc;
     // the gotoh classes' shape limit, and the range every key of theirs stays exact in
-    const int64_t mx = max_abs({rq.match, rq.mismatch, (int64_t)std::llabs((long long)rq.gt->gap_open) + std::llabs((long long)rq.gt->gap_extend)});
+    const int64_t gaps = (int64_t)std::llabs((long long)rq.gt->gap_open) + std::llabs((long long)rq.gt->gap_extend);
+    const int64_t mx = rq.sb ? std::max(rq.sb->max_abs, gaps) : max_abs({rq.match, rq.mismatch, gaps});
     for (uint64_t k = 0; k < rq.n_pairs; ++k) {
         const uint64_t n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         if (n > kGotohMaxN) return fail(ctx, PWA_E_CAPACITY, "gotoh alignments take patterns of at most 1024 symbols");
+        if (rq.sb && (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)mx >= (long double)(1u << 28)))
+            return fail(ctx, PWA_E_CAPACITY, "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|) must stay below 2^28");
         if (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)mx >= (long double)(1u << 28))
             return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
     }
@@ -484,6 +494,11 @@ int run_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const
     if (rc != PWA_OK) return rc;
     pl.G.dash = ar.dash_sym;
     if (rq.gt) pl.G.gap_extend = rq.gt->gap_extend;
+    if (rq.sb) {
+        pl.subst = rq.sb->d_tab;
+        pl.subst_n_sym = rq.sb->n_sym;
+        pl.subst_stride = rq.sb->stride;
+    }
     clock.mark("task list build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] fill launch %s RL=%d W|LN=%d grid=%u pairs=%u tasks=%u rows=%llu\n", L.cls.mini ? "mini" : "stripes", L.cls.rl,
                                L.cls.w, pl.grid, pl.G.n_pairs, pl.G.n_tasks, (unsigned long long)pl.row_bytes);
@@ -675,7 +690,7 @@ int pwa::selftest_align_plan(uint64_t x, int check) {
         }
         std::vector<uint32_t> pa(n_pairs), pb(n_pairs);
         const GotohSpec gs{-2, -1};
-        AlignRequest rq{PWA_MODE_NW + round % 3, 1, -1, gotoh ? -2 : -1, gotoh ? &gs : nullptr, nullptr, off.data(), n_seq, pa.data(), pb.data(), n_pairs, {}};
+        AlignRequest rq{PWA_MODE_NW + round % 3, 1, -1, gotoh ? -2 : -1, gotoh ? &gs : nullptr, nullptr, nullptr, off.data(), n_seq, pa.data(), pb.data(), n_pairs, {}};
         rq.out.mode = (AlignOutMode)(round / 16);
         if (rq.out.mode == OUT_OVERLAP && rq.semi()) rq.mode = PWA_MODE_NW;
         rq.out.ops_off = ops_off.data();
@@ -750,7 +765,7 @@ int pwa_align_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, co
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
     const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
 }
 
 int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
@@ -759,7 +774,7 @@ int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int g
                           uint64_t* start_cells, uint64_t needed[2]) {
     if (!ctx) return PWA_E_INVALID;
     const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
 }
 
 // the gotoh entry points' own checks; the request comes with gap = gap_open and no GotohSpec yet
@@ -771,13 +786,34 @@ static int gotoh_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend) {
     return align_batch_impl(ctx, rq, ctx->gotoh_stats);
 }
 
+// ... and the substitution-matrix ones': the table is checked, copied and uploaded for the call (the device copy goes back to the
+// context's buffer list when the call returns)
+static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n_sym, const int32_t* submat, int gap_extend) try {
+    if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gap penalties must be <= 0 (gap_open + L * gap_extend)");
+    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    SubstTable tab;
+    int rc = subst_prepare(ctx, code, n_sym, submat, tab);
+    if (rc != PWA_OK) return rc;
+    const GotohSpec gs{rq.gap, gap_extend};
+    SubstSpec ss{nullptr, tab.n_sym, tab.stride, tab.max_abs};
+    rq.gt = &gs;
+    rq.sb = &ss;
+    if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (before anything is allocated; align_batch_impl checks again)
+    HIPC(ctx, hipSetDevice(ctx->device));
+    if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
+    ss.d_tab = tab.dev.as<uint32_t>();
+    return align_batch_impl(ctx, rq, ctx->subst_stats);
+} catch (const std::bad_alloc&) {
+    return fail(ctx, PWA_E_NOMEM, "host allocation failed");
+}
+
 int pwa_align_gotoh_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
                           const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
                           int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
     const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
+    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
 }
 
 int pwa_align_gotoh_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
@@ -786,7 +822,7 @@ int pwa_align_gotoh_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch,
                                 uint64_t* mdz_off, uint64_t* end_cells, uint64_t* start_cells, uint64_t needed[2]) {
     if (!ctx) return PWA_E_INVALID;
     const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
+    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
 }
 
 static int put_stats(const AlignStats& st, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
@@ -800,13 +836,39 @@ int pwa_align_gotoh_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_m
     return ctx ? put_stats(ctx->gotoh_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
 }
 
+int pwa_align_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                          const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                          uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
+                          uint64_t* start_cells) {
+    if (!ctx) return PWA_E_INVALID;
+    if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
+    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
+    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
+                       gap_extend);
+}
+
+int pwa_align_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                                const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
+                                const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar, uint64_t cigar_cap,
+                                uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
+                                uint64_t* start_cells, uint64_t needed[2]) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
+    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
+                       gap_extend);
+}
+
+int pwa_align_subst_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
+    return ctx ? put_stats(ctx->subst_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+}
+
 int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
                  uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out,
                  int32_t* overlap_out) {
     if (!ctx) return PWA_E_INVALID;
     if (!overlap_out) return fail(ctx, PWA_E_INVALID, "null input");
     const AlignOut out{OUT_OVERLAP, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, overlap_out, {}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
 }
 
 int pwa_align(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* pattern, uint64_t n,

@@ -17,6 +17,10 @@ namespace pwa {
 void (*gotoh_fill_kernel_for(int rl, int mode, int ln))(const PairParams);
 void (*gotoh_walk_kernel_for(int rl, int mode, int ln))(const PairParams);
 void (*gotoh_scores_kernel_for(int rl, int mode, int ln))(const PairParams);   // the fills without a band (no walk follows)
+// subst_kernels.hip: the same classes and modes under a substitution table (device blob, n_sym, row stride); the walk is gotoh's
+typedef void (*subst_kernel_t)(const PairParams, const uint32_t*, int, int);
+subst_kernel_t subst_fill_kernel_for(int rl, int mode, int ln);
+subst_kernel_t subst_scores_kernel_for(int rl, int mode, int ln);
 }
 
 __global__ void pwa_nop_kernel(int* p) {
@@ -493,6 +497,8 @@ int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_r
 int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband) {
     HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
     if (mini) {
+        const subst_kernel_t sfill = !subst || gotoh < 0 ? nullptr : gotoh_scores ? subst_scores_kernel_for(geom.rl, gotoh, mini_ln) : subst_fill_kernel_for(geom.rl, gotoh, mini_ln);
+        if (subst && !sfill) return fail(ctx, PWA_E_INVALID, "internal: no substitution-matrix kernel for this form");
         const pair_kernel_t fill = gotoh >= 0 ? (gotoh_scores ? gotoh_scores_kernel_for(geom.rl, gotoh, mini_ln) : gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln))
                                               : mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
         const pair_kernel_t walk_fn = gotoh >= 0 ? gotoh_walk_kernel_for(geom.rl, gotoh, mini_ln)
@@ -507,11 +513,14 @@ int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int wa
         const uint32_t cap_per_cu = ctx->knobs.mini_per_cu > 0 ? (uint32_t)std::min(ctx->knobs.mini_per_cu, 5) : (tb ? 2u : 4u);
         const uint32_t per_cu = std::min<uint32_t>(cap_per_cu, (n_wg + (uint32_t)ctx->num_cu - 1) / (uint32_t)ctx->num_cu);
         static const uint32_t kPadKiB[6] = {0, 96, 64, 48, 36, 30};   // more than 160 KiB / (per_cu + 1), at most 160 KiB / per_cu
-        const size_t pad_lds = (size_t)kPadKiB[per_cu] * 1024;
-        HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+        // (the subst fills hold 4.25 KiB of LDS of their own: 5 KiB less padding keeps every per_cu inside the same two bounds)
+        const size_t pad_lds = (size_t)(kPadKiB[per_cu] - (sfill ? 5 : 0)) * 1024;
+        HIPC(ctx, hipFuncSetAttribute(sfill ? reinterpret_cast<const void*>(sfill) : reinterpret_cast<const void*>(fill),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
         const uint32_t g = std::min<uint32_t>(n_wg, (uint32_t)ctx->num_cu * per_cu);
         if (ctx->knobs.debug) std::fprintf(stderr, "[pwa] mini fill: %u tasks, %u workgroups of %d waves, %u per CU (%zu KiB of LDS each)\n", G.n_tasks, g, kMiniWaves, per_cu, pad_lds >> 10);
-        hipLaunchKernelGGL(fill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G);
+        if (sfill) hipLaunchKernelGGL(sfill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G, subst, subst_n_sym, subst_stride);
+        else hipLaunchKernelGGL(fill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G);
         HIPC(ctx, hipGetLastError());
         if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
         if (gotoh_scores) return PWA_OK;
@@ -587,6 +596,34 @@ int PairLaunch::check(pwa_ctx* ctx) {
     uint32_t q[2] = {0, 0};
     HIPC(ctx, hipMemcpy(q, p_queue, sizeof q, hipMemcpyDeviceToHost));
     if (q[1] != 0) return fail(ctx, PWA_E_HIP, "stripe pipeline timed out waiting for the stripe above");
+    return PWA_OK;
+}
+
+// A caller's substitution table, checked and laid out for the device: codes < n_sym for all 256 bytes, n_sym in 1 .. 32.  The table is
+// stored with the text code as the row (a lane adds its pattern rows' offsets to one row address per step); the row stride is odd below
+// 32 symbols, so that the rows of a small alphabet start in different LDS banks, and never more than 32 (4 KiB in all).
+int subst_prepare(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, SubstTable& t) {
+    if (!code || !submat) return fail(ctx, PWA_E_INVALID, "null input");
+    if (n_sym < 1 || n_sym > kSubstMaxSym) return fail(ctx, PWA_E_INVALID, "n_sym must be 1 .. 32");
+    for (int v = 0; v < 256; ++v)
+        if (code[v] >= n_sym) return fail(ctx, PWA_E_INVALID, "code map: every one of the 256 entries must be below n_sym");
+    t.n_sym = n_sym;
+    t.stride = std::min(n_sym | 1, kSubstMaxSym);
+    t.blob.assign((size_t)kSubstMapWords + kSubstTabWords, 0u);
+    std::memcpy(t.blob.data(), code, 256);
+    t.max_abs = 0;
+    for (int cp = 0; cp < n_sym; ++cp)
+        for (int ct = 0; ct < n_sym; ++ct) {
+            const int32_t s = submat[cp * n_sym + ct];
+            t.blob[(size_t)kSubstMapWords + (size_t)ct * t.stride + cp] = (uint32_t)s;
+            t.max_abs = std::max<int64_t>(t.max_abs, std::llabs((long long)s));
+        }
+    return PWA_OK;
+}
+int subst_upload(pwa_ctx* ctx, SubstTable& t) {
+    t.dev.pool = ctx;
+    HIPC(ctx, t.dev.alloc(t.blob.size() * sizeof(uint32_t)));
+    HIPC(ctx, upload_via_bounce(ctx, t.dev.p, t.blob.data(), t.blob.size() * sizeof(uint32_t)));
     return PWA_OK;
 }
 

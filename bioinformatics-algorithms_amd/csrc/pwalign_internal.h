@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kernel_table.h"
+#include "subst_table.h"
 
 // Host-side source / destination of the library's own host <-> device copies: page-locked, grow-only, kept in the context.
 // hipMemcpy from a short-lived pageable vector works, but the runtime registers its pages with the driver for the DMA, and
@@ -102,6 +103,7 @@ struct pwa_ctx {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     std::string err;
     AlignStats align_stats, gotoh_stats;   // the last pwa_align_batch / _cigar / pwa_overlaps, the last pwa_align_gotoh_batch(_cigar)
+    AlignStats subst_stats;                // the last pwa_align_subst_batch(_cigar)
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
@@ -155,7 +157,18 @@ struct DevBuf {   // RAII device allocation; with `pool` set, released buffers g
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// A caller's substitution table (include/pwalign.h, pwa_align_subst_batch) as the subst kernels read it (subst_fill.hip.h): the
+// 256-byte code map, then n_sym rows of `stride` raw scores with the TEXT code as the row; max_abs = max |submat|
+struct SubstTable {
+    std::vector<uint32_t> blob;
+    int n_sym = 0, stride = 0;
+    int64_t max_abs = 0;
+    DevBuf dev;   // the blob on the device (subst_upload)
+};
+
 // ---- defined in pwalign_ctx.hip (the comments are at the definitions)
+int subst_prepare(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, SubstTable& t);
+int subst_upload(pwa_ctx* ctx, SubstTable& t);
 void radix_sort_by_key(std::vector<uint64_t>& key, std::vector<uint32_t>& idx);
 void scan_bytes(const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const std::vector<uint8_t>& in, bool out[256],
                 uint64_t bytes_per_thread);
@@ -292,6 +305,8 @@ struct PairLaunch {
     bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
     int gotoh = -1;      // >= 0 (a PWA_MODE_*): the affine-gap mini-stripe kernels (gotoh_fill.hip.h); build_mini takes gap_open as gap
     bool gotoh_scores = false;   // ... their band-less form (gotoh_scores_kernel): score and end cell from the fill itself, no walk
+    const uint32_t* subst = nullptr;   // ... with gotoh >= 0: the device table of the substitution-matrix fills (subst_fill.hip.h) in their place
+    int subst_n_sym = 0, subst_stride = 0;
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;

@@ -379,6 +379,53 @@ int pwa_scores_gotoh(pwa_ctx *ctx, int mode, int match, int mismatch, int gap_op
                      int32_t *score_out, uint32_t *end_i_out, uint32_t *end_j_out);
 
 /*
+ * Substitution-matrix scoring for the affine-gap ("gotoh") calls: alignments (op lists, or CIGAR + MD:Z), batch objects and one-call
+ * scores.  The semantics are exactly those of the comment block of pwa_align_gotoh_batch above -- recurrences for E / F / H, a tie
+ * opens, the H tie-breaks per mode, boundaries, end cells, the three-state walk and its op bytes, the conventions for pairs with an
+ * empty side, gap_open <= 0 and gap_extend <= 0 (else PWA_E_INVALID; gap_open = 0 gives linear gaps) -- with one substitution:
+ *   s(i,j) = submat[ code[p[i-1]] * n_sym + code[t[j-1]] ]
+ *   code    uint8_t[256], byte value -> symbol code.  Every one of the 256 entries must be < n_sym, else PWA_E_INVALID: the caller
+ *           decides where unknown bytes, lower case, NUL and '-' go (a wildcard code with a row and a column of its own, say).
+ *   n_sym   1 .. 32, else PWA_E_INVALID.
+ *   submat  int32_t[n_sym * n_sym], row = pattern code, column = text code.  It may be asymmetric and may hold any signs, positive
+ *           off-diagonal entries in PWA_MODE_SW included.
+ * code and submat are copied during the call (a batch object keeps its own copy): the caller may free them afterwards.  A null code or
+ * submat is PWA_E_INVALID.  No named matrix (BLOSUM, PAM) ships with the library: the caller supplies the numbers.
+ * CIGAR and MD:Z are built from the ops and the RAW bytes, as in every other call: MD:Z reports BYTE IDENTITY, not the sign of the
+ * score.  'a' against 'A', mapped to one code and scored as a match, is an 'M' column that MD:Z lists as a mismatch.
+ * Range: every result is exact while (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|) < 2^28; a pair beyond that is
+ * PWA_E_CAPACITY.  Shape: patterns of at most 1024 symbols, else PWA_E_CAPACITY -- for the alignments AND for the scores (there is no
+ * strip form).  An empty pair list is PWA_OK.
+ *   pwa_align_subst_batch        pwa_align_gotoh_batch's arguments and outputs, (code, n_sym, submat) in place of (match, mismatch);
+ *   pwa_align_subst_batch_cigar  likewise pwa_align_gotoh_batch_cigar's (too small a buffer: PWA_E_CAPACITY with the exact needed[]);
+ *   pwa_subst_batch_create       a batch object like pwa_gotoh_batch_create's (pwa_batch_run / _d_scores / _set_d_scores / _fetch /
+ *                                _info / _last_ms / _run_times / _destroy); pwa_batch_cell_bits and pwa_batch_profile_form are 0;
+ *   pwa_scores_subst             the one-call form over lists of any size, as pwa_scores_gotoh; end cells when end_i_out or end_j_out
+ *                                is given;
+ *   pwa_align_subst_last_stats   device ms of the fills and walks of the last pwa_align_subst_batch(_cigar) on ctx, and their band
+ *                                bytes (the gotoh and linear figures are kept apart).
+ */
+int pwa_align_subst_batch(pwa_ctx *ctx, int mode /* NW, SW, SG */, const uint8_t code[256], int n_sym, const int32_t *submat,
+                          int gap_open, int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                          const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops,
+                          const uint64_t *ops_off, uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */,
+                          uint64_t *start_cells /* 2*n_pairs or NULL */);
+int pwa_align_subst_batch_cigar(pwa_ctx *ctx, int mode, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                                int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                                uint64_t needed[2] /* or NULL */);
+int pwa_subst_batch_create(pwa_ctx *ctx, int mode, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                           int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                           const uint32_t *pair_b, uint64_t n_pairs, int want_end_cells, pwa_batch **out);
+int pwa_scores_subst(pwa_ctx *ctx, int mode, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open, int gap_extend,
+                     const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                     uint64_t n_pairs, int32_t *score_out, uint32_t *end_i_out, uint32_t *end_j_out);
+int pwa_align_subst_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
+
+/*
  * The -g selection without the op lists: hw2.cpp:342-350 keeps, of every pair's global alignment, only
  * overlapLongestExactMatch(alignedPattern, alignedReference) (hw2.cpp:267-278) and the score.  Same fill and
  * traceback band as pwa_align_batch; the device walk looks at the symbols under each run of diagonal moves
