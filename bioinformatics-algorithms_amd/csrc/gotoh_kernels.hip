@@ -19,17 +19,7 @@ static gotoh_kernel_t gotoh_pick(int mode, int walk) {
 }
 
 static gotoh_kernel_t gotoh_kernel_for(int rl, int mode, int ln, int walk) {
-    if (ln == 64) return rl == 8 ? gotoh_pick<8, 64>(mode, walk) : rl == 16 ? gotoh_pick<16, 64>(mode, walk) : nullptr;
-    if (ln != 16) return nullptr;
-    switch (rl) {
-        case 4: return gotoh_pick<4, 16>(mode, walk);
-        case 6: return gotoh_pick<6, 16>(mode, walk);
-        case 8: return gotoh_pick<8, 16>(mode, walk);
-        case 10: return gotoh_pick<10, 16>(mode, walk);
-        case 12: return gotoh_pick<12, 16>(mode, walk);
-        case 16: return gotoh_pick<16, 16>(mode, walk);
-        default: return nullptr;
-    }
+    return gotoh_for_class(rl, ln, [&](auto rlc, auto lnc) { return gotoh_pick<decltype(rlc)::value, decltype(lnc)::value>(mode, walk); });
 }
 
 gotoh_kernel_t gotoh_fill_kernel_for(int rl, int mode, int ln) { return gotoh_kernel_for(rl, mode, ln, GK_FILL); }

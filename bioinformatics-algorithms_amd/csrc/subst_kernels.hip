@@ -14,17 +14,7 @@ static subst_kernel_t subst_pick(int mode, bool band) {
 }
 
 static subst_kernel_t subst_kernel_for(int rl, int mode, int ln, bool band) {
-    if (ln == 64) return rl == 8 ? subst_pick<8, 64>(mode, band) : rl == 16 ? subst_pick<16, 64>(mode, band) : nullptr;
-    if (ln != 16) return nullptr;
-    switch (rl) {
-        case 4: return subst_pick<4, 16>(mode, band);
-        case 6: return subst_pick<6, 16>(mode, band);
-        case 8: return subst_pick<8, 16>(mode, band);
-        case 10: return subst_pick<10, 16>(mode, band);
-        case 12: return subst_pick<12, 16>(mode, band);
-        case 16: return subst_pick<16, 16>(mode, band);
-        default: return nullptr;
-    }
+    return gotoh_for_class(rl, ln, [&](auto rlc, auto lnc) { return subst_pick<decltype(rlc)::value, decltype(lnc)::value>(mode, band); });
 }
 
 subst_kernel_t subst_fill_kernel_for(int rl, int mode, int ln) { return subst_kernel_for(rl, mode, ln, true); }
