@@ -381,7 +381,8 @@ __device__ __forceinline__ void scores16_body(const BatchParams& P) {
 // Boundary row and column are 0, pad rows and pad columns take s' = 0 (s = g: they only decay; their m never exceeds a real
 // cell's).  s' <= 254 is one byte: a profile register is one v_perm from the code's 4-byte table, the high byte of each half 0x00.
 // The 8 adds issue at the full rate, the other 20 of the row step's 28 at the packed rate ([gpu] tools/valu_issue.hip, row
-// "SW pk16 profile C=8 int"; that row has no v_mov, the kernel keeps the row's v_mov of the block's last H: DESIGN.md r05).
+// "SW pk16 profile C=8 int").  The kernel's own shape -- no v_mov, the last column's subtract deferred into the next row's step -- is
+// that tool's row "... int nomove" (DESIGN.md r05, r06).  Neither row runs the pad rows past the pattern's length rounded up to a pair of rows.
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
 template <int R, bool INT>
@@ -469,56 +470,186 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
             uint32_t u[C];
 #pragma unroll
             for (int k = 0; k < C; ++k) u[k] = edge;
-            uint32_t dprev = edge;
+            if constexpr (INT) {
+                // The move-free row, two rows to an asm text.  The last column's subtract of a row is deferred into the next row's
+                // step (pend = its m, still due): row r first reads the OLD col[r - 1] as its diagonal, then the deferred subtract
+                // writes col[r - 1] in place, and the row's last column takes it as "up".  Row 0 has neither (its diagonal and its
+                // last "up" are the boundary's 0).  28 VALU per row, no v_mov.
+                // Pad rows are not run: a pair whose first row is past the pattern's end (its profile offset is 32 = the pad code
+                // 4 x 8, exactly the rows r >= n; wave-uniform) branches over the rest of its text, so a task runs n rounded up to
+                // 2 rows.  The test sits behind the pair's first adds and the deferred subtract, so the rows that run pay one s_cmp
+                // and a not-taken branch per pair and no taken branch, and the first skipped pair has thereby done the pending
+                // subtract of the last row that ran; a later skipped pair writes the col of a pad row, which no real row reads
+                // (each costs 9 VALU and a taken branch instead of 56).  A branch in the C++ loop instead (an exit per pair) makes
+                // the compiler copy u[] and best[] at every exit: 11 v_mov per pair.
+                static_assert(R % 2 == 0, "the integer row runs its rows in pairs");
+                uint32_t pend = 0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                // the row's profile offset on the scalar unit, right before its row step (left to the compiler, all 152 are
-                // computed ahead and spill to VGPR lanes: one v_readlane_b32 per row)
-                uint32_t idx;
-                asm volatile("s_bfe_u32 %0, %1, %2" : "=s"(idx) : "s"(pw[r >> 2]), "i"((8 * (r & 3)) | (8 << 16)) : "scc");
-                const uint32_t left = col[r];
-                uint32_t t[C];
-                if constexpr (INT) {
+                for (int r = 0; r < R; r += 2) {
+                    uint32_t t[C], i0, i1;
+                    if (r == 0) {
+                        asm volatile(
+                            "s_bfe_u32 %[i0], %[pw], %[f0]\n\t"
+                            "s_set_gpr_idx_on %[i0], gpr_idx(SRC1)\n\t"
+                            "v_add_u32 %[t0], 0, v216\n\t"
+                            "v_add_u32 %[t1], %[u0], v217\n\t"
+                            "v_add_u32 %[t2], %[u1], v218\n\t"
+                            "v_add_u32 %[t3], %[u2], v219\n\t"
+                            "v_add_u32 %[t4], %[u3], v220\n\t"
+                            "v_add_u32 %[t5], %[u4], v221\n\t"
+                            "v_add_u32 %[t6], %[u5], v222\n\t"
+                            "v_add_u32 %[t7], %[u6], v223\n\t"
+                            "s_set_gpr_idx_off\n\t"
+                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[c0]\n\t"
+                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[pd], %[t7], 0, %[u6]\n\t"
+                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n\t"
+                            "s_bfe_u32 %[i1], %[pw], %[f1]\n\t"
+                            "s_set_gpr_idx_on %[i1], gpr_idx(SRC1)\n\t"
+                            "v_add_u32 %[t0], %[c0], v216\n\t"
+                            "v_add_u32 %[t1], %[u0], v217\n\t"
+                            "v_add_u32 %[t2], %[u1], v218\n\t"
+                            "v_add_u32 %[t3], %[u2], v219\n\t"
+                            "v_add_u32 %[t4], %[u3], v220\n\t"
+                            "v_add_u32 %[t5], %[u4], v221\n\t"
+                            "v_add_u32 %[t6], %[u5], v222\n\t"
+                            "v_add_u32 %[t7], %[u6], v223\n\t"
+                            "s_set_gpr_idx_off\n\t"
+                            "v_pk_sub_u16 %[c0], %[pd], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l1]\n\t"
+                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[pd], %[t7], %[c0], %[u6]\n\t"
+                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]"
+                            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
+                              [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [i0] "=&s"(i0), [i1] "=&s"(i1), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]),
+                              [u3] "+v"(u[3]), [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
+                              [b2] "+v"(best[2]), [b3] "+v"(best[3]), [pd] "+v"(pend), [c0] "+v"(col[r])
+                            : [l1] "v"(col[r + 1 < R ? r + 1 : r]), [pw] "s"(pw[r >> 2]), [f0] "i"((8 * (r & 3)) | (8 << 16)), [f1] "i"((8 * ((r + 1) & 3)) | (8 << 16)),
+                              [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                            : "m0", "scc");
+                    } else {
+                        asm volatile(
+                            "s_bfe_u32 %[i0], %[pw], %[f0]\n\t"
+                            "s_set_gpr_idx_on %[i0], gpr_idx(SRC1)\n\t"
+                            "v_add_u32 %[t0], %[cp], v216\n\t"
+                            "v_add_u32 %[t1], %[u0], v217\n\t"
+                            "v_add_u32 %[t2], %[u1], v218\n\t"
+                            "v_add_u32 %[t3], %[u2], v219\n\t"
+                            "v_add_u32 %[t4], %[u3], v220\n\t"
+                            "v_add_u32 %[t5], %[u4], v221\n\t"
+                            "v_add_u32 %[t6], %[u5], v222\n\t"
+                            "v_add_u32 %[t7], %[u6], v223\n\t"
+                            "s_set_gpr_idx_off\n\t"
+                            "v_pk_sub_u16 %[cp], %[pd], %[g] clamp\n\t"
+                            "s_cmp_eq_u32 %[i0], 32\n\t"
+                            "s_cbranch_scc1 .Lpad%=\n\t"
+                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[c0]\n\t"
+                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[pd], %[t7], %[cp], %[u6]\n\t"
+                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n\t"
+                            "s_bfe_u32 %[i1], %[pw], %[f1]\n\t"
+                            "s_set_gpr_idx_on %[i1], gpr_idx(SRC1)\n\t"
+                            "v_add_u32 %[t0], %[c0], v216\n\t"
+                            "v_add_u32 %[t1], %[u0], v217\n\t"
+                            "v_add_u32 %[t2], %[u1], v218\n\t"
+                            "v_add_u32 %[t3], %[u2], v219\n\t"
+                            "v_add_u32 %[t4], %[u3], v220\n\t"
+                            "v_add_u32 %[t5], %[u4], v221\n\t"
+                            "v_add_u32 %[t6], %[u5], v222\n\t"
+                            "v_add_u32 %[t7], %[u6], v223\n\t"
+                            "s_set_gpr_idx_off\n\t"
+                            "v_pk_sub_u16 %[c0], %[pd], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l1]\n\t"
+                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
+                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
+                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
+                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
+                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
+                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
+                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
+                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
+                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
+                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
+                            "v_pk_maximum3_f16 %[pd], %[t7], %[c0], %[u6]\n\t"
+                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n"
+                            ".Lpad%=:"
+                            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
+                              [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [i0] "=&s"(i0), [i1] "=&s"(i1), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]),
+                              [u3] "+v"(u[3]), [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
+                              [b2] "+v"(best[2]), [b3] "+v"(best[3]), [pd] "+v"(pend), [c0] "+v"(col[r]), [cp] "+v"(col[r > 0 ? r - 1 : 0])
+                            : [l1] "v"(col[r + 1 < R ? r + 1 : r]), [pw] "s"(pw[r >> 2]), [f0] "i"((8 * (r & 3)) | (8 << 16)), [f1] "i"((8 * ((r + 1) & 3)) | (8 << 16)),
+                              [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                            : "m0", "scc");
+                    }
+                }
+                // the last row's pending subtract, when no pair was skipped (otherwise col[R - 1] is a pad row's)
+                asm volatile("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(col[R - 1]) : "v"(pend), "s"(g));
+            } else {
+                // the f16 row keeps its per-row v_mov of the block's last G; it skips the same pairs of pad rows, row by row
+                uint32_t dprev = edge, tst = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    // the row's profile offset on the scalar unit, right before its row step (left to the compiler, all 152 are
+                    // computed ahead and spill to VGPR lanes: one v_readlane_b32 per row)
+                    uint32_t idx;
+                    asm volatile("s_bfe_u32 %0, %1, %2" : "=s"(idx) : "s"(pw[r >> 2]), "i"((8 * (r & 3)) | (8 << 16)) : "scc");
+                    if ((r & 1) == 0) tst = idx;   // rows 2k and 2k + 1 go by row 2k's offset, rows 0 and 1 always run (33: no offset)
+                    const uint32_t left = col[r];
+                    uint32_t t[C];
                     asm volatile(
-                        "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
-                        "v_add_u32 %[t0], %[d], v216\n\t"
-                        "v_add_u32 %[t1], %[u0], v217\n\t"
-                        "v_add_u32 %[t2], %[u1], v218\n\t"
-                        "v_add_u32 %[t3], %[u2], v219\n\t"
-                        "v_add_u32 %[t4], %[u3], v220\n\t"
-                        "v_add_u32 %[t5], %[u4], v221\n\t"
-                        "v_add_u32 %[t6], %[u5], v222\n\t"
-                        "v_add_u32 %[t7], %[u6], v223\n\t"
-                        "s_set_gpr_idx_off\n\t"
-                        "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l]\n\t"
-                        "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                        "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                        "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                        "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                        "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                        "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                        "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                        "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                        "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                        "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
-                        "v_pk_sub_u16 %[u7], %[t7], %[g] clamp\n\t"
-                        "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
-                        : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
-                          [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
-                          [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
-                          [b2] "+v"(best[2]), [b3] "+v"(best[3])
-                        : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
-                          "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
-                        : "m0", "scc");
-                } else {
-                    asm volatile(
+                        "s_cmp_eq_u32 %[tst], %[pc]\n\t"
+                        "s_cbranch_scc1 .Lpad%=\n\t"
                         "s_set_gpr_idx_on %[idx], gpr_idx(SRC1)\n\t"
                         "v_pk_add_f16 %[t0], %[d], v216 clamp\n\t"
                         "v_pk_add_f16 %[t1], %[u0], v217 clamp\n\t"
@@ -548,17 +679,18 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
                         "v_pk_add_f16 %[u6], %[t6], %[g]\n\t"
                         "v_pk_maximum3_f16 %[t7], %[t7], %[u7], %[u6]\n\t"
                         "v_pk_add_f16 %[u7], %[t7], %[g]\n\t"
-                        "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]"
+                        "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[t7]\n"
+                        ".Lpad%=:"
                         : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
                           [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]), [u3] "+v"(u[3]),
                           [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [u7] "+v"(u[7]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
                           [b2] "+v"(best[2]), [b3] "+v"(best[3])
-                        : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1),
-                          "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+                        : [d] "v"(dprev), [l] "v"(left), [idx] "s"(idx), [tst] "s"(tst), [pc] "i"(r < 2 ? 33 : 32), [g] "s"(g),
+                          "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
                         : "m0", "scc");
+                    dprev = left;
+                    col[r] = u[C - 1];
                 }
-                dprev = left;
-                col[r] = u[C - 1];
             }
         }
         const uint32_t out_a = P.slot_out[slot_a], out_b = P.slot_out[slot_b];   // (read here: no VGPRs held over the column loop)

@@ -57,11 +57,17 @@ namespace {
 // Packed f16 strip cells (batch_scores.hip.h, CELL16): VALU per lane row and column, both pairs together -- perm, pk_add,
 // pk_maximum3, pk_add clamp, 1/2 pk_maximum3 for the running best, + the hand-off share ([gpu] PMC on C3: 4.56)
 constexpr double kCell16Vpr = 4.6;
-// The profile form (PROF16): 3.5 VALU per lane row -- indexed pk_add clamp, pk_maximum3, pk_add, 1/2 pk_maximum3 -- + the row's
+// The profile form (PROF16): 3.5 VALU per lane row -- indexed pk_add clamp, pk_maximum3, pk_add, 1/2 pk_maximum3 -- + the f16 row's
 // v_mov and the per-block profile ([gpu] tools/valu_issue.hip: 6.43 against CELL16's 7.62 cycles per cell at two waves per SIMD;
-// its integer-coded row 6.00 in the same table: the same instruction count, priced alike)
+// its integer-coded row 6.00 in the same table).  The integer row has had no v_mov since r06; the figure was fitted before that and
+// has not been re-fitted, so both rows are still priced alike.
 constexpr double kProf16Vpr = 3.8;
-constexpr int kProf16R = 152;   // the rows of its single strip (batch_scores16p_kernel<152>)
+constexpr int kProf16R = 152;   // the rows of its single strip (batch_scores16p_kernel<152>): the admission limit
+// ... and the rows a task of an n-row pattern runs: the kernel skips the pad rows past n rounded up to a pair of rows.  Skipped rows
+// are priced as nothing, which is a little low: per 8-column block a skipped pair of the integer row still issues 9 VALU (of a pair's
+// 56), 2 scalar instructions and a taken branch, a skipped f16 row 3 scalar instructions, a taken branch and its v_mov.  For 100-row
+// patterns that is 26 pairs, ~230 VALU against ~2800 of the rows that run (about 8 %); DESIGN.md r06 has the measured times.
+constexpr uint64_t prof16_rows(uint64_t n) { return n <= 2 ? 2 : (n + 1) / 2 * 2; }
 // f16 bit pattern of k * 2^-11 for |k| <= 1023: a normal number (exponent k's leading bit + 4), exact
 uint32_t f16_bits_scaled(int k) {
     if (k == 0) return 0;
@@ -504,7 +510,7 @@ std::vector<HostTask> group_by_pattern(const BatchInput& in, std::vector<uint32_
 
 long double prof16_cost(const std::vector<HostTask>& tl) {   // in choose_strip_height's units
     long double cost = 0;
-    for (const auto& t : tl) cost += (long double)kProf16R * (long double)((t.m + 7) / 8 * 8) * 64.0L;
+    for (const auto& t : tl) cost += (long double)prof16_rows(t.maxlen) * (long double)((t.m + 7) / 8 * 8) * 64.0L;
     return cost * (long double)kProf16Vpr;
 }
 
@@ -725,7 +731,7 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
     const uint64_t kTaskLanes = b->cell16 ? 128 : 64;   // lane slots per wave task
     const bool own_texts = b->lanes || b->prof16;   // per-slot text arrays
     for (const auto& t : ht)
-        b->padded_cells += b->prof16 ? (uint64_t)kProf16R * ((t.m + 7) / 8 * 8) * kTaskLanes
+        b->padded_cells += b->prof16 ? prof16_rows(t.maxlen) * ((t.m + 7) / 8 * 8) * kTaskLanes
                                      : (t.maxlen + R - 1) / R * R * (b->lanes ? (t.m + 3) / 4 * 4 : t.m) * kTaskLanes;
     b->kern = find_batch_kernel(R, kmode, f.score_path);
     if (!b->kern) return fail(ctx, PWA_E_INVALID, "internal: no kernel instantiation");

@@ -148,6 +148,17 @@ OPP(k_prof4, "s_add_u32 %0, %0, 4\n\ts_and_b32 %0, %0, 15\n\ts_set_gpr_idx_on %0
 // for both halves), 8 max3, 8 v_pk_sub_u16 clamp, 4 best max3; no v_mov -- the last column's subtract writes the row's col register, which
 // the next row reads as its column-7 up (two row steps per asm text, v101 / v107 alternating as col[r] / col[r + 1])
 OPP(k_prof8i, "s_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v100, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v101\n\tv_pk_sub_u16 v72, v88, v102 clamp\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_sub_u16 v73, v89, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_sub_u16 v74, v90, v102 clamp\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_sub_u16 v75, v91, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_pk_maximum3_f16 v92, v84, v76, v75\n\tv_pk_sub_u16 v76, v92, v102 clamp\n\tv_pk_maximum3_f16 v93, v85, v77, v76\n\tv_pk_sub_u16 v77, v93, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v92, v93\n\tv_pk_maximum3_f16 v94, v86, v78, v77\n\tv_pk_sub_u16 v78, v94, v102 clamp\n\tv_pk_maximum3_f16 v95, v87, v107, v78\n\tv_pk_sub_u16 v101, v95, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v94, v95\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v100, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_maximum3_f16 v88, v80, v72, v107\n\tv_pk_sub_u16 v72, v88, v102 clamp\n\tv_pk_maximum3_f16 v89, v81, v73, v72\n\tv_pk_sub_u16 v73, v89, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v88, v89\n\tv_pk_maximum3_f16 v90, v82, v74, v73\n\tv_pk_sub_u16 v74, v90, v102 clamp\n\tv_pk_maximum3_f16 v91, v83, v75, v74\n\tv_pk_sub_u16 v75, v91, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v90, v91\n\tv_pk_maximum3_f16 v92, v84, v76, v75\n\tv_pk_sub_u16 v76, v92, v102 clamp\n\tv_pk_maximum3_f16 v93, v85, v77, v76\n\tv_pk_sub_u16 v77, v93, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v92, v93\n\tv_pk_maximum3_f16 v94, v86, v78, v77\n\tv_pk_sub_u16 v78, v94, v102 clamp\n\tv_pk_maximum3_f16 v95, v87, v101, v78\n\tv_pk_sub_u16 v107, v95, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v94, v95")
+// the integer row in the kernel's true shape (batch_scores.hip.h, INT = true): the last column's subtract is deferred into the next row's step
+// and writes the row's col register in place after the next row has read it as its diagonal (v101 = the pending m), two rows to a kernel asm
+// text with the pad test (s_cmp + a never-taken branch) behind the pair's first adds.  Two pairs per text here: the col registers
+// v96..v99 stand for col[r - 1 .. r + 2] and come round after four rows, which 152 distinct registers do not need to.
+OPP(k_prof8n, "s_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v99, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v99, v101, v102 clamp\n\ts_cmp_eq_u32 %0, 32\n\ts_cbranch_scc1 .Lpad%=\n\tv_pk_maximum3_f16 v80, v80, v72, v96\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v99, v78\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v96, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v96, v101, v102 clamp\n\tv_pk_maximum3_f16 v80, v80, v72, v97\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v96, v78\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\t.Lpad%=:\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v97, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v97, v101, v102 clamp\n\ts_cmp_eq_u32 %0, 32\n\ts_cbranch_scc1 .Lpbd%=\n\tv_pk_maximum3_f16 v80, v80, v72, v98\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v97, v78\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v80, v98, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v98, v101, v102 clamp\n\tv_pk_maximum3_f16 v80, v80, v72, v99\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v98, v78\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\t.Lpbd%=:")
+// ... and the same row split into two independent half-chains ("skew"): a step runs row r's columns 4..7 against row r + 1's columns
+// 0..3, interleaved instruction by instruction, so the dependent chain is 8 long instead of 16.  All eight adds sit under one
+// s_set_gpr_idx_on, row r's three (columns 5..7) first, then s_set_gpr_idx_idx to row r + 1's offset for its four and for column 4's add
+// of the NEXT step (it needs H(r, 3) before row r + 1 overwrites it: one more live register, v84 / v88 alternating).  28 VALU per step
+// of 16 cells as the nomove row, the same two scalar instructions per row and the same pad test per two rows; four steps per text.
+OPP(k_prof8s, "s_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_idx %0\n\tv_add_u32 v80, v96, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v88, v75, v36\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v99, v101, v102 clamp\n\ts_cmp_eq_u32 %0, 32\n\ts_cbranch_scc1 .Lskw0_%=\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_maximum3_f16 v80, v80, v72, v97\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v99, v78\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\t.Lskw0_%=:\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_idx %0\n\tv_add_u32 v80, v97, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v96, v101, v102 clamp\n\tv_pk_maximum3_f16 v88, v88, v76, v75\n\tv_pk_maximum3_f16 v80, v80, v72, v98\n\tv_pk_sub_u16 v76, v88, v102 clamp\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v88, v85\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v96, v78\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_idx %0\n\tv_add_u32 v80, v98, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v88, v75, v36\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v97, v101, v102 clamp\n\ts_cmp_eq_u32 %0, 32\n\ts_cbranch_scc1 .Lskw2_%=\n\tv_pk_maximum3_f16 v84, v84, v76, v75\n\tv_pk_maximum3_f16 v80, v80, v72, v99\n\tv_pk_sub_u16 v76, v84, v102 clamp\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v84, v85\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v97, v78\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\tv_pk_maximum3_f16 v104, v104, v82, v83\n\t.Lskw2_%=:\n\ts_set_gpr_idx_on %0, gpr_idx(SRC1)\n\tv_add_u32 v85, v76, v37\n\tv_add_u32 v86, v77, v38\n\tv_add_u32 v87, v78, v39\n\ts_add_u32 %0, %0, 8\n\ts_and_b32 %0, %0, 31\n\ts_set_gpr_idx_idx %0\n\tv_add_u32 v80, v99, v32\n\tv_add_u32 v81, v72, v33\n\tv_add_u32 v82, v73, v34\n\tv_add_u32 v83, v74, v35\n\tv_add_u32 v84, v75, v36\n\ts_set_gpr_idx_off\n\tv_pk_sub_u16 v98, v101, v102 clamp\n\tv_pk_maximum3_f16 v88, v88, v76, v75\n\tv_pk_maximum3_f16 v80, v80, v72, v96\n\tv_pk_sub_u16 v76, v88, v102 clamp\n\tv_pk_sub_u16 v72, v80, v102 clamp\n\tv_pk_maximum3_f16 v85, v85, v77, v76\n\tv_pk_maximum3_f16 v81, v81, v73, v72\n\tv_pk_sub_u16 v77, v85, v102 clamp\n\tv_pk_sub_u16 v73, v81, v102 clamp\n\tv_pk_maximum3_f16 v105, v105, v88, v85\n\tv_pk_maximum3_f16 v103, v103, v80, v81\n\tv_pk_maximum3_f16 v86, v86, v78, v77\n\tv_pk_maximum3_f16 v82, v82, v74, v73\n\tv_pk_sub_u16 v78, v86, v102 clamp\n\tv_pk_sub_u16 v74, v82, v102 clamp\n\tv_pk_maximum3_f16 v101, v87, v98, v78\n\tv_pk_maximum3_f16 v83, v83, v75, v74\n\tv_pk_sub_u16 v75, v83, v102 clamp\n\tv_pk_maximum3_f16 v106, v106, v86, v101\n\tv_pk_maximum3_f16 v104, v104, v82, v83")
 // (a v_movrels_b32 variant, one per column with M0 = code x C, does not exist here: gfx950 has no v_movrel* -- the assembler
 // rejects it as "instruction not supported on this GPU"; index mode is the only indexed VGPR read)
 OP(k_nop, "s_nop 0")
@@ -197,6 +208,7 @@ int main(int argc, char** argv) {
         {"v_pk_max_f16", k_pkmaxf16, 1}, {"v_pk_add_u16", k_pkaddu16, 1}, {"v_perm_b32 (sgpr table)", k_permsgpr, 1},
         {"SW cell16, 2 rows x 2 pairs /cell", k_cell16, 1},
         {"SW pk16 profile C=8 idx /cell", k_prof8, 4}, {"SW pk16 profile C=4 idx /cell", k_prof4, 2}, {"SW pk16 profile C=8 int /cell", k_prof8i, 8},
+        {"SW pk16 profile C=8 int nomove /cell", k_prof8n, 16}, {"SW pk16 profile C=8 int skew /cell", k_prof8s, 16},
         {"SW cell, profile form /cell", k_cell4, 1}, {"SW cell, table form   /cell", k_cell4old, 1}, {"s_nop 0", k_nop, 1}};
     struct { const char* n; kfn f; int chain, total; } dt_[] = {
         {"v_add_u32 chain", d_add, 4, 4}, {"v_and/v_or chain", d_and, 4, 4}, {"v_max3_i32 chain", d_max3, 4, 4}, {"v_add_u32_sdwa chain", d_sdwa, 4, 4},
