@@ -959,13 +959,9 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
             pd.push_back(d);
             b->padded_cells += (in.len(in.pair_a[k]) + 64 * geom.rl - 1) / (64 * geom.rl) * (64 * geom.rl) * in.len(in.pair_b[k]);
         }
-        b->pl.perm = keyed_scores;
-        b->pl.keyed = true;
-        b->pl.gap0 = gap0_scores;
-        b->pl.semi = in.semi;
-        b->pl.dist = in.nwdist();
-        b->pl.aff = in.affine();   // (go travels as the gap, ge beside it)
-        const int rc = b->pl.build(ctx, pd, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap, geom,
+        PairForm form{PF_STRIPE_FILL, b->mode, BAND_NONE, WALK_NONE, gap0_scores ? CELLS_GAP0 : keyed_scores ? CELLS_CODED : CELLS_PLAIN, geom.rl, geom.w};
+        if (in.nwdist() || in.affine()) form.family = in.nwdist() ? PF_STRIPE_DIST : PF_STRIPE_AFFINE, form.mode = PWA_MODE_NW;   // (affine: go travels as the gap, ge beside it)
+        const int rc = b->pl.build(ctx, pd, form, gap0_scores ? match - 2 * gap : match, gap0_scores ? mismatch - 2 * gap : mismatch, gap0_scores ? 0 : gap,
                                    in.affine() ? in.gap_extend : 0);
         if (rc != PWA_OK) return rc;
         b->pl.G.scores_out = b->scores.as<int32_t>();   // the device score vector is complete after run()
@@ -995,10 +991,8 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         b->mini.emplace_back(new PairLaunch());
         PairLaunch& ml = *b->mini.back();
         for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
-        ml.perm = ml.keyed = true;
-        ml.gap0 = mini_gap0;
-        ml.semi = in.semi;
-        const int rc = ml.build_mini(ctx, pd, n_real, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap, rl);
+        const PairForm form{PF_MINI_FILL, b->mode, BAND_NONE, WALK_NONE, mini_gap0 ? CELLS_GAP0 : CELLS_CODED, rl, 16};
+        const int rc = ml.build_mini(ctx, pd, n_real, form, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap);
         if (rc != PWA_OK) return rc;
         ml.G.scores_out = b->scores.as<int32_t>();
         names += std::string(names.empty() ? "" : " + ") + "mini_fill_kernel<RL=" + std::to_string(rl) + (local ? ",SW" : in.semi ? ",SG" : (mini_gap0 ? ",NW,GAP0" : ",NW")) + ",no-band>";
@@ -1056,17 +1050,12 @@ int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std
         b->mini.emplace_back(new PairLaunch());
         PairLaunch& ml = *b->mini.back();
         for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
-        ml.gotoh = b->mode;
-        ml.gotoh_scores = true;
-        const int rc = ml.build_mini(ctx, pd, n_real, in.match, in.mismatch, in.gap, cls.rl, cls.ln);
+        PairForm form{in.subst ? PF_MINI_SUBST : PF_MINI_GOTOH, b->mode, BAND_NONE, WALK_NONE, CELLS_KEYED, cls.rl, cls.ln};
+        if (in.subst) form.subst = SubstRef{b->subst.dev.as<uint32_t>(), b->subst.n_sym, b->subst.stride};
+        const int rc = ml.build_mini(ctx, pd, n_real, form, in.match, in.mismatch, in.gap);
         if (rc != PWA_OK) return rc;
         ml.G.gap_extend = in.gap_extend;
         ml.G.scores_out = b->scores.as<int32_t>();
-        if (in.subst) {
-            ml.subst = b->subst.dev.as<uint32_t>();
-            ml.subst_n_sym = b->subst.n_sym;
-            ml.subst_stride = b->subst.stride;
-        }
         names += std::string(names.empty() ? "" : " + ") + (in.subst ? "subst_scores_kernel<RL=" : "gotoh_scores_kernel<RL=") + std::to_string(cls.rl) + ",LN=" + std::to_string(cls.ln) + "," +
                  kModeName[b->mode] + ",no-band>";
     }
@@ -1406,11 +1395,11 @@ int pwa_batch_run(pwa_batch* b, void* stream_v) {
             HIPC(ctx, hipStreamWaitEvent(ms, ctx->aux_ev[0], 0));
         }
         if (b->use_pairs) {
-            const int rc = b->pl.launch(ctx, st, b->mode == PWA_MODE_SW, false, false, nullptr);
+            const int rc = b->pl.launch(ctx, st, nullptr);
             if (rc != PWA_OK) return rc;
         }
         for (auto& ml : b->mini) {
-            const int rc = ml->launch(ctx, ms, b->mode == PWA_MODE_SW, false, WALK_NONE, nullptr);
+            const int rc = ml->launch(ctx, ms, nullptr);
             if (rc != PWA_OK) return rc;
         }
         if (fork) {

@@ -297,15 +297,15 @@ int affine_tb_on_stripes(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector
         HIPC(ctx, hipMemsetAsync(d_res, 0, nc * sizeof(PairResult), ctx->stream));
         PairLaunch pl;
         pl.from_pool = true;
-        pl.aff = pl.aff_tb = true;
-        int rc = pl.build(ctx, pd, rq.match, rq.mismatch, rq.gap_open, PairGeom{4, max_n <= 256 ? 1 : 4}, rq.gap_extend);
+        const PairForm form{PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, 4, max_n <= 256 ? 1 : 4};
+        int rc = pl.build(ctx, pd, form, rq.match, rq.mismatch, rq.gap_open, rq.gap_extend);
         if (rc != PWA_OK) return rc;
         pl.G.scores_out = rs.d_scores.as<int32_t>();
         if (ctx->knobs.debug)
             std::fprintf(stderr, "[pwa] align_affine chunk: pairs %zu .. %zu, W=%d grid=%u tasks=%u band %.2f GB rows %llu B\n", ch.first, ch.second - 1,
-                         pl.geom.w, pl.grid, pl.G.n_tasks, (double)bo / 1e9, (unsigned long long)pl.row_bytes);
+                         pl.form.w, pl.grid, pl.G.n_tasks, (double)bo / 1e9, (unsigned long long)pl.row_bytes);
         HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        rc = pl.launch(ctx, ctx->stream, false, true, WALK_OPS, ctx->ev[1]);
+        rc = pl.launch(ctx, ctx->stream, ctx->ev[1]);
         if (rc != PWA_OK) return rc;
         HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
         HIPC(ctx, hipStreamSynchronize(ctx->stream));

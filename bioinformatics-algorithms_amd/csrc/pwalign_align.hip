@@ -51,9 +51,8 @@ struct GotohSpec {
 };
 // pwa_align_subst_batch(_cigar): the gotoh classes with the diagonal score from the caller's table (always beside a GotohSpec)
 struct SubstSpec {
-    const uint32_t* d_tab;   // SubstTable::dev
-    int n_sym, stride;
-    int64_t max_abs;         // max |submat|: the range rule's score term
+    SubstRef tab;      // SubstTable::dev and its layout
+    int64_t max_abs;   // max |submat|: the range rule's score term
 };
 constexpr uint64_t kGotohMaxN = 1024;   // patterns of the gotoh classes: 16 x kMiniRL rows, then 64 x 8 | 16 rows
 
@@ -484,26 +483,20 @@ int run_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const
     }
     PairLaunch pl;
     pl.from_pool = true;
-    pl.perm = ar.coded && plan.keyed;
-    pl.keyed = plan.keyed;
-    pl.gap0 = plan.gap0;
-    pl.semi = rq.semi();
-    pl.gotoh = rq.gt ? rq.mode : -1;
-    int rc = L.cls.mini ? pl.build_mini(ctx, pd, (uint32_t)np, plan.k_match, plan.k_mismatch, plan.k_gap, L.cls.rl, L.cls.w)
-                        : pl.build(ctx, pd, plan.k_match, plan.k_mismatch, plan.k_gap, PairGeom{L.cls.rl, L.cls.w});
+    const PairCells cells = plan.gap0 ? CELLS_GAP0 : ar.coded && plan.keyed ? CELLS_CODED : plan.keyed ? CELLS_KEYED : CELLS_PLAIN;
+    PairForm form{L.cls.mini ? PF_MINI_FILL : PF_STRIPE_FILL, rq.mode, plan.sband ? BAND_TB_SCORES : BAND_TB, walk_ops ? WALK_OPS : WALK_OVERLAP, cells, L.cls.rl, L.cls.w};
+    if (rq.gt) form.family = rq.sb ? PF_MINI_SUBST : PF_MINI_GOTOH, form.cells = CELLS_KEYED;   // (raw bytes, compared; always a mini class)
+    if (rq.sb) form.subst = rq.sb->tab;
+    int rc = L.cls.mini ? pl.build_mini(ctx, pd, (uint32_t)np, form, plan.k_match, plan.k_mismatch, plan.k_gap)
+                        : pl.build(ctx, pd, form, plan.k_match, plan.k_mismatch, plan.k_gap);
     if (rc != PWA_OK) return rc;
     pl.G.dash = ar.dash_sym;
     if (rq.gt) pl.G.gap_extend = rq.gt->gap_extend;
-    if (rq.sb) {
-        pl.subst = rq.sb->d_tab;
-        pl.subst_n_sym = rq.sb->n_sym;
-        pl.subst_stride = rq.sb->stride;
-    }
     clock.mark("task list build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] fill launch %s RL=%d W|LN=%d grid=%u pairs=%u tasks=%u rows=%llu\n", L.cls.mini ? "mini" : "stripes", L.cls.rl,
                                L.cls.w, pl.grid, pl.G.n_pairs, pl.G.n_tasks, (unsigned long long)pl.row_bytes);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    rc = pl.launch(ctx, ctx->stream, rq.local(), true, walk_ops ? WALK_OPS : WALK_OVERLAP, ctx->ev[1], plan.sband);
+    rc = pl.launch(ctx, ctx->stream, ctx->ev[1]);
     if (rc != PWA_OK) return rc;
     HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
@@ -795,13 +788,13 @@ static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n
     int rc = subst_prepare(ctx, code, n_sym, submat, tab);
     if (rc != PWA_OK) return rc;
     const GotohSpec gs{rq.gap, gap_extend};
-    SubstSpec ss{nullptr, tab.n_sym, tab.stride, tab.max_abs};
+    SubstSpec ss{{nullptr, tab.n_sym, tab.stride}, tab.max_abs};
     rq.gt = &gs;
     rq.sb = &ss;
     if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (before anything is allocated; align_batch_impl checks again)
     HIPC(ctx, hipSetDevice(ctx->device));
     if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
-    ss.d_tab = tab.dev.as<uint32_t>();
+    ss.tab.tab = tab.dev.as<uint32_t>();
     return align_batch_impl(ctx, rq, ctx->subst_stats);
 } catch (const std::bad_alloc&) {
     return fail(ctx, PWA_E_NOMEM, "host allocation failed");
@@ -953,27 +946,18 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
     pd[0].sband = d_sband.as<int32_t>();
     pd[0].res = d_res.as<PairResult>();
     PairLaunch pl;
-    pl.keyed = keyed;
-    pl.semi = semi;
-    int rc;
-    if (mini_rl) {
-        for (int d = 1; d < 4; ++d) {   // three empty patterns fill the wave; their padding goes behind the pair's bands
-            PairDesc e = pd[0];
-            e.n = 0;
-            e.tb = d_band.as<uint8_t>() + (uint64_t)d * band;
-            e.sband = d_sband.as<int32_t>() + (uint64_t)d * band;
-            pd.push_back(e);
-        }
-        pl.perm = true;
-        rc = pl.build_mini(ctx, pd, 1, match, mismatch, gap, mini_rl);
-    } else if (wide_rl) {
-        pl.perm = true;
-        rc = pl.build_mini(ctx, pd, 1, match, mismatch, gap, wide_rl, 64);
-    } else {
-        rc = pl.build(ctx, pd, match, mismatch, gap, geom);
+    PairForm form{PF_STRIPE_FILL, mode, BAND_TB_SCORES, WALK_NONE, keyed ? CELLS_KEYED : CELLS_PLAIN, geom.rl, geom.w};   // raw bytes; only the bands are read
+    if (mini_rl || wide_rl) form.family = PF_MINI_FILL, form.cells = CELLS_CODED, form.w = mini_rl ? 16 : 64;
+    for (int d = 1; mini_rl && d < 4; ++d) {   // three empty patterns fill the wave; their padding goes behind the pair's bands
+        PairDesc e = pd[0];
+        e.n = 0;
+        e.tb = d_band.as<uint8_t>() + (uint64_t)d * band;
+        e.sband = d_sband.as<int32_t>() + (uint64_t)d * band;
+        pd.push_back(e);
     }
+    int rc = form.mini() ? pl.build_mini(ctx, pd, 1, form, match, mismatch, gap) : pl.build(ctx, pd, form, match, mismatch, gap);
     if (rc != PWA_OK) return rc;
-    rc = pl.launch(ctx, ctx->stream, local, true, false, nullptr, true);
+    rc = pl.launch(ctx, ctx->stream, nullptr);
     if (rc != PWA_OK) return rc;
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     rc = pl.check(ctx);

@@ -18,7 +18,6 @@ void (*gotoh_fill_kernel_for(int rl, int mode, int ln))(const PairParams);
 void (*gotoh_walk_kernel_for(int rl, int mode, int ln))(const PairParams);
 void (*gotoh_scores_kernel_for(int rl, int mode, int ln))(const PairParams);   // the fills without a band (no walk follows)
 // subst_kernels.hip: the same classes and modes under a substitution table (device blob, n_sym, row stride); the walk is gotoh's
-typedef void (*subst_kernel_t)(const PairParams, const uint32_t*, int, int);
 subst_kernel_t subst_fill_kernel_for(int rl, int mode, int ln);
 subst_kernel_t subst_scores_kernel_for(int rl, int mode, int ln);
 }
@@ -389,16 +388,88 @@ size_t tb_band_bytes(uint64_t n, uint64_t m, int rl) {
     return (size_t)(stripes * band_steps(m) * 64 * rl);
 }
 
+// ---- PairForm -> kernels: the only caller of the kernel units' pickers.  Those take a geometry they have no instantiation for as
+// the nearest one and a flag that does not apply as unset, so everything a form may not combine is refused here.
+static bool resolve_pair_form(const PairForm& f, PairKernels& k) {   // false: no such kernel
+    k = PairKernels{};
+    const bool local = f.mode == PWA_MODE_SW, semi = f.mode == PWA_MODE_SG, tb = f.band != BAND_NONE, sband = f.band == BAND_TB_SCORES;
+    const bool coded = f.cells >= CELLS_CODED, gap0 = f.cells == CELLS_GAP0;
+    if (f.mode != PWA_MODE_NW && !local && !semi) return false;
+    if (!tb && f.walk != WALK_NONE) return false;                            // no band: only the end-cell pick
+    if (gap0 && (local || semi || sband)) return false;                      // the gap shift is global, and the score band holds H itself
+    if ((f.subst.tab != nullptr) != (f.family == PF_MINI_SUBST)) return false;
+    if (f.mini() ? f.w != 16 && f.w != 64 : (f.rl != 2 && f.rl != 4) || (f.w != 1 && f.w != 4)) return false;
+    k.walks = tb || f.family == PF_STRIPE_FILL || f.family == PF_MINI_FILL;   // (the linear-gap fills leave the end-cell pick to a walk)
+    switch (f.family) {
+        case PF_STRIPE_FILL:
+            // without a band: the keyed chunk over a coded arena, or the plain step (there is no keyed form on raw bytes)
+            if (!tb && f.cells == CELLS_KEYED) return false;
+            k.fill = tb       ? pair_fill_kernel_for(f.rl, f.w, local, true, sband, coded, f.cells != CELLS_PLAIN, gap0, true, semi)
+                     : coded ? pair_fill_kernel_for(f.rl, f.w, local, true, false, true, true, gap0, false, semi)
+                             : pair_fill_kernel_for(f.rl, f.w, local, false, false, false, true, false, true, semi);
+            k.walk = pair_traceback_kernel_for(f.rl, local, f.walk, semi);
+            break;
+        case PF_STRIPE_DIST:
+        case PF_STRIPE_AFFINE:   // the fill writes D[n][m] / M[n][m] into the score vector itself
+        case PF_STRIPE_AFFINE_TB: {
+            const bool atb = f.family == PF_STRIPE_AFFINE_TB;
+            if (f.mode != PWA_MODE_NW || f.cells != CELLS_PLAIN || f.band != (atb ? BAND_TB : BAND_NONE) || f.walk != (atb ? WALK_OPS : WALK_NONE)) return false;
+            k.fill = atb ? pair_affine_tb_kernel_for(f.rl, f.w) : f.family == PF_STRIPE_DIST ? pair_dist_kernel_for(f.rl, f.w) : pair_affine_kernel_for(f.rl, f.w);
+            if (atb) k.walk = pair_affine_walk_kernel_for(f.rl);
+            break;
+        }
+        case PF_MINI_FILL:
+            if (!coded) return false;
+            k.fill = mini_fill_kernel_for(f.rl, local, sband, gap0, tb, f.w, semi);
+            k.walk = mini_traceback_kernel_for(f.rl, local, f.walk, f.w, semi);
+            break;
+        case PF_MINI_GOTOH:
+        case PF_MINI_SUBST:
+            if (f.cells != CELLS_KEYED || sband || f.walk != (tb ? WALK_OPS : WALK_NONE)) return false;
+            if (f.family == PF_MINI_SUBST) k.sfill = tb ? subst_fill_kernel_for(f.rl, f.mode, f.w) : subst_scores_kernel_for(f.rl, f.mode, f.w);
+            else k.fill = tb ? gotoh_fill_kernel_for(f.rl, f.mode, f.w) : gotoh_scores_kernel_for(f.rl, f.mode, f.w);
+            if (tb) k.walk = gotoh_walk_kernel_for(f.rl, f.mode, f.w);
+            break;
+    }
+    k.block = f.mini() ? 64 * kMiniWaves : 64 * (unsigned)(f.w + 1);   // stripe engine: W compute waves + the helper wave
+    return (k.fill || k.sfill) && (k.walk || !k.walks);
+}
+
 // ---- PairLaunch (pwalign_internal.h)
+int PairLaunch::upload_desc(pwa_ctx* ctx, const std::vector<PairDesc>& pd) {
+    const size_t bytes = pd.size() * sizeof(PairDesc);
+    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, bytes, &p_desc));
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(bytes));
+    std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), bytes);
+    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, bytes, hipMemcpyHostToDevice));
+    return PWA_OK;
+}
+// the fields of G that every launch sets (the callers add scores_out, dash, gap_extend of the gotoh families)
+void PairLaunch::set_params(uint32_t n_pairs, uint32_t n_tasks, int match, int mismatch, int gap, int gap_extend) {
+    G = PairParams{};
+    G.pairs = static_cast<PairDesc*>(p_desc);
+    G.n_pairs = n_pairs;
+    G.n_tasks = n_tasks;
+    G.queue = static_cast<uint32_t*>(p_queue);
+    G.best = static_cast<StripeBest*>(p_best);
+    G.match = match;
+    G.mismatch = mismatch;
+    G.gap = gap;
+    G.gap_extend = gap_extend;
+    G.dash = 0x100;   // no symbol: set by the callers that walk for overlaps
+    G.trace_stripe = -1;
+}
 // pd[q].{pat,txt,n,m,tb,sband,res,ops,ops_cap} filled by the caller; this adds the pipeline fields
-int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g, int gap_extend) {
-    geom = g;
-    const uint64_t rows_per_stripe = 64ull * g.rl;
+int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, const PairForm& f, int match, int mismatch, int gap, int gap_extend) {
+    if (f.mini() || !resolve_pair_form(f, k)) return fail(ctx, PWA_E_INVALID, "internal: no stripe kernel for this form");
+    form = f;
+    const uint64_t vals = f.family == PF_STRIPE_FILL ? 1 : 2;   // int32 values per hand-off column
+    const uint64_t rows_per_stripe = 64ull * f.rl;
     std::vector<StripeTask> tl;
     uint64_t rows_i32 = 0, n_stripes_total = 0;
     for (size_t q = 0; q < pd.size(); ++q) {
         const uint64_t ns = ((uint64_t)pd[q].n + rows_per_stripe - 1) / rows_per_stripe;
-        const uint64_t nsup = (ns + g.w - 1) / g.w;
+        const uint64_t nsup = (ns + f.w - 1) / f.w;
         if (tl.size() + nsup >= 0xffffffffull || n_stripes_total + ns >= 0xffffffffull)
             return fail(ctx, PWA_E_CAPACITY, "too many stripe tasks in one launch");
         pd[q].first_task = (uint32_t)tl.size();
@@ -406,7 +477,7 @@ int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mi
         pd[q].n_stripes = (uint32_t)ns;
         pd[q].row_stride = (uint32_t)align_up((uint64_t)pd[q].m + 64, 64);
         for (uint64_t st = 0; st < nsup; ++st) tl.push_back({(uint32_t)q, (uint32_t)st});
-        rows_i32 += (nsup - 1) * pd[q].row_stride * (dist || aff ? 2 : 1);
+        rows_i32 += (nsup - 1) * pd[q].row_stride * vals;
         n_stripes_total += ns;
     }
     row_bytes = rows_i32 * sizeof(int32_t);
@@ -414,13 +485,10 @@ int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mi
     uint64_t ro = 0;
     for (auto& d : pd) {
         d.rows = static_cast<int32_t*>(p_rows) + ro;
-        const uint64_t nsup = ((uint64_t)d.n_stripes + g.w - 1) / g.w;
-        ro += (nsup - 1) * d.row_stride * (dist || aff ? 2 : 1);
+        const uint64_t nsup = ((uint64_t)d.n_stripes + f.w - 1) / f.w;
+        ro += (nsup - 1) * d.row_stride * vals;
     }
-    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
-    HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
-    std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), pd.size() * sizeof(PairDesc));
-    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, pd.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
+    if (const int rc = upload_desc(ctx, pd)) return rc;
     HIPC(ctx, take(ctx, tasks, pwa_ctx::POOL_TASKS, tl.size() * sizeof(StripeTask), &p_tasks));
     HIPC(ctx, ctx->pin[pwa_ctx::PIN_TL].reserve(tl.size() * sizeof(StripeTask)));
     std::memcpy(ctx->pin[pwa_ctx::PIN_TL].p, tl.data(), tl.size() * sizeof(StripeTask));
@@ -429,38 +497,25 @@ int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mi
     HIPC(ctx, take(ctx, progress, pwa_ctx::POOL_PROGRESS, progress_bytes, &p_progress));
     HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, std::max<uint64_t>(n_stripes_total, 1) * sizeof(StripeBest), &p_best));
     HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
-    G.pairs = static_cast<PairDesc*>(p_desc);
+    set_params((uint32_t)pd.size(), (uint32_t)tl.size(), match, mismatch, gap, gap_extend);
     G.tasks = static_cast<StripeTask*>(p_tasks);
-    G.n_pairs = (uint32_t)pd.size();
-    G.n_tasks = (uint32_t)tl.size();
-    G.queue = static_cast<uint32_t*>(p_queue);
     G.progress = static_cast<uint32_t*>(p_progress);
-    G.best = static_cast<StripeBest*>(p_best);
-    G.match = match;
-    G.mismatch = mismatch;
-    G.gap = gap;
-    G.gap_extend = gap_extend;
-    G.dash = 0x100;   // no symbol: set by the callers that walk for overlaps
-    G.stamps = nullptr;
-    G.trace_stripe = -1;
-    G.trace_base = 0;
     n_stripes = n_stripes_total;
     // Tasks come off the queue in global order, so correctness does not depend on how many workgroups
     // are resident.  One workgroup = W compute waves + 1 helper wave.
     // [gpu] single-stripe batches (4096 pairs 150 x 10k, NW + band): 8 workgroups per CU 4.11 ms, 12 or 16: 3.76 ms (three
     // compute waves per SIMD fill the issue slots two leave open); the HBM-bound SW + score-band batch does not care
-    int per_cu = g.w == 1 ? 12 : 3;
+    int per_cu = f.w == 1 ? 12 : 3;
     if (ctx->knobs.wg_per_cu > 0) per_cu = ctx->knobs.wg_per_cu;   // experiments only
     grid = (uint32_t)std::min<uint64_t>(tl.size(), (uint64_t)ctx->num_cu * per_cu);
     return PWA_OK;
 }
 // mini-stripe engine: pd = the real pairs first (n_real of them), then empty patterns up to a multiple of four; task t = the
 // pairs 4t .. 4t+3 (the caller orders them so that a task's texts are about equally long)
-int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, int match, int mismatch, int gap, int rl, int ln) {
-    mini = true;
-    mini_ln = ln;
-    geom = PairGeom{rl, 1};
-    const size_t ppw = (size_t)(64 / ln);   // pairs per wave: 4, or 1 (one pair per wave: 512- / 1024-row single stripes)
+int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, const PairForm& f, int match, int mismatch, int gap) {
+    if (!f.mini() || !resolve_pair_form(f, k)) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
+    form = f;
+    const size_t ppw = (size_t)(64 / f.w);   // pairs per wave: 4, or 1 (one pair per wave: 512- / 1024-row single stripes)
     if (pd.empty() || pd.size() % ppw || pd.size() >= 0xffffffffull || n_real > pd.size() || n_real + ppw - 1 < pd.size())
         return fail(ctx, PWA_E_INVALID, "internal: mini-stripe task list");
     for (size_t q = 0; q < pd.size(); ++q) {
@@ -470,106 +525,58 @@ int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_r
         pd[q].row_stride = 0;
         pd[q].rows = nullptr;
     }
-    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, pd.size() * sizeof(PairDesc), &p_desc));
-    HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(pd.size() * sizeof(PairDesc)));
-    std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), pd.size() * sizeof(PairDesc));
-    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, pd.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
+    if (const int rc = upload_desc(ctx, pd)) return rc;
     HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, pd.size() * sizeof(StripeBest), &p_best));
     HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
     progress_bytes = 0;
     row_bytes = 0;
-    G = PairParams{};
-    G.pairs = static_cast<PairDesc*>(p_desc);
-    G.n_pairs = n_real;
-    G.n_tasks = (uint32_t)(pd.size() / ppw);
-    G.queue = static_cast<uint32_t*>(p_queue);
-    G.best = static_cast<StripeBest*>(p_best);
-    G.match = match;
-    G.mismatch = mismatch;
-    G.gap = gap;
-    G.dash = 0x100;
-    G.trace_stripe = -1;
+    set_params(n_real, (uint32_t)(pd.size() / ppw), match, mismatch, gap, 0);
     n_stripes = pd.size();
     grid = G.n_tasks;   // (clamped to what the chip holds at launch time, where the kernel is known)
     return PWA_OK;
 }
 // enqueue: zero the queue / progress words, fill, then the walk (or only the end-cell pick)
-int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband) {
+int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, hipEvent_t after_fill) {
     HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
-    if (mini) {
-        const subst_kernel_t sfill = !subst || gotoh < 0 ? nullptr : gotoh_scores ? subst_scores_kernel_for(geom.rl, gotoh, mini_ln) : subst_fill_kernel_for(geom.rl, gotoh, mini_ln);
-        if (subst && !sfill) return fail(ctx, PWA_E_INVALID, "internal: no substitution-matrix kernel for this form");
-        const pair_kernel_t fill = gotoh >= 0 ? (gotoh_scores ? gotoh_scores_kernel_for(geom.rl, gotoh, mini_ln) : gotoh_fill_kernel_for(geom.rl, gotoh, mini_ln))
-                                              : mini_fill_kernel_for(geom.rl, local, sband, gap0 && !sband && !local, tb, mini_ln, semi);   // tb = false: no band at all
-        const pair_kernel_t walk_fn = gotoh >= 0 ? gotoh_walk_kernel_for(geom.rl, gotoh, mini_ln)
-                                                 : mini_traceback_kernel_for(geom.rl, local, tb ? walk : (int)WALK_NONE, mini_ln, semi);
-        if (!fill || !walk_fn || (gotoh < 0 && (!perm || !keyed))) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
+    const void* const fill_fn = k.sfill ? reinterpret_cast<const void*>(k.sfill) : reinterpret_cast<const void*>(k.fill);
+    uint32_t g = grid;
+    size_t pad_lds = 0;
+    if (form.mini()) {
         // Workgroups of four waves (one task each per round); `per_cu` of them per CU, enforced through the dynamic LDS request, so
         // that no CU gets more than its share whatever ran before (mini_fill.hip.h): with ceil(tasks / 4) workgroups for 256 CUs,
         // per_cu = ceil(workgroups / CUs), at most 2; longer task lists run in rounds ([gpu] pairs 150 x 10k: 8192 of them at two
         // waves per SIMD 2.68 ms, 16384 at four 6.61 ms -- 16 k concurrent write streams get 4.0 instead of 4.9 TB/s out of HBM).
         const uint32_t n_wg = (G.n_tasks + kMiniWaves - 1) / kMiniWaves;
         // (band-less fills have no write streams to thin out: four per CU -- [gpu] scores with end cells 2 - 3 % faster than at two)
-        const uint32_t cap_per_cu = ctx->knobs.mini_per_cu > 0 ? (uint32_t)std::min(ctx->knobs.mini_per_cu, 5) : (tb ? 2u : 4u);
+        const uint32_t cap_per_cu = ctx->knobs.mini_per_cu > 0 ? (uint32_t)std::min(ctx->knobs.mini_per_cu, 5) : (form.band != BAND_NONE ? 2u : 4u);
         const uint32_t per_cu = std::min<uint32_t>(cap_per_cu, (n_wg + (uint32_t)ctx->num_cu - 1) / (uint32_t)ctx->num_cu);
         static const uint32_t kPadKiB[6] = {0, 96, 64, 48, 36, 30};   // more than 160 KiB / (per_cu + 1), at most 160 KiB / per_cu
         // (the subst fills hold 4.25 KiB of LDS of their own: 5 KiB less padding keeps every per_cu inside the same two bounds)
-        const size_t pad_lds = (size_t)(kPadKiB[per_cu] - (sfill ? 5 : 0)) * 1024;
-        HIPC(ctx, hipFuncSetAttribute(sfill ? reinterpret_cast<const void*>(sfill) : reinterpret_cast<const void*>(fill),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
-        const uint32_t g = std::min<uint32_t>(n_wg, (uint32_t)ctx->num_cu * per_cu);
+        pad_lds = (size_t)(kPadKiB[per_cu] - (k.sfill ? 5 : 0)) * 1024;
+        g = std::min<uint32_t>(n_wg, (uint32_t)ctx->num_cu * per_cu);
         if (ctx->knobs.debug) std::fprintf(stderr, "[pwa] mini fill: %u tasks, %u workgroups of %d waves, %u per CU (%zu KiB of LDS each)\n", G.n_tasks, g, kMiniWaves, per_cu, pad_lds >> 10);
-        if (sfill) hipLaunchKernelGGL(sfill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G, subst, subst_n_sym, subst_stride);
-        else hipLaunchKernelGGL(fill, dim3(g), dim3(64 * kMiniWaves), pad_lds, st, G);
-        HIPC(ctx, hipGetLastError());
-        if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
-        if (gotoh_scores) return PWA_OK;
-        hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
-        HIPC(ctx, hipGetLastError());
-        return PWA_OK;
-    }
-    HIPC(ctx, hipMemsetAsync(p_progress, 0, progress_bytes, st));
-    if (!ctx->knobs.stamps.empty()) {
-        HIPC(ctx, stamps.alloc(n_stripes * 32 + 4 * 8192 * 8));
-        HIPC(ctx, hipMemsetAsync(stamps.p, 0, n_stripes * 32 + 4 * 8192 * 8, st));
-        G.stamps = stamps.as<unsigned long long>();
-        G.trace_base = (uint32_t)(n_stripes * 4);
-        G.trace_stripe = ctx->knobs.trace_stripe;
-    }
-    if (dist || aff) {   // hw4 distances / hw3 affine scores: the fill writes D[n][m] / M[n][m] into the score vector itself
-        const pair_kernel_t fill = dist ? pair_dist_kernel_for(geom.rl, geom.w)
-                                   : aff_tb ? pair_affine_tb_kernel_for(geom.rl, geom.w) : pair_affine_kernel_for(geom.rl, geom.w);
-        const pair_kernel_t walk_fn = aff_tb ? pair_affine_walk_kernel_for(geom.rl) : nullptr;
-        if (!fill || (aff_tb && !walk_fn)) return fail(ctx, PWA_E_INVALID, "internal: no distance / affine kernel for this geometry");
-        size_t pad_lds = 0;   // (one multi-stripe workgroup per CU when they are few: as below)
-        if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;
-        if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
-        hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
-        HIPC(ctx, hipGetLastError());
-        if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
-        if (aff_tb) {
-            hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
-            HIPC(ctx, hipGetLastError());
+    } else {
+        HIPC(ctx, hipMemsetAsync(p_progress, 0, progress_bytes, st));
+        if (!ctx->knobs.stamps.empty()) {
+            HIPC(ctx, stamps.alloc(n_stripes * 32 + 4 * 8192 * 8));
+            HIPC(ctx, hipMemsetAsync(stamps.p, 0, n_stripes * 32 + 4 * 8192 * 8, st));
+            G.stamps = stamps.as<unsigned long long>();
+            G.trace_base = (uint32_t)(n_stripes * 4);
+            G.trace_stripe = ctx->knobs.trace_stripe;
         }
-        return PWA_OK;
+        // A launch with no more multi-stripe workgroups than CUs asks for enough (unused) dynamic LDS that only ONE workgroup
+        // fits a CU: a stripe is one wave alone on its SIMD, and every stripe of a pair moves at the pace of the slowest --
+        // two workgroups sharing a CU's four SIMDs would slow the whole pipeline
+        if (form.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;   // static (<= 16 KiB) + 96 KiB > half of the CU's 160 KiB
     }
-    // (scores / end cells only over a coded arena, keys in range: the keyed chunk without a band -- batch_create_impl sets perm for that)
-    const bool noband = !tb && perm && keyed && !sband;
-    const pair_kernel_t fill = noband ? pair_fill_kernel_for(geom.rl, geom.w, local, true, false, true, true, gap0 && !local, false, semi)
-                                      : pair_fill_kernel_for(geom.rl, geom.w, local, tb, sband, perm && tb && keyed, keyed,
-                                                             gap0 && tb && keyed && perm && !sband && !local, true, semi);
-    const pair_kernel_t walk_fn = pair_traceback_kernel_for(geom.rl, local, walk, semi);
-    if (!fill || !walk_fn) return fail(ctx, PWA_E_INVALID, "internal: no fill kernel for this geometry");
-    // A launch with no more multi-stripe workgroups than CUs asks for enough (unused) dynamic LDS that only ONE workgroup
-    // fits a CU: a stripe is one wave alone on its SIMD, and every stripe of a pair moves at the pace of the slowest --
-    // two workgroups sharing a CU's four SIMDs would slow the whole pipeline
-    size_t pad_lds = 0;
-    if (geom.w > 1 && grid <= (uint32_t)ctx->num_cu && !ctx->knobs.no_lds_pad) pad_lds = 96 * 1024;   // static (<= 16 KiB) + 96 KiB > half of the CU's 160 KiB
-    if (pad_lds) HIPC(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
-    hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * (geom.w + 1)), pad_lds, st, G);
+    // (the attribute is the kernel's, not this launch's: another live launch of the same kernel may have asked for another padding)
+    if (form.mini() || pad_lds) HIPC(ctx, hipFuncSetAttribute(fill_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds));
+    if (k.sfill) hipLaunchKernelGGL(k.sfill, dim3(g), dim3(k.block), pad_lds, st, G, form.subst.tab, form.subst.n_sym, form.subst.stride);
+    else hipLaunchKernelGGL(k.fill, dim3(g), dim3(k.block), pad_lds, st, G);
     HIPC(ctx, hipGetLastError());
     if (after_fill) HIPC(ctx, hipEventRecord(after_fill, st));
-    hipLaunchKernelGGL(walk_fn, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
+    if (!k.walks) return PWA_OK;
+    hipLaunchKernelGGL(k.walk, dim3(G.n_pairs), dim3(64), 0, st, G);   // one wave per pair
     HIPC(ctx, hipGetLastError());
     return PWA_OK;
 }
@@ -650,6 +657,100 @@ uint64_t layout_arena(const uint64_t* seq_off, uint32_t n_seq, const std::vector
 
 }  // namespace pwa
 
+// pwa_selftest_host: every form the seven call sites of PairLaunch can build resolves to kernels -- each family at every geometry its
+// planner chooses, in every mode, band and walk it combines them with -- and a list of forms that mean nothing is refused.  (Kernel host
+// stubs have addresses without a device.)
+static int selftest_pair_forms() {
+    static const uint32_t tab_word = 0;
+    const SubstRef tab{&tab_word, 1, 1};
+    const std::vector<PairGeom> stripe = {{2, 1}, {2, 4}, {4, 1}, {4, 4}}, wide = {{6, 64}, {8, 64}, {12, 64}, {16, 64}};
+    std::vector<PairGeom> mini16, mini, gotoh;
+    for (const int rl : kMiniRL) mini16.push_back({rl, 16});
+    mini = gotoh = mini16;
+    mini.insert(mini.end(), wide.begin(), wide.end());   // (wide_rl_for)
+    gotoh.insert(gotoh.end(), {{8, 64}, {16, 64}});      // (TbPlan::class_of, setup_gotoh_mini)
+    int bad = 0;
+    PairKernels k;
+    auto must = [&](PairFamily fam, int mode, PairBand band, int walk, PairCells cells, PairGeom g) {
+        bad += !resolve_pair_form(PairForm{fam, mode, band, walk, cells, g.rl, g.w, fam == PF_MINI_SUBST ? tab : SubstRef{}}, k);
+    };
+    for (const int mode : {PWA_MODE_NW, PWA_MODE_SW, PWA_MODE_SG}) {
+        const bool nw = mode == PWA_MODE_NW;
+        // score batches (setup_off_strips, setup_gotoh_mini): no band, the end-cell pick
+        for (const PairGeom g : stripe)
+            for (const PairCells c : {CELLS_PLAIN, CELLS_CODED, CELLS_GAP0})
+                if (c != CELLS_GAP0 || nw) must(PF_STRIPE_FILL, mode, BAND_NONE, WALK_NONE, c, g);
+        for (const PairGeom g : mini16)
+            for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
+                if (c != CELLS_GAP0 || nw) must(PF_MINI_FILL, mode, BAND_NONE, WALK_NONE, c, g);
+        // alignment batches (run_launch: op or overlap walks; pwa_align_matrices: both bands, no walk)
+        for (const PairBand band : {BAND_TB, BAND_TB_SCORES})
+            for (const int walk : {WALK_NONE, WALK_OPS, WALK_OVERLAP}) {
+                if (walk == WALK_OVERLAP && mode == PWA_MODE_SG) continue;   // (validate_align)
+                for (const PairGeom g : stripe)
+                    for (const PairCells c : {CELLS_PLAIN, CELLS_KEYED, CELLS_CODED, CELLS_GAP0})
+                        if ((c != CELLS_PLAIN || g.rl == 4) && (c != CELLS_GAP0 || (nw && band == BAND_TB))) must(PF_STRIPE_FILL, mode, band, walk, c, g);
+                for (const PairGeom g : mini)
+                    for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
+                        if (c != CELLS_GAP0 || (nw && band == BAND_TB)) must(PF_MINI_FILL, mode, band, walk, c, g);
+            }
+        for (const PairGeom g : gotoh)
+            for (const PairFamily fam : {PF_MINI_GOTOH, PF_MINI_SUBST}) {
+                must(fam, mode, BAND_NONE, WALK_NONE, CELLS_KEYED, g);
+                must(fam, mode, BAND_TB, WALK_OPS, CELLS_KEYED, g);
+            }
+    }
+    for (const PairGeom g : stripe) {   // hw4 / hw3 (setup_off_strips; pwalign_affine_tb.hip: RL = 4)
+        must(PF_STRIPE_DIST, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
+        must(PF_STRIPE_AFFINE, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
+        if (g.rl == 4) must(PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, g);
+    }
+    if (bad) return 1;
+    const PairForm none[] = {
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 4, 4},             // a gotoh family with stripe geometry
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 2, 16},
+        {PF_MINI_SUBST, PWA_MODE_SW, BAND_NONE, WALK_NONE, CELLS_KEYED, 6, 64, tab},    // (the gotoh classes of 64 lanes: RL = 8 | 16)
+        {PF_STRIPE_FILL, PWA_MODE_SG, BAND_TB, WALK_OPS, CELLS_GAP0, 4, 4},             // the gap shift: global only ...
+        {PF_MINI_FILL, PWA_MODE_SG, BAND_NONE, WALK_NONE, CELLS_GAP0, 8, 16},
+        {PF_STRIPE_FILL, PWA_MODE_SW, BAND_NONE, WALK_NONE, CELLS_GAP0, 4, 4},
+        {PF_MINI_FILL, PWA_MODE_SW, BAND_TB, WALK_OPS, CELLS_GAP0, 8, 16},
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB_SCORES, WALK_OPS, CELLS_GAP0, 2, 4},      // ... and never with a score band
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_TB_SCORES, WALK_NONE, CELLS_GAP0, 16, 64},
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, 2, 4},            // the plain int32 traceback form at RL != 4
+        {PF_STRIPE_FILL, PWA_MODE_SG, BAND_TB_SCORES, WALK_NONE, CELLS_PLAIN, 2, 1},
+        {PF_STRIPE_FILL, PWA_MODE_SG, BAND_TB, WALK_OVERLAP, CELLS_CODED, 4, 4},        // no semi-global overlap walk
+        {PF_MINI_FILL, PWA_MODE_SG, BAND_TB, WALK_OVERLAP, CELLS_CODED, 8, 16},
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_NONE, WALK_OPS, CELLS_CODED, 4, 4},          // a walk over a band that is not there
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_NONE, WALK_OVERLAP, CELLS_CODED, 4, 16},
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_KEYED, 4, 4},         // no keyed band-less fill on raw bytes
+        {PF_STRIPE_FILL, 3, BAND_TB, WALK_OPS, CELLS_KEYED, 4, 4},                      // unknown mode
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 3, 4},            // geometries without an instantiation
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 4, 2},
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 8, 16},
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_CODED, 5, 16},
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_CODED, 4, 64},
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_CODED, 4, 1},
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_CODED, 8, 64},          // (one pair per wave: band only)
+        {PF_MINI_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 8, 16},             // the mini-stripe fills score by table
+        {PF_STRIPE_DIST, PWA_MODE_SW, BAND_NONE, WALK_NONE, CELLS_PLAIN, 4, 4},         // hw4 / hw3: global, one form each
+        {PF_STRIPE_DIST, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, 4, 4},
+        {PF_STRIPE_AFFINE, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_GAP0, 4, 4},
+        {PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, 2, 4},
+        {PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OVERLAP, CELLS_PLAIN, 4, 4},
+        {PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, 4, 4},
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB_SCORES, WALK_OPS, CELLS_KEYED, 8, 16},     // the gotoh kernels write no score band ...
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OVERLAP, CELLS_KEYED, 8, 16},        // ... and walk for op lists only
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_NONE, CELLS_KEYED, 8, 16},
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_CODED, 8, 16},
+        {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 8, 16, tab},       // a table without the subst family, and the reverse
+        {PF_STRIPE_FILL, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 4, 4, tab},
+        {PF_MINI_SUBST, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 8, 16},
+    };
+    for (const PairForm& f : none)
+        if (resolve_pair_form(f, k)) return 2;
+    return 0;
+}
+
 extern "C" {
 
 const char* pwa_version(void) { return "pwalign 0.1 gfx950"; }
@@ -706,7 +807,8 @@ int pwa_selftest_host(uint32_t seed) try {
             if (idx != want) return check;
         }
     }
-    return selftest_align_plan(x, check);
+    if (const int rc = selftest_pair_forms()) return check + rc;
+    return selftest_align_plan(x, check + 2);
 } catch (...) {
     return -1;
 }

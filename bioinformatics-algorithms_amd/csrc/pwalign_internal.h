@@ -278,6 +278,46 @@ struct PairGeom {
 PairGeom choose_geom(const Knobs& kn, uint64_t max_n, bool keyed = true, bool keyed_tb = false);
 size_t tb_band_bytes(uint64_t n, uint64_t m, int rl);
 
+// What a launch of the wavefront (pair) engine IS, as one value.  resolve_pair_form (pwalign_ctx.hip) maps it to PairKernels, or says
+// that there are none: build() / build_mini() refuse such a form with PWA_E_INVALID.
+enum PairFamily {
+    PF_STRIPE_FILL,        // pair_fill.hip.h: the linear-gap fills of the stripe engine and their walks
+    PF_STRIPE_DIST,        // pair_dist.hip.h: hw4's NW distance -- two values per hand-off column, no band, no walk
+    PF_STRIPE_AFFINE,      // pair_affine.hip.h: hw3's affine score, likewise; build() takes go as gap, and ge
+    PF_STRIPE_AFFINE_TB,   // pair_affine_tb.hip.h: hw3's affine alignment -- the fill writes a band, a walk follows
+    PF_MINI_FILL,          // mini_fill.hip.h: the mini-stripe engine, w lanes per pair, rl rows per lane, 64 / w pairs per wave
+    PF_MINI_GOTOH,         // gotoh_fill.hip.h: its affine-gap kernels (gap = gap_open); without a band the fill writes score and end cell itself: no walk
+    PF_MINI_SUBST          // subst_fill.hip.h: ... with the diagonal score from the table PairForm::subst; the walk is gotoh's
+};
+enum PairBand { BAND_NONE, BAND_TB, BAND_TB_SCORES };   // what the fill materialises: nothing, the traceback band, the band + the int32 score band
+enum PairCells {
+    CELLS_PLAIN,   // int32 compare-and-select on raw bytes: anything the reference's int holds (traceback fills: RL = 4 only)
+    CELLS_KEYED,   // H * 4 + priority (needs |H| < 2^28) on raw bytes; the gotoh families' cells
+    CELLS_CODED,   // ... on sequences coded 0..6 (pad 7), the key constants fit a byte: table scoring
+    CELLS_GAP0     // ... global, in gap-shifted coordinates: the caller gives build() gap 0 and the scores s - 2 gap
+};
+struct SubstRef {   // SubstTable::dev and its layout
+    const uint32_t* tab = nullptr;
+    int n_sym = 0, stride = 0;
+};
+struct PairForm {
+    PairFamily family;
+    int mode;          // PWA_MODE_NW | SW | SG (the hw3 / hw4 families: NW)
+    PairBand band;
+    int walk;          // WALK_NONE (end cells only; the only walk without a band) / WALK_OPS / WALK_OVERLAP
+    PairCells cells;   // the fill families' choice; hw3 / hw4: CELLS_PLAIN, gotoh / subst: CELLS_KEYED
+    int rl, w;         // rows per lane; stripe families: compute waves per workgroup (PairGeom), mini families: lanes per pair (16 | 64)
+    SubstRef subst = {};   // PF_MINI_SUBST only
+    bool mini() const { return family >= PF_MINI_FILL; }
+};
+typedef void (*subst_kernel_t)(const PairParams, const uint32_t*, int, int);
+struct PairKernels {
+    pair_kernel_t fill = nullptr, walk = nullptr;   // the fill, `block` threads per workgroup; the walk, one wave per pair, when `walks`
+    subst_kernel_t sfill = nullptr;                 // PF_MINI_SUBST: launched in the fill's place, with the table
+    unsigned block = 0;
+    bool walks = false;
+};
+
 // Device-side state of one launch of the wavefront (pair) engine: pair descriptors, the global
 // stripe-task list, hand-off rows, progress counters, per-stripe bests.
 struct PairLaunch {
@@ -293,30 +333,20 @@ struct PairLaunch {
         return e;
     }
     PairParams G{};
-    PairGeom geom{4, 4};
-    bool mini = false;   // the mini-stripe engine (mini_fill.hip.h): mini_ln lanes per pair, geom.rl rows per lane, 64 / mini_ln pairs per wave
-    int mini_ln = 16;
-    bool perm = false;   // sequences are coded 0..6 (pad 7) and the key constants fit a byte: table-scoring fill kernels
-    bool keyed = true;   // traceback fills keep H * 4 + priority (needs |H| < 2^28); false: plain int32 compare-and-select form
-    bool gap0 = false;   // global keyed table-scoring fill in gap-shifted coordinates: build() was given gap 0 and scores s - 2 gap
-    bool semi = false;   // semi-global (PWA_MODE_SG) fills and walks: row 0 free, the end record of row n (never with gap0)
-    bool dist = false;   // hw4's NW distance (pair_dist.hip.h): two values per hand-off column, no band, no walk; set before build()
-    bool aff = false;    // hw3's affine score (pair_affine.hip.h): likewise two values per column; build() takes go as gap, and ge
-    bool aff_tb = false; // ... with aff: hw3's affine alignment (pair_affine_tb.hip.h): the fill writes a band, a walk follows
-    int gotoh = -1;      // >= 0 (a PWA_MODE_*): the affine-gap mini-stripe kernels (gotoh_fill.hip.h); build_mini takes gap_open as gap
-    bool gotoh_scores = false;   // ... their band-less form (gotoh_scores_kernel): score and end cell from the fill itself, no walk
-    const uint32_t* subst = nullptr;   // ... with gotoh >= 0: the device table of the substitution-matrix fills (subst_fill.hip.h) in their place
-    int subst_n_sym = 0, subst_stride = 0;
+    PairForm form{};   // set and resolved by build() / build_mini()
+    PairKernels k;
     uint32_t grid = 0;
     uint64_t row_bytes = 0;
     uint64_t n_stripes = 0;
     DevBuf stamps;   // PWA_STAMPS=<file>: per-stripe time stamps of the fill (debugging the stripe pipeline)
 
     // pd[q].{pat,txt,n,m,tb,sband,res,ops,ops_cap} filled by the caller; this adds the pipeline fields
-    int build(pwa_ctx* ctx, std::vector<PairDesc>& pd, int match, int mismatch, int gap, PairGeom g, int gap_extend = 0);
-    int build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, int match, int mismatch, int gap, int rl, int ln = 16);
+    int build(pwa_ctx* ctx, std::vector<PairDesc>& pd, const PairForm& f, int match, int mismatch, int gap, int gap_extend = 0);
+    int build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, const PairForm& f, int match, int mismatch, int gap);
+    int upload_desc(pwa_ctx* ctx, const std::vector<PairDesc>& pd);
+    void set_params(uint32_t n_pairs, uint32_t n_tasks, int match, int mismatch, int gap, int gap_extend);
     // enqueue: zero the queue / progress words, fill, then the walk (or only the end-cell pick)
-    int launch(pwa_ctx* ctx, hipStream_t st, bool local, bool tb, int walk, hipEvent_t after_fill, bool sband = false);
+    int launch(pwa_ctx* ctx, hipStream_t st, hipEvent_t after_fill);
     // after the stream has been synchronised: did a bounded spin give up?
     int check(pwa_ctx* ctx);
 };
