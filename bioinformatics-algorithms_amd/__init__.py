@@ -32,6 +32,7 @@ EXPORTS = [
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
+    "pwa_align_banded_batch", "pwa_align_banded_batch_cigar", "pwa_align_banded_last_stats",
     "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
@@ -163,6 +164,9 @@ def lib():
     L.pwa_align_gotoh_batch.argtypes = gotoh_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_align_gotoh_batch_cigar.argtypes = gotoh_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
     L.pwa_align_gotoh_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
+    L.pwa_align_banded_batch.argtypes = L.pwa_align_gotoh_batch.argtypes + [i32p, i32p]   # ..., band_lo, band_hi
+    L.pwa_align_banded_batch_cigar.argtypes = L.pwa_align_gotoh_batch_cigar.argtypes + [i32p, i32p]
+    L.pwa_align_banded_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_gotoh_batch_create.argtypes = gotoh_in + [C.c_int, C.POINTER(vp)]
     L.pwa_scores_gotoh.argtypes = gotoh_in + [i32p, u32p, u32p]
     subst_in = batch_in[:2] + [vp, C.c_int, i32p] + gotoh_in[4:]   # ctx, mode, code[256], n_sym, submat, gap_open, gap_extend, sequences, pairs
@@ -266,6 +270,14 @@ def _subst_args(table, blob):
             raise PwaError("substitution table: byte 0x%02x of the sequences is outside the alphabet and no `unknown` code was given" % bad[0])
         code = np.where(code == _SUBST_NO_CODE, 0, code).astype(np.uint8)   # (bytes that do not occur: any valid code)
     return code, int(n_sym), submat, code.ctypes.data_as(C.c_void_p), submat.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def band_around(n, m, w, diag=None):
+    """(lo, hi) for align_banded_batch.  diag=None: the global band of an n x m pair, half-width w around the corner-to-corner
+    diagonals (valid for nw); diag=d: a read seeded on text diagonal d (j - i = d), for sg / sw."""
+    if diag is None:
+        return (min(0, m - n) - w, max(0, m - n) + w)
+    return (diag - w, diag + w)
 
 
 def read_fasta(paths, n_threads=0):
@@ -538,8 +550,8 @@ class Context:
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b):
-        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs"""
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=()):
+        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`)"""
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -554,13 +566,13 @@ class Context:
         nops = (C.c_uint64 * max(n, 1))()
         endc = (C.c_uint64 * (2 * max(n, 1)))()
         startc = (C.c_uint64 * (2 * max(n, 1)))()
-        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc)
+        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *tail)
         self._check(rc, name)
         raw = memoryview(ops)
         return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b):
+    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=()):
         """... and one that returns CIGAR and MD:Z strings built on the device"""
         import numpy as np
         blob, off, seqs = pack_sequences(seqs)
@@ -579,7 +591,7 @@ class Context:
         startc = (C.c_uint64 * (2 * max(n, 1)))()
         u64p = C.POINTER(C.c_uint64)
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
-                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None)
+                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None, *tail)
         self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
@@ -597,6 +609,34 @@ class Context:
         [dict(score, cigar, mdz, end, start)] as align_batch_cigar returns them."""
         return self._align_strings(self._L.pwa_align_gotoh_batch_cigar, "pwa_align_gotoh_batch_cigar",
                                    (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b)
+
+    # -- banded affine-gap alignments of long pairs: the gotoh calls inside a diagonal band per pair (include/pwalign.h)
+    @staticmethod
+    def _band_arrays(bands, n):
+        if len(bands) != n:
+            raise ValueError("bands: one (lo, hi) per pair")
+        lo = (C.c_int32 * max(n, 1))(*[int(b[0]) for b in bands])
+        hi = (C.c_int32 * max(n, 1))(*[int(b[1]) for b in bands])
+        return lo, hi
+
+    def align_banded_batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands):
+        """pwa_align_banded_batch: align_gotoh_batch over the cells with lo <= j - i <= hi, bands = [(lo, hi)] per pair (band_around) ->
+        [dict(score, ops, end, start)] as align_gotoh_batch returns them."""
+        return self._align_ops(self._L.pwa_align_banded_batch, "pwa_align_banded_batch",
+                               (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b,
+                               self._band_arrays(bands, len(pair_a)))
+
+    def align_banded_batch_cigar(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands):
+        """pwa_align_banded_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_gotoh_batch_cigar returns them."""
+        return self._align_strings(self._L.pwa_align_banded_batch_cigar, "pwa_align_banded_batch_cigar",
+                                   (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b,
+                                   self._band_arrays(bands, len(pair_a)))
+
+    def align_banded_stats(self):
+        """The last align_banded_batch(_cigar): device ms of its fills and walks, band bytes written."""
+        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_align_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_banded_last_stats")
+        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
 
     # -- substitution-matrix scoring (table = subst_table(...)): the gotoh calls with s(i, j) = submat[code[p], code[t]]
     def _subst_head(self, mode, table, gap_open, gap_extend, blob):

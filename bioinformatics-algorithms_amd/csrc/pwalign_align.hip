@@ -1,5 +1,5 @@
 // pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_align_subst_batch(_cigar),
-// pwa_overlaps (the range planner and its stages), pwa_align and pwa_align_matrices.
+// pwa_align_banded_batch(_cigar), pwa_overlaps (the range planner and its stages), pwa_align and pwa_align_matrices.
 #include "pwalign_internal.h"
 
 #include <chrono>
@@ -11,6 +11,7 @@
 #include <new>
 #include <numeric>
 
+#include "banded_fill.hip.h"
 #include "cigar.hip.h"
 #include "sufarr_ctx.h"
 
@@ -18,6 +19,7 @@ using namespace pwa;
 
 namespace pwa {
 hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
+hipError_t banded_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill);   // banded_kernels.hip
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -34,7 +36,8 @@ namespace {
 struct TbClass {
     bool mini;
     int rl, w;   // mini: rows per lane (w unused); stripe engine: its PairGeom
-    bool operator==(const TbClass& o) const { return mini == o.mini && rl == o.rl && w == o.w; }
+    bool banded = false;   // banded_fill.hip.h: one wave per pair (mini, w = 64), stripes of 64 rl rows over a diagonal band
+    bool operator==(const TbClass& o) const { return mini == o.mini && rl == o.rl && w == o.w && banded == o.banded; }
 };
 // pwa_align_batch_cigar: the walks' op lists stay on the device; per range the CIGAR / MD:Z passes (cigar.hip.h) pack the strings and
 // only those come back, at the running offsets
@@ -55,6 +58,20 @@ struct SubstSpec {
     int64_t max_abs;   // max |submat|: the range rule's score term
 };
 constexpr uint64_t kGotohMaxN = 1024;   // patterns of the gotoh classes: 16 x kMiniRL rows, then 64 x 8 | 16 rows
+// pwa_align_banded_batch(_cigar): the gotoh cell over a diagonal band per pair (always beside a GotohSpec); patterns of any length
+struct BandSpec {
+    const int32_t *lo, *hi;   // cell (i, j) of pair k is in the band iff lo[k] <= j - i <= hi[k]
+    // the band of pair k clamped to its matrix: -n <= lo, hi <= m.  The same cells -- except for a band that lies wholly outside the
+    // matrix (lo > m or hi < -n; valid for SW only), which becomes the corner diagonal m or -n: that adds the boundary cell (0, m) or
+    // (n, 0), whose H is 0 and from which no cell is reachable, so the result (score 0, end (0, 0), no ops) is the empty band's
+    int64_t lo_in(uint64_t k, uint64_t n, uint64_t m) const { return std::min<int64_t>(std::max<int64_t>(lo[k], -(int64_t)n), (int64_t)m); }
+    int64_t hi_in(uint64_t k, uint64_t n, uint64_t m) const { return std::max<int64_t>(std::min<int64_t>(hi[k], (int64_t)m), -(int64_t)n); }
+};
+// Stripe height of a banded pair.  A stripe of S = 64 rl rows over a band of B diagonals runs S + B + 62 steps (+ up to 15 of text
+// alignment) of ~F + C rl instructions (F: per-step moves, hand-off and store; C: the masked cell), so its cost per row is
+// (S + B + 77) (F + C rl) / S: with F ~ 27 and C ~ 22 the two heights built break even near B = 900, and the share of wasted steps
+// (S + 77) / (S + B + 77) falls with B.  Narrow bands take 256-row stripes, wide ones 512-row stripes.
+int banded_rl_for(int64_t width) { return width >= 1024 ? 8 : 4; }
 
 // What a call hands back next to the scores: the op lists (pwa_align_batch), the strings the device formats from them
 // (pwa_align_batch_cigar), or the overlap lengths the walk computes itself (pwa_overlaps)
@@ -80,6 +97,7 @@ struct AlignRequest {
     const uint32_t *pair_a, *pair_b;
     uint64_t n_pairs;
     AlignOut out;
+    const BandSpec* bd = nullptr;   // null: the whole matrix
     uint64_t slen(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
     bool local() const { return mode == PWA_MODE_SW; }
     bool semi() const { return mode == PWA_MODE_SG; }   // (semi-global: NW's classes, guards and codes; no gap shift)
@@ -115,6 +133,18 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
     const int64_t mx = rq.sb ? std::max(rq.sb->max_abs, gaps) : max_abs({rq.match, rq.mismatch, gaps});
     for (uint64_t k = 0; k < rq.n_pairs; ++k) {
         const uint64_t n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
+        if (rq.bd) {   // the band's validity per mode (include/pwalign.h), its width, then the range rule (an all-zero scoring counts as 1)
+            const int64_t lo = rq.bd->lo[k], hi = rq.bd->hi[k], d = (int64_t)m - (int64_t)n;
+            if (lo > hi) return fail(ctx, PWA_E_INVALID, "banded alignment: band_lo > band_hi");
+            if (rq.mode == PWA_MODE_NW && !(lo <= 0 && 0 <= hi && lo <= d && d <= hi))
+                return fail(ctx, PWA_E_INVALID, "banded NW alignment: the band must hold the diagonals 0 and m - n");
+            if (rq.mode == PWA_MODE_SG && !(hi >= 0 && (int64_t)n + lo <= (int64_t)m))
+                return fail(ctx, PWA_E_INVALID, "banded SG alignment: needs band_hi >= 0 and n + band_lo <= m");
+            if (hi - lo + 1 > (int64_t)kBandedMaxWidth) return fail(ctx, PWA_E_CAPACITY, "banded alignment: band wider than 4096 diagonals");
+            if (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 28))
+                return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
+            continue;
+        }
         if (n > kGotohMaxN) return fail(ctx, PWA_E_CAPACITY, "gotoh alignments take patterns of at most 1024 symbols");
         if (rq.sb && (m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)mx >= (long double)(1u << 28)))
             return fail(ctx, PWA_E_CAPACITY, "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|) must stay below 2^28");
@@ -169,8 +199,14 @@ struct TbPlan {
     bool keyed, gap0;    // cell form of the fills; k_*: the scores their kernels are given
     int k_match, k_mismatch, k_gap;
     bool mini_ok, wide_ok, tall_stripes;
+    const AlignRequest* banded = nullptr;   // the banded call's request (its BandSpec and lengths), else null
     uint64_t band_mult() const { return sband ? 5 : 1; }   // band bytes in HBM per byte of codes
-    TbClass class_of(uint64_t n) const {   // (w of a mini class = its lanes per pair)
+    // (k: the pair's index in the call's list; only the banded class looks at it -- its stripe height follows the pair's band width)
+    TbClass class_of(uint64_t n, uint64_t k = 0) const {   // (w of a mini class = its lanes per pair)
+        if (banded) {
+            const uint64_t m = banded->slen(banded->pair_b[k]);
+            return TbClass{true, kn->banded_rl ? kn->banded_rl : banded_rl_for(banded->bd->hi_in(k, n, m) - banded->bd->lo_in(k, n, m) + 1), 64, true};
+        }
         if (gotoh) return n <= 256 ? TbClass{true, mini_rl_for(n), 16} : TbClass{true, n <= 512 ? 8 : 16, 64};
         if (mini_ok && n <= 256) return TbClass{true, mini_rl_for(n), 16};
         if (wide_ok && n <= 1024) return TbClass{true, wide_rl_for(n), 64};
@@ -180,7 +216,12 @@ struct TbPlan {
     }
     // band bytes of a pair: the stripe engine's own (also the one-pair-per-wave form's: a single stripe of 64 RL rows); the four-pair
     // mini-stripe form's for a text of m_task columns (its task's longest)
-    uint64_t band_of(const TbClass& c, uint64_t n, uint64_t m_task) const {
+    // (the banded class: stripes x pitch x 64 rl -- from n, the band width and the stripe height; m only clips the widest window)
+    uint64_t band_of(const TbClass& c, uint64_t n, uint64_t m_task, uint64_t k = 0) const {
+        if (c.banded) {
+            const int64_t S = 64 * c.rl, B = banded->bd->hi_in(k, n, m_task) - banded->bd->lo_in(k, n, m_task) + 1;
+            return (uint64_t)(((int64_t)n + S - 1) / S * banded_steps(S, B, (int64_t)m_task) * S);
+        }
         if (c.mini && c.w == 16) return (uint64_t)mini_band_steps(m_task) * 16 * (uint64_t)c.rl;
         if (c.mini) return (uint64_t)band_steps(m_task) * 64 * (uint64_t)c.rl;
         return ::tb_band_bytes(n, m_task, c.rl);
@@ -192,6 +233,7 @@ TbPlan make_tb_plan(const AlignRequest& rq, const Knobs& kn, bool coded, bool sc
     TbPlan pl;
     pl.kn = &kn;
     pl.gotoh = rq.gt != nullptr;
+    pl.banded = rq.bd ? &rq : nullptr;
     pl.sband = score_band && !rq.gt;
     uint64_t longest_sum = 0;
     for (uint64_t k = 0; k < rq.n_pairs; ++k) longest_sum = std::max(longest_sum, rq.slen(rq.pair_a[k]) + rq.slen(rq.pair_b[k]));
@@ -242,7 +284,7 @@ RangeTarget range_target(const AlignRequest& rq, const TbPlan& plan, uint64_t bu
     for (uint64_t k = 0; k < rq.n_pairs; ++k) {
         const uint64_t n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         if (!(n && m) || n > 0x7fffffc0ull || m > 0x7fffffc0ull) continue;
-        total += align_up(plan.band_of(plan.class_of(n), n, m), 256) * plan.band_mult() + align_up(n + m + 1, 16);
+        total += align_up(plan.band_of(plan.class_of(n, k), n, m, k), 256) * plan.band_mult() + align_up(n + m + 1, 16);
         ++live;
     }
     if (!live) return t;
@@ -292,7 +334,7 @@ void lay_out_launches(const AlignRequest& rq, const TbPlan& plan, Range& rg) {
     for (uint64_t k = k0; k < rg.k1; ++k) {
         const uint64_t n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         if (!(n && m)) continue;
-        const TbClass c = plan.class_of(n);
+        const TbClass c = plan.class_of(n, k);
         size_t li = 0;
         while (li < rg.launches.size() && !(rg.launches[li].cls == c)) ++li;
         if (li == rg.launches.size()) {
@@ -314,7 +356,7 @@ void lay_out_launches(const AlignRequest& rq, const TbPlan& plan, Range& rg) {
         }
         for (size_t p = 0; p < np; ++p) {
             L.bo[p] = bo;
-            bo += align_up(plan.band_of(L.cls, rq.slen(rq.pair_a[k0 + L.q[p]]), L.cls.mini ? L.mt[p] : rq.slen(rq.pair_b[k0 + L.q[p]])), 256);
+            bo += align_up(plan.band_of(L.cls, rq.slen(rq.pair_a[k0 + L.q[p]]), L.cls.mini ? L.mt[p] : rq.slen(rq.pair_b[k0 + L.q[p]]), k0 + L.q[p]), 256);
         }
         for (uint32_t d = 0; d < L.n_dummy; ++d) {   // the last task's empty patterns write their padding here
             L.dummy_bo[d] = bo;
@@ -339,7 +381,7 @@ RangePlan plan_ranges(const AlignRequest& rq, const TbPlan& plan, const RangeTar
         while (k1 < rq.n_pairs) {
             const uint64_t n = rq.slen(rq.pair_a[k1]), m = rq.slen(rq.pair_b[k1]);
             if (n > 0x7fffffc0ull || m > 0x7fffffc0ull) return stop(PWA_E_CAPACITY, "sequence longer than 2^31");
-            const uint64_t need = (n && m) ? align_up(plan.band_of(plan.class_of(n), n, m), 256) : 0;
+            const uint64_t need = (n && m) ? align_up(plan.band_of(plan.class_of(n, k1), n, m, k1), 256) : 0;
             const uint64_t sneed = want_str ? str_bound(n + m) : 0;
             if (sneed > 0xffffffffull) return stop(PWA_E_CAPACITY, "strings of one pair may exceed 2^32 bytes");
             if (k1 > k0 && ((est + need) * band_mult + opsb + n + m > target.chunk_target || (need && live_in >= target.pairs_target) ||
@@ -450,9 +492,57 @@ int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& a
     return PWA_OK;
 }
 
+// One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; banded_kernels.hip
+// sizes the grid and launches fill + walk; the device times into `stats`
+int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, const Launch& L,
+                      const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
+    const size_t np = L.q.size();
+    const int64_t S = 64 * L.cls.rl;
+    std::vector<PairDesc> pd(np);
+    int64_t row_cap = 1;
+    for (size_t p = 0; p < np; ++p) {
+        const uint64_t q = L.q[p], k = rg.k0 + q, n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
+        const int64_t lo = rq.bd->lo_in(k, n, m), hi = rq.bd->hi_in(k, n, m);
+        PairDesc& d = pd[p];
+        std::memset(&d, 0, sizeof d);
+        d.pat = ar.base + ar.aoff[rq.pair_a[k]];
+        d.txt = ar.base + ar.aoff[rq.pair_b[k]];
+        d.n = (int32_t)n;
+        d.m = (int32_t)m;
+        d.tb = static_cast<uint8_t*>(ws.p_band) + L.bo[p];
+        d.res = ws.res() + q;
+        d.ops = ws.ops() + rh.ooff[q];
+        d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
+        d.n_stripes = (uint32_t)(((int64_t)n + S - 1) / S);
+        d.row_stride = (uint32_t)banded_steps(S, hi - lo + 1, (int64_t)m);
+        d.pad[0] = (uint32_t)(int32_t)lo;
+        d.pad[1] = (uint32_t)(int32_t)hi;
+        row_cap = std::max(row_cap, hi - lo + 1);
+        for (int64_t s = 0; s < (int64_t)d.n_stripes; ++s) stats.band_bytes += (uint64_t)(banded_chunks(s * S + 1, S, lo, hi, (int64_t)m) * 16 * S);   // what the fill stores
+    }
+    PairLaunch pl;
+    pl.from_pool = true;
+    if (const int rc = pl.upload_desc(ctx, pd)) return rc;
+    pl.set_params((uint32_t)np, (uint32_t)np, rq.match, rq.mismatch, rq.gap, rq.gt->gap_extend);
+    clock.mark("descriptor build + upload");
+    if (clock.on) std::fprintf(stderr, "[pwa] banded fill RL=%d pairs=%zu hand-off row=%lld entries\n", L.cls.rl, np, (long long)row_cap);
+    HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    HIPC(ctx, pwa::banded_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1]));
+    HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    clock.mark("fill + walk (device)");
+    float a = 0, c = 0;
+    HIPC(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
+    HIPC(ctx, hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]));
+    stats.fill_ms += a;
+    stats.tb_ms += c;
+    return PWA_OK;
+}
+
 // One launch: the pairs' descriptors, fill + walk, the device times into `stats`
 int run_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const TbPlan& plan, const AlignWorkspaces& ws, const Range& rg,
                const Launch& L, const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
+    if (L.cls.banded) return run_banded_launch(ctx, rq, ar, ws, rg, L, rh, stats, clock);
     const size_t np = L.q.size();
     const bool walk_ops = rq.walk_ops();
     std::vector<PairDesc> pd;
@@ -827,6 +917,44 @@ static int put_stats(const AlignStats& st, float* fill_ms, float* walk_ms, uint6
 
 int pwa_align_gotoh_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
     return ctx ? put_stats(ctx->gotoh_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+}
+
+// the banded entry points' own checks (gotoh_batch's, and the band arrays); validate_align checks every pair's band
+static int banded_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, const int32_t* band_lo, const int32_t* band_hi) {
+    if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
+    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    if (rq.n_pairs && (!band_lo || !band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
+    const GotohSpec gs{rq.gap, gap_extend};
+    const BandSpec bs{band_lo, band_hi};
+    rq.gt = &gs;
+    rq.bd = &bs;
+    return align_batch_impl(ctx, rq, ctx->banded_stats);
+}
+
+int pwa_align_banded_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                           const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                           int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells,
+                           const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
+    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
+    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
+                        band_lo, band_hi);
+}
+
+int pwa_align_banded_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                                 const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                                 int32_t* score_out, char* cigar, uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap,
+                                 uint64_t* mdz_off, uint64_t* end_cells, uint64_t* start_cells, uint64_t needed[2], const int32_t* band_lo,
+                                 const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
+    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
+                        band_lo, band_hi);
+}
+
+int pwa_align_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
+    return ctx ? put_stats(ctx->banded_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
 }
 
 int pwa_align_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,

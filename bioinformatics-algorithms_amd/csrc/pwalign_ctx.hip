@@ -72,6 +72,8 @@ void Knobs::read() {
     pipe_runs = num("PWA_PIPE_RUNS", 0);
     scores_route = num("PWA_SCORES_ROUTE", -1);
     tb_engine = num("PWA_TB_ENGINE", -1);
+    banded_rl = num("PWA_BANDED_RL", 0);
+    if (banded_rl != 4 && banded_rl != 8) banded_rl = 0;
     cell16 = num("PWA_CELL16", -1);
     prof16 = num("PWA_PROF16", -1);
     prof16_int = num("PWA_PROF16_INT", -1);

@@ -79,6 +79,7 @@ struct Knobs {
     uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
+    int banded_rl = 0;                          // PWA_BANDED_RL: 4 | 8 = every banded pair on stripes of 64 x 4 / 64 x 8 rows (tests), unset = by band width
     void read();   // (pwalign_ctx.hip)
 };
 
@@ -104,6 +105,7 @@ struct pwa_ctx {
     std::string err;
     AlignStats align_stats, gotoh_stats;   // the last pwa_align_batch / _cigar / pwa_overlaps, the last pwa_align_gotoh_batch(_cigar)
     AlignStats subst_stats;                // the last pwa_align_subst_batch(_cigar)
+    AlignStats banded_stats;               // the last pwa_align_banded_batch(_cigar)
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):

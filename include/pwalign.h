@@ -51,6 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
+ *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -355,6 +356,48 @@ int pwa_align_gotoh_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch,
                                 uint64_t needed[2] /* or NULL */);
 /* Device ms of the fills and walks of the last pwa_align_gotoh_batch(_cigar) on ctx, and the band bytes they wrote. */
 int pwa_align_gotoh_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
+
+/*
+ * BANDED affine-gap alignments of long pairs: pwa_align_gotoh_batch(_cigar) restricted to a diagonal band per pair.
+ *   pwa_align_banded_batch        pwa_align_gotoh_batch's arguments, then band_lo, band_hi (one value each per list pair);
+ *   pwa_align_banded_batch_cigar  pwa_align_gotoh_batch_cigar's arguments, then the same two arrays;
+ *   pwa_align_banded_last_stats   device ms of the fills and walks of the last such call on ctx, and the band bytes they wrote.
+ * Everything not said here is the gotoh block's rule above: E / F / H, "a tie opens", the H tie-break per mode, raw-byte equality, the
+ * sign rule for gap_open / gap_extend, op order, empty-side conventions, op-region layout, string buffers, PWA_RANGE_BYTES, the empty
+ * list, and the range rule (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) < 2^28 (an all-zero scoring counts as 1).
+ * The band.  Cell (i, j), 0 <= i <= n, 0 <= j <= m, is in the band of pair k iff band_lo[k] <= j - i <= band_hi[k].  Every cell
+ * outside the band is -inf in H, E and F.  The result is the exact optimum over the paths that stay inside the band, with the walk and
+ * the tie-breaks applied to the banded matrices.
+ * Boundaries.  A boundary cell keeps its mode's boundary value only when the boundary path that value stands for lies in the band,
+ * else it is -inf:
+ *   NW row 0,  H[0][j] = gap_open + j * gap_extend:  needs band_lo <= 0 and j <= band_hi;
+ *   NW / SG column 0,  H[i][0] = gap_open + i * gap_extend:  needs band_hi >= 0 and -i >= band_lo;
+ *   the free boundaries (SG / SW row 0, SW column 0, value 0):  need the cell itself in the band.
+ * Ends.  NW ends at (n, m); SG at the smallest in-band j with maximal H[n][j]; SW at the first row-major maximum over in-band cells,
+ * or at (0, 0) with no ops when no in-band H is positive.
+ * Validity, checked before any device work, in pair order (the first offending pair decides the error):  PWA_E_INVALID for
+ * band_lo > band_hi; for NW unless band_lo <= 0 <= band_hi and band_lo <= m - n <= band_hi; for SG unless band_hi >= 0 and
+ * n + band_lo <= m (together: an in-band path from row 0 to row n exists).  SW takes any band.  A pair with an empty side follows the
+ * gotoh conventions, provided its band is valid.
+ * Shape.  Patterns and texts of any length the linear calls take.  Band width band_hi - band_lo + 1 of at most 4096 (the hand-off row
+ * of a pair lives in LDS), else PWA_E_CAPACITY.
+ * Identity.  If the walk of the unbanded gotoh alignment stays inside the band, the banded call returns the same score, cells and op
+ * list byte for byte: banded values are <= the unbanded ones everywhere and equal on that path, so every priority choice and every
+ * open / extend bit on the path is the same (the bits of cells whose E or F is -inf are never read by a walk).
+ */
+int pwa_align_banded_batch(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mismatch, int gap_open, int gap_extend,
+                           const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                           const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off,
+                           uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                           const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_align_banded_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch, int gap_open, int gap_extend,
+                                 const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                                 const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                 char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                 char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                 uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                                 uint64_t needed[2] /* or NULL */, const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_align_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
 
 /*
  * Affine-gap ("gotoh") SCORES of many pairs: what pwa_scores / pwa_batch_create are to pwa_align_batch.  Recurrence, boundaries, raw-byte
