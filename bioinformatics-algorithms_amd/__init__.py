@@ -33,6 +33,7 @@ EXPORTS = [
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
     "pwa_align_banded_batch", "pwa_align_banded_batch_cigar", "pwa_align_banded_last_stats",
+    "pwa_scores_banded", "pwa_scores_banded_last_stats",
     "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
@@ -169,6 +170,8 @@ def lib():
     L.pwa_align_banded_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_gotoh_batch_create.argtypes = gotoh_in + [C.c_int, C.POINTER(vp)]
     L.pwa_scores_gotoh.argtypes = gotoh_in + [i32p, u32p, u32p]
+    L.pwa_scores_banded.argtypes = gotoh_in + [i32p, u32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, band_lo, band_hi
+    L.pwa_scores_banded_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p]
     subst_in = batch_in[:2] + [vp, C.c_int, i32p] + gotoh_in[4:]   # ctx, mode, code[256], n_sym, submat, gap_open, gap_extend, sequences, pairs
     L.pwa_align_subst_batch.argtypes = subst_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_align_subst_batch_cigar.argtypes = subst_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
@@ -637,6 +640,29 @@ class Context:
         f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
         self._check(self._L.pwa_align_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_banded_last_stats")
         return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
+
+    def scores_banded(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, want_end=False):
+        """pwa_scores_banded: score (and, with want_end, end cell) of every pair of align_banded_batch's list, without the alignments:
+        no traceback band, no walk -> scores, or (scores, end_i, end_j) as scores_gotoh_oneshot returns them."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        lo, hi = self._band_arrays(bands, n)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei = (C.c_uint32 * max(n, 1))() if want_end else None
+        ej = (C.c_uint32 * max(n, 1))() if want_end else None
+        rc = self._L.pwa_scores_banded(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ei, ej, lo, hi)
+        self._check(rc, "pwa_scores_banded")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n])
+        return list(sc[:n])
+
+    def scores_banded_stats(self):
+        """The last scores_banded: device ms of its score passes, and the in-band cells of its list."""
+        f, c = C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_scores_banded_last_stats(self._h, C.byref(f), C.byref(c)), "pwa_scores_banded_last_stats")
+        return dict(fill_ms=f.value, in_band_cells=c.value)
 
     # -- substitution-matrix scoring (table = subst_table(...)): the gotoh calls with s(i, j) = submat[code[p], code[t]]
     def _subst_head(self, mode, table, gap_open, gap_extend, blob):

@@ -1,5 +1,6 @@
 // pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_align_subst_batch(_cigar),
-// pwa_align_banded_batch(_cigar), pwa_overlaps (the range planner and its stages), pwa_align and pwa_align_matrices.
+// pwa_align_banded_batch(_cigar) and its scores-only form pwa_scores_banded, pwa_overlaps (the range planner and its stages), pwa_align
+// and pwa_align_matrices.
 #include "pwalign_internal.h"
 
 #include <chrono>
@@ -20,6 +21,7 @@ using namespace pwa;
 namespace pwa {
 hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
 hipError_t banded_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill);   // banded_kernels.hip
+hipError_t banded_scores_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st);                    // banded_scores_kernels.hip
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -74,8 +76,9 @@ struct BandSpec {
 int banded_rl_for(int64_t width) { return width >= 1024 ? 8 : 4; }
 
 // What a call hands back next to the scores: the op lists (pwa_align_batch), the strings the device formats from them
-// (pwa_align_batch_cigar), or the overlap lengths the walk computes itself (pwa_overlaps)
-enum AlignOutMode { OUT_OPS, OUT_STRINGS, OUT_OVERLAP };
+// (pwa_align_batch_cigar), the overlap lengths the walk computes itself (pwa_overlaps), or nothing: scores and end cells of a banded
+// list (pwa_scores_banded), whose launches write no band and run no walk
+enum AlignOutMode { OUT_OPS, OUT_STRINGS, OUT_OVERLAP, OUT_SCORES };
 struct AlignOut {
     AlignOutMode mode;
     int32_t* score;
@@ -85,6 +88,7 @@ struct AlignOut {
     uint64_t* n_ops;
     int32_t* overlap;                    // OUT_OVERLAP
     StrOut str;                          // OUT_STRINGS
+    uint32_t *end_i = nullptr, *end_j = nullptr;   // OUT_SCORES: n_pairs each, or null
 };
 // The caller's scoring, sequences, pair list and outputs, as the stages of align_batch_impl see them
 struct AlignRequest {
@@ -103,6 +107,7 @@ struct AlignRequest {
     bool semi() const { return mode == PWA_MODE_SG; }   // (semi-global: NW's classes, guards and codes; no gap shift)
     bool want_ops() const { return out.mode == OUT_OPS; }
     bool want_str() const { return out.mode == OUT_STRINGS; }
+    bool scores_only() const { return out.mode == OUT_SCORES; }   // no band, no walk, no ops (walk_ops() only says: not pwa_overlaps)
     bool walk_ops() const { return out.mode != OUT_OVERLAP; }   // WALK_OPS; the op lists come back (want_ops) or are formatted on the device (want_str)
 };
 
@@ -200,6 +205,7 @@ struct TbPlan {
     int k_match, k_mismatch, k_gap;
     bool mini_ok, wide_ok, tall_stripes;
     const AlignRequest* banded = nullptr;   // the banded call's request (its BandSpec and lengths), else null
+    bool scores = false;                    // ... and it is pwa_scores_banded: no pair has a band or op bytes
     uint64_t band_mult() const { return sband ? 5 : 1; }   // band bytes in HBM per byte of codes
     // (k: the pair's index in the call's list; only the banded class looks at it -- its stripe height follows the pair's band width)
     TbClass class_of(uint64_t n, uint64_t k = 0) const {   // (w of a mini class = its lanes per pair)
@@ -218,6 +224,7 @@ struct TbPlan {
     // mini-stripe form's for a text of m_task columns (its task's longest)
     // (the banded class: stripes x pitch x 64 rl -- from n, the band width and the stripe height; m only clips the widest window)
     uint64_t band_of(const TbClass& c, uint64_t n, uint64_t m_task, uint64_t k = 0) const {
+        if (scores) return 0;
         if (c.banded) {
             const int64_t S = 64 * c.rl, B = banded->bd->hi_in(k, n, m_task) - banded->bd->lo_in(k, n, m_task) + 1;
             return (uint64_t)(((int64_t)n + S - 1) / S * banded_steps(S, B, (int64_t)m_task) * S);
@@ -234,6 +241,7 @@ TbPlan make_tb_plan(const AlignRequest& rq, const Knobs& kn, bool coded, bool sc
     pl.kn = &kn;
     pl.gotoh = rq.gt != nullptr;
     pl.banded = rq.bd ? &rq : nullptr;
+    pl.scores = rq.scores_only();
     pl.sband = score_band && !rq.gt;
     uint64_t longest_sum = 0;
     for (uint64_t k = 0; k < rq.n_pairs; ++k) longest_sum = std::max(longest_sum, rq.slen(rq.pair_a[k]) + rq.slen(rq.pair_b[k]));
@@ -284,7 +292,7 @@ RangeTarget range_target(const AlignRequest& rq, const TbPlan& plan, uint64_t bu
     for (uint64_t k = 0; k < rq.n_pairs; ++k) {
         const uint64_t n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         if (!(n && m) || n > 0x7fffffc0ull || m > 0x7fffffc0ull) continue;
-        total += align_up(plan.band_of(plan.class_of(n, k), n, m, k), 256) * plan.band_mult() + align_up(n + m + 1, 16);
+        total += align_up(plan.band_of(plan.class_of(n, k), n, m, k), 256) * plan.band_mult() + (plan.scores ? 0 : align_up(n + m + 1, 16));
         ++live;
     }
     if (!live) return t;
@@ -366,7 +374,8 @@ void lay_out_launches(const AlignRequest& rq, const TbPlan& plan, Range& rg) {
     rg.band = bo;
 }
 
-// Ranges of consecutive pairs whose traceback bands fit the target (a single pair: whatever it needs, if the free HBM holds it)
+// Ranges of consecutive pairs whose traceback bands fit the target (a single pair: whatever it needs, if the free HBM holds it).
+// A scores-only list has neither band nor op bytes: nothing here cuts it (its arena is built whole before the ranges are planned).
 RangePlan plan_ranges(const AlignRequest& rq, const TbPlan& plan, const RangeTarget& target, uint64_t budget, uint64_t free_b) {
     RangePlan rp;
     auto stop = [&rp](int code, const char* msg) -> RangePlan& {
@@ -374,7 +383,7 @@ RangePlan plan_ranges(const AlignRequest& rq, const TbPlan& plan, const RangeTar
         rp.msg = msg;
         return rp;
     };
-    const bool want_ops = rq.want_ops(), want_str = rq.want_str();
+    const bool want_ops = rq.want_ops(), want_str = rq.want_str(), scores = rq.scores_only();
     const uint64_t band_mult = plan.band_mult();
     for (uint64_t k0 = 0; k0 < rq.n_pairs;) {
         uint64_t k1 = k0, est = 0, opsb = 0, live_in = 0, strb = 0;
@@ -384,12 +393,12 @@ RangePlan plan_ranges(const AlignRequest& rq, const TbPlan& plan, const RangeTar
             const uint64_t need = (n && m) ? align_up(plan.band_of(plan.class_of(n, k1), n, m, k1), 256) : 0;
             const uint64_t sneed = want_str ? str_bound(n + m) : 0;
             if (sneed > 0xffffffffull) return stop(PWA_E_CAPACITY, "strings of one pair may exceed 2^32 bytes");
-            if (k1 > k0 && ((est + need) * band_mult + opsb + n + m > target.chunk_target || (need && live_in >= target.pairs_target) ||
+            if (k1 > k0 && !scores && ((est + need) * band_mult + opsb + n + m > target.chunk_target || (need && live_in >= target.pairs_target) ||
                             strb + sneed > 0xffffffffull))
                 break;
             live_in += need != 0;
             est += need;
-            opsb += align_up(n + m + 1, 16);
+            opsb += scores ? 0 : align_up(n + m + 1, 16);
             strb += sneed;
             ++k1;
         }
@@ -430,10 +439,10 @@ int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& pl
     ws.aux_part_at = ws.aux_len_at + align_up(len_words * 4, 256);
     if (rp.ranges.empty()) return PWA_OK;
     // + one traceback window: the walk stages whole windows
-    HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, rp.band_cap + 32768, ws.d_band, &ws.p_band));
+    if (!rq.scores_only()) HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, rp.band_cap + 32768, ws.d_band, &ws.p_band));
     if (plan.sband)
         HIPC(ctx, cached_workspace(ctx->sband_cache, ctx->sband_cache_bytes, rp.band_cap * sizeof(int32_t), ws.d_sband, &ws.p_sband));
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
+    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
     HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * sizeof(PairResult), ws.d_res_own, &ws.p_res));
     if (rq.want_str()) {
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], rp.str_cap, ws.d_str_own, &ws.p_str));
@@ -492,12 +501,21 @@ int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& a
     return PWA_OK;
 }
 
+// Cells (i, j) of an n x m matrix, 1 <= i <= n, 1 <= j <= m, with lo <= j - i <= hi: what a banded fill computes
+uint64_t banded_cells(int64_t n, int64_t m, int64_t lo, int64_t hi) {
+    uint64_t cells = 0;
+    for (int64_t d = std::max(lo, 1 - n); d <= std::min(hi, m - 1); ++d) cells += (uint64_t)(d >= 0 ? std::min(n, m - d) : std::min(n + d, m));
+    return cells;
+}
+
 // One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; banded_kernels.hip
-// sizes the grid and launches fill + walk; the device times into `stats`
+// sizes the grid and launches fill + walk; the device times into `stats`.  A scores-only request: the same descriptors without band
+// and op regions, banded_scores_kernels.hip's pass alone, and the pairs' in-band cells into `stats`
 int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, const Launch& L,
                       const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const size_t np = L.q.size();
     const int64_t S = 64 * L.cls.rl;
+    const bool scores = rq.scores_only();
     std::vector<PairDesc> pd(np);
     int64_t row_cap = 1;
     for (size_t p = 0; p < np; ++p) {
@@ -509,33 +527,39 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
         d.txt = ar.base + ar.aoff[rq.pair_b[k]];
         d.n = (int32_t)n;
         d.m = (int32_t)m;
-        d.tb = static_cast<uint8_t*>(ws.p_band) + L.bo[p];
+        d.tb = scores ? nullptr : static_cast<uint8_t*>(ws.p_band) + L.bo[p];
         d.res = ws.res() + q;
-        d.ops = ws.ops() + rh.ooff[q];
+        d.ops = scores ? nullptr : ws.ops() + rh.ooff[q];
         d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
         d.n_stripes = (uint32_t)(((int64_t)n + S - 1) / S);
         d.row_stride = (uint32_t)banded_steps(S, hi - lo + 1, (int64_t)m);
         d.pad[0] = (uint32_t)(int32_t)lo;
         d.pad[1] = (uint32_t)(int32_t)hi;
         row_cap = std::max(row_cap, hi - lo + 1);
-        for (int64_t s = 0; s < (int64_t)d.n_stripes; ++s) stats.band_bytes += (uint64_t)(banded_chunks(s * S + 1, S, lo, hi, (int64_t)m) * 16 * S);   // what the fill stores
+        if (scores) stats.cells += banded_cells((int64_t)n, (int64_t)m, lo, hi);
+        for (int64_t s = 0; !scores && s < (int64_t)d.n_stripes; ++s) stats.band_bytes += (uint64_t)(banded_chunks(s * S + 1, S, lo, hi, (int64_t)m) * 16 * S);   // what the fill stores
     }
     PairLaunch pl;
     pl.from_pool = true;
     if (const int rc = pl.upload_desc(ctx, pd)) return rc;
     pl.set_params((uint32_t)np, (uint32_t)np, rq.match, rq.mismatch, rq.gap, rq.gt->gap_extend);
     clock.mark("descriptor build + upload");
-    if (clock.on) std::fprintf(stderr, "[pwa] banded fill RL=%d pairs=%zu hand-off row=%lld entries\n", L.cls.rl, np, (long long)row_cap);
+    if (clock.on) std::fprintf(stderr, "[pwa] banded %s RL=%d pairs=%zu hand-off row=%lld entries\n", scores ? "scores" : "fill", L.cls.rl, np, (long long)row_cap);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    HIPC(ctx, pwa::banded_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1]));
+    if (scores) {
+        HIPC(ctx, pwa::banded_scores_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream));
+        HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    } else {
+        HIPC(ctx, pwa::banded_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1]));
+    }
     HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
-    clock.mark("fill + walk (device)");
+    clock.mark(scores ? "scores pass (device)" : "fill + walk (device)");
     float a = 0, c = 0;
     HIPC(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
     HIPC(ctx, hipEventElapsedTime(&c, ctx->ev[1], ctx->ev[2]));
     stats.fill_ms += a;
-    stats.tb_ms += c;
+    if (!scores) stats.tb_ms += c;
     return PWA_OK;
 }
 
@@ -691,6 +715,8 @@ int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& w
             o.end_cells[2 * k] = res[q].end_i;
             o.end_cells[2 * k + 1] = res[q].end_j;
         }
+        if (o.end_i) o.end_i[k] = res[q].end_i;
+        if (o.end_j) o.end_j[k] = res[q].end_j;
     }
     return PWA_OK;
 }
@@ -732,7 +758,7 @@ int align_batch_impl(pwa_ctx* ctx, const AlignRequest& rq, AlignStats& stats) tr
         clock.mark("scatter to caller buffers");
     }
     if (clock.on) std::fprintf(stderr, "[pwa] %s: %llu pairs in %zu range(s): fills %.3f ms, walks %.3f ms (device), %.2f GB of band written\n",
-                               rq.want_ops() ? "align_batch" : rq.want_str() ? "align_batch_cigar" : "overlaps", (unsigned long long)rq.n_pairs,
+                               rq.want_ops() ? "align_batch" : rq.want_str() ? "align_batch_cigar" : rq.scores_only() ? "scores_banded" : "overlaps", (unsigned long long)rq.n_pairs,
                                rp.ranges.size(), stats.fill_ms, stats.tb_ms, (double)stats.band_bytes / 1e9);
     if (rq.want_str()) {
         const StrOut& str = rq.out.str;
@@ -920,7 +946,7 @@ int pwa_align_gotoh_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_m
 }
 
 // the banded entry points' own checks (gotoh_batch's, and the band arrays); validate_align checks every pair's band
-static int banded_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, const int32_t* band_lo, const int32_t* band_hi) {
+static int banded_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, const int32_t* band_lo, const int32_t* band_hi, AlignStats& stats) {
     if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
     if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
     if (rq.n_pairs && (!band_lo || !band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
@@ -928,7 +954,7 @@ static int banded_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, const int
     const BandSpec bs{band_lo, band_hi};
     rq.gt = &gs;
     rq.bd = &bs;
-    return align_batch_impl(ctx, rq, ctx->banded_stats);
+    return align_batch_impl(ctx, rq, stats);
 }
 
 int pwa_align_banded_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
@@ -939,7 +965,7 @@ int pwa_align_banded_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int 
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
     const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
     return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
-                        band_lo, band_hi);
+                        band_lo, band_hi, ctx->banded_stats);
 }
 
 int pwa_align_banded_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
@@ -950,11 +976,28 @@ int pwa_align_banded_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch
     if (!ctx) return PWA_E_INVALID;
     const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
     return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
-                        band_lo, band_hi);
+                        band_lo, band_hi, ctx->banded_stats);
 }
 
 int pwa_align_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
     return ctx ? put_stats(ctx->banded_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+}
+
+// the scores-only form: the same request with nothing to hand back but scores and end cells (OUT_SCORES: no band, no walk)
+int pwa_scores_banded(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
+                      uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out,
+                      uint32_t* end_j_out, const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
+    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
+                        band_lo, band_hi, ctx->banded_scores_stats);
+}
+
+int pwa_scores_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, uint64_t* in_band_cells) {
+    if (!ctx) return PWA_E_INVALID;
+    if (fill_ms) *fill_ms = ctx->banded_scores_stats.fill_ms;
+    if (in_band_cells) *in_band_cells = ctx->banded_scores_stats.cells;
+    return PWA_OK;
 }
 
 int pwa_align_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,

@@ -79,14 +79,16 @@ struct Knobs {
     uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
-    int banded_rl = 0;                          // PWA_BANDED_RL: 4 | 8 = every banded pair on stripes of 64 x 4 / 64 x 8 rows (tests), unset = by band width
+    int banded_rl = 0;                          // PWA_BANDED_RL: 4 | 8 = every banded pair (alignments and scores) on stripes of 64 x 4 / 64 x 8 rows (tests), unset = by band width
     void read();   // (pwalign_ctx.hip)
 };
 
-// Device ms of the fills / walks of a batch of full alignments (event-timed, summed over its launches) and the band bytes they wrote
+// Device ms of the fills / walks of a batch of full alignments (event-timed, summed over its launches) and the band bytes they wrote;
+// a scores-only banded call: no walk and no band, the in-band cells of its pairs instead
 struct AlignStats {
     float fill_ms = 0.f, tb_ms = 0.f;
     uint64_t band_bytes = 0;
+    uint64_t cells = 0;
 };
 
 // pwa_align_affine_batch: pairs it ran on the stripe engine, device ms of their fills / walks, band bytes written
@@ -106,6 +108,7 @@ struct pwa_ctx {
     AlignStats align_stats, gotoh_stats;   // the last pwa_align_batch / _cigar / pwa_overlaps, the last pwa_align_gotoh_batch(_cigar)
     AlignStats subst_stats;                // the last pwa_align_subst_batch(_cigar)
     AlignStats banded_stats;               // the last pwa_align_banded_batch(_cigar)
+    AlignStats banded_scores_stats;        // the last pwa_scores_banded
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):

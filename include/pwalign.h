@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
- *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
+ *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -398,6 +398,23 @@ int pwa_align_banded_batch_cigar(pwa_ctx *ctx, int mode, int match, int mismatch
                                  uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
                                  uint64_t needed[2] /* or NULL */, const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
 int pwa_align_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
+
+/*
+ * BANDED affine-gap SCORES of long pairs: the banded block above without alignments -- no traceback band, no walk.
+ * For every list that pwa_align_banded_batch accepts, score_out[k], end_i_out[k] and end_j_out[k] equal that call's score and end cell for pair k.
+ * That covers the boundary rule, the end rule per mode, the empty-side conventions, the empty list (PWA_OK), and validity: the same checks
+ * with the same codes, before any device work and in pair order; a null score_out, band_lo or band_hi with n_pairs > 0 is PWA_E_INVALID.
+ * end_i_out / end_j_out may each be NULL.  No band bytes exist, so PWA_RANGE_BYTES does not cut the list.
+ *   pwa_scores_banded_last_stats  device ms of the score passes of the last such call on ctx, and its in-band cells: the cells (i, j),
+ *                                 1 <= i <= n, 1 <= j <= m, band_lo <= j - i <= band_hi, summed over the list (what the recurrence
+ *                                 computes; a pair with an empty side counts 0).  A call that fails validation leaves them unchanged.
+ * Not offered: a batch object (no pwa_banded_batch_create / pwa_batch_run, no sharding), and substitution matrices in the band.
+ */
+int pwa_scores_banded(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mismatch, int gap_open, int gap_extend,
+                      const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                      const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint32_t *end_i_out /* or NULL */,
+                      uint32_t *end_j_out /* or NULL */, const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_scores_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, uint64_t *in_band_cells);
 
 /*
  * Affine-gap ("gotoh") SCORES of many pairs: what pwa_scores / pwa_batch_create are to pwa_align_batch.  Recurrence, boundaries, raw-byte
