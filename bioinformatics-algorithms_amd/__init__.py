@@ -35,6 +35,7 @@ EXPORTS = [
     "pwa_align_banded_batch", "pwa_align_banded_batch_cigar", "pwa_align_banded_last_stats",
     "pwa_scores_banded", "pwa_scores_banded_last_stats",
     "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
+    "pwa_align_banded_subst_batch", "pwa_align_banded_subst_batch_cigar", "pwa_scores_banded_subst",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
@@ -178,6 +179,9 @@ def lib():
     L.pwa_align_subst_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     L.pwa_subst_batch_create.argtypes = subst_in + [C.c_int, C.POINTER(vp)]
     L.pwa_scores_subst.argtypes = subst_in + [i32p, u32p, u32p]
+    L.pwa_align_banded_subst_batch.argtypes = L.pwa_align_subst_batch.argtypes + [i32p, i32p]   # ..., band_lo, band_hi
+    L.pwa_align_banded_subst_batch_cigar.argtypes = L.pwa_align_subst_batch_cigar.argtypes + [i32p, i32p]
+    L.pwa_scores_banded_subst.argtypes = subst_in + [i32p, u32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, band_lo, band_hi
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
     L.pwa_cigar_bound.argtypes = [C.c_uint64]
@@ -699,6 +703,40 @@ class Context:
         ei = (C.c_uint32 * max(n, 1))() if want_end else None
         ej = (C.c_uint32 * max(n, 1))() if want_end else None
         self._check(self._L.pwa_scores_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej), "pwa_scores_subst")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n])
+        return list(sc[:n])
+
+    # -- ... in a diagonal band per pair: patterns of any length (the banded calls with a table; they report into the banded stats)
+    def align_banded_subst_batch(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands):
+        """pwa_align_banded_subst_batch: align_subst_batch over the cells with lo <= j - i <= hi, bands = [(lo, hi)] per pair ->
+        [dict(score, ops, end, start)] as align_banded_batch returns them."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._align_ops(self._L.pwa_align_banded_subst_batch, "pwa_align_banded_subst_batch", head, packed, pair_a, pair_b,
+                               self._band_arrays(bands, len(pair_a)))
+
+    def align_banded_subst_batch_cigar(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands):
+        """pwa_align_banded_subst_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_banded_batch_cigar returns them; MD:Z
+        reports byte identity, not score sign."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._align_strings(self._L.pwa_align_banded_subst_batch_cigar, "pwa_align_banded_subst_batch_cigar", head, packed, pair_a, pair_b,
+                                   self._band_arrays(bands, len(pair_a)))
+
+    def scores_banded_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands, want_end=False):
+        """pwa_scores_banded_subst: score (and, with want_end, end cell) of every pair of align_banded_subst_batch's list, without the
+        alignments -> scores, or (scores, end_i, end_j) as scores_banded returns them."""
+        blob, off, seqs = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, blob)
+        n = len(pair_a)
+        lo, hi = self._band_arrays(bands, n)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei = (C.c_uint32 * max(n, 1))() if want_end else None
+        ej = (C.c_uint32 * max(n, 1))() if want_end else None
+        self._check(self._L.pwa_scores_banded_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej, lo, hi), "pwa_scores_banded_subst")
         if want_end:
             return list(sc[:n]), list(ei[:n]), list(ej[:n])
         return list(sc[:n])

@@ -1,6 +1,7 @@
 // pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_align_subst_batch(_cigar),
-// pwa_align_banded_batch(_cigar) and its scores-only form pwa_scores_banded, pwa_overlaps (the range planner and its stages), pwa_align
-// and pwa_align_matrices.
+// pwa_align_banded_batch(_cigar) and its scores-only form pwa_scores_banded, their substitution-matrix forms
+// pwa_align_banded_subst_batch(_cigar) and pwa_scores_banded_subst, pwa_overlaps (the range planner and its stages), pwa_align and
+// pwa_align_matrices.
 #include "pwalign_internal.h"
 
 #include <chrono>
@@ -22,6 +23,8 @@ namespace pwa {
 hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
 hipError_t banded_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill);   // banded_kernels.hip
 hipError_t banded_scores_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st);                    // banded_scores_kernels.hip
+hipError_t banded_subst_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk,
+                               const uint32_t* blob, int n_sym, int stride);                                                         // banded_subst_kernels.hip
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -54,7 +57,8 @@ uint64_t str_bound(uint64_t n_plus_m) { return pwa_cigar_bound(n_plus_m) + pwa_m
 struct GotohSpec {
     int gap_open, gap_extend;
 };
-// pwa_align_subst_batch(_cigar): the gotoh classes with the diagonal score from the caller's table (always beside a GotohSpec)
+// pwa_align_subst_batch(_cigar): the gotoh classes with the diagonal score from the caller's table (always beside a GotohSpec); beside a
+// BandSpec too: pwa_align_banded_subst_batch(_cigar), pwa_scores_banded_subst
 struct SubstSpec {
     SubstRef tab;      // SubstTable::dev and its layout
     int64_t max_abs;   // max |submat|: the range rule's score term
@@ -147,7 +151,8 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
                 return fail(ctx, PWA_E_INVALID, "banded SG alignment: needs band_hi >= 0 and n + band_lo <= m");
             if (hi - lo + 1 > (int64_t)kBandedMaxWidth) return fail(ctx, PWA_E_CAPACITY, "banded alignment: band wider than 4096 diagonals");
             if (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 28))
-                return fail(ctx, PWA_E_CAPACITY, "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
+                return fail(ctx, PWA_E_CAPACITY, rq.sb ? "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) must stay below 2^28"
+                                                       : "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
             continue;
         }
         if (n > kGotohMaxN) return fail(ctx, PWA_E_CAPACITY, "gotoh alignments take patterns of at most 1024 symbols");
@@ -510,7 +515,8 @@ uint64_t banded_cells(int64_t n, int64_t m, int64_t lo, int64_t hi) {
 
 // One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; banded_kernels.hip
 // sizes the grid and launches fill + walk; the device times into `stats`.  A scores-only request: the same descriptors without band
-// and op regions, banded_scores_kernels.hip's pass alone, and the pairs' in-band cells into `stats`
+// and op regions, banded_scores_kernels.hip's pass alone, and the pairs' in-band cells into `stats`.  With a table (rq.sb) the same
+// descriptors go to banded_subst_kernels.hip's fill or pass; the walk is the same
 int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, const Launch& L,
                       const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const size_t np = L.q.size();
@@ -542,11 +548,17 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
     PairLaunch pl;
     pl.from_pool = true;
     if (const int rc = pl.upload_desc(ctx, pd)) return rc;
-    pl.set_params((uint32_t)np, (uint32_t)np, rq.match, rq.mismatch, rq.gap, rq.gt->gap_extend);
+    // (a table launch: match / mismatch = +- max |submat| -- banded_body places its sentinel by them; the range rule keeps them below 2^27)
+    const int k_match = rq.sb ? (int)rq.sb->max_abs : rq.match, k_mismatch = rq.sb ? -(int)rq.sb->max_abs : rq.mismatch;
+    pl.set_params((uint32_t)np, (uint32_t)np, k_match, k_mismatch, rq.gap, rq.gt->gap_extend);
     clock.mark("descriptor build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] banded %s RL=%d pairs=%zu hand-off row=%lld entries\n", scores ? "scores" : "fill", L.cls.rl, np, (long long)row_cap);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (scores) {
+    if (rq.sb) {
+        const SubstRef& t = rq.sb->tab;
+        HIPC(ctx, pwa::banded_subst_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], !scores, t.tab, t.n_sym, t.stride));
+        if (scores) HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    } else if (scores) {
         HIPC(ctx, pwa::banded_scores_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream));
         HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     } else {
@@ -897,21 +909,27 @@ static int gotoh_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend) {
 
 // ... and the substitution-matrix ones': the table is checked, copied and uploaded for the call (the device copy goes back to the
 // context's buffer list when the call returns)
-static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n_sym, const int32_t* submat, int gap_extend) try {
+// With band arrays (band_lo / band_hi, `stats` the banded slot of the calling form) the request also gets its BandSpec: the banded
+// substitution-matrix calls.  The table is uploaded once per call; every range of a PWA_RANGE_BYTES-cut list launches with it.
+static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n_sym, const int32_t* submat, int gap_extend, AlignStats& stats,
+                       bool banded = false, const int32_t* band_lo = nullptr, const int32_t* band_hi = nullptr) try {
     if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gap penalties must be <= 0 (gap_open + L * gap_extend)");
     if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
     SubstTable tab;
     int rc = subst_prepare(ctx, code, n_sym, submat, tab);
     if (rc != PWA_OK) return rc;
+    if (banded && rq.n_pairs && (!band_lo || !band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
     const GotohSpec gs{rq.gap, gap_extend};
     SubstSpec ss{{nullptr, tab.n_sym, tab.stride}, tab.max_abs};
+    const BandSpec bs{band_lo, band_hi};
     rq.gt = &gs;
     rq.sb = &ss;
+    if (banded) rq.bd = &bs;
     if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (before anything is allocated; align_batch_impl checks again)
     HIPC(ctx, hipSetDevice(ctx->device));
     if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
     ss.tab.tab = tab.dev.as<uint32_t>();
-    return align_batch_impl(ctx, rq, ctx->subst_stats);
+    return align_batch_impl(ctx, rq, stats);
 } catch (const std::bad_alloc&) {
     return fail(ctx, PWA_E_NOMEM, "host allocation failed");
 }
@@ -1008,7 +1026,7 @@ int pwa_align_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
     const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
     return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend);
+                       gap_extend, ctx->subst_stats);
 }
 
 int pwa_align_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
@@ -1019,7 +1037,40 @@ int pwa_align_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int
     if (!ctx) return PWA_E_INVALID;
     const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
     return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend);
+                       gap_extend, ctx->subst_stats);
+}
+
+// the banded forms: subst_batch with the band arrays; they report where the banded calls report
+int pwa_align_banded_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                                 const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                                 uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
+                                 uint64_t* start_cells, const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
+    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
+    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
+                       gap_extend, ctx->banded_stats, true, band_lo, band_hi);
+}
+
+int pwa_align_banded_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                                       const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
+                                       const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar, uint64_t cigar_cap,
+                                       uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
+                                       uint64_t* start_cells, uint64_t needed[2], const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
+    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
+                       gap_extend, ctx->banded_stats, true, band_lo, band_hi);
+}
+
+int pwa_scores_banded_subst(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
+                            const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                            uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, const int32_t* band_lo,
+                            const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
+    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
+                       gap_extend, ctx->banded_scores_stats, true, band_lo, band_hi);
 }
 
 int pwa_align_subst_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {

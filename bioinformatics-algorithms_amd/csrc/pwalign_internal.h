@@ -107,8 +107,8 @@ struct pwa_ctx {
     std::string err;
     AlignStats align_stats, gotoh_stats;   // the last pwa_align_batch / _cigar / pwa_overlaps, the last pwa_align_gotoh_batch(_cigar)
     AlignStats subst_stats;                // the last pwa_align_subst_batch(_cigar)
-    AlignStats banded_stats;               // the last pwa_align_banded_batch(_cigar)
-    AlignStats banded_scores_stats;        // the last pwa_scores_banded
+    AlignStats banded_stats;               // the last pwa_align_banded_batch(_cigar) or pwa_align_banded_subst_batch(_cigar)
+    AlignStats banded_scores_stats;        // the last pwa_scores_banded or pwa_scores_banded_subst
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):

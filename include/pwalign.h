@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
- *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
+ *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded and their _subst forms: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -408,7 +408,7 @@ int pwa_align_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_
  *   pwa_scores_banded_last_stats  device ms of the score passes of the last such call on ctx, and its in-band cells: the cells (i, j),
  *                                 1 <= i <= n, 1 <= j <= m, band_lo <= j - i <= band_hi, summed over the list (what the recurrence
  *                                 computes; a pair with an empty side counts 0).  A call that fails validation leaves them unchanged.
- * Not offered: a batch object (no pwa_banded_batch_create / pwa_batch_run, no sharding), and substitution matrices in the band.
+ * Not offered: a batch object (no pwa_banded_batch_create / pwa_batch_run, no sharding).
  */
 int pwa_scores_banded(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mismatch, int gap_open, int gap_extend,
                       const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
@@ -484,6 +484,53 @@ int pwa_scores_subst(pwa_ctx *ctx, int mode, const uint8_t code[256], int n_sym,
                      const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
                      uint64_t n_pairs, int32_t *score_out, uint32_t *end_i_out, uint32_t *end_j_out);
 int pwa_align_subst_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *band_bytes);
+
+/*
+ * BANDED affine-gap alignments and scores of long pairs UNDER A SUBSTITUTION MATRIX: the banded calls with the table of the block
+ * above, for what neither family takes alone -- a protein of more than 1024 residues under BLOSUM-style scores, a long read or contig
+ * with a neutral N, transitions scored apart from transversions, or folded lower case.
+ *   pwa_align_banded_subst_batch        pwa_align_subst_batch's arguments, then band_lo, band_hi (one value each per list pair);
+ *   pwa_align_banded_subst_batch_cigar  pwa_align_subst_batch_cigar's arguments, then the same two arrays;
+ *   pwa_scores_banded_subst             pwa_scores_banded's arguments with (code, n_sym, submat) in place of (match, mismatch).
+ * Semantics: exactly those of the banded block (pwa_align_banded_batch, pwa_scores_banded) -- the band, the boundary rule, the ends per
+ * mode, validity, pairs with an empty side, the empty list (PWA_OK), PWA_RANGE_BYTES (the table is uploaded once per call and serves
+ * every range; the scores form is not cut), the op regions and the string buffers -- with
+ *   s(i,j) = submat[ code[p[i-1]] * n_sym + code[t[j-1]] ]
+ * and code, n_sym, submat as in the substitution-matrix block: the table may be asymmetric and may hold any signs; both are copied
+ * during the call.  CIGAR and MD:Z come from the ops and the RAW bytes: MD:Z reports byte identity, not the sign of the score.
+ * Range: every result is exact while (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) < 2^28; a pair beyond that is
+ * PWA_E_CAPACITY.  Shape: patterns and texts of any length the linear calls take; band width of at most 4096, else PWA_E_CAPACITY.
+ * Checks, all before any device work: first the call's own, as pwa_align_subst_batch makes them (PWA_E_INVALID for a null code or
+ * submat, n_sym outside 1 .. 32, a code[] entry >= n_sym, gap_open > 0 or gap_extend > 0, a null band_lo or band_hi with n_pairs > 0);
+ * then per pair, in pair order, the band's validity, its width and the range rule (the first offending pair decides the error).
+ * Why the sentinel of the banded kernels still lies below every real value: with A = max(max |submat|, |gap_open| + |gap_extend|, 1)
+ * every H, E or F that stands for a path inside the band is a sum of at most n + m + 1 steps of magnitude <= A each, so |V| < 2^28 - A
+ * under the range rule; the alignment fill's sentinel key -2^31 + 8 A + 1 is below every key V * 8 + 0..7, the score pass's plain
+ * sentinel -2^30 below every V and V + gap_open + gap_extend, and a sentinel meets at most one gap extension (>= -A) before the sum is
+ * compared and dropped.  Only |s| enters the bound: asymmetry and positive off-diagonal entries change nothing.
+ * Stats: the alignment calls report into pwa_align_banded_last_stats, the score call into pwa_scores_banded_last_stats (its in-band
+ * cell count means what it means there); pwa_align_subst_last_stats is not touched.  A call that fails validation leaves them unchanged.
+ * Not offered: a batch object, named matrices.
+ */
+int pwa_align_banded_subst_batch(pwa_ctx *ctx, int mode /* NW, SW, SG */, const uint8_t code[256], int n_sym, const int32_t *submat,
+                                 int gap_open, int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                 const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops,
+                                 const uint64_t *ops_off, uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */,
+                                 uint64_t *start_cells /* 2*n_pairs or NULL */, const int32_t *band_lo /* n_pairs */,
+                                 const int32_t *band_hi /* n_pairs */);
+int pwa_align_banded_subst_batch_cigar(pwa_ctx *ctx, int mode, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                                       int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                       const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                       char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                       char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                       uint64_t *end_cells /* 2*n_pairs or NULL */, uint64_t *start_cells /* 2*n_pairs or NULL */,
+                                       uint64_t needed[2] /* or NULL */, const int32_t *band_lo /* n_pairs */,
+                                       const int32_t *band_hi /* n_pairs */);
+int pwa_scores_banded_subst(pwa_ctx *ctx, int mode /* NW, SW, SG */, const uint8_t code[256], int n_sym, const int32_t *submat,
+                            int gap_open, int gap_extend, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                            const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                            uint32_t *end_i_out /* or NULL */, uint32_t *end_j_out /* or NULL */, const int32_t *band_lo /* n_pairs */,
+                            const int32_t *band_hi /* n_pairs */);
 
 /*
  * The -g selection without the op lists: hw2.cpp:342-350 keeps, of every pair's global alignment, only
