@@ -34,6 +34,7 @@ EXPORTS = [
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
     "pwa_align_banded_batch", "pwa_align_banded_batch_cigar", "pwa_align_banded_last_stats",
     "pwa_scores_banded", "pwa_scores_banded_last_stats",
+    "pwa_extend_banded_batch", "pwa_extend_banded_batch_cigar", "pwa_scores_extend_banded", "pwa_extend_banded_last_stats",
     "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
     "pwa_align_banded_subst_batch", "pwa_align_banded_subst_batch_cigar", "pwa_scores_banded_subst",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
@@ -173,6 +174,11 @@ def lib():
     L.pwa_scores_gotoh.argtypes = gotoh_in + [i32p, u32p, u32p]
     L.pwa_scores_banded.argtypes = gotoh_in + [i32p, u32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, band_lo, band_hi
     L.pwa_scores_banded_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p]
+    ext_in = [vp] + gotoh_in[2:6] + [C.c_int] + gotoh_in[6:]   # ctx, match, mismatch, gap_open, gap_extend, xdrop, sequences, pairs
+    L.pwa_extend_banded_batch.argtypes = ext_in + [i32p, vp, u64p, u64p, u64p, u32p, i32p, i32p]   # ..., end_cells, rows, band_lo, band_hi
+    L.pwa_extend_banded_batch_cigar.argtypes = ext_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u32p, u64p, i32p, i32p]
+    L.pwa_scores_extend_banded.argtypes = ext_in + [i32p, u32p, u32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, rows, band_lo, band_hi
+    L.pwa_extend_banded_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]
     subst_in = batch_in[:2] + [vp, C.c_int, i32p] + gotoh_in[4:]   # ctx, mode, code[256], n_sym, submat, gap_open, gap_extend, sequences, pairs
     L.pwa_align_subst_batch.argtypes = subst_in + [i32p, vp, u64p, u64p, u64p, u64p]
     L.pwa_align_subst_batch_cigar.argtypes = subst_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p]
@@ -557,8 +563,9 @@ class Context:
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=()):
-        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`)"""
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False):
+        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`);
+        ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result"""
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -572,14 +579,17 @@ class Context:
         sc = (C.c_int32 * max(n, 1))()
         nops = (C.c_uint64 * max(n, 1))()
         endc = (C.c_uint64 * (2 * max(n, 1)))()
-        startc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *tail)
         self._check(rc, name)
         raw = memoryview(ops)
+        if ext:
+            return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
+                         rows=startc[k]) for k in range(n)]
         return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=()):
+    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False):
         """... and one that returns CIGAR and MD:Z strings built on the device"""
         import numpy as np
         blob, off, seqs = pack_sequences(seqs)
@@ -595,13 +605,16 @@ class Context:
         md_off = np.zeros(n + 1, dtype=np.uint64)
         sc = (C.c_int32 * max(n, 1))()
         endc = (C.c_uint64 * (2 * max(n, 1)))()
-        startc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
         u64p = C.POINTER(C.c_uint64)
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
                 md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None, *tail)
         self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
+        if ext:
+            return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
+                         rows=startc[k]) for k in range(n)]
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
@@ -667,6 +680,44 @@ class Context:
         f, c = C.c_float(0), C.c_uint64(0)
         self._check(self._L.pwa_scores_banded_last_stats(self._h, C.byref(f), C.byref(c)), "pwa_scores_banded_last_stats")
         return dict(fill_ms=f.value, in_band_cells=c.value)
+
+    # -- banded X-drop extension ("EXT"): anchored at (0, 0), free end, rows given up xdrop below the best (include/pwalign.h)
+    def extend_banded_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, xdrop):
+        """pwa_extend_banded_batch: extension alignments from (0, 0) inside bands = [(lo, hi)] per pair with lo <= 0 <= hi; xdrop < 0:
+        no row stops -> [dict(score, ops, end, start, rows)] as align_banded_batch returns them, start = (0, 0), rows = the rows
+        considered before the X-drop stopped the sweep."""
+        return self._align_ops(self._L.pwa_extend_banded_batch, "pwa_extend_banded_batch",
+                               (self._h, match, mismatch, gap_open, gap_extend, xdrop), seqs, pair_a, pair_b,
+                               self._band_arrays(bands, len(pair_a)), ext=True)
+
+    def extend_banded_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, xdrop):
+        """pwa_extend_banded_batch_cigar -> [dict(score, cigar, mdz, end, start, rows)] as align_banded_batch_cigar returns them."""
+        return self._align_strings(self._L.pwa_extend_banded_batch_cigar, "pwa_extend_banded_batch_cigar",
+                                   (self._h, match, mismatch, gap_open, gap_extend, xdrop), seqs, pair_a, pair_b,
+                                   self._band_arrays(bands, len(pair_a)), ext=True)
+
+    def scores_extend_banded(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, xdrop, want_end=False):
+        """pwa_scores_extend_banded: score (and, with want_end, end cell and rows) of every pair of extend_banded_batch's list, without
+        the alignments -> scores, or (scores, end_i, end_j, rows)."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        lo, hi = self._band_arrays(bands, n)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei, ej, rw = [(C.c_uint32 * max(n, 1))() if want_end else None for _ in range(3)]
+        rc = self._L.pwa_scores_extend_banded(self._h, match, mismatch, gap_open, gap_extend, xdrop, blob, off, len(seqs), pa, pb, n, sc, ei, ej, rw, lo, hi)
+        self._check(rc, "pwa_scores_extend_banded")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n]), list(rw[:n])
+        return list(sc[:n])
+
+    def extend_banded_stats(self):
+        """The last extend_banded_batch(_cigar) or scores_extend_banded: device ms of its fills and walks (walk_ms = 0 after the scores
+        call), and the rows it considered (the sum of `rows`)."""
+        f, w, r = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(self._L.pwa_extend_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(r)), "pwa_extend_banded_last_stats")
+        return dict(fill_ms=f.value, walk_ms=w.value, rows_considered=r.value)
 
     # -- substitution-matrix scoring (table = subst_table(...)): the gotoh calls with s(i, j) = submat[code[p], code[t]]
     def _subst_head(self, mode, table, gap_open, gap_extend, blob):

@@ -27,6 +27,13 @@
 // gap extension (>= -8 A) or the -2 between the two H forms -- never twice, because the sum is compared, loses against SENT or a real
 // key, and is dropped.  Sums that do wrap belong to out-of-band cells, whose results are discarded by the mask.  Every in-band cell of
 // a valid band is reachable from the boundary inside the band (pwalign.h: validity), so its H is real.
+// The EXT form (MODE = kBandedExt; pwa_extend_banded_batch) is NW's matrix -- boundaries, priorities, code bytes, so the
+// NW walk reads its band -- with SW's per-row first-maximum keys over signed H, and a test at the end of every stripe
+// (banded_ext_stripe_end) that folds the stripe's rows into the best-cell record in row order and finds the first row that the
+// X-drop stops; the wave then leaves the stripe loop.  Why its row key fits: the key is H << 4 | (15 - q) with H of either sign, and
+// the host admits an EXT pair only while (n + m + 2) A < 2^27 -- one bit tighter than above -- so |H| <= (n + m) A < 2^27 - 2 A and
+// H * 16 + 0..15 lies strictly inside int32; "no in-band cell" is INT_MIN, below every real key, and INT_MIN >> 4 = -2^27 is below
+// every real H.  best - xdrop cannot wrap: 0 <= best < 2^27 and 0 <= xdrop <= 2^27.
 // Traceback band: per pair, stripe after stripe, a fixed pitch of banded_steps() steps of [64 lanes][RL code bytes] (BandGeo<64, RL>,
 // one aligned store per lane and step); step t of stripe s holds lane k's column c0a(s) + t - k.
 #pragma once
@@ -36,6 +43,8 @@ namespace pwa {
 
 constexpr int kBandedMaxWidth = 4096;   // band_hi - band_lo + 1: the hand-off row of a wave is at most 32 KiB of LDS
 constexpr int kBandedWaves = 4;         // waves (pairs in flight) per workgroup
+constexpr int kBandedExt = 3;           // MODE of the EXT form (extension from (0, 0) with an X-drop): no public mode value
+constexpr int kBandedExtNone = (int)0x80000000;   // EXT row key: the row has no in-band cell (yet)
 
 // first column a stripe's front starts at: c0 = max(1, i0 + lo), rounded down to a 16-byte boundary of the text
 __host__ __device__ inline int64_t banded_c0a(int64_t i0, int64_t lo) {
@@ -69,7 +78,7 @@ __device__ __forceinline__ void banded_chunk(const int t0, const int k, const in
     typedef BandGeo<64, RL> Geo;
     typedef GotohPrio<MODE> PR;
     constexpr int NQ = (RL + 3) / 4;
-    constexpr bool SW = MODE == 1, SG = MODE == 2;
+    constexpr bool SW = MODE == 1, SG = MODE == 2, EXT = MODE == kBandedExt;
     static_assert(Geo::PB == 0, "banded stripes: one store plane");
     int cmax[RL], kprev[RL];
     static_for<0, 16>([&](auto qc) {
@@ -100,9 +109,9 @@ __device__ __forceinline__ void banded_chunk(const int t0, const int k, const in
             if (r % 4 == 3) gotoh_put_code<3>(codes[r / 4], c);
             const int base = kk & ~7;
             const int hn = p_addw(base, K.cE);
-            if (SW) {   // first maximum of the row over in-band cells (gotoh_chunk's folded keys)
+            if (SW || EXT) {   // first maximum of the row over in-band cells (gotoh_chunk's folded keys; EXT: H of either sign)
                 int key = (int)(((unsigned)base << 1) | (unsigned)(15 - q));
-                key = a ? key : 0;
+                key = a ? key : EXT ? kBandedExtNone : 0;
                 if (q % 2 == 0) kprev[r] = key;
                 else {
                     cmax[r] = q == 1 ? max(kprev[r], key) : max(max(cmax[r], kprev[r]), key);
@@ -133,7 +142,7 @@ __device__ __forceinline__ void banded_chunk(const int t0, const int k, const in
         if constexpr (Geo::PA == 8) PWA_BAND_STORE((PWA_GLOBAL mu32x2*)(tba + q * Geo::SR), (mu32x2{codes[0], codes[1]}));
         if (k == 63 && a) row[x - (RL - 1)] = bint2{uh, uf};                   // the stripe's bottom row, for the stripe below
     });
-    if (SW) {
+    if (SW || EXT) {
 #pragma unroll
         for (int r = 0; r < RL; ++r) {
             const bool better = cmax[r] > (bs[r] | 15);
@@ -143,15 +152,74 @@ __device__ __forceinline__ void banded_chunk(const int t0, const int k, const in
     }
 }
 
+// EXT, once per stripe: the stripe's 64 RL row records (bs / bj: each row's maximum over its in-band cells and where its first one is)
+// in row order into the wave-uniform best-cell record (best_s, best_i, best_j), and the first row the X-drop stops: row i stops iff
+// rmax(i) < best(i - 1) - xdrop (xdrop >= 0; a row without an in-band cell is -inf).  best(i - 1) before the first stop is the
+// maximum of the record carried in and of every earlier row, so: an exclusive prefix maximum over lanes of the lanes' row maxima,
+// seeded with the carried record; each lane tests its RL rows in order against that running best; one ballot finds the first stopping
+// lane; the record is reduced over the rows before the stop by (H desc, i asc) and replaces the carried one on a strictly larger H.
+// Returns the stopping row, or 0.  jbase: column of this lane at step 0 (c0a - lane).  Rows past n neither stop nor count.
+template <int RL>
+__device__ __forceinline__ int banded_ext_stripe_end(const int (&bs)[RL], const int (&bj)[RL], const int i_first, const int n, const int jbase,
+                                                     const int xdrop, int& best_s, int& best_i, int& best_j) {
+    constexpr int NINF = kBandedExtNone >> 4;   // -2^27: below every real H
+    const int k = threadIdx.x & 63;
+    int h[RL], pm = NINF;
+#pragma unroll
+    for (int r = 0; r < RL; ++r) {
+        h[r] = i_first + r <= n ? bs[r] >> 4 : NINF;
+        pm = max(pm, h[r]);
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(pm, off);
+        pm = k >= off ? max(pm, o) : pm;
+    }
+    int b = __shfl_up(pm, 1);
+    b = k ? max(b, best_s) : best_s;   // best(i_first - 1), if no row above stops
+    int stop_r = RL, cs = NINF, ci = 0, cj = 0;
+#pragma unroll
+    for (int r = 0; r < RL; ++r) {
+        const bool live = i_first + r <= n && stop_r == RL;
+        const bool stops = live && xdrop >= 0 && (h[r] == NINF || h[r] < b - xdrop);
+        stop_r = stops ? r : stop_r;
+        const bool kept = live && !stops;
+        if (kept && h[r] > cs) {   // rows in increasing order: a tie keeps the earlier row
+            cs = h[r];
+            ci = i_first + r;
+            cj = jbase + bj[r] + (15 - (bs[r] & 15));
+        }
+        b = kept ? max(b, h[r]) : b;
+    }
+    const uint64_t sm = __ballot(stop_r < RL);
+    const int first = sm ? (int)__builtin_ctzll(sm) : 64;   // the first stopping lane: rows of the lanes behind it are not considered
+    cs = k > first ? NINF : cs;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int so = __shfl_xor(cs, off), io = __shfl_xor(ci, off), jo = __shfl_xor(cj, off);
+        const bool better = so > cs || (so == cs && io < ci);
+        cs = better ? so : cs;
+        ci = better ? io : ci;
+        cj = better ? jo : cj;
+    }
+    const bool take = cs > best_s;
+    best_s = __builtin_amdgcn_readfirstlane(take ? cs : best_s);
+    best_i = __builtin_amdgcn_readfirstlane(take ? ci : best_i);
+    best_j = __builtin_amdgcn_readfirstlane(take ? cj : best_j);
+    return sm ? __builtin_amdgcn_readfirstlane(__shfl(i_first + stop_r, first & 63)) : 0;
+}
+
 // The fill.  Workgroups of kBandedWaves waves, pairs dealt statically (the host sorts them longest first); PairDesc::pad[0 / 1] = the band
 // clamped to the matrix (lo >= -n, hi <= m), row_stride = the band pitch in steps (banded_steps), n_stripes = ceil(n / 64 RL).
 // row_cap: entries of a wave's hand-off row (the launch's widest band); dynamic LDS = kBandedWaves * row_cap * 8 bytes.
+// EXT: xdrop is the call's; the wave leaves a pair's stripe loop at the stripe whose test finds a stopping row, and PairResult::overlap
+// (unused by the banded class) carries rows_out.
 template <int RL, int MODE, class Score>
-__device__ __forceinline__ void banded_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds) {
+__device__ __forceinline__ void banded_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds, const int xdrop = 0) {
     static_assert(RL == 4 || RL == 8, "banded stripes: 256 or 512 rows");
     typedef BandGeo<64, RL> Geo;
     typedef GotohPrio<MODE> PR;
-    constexpr bool NW = MODE == 0, SW = MODE == 1, SG = MODE == 2;
+    constexpr bool EXT = MODE == kBandedExt, NW = MODE == 0 || EXT, SW = MODE == 1, SG = MODE == 2;   // (EXT: NW's matrix)
     constexpr int S = 64 * RL;
     const int k = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -174,7 +242,8 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
         const uintptr_t tg = (uintptr_t)(((uint64_t)thi << 32) | tlo);
         // column 0 of row i holds its mode's boundary value only where the boundary path lies in the band
         auto valid0 = [&](int i) { return SW ? (-i >= lo && -i <= hi) : (hi >= 0 && -i >= lo); };
-        int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes
+        int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes; EXT: the wave's (uniform)
+        int ext_rows = min(n, m - lo);      // EXT: rows_out when no row stops -- the last row that has an in-band cell
         for (int s = 0; s < n_str; ++s) {
             const int i0 = s * S + 1, ib = i0 - 1;
             const int c0 = max(1, i0 + lo), c1 = min(m, i0 + S - 1 + hi);
@@ -193,7 +262,7 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
                 const bool v = valid0(i);
                 hl[r] = v ? p_addw(p_mulw(h, 8), K.cE) : SENT;
                 el[r] = v ? p_addw(p_mulw(p_addw(h, go), 8), 2 * PR::E) : SENT;   // E[i][0] = H[i][0] + gap_open: its extension ties the opening
-                bs[r] = 0;
+                bs[r] = EXT ? kBandedExtNone : 0;
                 bj[r] = 0;
             }
             // the row above at column j (row ib): its (H as an F-open candidate, F) keys, the sentinel where it is not in the band
@@ -248,6 +317,14 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
                     banded_chunk<RL, MODE, true>(t0, k, jm, m, xb, B, rs, hl, el, diag0, bot_h, bot_f, tch, tcv, thv, tfv, K, SENT, bs, bj, own, sg_v, sg_t,
                                                  tbs, row, sc);
             }
+            if constexpr (EXT) {   // (a stop at the first row of a stripe is found here, by that stripe's test, with the record carried in)
+                const int stop = banded_ext_stripe_end<RL>(bs, bj, i_first, n, c0a - k, xdrop, lb_s, lb_i, lb_j);
+                if (stop) {
+                    ext_rows = stop - 1;
+                    break;
+                }
+                continue;
+            }
             PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
             if (SG) {
                 if (last && n >= i_first && n < i_first + RL) {
@@ -274,6 +351,13 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
                     }
                 }
             }
+        }
+        if (EXT && k == 0) {
+            PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
+            res->score = lb_s;
+            res->end_i = (uint32_t)lb_i;
+            res->end_j = (uint32_t)lb_j;
+            res->overlap = ext_rows;
         }
         if (SW) {
             int s_best = lb_s, i_best = lb_i, j_best = lb_j;

@@ -31,6 +31,10 @@
 // row and chunk (first maximum of a row), one (H, i, j) record per lane across stripes replaced on a strictly larger H only, the
 // (H desc, i asc) reduction; SG the first maximum of row n over its in-band columns (sg_track's pick); NW the state of row n frozen
 // at column m.  SW's H << 4 fits: H <= min(n, m) match < 2^27 under the range rule.
+// The EXT form (MODE = kBandedExt; pwa_scores_extend_banded) is banded_fill.hip.h's: NW's boundaries and tie order, the row keys over
+// signed H with kBandedExtNone for "no in-band cell", banded_ext_stripe_end at the end of every stripe.  Its H << 4 holds a negative H
+// because the host admits an EXT pair only while (n + m + 2) A < 2^27: |H| <= (n + m) A < 2^27, so H * 16 + 0..15 stays inside int32
+// and above kBandedExtNone.
 #pragma once
 #include "banded_fill.hip.h"
 
@@ -53,7 +57,7 @@ __device__ __forceinline__ void banded_scores_chunk(const int t0, const int k, c
                                                     int (&hl)[RL], int (&el)[RL], int& diag0, int& bot_h, int& bot_f, int& tch, const int tcv,
                                                     const int thv, const int tfv, const int oe, const int ge, int (&bs)[RL], int (&bj)[RL],
                                                     const int (&own)[RL], int& sg_v, int& sg_t, lds_bint2* const row, const Score& sc) {
-    constexpr bool SW = MODE == 1, SG = MODE == 2;
+    constexpr bool SW = MODE == 1, SG = MODE == 2, EXT = MODE == kBandedExt;
     constexpr int SENT = kBandedSent;
     int cmax[RL], kprev[RL];
     static_for<0, 16>([&](auto qc) {
@@ -76,9 +80,9 @@ __device__ __forceinline__ void banded_scores_chunk(const int t0, const int k, c
             int h = max(max(p_addw(dg, sc.diag(tn, rs[r])), e), f);
             if (SW) h = max(h, 0);
             const int hn = p_addw(h, oe);
-            if (SW) {   // first maximum of the row over in-band cells (gotoh_chunk's folded keys)
+            if (SW || EXT) {   // first maximum of the row over in-band cells (gotoh_chunk's folded keys; EXT: H of either sign)
                 int key = (int)(((unsigned)h << 4) | (unsigned)(15 - q));
-                key = a ? key : 0;
+                key = a ? key : EXT ? kBandedExtNone : 0;
                 if (q % 2 == 0) kprev[r] = key;
                 else {
                     cmax[r] = q == 1 ? max(kprev[r], key) : max(max(cmax[r], kprev[r]), key);
@@ -106,7 +110,7 @@ __device__ __forceinline__ void banded_scores_chunk(const int t0, const int k, c
         tch = tn;
         if (k == 63 && a) row[x - (RL - 1)] = bint2{uh, uf};                   // the stripe's bottom row, for the stripe below
     });
-    if (SW) {
+    if (SW || EXT) {
 #pragma unroll
         for (int r = 0; r < RL; ++r) {
             const bool better = cmax[r] > (bs[r] | 15);
@@ -118,10 +122,11 @@ __device__ __forceinline__ void banded_scores_chunk(const int t0, const int k, c
 
 // The scores pass: banded_body's sweep (same windows, staging, hand-off row and result rules) around the value cell.
 // row_cap: entries of a wave's hand-off row (the launch's widest band); dynamic LDS = kBandedWaves * row_cap * 8 bytes.
+// EXT: xdrop, the early exit from the stripe loop and rows_out in PairResult::overlap as in banded_body.
 template <int RL, int MODE, class Score>
-__device__ __forceinline__ void banded_scores_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds) {
+__device__ __forceinline__ void banded_scores_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds, const int xdrop = 0) {
     static_assert(RL == 4 || RL == 8, "banded stripes: 256 or 512 rows");
-    constexpr bool NW = MODE == 0, SW = MODE == 1, SG = MODE == 2;
+    constexpr bool EXT = MODE == kBandedExt, NW = MODE == 0 || EXT, SW = MODE == 1, SG = MODE == 2;   // (EXT: NW's matrix)
     constexpr int S = 64 * RL;
     constexpr int SENT = kBandedSent;
     const int k = threadIdx.x & 63;
@@ -141,7 +146,8 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
         const uintptr_t tg = (uintptr_t)(((uint64_t)thi << 32) | tlo);
         // column 0 of row i holds its mode's boundary value only where the boundary path lies in the band
         auto valid0 = [&](int i) { return SW ? (-i >= lo && -i <= hi) : (hi >= 0 && -i >= lo); };
-        int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes
+        int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes; EXT: the wave's (uniform)
+        int ext_rows = min(n, m - lo);      // EXT: rows_out when no row stops -- the last row that has an in-band cell
         for (int s = 0; s < n_str; ++s) {
             const int i0 = s * S + 1, ib = i0 - 1;
             const int c0 = max(1, i0 + lo), c1 = min(m, i0 + S - 1 + hi);
@@ -160,7 +166,7 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
                 const bool v = valid0(i);
                 hl[r] = v ? p_addw(h, oe) : SENT;
                 el[r] = v ? p_addw(h, go) : SENT;   // E[i][0] = H[i][0] + gap_open: its extension equals the opening
-                bs[r] = 0;
+                bs[r] = EXT ? kBandedExtNone : 0;
                 bj[r] = 0;
             }
             // the row above at column j (row ib): H + oe and F, the sentinel where it is not in the band
@@ -213,6 +219,14 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
                     banded_scores_chunk<RL, MODE, true>(t0, k, jm, m, xb, B, rs, hl, el, diag0, bot_h, bot_f, tch, tcv, thv, tfv, oe, ge, bs, bj, own, sg_v,
                                                         sg_t, row, sc);
             }
+            if constexpr (EXT) {   // (a stop at the first row of a stripe is found here, by that stripe's test, with the record carried in)
+                const int stop = banded_ext_stripe_end<RL>(bs, bj, i_first, n, c0a - k, xdrop, lb_s, lb_i, lb_j);
+                if (stop) {
+                    ext_rows = stop - 1;
+                    break;
+                }
+                continue;
+            }
             PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
             if (SG) {
                 if (last && n >= i_first && n < i_first + RL) {
@@ -239,6 +253,13 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
                     }
                 }
             }
+        }
+        if (EXT && k == 0) {
+            PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;
+            res->score = lb_s;
+            res->end_i = (uint32_t)lb_i;
+            res->end_j = (uint32_t)lb_j;
+            res->overlap = ext_rows;
         }
         if (SW) {
             int s_best = lb_s, i_best = lb_i, j_best = lb_j;

@@ -25,6 +25,8 @@ hipError_t banded_launch(const PairParams& G, int rl, int mode, int row_cap, int
 hipError_t banded_scores_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st);                    // banded_scores_kernels.hip
 hipError_t banded_subst_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk,
                                const uint32_t* blob, int n_sym, int stride);                                                         // banded_subst_kernels.hip
+hipError_t banded_ext_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, int xdrop);  // banded_ext_kernels.hip
+hipError_t banded_ext_scores_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, int xdrop);
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -73,6 +75,13 @@ struct BandSpec {
     int64_t lo_in(uint64_t k, uint64_t n, uint64_t m) const { return std::min<int64_t>(std::max<int64_t>(lo[k], -(int64_t)n), (int64_t)m); }
     int64_t hi_in(uint64_t k, uint64_t n, uint64_t m) const { return std::max<int64_t>(std::min<int64_t>(hi[k], (int64_t)m), -(int64_t)n); }
 };
+// pwa_extend_banded_batch(_cigar), pwa_scores_extend_banded ("EXT"; always beside a BandSpec, mode = PWA_MODE_NW: the matrix, the band
+// layout and the walk are NW's): the end is the first row-major maximum with (0, 0), rows are given up xdrop below the best.  The planner
+// (TbPlan::class_of / band_of) sizes a pair's band for all n rows: the host cannot know the stop row
+struct ExtSpec {
+    int xdrop;   // < 0: no row ever stops
+};
+constexpr int64_t kExtMaxXdrop = 1 << 27;
 // Stripe height of a banded pair.  A stripe of S = 64 rl rows over a band of B diagonals runs S + B + 62 steps (+ up to 15 of text
 // alignment) of ~F + C rl instructions (F: per-step moves, hand-off and store; C: the masked cell), so its cost per row is
 // (S + B + 77) (F + C rl) / S: with F ~ 27 and C ~ 22 the two heights built break even near B = 900, and the share of wasted steps
@@ -93,6 +102,7 @@ struct AlignOut {
     int32_t* overlap;                    // OUT_OVERLAP
     StrOut str;                          // OUT_STRINGS
     uint32_t *end_i = nullptr, *end_j = nullptr;   // OUT_SCORES: n_pairs each, or null
+    uint32_t* rows = nullptr;                      // EXT: rows considered per pair (n_pairs), or null
 };
 // The caller's scoring, sequences, pair list and outputs, as the stages of align_batch_impl see them
 struct AlignRequest {
@@ -106,6 +116,7 @@ struct AlignRequest {
     uint64_t n_pairs;
     AlignOut out;
     const BandSpec* bd = nullptr;   // null: the whole matrix
+    const ExtSpec* ext = nullptr;   // EXT: extension from (0, 0) with an X-drop, else null
     uint64_t slen(uint32_t s) const { return seq_off[s + 1] - seq_off[s]; }
     bool local() const { return mode == PWA_MODE_SW; }
     bool semi() const { return mode == PWA_MODE_SG; }   // (semi-global: NW's classes, guards and codes; no gap shift)
@@ -135,6 +146,7 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
         (rq.want_str() && (!o.str.cigar_off || !o.str.mdz_off || (o.str.cigar_cap && !o.str.cigar) || (o.str.mdz_cap && !o.str.mdz))) ||
         (rq.n_pairs && (!rq.pair_a || !rq.pair_b)))
         return fail(ctx, PWA_E_INVALID, "null input");
+    if (rq.ext && (int64_t)rq.ext->xdrop > kExtMaxXdrop) return fail(ctx, PWA_E_INVALID, "EXT: xdrop must be at most 2^27 (negative: no row stops)");
     const int rc = check_pair_list(ctx, rq.pair_a, rq.pair_b, rq.n_pairs, rq.n_seq);
     if (rc != PWA_OK || !rq.gt) return rc;
     // the gotoh classes' shape limit, and the range every key of theirs stays exact in
@@ -145,11 +157,15 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
         if (rq.bd) {   // the band's validity per mode (include/pwalign.h), its width, then the range rule (an all-zero scoring counts as 1)
             const int64_t lo = rq.bd->lo[k], hi = rq.bd->hi[k], d = (int64_t)m - (int64_t)n;
             if (lo > hi) return fail(ctx, PWA_E_INVALID, "banded alignment: band_lo > band_hi");
-            if (rq.mode == PWA_MODE_NW && !(lo <= 0 && 0 <= hi && lo <= d && d <= hi))
+            if (rq.ext && !(lo <= 0 && 0 <= hi)) return fail(ctx, PWA_E_INVALID, "banded EXT alignment: the band must hold the anchor, band_lo <= 0 <= band_hi");
+            if (!rq.ext && rq.mode == PWA_MODE_NW && !(lo <= 0 && 0 <= hi && lo <= d && d <= hi))
                 return fail(ctx, PWA_E_INVALID, "banded NW alignment: the band must hold the diagonals 0 and m - n");
             if (rq.mode == PWA_MODE_SG && !(hi >= 0 && (int64_t)n + lo <= (int64_t)m))
                 return fail(ctx, PWA_E_INVALID, "banded SG alignment: needs band_hi >= 0 and n + band_lo <= m");
             if (hi - lo + 1 > (int64_t)kBandedMaxWidth) return fail(ctx, PWA_E_CAPACITY, "banded alignment: band wider than 4096 diagonals");
+            // (EXT: one bit tighter -- its row keys hold H * 16 with H of either sign, banded_fill.hip.h)
+            if (rq.ext && (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 27)))
+                return fail(ctx, PWA_E_CAPACITY, "EXT scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|, 1) must stay below 2^27");
             if (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 28))
                 return fail(ctx, PWA_E_CAPACITY, rq.sb ? "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) must stay below 2^28"
                                                        : "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
@@ -489,7 +505,7 @@ int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& a
         const uint64_t k = k0 + q, n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         std::memset(&res[q], 0, sizeof(PairResult));
         rh.ooff[q] = rg.tiled ? rq.out.ops_off[k] - rh.ops_lo : oo;
-        if (!(n && m) && !local) {   // (semi-global: column 0, or nothing for an empty pattern)
+        if (!(n && m) && !local && !rq.ext) {   // (semi-global: column 0, or nothing for an empty pattern; EXT: score 0 at (0, 0))
             res[q].score = wrap_mul((int64_t)(semi ? n : n + m), rq.gap);
             if (rq.gt) {   // one gap of length L: gap_open + L * gap_extend
                 const uint64_t L = semi ? n : n + m;
@@ -542,7 +558,7 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
         d.pad[0] = (uint32_t)(int32_t)lo;
         d.pad[1] = (uint32_t)(int32_t)hi;
         row_cap = std::max(row_cap, hi - lo + 1);
-        if (scores) stats.cells += banded_cells((int64_t)n, (int64_t)m, lo, hi);
+        if (scores && !rq.ext) stats.cells += banded_cells((int64_t)n, (int64_t)m, lo, hi);   // (EXT counts the rows it considered: scatter_range)
         for (int64_t s = 0; !scores && s < (int64_t)d.n_stripes; ++s) stats.band_bytes += (uint64_t)(banded_chunks(s * S + 1, S, lo, hi, (int64_t)m) * 16 * S);   // what the fill stores
     }
     PairLaunch pl;
@@ -554,7 +570,14 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
     clock.mark("descriptor build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] banded %s RL=%d pairs=%zu hand-off row=%lld entries\n", scores ? "scores" : "fill", L.cls.rl, np, (long long)row_cap);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (rq.sb) {
+    if (rq.ext) {   // the same descriptors; the fill leaves rows_out in PairResult::overlap, the walk is NW's
+        if (scores) {
+            HIPC(ctx, pwa::banded_ext_scores_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, rq.ext->xdrop));
+            HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        } else {
+            HIPC(ctx, pwa::banded_ext_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], rq.ext->xdrop));
+        }
+    } else if (rq.sb) {
         const SubstRef& t = rq.sb->tab;
         HIPC(ctx, pwa::banded_subst_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], !scores, t.tab, t.n_sym, t.stride));
         if (scores) HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -657,7 +680,7 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
             if (ar.seen[v]) cp.decode = cp.decode << 8 | (uint64_t)v;   // code c = the c-th symbol seen, in byte order
     cp.nc = (uint32_t)nc;
     cp.coded = ar.coded;
-    cp.local = rq.local();
+    cp.local = rq.local() || rq.ext;   // (EXT: a pair with an empty side has no ops, as SW's)
     cp.semi = rq.semi();
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPC(ctx, pwa::cigar_launch(cp, false, ctx->stream));
@@ -687,7 +710,8 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
 }
 
 // The range's results (and op lists) back on the host and into the caller's arrays
-int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& ws, const Range& rg, RangeHost& rh, AlignClock& clock) {
+// (EXT: rows_out travels in PairResult::overlap, which the banded class does not use otherwise; their sum goes into stats.cells)
+int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& ws, const Range& rg, RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const uint64_t k0 = rg.k0, nc = rg.k1 - rg.k0;
     const AlignOut& o = rq.out;
     const bool local = rq.local(), semi = rq.semi(), want_ops = rq.want_ops();
@@ -707,7 +731,7 @@ int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& w
         if (!(n && m)) {
             // one side empty: NW walks the boundary (hw2.cpp:170-179), SW emits nothing (239), SG walks column 0; no
             // column without a gap, so the overlap is 0 (hw2.cpp:267-278)
-            cnt = local ? 0 : semi ? n : n + m;
+            cnt = local || rq.ext ? 0 : semi ? n : n + m;
             if (want_ops)
                 for (uint64_t c = 0; c < cnt; ++c) o.ops[o.ops_off[k] + c] = n ? 'D' : 'I';
             if (o.start_cells) o.start_cells[2 * k] = o.start_cells[2 * k + 1] = 0;
@@ -726,6 +750,11 @@ int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& w
         if (o.end_cells) {
             o.end_cells[2 * k] = res[q].end_i;
             o.end_cells[2 * k + 1] = res[q].end_j;
+        }
+        if (rq.ext) {
+            const uint32_t rows = (n && m) ? (uint32_t)res[q].overlap : 0u;
+            if (o.rows) o.rows[k] = rows;
+            stats.cells += rows;
         }
         if (o.end_i) o.end_i[k] = res[q].end_i;
         if (o.end_j) o.end_j[k] = res[q].end_j;
@@ -766,7 +795,7 @@ int align_batch_impl(pwa_ctx* ctx, const AlignRequest& rq, AlignStats& stats) tr
             if ((rc = format_range_strings(ctx, rq, arena, ws, rg, rh)) != PWA_OK) return rc;
             clock.mark("strings (device) + copy back");
         }
-        if ((rc = scatter_range(ctx, rq, ws, rg, rh, clock)) != PWA_OK) return rc;
+        if ((rc = scatter_range(ctx, rq, ws, rg, rh, stats, clock)) != PWA_OK) return rc;
         clock.mark("scatter to caller buffers");
     }
     if (clock.on) std::fprintf(stderr, "[pwa] %s: %llu pairs in %zu range(s): fills %.3f ms, walks %.3f ms (device), %.2f GB of band written\n",
@@ -1015,6 +1044,56 @@ int pwa_scores_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, uint64_t* i
     if (!ctx) return PWA_E_INVALID;
     if (fill_ms) *fill_ms = ctx->banded_scores_stats.fill_ms;
     if (in_band_cells) *in_band_cells = ctx->banded_scores_stats.cells;
+    return PWA_OK;
+}
+
+// the EXT entry points: banded_batch with NW's matrix and the call's ExtSpec; they report into their own slot
+static int extend_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, int xdrop, const int32_t* band_lo, const int32_t* band_hi) {
+    const ExtSpec es{xdrop};
+    rq.ext = &es;
+    return banded_batch(ctx, rq, gap_extend, band_lo, band_hi, ctx->ext_stats);
+}
+
+int pwa_extend_banded_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
+                            const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                            int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint32_t* rows_out,
+                            const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
+    AlignOut out{OUT_OPS, score_out, end_cells, nullptr, ops, ops_off, n_ops, nullptr, {}};
+    out.rows = rows_out;
+    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
+                        gap_extend, xdrop, band_lo, band_hi);
+}
+
+int pwa_extend_banded_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
+                                  const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                                  int32_t* score_out, char* cigar, uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap,
+                                  uint64_t* mdz_off, uint64_t* end_cells, uint32_t* rows_out, uint64_t needed[2], const int32_t* band_lo,
+                                  const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    AlignOut out{OUT_STRINGS, score_out, end_cells, nullptr, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
+    out.rows = rows_out;
+    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
+                        gap_extend, xdrop, band_lo, band_hi);
+}
+
+int pwa_scores_extend_banded(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
+                             const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
+                             int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, uint32_t* rows_out, const int32_t* band_lo,
+                             const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
+    out.rows = rows_out;
+    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
+                        gap_extend, xdrop, band_lo, band_hi);
+}
+
+int pwa_extend_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* rows_considered) {
+    if (!ctx) return PWA_E_INVALID;
+    if (fill_ms) *fill_ms = ctx->ext_stats.fill_ms;
+    if (walk_ms) *walk_ms = ctx->ext_stats.tb_ms;
+    if (rows_considered) *rows_considered = ctx->ext_stats.cells;
     return PWA_OK;
 }
 

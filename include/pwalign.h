@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
- *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded and their _subst forms: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
+ *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -415,6 +415,62 @@ int pwa_scores_banded(pwa_ctx *ctx, int mode /* NW, SW, SG */, int match, int mi
                       const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint32_t *end_i_out /* or NULL */,
                       uint32_t *end_j_out /* or NULL */, const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
 int pwa_scores_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, uint64_t *in_band_cells);
+
+/*
+ * BANDED X-DROP EXTENSION of long pairs ("EXT"): the alignment is anchored at cell (0, 0) -- a seed's end --, its end is free in both
+ * sequences, and the sweep over the rows is given up once the score has fallen xdrop below the best seen (BLAST's X-drop; the zdrop of
+ * ksw2_extz without its diagonal term).
+ *   pwa_extend_banded_batch        pwa_align_banded_batch's arguments without `mode` and `start_cells`, xdrop after gap_extend, and rows_out;
+ *   pwa_extend_banded_batch_cigar  pwa_align_banded_batch_cigar's, changed the same way;
+ *   pwa_scores_extend_banded       pwa_scores_banded's, changed the same way: no traceback band, no walk;
+ *   pwa_extend_banded_last_stats   device ms of the fills and walks of the last of these three calls on ctx, and the sum of its rows_out.
+ * Everything not said here is the banded block's rule (pwa_align_banded_batch): the gotoh recurrences, "a tie opens", raw-byte
+ * equality, gap_open <= 0 and gap_extend <= 0, the band band_lo <= j - i <= band_hi with -inf outside, a width of at most 4096
+ * (else PWA_E_CAPACITY), op order and op-region layout, string buffers, PWA_RANGE_BYTES, and the empty list.
+ * Matrix.  The banded NW matrix: H[0][0] = 0, row 0 and column 0 hold gap_open + L * gap_extend under the banded boundary rule, the H
+ * tie-break is NW's (diag >= E >= F), and there is no zero floor.
+ * Validity.  band_lo <= 0 <= band_hi: the anchor is in the band; otherwise PWA_E_INVALID.  Nothing is required of m - n.
+ * band_lo > band_hi is checked first, then this rule, then the width; in pair order, and the first offending pair decides.
+ * Best cell.  The record starts as (score 0, cell (0, 0)).  Rows i = 1, 2, ... are taken in order; rmax(i) is the maximum of H[i][j]
+ * over the in-band cells with 1 <= j <= m (-inf when the row has none), and the smallest such j stands for the row.  A row replaces
+ * the record only on a strictly larger value: the end cell is the first row-major maximum, and a best score of 0 ends at (0, 0) with
+ * no ops.
+ * X-drop.  With xdrop >= 0, row i stops the sweep iff rmax(i) < best(i - 1) - xdrop, best(i - 1) being the record's score after row
+ * i - 1.  The first such row r* and every row below it are not considered, and rows_out[k] = r* - 1, or n when no row stops.  A row
+ * whose band has left the matrix (i + band_lo > m) has rmax = -inf and stops the sweep whenever xdrop >= 0.  With xdrop < 0 no row ever
+ * stops, and rows_out[k] is the last row that has an in-band cell (min(n, m - band_lo) for a clamped band).  xdrop > 2^27 is
+ * PWA_E_INVALID.
+ * Walk.  From the end cell in state H, NW's walk on the banded matrices, down to (0, 0).  The start cell is always (0, 0), so the calls
+ * do not return it.
+ * Empty sides.  A pair with an empty side scores 0, ends at (0, 0), has no ops and rows_out = 0; its band must still be valid.
+ * Range.  (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|, 1) < 2^27, else PWA_E_CAPACITY: one bit tighter than the
+ * banded rule, because the row maxima are kept as H * 16 + 4 column bits and H may be negative here.
+ * Memory.  A pair's traceback band is planned for all n rows: the host cannot know the stop row.
+ * Identities.  (1) With xdrop < 0 the score is the maximum over all in-band cells of the banded NW matrix, together with 0.  (2) If
+ * the stop row lies below the end row that xdrop < 0 gives, both calls return the same score, end cell and ops.  (3) The scores call
+ * equals the alignment call on (score, end, rows).
+ * end_cells, rows_out, end_i_out and end_j_out may each be NULL.  A null score_out, band_lo or band_hi with n_pairs > 0 is
+ * PWA_E_INVALID.  A call that fails validation leaves the stats unchanged; walk_ms is 0 after the scores call.
+ * Not offered: a substitution-matrix form, ksw2's diagonal-aware Z-drop term, the best score of row n, a batch object.
+ */
+int pwa_extend_banded_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop,
+                            const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                            const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off,
+                            uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */, uint32_t *rows_out /* n_pairs or NULL */,
+                            const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_extend_banded_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop,
+                                  const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                                  const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                  char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                  char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                  uint64_t *end_cells /* 2*n_pairs or NULL */, uint32_t *rows_out /* n_pairs or NULL */,
+                                  uint64_t needed[2] /* or NULL */, const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_scores_extend_banded(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop,
+                             const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                             const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint32_t *end_i_out /* or NULL */,
+                             uint32_t *end_j_out /* or NULL */, uint32_t *rows_out /* or NULL */,
+                             const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
+int pwa_extend_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *rows_considered);
 
 /*
  * Affine-gap ("gotoh") SCORES of many pairs: what pwa_scores / pwa_batch_create are to pwa_align_batch.  Recurrence, boundaries, raw-byte
