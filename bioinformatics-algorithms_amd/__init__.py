@@ -35,6 +35,7 @@ EXPORTS = [
     "pwa_align_banded_batch", "pwa_align_banded_batch_cigar", "pwa_align_banded_last_stats",
     "pwa_scores_banded", "pwa_scores_banded_last_stats",
     "pwa_extend_banded_batch", "pwa_extend_banded_batch_cigar", "pwa_scores_extend_banded", "pwa_extend_banded_last_stats",
+    "pwa_extend_banded_subst_batch", "pwa_extend_banded_subst_batch_cigar", "pwa_scores_extend_banded_subst",
     "pwa_align_subst_batch", "pwa_align_subst_batch_cigar", "pwa_subst_batch_create", "pwa_scores_subst", "pwa_align_subst_last_stats",
     "pwa_align_banded_subst_batch", "pwa_align_banded_subst_batch_cigar", "pwa_scores_banded_subst",
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
@@ -188,6 +189,11 @@ def lib():
     L.pwa_align_banded_subst_batch.argtypes = L.pwa_align_subst_batch.argtypes + [i32p, i32p]   # ..., band_lo, band_hi
     L.pwa_align_banded_subst_batch_cigar.argtypes = L.pwa_align_subst_batch_cigar.argtypes + [i32p, i32p]
     L.pwa_scores_banded_subst.argtypes = subst_in + [i32p, u32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, band_lo, band_hi
+    ext_subst_in = [vp] + subst_in[2:7] + [C.c_int] + subst_in[7:]   # ctx, code[256], n_sym, submat, gap_open, gap_extend, xdrop, sequences, pairs
+    # ..., end_cells, rows, pend_score, pend_j, band_lo, band_hi
+    L.pwa_extend_banded_subst_batch.argtypes = ext_subst_in + [i32p, vp, u64p, u64p, u64p, u32p, i32p, u32p, i32p, i32p]
+    L.pwa_extend_banded_subst_batch_cigar.argtypes = ext_subst_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u32p, i32p, u32p, u64p, i32p, i32p]
+    L.pwa_scores_extend_banded_subst.argtypes = ext_subst_in + [i32p, u32p, u32p, u32p, i32p, u32p, i32p, i32p]   # ..., score, end_i, end_j, rows, pend_score, pend_j, band_lo, band_hi
     L.pwa_align_affine_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64,
                                          i32p, vp, u64p, u64p]
     L.pwa_cigar_bound.argtypes = [C.c_uint64]
@@ -235,6 +241,14 @@ def pack_sequences(seqs):
         tot += len(s)
     off[len(seqs)] = tot
     return b"".join(seqs), off, seqs
+
+
+EXT_NO_PEND = -(1 << 31)   # PWA_EXT_NO_PEND: pend_score_out of a pair whose row n was not reached or not kept
+
+
+def _pend(score, j):
+    """a pair's pattern-end result as the Python calls return it: (score, j), or None where there is none"""
+    return None if score == EXT_NO_PEND else (score, j)
 
 
 _SUBST_NO_CODE = 255   # subst_table(unknown=None): a byte outside the alphabet (no code is that large: n_sym <= 32)
@@ -563,9 +577,10 @@ class Context:
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False):
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
         """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`);
-        ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result"""
+        ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result;
+        pend: ... with pend_score_out and pend_j_out behind rows_out, and a `pend` key"""
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -580,16 +595,20 @@ class Context:
         nops = (C.c_uint64 * max(n, 1))()
         endc = (C.c_uint64 * (2 * max(n, 1)))()
         startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
-        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *tail)
+        pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if pend else ()
+        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *pe, *tail)
         self._check(rc, name)
         raw = memoryview(ops)
         if ext:
-            return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
-                         rows=startc[k]) for k in range(n)]
+            out = [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
+                        rows=startc[k]) for k in range(n)]
+            for k in range(n if pend else 0):
+                out[k]["pend"] = _pend(pe[0][k], pe[1][k])
+            return out
         return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False):
+    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
         """... and one that returns CIGAR and MD:Z strings built on the device"""
         import numpy as np
         blob, off, seqs = pack_sequences(seqs)
@@ -607,14 +626,18 @@ class Context:
         endc = (C.c_uint64 * (2 * max(n, 1)))()
         startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
         u64p = C.POINTER(C.c_uint64)
+        pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if pend else ()
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
-                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, None, *tail)
+                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, *pe, None, *tail)
         self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
         if ext:
-            return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
-                         rows=startc[k]) for k in range(n)]
+            out = [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
+                        rows=startc[k]) for k in range(n)]
+            for k in range(n if pend else 0):
+                out[k]["pend"] = _pend(pe[0][k], pe[1][k])
+            return out
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
@@ -713,7 +736,7 @@ class Context:
         return list(sc[:n])
 
     def extend_banded_stats(self):
-        """The last extend_banded_batch(_cigar) or scores_extend_banded: device ms of its fills and walks (walk_ms = 0 after the scores
+        """The last extend_banded_batch(_cigar) or scores_extend_banded, or their _subst forms: device ms of its fills and walks (walk_ms = 0 after the scores
         call), and the rows it considered (the sum of `rows`)."""
         f, w, r = C.c_float(0), C.c_float(0), C.c_uint64(0)
         self._check(self._L.pwa_extend_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(r)), "pwa_extend_banded_last_stats")
@@ -790,6 +813,46 @@ class Context:
         self._check(self._L.pwa_scores_banded_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej, lo, hi), "pwa_scores_banded_subst")
         if want_end:
             return list(sc[:n]), list(ei[:n]), list(ej[:n])
+        return list(sc[:n])
+
+    # -- ... and the X-drop extension calls with a table, which also say whether and how the extension reached the pattern's end
+    def _ext_subst_head(self, table, gap_open, gap_extend, xdrop, blob):
+        code, n_sym, submat, code_p, submat_p = _subst_args(table, blob)
+        return (self._h, code_p, n_sym, submat_p, gap_open, gap_extend, xdrop), (code, submat)
+
+    def extend_banded_subst_batch(self, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands, xdrop):
+        """pwa_extend_banded_subst_batch: extend_banded_batch under table = subst_table(...) -> [dict(score, ops, end, start, rows,
+        pend)]; pend = (score, j) of the best cell of the pattern's last row when the sweep kept that row, else None."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._ext_subst_head(table, gap_open, gap_extend, xdrop, packed[0])
+        return self._align_ops(self._L.pwa_extend_banded_subst_batch, "pwa_extend_banded_subst_batch", head, packed, pair_a, pair_b,
+                               self._band_arrays(bands, len(pair_a)), ext=True, pend=True)
+
+    def extend_banded_subst_batch_cigar(self, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands, xdrop):
+        """pwa_extend_banded_subst_batch_cigar -> [dict(score, cigar, mdz, end, start, rows, pend)]; MD:Z reports byte identity, not
+        score sign."""
+        packed = pack_sequences(seqs)
+        head, _keep = self._ext_subst_head(table, gap_open, gap_extend, xdrop, packed[0])
+        return self._align_strings(self._L.pwa_extend_banded_subst_batch_cigar, "pwa_extend_banded_subst_batch_cigar", head, packed, pair_a, pair_b,
+                                   self._band_arrays(bands, len(pair_a)), ext=True, pend=True)
+
+    def scores_extend_banded_subst(self, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands, xdrop, want_end=False):
+        """pwa_scores_extend_banded_subst: score (and, with want_end, end cell, rows and pattern-end result) of every pair of
+        extend_banded_subst_batch's list, without the alignments -> scores, or (scores, end_i, end_j, rows, pend) with pend a list of
+        (score, j) or None.  Stats: extend_banded_stats."""
+        blob, off, seqs = pack_sequences(seqs)
+        head, _keep = self._ext_subst_head(table, gap_open, gap_extend, xdrop, blob)
+        n = len(pair_a)
+        lo, hi = self._band_arrays(bands, n)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ei, ej, rw, pj = [(C.c_uint32 * max(n, 1))() if want_end else None for _ in range(4)]
+        ps = (C.c_int32 * max(n, 1))() if want_end else None
+        rc = self._L.pwa_scores_extend_banded_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej, rw, ps, pj, lo, hi)
+        self._check(rc, "pwa_scores_extend_banded_subst")
+        if want_end:
+            return list(sc[:n]), list(ei[:n]), list(ej[:n]), list(rw[:n]), [_pend(ps[k], pj[k]) for k in range(n)]
         return list(sc[:n])
 
     def batch_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):

@@ -209,12 +209,28 @@ __device__ __forceinline__ int banded_ext_stripe_end(const int (&bs)[RL], const 
     return sm ? __builtin_amdgcn_readfirstlane(__shfl(i_first + stop_r, first & 63)) : 0;
 }
 
+// EXT, once per pair, after the test of the stripe that holds row n found no stop (and no stripe above it did), for a row n that has an
+// in-band cell (n <= m - lo): the pattern-end record {rmax(n), the smallest column attaining it} from the row's own record, as
+// banded_ext_stripe_end reads it.  One lane holds the row; pend[0..1] keep the host's "no value" wherever this does not run.  It is
+// neither reached nor compiled unless the body is instantiated with PEND.
+template <int RL>
+__device__ __forceinline__ void banded_ext_pattern_end(PWA_GLOBAL int* const pend, const int (&bs)[RL], const int (&bj)[RL], const int i_first, const int n,
+                                                       const int jbase) {
+#pragma unroll
+    for (int r = 0; r < RL; ++r)
+        if (i_first + r == n) {
+            pend[0] = bs[r] >> 4;
+            pend[1] = jbase + bj[r] + (15 - (bs[r] & 15));
+        }
+}
+
 // The fill.  Workgroups of kBandedWaves waves, pairs dealt statically (the host sorts them longest first); PairDesc::pad[0 / 1] = the band
 // clamped to the matrix (lo >= -n, hi <= m), row_stride = the band pitch in steps (banded_steps), n_stripes = ceil(n / 64 RL).
 // row_cap: entries of a wave's hand-off row (the launch's widest band); dynamic LDS = kBandedWaves * row_cap * 8 bytes.
 // EXT: xdrop is the call's; the wave leaves a pair's stripe loop at the stripe whose test finds a stopping row, and PairResult::overlap
-// (unused by the banded class) carries rows_out.
-template <int RL, int MODE, class Score>
+// (unused by the banded class) carries rows_out.  PEND (EXT only; the table kernels of banded_ext_subst_kernels.hip): PairDesc::rows, unused
+// by the banded class too, points at the pair's pattern-end record, written by banded_ext_pattern_end when the sweep keeps row n.
+template <int RL, int MODE, bool PEND = false, class Score>
 __device__ __forceinline__ void banded_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds, const int xdrop = 0) {
     static_assert(RL == 4 || RL == 8, "banded stripes: 256 or 512 rows");
     typedef BandGeo<64, RL> Geo;
@@ -244,6 +260,7 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
         auto valid0 = [&](int i) { return SW ? (-i >= lo && -i <= hi) : (hi >= 0 && -i >= lo); };
         int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes; EXT: the wave's (uniform)
         int ext_rows = min(n, m - lo);      // EXT: rows_out when no row stops -- the last row that has an in-band cell
+        PWA_GLOBAL int* const pend = PEND ? (PWA_GLOBAL int*)P->rows : nullptr;   // the pair's pattern-end record {rmax(n), its first column}
         for (int s = 0; s < n_str; ++s) {
             const int i0 = s * S + 1, ib = i0 - 1;
             const int c0 = max(1, i0 + lo), c1 = min(m, i0 + S - 1 + hi);
@@ -323,6 +340,8 @@ __device__ __forceinline__ void banded_body(const PairParams& G, const int row_c
                     ext_rows = stop - 1;
                     break;
                 }
+                if constexpr (PEND)   // row n was kept (ext_rows stays n) and has an in-band cell
+                    if (last && n <= m - lo) banded_ext_pattern_end<RL>(pend, bs, bj, i_first, n, c0a - k);
                 continue;
             }
             PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;

@@ -122,8 +122,8 @@ __device__ __forceinline__ void banded_scores_chunk(const int t0, const int k, c
 
 // The scores pass: banded_body's sweep (same windows, staging, hand-off row and result rules) around the value cell.
 // row_cap: entries of a wave's hand-off row (the launch's widest band); dynamic LDS = kBandedWaves * row_cap * 8 bytes.
-// EXT: xdrop, the early exit from the stripe loop and rows_out in PairResult::overlap as in banded_body.
-template <int RL, int MODE, class Score>
+// EXT: xdrop, the early exit from the stripe loop, rows_out in PairResult::overlap and, with PEND, the pattern-end record as in banded_body.
+template <int RL, int MODE, bool PEND = false, class Score>
 __device__ __forceinline__ void banded_scores_body(const PairParams& G, const int row_cap, const Score& sc, lds_bint2* const lds, const int xdrop = 0) {
     static_assert(RL == 4 || RL == 8, "banded stripes: 256 or 512 rows");
     constexpr bool EXT = MODE == kBandedExt, NW = MODE == 0 || EXT, SW = MODE == 1, SG = MODE == 2;   // (EXT: NW's matrix)
@@ -148,6 +148,7 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
         auto valid0 = [&](int i) { return SW ? (-i >= lo && -i <= hi) : (hi >= 0 && -i >= lo); };
         int lb_s = 0, lb_i = 0, lb_j = 0;   // SW: this lane's record over all its rows and stripes; EXT: the wave's (uniform)
         int ext_rows = min(n, m - lo);      // EXT: rows_out when no row stops -- the last row that has an in-band cell
+        PWA_GLOBAL int* const pend = PEND ? (PWA_GLOBAL int*)P->rows : nullptr;   // the pair's pattern-end record {rmax(n), its first column}
         for (int s = 0; s < n_str; ++s) {
             const int i0 = s * S + 1, ib = i0 - 1;
             const int c0 = max(1, i0 + lo), c1 = min(m, i0 + S - 1 + hi);
@@ -225,6 +226,8 @@ __device__ __forceinline__ void banded_scores_body(const PairParams& G, const in
                     ext_rows = stop - 1;
                     break;
                 }
+                if constexpr (PEND)   // row n was kept (ext_rows stays n) and has an in-band cell
+                    if (last && n <= m - lo) banded_ext_pattern_end<RL>(pend, bs, bj, i_first, n, c0a - k);
                 continue;
             }
             PWA_GLOBAL PairResult* const res = (PWA_GLOBAL PairResult*)P->res;

@@ -1,6 +1,8 @@
 // pwalign_align.hip -- alignment batches: pwa_align_batch(_cigar), pwa_align_gotoh_batch(_cigar), pwa_align_subst_batch(_cigar),
 // pwa_align_banded_batch(_cigar) and its scores-only form pwa_scores_banded, their substitution-matrix forms
-// pwa_align_banded_subst_batch(_cigar) and pwa_scores_banded_subst, pwa_overlaps (the range planner and its stages), pwa_align and
+// pwa_align_banded_subst_batch(_cigar) and pwa_scores_banded_subst, the X-drop extension calls pwa_extend_banded_batch(_cigar) and
+// pwa_scores_extend_banded with their substitution-matrix forms pwa_extend_banded_subst_batch(_cigar) and
+// pwa_scores_extend_banded_subst, pwa_overlaps (the range planner and its stages), pwa_align and
 // pwa_align_matrices.
 #include "pwalign_internal.h"
 
@@ -27,6 +29,8 @@ hipError_t banded_subst_launch(const PairParams& G, int rl, int mode, int row_ca
                                const uint32_t* blob, int n_sym, int stride);                                                         // banded_subst_kernels.hip
 hipError_t banded_ext_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, int xdrop);  // banded_ext_kernels.hip
 hipError_t banded_ext_scores_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, int xdrop);
+hipError_t banded_ext_subst_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk, int xdrop,
+                                   const uint32_t* blob, int n_sym, int stride);                                                     // banded_ext_subst_kernels.hip
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -60,7 +64,8 @@ struct GotohSpec {
     int gap_open, gap_extend;
 };
 // pwa_align_subst_batch(_cigar): the gotoh classes with the diagonal score from the caller's table (always beside a GotohSpec); beside a
-// BandSpec too: pwa_align_banded_subst_batch(_cigar), pwa_scores_banded_subst
+// BandSpec too: pwa_align_banded_subst_batch(_cigar), pwa_scores_banded_subst; beside an ExtSpec as well: pwa_extend_banded_subst_batch(_cigar),
+// pwa_scores_extend_banded_subst
 struct SubstSpec {
     SubstRef tab;      // SubstTable::dev and its layout
     int64_t max_abs;   // max |submat|: the range rule's score term
@@ -103,6 +108,8 @@ struct AlignOut {
     StrOut str;                          // OUT_STRINGS
     uint32_t *end_i = nullptr, *end_j = nullptr;   // OUT_SCORES: n_pairs each, or null
     uint32_t* rows = nullptr;                      // EXT: rows considered per pair (n_pairs), or null
+    int32_t* pend_score = nullptr;                 // EXT with a table: the pattern-end result per pair (n_pairs each), or null
+    uint32_t* pend_j = nullptr;
 };
 // The caller's scoring, sequences, pair list and outputs, as the stages of align_batch_impl see them
 struct AlignRequest {
@@ -124,6 +131,9 @@ struct AlignRequest {
     bool want_str() const { return out.mode == OUT_STRINGS; }
     bool scores_only() const { return out.mode == OUT_SCORES; }   // no band, no walk, no ops (walk_ops() only says: not pwa_overlaps)
     bool walk_ops() const { return out.mode != OUT_OVERLAP; }   // WALK_OPS; the op lists come back (want_ops) or are formatted on the device (want_str)
+    // the EXT calls with a table also return the pattern-end result: a {score, j} record per pair travels behind the range's PairResults
+    bool pend() const { return ext && sb; }
+    size_t res_bytes() const { return sizeof(PairResult) + (pend() ? 2 * sizeof(int32_t) : 0); }
 };
 
 // PWA_DEBUG: host-side time between marks
@@ -165,7 +175,8 @@ int validate_align(pwa_ctx* ctx, const AlignRequest& rq) {
             if (hi - lo + 1 > (int64_t)kBandedMaxWidth) return fail(ctx, PWA_E_CAPACITY, "banded alignment: band wider than 4096 diagonals");
             // (EXT: one bit tighter -- its row keys hold H * 16 with H of either sign, banded_fill.hip.h)
             if (rq.ext && (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 27)))
-                return fail(ctx, PWA_E_CAPACITY, "EXT scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|, 1) must stay below 2^27");
+                return fail(ctx, PWA_E_CAPACITY, rq.sb ? "EXT scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) must stay below 2^27"
+                                                       : "EXT scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|, 1) must stay below 2^27");
             if (n > 0x7fffffc0ull || m > 0x7fffffc0ull || (long double)(n + m + 2) * (long double)std::max<int64_t>(mx, 1) >= (long double)(1u << 28))
                 return fail(ctx, PWA_E_CAPACITY, rq.sb ? "substitution-matrix scores out of range: (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) must stay below 2^28"
                                                        : "gotoh scores out of range: (n + m + 2) * max(|match|, |mismatch|, |gap_open| + |gap_extend|) must stay below 2^28");
@@ -464,7 +475,7 @@ int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& pl
     if (plan.sband)
         HIPC(ctx, cached_workspace(ctx->sband_cache, ctx->sband_cache_bytes, rp.band_cap * sizeof(int32_t), ws.d_sband, &ws.p_sband));
     HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * sizeof(PairResult), ws.d_res_own, &ws.p_res));
+    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * rq.res_bytes(), ws.d_res_own, &ws.p_res));
     if (rq.want_str()) {
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], rp.str_cap, ws.d_str_own, &ws.p_str));
         HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR_AUX], ctx->pool_bytes[pwa_ctx::POOL_STR_AUX],
@@ -477,6 +488,7 @@ int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& pl
 // ranges before it left
 struct RangeHost {
     PairResult* res = nullptr;     // uploaded, and read back after the walk
+    int32_t* pend = nullptr;       // AlignRequest::pend(): the range's {score, j} records, behind its results on the host and on the device
     CigarPair* cpairs = nullptr;   // pwa_align_batch_cigar: the range's pair list, then (same page-locked buffer) its string offsets
     uint32_t* clen = nullptr;
     std::vector<uint64_t> ooff;
@@ -490,8 +502,9 @@ struct RangeHost {
 int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, RangeHost& rh) {
     const uint64_t k0 = rg.k0, nc = rg.k1 - rg.k0;
     const bool local = rq.local(), semi = rq.semi(), want_ops = rq.want_ops(), want_str = rq.want_str();
-    HIPC(ctx, ctx->pin[pwa_ctx::PIN_RES].reserve(nc * sizeof(PairResult)));
+    HIPC(ctx, ctx->pin[pwa_ctx::PIN_RES].reserve(nc * rq.res_bytes()));
     PairResult* const res = rh.res = ctx->pin[pwa_ctx::PIN_RES].as<PairResult>();
+    rh.pend = rq.pend() ? reinterpret_cast<int32_t*>(res + nc) : nullptr;
     if (want_str) {
         HIPC(ctx, ctx->pin[pwa_ctx::PIN_STR].reserve(nc * sizeof(CigarPair) + (2 * nc + 2) * 4));
         rh.cpairs = ctx->pin[pwa_ctx::PIN_STR].as<CigarPair>();
@@ -514,10 +527,14 @@ int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& a
             res[q].end_i = (uint32_t)n;
             res[q].end_j = semi ? 0u : (uint32_t)m;
         }
+        if (rh.pend) {   // what the host reads when the kernel writes nothing: no value -- or, for an empty pattern, the anchor itself
+            rh.pend[2 * q] = n ? PWA_EXT_NO_PEND : 0;
+            rh.pend[2 * q + 1] = 0;
+        }
         if (want_str) rh.cpairs[q] = CigarPair{ar.aoff[rq.pair_a[k]], ar.aoff[rq.pair_b[k]], rh.ooff[q], (uint32_t)n, (uint32_t)m};
         oo += align_up(n + m + 1, 16);
     }
-    HIPC(ctx, hipMemcpy(ws.res(), res, nc * sizeof(PairResult), hipMemcpyHostToDevice));
+    HIPC(ctx, hipMemcpy(ws.res(), res, nc * rq.res_bytes(), hipMemcpyHostToDevice));
     if (want_str) HIPC(ctx, hipMemcpyAsync(ws.p_aux, rh.cpairs, nc * sizeof(CigarPair), hipMemcpyHostToDevice, ctx->stream));
     return PWA_OK;
 }
@@ -532,7 +549,8 @@ uint64_t banded_cells(int64_t n, int64_t m, int64_t lo, int64_t hi) {
 // One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; banded_kernels.hip
 // sizes the grid and launches fill + walk; the device times into `stats`.  A scores-only request: the same descriptors without band
 // and op regions, banded_scores_kernels.hip's pass alone, and the pairs' in-band cells into `stats`.  With a table (rq.sb) the same
-// descriptors go to banded_subst_kernels.hip's fill or pass; the walk is the same
+// descriptors go to banded_subst_kernels.hip's fill or pass; the walk is the same.  EXT with a table: PairDesc::rows (unused by the banded
+// class otherwise) points at the pair's pattern-end record, and banded_ext_subst_kernels.hip's fill or pass runs
 int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, const Launch& L,
                       const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const size_t np = L.q.size();
@@ -551,6 +569,7 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
         d.m = (int32_t)m;
         d.tb = scores ? nullptr : static_cast<uint8_t*>(ws.p_band) + L.bo[p];
         d.res = ws.res() + q;
+        if (rq.pend()) d.rows = reinterpret_cast<int32_t*>(ws.res() + (rg.k1 - rg.k0)) + 2 * q;
         d.ops = scores ? nullptr : ws.ops() + rh.ooff[q];
         d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
         d.n_stripes = (uint32_t)(((int64_t)n + S - 1) / S);
@@ -570,7 +589,11 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
     clock.mark("descriptor build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] banded %s RL=%d pairs=%zu hand-off row=%lld entries\n", scores ? "scores" : "fill", L.cls.rl, np, (long long)row_cap);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (rq.ext) {   // the same descriptors; the fill leaves rows_out in PairResult::overlap, the walk is NW's
+    if (rq.ext && rq.sb) {
+        const SubstRef& t = rq.sb->tab;
+        HIPC(ctx, pwa::banded_ext_subst_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], !scores, rq.ext->xdrop, t.tab, t.n_sym, t.stride));
+        if (scores) HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    } else if (rq.ext) {   // the same descriptors; the fill leaves rows_out in PairResult::overlap, the walk is NW's
         if (scores) {
             HIPC(ctx, pwa::banded_ext_scores_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, rq.ext->xdrop));
             HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -710,13 +733,14 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
 }
 
 // The range's results (and op lists) back on the host and into the caller's arrays
-// (EXT: rows_out travels in PairResult::overlap, which the banded class does not use otherwise; their sum goes into stats.cells)
+// (EXT: rows_out travels in PairResult::overlap, which the banded class does not use otherwise; their sum goes into stats.cells;
+// with a table the pattern-end records come back behind the results, in the same copy)
 int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& ws, const Range& rg, RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const uint64_t k0 = rg.k0, nc = rg.k1 - rg.k0;
     const AlignOut& o = rq.out;
     const bool local = rq.local(), semi = rq.semi(), want_ops = rq.want_ops();
     PairResult* const res = rh.res;
-    HIPC(ctx, hipMemcpy(res, ws.res(), nc * sizeof(PairResult), hipMemcpyDeviceToHost));
+    HIPC(ctx, hipMemcpy(res, ws.res(), nc * rq.res_bytes(), hipMemcpyDeviceToHost));
     if (want_ops && rg.tiled && rg.span) HIPC(ctx, hipMemcpy(o.ops + rh.ops_lo, ws.ops(), rg.span, hipMemcpyDeviceToHost));   // straight into the caller's list
     if (want_ops && !rg.tiled) HIPC(ctx, hipMemcpy(rh.host_ops.data(), ws.ops(), rg.opsb, hipMemcpyDeviceToHost));
     clock.mark("results (+ ops) to host");
@@ -755,6 +779,8 @@ int scatter_range(pwa_ctx* ctx, const AlignRequest& rq, const AlignWorkspaces& w
             const uint32_t rows = (n && m) ? (uint32_t)res[q].overlap : 0u;
             if (o.rows) o.rows[k] = rows;
             stats.cells += rows;
+            if (rh.pend && o.pend_score) o.pend_score[k] = rh.pend[2 * q];
+            if (rh.pend && o.pend_j) o.pend_j[k] = (uint32_t)rh.pend[2 * q + 1];
         }
         if (o.end_i) o.end_i[k] = res[q].end_i;
         if (o.end_j) o.end_j[k] = res[q].end_j;
@@ -940,8 +966,9 @@ static int gotoh_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend) {
 // context's buffer list when the call returns)
 // With band arrays (band_lo / band_hi, `stats` the banded slot of the calling form) the request also gets its BandSpec: the banded
 // substitution-matrix calls.  The table is uploaded once per call; every range of a PWA_RANGE_BYTES-cut list launches with it.
+// With an ExtSpec beside the band arrays: the EXT calls under a table (NW's matrix).
 static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n_sym, const int32_t* submat, int gap_extend, AlignStats& stats,
-                       bool banded = false, const int32_t* band_lo = nullptr, const int32_t* band_hi = nullptr) try {
+                       bool banded = false, const int32_t* band_lo = nullptr, const int32_t* band_hi = nullptr, const ExtSpec* ext = nullptr) try {
     if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gap penalties must be <= 0 (gap_open + L * gap_extend)");
     if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
     SubstTable tab;
@@ -954,6 +981,7 @@ static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n
     rq.gt = &gs;
     rq.sb = &ss;
     if (banded) rq.bd = &bs;
+    rq.ext = ext;
     if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (before anything is allocated; align_batch_impl checks again)
     HIPC(ctx, hipSetDevice(ctx->device));
     if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
@@ -1087,6 +1115,46 @@ int pwa_scores_extend_banded(pwa_ctx* ctx, int match, int mismatch, int gap_open
     out.rows = rows_out;
     return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
                         gap_extend, xdrop, band_lo, band_hi);
+}
+
+// their substitution-matrix forms: subst_batch with the band arrays and the ExtSpec, NW's matrix; they report into the EXT slot
+int pwa_extend_banded_subst_batch(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
+                                  const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                                  uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
+                                  uint32_t* rows_out, int32_t* pend_score_out, uint32_t* pend_j_out, const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
+    AlignOut out{OUT_OPS, score_out, end_cells, nullptr, ops, ops_off, n_ops, nullptr, {}};
+    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
+    const ExtSpec es{xdrop};
+    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
+                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
+}
+
+int pwa_extend_banded_subst_batch_cigar(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
+                                        const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
+                                        const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar, uint64_t cigar_cap,
+                                        uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells, uint32_t* rows_out,
+                                        int32_t* pend_score_out, uint32_t* pend_j_out, uint64_t needed[2], const int32_t* band_lo,
+                                        const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    AlignOut out{OUT_STRINGS, score_out, end_cells, nullptr, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
+    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
+    const ExtSpec es{xdrop};
+    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
+                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
+}
+
+int pwa_scores_extend_banded_subst(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
+                                   const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
+                                   uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, uint32_t* rows_out,
+                                   int32_t* pend_score_out, uint32_t* pend_j_out, const int32_t* band_lo, const int32_t* band_hi) {
+    if (!ctx) return PWA_E_INVALID;
+    AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
+    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
+    const ExtSpec es{xdrop};
+    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
+                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
 }
 
 int pwa_extend_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* rows_considered) {

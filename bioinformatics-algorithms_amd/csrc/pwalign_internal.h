@@ -109,7 +109,7 @@ struct pwa_ctx {
     AlignStats subst_stats;                // the last pwa_align_subst_batch(_cigar)
     AlignStats banded_stats;               // the last pwa_align_banded_batch(_cigar) or pwa_align_banded_subst_batch(_cigar)
     AlignStats banded_scores_stats;        // the last pwa_scores_banded or pwa_scores_banded_subst
-    AlignStats ext_stats;                  // the last pwa_extend_banded_batch(_cigar) or pwa_scores_extend_banded (cells: the sum of rows_out)
+    AlignStats ext_stats;                  // the last pwa_extend_banded_batch(_cigar), pwa_scores_extend_banded or a _subst form of them (cells: the sum of rows_out)
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):

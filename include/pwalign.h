@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
- *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls: every pair on stripes of 256 / 512 rows (default: by the pair's band width)
+ *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -451,7 +451,8 @@ int pwa_scores_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, uint64_t *i
  * equals the alignment call on (score, end, rows).
  * end_cells, rows_out, end_i_out and end_j_out may each be NULL.  A null score_out, band_lo or band_hi with n_pairs > 0 is
  * PWA_E_INVALID.  A call that fails validation leaves the stats unchanged; walk_ms is 0 after the scores call.
- * Not offered: a substitution-matrix form, ksw2's diagonal-aware Z-drop term, the best score of row n, a batch object.
+ * Not offered: ksw2's diagonal-aware Z-drop term, the pattern-end result (the best score of row n: the substitution-matrix forms below
+ * return it), a batch object.
  */
 int pwa_extend_banded_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop,
                             const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
@@ -471,6 +472,67 @@ int pwa_scores_extend_banded(pwa_ctx *ctx, int match, int mismatch, int gap_open
                              uint32_t *end_j_out /* or NULL */, uint32_t *rows_out /* or NULL */,
                              const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
 int pwa_extend_banded_last_stats(const pwa_ctx *ctx, float *fill_ms, float *walk_ms, uint64_t *rows_considered);
+
+/*
+ * BANDED X-DROP EXTENSION UNDER A SUBSTITUTION MATRIX, with a PATTERN-END result: the EXT calls above with the caller's score table,
+ * for a protein seed extended under BLOSUM-style scores, a long read with a neutral N, transitions scored apart from transversions.
+ *   pwa_extend_banded_subst_batch        pwa_extend_banded_batch's arguments with (code, n_sym, submat) in place of (match, mismatch),
+ *                                        and pend_score_out, pend_j_out after rows_out;
+ *   pwa_extend_banded_subst_batch_cigar  pwa_extend_banded_batch_cigar's, changed the same way;
+ *   pwa_scores_extend_banded_subst       pwa_scores_extend_banded's, changed the same way: no traceback band, no walk.
+ * Semantics: exactly those of the EXT block -- the banded NW matrix with no zero floor, validity band_lo <= 0 <= band_hi, the record
+ * and rmax(i) over 1 <= j <= m, the stop rule, rows_out, NW's walk, the empty-side conventions, the band width of at most 4096,
+ * PWA_RANGE_BYTES (the table is uploaded once per call and serves every range), the empty list (PWA_OK) -- with
+ *   s(i,j) = submat[ code[p[i-1]] * n_sym + code[t[j-1]] ]
+ * and code, n_sym, submat as in the substitution-matrix block: n_sym is 1 .. 32, every one of the 256 code entries is < n_sym, the
+ * table may be asymmetric and may hold any signs, and both are copied during the call.  CIGAR and MD:Z come from the ops and the RAW
+ * bytes: MD:Z reports byte identity, not the sign of the score.
+ * Pattern end (ksw2_extz's mqe / mqe_t): did the extension reach the end of the pattern, and what does the to-end alignment score?
+ * If n >= 1 and rows_out[k] == n: pend_score_out[k] = rmax(n), pend_j_out[k] = the smallest column attaining it (rows_out == n
+ * implies that row n has an in-band cell with j >= 1, so the value is real; it may lie below score_out[k], whose end row is then
+ * above n).  Otherwise -- a row up to and including n stopped the sweep, the band left the matrix before row n, or m = 0 with n > 0 --
+ * pend_score_out[k] = PWA_EXT_NO_PEND and pend_j_out[k] = 0.  For n = 0 the anchor is the pattern's end: score 0 and j 0.  The
+ * result depends on nothing but the fill, so the three calls agree on it.  Where pend_j >= 1, pend_score is the score that
+ * pwa_scores_banded_subst(PWA_MODE_NW) gives for the pattern against the text's first pend_j symbols under the same band.
+ * pend_score_out and pend_j_out may each be NULL.
+ * Range.  (n + m + 2) * max(max |submat|, |gap_open| + |gap_extend|, 1) < 2^27, else PWA_E_CAPACITY: the EXT block's one-bit-tighter
+ * rule with the table's magnitude, because the row maxima are kept as H * 16 + 4 column bits and H may be negative.  With A that
+ * maximum, every H, E or F that stands for a path inside the band is a sum of at most n + m + 1 steps of magnitude <= A each, so
+ * |V| < 2^27 - A: the alignment fill's sentinel key -2^31 + 8 A + 1 is below every key V * 8 + 0..7, the score pass's plain sentinel
+ * -2^30 below every V and V + gap_open + gap_extend, and a sentinel meets at most one gap extension (>= -A) before the sum is compared
+ * and dropped; only |s| enters the bound.  The row key H * 16 + 0..15 of a real H lies strictly inside int32 and above the key
+ * INT32_MIN of a row without an in-band cell, whose H reads as -2^27, below every real H; best - xdrop cannot wrap.
+ * Checks, all before any device work: first the table's own, as pwa_align_banded_subst_batch makes them (PWA_E_INVALID for a null
+ * code or submat, n_sym outside 1 .. 32, a code[] entry >= n_sym, gap_open > 0 or gap_extend > 0, a null band_lo or band_hi with
+ * n_pairs > 0); then xdrop > 2^27 (PWA_E_INVALID); then per pair, in pair order, band_lo > band_hi, the anchor rule, the width and
+ * the range rule (the first offending pair decides the error).
+ * Stats: pwa_extend_banded_last_stats, the same record as the byte-compare EXT calls; pwa_align_subst_last_stats and the
+ * pwa_align_banded / pwa_scores_banded stats are not touched.  A call that fails validation leaves all stats unchanged.
+ * Not offered: ksw2's diagonal-aware Z-drop term, a batch object, named matrices.
+ */
+#define PWA_EXT_NO_PEND INT32_MIN /* pend_score_out: row n was not reached or not kept */
+int pwa_extend_banded_subst_batch(pwa_ctx *ctx, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                                  int gap_extend, int xdrop, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                  const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out, uint8_t *ops,
+                                  const uint64_t *ops_off, uint64_t *n_ops, uint64_t *end_cells /* 2*n_pairs or NULL */,
+                                  uint32_t *rows_out /* n_pairs or NULL */, int32_t *pend_score_out /* n_pairs or NULL */,
+                                  uint32_t *pend_j_out /* n_pairs or NULL */, const int32_t *band_lo /* n_pairs */,
+                                  const int32_t *band_hi /* n_pairs */);
+int pwa_extend_banded_subst_batch_cigar(pwa_ctx *ctx, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                                        int gap_extend, int xdrop, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                        const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                        char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                        char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                        uint64_t *end_cells /* 2*n_pairs or NULL */, uint32_t *rows_out /* n_pairs or NULL */,
+                                        int32_t *pend_score_out /* n_pairs or NULL */, uint32_t *pend_j_out /* n_pairs or NULL */,
+                                        uint64_t needed[2] /* or NULL */, const int32_t *band_lo /* n_pairs */,
+                                        const int32_t *band_hi /* n_pairs */);
+int pwa_scores_extend_banded_subst(pwa_ctx *ctx, const uint8_t code[256], int n_sym, const int32_t *submat, int gap_open,
+                                   int gap_extend, int xdrop, const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq,
+                                   const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                   uint32_t *end_i_out /* or NULL */, uint32_t *end_j_out /* or NULL */, uint32_t *rows_out /* or NULL */,
+                                   int32_t *pend_score_out /* or NULL */, uint32_t *pend_j_out /* or NULL */,
+                                   const int32_t *band_lo /* n_pairs */, const int32_t *band_hi /* n_pairs */);
 
 /*
  * Affine-gap ("gotoh") SCORES of many pairs: what pwa_scores / pwa_batch_create are to pwa_align_batch.  Recurrence, boundaries, raw-byte
