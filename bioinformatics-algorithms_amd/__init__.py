@@ -41,11 +41,31 @@ EXPORTS = [
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
+    "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
 ]
 
 
 class PwaError(RuntimeError):
     pass
+
+
+def approx_plan(n, pat_len, max_dist, chunk):
+    """pwa_approx_plan (host only): the tasks (pattern, scan_lo, lo, hi) of a text of n against patterns of these lengths and bounds."""
+    L = lib()
+    n_pat = len(pat_len)
+    pl = (C.c_uint32 * max(n_pat, 1))(*pat_len)
+    md = (C.c_uint32 * max(n_pat, 1))(*max_dist)
+    nt = C.c_uint64(0)
+    rc = L.pwa_approx_plan(n, pl, md, n_pat, chunk, None, None, None, None, 0, C.byref(nt))
+    if rc not in (0, -5):
+        raise PwaError("pwa_approx_plan: %s" % L.pwa_strerror(rc).decode())
+    cap = nt.value
+    tp = (C.c_uint32 * max(cap, 1))()
+    ts, tl, th = ((C.c_uint64 * max(cap, 1))() for _ in range(3))
+    rc = L.pwa_approx_plan(n, pl, md, n_pat, chunk, tp, ts, tl, th, cap, C.byref(nt))
+    if rc != 0:
+        raise PwaError("pwa_approx_plan: %s" % L.pwa_strerror(rc).decode())
+    return [(tp[t], ts[t], tl[t], th[t]) for t in range(cap)]
 
 
 _hw1 = None
@@ -220,6 +240,10 @@ def lib():
     L.pwa_sa_last_stats.argtypes = [vp, u32p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pwa_sa_destroy.argtypes = [vp]
     L.pwa_sa_destroy.restype = None
+    L.pwa_approx_find.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u32p, i32p, u32p]
+    L.pwa_approx_occurrences.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
+    L.pwa_approx_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
+    L.pwa_approx_plan.argtypes = [C.c_uint64, u32p, u32p, C.c_uint32, C.c_uint32, u32p, u64p, u64p, u64p, C.c_uint64, u64p]
     _lib = L
     return L
 
@@ -989,6 +1013,45 @@ class Context:
             return [[(occ[e] >> 32, occ[e] & 0xffffffff) for e in range(occ_off[k], occ_off[k + 1])] for k in range(n_pat)]
         finally:
             self._L.pwa_sa_destroy(ix)
+
+    # -- k-edit approximate search of one text (include/pwalign.h, pwa_approx_*)
+    def _approx_args(self, text, patterns, k):
+        blob, off, pats = pack_sequences(patterns)
+        n_pat = len(pats)
+        ks = [k] * n_pat if isinstance(k, int) else list(k)
+        if len(ks) != n_pat:
+            raise ValueError("k: one int, or one per pattern")
+        return _b(text), blob, off, n_pat, (C.c_uint32 * max(n_pat, 1))(*ks)
+
+    def _approx_stats(self):
+        c, f, t, col = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_approx_last_stats(self._h, C.byref(c), C.byref(f), C.byref(t), C.byref(col)), "pwa_approx_last_stats")
+        self.approx_stats = dict(count_ms=c.value, fill_ms=f.value, tasks=t.value, columns=col.value)
+
+    def count_approx(self, text, patterns, k):
+        """Per pattern, the ends e in 1 .. len(text) where it matches text[.. e) within k edits (k: one int, or one per pattern):
+        (counts, best), best[q] = (dist, end) of the smallest distance and, at that distance, the smallest end, or None."""
+        text, blob, off, n_pat, kd = self._approx_args(text, patterns, k)
+        cnt = (C.c_uint32 * max(n_pat, 1))()
+        bd = (C.c_int32 * max(n_pat, 1))()
+        be = (C.c_uint32 * max(n_pat, 1))()
+        self._check(self._L.pwa_approx_find(self._h, text, len(text), blob, off, n_pat, kd, cnt, bd, be), "pwa_approx_find")
+        self._approx_stats()
+        return list(cnt[:n_pat]), [(bd[q], be[q]) if bd[q] >= 0 else None for q in range(n_pat)]
+
+    def find_approx(self, text, patterns, k):
+        """Per pattern, the list of (end, dist) of its hits in ascending end."""
+        text, blob, off, n_pat, kd = self._approx_args(text, patterns, k)
+        cnt = (C.c_uint32 * max(n_pat, 1))()
+        self._check(self._L.pwa_approx_find(self._h, text, len(text), blob, off, n_pat, kd, cnt, None, None), "pwa_approx_find")
+        cap = sum(cnt[:n_pat])
+        occ_off = (C.c_uint64 * (n_pat + 1))()
+        occ = (C.c_uint64 * max(cap, 1))()
+        need = C.c_uint64(0)
+        self._check(self._L.pwa_approx_occurrences(self._h, text, len(text), blob, off, n_pat, kd, occ_off, occ, cap, C.byref(need)),
+                    "pwa_approx_occurrences")
+        self._approx_stats()
+        return [[(occ[x] >> 32, occ[x] & 0xffffffff) for x in range(occ_off[q], occ_off[q + 1])] for q in range(n_pat)]
 
 
 class Batch:

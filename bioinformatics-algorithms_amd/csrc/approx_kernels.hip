@@ -1,0 +1,366 @@
+// approx_kernels.hip -- the approximate-search entries of include/pwalign.h (pwa_approx_*): validation, the task plan, the lane
+// order, device buffers, the count and the fill pass.  Kernels: approx.hip.h.  DESIGN.md §3.18.
+#include "../../include/pwalign.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "approx.hip.h"
+#include "approx_ctx.h"
+#include "sufarr_ctx.h"
+
+using namespace pwa::approx;
+
+namespace {
+
+constexpr uint64_t kDefaultSliceHits = 1ull << 27;   // 8 B of staging per hit: 1 GB per slice at most
+constexpr uint64_t kMaxSliceHits = 1ull << 31;       // offsets within a slice are uint32
+
+struct Dev {   // one device allocation, freed with its owner
+    void* p = nullptr;
+    Dev() = default;
+    Dev(const Dev&) = delete;
+    Dev& operator=(const Dev&) = delete;
+    ~Dev() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        return hipMalloc(&p, std::max<size_t>(bytes, 16));
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+struct Fail {   // an error on the way: the code and what to say about it
+    int code;
+    std::string what;
+};
+void check(hipError_t e, const char* what) {
+    if (e != hipSuccess) throw Fail{e == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
+}
+#define AP_CHECK(call) check((call), #call)
+
+using scan_kernel_t = decltype(&approx_scan_kernel<1, false>);
+template <bool FILL>
+scan_kernel_t scan_kernel_for(int W) {
+    switch (W) {
+        case 1: return approx_scan_kernel<1, FILL>;
+        case 2: return approx_scan_kernel<2, FILL>;
+        case 3: return approx_scan_kernel<3, FILL>;
+        case 4: return approx_scan_kernel<4, FILL>;
+        case 5: return approx_scan_kernel<5, FILL>;
+        case 6: return approx_scan_kernel<6, FILL>;
+        case 7: return approx_scan_kernel<7, FILL>;
+        default: return approx_scan_kernel<8, FILL>;
+    }
+}
+
+// Everything a call keeps on the device and the host between its passes
+struct Search {
+    uint32_t rows = 0;                            // sigma + 1: the codes of the call
+    uint64_t n_tasks = 0, columns = 0;
+    std::vector<Pat> pats;
+    uint32_t first_wave[kMaxWords + 2] = {};      // class W's waves are lane_task[64 * first_wave[W] .. 64 * first_wave[W + 1])
+    Dev text, blob, d_pats, peq, tasks, lane_task, task_cnt, pat_cnt, pat_best;
+    std::vector<uint32_t> h_cnt;                  // hits per pattern
+    std::vector<uint64_t> h_best;
+};
+
+void launch_scan(const pwa::ApproxCtxView& v, Search& s, bool fill, uint32_t t0, uint32_t t1, const uint32_t* d_off, uint64_t* d_out, uint32_t out_cap) {
+    for (int W = 1; W <= kMaxWords; ++W) {
+        const uint32_t waves = s.first_wave[W + 1] - s.first_wave[W];
+        if (!waves) continue;
+        scan_kernel_t kern = fill ? scan_kernel_for<true>(W) : scan_kernel_for<false>(W);
+        const size_t lds = (size_t)s.rows * W * 64 * 8;
+        if (lds > 64 * 1024) AP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(waves), dim3(64), lds, v.stream, s.text.as<uint8_t>(), s.peq.as<uint64_t>(), s.d_pats.as<Pat>(), s.tasks.as<Task>(),
+                           s.lane_task.as<uint32_t>() + (size_t)64 * s.first_wave[W], s.rows, s.task_cnt.as<uint32_t>(), s.pat_cnt.as<uint32_t>(),
+                           s.pat_best.as<unsigned long long>(), t0, t1, d_off, d_out, out_cap);
+        AP_CHECK(hipGetLastError());
+    }
+}
+
+// The limits of include/pwalign.h, without the device; on PWA_OK tab maps a byte to its code and sigma is the number of pattern bytes
+int validate(const pwa::ApproxCtxView& v, const char* who, uint64_t n, const uint8_t* pb, const uint64_t* poff, uint32_t n_pat, CodeTable& tab, uint32_t& sigma) {
+    if (n >= (1ull << 31)) {
+        *v.err = std::string(who) + ": a text of " + std::to_string(n) + " bytes; positions are int32, so at most 2^31 - 1";
+        return PWA_E_CAPACITY;
+    }
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        if (poff[q + 1] < poff[q]) return PWA_E_INVALID;
+        const uint64_t m = poff[q + 1] - poff[q];
+        if (m == 0) {
+            *v.err = std::string(who) + ": pattern " + std::to_string(q) + " is empty";
+            return PWA_E_INVALID;
+        }
+        if (m > 64 * kMaxWords) {
+            *v.err = std::string(who) + ": pattern " + std::to_string(q) + " has " + std::to_string(m) + " symbols, at most " + std::to_string(64 * kMaxWords);
+            return PWA_E_CAPACITY;
+        }
+    }
+    bool seen[256] = {};
+    if (n_pat)
+        for (uint64_t i = poff[0]; i < poff[n_pat]; ++i) seen[pb[i]] = true;
+    sigma = 0;
+    for (int c = 0; c < 256; ++c) sigma += seen[c];
+    if (sigma > kMaxSym) {
+        *v.err = std::string(who) + ": the patterns hold " + std::to_string(sigma) + " distinct byte values, at most " + std::to_string(kMaxSym);
+        return PWA_E_CAPACITY;
+    }
+    uint32_t next = 0;
+    for (int c = 0; c < 256; ++c) tab.t[c] = seen[c] ? (uint8_t)next++ : (uint8_t)sigma;
+    return PWA_OK;
+}
+
+// Uploads, codes the text, builds the masks, runs the count pass; fills s.h_cnt / s.h_best and the stats of v
+void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uint64_t n, const uint8_t* pb, const uint64_t* poff, uint32_t n_pat,
+                const uint32_t* max_dist, const CodeTable& tab, uint32_t sigma) {
+    s.rows = sigma + 1;
+    s.h_cnt.assign(n_pat, 0);
+    s.h_best.assign(n_pat, kNoBest);
+    *v.stats = pwa::ApproxStats{};
+    if (!n || !n_pat) return;
+    // the plan, as any caller gets it
+    std::vector<uint32_t> len(n_pat);
+    for (uint32_t q = 0; q < n_pat; ++q) len[q] = (uint32_t)(poff[q + 1] - poff[q]);
+    uint64_t nt = 0;
+    (void)pwa_approx_plan(n, len.data(), max_dist, n_pat, v.chunk, nullptr, nullptr, nullptr, nullptr, 0, &nt);
+    if (nt >= kNoTask) throw Fail{PWA_E_CAPACITY, "pwa_approx: " + std::to_string(nt) + " tasks; task numbers are uint32 (raise PWA_APPROX_CHUNK)"};
+    std::vector<uint32_t> t_pat(nt);
+    std::vector<uint64_t> t_scan(nt), t_lo(nt), t_hi(nt);
+    if (pwa_approx_plan(n, len.data(), max_dist, n_pat, v.chunk, t_pat.data(), t_scan.data(), t_lo.data(), t_hi.data(), nt, &nt) != PWA_OK)
+        throw Fail{PWA_E_INVALID, "pwa_approx: the task plan failed"};
+    s.n_tasks = nt;
+    std::vector<Task> tasks(nt);
+    for (uint64_t t = 0; t < nt; ++t) {
+        tasks[t] = Task{t_pat[t], (uint32_t)t_scan[t], (uint32_t)t_lo[t], (uint32_t)t_hi[t]};
+        s.columns += t_hi[t] - t_scan[t];
+    }
+    // patterns, their masks' places, their first tasks
+    const uint64_t base = poff[0], bytes = poff[n_pat] - base;
+    s.pats.resize(n_pat);
+    std::vector<uint32_t> first_task(n_pat + 1, 0);
+    uint64_t peq_words = 0;
+    const uint64_t per_pat = (n + v.chunk - 1) / v.chunk;
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        const uint32_t W = (len[q] + 63) / 64;
+        if (peq_words + (uint64_t)s.rows * W > 0xffffffffull || poff[q] - base > 0xffffffffull)
+            throw Fail{PWA_E_CAPACITY, "pwa_approx: the patterns of one call exceed 32-bit offsets"};
+        s.pats[q] = Pat{(uint32_t)(poff[q] - base), len[q], std::min(max_dist[q], len[q]), (uint32_t)peq_words, W};
+        peq_words += (uint64_t)s.rows * W;
+        first_task[q + 1] = first_task[q] + (uint32_t)per_pat;
+    }
+    // lane order: per word class, chunk by chunk, the patterns of the class side by side; a wave holds one class
+    std::vector<uint32_t> lane_task;
+    lane_task.reserve(nt + 64 * kMaxWords);
+    for (int W = 1; W <= kMaxWords; ++W) {
+        s.first_wave[W] = (uint32_t)(lane_task.size() / 64);
+        std::vector<uint32_t> of_class;
+        for (uint32_t q = 0; q < n_pat; ++q)
+            if ((int)s.pats[q].W == W) of_class.push_back(q);
+        for (uint64_t c = 0; c < per_pat && !of_class.empty(); ++c)
+            for (uint32_t q : of_class) lane_task.push_back(first_task[q] + (uint32_t)c);
+        lane_task.resize((lane_task.size() + 63) / 64 * 64, kNoTask);
+    }
+    s.first_wave[kMaxWords + 1] = (uint32_t)(lane_task.size() / 64);
+
+    (void)hipSetDevice(v.device);
+    const size_t tbytes = (n + 15) / 16 * 16 + 16;
+    AP_CHECK(s.text.alloc(tbytes));
+    AP_CHECK(s.blob.alloc(bytes));
+    AP_CHECK(s.d_pats.alloc((size_t)n_pat * sizeof(Pat)));
+    AP_CHECK(s.peq.alloc(peq_words * 8));
+    AP_CHECK(s.tasks.alloc(nt * sizeof(Task)));
+    AP_CHECK(s.lane_task.alloc(lane_task.size() * 4));
+    AP_CHECK(s.task_cnt.alloc(nt * 4));
+    AP_CHECK(s.pat_cnt.alloc((size_t)n_pat * 4));
+    AP_CHECK(s.pat_best.alloc((size_t)n_pat * 8));
+    Events ev;
+    AP_CHECK(hipEventCreate(&ev.a));
+    AP_CHECK(hipEventCreate(&ev.b));
+    AP_CHECK(hipMemsetAsync(s.text.p, 0, tbytes, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.d_pats.p, s.pats.data(), (size_t)n_pat * sizeof(Pat), hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.tasks.p, tasks.data(), nt * sizeof(Task), hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.lane_task.p, lane_task.data(), lane_task.size() * 4, hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemsetAsync(s.pat_cnt.p, 0, (size_t)n_pat * 4, v.stream));
+    AP_CHECK(hipMemsetAsync(s.pat_best.p, 0xff, (size_t)n_pat * 8, v.stream));
+    AP_CHECK(hipEventRecord(ev.a, v.stream));
+    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), tbytes / 16, tab.t));
+    const uint64_t mask_threads = (uint64_t)n_pat * s.rows * kMaxWords;
+    approx_masks_kernel<<<(uint32_t)((mask_threads + 255) / 256), 256, 0, v.stream>>>(s.blob.as<uint8_t>(), s.d_pats.as<Pat>(), n_pat, s.rows, tab, s.peq.as<uint64_t>());
+    AP_CHECK(hipGetLastError());
+    launch_scan(v, s, false, 0, 0, nullptr, nullptr, 0);
+    AP_CHECK(hipEventRecord(ev.b, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.h_cnt.data(), s.pat_cnt.p, (size_t)n_pat * 4, hipMemcpyDeviceToHost, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.h_best.data(), s.pat_best.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, v.stream));
+    AP_CHECK(hipStreamSynchronize(v.stream));
+    AP_CHECK(hipEventElapsedTime(&v.stats->count_ms, ev.a, ev.b));
+    v.stats->tasks = nt;
+    v.stats->columns = s.columns;
+    if (v.debug)
+        std::fprintf(stderr, "[pwa] approx count: %u patterns, sigma=%u, %llu tasks, %llu columns, device %.3f ms\n", n_pat, sigma, (unsigned long long)nt,
+                     (unsigned long long)s.columns, v.stats->count_ms);
+}
+
+// The fill pass: slices of whole tasks whose hits fit the staging budget (one task alone may exceed it: at most chunk hits)
+void fill_pass(const pwa::ApproxCtxView& v, Search& s, uint64_t* occ) {
+    if (!s.n_tasks) return;
+    const uint64_t budget = std::min(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultSliceHits, kMaxSliceHits);
+    std::vector<uint32_t> cnt(s.n_tasks);
+    AP_CHECK(hipMemcpyAsync(cnt.data(), s.task_cnt.p, s.n_tasks * 4, hipMemcpyDeviceToHost, v.stream));
+    AP_CHECK(hipStreamSynchronize(v.stream));
+    struct Slice {
+        uint32_t t0, t1;
+        uint64_t hits;
+    };
+    std::vector<Slice> slices;
+    uint64_t max_hits = 0;
+    uint32_t max_nt = 0;
+    for (uint32_t t0 = 0; t0 < s.n_tasks;) {
+        uint64_t hits = cnt[t0];
+        uint32_t t1 = t0 + 1;
+        while (t1 < s.n_tasks && hits + cnt[t1] <= budget) hits += cnt[t1++];
+        if (hits) {
+            slices.push_back({t0, t1, hits});
+            max_hits = std::max(max_hits, hits);
+            max_nt = std::max(max_nt, t1 - t0);
+        }
+        t0 = t1;
+    }
+    if (slices.empty()) return;
+    Dev off, part, stage;
+    AP_CHECK(off.alloc((size_t)max_nt * 4));
+    AP_CHECK(part.alloc(pwa::scan_part_words(max_nt) * 4));
+    AP_CHECK(stage.alloc(max_hits * 8));
+    Events ev;
+    AP_CHECK(hipEventCreate(&ev.a));
+    AP_CHECK(hipEventCreate(&ev.b));
+    uint64_t kept = 0;
+    for (const Slice& sl : slices) {
+        const uint32_t nt = sl.t1 - sl.t0;
+        AP_CHECK(hipEventRecord(ev.a, v.stream));
+        AP_CHECK(hipMemcpyAsync(off.p, s.task_cnt.as<uint32_t>() + sl.t0, (size_t)nt * 4, hipMemcpyDeviceToDevice, v.stream));
+        pwa::scan_excl(v.stream, off.as<uint32_t>(), nt, part.as<uint32_t>());
+        AP_CHECK(hipGetLastError());
+        launch_scan(v, s, true, sl.t0, sl.t1, off.as<uint32_t>(), stage.as<uint64_t>(), (uint32_t)sl.hits);
+        AP_CHECK(hipEventRecord(ev.b, v.stream));
+        AP_CHECK(hipMemcpyAsync(occ + kept, stage.p, sl.hits * 8, hipMemcpyDeviceToHost, v.stream));
+        AP_CHECK(hipStreamSynchronize(v.stream));
+        float ms = 0.f;
+        AP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        v.stats->fill_ms += ms;
+        kept += sl.hits;
+    }
+    if (v.debug) std::fprintf(stderr, "[pwa] approx fill: %zu slices, %llu hits, device %.3f ms\n", slices.size(), (unsigned long long)kept, v.stats->fill_ms);
+}
+
+int fail(pwa::ApproxCtxView& v, const Fail& f) {
+    *v.err = f.what;
+    return f.code;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pwa_approx_plan(uint64_t n, const uint32_t* pat_len, const uint32_t* max_dist, uint32_t n_pat, uint32_t chunk, uint32_t* task_pat,
+                    uint64_t* task_scan_lo, uint64_t* task_lo, uint64_t* task_hi, uint64_t cap, uint64_t* n_tasks) {
+    if (!n_tasks || !chunk || ((!pat_len || !max_dist) && n_pat)) return PWA_E_INVALID;
+    for (uint32_t q = 0; q < n_pat; ++q)
+        if (!pat_len[q]) return PWA_E_INVALID;
+    const uint64_t per_pat = n / chunk + (n % chunk != 0);
+    *n_tasks = per_pat * n_pat;
+    if (*n_tasks > cap) return PWA_E_CAPACITY;
+    if (*n_tasks && (!task_pat || !task_scan_lo || !task_lo || !task_hi)) return PWA_E_INVALID;
+    uint64_t t = 0;
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        const uint64_t w = (uint64_t)pat_len[q] + std::min(max_dist[q], pat_len[q]);
+        for (uint64_t lo = 0; lo < n; lo += chunk, ++t) {
+            task_pat[t] = q;
+            task_scan_lo[t] = (lo > w ? lo - w : 0) & ~15ull;
+            task_lo[t] = lo;
+            task_hi[t] = std::min<uint64_t>(lo + chunk, n);
+        }
+    }
+    return PWA_OK;
+}
+
+int pwa_approx_find(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat,
+                    const uint32_t* max_dist, uint32_t* counts_out, int32_t* best_dist_out, uint32_t* best_end_out) {
+    if (!ctx || !pat_off || (!text && n) || ((!max_dist || !counts_out) && n_pat) || (!pat_bytes && pat_off[n_pat] != pat_off[0])) return PWA_E_INVALID;
+    pwa::ApproxCtxView v = pwa::approx_ctx_view(ctx);
+    CodeTable tab;
+    uint32_t sigma = 0;
+    if (const int rc = validate(v, "pwa_approx_find", n, pat_bytes, pat_off, n_pat, tab, sigma)) return rc;
+    try {
+        Search s;
+        count_pass(v, s, text, n, pat_bytes, pat_off, n_pat, max_dist, tab, sigma);
+        for (uint32_t q = 0; q < n_pat; ++q) {
+            counts_out[q] = s.h_cnt[q];
+            const bool hit = s.h_best[q] != kNoBest;
+            if (best_dist_out) best_dist_out[q] = hit ? (int32_t)(s.h_best[q] >> 32) : -1;
+            if (best_end_out) best_end_out[q] = hit ? (uint32_t)s.h_best[q] : 0;
+        }
+    } catch (const Fail& f) {
+        return fail(v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_approx_occurrences(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat,
+                           const uint32_t* max_dist, uint64_t* occ_off, uint64_t* occ, uint64_t cap, uint64_t* needed) {
+    if (!ctx || !pat_off || !occ_off || (!text && n) || (!max_dist && n_pat) || (!occ && cap) || (!pat_bytes && pat_off[n_pat] != pat_off[0]))
+        return PWA_E_INVALID;
+    pwa::ApproxCtxView v = pwa::approx_ctx_view(ctx);
+    CodeTable tab;
+    uint32_t sigma = 0;
+    if (const int rc = validate(v, "pwa_approx_occurrences", n, pat_bytes, pat_off, n_pat, tab, sigma)) return rc;
+    try {
+        Search s;
+        count_pass(v, s, text, n, pat_bytes, pat_off, n_pat, max_dist, tab, sigma);
+        uint64_t total = 0;
+        for (uint32_t q = 0; q < n_pat; ++q) {
+            occ_off[q] = total;
+            total += s.h_cnt[q];
+        }
+        occ_off[n_pat] = total;
+        if (needed) *needed = total;
+        if (total > cap) {
+            *v.err = "pwa_approx_occurrences: " + std::to_string(total) + " hits, capacity " + std::to_string(cap);
+            return PWA_E_CAPACITY;
+        }
+        if (total) fill_pass(v, s, occ);
+    } catch (const Fail& f) {
+        return fail(v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_approx_last_stats(const pwa_ctx* ctx, float* count_ms, float* fill_ms, uint64_t* tasks, uint64_t* columns) {
+    if (!ctx) return PWA_E_INVALID;
+    const pwa::ApproxStats& st = pwa::approx_stats_of(ctx);
+    if (count_ms) *count_ms = st.count_ms;
+    if (fill_ms) *fill_ms = st.fill_ms;
+    if (tasks) *tasks = st.tasks;
+    if (columns) *columns = st.columns;
+    return PWA_OK;
+}
+
+}  // extern "C"

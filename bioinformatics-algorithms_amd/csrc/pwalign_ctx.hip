@@ -8,6 +8,7 @@
 #include <cstring>
 #include <new>
 
+#include "approx_ctx.h"
 #include "sufarr_ctx.h"
 
 using namespace pwa;
@@ -79,6 +80,7 @@ void Knobs::read() {
     prof16_int = num("PWA_PROF16_INT", -1);
     affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
     if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    if (const char* e = std::getenv("PWA_APPROX_CHUNK")) approx_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)), 1u << 30);
 }
 
 pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
@@ -89,6 +91,27 @@ pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
     v.occ_chunk_hits = c->knobs.occ_chunk_hits;
     v.err = &c->err;
     return v;
+}
+
+pwa::ApproxCtxView pwa::approx_ctx_view(pwa_ctx* c) {
+    ApproxCtxView v;
+    v.device = c->device;
+    v.stream = c->stream;
+    v.debug = c->knobs.debug;
+    v.chunk = c->knobs.approx_chunk;
+    v.occ_chunk_hits = c->knobs.occ_chunk_hits;
+    v.err = &c->err;
+    v.stats = &c->approx_stats;
+    return v;
+}
+const pwa::ApproxStats& pwa::approx_stats_of(const pwa_ctx* c) { return c->approx_stats; }
+
+hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_t* table) {
+    if (!n16) return hipSuccess;
+    RecodeTable rt;
+    std::memcpy(rt.t, table, 256);
+    hipLaunchKernelGGL(pwa_recode_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 4096)), dim3(256), 0, s, p, n16, rt);
+    return hipGetLastError();
 }
 
 namespace {

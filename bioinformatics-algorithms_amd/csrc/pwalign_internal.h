@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "approx_ctx.h"
 #include "kernel_table.h"
 #include "subst_table.h"
 
@@ -76,7 +77,9 @@ struct Knobs {
                                                 // texts), 1 = always where the batch admits it, unset = by estimated cost
     int prof16_int = -1;                        // PWA_PROF16_INT: 0 = never the profile form's integer-coded row, 1 or unset = wherever the
                                                 // scoring admits it (mismatch >= gap and match >= gap)
-    uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences (tests: several chunks)
+    uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences, most staged hits per slice
+                                                // of tasks of pwa_approx_occurrences (tests: several chunks)
+    uint32_t approx_chunk = 4096;               // PWA_APPROX_CHUNK: most text columns one task of pwa_approx_* reports
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
     int banded_rl = 0;                          // PWA_BANDED_RL: 4 | 8 = every banded pair (alignments and scores) on stripes of 64 x 4 / 64 x 8 rows (tests), unset = by band width
@@ -111,6 +114,7 @@ struct pwa_ctx {
     AlignStats banded_scores_stats;        // the last pwa_scores_banded or pwa_scores_banded_subst
     AlignStats ext_stats;                  // the last pwa_extend_banded_batch(_cigar), pwa_scores_extend_banded or a _subst form of them (cells: the sum of rows_out)
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
+    pwa::ApproxStats approx_stats;         // the last pwa_approx_find / pwa_approx_occurrences
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
     // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the

@@ -52,7 +52,9 @@
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
- *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list)
+ *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
+ *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks
+ *   PWA_APPROX_CHUNK=N            pwa_approx_find / pwa_approx_occurrences: a task reports at most N text columns (default 4096)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
  *   PWA_NO_PAIR_TABLE, PWA_NO_KEYED_TB, PWA_NO_GAP_SHIFT, PWA_NO_TILED_OPS, PWA_NO_PACKED_DIST, PWA_FORCE_LANES,
@@ -709,6 +711,44 @@ int pwa_sa_occurrences(pwa_sa_index *ix, const uint8_t *pat_bytes, const uint64_
                        uint32_t n_ref, const uint32_t *header_rank, uint64_t *occ_off, uint64_t *occ, uint64_t cap, uint64_t *needed);
 int pwa_sa_last_stats(const pwa_sa_index *ix, uint32_t *rounds, float *build_ms, float *search_ms);
 void pwa_sa_destroy(pwa_sa_index *ix);
+
+/* ---- k-edit approximate pattern search (Sellers' DP on bit-parallel columns, Myers 1999)
+ *
+ * For a pattern p of m >= 1 bytes and a text t of n bytes:  D[0][j] = 0, D[i][0] = i,
+ *   D[i][j] = min(D[i-1][j-1] + (p[i-1] != t[j-1]), D[i-1][j] + 1, D[i][j-1] + 1),
+ * bytes compared as bytes.  A hit of pattern q is every end e in 1 .. n with D[m][e] <= max_dist[q]; its distance is D[m][e].  e = 0 is
+ * never a hit; max_dist >= m is legal (every end is then a hit, with its exact distance).  Pattern q is
+ * pat_bytes[pat_off[q] .. pat_off[q + 1]).
+ *   pwa_approx_find         counts_out[n_pat]: hits per pattern.  best_dist_out / best_end_out (each may be NULL): the smallest distance
+ *                           and, among the hits of that distance, the smallest end; -1 and 0 for a pattern without a hit.  One pass over
+ *                           the text (the count pass).
+ *   pwa_approx_occurrences  pattern q's hits are occ[occ_off[q] .. occ_off[q + 1]), in ascending end, occ[x] = (uint64_t)e << 32 | dist.
+ *                           The count pass, then the fill pass, whose hits are staged on the device in slices of whole tasks.
+ *                           PWA_E_CAPACITY with *needed set (needed may be NULL) when cap < the number of hits; occ_off is complete
+ *                           then, occ is untouched.  The sum of pwa_approx_find's counts always suffices.
+ *   pwa_approx_last_stats   of the last of the two calls on ctx: device ms of the count and of the fill pass (events; fill_ms is 0 after
+ *                           pwa_approx_find), the number of tasks, and the text columns they scanned, warm-up included.
+ *   pwa_approx_plan         host only, no context, no GPU: the task list the two calls run.  A task is (pattern, report columns [lo, hi),
+ *                           first scanned column scan_lo): the scan starts from the fresh column D[i] = i at scan_lo and reports ends
+ *                           lo + 1 .. hi.  Per pattern the [lo, hi) tile [0, n) in ascending order with hi - lo <= chunk, tasks come in
+ *                           (pattern, lo) order, and scan_lo = max(0, lo - w) rounded down to a multiple of 16, w = m + min(max_dist, m):
+ *                           an alignment of cost <= max_dist spans at most that many columns, so a hit is recomputed exactly, and a
+ *                           fresh start only raises values, so nothing else becomes one.  *n_tasks receives the number of tasks;
+ *                           PWA_E_CAPACITY when cap is smaller (call with cap = 0 to size the arrays, which may then be NULL).
+ *                           PWA_E_INVALID for chunk = 0, a pattern length of 0, or a null pat_len / max_dist / n_tasks.
+ * Limits, checked before any device work: null ctx or a null required pointer PWA_E_INVALID; n >= 2^31 PWA_E_CAPACITY; then in
+ * pattern order m = 0 PWA_E_INVALID and m > 512 PWA_E_CAPACITY; more than 32 distinct byte values over all patterns of the call
+ * PWA_E_CAPACITY (text bytes that no pattern contains are legal and match nothing).  n = 0 or n_pat = 0: a valid call without hits. */
+int pwa_approx_find(pwa_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *pat_bytes, const uint64_t *pat_off,
+                    uint32_t n_pat, const uint32_t *max_dist, uint32_t *counts_out,
+                    int32_t *best_dist_out /* or NULL */, uint32_t *best_end_out /* or NULL */);
+int pwa_approx_occurrences(pwa_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *pat_bytes, const uint64_t *pat_off,
+                           uint32_t n_pat, const uint32_t *max_dist, uint64_t *occ_off /* n_pat + 1 */, uint64_t *occ,
+                           uint64_t cap, uint64_t *needed);
+int pwa_approx_last_stats(const pwa_ctx *ctx, float *count_ms, float *fill_ms, uint64_t *tasks, uint64_t *columns);
+int pwa_approx_plan(uint64_t n, const uint32_t *pat_len, const uint32_t *max_dist, uint32_t n_pat, uint32_t chunk,
+                    uint32_t *task_pat, uint64_t *task_scan_lo, uint64_t *task_lo, uint64_t *task_hi, uint64_t cap,
+                    uint64_t *n_tasks);
 
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
