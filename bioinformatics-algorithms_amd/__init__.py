@@ -491,18 +491,8 @@ class Context:
 
     def scores_gotoh_oneshot(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, want_end=False):
         """pwa_scores_gotoh: the one-call form (pair lists of any size: cut into arena-sized runs by the library)."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei = (C.c_uint32 * max(n, 1))() if want_end else None
-        ej = (C.c_uint32 * max(n, 1))() if want_end else None
-        rc = self._L.pwa_scores_gotoh(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ei, ej)
-        self._check(rc, "pwa_scores_gotoh")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n])
-        return list(sc[:n])
+        return self._scores_call(self._L.pwa_scores_gotoh, "pwa_scores_gotoh", (self._h, MODE[mode], match, mismatch, gap_open, gap_extend),
+                                 seqs, pair_a, pair_b, want_end)
 
     def batch_gotoh(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, want_end=False):
         return Batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, want_end, gap_extend=gap_extend, gotoh=True)
@@ -601,44 +591,70 @@ class Context:
         return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
                      start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
 
-    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
-        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`);
-        ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result;
-        pend: ... with pend_score_out and pend_j_out behind rows_out, and a `pend` key"""
+    def _scores_call(self, fn, name, head, seqs, pair_a, pair_b, want_end, extra=0, pend=False, tail=()):
+        """a one-call score pass whose arguments are `head` (context .. scoring), the sequences, the pairs, score_out, end_i_out and
+        end_j_out, `extra` more uint32 outputs (an extension call's rows_out), with `pend` pend_score_out and pend_j_out, and `tail`
+        -> scores, or with want_end (scores, end_i, end_j, the extra lists ..., the pattern-end list)"""
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
         pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        u32 = [(C.c_uint32 * max(n, 1))() if want_end else None for _ in range(2 + extra)]
+        pe = ()
+        if pend:
+            pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if want_end else (None, None)
+        self._check(fn(*head, blob, off, len(seqs), pa, pb, n, sc, *u32, *pe, *tail), name)
+        if not want_end:
+            return list(sc[:n])
+        out = (list(sc[:n]),) + tuple(list(a[:n]) for a in u32)
+        return out + ([_pend(pe[0][k], pe[1][k]) for k in range(n)],) if pend else out
+
+    @staticmethod
+    def _align_begin(seqs, pair_a, pair_b, ext, pend):
+        """what _align_ops and _align_strings start with: the packed sequences, the pair arrays and the outputs both have
+        -> blob, off, seqs, n, pa, pb, sc, endc, startc (ext: rows_out in its place), pe (pend: pend_score_out, pend_j_out)"""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        endc = (C.c_uint64 * (2 * max(n, 1)))()
+        startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
+        pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if pend else ()
+        return blob, off, seqs, n, pa, pb, sc, endc, startc, pe
+
+    @staticmethod
+    def _align_results(n, own, sc, endc, startc, pe, ext):
+        """... and end with: own(k) = the keys of pair k that only the one call has, between score and end"""
+        if not ext:
+            return [dict(score=sc[k], **own(k), end=(endc[2 * k], endc[2 * k + 1]), start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+        out = [dict(score=sc[k], **own(k), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0), rows=startc[k]) for k in range(n)]
+        for k in range(n if pe else 0):
+            out[k]["pend"] = _pend(pe[0][k], pe[1][k])
+        return out
+
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
+        """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`);
+        ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result;
+        pend: ... with pend_score_out and pend_j_out behind rows_out, and a `pend` key"""
+        blob, off, seqs, n, pa, pb, sc, endc, startc, pe = self._align_begin(seqs, pair_a, pair_b, ext, pend)
         ooff = (C.c_uint64 * max(n, 1))()
         tot = 0
         for k in range(n):
             ooff[k] = tot
             tot += len(seqs[pair_a[k]]) + len(seqs[pair_b[k]])
         ops = C.create_string_buffer(tot + 1)
-        sc = (C.c_int32 * max(n, 1))()
         nops = (C.c_uint64 * max(n, 1))()
-        endc = (C.c_uint64 * (2 * max(n, 1)))()
-        startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
-        pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if pend else ()
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *pe, *tail)
         self._check(rc, name)
         raw = memoryview(ops)
-        if ext:
-            out = [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
-                        rows=startc[k]) for k in range(n)]
-            for k in range(n if pend else 0):
-                out[k]["pend"] = _pend(pe[0][k], pe[1][k])
-            return out
-        return [dict(score=sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]), end=(endc[2 * k], endc[2 * k + 1]),
-                     start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+        return self._align_results(n, lambda k: dict(ops=bytes(raw[ooff[k]:ooff[k] + nops[k]])), sc, endc, startc, pe, ext)
 
     def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
         """... and one that returns CIGAR and MD:Z strings built on the device"""
         import numpy as np
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        blob, off, seqs, n, pa, pb, sc, endc, startc, pe = self._align_begin(seqs, pair_a, pair_b, ext, pend)
         lens = np.array([len(x) for x in seqs] or [0], dtype=np.uint64)
         nm = lens[np.asarray(pair_a, dtype=np.int64)] + lens[np.asarray(pair_b, dtype=np.int64)] if n else np.zeros(0, np.uint64)
         cap_c, cap_m = int((2 * nm + 24).sum()), int((3 * nm + 24).sum())   # pwa_cigar_bound / pwa_mdz_bound
@@ -646,24 +662,19 @@ class Context:
         md = np.empty(max(cap_m, 1), dtype=np.uint8)
         cg_off = np.zeros(n + 1, dtype=np.uint64)
         md_off = np.zeros(n + 1, dtype=np.uint64)
-        sc = (C.c_int32 * max(n, 1))()
-        endc = (C.c_uint64 * (2 * max(n, 1)))()
-        startc = (C.c_uint32 * max(n, 1))() if ext else (C.c_uint64 * (2 * max(n, 1)))()
         u64p = C.POINTER(C.c_uint64)
-        pe = ((C.c_int32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()) if pend else ()
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
                 md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, *pe, None, *tail)
         self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
-        if ext:
-            out = [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0),
-                        rows=startc[k]) for k in range(n)]
-            for k in range(n if pend else 0):
-                out[k]["pend"] = _pend(pe[0][k], pe[1][k])
-            return out
-        return [dict(score=sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]], end=(endc[2 * k], endc[2 * k + 1]),
-                     start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
+        return self._align_results(n, lambda k: dict(cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]]), sc, endc, startc, pe, ext)
+
+    def _stats3(self, fn, name, third):
+        """a last-stats call of three values: device ms of the fills and of the walks, and a count under the key `third`"""
+        f, w, c = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        self._check(fn(self._h, C.byref(f), C.byref(w), C.byref(c)), name)
+        return {"fill_ms": f.value, "walk_ms": w.value, third: c.value}
 
     def align_gotoh_batch(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend):
         """pwa_align_gotoh_batch: affine-gap alignments (a gap of length L scores gap_open + L * gap_extend; include/pwalign.h) ->
@@ -701,26 +712,13 @@ class Context:
 
     def align_banded_stats(self):
         """The last align_banded_batch(_cigar): device ms of its fills and walks, band bytes written."""
-        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
-        self._check(self._L.pwa_align_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_banded_last_stats")
-        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
+        return self._stats3(self._L.pwa_align_banded_last_stats, "pwa_align_banded_last_stats", "band_bytes")
 
     def scores_banded(self, mode, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, want_end=False):
         """pwa_scores_banded: score (and, with want_end, end cell) of every pair of align_banded_batch's list, without the alignments:
         no traceback band, no walk -> scores, or (scores, end_i, end_j) as scores_gotoh_oneshot returns them."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        lo, hi = self._band_arrays(bands, n)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei = (C.c_uint32 * max(n, 1))() if want_end else None
-        ej = (C.c_uint32 * max(n, 1))() if want_end else None
-        rc = self._L.pwa_scores_banded(self._h, MODE[mode], match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ei, ej, lo, hi)
-        self._check(rc, "pwa_scores_banded")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n])
-        return list(sc[:n])
+        return self._scores_call(self._L.pwa_scores_banded, "pwa_scores_banded", (self._h, MODE[mode], match, mismatch, gap_open, gap_extend),
+                                 seqs, pair_a, pair_b, want_end, tail=self._band_arrays(bands, len(pair_a)))
 
     def scores_banded_stats(self):
         """The last scores_banded: device ms of its score passes, and the in-band cells of its list."""
@@ -746,25 +744,13 @@ class Context:
     def scores_extend_banded(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, bands, xdrop, want_end=False):
         """pwa_scores_extend_banded: score (and, with want_end, end cell and rows) of every pair of extend_banded_batch's list, without
         the alignments -> scores, or (scores, end_i, end_j, rows)."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        lo, hi = self._band_arrays(bands, n)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei, ej, rw = [(C.c_uint32 * max(n, 1))() if want_end else None for _ in range(3)]
-        rc = self._L.pwa_scores_extend_banded(self._h, match, mismatch, gap_open, gap_extend, xdrop, blob, off, len(seqs), pa, pb, n, sc, ei, ej, rw, lo, hi)
-        self._check(rc, "pwa_scores_extend_banded")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n]), list(rw[:n])
-        return list(sc[:n])
+        return self._scores_call(self._L.pwa_scores_extend_banded, "pwa_scores_extend_banded", (self._h, match, mismatch, gap_open, gap_extend, xdrop),
+                                 seqs, pair_a, pair_b, want_end, extra=1, tail=self._band_arrays(bands, len(pair_a)))
 
     def extend_banded_stats(self):
         """The last extend_banded_batch(_cigar) or scores_extend_banded, or their _subst forms: device ms of its fills and walks (walk_ms = 0 after the scores
         call), and the rows it considered (the sum of `rows`)."""
-        f, w, r = C.c_float(0), C.c_float(0), C.c_uint64(0)
-        self._check(self._L.pwa_extend_banded_last_stats(self._h, C.byref(f), C.byref(w), C.byref(r)), "pwa_extend_banded_last_stats")
-        return dict(fill_ms=f.value, walk_ms=w.value, rows_considered=r.value)
+        return self._stats3(self._L.pwa_extend_banded_last_stats, "pwa_extend_banded_last_stats", "rows_considered")
 
     # -- substitution-matrix scoring (table = subst_table(...)): the gotoh calls with s(i, j) = submat[code[p], code[t]]
     def _subst_head(self, mode, table, gap_open, gap_extend, blob):
@@ -792,18 +778,9 @@ class Context:
 
     def scores_subst_oneshot(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):
         """pwa_scores_subst: the one-call form (pair lists of any size: cut into arena-sized runs by the library)."""
-        blob, off, seqs = pack_sequences(seqs)
-        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, blob)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei = (C.c_uint32 * max(n, 1))() if want_end else None
-        ej = (C.c_uint32 * max(n, 1))() if want_end else None
-        self._check(self._L.pwa_scores_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej), "pwa_scores_subst")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n])
-        return list(sc[:n])
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._scores_call(self._L.pwa_scores_subst, "pwa_scores_subst", head, packed, pair_a, pair_b, want_end)
 
     # -- ... in a diagonal band per pair: patterns of any length (the banded calls with a table; they report into the banded stats)
     def align_banded_subst_batch(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands):
@@ -825,19 +802,10 @@ class Context:
     def scores_banded_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, bands, want_end=False):
         """pwa_scores_banded_subst: score (and, with want_end, end cell) of every pair of align_banded_subst_batch's list, without the
         alignments -> scores, or (scores, end_i, end_j) as scores_banded returns them."""
-        blob, off, seqs = pack_sequences(seqs)
-        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, blob)
-        n = len(pair_a)
-        lo, hi = self._band_arrays(bands, n)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei = (C.c_uint32 * max(n, 1))() if want_end else None
-        ej = (C.c_uint32 * max(n, 1))() if want_end else None
-        self._check(self._L.pwa_scores_banded_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej, lo, hi), "pwa_scores_banded_subst")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n])
-        return list(sc[:n])
+        packed = pack_sequences(seqs)
+        head, _keep = self._subst_head(mode, table, gap_open, gap_extend, packed[0])
+        return self._scores_call(self._L.pwa_scores_banded_subst, "pwa_scores_banded_subst", head, packed, pair_a, pair_b, want_end,
+                                 tail=self._band_arrays(bands, len(pair_a)))
 
     # -- ... and the X-drop extension calls with a table, which also say whether and how the extension reached the pattern's end
     def _ext_subst_head(self, table, gap_open, gap_extend, xdrop, blob):
@@ -864,35 +832,21 @@ class Context:
         """pwa_scores_extend_banded_subst: score (and, with want_end, end cell, rows and pattern-end result) of every pair of
         extend_banded_subst_batch's list, without the alignments -> scores, or (scores, end_i, end_j, rows, pend) with pend a list of
         (score, j) or None.  Stats: extend_banded_stats."""
-        blob, off, seqs = pack_sequences(seqs)
-        head, _keep = self._ext_subst_head(table, gap_open, gap_extend, xdrop, blob)
-        n = len(pair_a)
-        lo, hi = self._band_arrays(bands, n)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ei, ej, rw, pj = [(C.c_uint32 * max(n, 1))() if want_end else None for _ in range(4)]
-        ps = (C.c_int32 * max(n, 1))() if want_end else None
-        rc = self._L.pwa_scores_extend_banded_subst(*head, blob, off, len(seqs), pa, pb, n, sc, ei, ej, rw, ps, pj, lo, hi)
-        self._check(rc, "pwa_scores_extend_banded_subst")
-        if want_end:
-            return list(sc[:n]), list(ei[:n]), list(ej[:n]), list(rw[:n]), [_pend(ps[k], pj[k]) for k in range(n)]
-        return list(sc[:n])
+        packed = pack_sequences(seqs)
+        head, _keep = self._ext_subst_head(table, gap_open, gap_extend, xdrop, packed[0])
+        return self._scores_call(self._L.pwa_scores_extend_banded_subst, "pwa_scores_extend_banded_subst", head, packed, pair_a, pair_b, want_end,
+                                 extra=1, pend=True, tail=self._band_arrays(bands, len(pair_a)))
 
     def batch_subst(self, mode, seqs, pair_a, pair_b, table, gap_open, gap_extend, want_end=False):
         return Batch(self, mode, seqs, pair_a, pair_b, 0, 0, gap_open, want_end, gap_extend=gap_extend, subst=table)
 
     def align_subst_stats(self):
         """The last align_subst_batch(_cigar): device ms of its fills and walks, band bytes written."""
-        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
-        self._check(self._L.pwa_align_subst_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_subst_last_stats")
-        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
+        return self._stats3(self._L.pwa_align_subst_last_stats, "pwa_align_subst_last_stats", "band_bytes")
 
     def align_gotoh_stats(self):
         """The last align_gotoh_batch(_cigar): device ms of its fills and walks, band bytes written."""
-        f, w, b = C.c_float(0), C.c_float(0), C.c_uint64(0)
-        self._check(self._L.pwa_align_gotoh_last_stats(self._h, C.byref(f), C.byref(w), C.byref(b)), "pwa_align_gotoh_last_stats")
-        return dict(fill_ms=f.value, walk_ms=w.value, band_bytes=b.value)
+        return self._stats3(self._L.pwa_align_gotoh_last_stats, "pwa_align_gotoh_last_stats", "band_bytes")
 
     def align_batch_arrays(self, mode, packed, pair_a, pair_b, match, mismatch, gap, out=None):
         """pwa_align_batch on caller-held buffers, the way a compiled host calls it: `packed` = pack_sequences(seqs) done once,

@@ -38,13 +38,7 @@
 // One wave per pair, stripes of 64 x 4 or 64 x 8 rows.  Own translation unit.
 #include "banded_subst.hip.h"
 
-#include <algorithm>
-
 namespace pwa {
-
-typedef void (*banded_ext_subst_t)(const PairParams, const int, const int, const uint32_t*, int, int);
-typedef void (*banded_walk_t)(const PairParams);
-banded_walk_t banded_walk_kernel_for(int rl, int mode);   // banded_kernels.hip
 
 // The fill: G.gap = gap_open, G.gap_extend = gap_extend, G.match / G.mismatch = +- max |submat| (banded_body's sentinel reads them).
 // Dynamic LDS: kBandedWaves * row_cap * 8 bytes, as banded_fill_kernel.
@@ -69,33 +63,13 @@ __global__ __launch_bounds__(64 * kBandedWaves) void banded_ext_subst_scores_ker
     banded_scores_body<RL, kBandedExt, true>(G, row_cap, SubstTableScore{L, n_sym - 1, stride * 4}, (lds_bint2*)banded_ext_subst_scores_lds, xdrop);
 }
 
-static banded_ext_subst_t banded_ext_subst_kernel_for(int rl, bool band) {
-    if (!band) return rl == 4 ? banded_ext_subst_scores_kernel<4> : rl == 8 ? banded_ext_subst_scores_kernel<8> : nullptr;
-    return rl == 4 ? banded_ext_subst_fill_kernel<4> : rl == 8 ? banded_ext_subst_fill_kernel<8> : nullptr;
-}
-
-// Fill (walk = true: then NW's walk from the end cells the fill left, one wave per pair; `after_fill` is recorded between them) or
-// score pass on `st`.  row_cap: the launch's widest band.  The grid is banded_subst_launch's: what the runtime's occupancy figure says
-// is resident at once, and no more (pairs are dealt statically, longest first).  Only the dynamic LDS -- the hand-off rows -- is named
-// to the runtime; it counts the kernel's static table (SubstLds) itself, both for the attribute's limit and for the occupancy figure.
-hipError_t banded_ext_subst_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk, int xdrop,
-                                   const uint32_t* blob, int n_sym, int stride) {
-    const banded_ext_subst_t fill = banded_ext_subst_kernel_for(rl, walk);
-    const banded_walk_t wk = walk ? banded_walk_kernel_for(rl, 0) : nullptr;
-    if (!fill || (walk && !wk) || row_cap < 1 || row_cap > kBandedMaxWidth || !G.n_pairs || num_cu < 1) return hipErrorInvalidValue;
-    if (!blob || n_sym < 1 || n_sym > kSubstMaxSym || stride < n_sym || stride > kSubstMaxSym) return hipErrorInvalidValue;
-    const size_t lds = (size_t)kBandedWaves * (size_t)row_cap * sizeof(bint2);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fill), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    int per_cu = 0;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fill), 64 * kBandedWaves, lds)) != hipSuccess) return e;
-    const uint32_t n_wg = (G.n_pairs + kBandedWaves - 1) / kBandedWaves;
-    const uint32_t grid = std::min<uint32_t>(n_wg, (uint32_t)num_cu * (uint32_t)std::max(per_cu, 1));
-    hipLaunchKernelGGL(fill, dim3(grid), dim3(64 * kBandedWaves), lds, st, G, row_cap, xdrop, blob, n_sym, stride);
-    if ((e = hipGetLastError()) != hipSuccess || !walk) return e;
-    if (after_fill && (e = hipEventRecord(after_fill, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(wk, dim3(G.n_pairs), dim3(64), 0, st, G);
-    return hipGetLastError();
+// The host stub of the fill (band = true) or of the score pass; rl: 8, else 4 (resolve_banded_form is the only caller).  Both take
+// (G, row_cap, xdrop, blob, n_sym, stride).
+const void* banded_ext_subst_kernel_for(int rl, bool band) {
+    void (*const fn)(const PairParams, const int, const int, const uint32_t*, int, int) =
+        band ? (rl == 8 ? banded_ext_subst_fill_kernel<8> : banded_ext_subst_fill_kernel<4>)
+             : (rl == 8 ? banded_ext_subst_scores_kernel<8> : banded_ext_subst_scores_kernel<4>);
+    return reinterpret_cast<const void*>(fn);
 }
 
 }  // namespace pwa

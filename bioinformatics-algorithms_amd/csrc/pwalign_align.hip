@@ -23,14 +23,6 @@ using namespace pwa;
 
 namespace pwa {
 hipError_t cigar_launch(const CigarParams& p, bool write, hipStream_t s);   // cigar_kernels.hip
-hipError_t banded_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill);   // banded_kernels.hip
-hipError_t banded_scores_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st);                    // banded_scores_kernels.hip
-hipError_t banded_subst_launch(const PairParams& G, int rl, int mode, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk,
-                               const uint32_t* blob, int n_sym, int stride);                                                         // banded_subst_kernels.hip
-hipError_t banded_ext_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, int xdrop);  // banded_ext_kernels.hip
-hipError_t banded_ext_scores_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, int xdrop);
-hipError_t banded_ext_subst_launch(const PairParams& G, int rl, int row_cap, int num_cu, hipStream_t st, hipEvent_t after_fill, bool walk, int xdrop,
-                                   const uint32_t* blob, int n_sym, int stride);                                                     // banded_ext_subst_kernels.hip
 }
 
 // ------------------------------------------------------------------------- full alignments
@@ -98,19 +90,34 @@ int banded_rl_for(int64_t width) { return width >= 1024 ? 8 : 4; }
 // list (pwa_scores_banded), whose launches write no band and run no walk
 enum AlignOutMode { OUT_OPS, OUT_STRINGS, OUT_OVERLAP, OUT_SCORES };
 struct AlignOut {
-    AlignOutMode mode;
-    int32_t* score;
-    uint64_t *end_cells, *start_cells;   // 2 * n_pairs each, or null
-    uint8_t* ops;                        // OUT_OPS
-    const uint64_t* ops_off;
-    uint64_t* n_ops;
-    int32_t* overlap;                    // OUT_OVERLAP
-    StrOut str;                          // OUT_STRINGS
-    uint32_t *end_i = nullptr, *end_j = nullptr;   // OUT_SCORES: n_pairs each, or null
-    uint32_t* rows = nullptr;                      // EXT: rows considered per pair (n_pairs), or null
-    int32_t* pend_score = nullptr;                 // EXT with a table: the pattern-end result per pair (n_pairs each), or null
+    AlignOutMode mode = OUT_OPS;
+    int32_t* score = nullptr;
+    uint64_t *end_cells = nullptr, *start_cells = nullptr;   // 2 * n_pairs each, or null
+    uint8_t* ops = nullptr;                                  // OUT_OPS
+    const uint64_t* ops_off = nullptr;
+    uint64_t* n_ops = nullptr;
+    int32_t* overlap = nullptr;                              // OUT_OVERLAP
+    StrOut str = {};                                         // OUT_STRINGS
+    uint32_t *end_i = nullptr, *end_j = nullptr;             // OUT_SCORES: n_pairs each, or null
+    uint32_t* rows = nullptr;                                // EXT: rows considered per pair (n_pairs), or null
+    int32_t* pend_score = nullptr;                           // EXT with a table: the pattern-end result per pair (n_pairs each), or null
     uint32_t* pend_j = nullptr;
+    // the EXT calls' additions to any of the three below
+    AlignOut& ext(uint32_t* r, int32_t* ps = nullptr, uint32_t* pj = nullptr) { return rows = r, pend_score = ps, pend_j = pj, *this; }
 };
+AlignOut out_ops(int32_t* score, uint64_t* end_cells, uint64_t* start_cells, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops) {
+    return AlignOut{OUT_OPS, score, end_cells, start_cells, ops, ops_off, n_ops};
+}
+AlignOut out_strings(int32_t* score, uint64_t* end_cells, uint64_t* start_cells, const StrOut& str) {
+    AlignOut o{OUT_STRINGS, score, end_cells, start_cells};
+    o.str = str;
+    return o;
+}
+AlignOut out_scores(int32_t* score, uint32_t* end_i, uint32_t* end_j) {
+    AlignOut o{OUT_SCORES, score};
+    o.end_i = end_i, o.end_j = end_j;
+    return o;
+}
 // The caller's scoring, sequences, pair list and outputs, as the stages of align_batch_impl see them
 struct AlignRequest {
     int mode, match, mismatch, gap;
@@ -135,6 +142,11 @@ struct AlignRequest {
     bool pend() const { return ext && sb; }
     size_t res_bytes() const { return sizeof(PairResult) + (pend() ? 2 * sizeof(int32_t) : 0); }
 };
+// ... as an entry point has them: scoring (gap: the linear gap, or gap_open), sequences, pair list, outputs; no spec yet
+AlignRequest request(int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a,
+                     const uint32_t* pair_b, uint64_t n_pairs, const AlignOut& out) {
+    return AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out};
+}
 
 // PWA_DEBUG: host-side time between marks
 struct AlignClock {
@@ -546,11 +558,11 @@ uint64_t banded_cells(int64_t n, int64_t m, int64_t lo, int64_t hi) {
     return cells;
 }
 
-// One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; banded_kernels.hip
-// sizes the grid and launches fill + walk; the device times into `stats`.  A scores-only request: the same descriptors without band
-// and op regions, banded_scores_kernels.hip's pass alone, and the pairs' in-band cells into `stats`.  With a table (rq.sb) the same
-// descriptors go to banded_subst_kernels.hip's fill or pass; the walk is the same.  EXT with a table: PairDesc::rows (unused by the banded
-// class otherwise) points at the pair's pattern-end record, and banded_ext_subst_kernels.hip's fill or pass runs
+// One launch of the banded class: the descriptors carry the clamped band, the band pitch and the stripe count; the request and the
+// class make one BandedForm, whose kernels pwa::banded_launch (pwalign_ctx.hip) resolves, sizes the grid for and launches -- fill +
+// walk, or for a scores-only request the score pass alone over the same descriptors without band and op regions --; the device times
+// (and a scores-only request's in-band cells) into `stats`.  EXT with a table: PairDesc::rows (unused by the banded class otherwise)
+// points at the pair's pattern-end record
 int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const AlignWorkspaces& ws, const Range& rg, const Launch& L,
                       const RangeHost& rh, AlignStats& stats, AlignClock& clock) {
     const size_t np = L.q.size();
@@ -589,27 +601,9 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
     clock.mark("descriptor build + upload");
     if (clock.on) std::fprintf(stderr, "[pwa] banded %s RL=%d pairs=%zu hand-off row=%lld entries\n", scores ? "scores" : "fill", L.cls.rl, np, (long long)row_cap);
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (rq.ext && rq.sb) {
-        const SubstRef& t = rq.sb->tab;
-        HIPC(ctx, pwa::banded_ext_subst_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], !scores, rq.ext->xdrop, t.tab, t.n_sym, t.stride));
-        if (scores) HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    } else if (rq.ext) {   // the same descriptors; the fill leaves rows_out in PairResult::overlap, the walk is NW's
-        if (scores) {
-            HIPC(ctx, pwa::banded_ext_scores_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, rq.ext->xdrop));
-            HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-        } else {
-            HIPC(ctx, pwa::banded_ext_launch(pl.G, L.cls.rl, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], rq.ext->xdrop));
-        }
-    } else if (rq.sb) {
-        const SubstRef& t = rq.sb->tab;
-        HIPC(ctx, pwa::banded_subst_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1], !scores, t.tab, t.n_sym, t.stride));
-        if (scores) HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    } else if (scores) {
-        HIPC(ctx, pwa::banded_scores_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream));
-        HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    } else {
-        HIPC(ctx, pwa::banded_launch(pl.G, L.cls.rl, rq.mode, (int)row_cap, ctx->num_cu, ctx->stream, ctx->ev[1]));
-    }
+    // (EXT: the same descriptors; the fill leaves rows_out in PairResult::overlap, the walk is NW's)
+    const BandedForm form{L.cls.rl, rq.mode, rq.ext != nullptr, rq.sb != nullptr, !scores};
+    HIPC(ctx, pwa::banded_launch(form, pl.G, (int)row_cap, rq.ext ? rq.ext->xdrop : 0, rq.sb ? rq.sb->tab : SubstRef{}, ctx->num_cu, ctx->stream, ctx->ev[1]));
     HIPC(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     HIPC(ctx, hipStreamSynchronize(ctx->stream));
     clock.mark(scores ? "scores pass (device)" : "fill + walk (device)");
@@ -932,6 +926,63 @@ int pwa::selftest_align_plan(uint64_t x, int check) {
     return 0;
 }
 
+// What an affine-gap entry point adds to its request (whose gap is gap_open): the call's table, band arrays and xdrop where it has
+// them, and the context's stats slot it reports into
+struct AffineSpec {
+    int gap_extend;
+    AlignStats* stats;
+    bool subst = false, banded = false, ext = false;
+    const uint8_t* code = nullptr;   // subst
+    int n_sym = 0;
+    const int32_t* submat = nullptr;
+    const int32_t *band_lo = nullptr, *band_hi = nullptr;   // banded: one (lo, hi) per pair
+    int xdrop = 0;                                          // ext
+    AffineSpec& table(const uint8_t* c, int n, const int32_t* m) { return subst = true, code = c, n_sym = n, submat = m, *this; }
+    AffineSpec& band(const int32_t* lo, const int32_t* hi) { return banded = true, band_lo = lo, band_hi = hi, *this; }
+    AffineSpec& extend(int x) { return ext = true, xdrop = x, *this; }
+};
+
+// The affine-gap entry points' own checks, in the order every one of them has had them -- gap signs, mode, the table, the band arrays
+// (validate_align checks every pair's band) --, then the spec structs hang on the request.  A table is checked, copied and uploaded
+// for the call, once (every range of a PWA_RANGE_BYTES-cut list launches with it; the device copy goes back to the context's buffer
+// list when the call returns), after the request has been validated: nothing is allocated for a request that is refused.
+static int affine_batch(pwa_ctx* ctx, AlignRequest rq, const AffineSpec& sp) try {
+    if (rq.gap > 0 || sp.gap_extend > 0)
+        return fail(ctx, PWA_E_INVALID, sp.subst ? "gap penalties must be <= 0 (gap_open + L * gap_extend)" : "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
+    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
+    SubstTable tab;
+    int rc = sp.subst ? subst_prepare(ctx, sp.code, sp.n_sym, sp.submat, tab) : PWA_OK;
+    if (rc != PWA_OK) return rc;
+    if (sp.banded && rq.n_pairs && (!sp.band_lo || !sp.band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
+    const GotohSpec gs{rq.gap, sp.gap_extend};
+    SubstSpec ss{{nullptr, tab.n_sym, tab.stride}, tab.max_abs};
+    const BandSpec bs{sp.band_lo, sp.band_hi};
+    const ExtSpec es{sp.xdrop};
+    rq.gt = &gs;
+    if (sp.subst) rq.sb = &ss;
+    if (sp.banded) rq.bd = &bs;
+    if (sp.ext) rq.ext = &es;
+    if (sp.subst) {
+        if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (align_batch_impl checks again)
+        HIPC(ctx, hipSetDevice(ctx->device));
+        if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
+        ss.tab.tab = tab.dev.as<uint32_t>();
+    }
+    return align_batch_impl(ctx, rq, *sp.stats);
+} catch (const std::bad_alloc&) {
+    return fail(ctx, PWA_E_NOMEM, "host allocation failed");
+}
+
+// a stats slot of the context into a call's (optional) outputs; `count`: its band bytes, or the cells / rows of the banded score and EXT calls
+static int put_stats(const pwa_ctx* ctx, AlignStats pwa_ctx::*slot, float* fill_ms, float* walk_ms, uint64_t* count, uint64_t AlignStats::*what = &AlignStats::band_bytes) {
+    if (!ctx) return PWA_E_INVALID;
+    const AlignStats& st = ctx->*slot;
+    if (fill_ms) *fill_ms = st.fill_ms;
+    if (walk_ms) *walk_ms = st.tb_ms;
+    if (count) *count = st.*what;
+    return PWA_OK;
+}
+
 extern "C" {
 
 int pwa_align_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes,
@@ -940,8 +991,8 @@ int pwa_align_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, co
                     uint64_t* end_cells, uint64_t* start_cells) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    return align_batch_impl(ctx, request(mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                         out_ops(score_out, end_cells, start_cells, ops, ops_off, n_ops)), ctx->align_stats);
 }
 
 int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
@@ -949,55 +1000,19 @@ int pwa_align_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int g
                           uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
                           uint64_t* start_cells, uint64_t needed[2]) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    return align_batch_impl(ctx, request(mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                         out_strings(score_out, end_cells, start_cells, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed})), ctx->align_stats);
 }
 
-// the gotoh entry points' own checks; the request comes with gap = gap_open and no GotohSpec yet
-static int gotoh_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend) {
-    if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
-    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
-    const GotohSpec gs{rq.gap, gap_extend};
-    rq.gt = &gs;
-    return align_batch_impl(ctx, rq, ctx->gotoh_stats);
-}
-
-// ... and the substitution-matrix ones': the table is checked, copied and uploaded for the call (the device copy goes back to the
-// context's buffer list when the call returns)
-// With band arrays (band_lo / band_hi, `stats` the banded slot of the calling form) the request also gets its BandSpec: the banded
-// substitution-matrix calls.  The table is uploaded once per call; every range of a PWA_RANGE_BYTES-cut list launches with it.
-// With an ExtSpec beside the band arrays: the EXT calls under a table (NW's matrix).
-static int subst_batch(pwa_ctx* ctx, AlignRequest rq, const uint8_t* code, int n_sym, const int32_t* submat, int gap_extend, AlignStats& stats,
-                       bool banded = false, const int32_t* band_lo = nullptr, const int32_t* band_hi = nullptr, const ExtSpec* ext = nullptr) try {
-    if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gap penalties must be <= 0 (gap_open + L * gap_extend)");
-    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
-    SubstTable tab;
-    int rc = subst_prepare(ctx, code, n_sym, submat, tab);
-    if (rc != PWA_OK) return rc;
-    if (banded && rq.n_pairs && (!band_lo || !band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
-    const GotohSpec gs{rq.gap, gap_extend};
-    SubstSpec ss{{nullptr, tab.n_sym, tab.stride}, tab.max_abs};
-    const BandSpec bs{band_lo, band_hi};
-    rq.gt = &gs;
-    rq.sb = &ss;
-    if (banded) rq.bd = &bs;
-    rq.ext = ext;
-    if ((rc = validate_align(ctx, rq)) != PWA_OK) return rc;   // (before anything is allocated; align_batch_impl checks again)
-    HIPC(ctx, hipSetDevice(ctx->device));
-    if ((rc = subst_upload(ctx, tab)) != PWA_OK) return rc;
-    ss.tab.tab = tab.dev.as<uint32_t>();
-    return align_batch_impl(ctx, rq, stats);
-} catch (const std::bad_alloc&) {
-    return fail(ctx, PWA_E_NOMEM, "host allocation failed");
-}
-
+// affine gaps on the gotoh mini-stripe kernels
 int pwa_align_gotoh_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
                           const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
                           int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
+    return affine_batch(ctx, request(mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_ops(score_out, end_cells, start_cells, ops, ops_off, n_ops)),
+                        AffineSpec{gap_extend, &ctx->gotoh_stats});
 }
 
 int pwa_align_gotoh_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
@@ -1005,42 +1020,24 @@ int pwa_align_gotoh_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch,
                                 int32_t* score_out, char* cigar, uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap,
                                 uint64_t* mdz_off, uint64_t* end_cells, uint64_t* start_cells, uint64_t needed[2]) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return gotoh_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend);
-}
-
-static int put_stats(const AlignStats& st, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
-    if (fill_ms) *fill_ms = st.fill_ms;
-    if (walk_ms) *walk_ms = st.tb_ms;
-    if (band_bytes) *band_bytes = st.band_bytes;
-    return PWA_OK;
+    return affine_batch(ctx, request(mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, start_cells, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed})),
+                        AffineSpec{gap_extend, &ctx->gotoh_stats});
 }
 
 int pwa_align_gotoh_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
-    return ctx ? put_stats(ctx->gotoh_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+    return put_stats(ctx, &pwa_ctx::gotoh_stats, fill_ms, walk_ms, band_bytes);
 }
 
-// the banded entry points' own checks (gotoh_batch's, and the band arrays); validate_align checks every pair's band
-static int banded_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, const int32_t* band_lo, const int32_t* band_hi, AlignStats& stats) {
-    if (rq.gap > 0 || gap_extend > 0) return fail(ctx, PWA_E_INVALID, "gotoh gap penalties must be <= 0 (gap_open + L * gap_extend)");
-    if (rq.mode != PWA_MODE_NW && rq.mode != PWA_MODE_SW && rq.mode != PWA_MODE_SG) return fail(ctx, PWA_E_INVALID, "unknown mode");
-    if (rq.n_pairs && (!band_lo || !band_hi)) return fail(ctx, PWA_E_INVALID, "null input");
-    const GotohSpec gs{rq.gap, gap_extend};
-    const BandSpec bs{band_lo, band_hi};
-    rq.gt = &gs;
-    rq.bd = &bs;
-    return align_batch_impl(ctx, rq, stats);
-}
-
+// ... inside a diagonal band per pair
 int pwa_align_banded_batch(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
                            const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
                            int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint64_t* start_cells,
                            const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
-                        band_lo, band_hi, ctx->banded_stats);
+    return affine_batch(ctx, request(mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_ops(score_out, end_cells, start_cells, ops, ops_off, n_ops)),
+                        AffineSpec{gap_extend, &ctx->banded_stats}.band(band_lo, band_hi));
 }
 
 int pwa_align_banded_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
@@ -1049,13 +1046,13 @@ int pwa_align_banded_batch_cigar(pwa_ctx* ctx, int mode, int match, int mismatch
                                  uint64_t* mdz_off, uint64_t* end_cells, uint64_t* start_cells, uint64_t needed[2], const int32_t* band_lo,
                                  const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
-                        band_lo, band_hi, ctx->banded_stats);
+    return affine_batch(ctx, request(mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, start_cells, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed})),
+                        AffineSpec{gap_extend, &ctx->banded_stats}.band(band_lo, band_hi));
 }
 
 int pwa_align_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
-    return ctx ? put_stats(ctx->banded_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+    return put_stats(ctx, &pwa_ctx::banded_stats, fill_ms, walk_ms, band_bytes);
 }
 
 // the scores-only form: the same request with nothing to hand back but scores and end cells (OUT_SCORES: no band, no walk)
@@ -1063,35 +1060,24 @@ int pwa_scores_banded(pwa_ctx* ctx, int mode, int match, int mismatch, int gap_o
                       uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out,
                       uint32_t* end_j_out, const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
-    return banded_batch(ctx, AlignRequest{mode, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, gap_extend,
-                        band_lo, band_hi, ctx->banded_scores_stats);
+    return affine_batch(ctx, request(mode, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_scores(score_out, end_i_out, end_j_out)),
+                        AffineSpec{gap_extend, &ctx->banded_scores_stats}.band(band_lo, band_hi));
 }
 
 int pwa_scores_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, uint64_t* in_band_cells) {
-    if (!ctx) return PWA_E_INVALID;
-    if (fill_ms) *fill_ms = ctx->banded_scores_stats.fill_ms;
-    if (in_band_cells) *in_band_cells = ctx->banded_scores_stats.cells;
-    return PWA_OK;
+    return put_stats(ctx, &pwa_ctx::banded_scores_stats, fill_ms, nullptr, in_band_cells, &AlignStats::cells);
 }
 
-// the EXT entry points: banded_batch with NW's matrix and the call's ExtSpec; they report into their own slot
-static int extend_batch(pwa_ctx* ctx, AlignRequest rq, int gap_extend, int xdrop, const int32_t* band_lo, const int32_t* band_hi) {
-    const ExtSpec es{xdrop};
-    rq.ext = &es;
-    return banded_batch(ctx, rq, gap_extend, band_lo, band_hi, ctx->ext_stats);
-}
-
+// the EXT entry points: the banded calls over NW's matrix with the call's xdrop; they report into their own slot
 int pwa_extend_banded_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
                             const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs,
                             int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells, uint32_t* rows_out,
                             const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    AlignOut out{OUT_OPS, score_out, end_cells, nullptr, ops, ops_off, n_ops, nullptr, {}};
-    out.rows = rows_out;
-    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
-                        gap_extend, xdrop, band_lo, band_hi);
+    return affine_batch(ctx, request(PWA_MODE_NW, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_ops(score_out, end_cells, nullptr, ops, ops_off, n_ops).ext(rows_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.band(band_lo, band_hi).extend(xdrop));
 }
 
 int pwa_extend_banded_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
@@ -1100,10 +1086,9 @@ int pwa_extend_banded_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap
                                   uint64_t* mdz_off, uint64_t* end_cells, uint32_t* rows_out, uint64_t needed[2], const int32_t* band_lo,
                                   const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    AlignOut out{OUT_STRINGS, score_out, end_cells, nullptr, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    out.rows = rows_out;
-    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
-                        gap_extend, xdrop, band_lo, band_hi);
+    return affine_batch(ctx, request(PWA_MODE_NW, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}).ext(rows_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.band(band_lo, band_hi).extend(xdrop));
 }
 
 int pwa_scores_extend_banded(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, int xdrop, const uint8_t* seq_bytes,
@@ -1111,24 +1096,20 @@ int pwa_scores_extend_banded(pwa_ctx* ctx, int match, int mismatch, int gap_open
                              int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, uint32_t* rows_out, const int32_t* band_lo,
                              const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
-    out.rows = rows_out;
-    return extend_batch(ctx, AlignRequest{PWA_MODE_NW, match, mismatch, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out},
-                        gap_extend, xdrop, band_lo, band_hi);
+    return affine_batch(ctx, request(PWA_MODE_NW, match, mismatch, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_scores(score_out, end_i_out, end_j_out).ext(rows_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.band(band_lo, band_hi).extend(xdrop));
 }
 
-// their substitution-matrix forms: subst_batch with the band arrays and the ExtSpec, NW's matrix; they report into the EXT slot
+// their substitution-matrix forms, which also hand back the pattern-end result
 int pwa_extend_banded_subst_batch(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
                                   const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                                   uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
                                   uint32_t* rows_out, int32_t* pend_score_out, uint32_t* pend_j_out, const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    AlignOut out{OUT_OPS, score_out, end_cells, nullptr, ops, ops_off, n_ops, nullptr, {}};
-    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
-    const ExtSpec es{xdrop};
-    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
-                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
+    return affine_batch(ctx, request(PWA_MODE_NW, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_ops(score_out, end_cells, nullptr, ops, ops_off, n_ops).ext(rows_out, pend_score_out, pend_j_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.table(code, n_sym, submat).band(band_lo, band_hi).extend(xdrop));
 }
 
 int pwa_extend_banded_subst_batch_cigar(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
@@ -1138,11 +1119,9 @@ int pwa_extend_banded_subst_batch_cigar(pwa_ctx* ctx, const uint8_t* code, int n
                                         int32_t* pend_score_out, uint32_t* pend_j_out, uint64_t needed[2], const int32_t* band_lo,
                                         const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    AlignOut out{OUT_STRINGS, score_out, end_cells, nullptr, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
-    const ExtSpec es{xdrop};
-    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
-                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
+    return affine_batch(ctx, request(PWA_MODE_NW, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}).ext(rows_out, pend_score_out, pend_j_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.table(code, n_sym, submat).band(band_lo, band_hi).extend(xdrop));
 }
 
 int pwa_scores_extend_banded_subst(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend, int xdrop,
@@ -1150,30 +1129,24 @@ int pwa_scores_extend_banded_subst(pwa_ctx* ctx, const uint8_t* code, int n_sym,
                                    uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, uint32_t* rows_out,
                                    int32_t* pend_score_out, uint32_t* pend_j_out, const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
-    out.rows = rows_out, out.pend_score = pend_score_out, out.pend_j = pend_j_out;
-    const ExtSpec es{xdrop};
-    return subst_batch(ctx, AlignRequest{PWA_MODE_NW, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym,
-                       submat, gap_extend, ctx->ext_stats, true, band_lo, band_hi, &es);
+    return affine_batch(ctx, request(PWA_MODE_NW, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_scores(score_out, end_i_out, end_j_out).ext(rows_out, pend_score_out, pend_j_out)),
+                        AffineSpec{gap_extend, &ctx->ext_stats}.table(code, n_sym, submat).band(band_lo, band_hi).extend(xdrop));
 }
 
 int pwa_extend_banded_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* rows_considered) {
-    if (!ctx) return PWA_E_INVALID;
-    if (fill_ms) *fill_ms = ctx->ext_stats.fill_ms;
-    if (walk_ms) *walk_ms = ctx->ext_stats.tb_ms;
-    if (rows_considered) *rows_considered = ctx->ext_stats.cells;
-    return PWA_OK;
+    return put_stats(ctx, &pwa_ctx::ext_stats, fill_ms, walk_ms, rows_considered, &AlignStats::cells);
 }
 
+// the gotoh classes with the diagonal score from the caller's table
 int pwa_align_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
                           const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                           uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
                           uint64_t* start_cells) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend, ctx->subst_stats);
+    return affine_batch(ctx, request(mode, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_ops(score_out, end_cells, start_cells, ops, ops_off, n_ops)),
+                        AffineSpec{gap_extend, &ctx->subst_stats}.table(code, n_sym, submat));
 }
 
 int pwa_align_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
@@ -1182,21 +1155,20 @@ int pwa_align_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int
                                 uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
                                 uint64_t* start_cells, uint64_t needed[2]) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend, ctx->subst_stats);
+    return affine_batch(ctx, request(mode, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, start_cells, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed})),
+                        AffineSpec{gap_extend, &ctx->subst_stats}.table(code, n_sym, submat));
 }
 
-// the banded forms: subst_batch with the band arrays; they report where the banded calls report
+// the banded forms; they report where the banded calls report
 int pwa_align_banded_subst_batch(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
                                  const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b,
                                  uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off, uint64_t* n_ops, uint64_t* end_cells,
                                  uint64_t* start_cells, const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
     if (!ops) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OPS, score_out, end_cells, start_cells, ops, ops_off, n_ops, nullptr, {}};
-    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend, ctx->banded_stats, true, band_lo, band_hi);
+    return affine_batch(ctx, request(mode, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_ops(score_out, end_cells, start_cells, ops, ops_off, n_ops)),
+                        AffineSpec{gap_extend, &ctx->banded_stats}.table(code, n_sym, submat).band(band_lo, band_hi));
 }
 
 int pwa_align_banded_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
@@ -1205,9 +1177,9 @@ int pwa_align_banded_subst_batch_cigar(pwa_ctx* ctx, int mode, const uint8_t* co
                                        uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t* end_cells,
                                        uint64_t* start_cells, uint64_t needed[2], const int32_t* band_lo, const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_STRINGS, score_out, end_cells, start_cells, nullptr, nullptr, nullptr, nullptr, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed}};
-    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend, ctx->banded_stats, true, band_lo, band_hi);
+    return affine_batch(ctx, request(mode, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                                     out_strings(score_out, end_cells, start_cells, {cigar, mdz, cigar_cap, mdz_cap, cigar_off, mdz_off, needed})),
+                        AffineSpec{gap_extend, &ctx->banded_stats}.table(code, n_sym, submat).band(band_lo, band_hi));
 }
 
 int pwa_scores_banded_subst(pwa_ctx* ctx, int mode, const uint8_t* code, int n_sym, const int32_t* submat, int gap_open, int gap_extend,
@@ -1215,13 +1187,12 @@ int pwa_scores_banded_subst(pwa_ctx* ctx, int mode, const uint8_t* code, int n_s
                             uint64_t n_pairs, int32_t* score_out, uint32_t* end_i_out, uint32_t* end_j_out, const int32_t* band_lo,
                             const int32_t* band_hi) {
     if (!ctx) return PWA_E_INVALID;
-    const AlignOut out{OUT_SCORES, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, end_i_out, end_j_out};
-    return subst_batch(ctx, AlignRequest{mode, 0, 0, gap_open, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, code, n_sym, submat,
-                       gap_extend, ctx->banded_scores_stats, true, band_lo, band_hi);
+    return affine_batch(ctx, request(mode, 0, 0, gap_open, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out_scores(score_out, end_i_out, end_j_out)),
+                        AffineSpec{gap_extend, &ctx->banded_scores_stats}.table(code, n_sym, submat).band(band_lo, band_hi));
 }
 
 int pwa_align_subst_last_stats(const pwa_ctx* ctx, float* fill_ms, float* walk_ms, uint64_t* band_bytes) {
-    return ctx ? put_stats(ctx->subst_stats, fill_ms, walk_ms, band_bytes) : PWA_E_INVALID;
+    return put_stats(ctx, &pwa_ctx::subst_stats, fill_ms, walk_ms, band_bytes);
 }
 
 int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* seq_bytes, const uint64_t* seq_off,
@@ -1229,8 +1200,9 @@ int pwa_overlaps(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const
                  int32_t* overlap_out) {
     if (!ctx) return PWA_E_INVALID;
     if (!overlap_out) return fail(ctx, PWA_E_INVALID, "null input");
-    const AlignOut out{OUT_OVERLAP, score_out, nullptr, nullptr, nullptr, nullptr, nullptr, overlap_out, {}};
-    return align_batch_impl(ctx, AlignRequest{mode, match, mismatch, gap, nullptr, nullptr, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out}, ctx->align_stats);
+    AlignOut out;
+    out.mode = OUT_OVERLAP, out.score = score_out, out.overlap = overlap_out;
+    return align_batch_impl(ctx, request(mode, match, mismatch, gap, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, out), ctx->align_stats);
 }
 
 int pwa_align(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, const uint8_t* pattern, uint64_t n,
@@ -1365,7 +1337,7 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
 }
 
 int pwa_align_last_stats(const pwa_ctx* ctx, float* fill_ms, float* traceback_ms, uint64_t* band_bytes) {
-    return ctx ? put_stats(ctx->align_stats, fill_ms, traceback_ms, band_bytes) : PWA_E_INVALID;
+    return put_stats(ctx, &pwa_ctx::align_stats, fill_ms, traceback_ms, band_bytes);
 }
 
 }  // extern "C"

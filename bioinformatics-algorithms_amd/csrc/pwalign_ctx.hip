@@ -9,6 +9,7 @@
 #include <new>
 
 #include "approx_ctx.h"
+#include "banded_fill.hip.h"
 #include "sufarr_ctx.h"
 
 using namespace pwa;
@@ -21,6 +22,13 @@ void (*gotoh_scores_kernel_for(int rl, int mode, int ln))(const PairParams);   /
 // subst_kernels.hip: the same classes and modes under a substitution table (device blob, n_sym, row stride); the walk is gotoh's
 subst_kernel_t subst_fill_kernel_for(int rl, int mode, int ln);
 subst_kernel_t subst_scores_kernel_for(int rl, int mode, int ln);
+// banded_kernels.hip, banded_scores_kernels.hip, banded_subst_kernels.hip, banded_ext_kernels.hip, banded_ext_subst_kernels.hip: the
+// banded class's fills (band = true) and score passes, and the walk over the fills' band; rl = 8, else 4; mode = SW, SG, else NW
+const void* banded_kernel_for(int rl, int mode, bool walk);
+const void* banded_scores_kernel_for(int rl, int mode);
+const void* banded_subst_kernel_for(int rl, int mode, bool band);
+const void* banded_ext_kernel_for(int rl, bool band);
+const void* banded_ext_subst_kernel_for(int rl, bool band);
 }
 
 __global__ void pwa_nop_kernel(int* p) {
@@ -631,6 +639,49 @@ int PairLaunch::check(pwa_ctx* ctx) {
     return PWA_OK;
 }
 
+// ---- BandedForm -> kernels: the only caller of the banded units' pickers, which read any rl as 4 or 8 and any mode as one of the three.
+// EXT is an extension over NW's matrix: no other mode, and the walk over its band is NW's.
+bool resolve_banded_form(const BandedForm& f, BandedKernels& k) {   // false: no such kernel
+    k = BandedKernels{};
+    if ((f.rl != 4 && f.rl != 8) || (f.mode != PWA_MODE_NW && f.mode != PWA_MODE_SW && f.mode != PWA_MODE_SG) || (f.ext && f.mode != PWA_MODE_NW)) return false;
+    k.fill = f.ext ? (f.subst ? banded_ext_subst_kernel_for(f.rl, f.walk) : banded_ext_kernel_for(f.rl, f.walk))
+             : f.subst ? banded_subst_kernel_for(f.rl, f.mode, f.walk)
+             : f.walk  ? banded_kernel_for(f.rl, f.mode, false)
+                       : banded_scores_kernel_for(f.rl, f.mode);
+    if (f.walk) k.walk = banded_kernel_for(f.rl, f.mode, true);
+    return k.fill && (k.walk || !f.walk);
+}
+
+// The fill's grid is what is resident at once -- the runtime's occupancy figure for this kernel (its VGPRs: 79 .. 248, two to six
+// waves per SIMD) with this launch's hand-off rows in LDS -- and no more: pairs are dealt statically, longest first, so a workgroup
+// that had to wait for a slot would run its whole share behind the others.  Only the dynamic LDS -- the hand-off rows -- is named to
+// the runtime; it counts a table kernel's static SubstLds itself, both for the attribute's limit and for the occupancy figure.
+hipError_t banded_launch(const BandedForm& f, const PairParams& G, int row_cap, int xdrop, const SubstRef& tab, int num_cu, hipStream_t st,
+                         hipEvent_t after_fill) {
+    BandedKernels k;
+    if (!resolve_banded_form(f, k) || row_cap < 1 || row_cap > kBandedMaxWidth || !G.n_pairs || num_cu < 1) return hipErrorInvalidValue;
+    if (f.subst && (!tab.tab || tab.n_sym < 1 || tab.n_sym > kSubstMaxSym || tab.stride < tab.n_sym || tab.stride > kSubstMaxSym)) return hipErrorInvalidValue;
+    const size_t lds = (size_t)kBandedWaves * (size_t)row_cap * sizeof(bint2);
+    hipError_t e = hipFuncSetAttribute(k.fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    int per_cu = 0;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fill, 64 * kBandedWaves, lds)) != hipSuccess) return e;
+    const uint32_t n_wg = (G.n_pairs + kBandedWaves - 1) / kBandedWaves;
+    const uint32_t grid = std::min<uint32_t>(n_wg, (uint32_t)num_cu * (uint32_t)std::max(per_cu, 1));
+    // the kernel's own parameter order: G, row_cap, then xdrop (EXT), then blob, n_sym, stride (a table)
+    PairParams g = G;
+    SubstRef t = tab;
+    void* args[6] = {&g, &row_cap};
+    int n_args = 2;
+    if (f.ext) args[n_args++] = &xdrop;
+    if (f.subst) args[n_args++] = &t.tab, args[n_args++] = &t.n_sym, args[n_args++] = &t.stride;
+    if ((e = hipLaunchKernel(k.fill, dim3(grid), dim3(64 * kBandedWaves), args, lds, st)) != hipSuccess) return e;
+    if (after_fill && (e = hipEventRecord(after_fill, st)) != hipSuccess) return e;
+    if (!k.walk) return hipSuccess;
+    void* walk_args[1] = {&g};
+    return hipLaunchKernel(k.walk, dim3(G.n_pairs), dim3(64), walk_args, 0, st);   // one wave per pair
+}
+
 // A caller's substitution table, checked and laid out for the device: codes < n_sym for all 256 bytes, n_sym in 1 .. 32.  The table is
 // stored with the text code as the row (a lane adds its pattern rows' offsets to one row address per step); the row stride is odd below
 // 32 symbols, so that the rows of a small alphabet start in different LDS banks, and never more than 32 (4 KiB in all).
@@ -776,6 +827,45 @@ static int selftest_pair_forms() {
     return 0;
 }
 
+// ... and the banded class: the 32 forms run_banded_launch can build resolve (the 24 plain ones, the 8 of EXT over NW's matrix), each
+// to a fill of its own; a score pass has no walk, a fill has the walk of the byte-compare fill of its rl and mode (EXT: NW's), six in
+// all; geometries, modes and EXT combinations that mean nothing are refused.
+static int selftest_banded_forms() {
+    std::vector<const void*> fills, walks;
+    BandedKernels k, plain;
+    for (const int rl : {4, 8})
+        for (const int mode : {PWA_MODE_NW, PWA_MODE_SW, PWA_MODE_SG})
+            for (const bool ext : {false, true})
+                for (const bool subst : {false, true})
+                    for (const bool walk : {false, true}) {
+                        if (ext && mode != PWA_MODE_NW) continue;
+                        if (!resolve_banded_form(BandedForm{rl, mode, ext, subst, walk}, k) || !k.fill) return 1;
+                        if (!resolve_banded_form(BandedForm{rl, mode, false, false, true}, plain)) return 1;
+                        if (k.walk != (walk ? plain.walk : nullptr)) return 2;
+                        fills.push_back(k.fill);
+                        if (!ext && !subst && walk) walks.push_back(k.walk);
+                    }
+    for (std::vector<const void*>* v : {&fills, &walks}) {
+        std::sort(v->begin(), v->end());
+        if (std::adjacent_find(v->begin(), v->end()) != v->end()) return 2;
+    }
+    if (fills.size() != 32 || walks.size() != 6 || !walks[0]) return 2;
+    const BandedForm none[] = {
+        {2, PWA_MODE_NW, false, false, true},   // stripe heights without an instantiation
+        {6, PWA_MODE_SW, false, true, false},
+        {16, PWA_MODE_NW, true, false, true},
+        {4, 3, false, false, true},             // unknown mode
+        {8, 3, false, true, false},
+        {4, PWA_MODE_SW, true, false, true},    // EXT is NW's matrix
+        {8, PWA_MODE_SW, true, true, false},
+        {4, PWA_MODE_SG, true, true, true},
+        {8, PWA_MODE_SG, true, false, false},
+    };
+    for (const BandedForm& f : none)
+        if (resolve_banded_form(f, k)) return 3;
+    return 0;
+}
+
 extern "C" {
 
 const char* pwa_version(void) { return "pwalign 0.1 gfx950"; }
@@ -833,7 +923,8 @@ int pwa_selftest_host(uint32_t seed) try {
         }
     }
     if (const int rc = selftest_pair_forms()) return check + rc;
-    return selftest_align_plan(x, check + 2);
+    if (const int rc = selftest_banded_forms()) return check + 2 + rc;
+    return selftest_align_plan(x, check + 5);
 } catch (...) {
     return -1;
 }

@@ -328,6 +328,23 @@ struct PairKernels {
     bool walks = false;
 };
 
+// What a launch of the banded class (banded_fill.hip.h: one wave per pair, stripes of 64 rl rows over a diagonal band) IS, as one value.
+// resolve_banded_form (pwalign_ctx.hip) maps it to the kernels' host stubs, or says that there are none.
+struct BandedForm {
+    int rl, mode;   // rows per lane (4 | 8); PWA_MODE_NW | SW | SG (EXT: NW)
+    bool ext;       // extension from (0, 0) with an X-drop: the kernels take xdrop behind row_cap
+    bool subst;     // the diagonal score from a table: the kernels end with (blob, n_sym, stride)
+    bool walk;      // false: the score pass (no band, no walk kernel)
+};
+struct BandedKernels {
+    const void *fill = nullptr, *walk = nullptr;   // the fill or score pass, 64 * kBandedWaves threads per workgroup; the walk, one wave per pair
+};
+bool resolve_banded_form(const BandedForm& f, BandedKernels& k);
+// Fill or score pass, then the form's walk, on `st`; `after_fill` is recorded behind the fill in every form.  row_cap: the launch's
+// widest band; xdrop and tab: read by the forms that have them.
+hipError_t banded_launch(const BandedForm& f, const PairParams& G, int row_cap, int xdrop, const SubstRef& tab, int num_cu, hipStream_t st,
+                         hipEvent_t after_fill);
+
 // Device-side state of one launch of the wavefront (pair) engine: pair descriptors, the global
 // stripe-task list, hand-off rows, progress counters, per-stripe bests.
 struct PairLaunch {

@@ -55,7 +55,10 @@ def test_dropin_library_exports_the_reference_signatures():
 def test_host_sorting_helpers_selftest():
     """The scheduler's stable sorts (counting sort incl. its multi-threaded form, length sort, radix sort) against std::stable_sort on
     lists of up to 2^20 elements, and the range planner of the alignment batches on random length lists (all three classes, empty sides,
-    linear and gotoh, several ranges, score band, gapped op regions) against the invariants of a plan -- inside the library, no GPU involved."""
+    linear and gotoh, several ranges, score band, gapped op regions) against the invariants of a plan; and that every launch form
+    resolves to kernels -- the pair engine's PairForm values, and the banded class's 32 BandedForm values (rl 4 | 8, three modes and EXT
+    over NW, with and without a table, fill or score pass) to 32 distinct fills and the six walks, a score pass to no walk, with stripe
+    heights 2, 6 and 16, mode 3 and EXT under SW or SG refused -- inside the library, no GPU involved."""
     L = load_pkg().lib()
     L.pwa_selftest_host.argtypes = [C.c_uint32]
     L.pwa_selftest_host.restype = C.c_int
