@@ -42,7 +42,11 @@ EXPORTS = [
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
+    "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
 ]
+
+
+APPROX_NO_START = 0xffffffff   # PWA_APPROX_NO_START
 
 
 class PwaError(RuntimeError):
@@ -66,6 +70,35 @@ def approx_plan(n, pat_len, max_dist, chunk):
     if rc != 0:
         raise PwaError("pwa_approx_plan: %s" % L.pwa_strerror(rc).decode())
     return [(tp[t], ts[t], tl[t], th[t]) for t in range(cap)]
+
+
+def approx_minima(hits, pat_len, k, n):
+    """pwa_approx_minima (host only): per pattern, the locally minimal ends of its COMPLETE hit list [(end, dist)] (find_approx's, for
+    a text of n and the bound k: one int, or one per pattern) -> per pattern [(end, dist)], the leftmost end of every plateau that
+    is entered by a descent and left by a rise."""
+    L = lib()
+    n_pat = len(hits)
+    ks = [k] * n_pat if isinstance(k, int) else list(k)
+    if len(ks) != n_pat or len(pat_len) != n_pat:
+        raise ValueError("one pattern length and one k (or one int) per hit list")
+    pl = (C.c_uint32 * max(n_pat, 1))(*pat_len)
+    md = (C.c_uint32 * max(n_pat, 1))(*ks)
+    occ_off, occ = _pack_hits(hits)
+    rc = L.pwa_approx_minima(n, pl, md, n_pat, occ_off, occ)
+    if rc != 0:
+        raise PwaError("pwa_approx_minima: %s" % L.pwa_strerror(rc).decode())
+    return [[(occ[x] >> 32, occ[x] & 0xffffffff) for x in range(occ_off[q], occ_off[q + 1])] for q in range(n_pat)]
+
+
+def _pack_hits(hits):
+    """per-pattern [(end, dist)] -> (occ_off, occ) as pwa_approx_occurrences writes them"""
+    n_pat = len(hits)
+    occ_off = (C.c_uint64 * (n_pat + 1))()
+    for q, h in enumerate(hits):
+        occ_off[q + 1] = occ_off[q] + len(h)
+    total = occ_off[n_pat]
+    occ = (C.c_uint64 * max(total, 1))(*[e << 32 | d for h in hits for e, d in h])
+    return occ_off, occ
 
 
 _hw1 = None
@@ -244,6 +277,9 @@ def lib():
     L.pwa_approx_occurrences.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
     L.pwa_approx_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
     L.pwa_approx_plan.argtypes = [C.c_uint64, u32p, u32p, C.c_uint32, C.c_uint32, u32p, u64p, u64p, u64p, C.c_uint64, u64p]
+    L.pwa_approx_starts.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u64p, u64p, u32p]
+    L.pwa_approx_starts_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p, u64p]
+    L.pwa_approx_minima.argtypes = [C.c_uint64, u32p, u32p, C.c_uint32, u64p, u64p]
     _lib = L
     return L
 
@@ -1006,6 +1042,58 @@ class Context:
                     "pwa_approx_occurrences")
         self._approx_stats()
         return [[(occ[x] >> 32, occ[x] & 0xffffffff) for x in range(occ_off[q], occ_off[q + 1])] for q in range(n_pat)]
+
+    # -- from a hit to a placement: starts, locally minimal ends, alignments (include/pwalign.h, pwa_approx_starts / pwa_approx_minima)
+    def starts_approx(self, text, patterns, hits):
+        """Per pattern, the starts of its hits [(end, dist)], parallel to them: the largest s with ed(pattern, text[s:end]) <= dist,
+        None where there is none (a dist below the true distance of that end).  Any subset of find_approx's hits, in any order."""
+        blob, off, pats = pack_sequences(patterns)
+        n_pat = len(pats)
+        if len(hits) != n_pat:
+            raise ValueError("hits: one list of (end, dist) per pattern")
+        text = _b(text)
+        occ_off, occ = _pack_hits(hits)
+        total = occ_off[n_pat]
+        out = (C.c_uint32 * max(total, 1))()
+        self._check(self._L.pwa_approx_starts(self._h, text, len(text), blob, off, n_pat, occ_off, occ, out), "pwa_approx_starts")
+        ms, nh, col = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_approx_starts_last_stats(self._h, C.byref(ms), C.byref(nh), C.byref(col)), "pwa_approx_starts_last_stats")
+        self.approx_starts_stats = dict(ms=ms.value, hits=nh.value, columns=col.value)
+        return [[None if out[x] == APPROX_NO_START else out[x] for x in range(occ_off[q], occ_off[q + 1])] for q in range(n_pat)]
+
+    def locate_approx(self, text, patterns, k, select="minima"):
+        """Per pattern, [(start, end, dist)] in ascending end of its hits within k edits: find_approx, then the selection -- "all":
+        every hit; "minima": the locally minimal ends (approx_minima); "best": the one hit count_approx names -- then starts_approx."""
+        if select not in ("minima", "all", "best"):
+            raise ValueError('select: "minima", "all" or "best"')
+        blob, off, pats = packed = pack_sequences(patterns)
+        hits = self.find_approx(text, packed, k)
+        if select == "minima":
+            hits = approx_minima(hits, [len(p) for p in pats], k, len(_b(text)))
+        elif select == "best":
+            hits = [[min(h, key=lambda x: (x[1], x[0]))] if h else [] for h in hits]
+        starts = self.starts_approx(text, packed, hits)
+        return [[(s, e, d) for s, (e, d) in zip(ss, h)] for ss, h in zip(starts, hits)]
+
+    def align_approx(self, text, patterns, k, select="minima"):
+        """Per pattern, [dict(start, end, dist, score, cigar, mdz)] of locate_approx's placements: the global alignment of the pattern
+        against text[start:end] under unit costs (align_gotoh_batch_cigar("nw", ..., 0, -1, 0, -1)), so score == -dist; a hit with
+        start == end follows that call's empty-side convention."""
+        blob, off, pats = packed = pack_sequences(patterns)
+        text = _b(text)
+        placed = self.locate_approx(text, packed, k, select)
+        seqs, pa, pb = list(pats), [], []
+        for q, pl in enumerate(placed):
+            for s, e, _ in pl:
+                pa.append(q)
+                pb.append(len(seqs))
+                seqs.append(text[s:e])
+        al = self.align_gotoh_batch_cigar("nw", seqs, pa, pb, 0, -1, 0, -1) if pa else []
+        out, at = [], 0
+        for pl in placed:
+            out.append([dict(start=s, end=e, dist=d, score=a["score"], cigar=a["cigar"], mdz=a["mdz"]) for (s, e, d), a in zip(pl, al[at:at + len(pl)])])
+            at += len(pl)
+        return out
 
 
 class Batch:

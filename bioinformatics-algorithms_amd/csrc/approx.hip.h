@@ -155,5 +155,125 @@ __global__ __launch_bounds__(64) void approx_scan_kernel(const uint8_t* __restri
     }
 }
 
+// ---- start positions of hits (pwa_approx_starts): the same column, anchored, run backwards from a hit's end.
+//
+// The start of a hit (e, d) is the largest s with ed(p, text[s:e]) <= d: the first column j at which row m of the reversed pattern
+// against text[e-1], text[e-2], ... reaches d under D'[0][j] = j, then s = e - j.  The anchored form differs from the search form in two
+// places: the pad rows match NO symbol (Eq = 0 for every code) and hold Pv = Mv = 0, and a 1 enters the Ph shift at bit 0 in every
+// column.  The pad rows then keep Ph = 1, Mh = 0, Pv = Mv = 0 for good (Xh = 0 there and no carry leaves them) and hand the +1 of row 0
+// into pattern row 1; row m is still bit 31 of the last register.
+
+constexpr uint32_t kNoStart = 0xffffffffu;
+
+struct Hit {   // one hit on the device: the pattern, its end and distance as the occurrence list has them, and where its start goes
+    uint32_t pat, end, dist, out;
+};
+
+// Masks of every REVERSED pattern with the pad bits clear: thread (pattern, code, word), the layout of approx_masks_kernel.
+__global__ __launch_bounds__(256) void approx_masks_rev_kernel(const uint8_t* __restrict__ blob, const Pat* __restrict__ pats, uint32_t n_pat, uint32_t rows,
+                                                               const CodeTable tab, uint64_t* __restrict__ peq) {
+    const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t q = x / (rows * kMaxWords);
+    const uint32_t r = (uint32_t)(x % (rows * kMaxWords)), code = r / kMaxWords, w = r % kMaxWords;
+    if (q >= n_pat) return;
+    const Pat p = pats[q];
+    if (w >= p.W) return;
+    const uint32_t pad = 64 * p.W - p.m;
+    uint64_t bits = 0;
+    for (uint32_t b = 0; b < 64; ++b) {
+        const uint32_t pos = 64 * w + b;
+        if (pos >= pad && tab.t[blob[p.off + (p.m - 1 - (pos - pad))]] == code) bits |= 1ull << b;
+    }
+    peq[p.peq + code * p.W + w] = bits;
+}
+
+// One wave per workgroup, lane l of workgroup b runs hits[64 b + l] (below n_hits) and writes start_out[its out].  LDS as the scan's.
+// The coded text is read backwards in aligned dwords, the highest byte first and the next dword one ahead; the dword below the one
+// that holds text[0] is never addressed (a lane has stopped by then: j = e is its last column at the latest).
+template <int W>
+__global__ __launch_bounds__(64) void approx_start_kernel(const uint8_t* __restrict__ text, const uint64_t* __restrict__ peq, const Pat* __restrict__ pats,
+                                                          const Hit* __restrict__ hits, uint32_t n_hits, uint32_t rows, uint32_t* __restrict__ start_out) {
+    extern __shared__ uint2 approx_lds[];
+    constexpr int N = 2 * W;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t idx = blockIdx.x * 64 + lane;
+    if (idx >= n_hits) return;
+    const Hit h = hits[idx];
+    const Pat p = pats[h.pat];
+    const int dist = (int)h.dist;
+    int score = (int)p.m;
+    if (score <= dist) {   // j = 0, before any symbol: the empty substring
+        start_out[h.out] = h.end;
+        return;
+    }
+    {
+        const uint2* src = reinterpret_cast<const uint2*>(peq + p.peq);
+        for (uint32_t i = 0; i < rows * W; ++i) approx_lds[i * 64 + lane] = src[i];
+    }
+    uint32_t pv[N], mv[N];
+    {
+        const uint32_t pad = 64 * W - p.m;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const uint32_t b = 32 * i;   // ones from bit pad up
+            pv[i] = pad <= b ? ~0u : pad >= b + 32 ? 0u : ~0u << (pad - b);
+            mv[i] = 0;
+        }
+    }
+    const uint32_t jmax = h.end < p.m + h.dist ? h.end : p.m + h.dist;   // >= 1
+    const uint32_t* text32 = reinterpret_cast<const uint32_t*>(text);
+    uint32_t di = (h.end - 1) >> 2;
+    uint32_t left = ((h.end - 1) & 3u) + 1;
+    uint32_t cur = text32[di] << (8 * (4 - left));
+    uint32_t nxt = di ? text32[di - 1] : 0;
+    const uint2* eq_lane = approx_lds + lane;
+    uint32_t j = 0, res = kNoStart;
+    for (;;) {
+        if (left == 0) {
+            cur = nxt;
+            left = 4;
+            --di;
+            nxt = di ? text32[di - 1] : 0;
+        }
+        const uint32_t code = cur >> 24;
+        cur <<= 8;
+        --left;
+        const uint2* eqp = eq_lane + code * (W * 64);
+        uint32_t carry = 0, ph_in = 0x80000000u, mh_in = 0, ph_top = 0, mh_top = 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint2 e2 = eqp[w * 64];
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                const int i = 2 * w + hh;
+                const uint32_t eq = hh ? e2.y : e2.x;
+                const uint32_t sum = __builtin_addc(eq & pv[i], pv[i], carry, &carry);
+                const uint32_t xh = (sum ^ pv[i]) | eq;
+                const uint32_t ph = mv[i] | ~(xh | pv[i]);
+                const uint32_t mh = pv[i] & xh;
+                const uint32_t xv = eq | mv[i];
+                const uint32_t ph1 = __builtin_amdgcn_alignbit(ph, ph_in, 31);
+                const uint32_t mh1 = __builtin_amdgcn_alignbit(mh, mh_in, 31);
+                pv[i] = mh1 | ~(xv | ph1);
+                mv[i] = ph1 & xv;
+                ph_in = ph;
+                mh_in = mh;
+                if (i == N - 1) {
+                    ph_top = ph;
+                    mh_top = mh;
+                }
+            }
+        }
+        score += (int)(ph_top >> 31) - (int)(mh_top >> 31);
+        ++j;
+        if (score <= dist) {
+            res = h.end - j;
+            break;
+        }
+        if (j == jmax) break;
+    }
+    start_out[h.out] = res;
+}
+
 }  // namespace approx
 }  // namespace pwa

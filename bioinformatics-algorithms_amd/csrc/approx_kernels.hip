@@ -1,5 +1,6 @@
 // approx_kernels.hip -- the approximate-search entries of include/pwalign.h (pwa_approx_*): validation, the task plan, the lane
-// order, device buffers, the count and the fill pass.  Kernels: approx.hip.h.  DESIGN.md §3.18.
+// order, device buffers, the count and the fill pass; the starts pass over a hit list and the host-only minima of
+// one (§3.19).  Kernels: approx.hip.h.
 #include "../../include/pwalign.h"
 
 #include <hip/hip_runtime.h>
@@ -70,6 +71,8 @@ scan_kernel_t scan_kernel_for(int W) {
 struct Search {
     uint32_t rows = 0;                            // sigma + 1: the codes of the call
     uint64_t n_tasks = 0, columns = 0;
+    uint64_t peq_words = 0;                       // of one mask array of the call
+    size_t tbytes = 0;                            // of the padded text buffer
     std::vector<Pat> pats;
     uint32_t first_wave[kMaxWords + 2] = {};      // class W's waves are lane_task[64 * first_wave[W] .. 64 * first_wave[W + 1])
     Dev text, blob, d_pats, peq, tasks, lane_task, task_cnt, pat_cnt, pat_best;
@@ -123,6 +126,34 @@ int validate(const pwa::ApproxCtxView& v, const char* who, uint64_t n, const uin
     return PWA_OK;
 }
 
+// What every pass starts from: the patterns of the call (s.pats, with bound min(max_dist, m), or m without max_dist) and the places
+// of their masks, and on the device the raw text (padded to 16 bytes + 16 with zeros), the pattern bytes and the pattern records,
+// enqueued on the stream.  The caller codes the text and builds its masks inside its own events.
+void stage_inputs(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uint64_t n, const uint8_t* pb, const uint64_t* poff, uint32_t n_pat,
+                  const uint32_t* max_dist, uint32_t sigma) {
+    s.rows = sigma + 1;
+    const uint64_t base = poff[0], bytes = poff[n_pat] - base;
+    s.pats.resize(n_pat);
+    s.peq_words = 0;
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        const uint32_t m = (uint32_t)(poff[q + 1] - poff[q]), W = (m + 63) / 64;
+        if (s.peq_words + (uint64_t)s.rows * W > 0xffffffffull || poff[q] - base > 0xffffffffull)
+            throw Fail{PWA_E_CAPACITY, "pwa_approx: the patterns of one call exceed 32-bit offsets"};
+        s.pats[q] = Pat{(uint32_t)(poff[q] - base), m, max_dist ? std::min(max_dist[q], m) : m, (uint32_t)s.peq_words, W};
+        s.peq_words += (uint64_t)s.rows * W;
+    }
+    (void)hipSetDevice(v.device);
+    s.tbytes = (n + 15) / 16 * 16 + 16;
+    AP_CHECK(s.text.alloc(s.tbytes));
+    AP_CHECK(s.blob.alloc(bytes));
+    AP_CHECK(s.d_pats.alloc((size_t)n_pat * sizeof(Pat)));
+    AP_CHECK(s.peq.alloc(s.peq_words * 8));
+    AP_CHECK(hipMemsetAsync(s.text.p, 0, s.tbytes, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
+    AP_CHECK(hipMemcpyAsync(s.d_pats.p, s.pats.data(), (size_t)n_pat * sizeof(Pat), hipMemcpyHostToDevice, v.stream));
+}
+
 // Uploads, codes the text, builds the masks, runs the count pass; fills s.h_cnt / s.h_best and the stats of v
 void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uint64_t n, const uint8_t* pb, const uint64_t* poff, uint32_t n_pat,
                 const uint32_t* max_dist, const CodeTable& tab, uint32_t sigma) {
@@ -147,20 +178,11 @@ void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uin
         tasks[t] = Task{t_pat[t], (uint32_t)t_scan[t], (uint32_t)t_lo[t], (uint32_t)t_hi[t]};
         s.columns += t_hi[t] - t_scan[t];
     }
-    // patterns, their masks' places, their first tasks
-    const uint64_t base = poff[0], bytes = poff[n_pat] - base;
-    s.pats.resize(n_pat);
+    // patterns and their masks' places, the uploads every pass shares, then the first tasks
+    stage_inputs(v, s, text, n, pb, poff, n_pat, max_dist, sigma);
     std::vector<uint32_t> first_task(n_pat + 1, 0);
-    uint64_t peq_words = 0;
     const uint64_t per_pat = (n + v.chunk - 1) / v.chunk;
-    for (uint32_t q = 0; q < n_pat; ++q) {
-        const uint32_t W = (len[q] + 63) / 64;
-        if (peq_words + (uint64_t)s.rows * W > 0xffffffffull || poff[q] - base > 0xffffffffull)
-            throw Fail{PWA_E_CAPACITY, "pwa_approx: the patterns of one call exceed 32-bit offsets"};
-        s.pats[q] = Pat{(uint32_t)(poff[q] - base), len[q], std::min(max_dist[q], len[q]), (uint32_t)peq_words, W};
-        peq_words += (uint64_t)s.rows * W;
-        first_task[q + 1] = first_task[q] + (uint32_t)per_pat;
-    }
+    for (uint32_t q = 0; q < n_pat; ++q) first_task[q + 1] = first_task[q] + (uint32_t)per_pat;
     // lane order: per word class, chunk by chunk, the patterns of the class side by side; a wave holds one class
     std::vector<uint32_t> lane_task;
     lane_task.reserve(nt + 64 * kMaxWords);
@@ -175,12 +197,6 @@ void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uin
     }
     s.first_wave[kMaxWords + 1] = (uint32_t)(lane_task.size() / 64);
 
-    (void)hipSetDevice(v.device);
-    const size_t tbytes = (n + 15) / 16 * 16 + 16;
-    AP_CHECK(s.text.alloc(tbytes));
-    AP_CHECK(s.blob.alloc(bytes));
-    AP_CHECK(s.d_pats.alloc((size_t)n_pat * sizeof(Pat)));
-    AP_CHECK(s.peq.alloc(peq_words * 8));
     AP_CHECK(s.tasks.alloc(nt * sizeof(Task)));
     AP_CHECK(s.lane_task.alloc(lane_task.size() * 4));
     AP_CHECK(s.task_cnt.alloc(nt * 4));
@@ -189,16 +205,12 @@ void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uin
     Events ev;
     AP_CHECK(hipEventCreate(&ev.a));
     AP_CHECK(hipEventCreate(&ev.b));
-    AP_CHECK(hipMemsetAsync(s.text.p, 0, tbytes, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.d_pats.p, s.pats.data(), (size_t)n_pat * sizeof(Pat), hipMemcpyHostToDevice, v.stream));
     AP_CHECK(hipMemcpyAsync(s.tasks.p, tasks.data(), nt * sizeof(Task), hipMemcpyHostToDevice, v.stream));
     AP_CHECK(hipMemcpyAsync(s.lane_task.p, lane_task.data(), lane_task.size() * 4, hipMemcpyHostToDevice, v.stream));
     AP_CHECK(hipMemsetAsync(s.pat_cnt.p, 0, (size_t)n_pat * 4, v.stream));
     AP_CHECK(hipMemsetAsync(s.pat_best.p, 0xff, (size_t)n_pat * 8, v.stream));
     AP_CHECK(hipEventRecord(ev.a, v.stream));
-    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), tbytes / 16, tab.t));
+    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
     const uint64_t mask_threads = (uint64_t)n_pat * s.rows * kMaxWords;
     approx_masks_kernel<<<(uint32_t)((mask_threads + 255) / 256), 256, 0, v.stream>>>(s.blob.as<uint8_t>(), s.d_pats.as<Pat>(), n_pat, s.rows, tab, s.peq.as<uint64_t>());
     AP_CHECK(hipGetLastError());
@@ -265,6 +277,85 @@ void fill_pass(const pwa::ApproxCtxView& v, Search& s, uint64_t* occ) {
         kept += sl.hits;
     }
     if (v.debug) std::fprintf(stderr, "[pwa] approx fill: %zu slices, %llu hits, device %.3f ms\n", slices.size(), (unsigned long long)kept, v.stats->fill_ms);
+}
+
+using start_kernel_t = decltype(&approx_start_kernel<1>);
+start_kernel_t start_kernel_for(int W) {
+    switch (W) {
+        case 1: return approx_start_kernel<1>;
+        case 2: return approx_start_kernel<2>;
+        case 3: return approx_start_kernel<3>;
+        case 4: return approx_start_kernel<4>;
+        case 5: return approx_start_kernel<5>;
+        case 6: return approx_start_kernel<6>;
+        case 7: return approx_start_kernel<7>;
+        default: return approx_start_kernel<8>;
+    }
+}
+
+// The starts pass: the hits sorted into word classes (a counting sort, stable), then slices of at most PWA_OCC_CHUNK_HITS records, each
+// slice one launch per word class it touches; the starts land in a device array parallel to occ and come back in one copy.
+void starts_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uint64_t n, const uint8_t* pb, const uint64_t* poff, uint32_t n_pat,
+                 const uint64_t* occ_off, const uint64_t* occ, const CodeTable& tab, uint32_t sigma, uint32_t* start_out) {
+    const uint64_t total = occ_off[n_pat] - occ_off[0];
+    stage_inputs(v, s, text, n, pb, poff, n_pat, nullptr, sigma);
+    uint64_t class_at[kMaxWords + 2] = {};   // class W's records are sorted[class_at[W] .. class_at[W + 1])
+    for (uint32_t q = 0; q < n_pat; ++q) class_at[s.pats[q].W + 1] += occ_off[q + 1] - occ_off[q];
+    for (int W = 1; W <= kMaxWords; ++W) class_at[W + 1] += class_at[W];
+    std::vector<Hit> sorted(total);
+    {
+        uint64_t at[kMaxWords + 1];
+        for (int W = 1; W <= kMaxWords; ++W) at[W] = class_at[W];
+        for (uint32_t q = 0; q < n_pat; ++q)
+            for (uint64_t x = occ_off[q]; x < occ_off[q + 1]; ++x)
+                sorted[at[s.pats[q].W]++] = Hit{q, (uint32_t)(occ[x] >> 32), (uint32_t)occ[x], (uint32_t)(x - occ_off[0])};
+    }
+    const uint64_t budget = std::min(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultSliceHits, kMaxSliceHits);
+    const uint64_t slice_cap = std::min(budget, total);
+    Dev recs, starts;
+    AP_CHECK(recs.alloc(slice_cap * sizeof(Hit)));
+    AP_CHECK(starts.alloc(total * 4));
+    Events ev;
+    AP_CHECK(hipEventCreate(&ev.a));
+    AP_CHECK(hipEventCreate(&ev.b));
+    float ms = 0.f, part = 0.f;
+    AP_CHECK(hipEventRecord(ev.a, v.stream));
+    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
+    const uint64_t mask_threads = (uint64_t)n_pat * s.rows * kMaxWords;
+    approx_masks_rev_kernel<<<(uint32_t)((mask_threads + 255) / 256), 256, 0, v.stream>>>(s.blob.as<uint8_t>(), s.d_pats.as<Pat>(), n_pat, s.rows, tab,
+                                                                                          s.peq.as<uint64_t>());
+    AP_CHECK(hipGetLastError());
+    AP_CHECK(hipEventRecord(ev.b, v.stream));
+    AP_CHECK(hipStreamSynchronize(v.stream));
+    AP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    uint64_t slices = 0;
+    for (uint64_t h0 = 0; h0 < total; h0 += slice_cap, ++slices) {
+        const uint64_t h1 = std::min(h0 + slice_cap, total);
+        AP_CHECK(hipMemcpyAsync(recs.p, sorted.data() + h0, (h1 - h0) * sizeof(Hit), hipMemcpyHostToDevice, v.stream));
+        AP_CHECK(hipEventRecord(ev.a, v.stream));
+        for (int W = 1; W <= kMaxWords; ++W) {
+            const uint64_t c0 = std::max(h0, class_at[W]), c1 = std::min(h1, class_at[W + 1]);
+            if (c0 >= c1) continue;
+            start_kernel_t kern = start_kernel_for(W);
+            const size_t lds = (size_t)s.rows * W * 64 * 8;
+            if (lds > 64 * 1024) AP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3((uint32_t)((c1 - c0 + 63) / 64)), dim3(64), lds, v.stream, s.text.as<uint8_t>(), s.peq.as<uint64_t>(), s.d_pats.as<Pat>(),
+                               recs.as<Hit>() + (c0 - h0), (uint32_t)(c1 - c0), s.rows, starts.as<uint32_t>());
+            AP_CHECK(hipGetLastError());
+        }
+        AP_CHECK(hipEventRecord(ev.b, v.stream));
+        AP_CHECK(hipStreamSynchronize(v.stream));   // the records of the next slice go into the same buffer
+        AP_CHECK(hipEventElapsedTime(&part, ev.a, ev.b));
+        ms += part;
+    }
+    AP_CHECK(hipMemcpyAsync(start_out, starts.p, total * 4, hipMemcpyDeviceToHost, v.stream));
+    AP_CHECK(hipStreamSynchronize(v.stream));
+    uint64_t columns = 0;   // what the lanes scanned, read off their answers: e - start, or the whole bound where there is none
+    for (const Hit& h : sorted) columns += start_out[h.out] == kNoStart ? std::min<uint64_t>(h.end, (uint64_t)s.pats[h.pat].m + h.dist) : h.end - start_out[h.out];
+    *v.starts_stats = pwa::ApproxStartsStats{ms, total, columns};
+    if (v.debug)
+        std::fprintf(stderr, "[pwa] approx starts: %llu hits, %llu slices, %llu columns, device %.3f ms\n", (unsigned long long)total, (unsigned long long)slices,
+                     (unsigned long long)columns, ms);
 }
 
 int fail(pwa::ApproxCtxView& v, const Fail& f) {
@@ -350,6 +441,87 @@ int pwa_approx_occurrences(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const 
     } catch (const std::bad_alloc&) {
         return PWA_E_NOMEM;
     }
+    return PWA_OK;
+}
+
+int pwa_approx_starts(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat,
+                      const uint64_t* occ_off, const uint64_t* occ, uint32_t* start_out) {
+    if (!ctx || !pat_off || !occ_off || (!text && n) || (!pat_bytes && pat_off[n_pat] != pat_off[0])) return PWA_E_INVALID;
+    pwa::ApproxCtxView v = pwa::approx_ctx_view(ctx);
+    CodeTable tab;
+    uint32_t sigma = 0;
+    if (const int rc = validate(v, "pwa_approx_starts", n, pat_bytes, pat_off, n_pat, tab, sigma)) return rc;
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        if (occ_off[q + 1] < occ_off[q]) return PWA_E_INVALID;
+        if (occ_off[q + 1] > occ_off[q] && (!occ || !start_out)) return PWA_E_INVALID;
+        const uint64_t m = pat_off[q + 1] - pat_off[q];
+        for (uint64_t x = occ_off[q]; x < occ_off[q + 1]; ++x) {
+            const uint64_t e = occ[x] >> 32, d = occ[x] & 0xffffffffull;
+            if (e == 0 || e > n || d > m) {
+                *v.err = "pwa_approx_starts: hit " + std::to_string(x - occ_off[q]) + " of pattern " + std::to_string(q) + " (end " + std::to_string(e) +
+                         ", dist " + std::to_string(d) + ") lies outside a text of " + std::to_string(n) + " and a pattern of " + std::to_string(m);
+                return PWA_E_INVALID;
+            }
+        }
+    }
+    if (n_pat && occ_off[n_pat] - occ_off[0] > 0xffffffffull) {
+        *v.err = "pwa_approx_starts: more than 2^32 - 1 hits in one call";
+        return PWA_E_CAPACITY;
+    }
+    try {
+        *v.starts_stats = pwa::ApproxStartsStats{};
+        if (!n_pat || occ_off[n_pat] == occ_off[0]) return PWA_OK;
+        Search s;
+        starts_pass(v, s, text, n, pat_bytes, pat_off, n_pat, occ_off, occ, tab, sigma, start_out);
+    } catch (const Fail& f) {
+        return fail(v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_approx_starts_last_stats(const pwa_ctx* ctx, float* ms, uint64_t* hits, uint64_t* columns) {
+    if (!ctx) return PWA_E_INVALID;
+    const pwa::ApproxStartsStats& st = pwa::approx_starts_stats_of(ctx);
+    if (ms) *ms = st.ms;
+    if (hits) *hits = st.hits;
+    if (columns) *columns = st.columns;
+    return PWA_OK;
+}
+
+int pwa_approx_minima(uint64_t n, const uint32_t* pat_len, const uint32_t* max_dist, uint32_t n_pat, uint64_t* occ_off, uint64_t* occ) {
+    if (!occ_off || ((!pat_len || !max_dist) && n_pat)) return PWA_E_INVALID;
+    if (n_pat && occ_off[n_pat] != occ_off[0] && !occ) return PWA_E_INVALID;
+    // the whole list is checked before any of it moves
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        if (!pat_len[q] || occ_off[q + 1] < occ_off[q]) return PWA_E_INVALID;
+        const uint64_t kq = std::min(max_dist[q], pat_len[q]);
+        uint64_t before = 0;
+        for (uint64_t x = occ_off[q]; x < occ_off[q + 1]; ++x) {
+            const uint64_t e = occ[x] >> 32, d = occ[x] & 0xffffffffull;
+            if (e <= before || e > n || d > kq) return PWA_E_INVALID;
+            before = e;
+        }
+    }
+    uint64_t kept = n_pat ? occ_off[0] : 0, lo = kept;
+    for (uint32_t q = 0; q < n_pat; ++q) {
+        const uint64_t hi = occ_off[q + 1], m = pat_len[q], above = std::min<uint64_t>(max_dist[q], m) + 1;   // c of a column without a hit
+        occ_off[q] = kept;
+        for (uint64_t x = lo; x < hi;) {
+            const uint64_t e = occ[x] >> 32, d = occ[x] & 0xffffffffull;
+            const uint64_t left = x > lo && (occ[x - 1] >> 32) + 1 == e ? (occ[x - 1] & 0xffffffffull) : e == 1 ? m : above;
+            uint64_t f = x;   // the plateau's last hit: adjacent ends of the same distance
+            while (f + 1 < hi && (occ[f + 1] >> 32) == (occ[f] >> 32) + 1 && (occ[f + 1] & 0xffffffffull) == d) ++f;
+            const uint64_t ef = occ[f] >> 32;
+            const bool rises = ef == n || (f + 1 < hi && (occ[f + 1] >> 32) == ef + 1 ? (occ[f + 1] & 0xffffffffull) : above) > d;
+            const uint64_t key = occ[x];   // (x - 1 was read above, before anything at or after kept <= x is written)
+            if (left > d && rises) occ[kept++] = key;
+            x = f + 1;
+        }
+        lo = hi;
+    }
+    if (n_pat) occ_off[n_pat] = kept;
     return PWA_OK;
 }
 

@@ -110,9 +110,11 @@ pwa::ApproxCtxView pwa::approx_ctx_view(pwa_ctx* c) {
     v.occ_chunk_hits = c->knobs.occ_chunk_hits;
     v.err = &c->err;
     v.stats = &c->approx_stats;
+    v.starts_stats = &c->approx_starts_stats;
     return v;
 }
 const pwa::ApproxStats& pwa::approx_stats_of(const pwa_ctx* c) { return c->approx_stats; }
+const pwa::ApproxStartsStats& pwa::approx_starts_stats_of(const pwa_ctx* c) { return c->approx_starts_stats; }
 
 hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_t* table) {
     if (!n16) return hipSuccess;

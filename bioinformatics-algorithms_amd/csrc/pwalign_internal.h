@@ -115,6 +115,7 @@ struct pwa_ctx {
     AlignStats ext_stats;                  // the last pwa_extend_banded_batch(_cigar), pwa_scores_extend_banded or a _subst form of them (cells: the sum of rows_out)
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     pwa::ApproxStats approx_stats;         // the last pwa_approx_find / pwa_approx_occurrences
+    pwa::ApproxStartsStats approx_starts_stats;   // the last pwa_approx_starts
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
     // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the

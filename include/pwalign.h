@@ -53,7 +53,8 @@
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
- *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks
+ *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
+ *                                 pwa_approx_starts: at most N hit records on the device per slice
  *   PWA_APPROX_CHUNK=N            pwa_approx_find / pwa_approx_occurrences: a task reports at most N text columns (default 4096)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
@@ -749,6 +750,42 @@ int pwa_approx_last_stats(const pwa_ctx *ctx, float *count_ms, float *fill_ms, u
 int pwa_approx_plan(uint64_t n, const uint32_t *pat_len, const uint32_t *max_dist, uint32_t n_pat, uint32_t chunk,
                     uint32_t *task_pat, uint64_t *task_scan_lo, uint64_t *task_lo, uint64_t *task_hi, uint64_t cap,
                     uint64_t *n_tasks);
+
+/* ---- from a hit to a placement: start positions and locally minimal ends of k-edit hits
+ *
+ * With ed(a, b) the unit-cost edit distance (the recurrence above with D[0][j] = j), the start of a hit (q, e, d) is the LARGEST
+ * s <= e with ed(p_q, text[s .. e)) <= d: the shortest occurrence that ends at e.  For a true hit d = D[m][e] is the minimum over all
+ * starts, so equality is reached and m - d <= e - s <= min(e, m + d); s = e (the empty substring) is the answer when d = m.
+ *   pwa_approx_starts       start_out[x] = the start of hit occ[x], for x in occ_off[0] .. occ_off[n_pat) -- start_out is parallel to
+ *                           occ, whose base is occ_off[0].  occ / occ_off are what pwa_approx_occurrences writes (pattern q's hits are
+ *                           occ[occ_off[q] .. occ_off[q + 1]), occ[x] = (uint64_t)e << 32 | dist); any subset, any order within a
+ *                           pattern and duplicates are legal.  One lane per hit runs the anchored column of the reversed pattern
+ *                           backwards from e over at most min(e, m + dist) text symbols; the hits go to the device in slices of at
+ *                           most PWA_OCC_CHUNK_HITS records.  A dist below the true D[m][e] is not an error: the scan stops at that
+ *                           bound and writes PWA_APPROX_NO_START.  A dist above it gives the first column at which row m reaches it
+ *                           (row m moves by +-1 per column from m down, so "<= dist" and "= dist" coincide).
+ *                           Limits: those of pwa_approx_find, checked in the same order, before any device work; then, in list
+ *                           order, PWA_E_INVALID for occ_off not ascending, a hit with e = 0, with e > n, or with dist > m; more than
+ *                           2^32 - 1 hits PWA_E_CAPACITY.  No hits or n_pat = 0: a valid call.
+ *   pwa_approx_starts_last_stats  of the last pwa_approx_starts on ctx: device ms of the pass (events: coding the text, the masks,
+ *                           the scans of every slice), the hits run, the text columns they scanned.
+ *   pwa_approx_minima       host only, no context, no GPU: thins the COMPLETE ascending hit list of pwa_approx_occurrences for the
+ *                           same n, lengths and bounds down to its locally minimal ends, in place (occ compacted, occ_off rewritten
+ *                           from occ_off[0] on).  With k' = min(max_dist, m), c(e) = dist of the hit at e, c(e) = k' + 1 for an end
+ *                           1 <= e <= n without a hit and c(0) = m, a hit at e is kept iff c(e - 1) > c(e) and, with f the last
+ *                           column of the run c(e) = c(e + 1) = ... = c(f), f = n or c(f + 1) > c(e): the leftmost end of every
+ *                           plateau entered by a descent and left by a rise, the text end counting as a rise.  Exact without the DP
+ *                           row: an end missing from the list has D[m][e] > k', above every hit, and clipping it to k' + 1 changes
+ *                           no comparison that involves a hit.  PWA_E_INVALID (nothing is changed then) for a null pointer, a
+ *                           pattern length of 0, offsets not ascending, ends not strictly ascending within a pattern, an end outside
+ *                           1 .. n, or dist > k'. */
+#define PWA_APPROX_NO_START 0xffffffffu
+int pwa_approx_starts(pwa_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *pat_bytes, const uint64_t *pat_off,
+                      uint32_t n_pat, const uint64_t *occ_off /* n_pat + 1 */, const uint64_t *occ /* e << 32 | dist */,
+                      uint32_t *start_out /* parallel to occ */);
+int pwa_approx_starts_last_stats(const pwa_ctx *ctx, float *ms, uint64_t *hits, uint64_t *columns);
+int pwa_approx_minima(uint64_t n, const uint32_t *pat_len, const uint32_t *max_dist, uint32_t n_pat,
+                      uint64_t *occ_off /* in: n_pat + 1; out: of the kept hits */, uint64_t *occ /* compacted in place */);
 
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
