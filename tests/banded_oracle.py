@@ -4,7 +4,9 @@ gotoh_oracle's recurrences, tie rules and walk over the cells with lo <= j - i <
 its in-band columns only: the tables are kept in band coordinates, slot x of row i = cell (i, i + lo + x), so the row above sits one
 slot to the right and the diagonal neighbour in the same slot.  The closed-form left chain of gotoh_oracle.fill stays valid because a
 row's in-band columns are contiguous.  A group of pairs (any lengths, any bands) is filled together, padded to the longest pattern and
-the widest band.  int64 with a far -inf."""
+the widest band.  int64 with a far -inf.  The diagonal score is gotoh_oracle's scoring value `sc` (match / mismatch, or a substitution
+table: pwa_align_banded_subst_batch).  Per row the fill also keeps the maximum of H over the in-band cells with j >= 1 and its first
+column: what the X-drop extension (banded_ext_oracle) reads from the NW band."""
 import numpy as np
 
 import gotoh_oracle as go_
@@ -25,9 +27,27 @@ def band_valid(mode, n, m, lo, hi):
     return True
 
 
-def fill(pairs, bands, mode, match, mismatch, go, ge):
-    """pairs: [(p, t)], bands: [(lo, hi)] -> dict(src, eop, fop: (G, nmax + 1, B) in band coordinates; hlast: H of each pair's row n;
-    best: SW's first row-major maximum (score, i, j) per pair; lo: the bands' lo)"""
+def random_band(rng, mode, n, m):
+    """a random valid band: the narrowest one the mode admits a quarter of the time (width 1 where that is valid), else wider"""
+    d = m - n
+    k1, k2 = [(0, 0), (rng.randint(0, 3), rng.randint(0, 3)), (rng.randint(0, n + m), rng.randint(0, n + m))][min(rng.randint(0, 3), 2)]
+    if mode == "nw":
+        b = (min(0, d) - k1, max(0, d) + k2)
+    elif mode == "sg":
+        lo = rng.randint(-n - 1, d)
+        b = (lo, max(lo, 0) + (0 if k1 == 0 else k2))
+    else:
+        lo = rng.randint(-n - 2, m + 2)
+        b = (lo, lo + (0 if k1 == 0 else k2))
+    assert band_valid(mode, n, m, *b)
+    return b
+
+
+def fill(pairs, bands, mode, sc, go, ge):
+    """pairs: [(p, t)] (raw bytes), bands: [(lo, hi)] -> dict(src, eop, fop: (G, nmax + 1, B) in band coordinates; hlast: H of each
+    pair's row n; best: SW's first row-major maximum (score, i, j) per pair; lo, W: the clamped bands' lo and width; rmax, rcol: (G,
+    nmax + 1), per row i >= 1 the maximum of H over the in-band cells with j >= 1 (NEG when there is none) and its first column)"""
+    score = go_.scorer(sc)[0]
     G = len(pairs)
     ns = np.array([len(p) for p, _ in pairs], dtype=np.int64)
     ms = np.array([len(t) for _, t in pairs], dtype=np.int64)
@@ -40,7 +60,7 @@ def fill(pairs, bands, mode, match, mismatch, go, ge):
     B = int(W.max())
     nmax, mmax = int(ns.max()), int(ms.max())
     P = np.zeros((G, max(nmax, 1)), dtype=np.int16)
-    T = np.full((G, max(mmax, 1)), -1, dtype=np.int16)
+    T = np.full((G, max(mmax, 1)), -1, dtype=np.int16)   # (columns past a text are outside its matrix: masked by `inb`)
     for g, (p, t) in enumerate(pairs):
         P[g, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
         T[g, :len(t)] = np.frombuffer(bytes(t), dtype=np.uint8)
@@ -51,6 +71,8 @@ def fill(pairs, bands, mode, match, mismatch, go, ge):
     fop = np.zeros((G, nmax + 1, B), dtype=bool)
     hlast = np.full((G, B), NEG, dtype=np.int64)
     best = np.zeros((G, 3), dtype=np.int64)
+    rmax = np.full((G, nmax + 1), NEG, dtype=np.int64)
+    rcol = np.zeros((G, nmax + 1), dtype=np.int64)
     rows = np.arange(G)
     Hp = Fp = None
     for i in range(0, nmax + 1):
@@ -65,8 +87,7 @@ def fill(pairs, bands, mode, match, mismatch, go, ge):
             up_h = np.concatenate([Hp[:, 1:], np.full((G, 1), NEG, dtype=np.int64)], axis=1)   # (i - 1, j)
             up_f = np.concatenate([Fp[:, 1:], np.full((G, 1), NEG, dtype=np.int64)], axis=1)
             tsym = T[rows[:, None], np.clip(j - 1, 0, max(mmax, 1) - 1)]
-            s = np.where(P[:, i - 1:i] == tsym, match, mismatch).astype(np.int64)
-            diag = Hp + s                                                # (i - 1, j - 1): the same slot
+            diag = Hp + score(P[:, i - 1:i], tsym)                       # (i - 1, j - 1): the same slot
             fo, fe = up_h + oe, up_f + ge
             F = np.maximum(fo, fe)
             fopen = fo >= fe
@@ -94,6 +115,9 @@ def fill(pairs, bands, mode, match, mismatch, go, ge):
             else:
                 c = np.where(diag == H, SRC_D, np.where(E == H, SRC_E, SRC_F))
             src[:, i, :] = c
+            Hc = np.where(inb & (j >= 1) & (H > _LOW), H, NEG)
+            rmax[:, i] = Hc.max(axis=1)
+            rcol[:, i] = i + lo + np.argmax(Hc == rmax[:, i:i + 1], axis=1)
         if mode == "sw":
             rb = H.max(axis=1)
             better = rb > best[:, 0]
@@ -104,7 +128,7 @@ def fill(pairs, bands, mode, match, mismatch, go, ge):
         last = ns == i
         hlast[last] = H[last]
         Hp, Fp = H, F
-    return dict(src=src, eop=eop, fop=fop, hlast=hlast, best=best, lo=lo, W=W)
+    return dict(src=src, eop=eop, fop=fop, hlast=hlast, best=best, lo=lo, W=W, rmax=rmax, rcol=rcol)
 
 
 def walk(tab, g, mode, i, j):
@@ -158,7 +182,7 @@ def result(tab, g, mode, n, m, go, ge):
     return dict(score=score, end=end, start=start, ops=ops)
 
 
-def align_many(pairs, bands, mode, match, mismatch, go, ge, group=64):
+def align_many(pairs, bands, mode, sc, go, ge, group=64):
     """[(p, t)], [(lo, hi)] (valid bands) -> [dict(score, end, start, ops)]; pairs of similar pattern length are filled together"""
     out = [None] * len(pairs)
     live = [k for k, (p, t) in enumerate(pairs) if len(p) and len(t)]
@@ -168,14 +192,14 @@ def align_many(pairs, bands, mode, match, mismatch, go, ge, group=64):
     live.sort(key=lambda k: (len(pairs[k][0]), bands[k][1] - bands[k][0]))
     for a in range(0, len(live), group):
         kk = live[a:a + group]
-        tab = fill([pairs[k] for k in kk], [bands[k] for k in kk], mode, match, mismatch, go, ge)
+        tab = fill([pairs[k] for k in kk], [bands[k] for k in kk], mode, sc, go, ge)
         for g, k in enumerate(kk):
             out[k] = result(tab, g, mode, len(pairs[k][0]), len(pairs[k][1]), go, ge)
     return out
 
 
-def align(p, t, band, mode, match, mismatch, go, ge):
-    return align_many([(p, t)], [band], mode, match, mismatch, go, ge)[0]
+def align(p, t, band, mode, sc, go, ge):
+    return align_many([(p, t)], [band], mode, sc, go, ge)[0]
 
 
 def ops_in_band(ops, start, band):
@@ -208,8 +232,9 @@ def walk_diagonals(ops, start):
     return dmin, dmax
 
 
-def scalar_dp(p, t, band, mode, match, mismatch, go, ge):
+def scalar_dp(p, t, band, mode, sc, go, ge):
     """Plain three-matrix DP with a band mask and float -inf, cell by cell (small pairs) -> dict(score, end, start, ops)"""
+    cell = go_.scorer(sc)[1]
     n, m = len(p), len(t)
     lo, hi = band
     oe = go + ge
@@ -241,7 +266,7 @@ def scalar_dp(p, t, band, mode, match, mismatch, go, ge):
             E[i][j], eop[i][j] = (eo, True) if eo >= ee else (ee, False)
             fo, fe = H[i - 1][j] + oe, F[i - 1][j] + ge
             F[i][j], fop[i][j] = (fo, True) if fo >= fe else (fe, False)
-            d = H[i - 1][j - 1] + (match if p[i - 1] == t[j - 1] else mismatch)
+            d = H[i - 1][j - 1] + cell(p[i - 1], t[j - 1])
             if mode == "sw":
                 h = max(0, d, E[i][j], F[i][j])
                 src[i][j] = SRC_Z if h == 0 else SRC_D if d == h else SRC_F if F[i][j] == h else SRC_E

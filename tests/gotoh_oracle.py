@@ -5,7 +5,12 @@ SW: zero > diag > F > E.  Rows are computed one at a time for a group of same-sh
 chain is closed form: with gap_open <= 0, reopening a gap from an E-derived H is never better than extending it, so
     E[i][j] = (j - 1) * ge + oe + max_{k < j}(A[k] - k * ge),   A[k] = max(diag, F) at column k (SW: and 0), A[0] = H[i][0]
 and H = max(A, E).  The open / extend bits and the H source then follow from the values with the tie rules.  DP column j depends
-only on columns <= j: the tables of (p, t[:m']) are the first m' + 1 columns of those of (p, t) (`prefixes`)."""
+only on columns <= j: the tables of (p, t[:m']) are the first m' + 1 columns of those of (p, t) (`prefixes`).
+
+The scoring of a diagonal step is one value `sc`, here and in the banded oracles built on this module: a pair (match, mismatch)
+(pwa_align_gotoh_batch) or a substitution table (code[256], n_sym, submat) as subst_table returns it (pwa_align_subst_batch): row =
+pattern code, column = text code; the matrix may be asymmetric and hold any signs.  `scorer` is the only place that tells the two
+apart."""
 import numpy as np
 
 MODES = {"nw": 0, "sw": 1, "sg": 2}
@@ -17,9 +22,34 @@ def _arr(x):
     return np.frombuffer(bytes(x), dtype=np.uint8)
 
 
-def fill(P, T, mode, match, mismatch, go, ge):
-    """P: (B, n) uint8, T: (B, m) uint8 -> dict(H, src, eop, fop): H (B, n + 1, m + 1) int64; src the H source (uint8), eop / fop
+def scorer(sc):
+    """sc -> (row, cell): row(pattern symbols (B, 1), text symbols (B, m)) -> (B, m) int64 diagonal scores, cell(a, b) -> int.  A
+    banded fill pads its texts with -1 and its patterns with 0; those slots lie outside the matrix and the fill masks them: -1
+    equals no byte, and the table reads it as byte 0 and a byte without a code as the last symbol (`row` only: `cell` sees real
+    bytes, and one without a code is an error there)."""
+    if len(sc) == 2:
+        match, mismatch = sc
+        return (lambda pc, ts: np.where(pc == ts, match, mismatch).astype(np.int64)), (lambda a, b: match if a == b else mismatch)
+    code, n_sym, submat = sc
+    code, M = np.asarray(code, dtype=np.int64), np.asarray(submat, dtype=np.int64).reshape(n_sym, n_sym)
+    sym = lambda x: np.minimum(code[np.maximum(x, 0)], n_sym - 1)
+    return (lambda pc, ts: M[sym(pc), sym(ts)]), (lambda a, b: int(M[code[a], code[b]]))
+
+
+def random_table(seed, alphabet, lo=-9, hi=11, unknown=None, fold_case=False):
+    """an asymmetric matrix with entries in lo..hi, a positive diagonal and some positive off-diagonal entries, as a scoring value"""
+    from conftest import load_pkg
+    rng = np.random.RandomState(seed)
+    k = len(alphabet)
+    m = rng.randint(lo, hi + 1, size=(k, k))
+    m[np.arange(k), np.arange(k)] = rng.randint(1, hi + 1, size=k)
+    return load_pkg().subst_table(alphabet, m, unknown=unknown, fold_case=fold_case)
+
+
+def fill(P, T, mode, sc, go, ge):
+    """P: (B, n) uint8, T: (B, m) uint8 (raw bytes) -> dict(H, src, eop, fop): H (B, n + 1, m + 1) int64; src the H source (uint8), eop / fop
     whether E / F opened at the cell (bool); row 0 and column 0 hold the boundary values (src there is unused)."""
+    row = scorer(sc)[0]
     P, T = np.atleast_2d(P), np.atleast_2d(T)
     nb, n = P.shape
     m = T.shape[1]
@@ -36,8 +66,7 @@ def fill(P, T, mode, match, mismatch, go, ge):
     Fp = np.full((nb, m + 1), NEG, dtype=np.int64)   # F of row 0: -inf
     for i in range(1, n + 1):
         hp = H[:, i - 1, :]
-        s = np.where(P[:, i - 1:i] == T, match, mismatch).astype(np.int64)
-        diag = hp[:, :-1] + s
+        diag = hp[:, :-1] + row(P[:, i - 1:i], T)
         fo, fe = hp + oe, Fp + ge
         F = np.maximum(fo, fe)
         fopen = fo >= fe
@@ -136,20 +165,20 @@ def _one(tab, x):
     return {k: v[x] for k, v in tab.items()}
 
 
-def align(p, t, mode, match, mismatch, go, ge, want_ops=True):
+def align(p, t, mode, sc, go, ge, want_ops=True):
     p, t = _arr(p), _arr(t)
-    tab = fill(p[None, :], t[None, :], mode, match, mismatch, go, ge)
+    tab = fill(p[None, :], t[None, :], mode, sc, go, ge)
     return result(_one(tab, 0), mode, len(p), len(t), go, ge, want_ops)
 
 
-def prefixes(p, t, ms, mode, match, mismatch, go, ge, want_ops=True):
+def prefixes(p, t, ms, mode, sc, go, ge, want_ops=True):
     """(p, t[:m]) for every m in ms, from one fill of (p, t)"""
     p, t = _arr(p), _arr(t)
-    tab = _one(fill(p[None, :], t[None, :], mode, match, mismatch, go, ge), 0)
+    tab = _one(fill(p[None, :], t[None, :], mode, sc, go, ge), 0)
     return [result(tab, mode, len(p), m, go, ge, want_ops) for m in ms]
 
 
-def align_many(pairs, mode, match, mismatch, go, ge, want_ops=True, group=32):
+def align_many(pairs, mode, sc, go, ge, want_ops=True, group=32):
     """[(p, t)] -> [dict]; pairs of the same shape are filled together, `group` at a time"""
     out = [None] * len(pairs)
     by_shape = {}
@@ -160,14 +189,15 @@ def align_many(pairs, mode, match, mismatch, go, ge, want_ops=True, group=32):
             kk = ks[g:g + group]
             P = np.stack([_arr(pairs[k][0]) for k in kk]) if n else np.zeros((len(kk), 0), np.uint8)
             T = np.stack([_arr(pairs[k][1]) for k in kk]) if m else np.zeros((len(kk), 0), np.uint8)
-            tab = fill(P, T, mode, match, mismatch, go, ge)
+            tab = fill(P, T, mode, sc, go, ge)
             for x, k in enumerate(kk):
                 out[k] = result(_one(tab, x), mode, n, m, go, ge, want_ops)
     return out
 
 
-def op_score(p, t, ops, start, match, mismatch, go, ge):
+def op_score(p, t, ops, start, sc, go, ge):
     """The affine score of an op list (traceback order) from its start cell: every maximal run of 'I' or of 'D' is one gap."""
+    cell = scorer(sc)[1]
     i, j = start
     s, run, prev = 0, 0, None
     for o in reversed(bytes(ops)):
@@ -175,7 +205,7 @@ def op_score(p, t, ops, start, match, mismatch, go, ge):
             s += go + run * ge
             run = 0
         if o == 77:
-            s += match if p[i] == t[j] else mismatch
+            s += cell(p[i], t[j])
             i += 1
             j += 1
         else:
@@ -190,8 +220,9 @@ def op_score(p, t, ops, start, match, mismatch, go, ge):
     return s
 
 
-def scalar_dp(p, t, mode, match, mismatch, go, ge):
+def scalar_dp(p, t, mode, sc, go, ge):
     """Plain three-matrix DP with -inf, cell by cell (small pairs): -> (H, src, eop, fop) as lists of lists"""
+    cell = scorer(sc)[1]
     n, m = len(p), len(t)
     oe = go + ge
     inf = float("-inf")
@@ -211,7 +242,7 @@ def scalar_dp(p, t, mode, match, mismatch, go, ge):
             E[i][j], eop[i][j] = (eo, True) if eo >= ee else (ee, False)
             fo, fe = H[i - 1][j] + oe, F[i - 1][j] + ge
             F[i][j], fop[i][j] = (fo, True) if fo >= fe else (fe, False)
-            d = H[i - 1][j - 1] + (match if p[i - 1] == t[j - 1] else mismatch)
+            d = H[i - 1][j - 1] + cell(p[i - 1], t[j - 1])
             if mode == "sw":
                 h = max(0, d, E[i][j], F[i][j])
                 src[i][j] = SRC_Z if h == 0 else SRC_D if d == h else SRC_F if F[i][j] == h else SRC_E

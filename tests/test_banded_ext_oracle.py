@@ -44,10 +44,10 @@ def cases():
 @pytest.mark.parametrize("xdrop", XDROPS)
 def test_numpy_equals_scalar(cases, sc, xdrop):
     pairs, bands = cases
-    got = XO.extend_many(pairs, bands, *sc, xdrop)
+    got = XO.extend_many(pairs, bands, sc[:2], *sc[2:], xdrop)
     stopped = 0
     for k, ((p, t), band) in enumerate(zip(pairs, bands)):
-        want = XO.scalar_dp(p, t, band, *sc, xdrop)
+        want = XO.scalar_dp(p, t, band, sc[:2], *sc[2:], xdrop)
         assert got[k] == want, (k, p, t, band, sc, xdrop)
         stopped += want["rows"] < len(p)
     assert xdrop == 1 << 27 or stopped >= 10   # (the cases do stop early; with the largest drop only a band that leaves the matrix does)
@@ -56,11 +56,11 @@ def test_numpy_equals_scalar(cases, sc, xdrop):
 @pytest.mark.parametrize("sc", ALL_SCORINGS)
 def test_no_drop_is_the_banded_nw_score_where_it_ends_in_the_corner(cases, sc):
     pairs, bands = cases
-    got = XO.extend_many(pairs, bands, *sc, -1)
+    got = XO.extend_many(pairs, bands, sc[:2], *sc[2:], -1)
     hits = 0
     for k, ((p, t), band) in enumerate(zip(pairs, bands)):
         if BO.band_valid("nw", len(p), len(t), *band) and got[k]["end"] == (len(p), len(t)):
-            assert got[k]["score"] == BO.align(p, t, band, "nw", *sc)["score"], (k, band)
+            assert got[k]["score"] == BO.align(p, t, band, "nw", sc[:2], *sc[2:])["score"], (k, band)
             hits += 1
     assert hits >= 10
 
@@ -68,9 +68,9 @@ def test_no_drop_is_the_banded_nw_score_where_it_ends_in_the_corner(cases, sc):
 @pytest.mark.parametrize("sc", ALL_SCORINGS)
 def test_identity_1_score_is_the_maximum_over_the_band_with_zero(cases, sc):
     pairs, bands = cases
-    got = XO.extend_many(pairs, bands, *sc, -1)
+    got = XO.extend_many(pairs, bands, sc[:2], *sc[2:], -1)
     for k, ((p, t), band) in enumerate(zip(pairs, bands)):
-        H = XO.scalar_dp(p, t, band, *sc, -1, matrix=True)["H"]
+        H = XO.scalar_dp(p, t, band, sc[:2], *sc[2:], -1, matrix=True)["H"]
         cells = [H[i][j] for i in range(1, len(p) + 1) for j in range(1, len(t) + 1) if band[0] <= j - i <= band[1]]
         assert got[k]["score"] == max(cells + [0]), (k, band)
 
@@ -79,8 +79,8 @@ def test_identity_1_score_is_the_maximum_over_the_band_with_zero(cases, sc):
 @pytest.mark.parametrize("xdrop", [0, 3, 10])
 def test_identity_2_a_stop_below_the_end_row_changes_nothing(cases, sc, xdrop):
     pairs, bands = cases
-    free = XO.extend_many(pairs, bands, *sc, -1)
-    got = XO.extend_many(pairs, bands, *sc, xdrop)
+    free = XO.extend_many(pairs, bands, sc[:2], *sc[2:], -1)
+    got = XO.extend_many(pairs, bands, sc[:2], *sc[2:], xdrop)
     same = 0
     for k, (f, g) in enumerate(zip(free, got)):
         assert g["rows"] <= f["rows"], k
@@ -94,9 +94,9 @@ def test_identity_2_a_stop_below_the_end_row_changes_nothing(cases, sc, xdrop):
 
 def test_empty_sides_and_the_anchor():
     z = dict(score=0, end=(0, 0), start=(0, 0), ops=b"", rows=0)
-    for p, t in [(b"", b""), (b"ACG", b""), (b"", b"ACG")]:
-        assert XO.extend(p, t, (0, 0), 1, -4, -6, -1, 5) == z == XO.scalar_dp(p, t, (0, 0), 1, -4, -6, -1, 5)
+    for p, t, pend in [(b"", b"", (0, 0)), (b"ACG", b"", None), (b"", b"ACG", (0, 0))]:
+        assert XO.extend(p, t, (0, 0), (1, -4), -6, -1, 5) == dict(z, pend=pend) == XO.scalar_dp(p, t, (0, 0), (1, -4), -6, -1, 5)
     # first symbols differ: nothing beats the anchor
-    r = XO.extend(b"AAAA", b"CAAA", (-1, 1), 1, -4, -6, -1, -1)
+    r = XO.extend(b"AAAA", b"CAAA", (-1, 1), (1, -4), -6, -1, -1)
     assert (r["score"], r["end"], r["ops"]) == (0, (0, 0), b"")
     assert XO.band_valid(3, 3, -1, 0) and not XO.band_valid(3, 3, 1, 2) and not XO.band_valid(3, 3, -2, -1)

@@ -1,5 +1,5 @@
-"""The four banded numpy oracles at the int32 range limits of the calls they restate, without a GPU: banded_oracle, banded_subst_oracle,
-banded_ext_oracle and banded_ext_subst_oracle against their own scalar_dp on small pairs under the at-the-bound scorings that
+"""The banded numpy oracles at the int32 range limits of the four calls they restate, without a GPU: banded_oracle and banded_ext_oracle,
+each under match / mismatch and under a substitution table, against their own scalar_dp on small pairs under the at-the-bound scorings that
 test_gpu_banded_limits.py runs on the device -- A = top(n, m, 28) for the alignment calls and top(n, m, 27) for EXT, A as validate_align
 (pwalign_align.hip) computes it.  The device tests lean on the numpy forms at these magnitudes, where nothing had compared them yet.
 
@@ -13,9 +13,7 @@ import numpy as np
 import pytest
 
 import banded_ext_oracle as XO
-import banded_ext_subst_oracle as XSO
 import banded_oracle as BO
-import banded_subst_oracle as BSO
 from conftest import load_pkg
 
 MODES = ["nw", "sw", "sg"]
@@ -84,10 +82,11 @@ def _bands(n, m, valid):
 def test_the_scalar_dps_hold_python_ints():
     t = top(24, 24, 27)
     p, q = _pairs(24, 24)[1]
-    H = XSO.scalar_dp(p, q, (-3, 3), asym_table(t, 3), -(t // 2), -(t - t // 2), -1, matrix=True)["H"]
+    H = XO.scalar_dp(p, q, (-3, 3), asym_table(t, 3), -(t // 2), -(t - t // 2), -1, matrix=True)["H"]
     cells = [v for row in H for v in row]
     assert all(type(v) is int or v == float("-inf") for v in cells) and sum(type(v) is int for v in cells) > 100
-    for r in (BO.scalar_dp(p, q, (-3, 3), "nw", *scoring("positive", t)), XO.scalar_dp(p, q, (-3, 3), *scoring("negative", t), 10)):
+    pos, neg = scoring("positive", t), scoring("negative", t)
+    for r in (BO.scalar_dp(p, q, (-3, 3), "nw", pos[:2], *pos[2:]), XO.scalar_dp(p, q, (-3, 3), neg[:2], *neg[2:], 10)):
         assert type(r["score"]) is int
 
 
@@ -103,12 +102,12 @@ def test_banded_and_banded_subst_equal_scalar_at_the_2_28_bound(mode, kind):
         pairs = [pt for pt in _pairs(n, m) for _ in named]
         bands = [b for _ in _pairs(n, m) for _, b in named]
         widths |= {w for w, _ in named}
-        got = BO.align_many(pairs, bands, mode, *sc)
-        gots = BSO.align_many(pairs, bands, mode, table, sc[2], sc[3])
+        got = BO.align_many(pairs, bands, mode, sc[:2], *sc[2:])
+        gots = BO.align_many(pairs, bands, mode, table, sc[2], sc[3])
         for k, ((p, q), band) in enumerate(zip(pairs, bands)):
-            want = BO.scalar_dp(p, q, band, mode, *sc)
+            want = BO.scalar_dp(p, q, band, mode, sc[:2], *sc[2:])
             assert got[k] == want, (n, m, band, sc)
-            assert gots[k] == want == BSO.scalar_dp(p, q, band, mode, table, sc[2], sc[3]), (n, m, band, sc)
+            assert gots[k] == want == BO.scalar_dp(p, q, band, mode, table, sc[2], sc[3]), (n, m, band, sc)
             reach = max(reach, abs(want["score"]))
     assert widths == {"1", "7", "full"}
     if kind != "extend0" and (mode != "sw" or kind == "positive"):   # (where a gap run costs per symbol, and SW's floor is not the answer)
@@ -124,9 +123,9 @@ def test_banded_subst_equals_scalar_under_an_asymmetric_table_at_the_bound(mode)
         for go, ge in [(-(t // 3), -(t - t // 3)), (0, -t), (-t, 0)]:
             pairs = [pt for pt in _pairs(n, m) for _ in named]
             bands = [b for _ in _pairs(n, m) for _, b in named]
-            got = BSO.align_many(pairs, bands, mode, table, go, ge)
+            got = BO.align_many(pairs, bands, mode, table, go, ge)
             for k, ((p, q), band) in enumerate(zip(pairs, bands)):
-                assert got[k] == BSO.scalar_dp(p, q, band, mode, table, go, ge), (n, m, band, go, ge)
+                assert got[k] == BO.scalar_dp(p, q, band, mode, table, go, ge), (n, m, band, go, ge)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -140,14 +139,14 @@ def test_ext_and_ext_subst_equal_scalar_at_the_2_27_bound(kind):
         pairs = [pt for pt in _pairs(n, m) for _ in named]
         bands = [b for _ in _pairs(n, m) for _, b in named]
         widths |= {w for w, _ in named}
-        got = XO.extend_multi(pairs, bands, *sc, XDROPS)
-        gots = XSO.extend_multi(pairs, bands, table, sc[2], sc[3], XDROPS)
+        got = XO.extend_multi(pairs, bands, sc[:2], *sc[2:], XDROPS)
+        gots = XO.extend_multi(pairs, bands, table, sc[2], sc[3], XDROPS)
         for xdrop in XDROPS:
             for k, ((p, q), band) in enumerate(zip(pairs, bands)):
-                want = XSO.scalar_dp(p, q, band, table, sc[2], sc[3], xdrop)
+                want = XO.scalar_dp(p, q, band, table, sc[2], sc[3], xdrop)
                 assert gots[xdrop][k] == want, (n, m, band, sc, xdrop)
-                pend = want.pop("pend")
-                assert got[xdrop][k] == want == XO.scalar_dp(p, q, band, *sc, xdrop), (n, m, band, sc, xdrop)
+                pend = want["pend"]   # (compared with every other key: the byte compare gives the table's pattern end)
+                assert got[xdrop][k] == want == XO.scalar_dp(p, q, band, sc[:2], *sc[2:], xdrop), (n, m, band, sc, xdrop)
                 reach = max(reach, want["score"])
                 low = min(low, pend[0] if pend else 0)
     assert widths == {"1", "7", "full"}
@@ -162,7 +161,7 @@ def test_ext_subst_equals_scalar_under_an_asymmetric_and_an_all_negative_table_a
         pairs = [pt for pt in _pairs(n, m) for _ in named]
         bands = [b for _ in _pairs(n, m) for _, b in named]
         for table, go, ge in [(asym_table(t, n + m), -(t // 3), -(t - t // 3)), (load_pkg().subst_table(b"ACGT", np.full((4, 4), -t)), 0, -t)]:
-            got = XSO.extend_multi(pairs, bands, table, go, ge, XDROPS)
+            got = XO.extend_multi(pairs, bands, table, go, ge, XDROPS)
             for xdrop in XDROPS:
                 for k, ((p, q), band) in enumerate(zip(pairs, bands)):
-                    assert got[xdrop][k] == XSO.scalar_dp(p, q, band, table, go, ge, xdrop), (n, m, band, go, ge, xdrop)
+                    assert got[xdrop][k] == XO.scalar_dp(p, q, band, table, go, ge, xdrop), (n, m, band, go, ge, xdrop)

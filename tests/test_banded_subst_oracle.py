@@ -1,17 +1,15 @@
-"""The banded substitution-matrix oracle (banded_subst_oracle.py) against a scalar three-matrix DP with a band mask, float -inf and the
-table; against banded_oracle where the table is match on the diagonal and mismatch off it; and against subst_oracle where the band
-covers the whole matrix."""
+"""The banded oracle (banded_oracle.py) under a substitution table against a scalar three-matrix DP with a band mask, float -inf and the
+table; against its own byte compare where the table is match on the diagonal and mismatch off it; and against gotoh_oracle under the
+same table where the band covers the whole matrix."""
 import random
 
 import numpy as np
 import pytest
 
 import banded_oracle as BO
-import banded_subst_oracle as BSO
-import subst_oracle as SO
+import gotoh_oracle as GO
 from conftest import load_pkg
-from test_banded_oracle import _valid_band
-from test_subst_oracle import random_table
+from gotoh_oracle import random_table
 
 MODES = ["nw", "sw", "sg"]
 GAPS = [(-5, -2), (-1, -1), (0, -3)]
@@ -42,14 +40,14 @@ def test_against_scalar_dp(mode, gaps):
     M = np.asarray(table[2]).reshape(4, 4)
     assert (M != M.T).any() and (M[~np.eye(4, dtype=bool)] > 0).any()
     pairs = _pairs(rng, 150, lo_len=0)
-    bands = [_valid_band(rng, mode, len(p), len(t)) for p, t in pairs]
+    bands = [BO.random_band(rng, mode, len(p), len(t)) for p, t in pairs]
     assert any(lo == hi for lo, hi in bands)
-    got = BSO.align_many(pairs, bands, mode, table, *gaps)
+    got = BO.align_many(pairs, bands, mode, table, *gaps)
     for (p, t), b, g in zip(pairs, bands, got):
-        assert g == BSO.scalar_dp(p, t, b, mode, table, *gaps), (mode, p, t, b)
+        assert g == BO.scalar_dp(p, t, b, mode, table, *gaps), (mode, p, t, b)
         if len(p) and len(t) and (mode != "sw" or g["ops"]):
             assert BO.ops_in_band(g["ops"], g["start"], b)
-            assert SO.op_score(p, t, g["ops"], g["start"], table, *gaps) == g["score"]
+            assert GO.op_score(p, t, g["ops"], g["start"], table, *gaps) == g["score"]
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -59,8 +57,8 @@ def test_match_mismatch_table_is_the_banded_oracle(mode, sc):
     table = load_pkg().subst_table(ALPHA, np.where(np.eye(4, dtype=bool), match, mismatch))
     rng = random.Random(3 + MODES.index(mode))
     pairs = _pairs(rng, 120, lo_len=0)
-    bands = [_valid_band(rng, mode, len(p), len(t)) for p, t in pairs]
-    assert BSO.align_many(pairs, bands, mode, table, go, ge) == BO.align_many(pairs, bands, mode, match, mismatch, go, ge)
+    bands = [BO.random_band(rng, mode, len(p), len(t)) for p, t in pairs]
+    assert BO.align_many(pairs, bands, mode, table, go, ge) == BO.align_many(pairs, bands, mode, (match, mismatch), go, ge)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -70,4 +68,4 @@ def test_full_cover_is_the_subst_oracle(mode, gaps):
     rng = random.Random(5 + MODES.index(mode))
     pairs = _pairs(rng, 120, lo_len=0)
     bands = [(-len(p), len(t)) for p, t in pairs]
-    assert BSO.align_many(pairs, bands, mode, table, *gaps) == SO.align_many(pairs, mode, table, *gaps)
+    assert BO.align_many(pairs, bands, mode, table, *gaps) == GO.align_many(pairs, mode, table, *gaps)

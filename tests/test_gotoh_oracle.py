@@ -29,8 +29,8 @@ def test_oracle_matches_scalar_dp(mode, sc):
     for _ in range(12):
         n, m = rng.randint(1, 14), rng.randint(1, 14)
         p, t = _rand(rng, n, b"AC"), _rand(rng, m, b"ACG")
-        tab = GO.fill(GO._arr(p)[None, :], GO._arr(t)[None, :], mode, match, mismatch, go, ge)
-        H, src, eop, fop = GO.scalar_dp(p, t, mode, match, mismatch, go, ge)
+        tab = GO.fill(GO._arr(p)[None, :], GO._arr(t)[None, :], mode, (match, mismatch), go, ge)
+        H, src, eop, fop = GO.scalar_dp(p, t, mode, (match, mismatch), go, ge)
         assert tab["H"][0].tolist() == H
         for i in range(1, n + 1):
             for j in range(1, m + 1):
@@ -45,8 +45,8 @@ def test_op_scores_equal_scores(mode, sc):
     rng = random.Random(7 + len(mode))
     match, mismatch, go, ge = sc
     pairs = [(_rand(rng, rng.randint(0, 40)), _rand(rng, rng.randint(0, 60))) for _ in range(40)]
-    for (p, t), r in zip(pairs, GO.align_many(pairs, mode, match, mismatch, go, ge)):
-        assert GO.op_score(p, t, r["ops"], r["start"], match, mismatch, go, ge) == r["score"]
+    for (p, t), r in zip(pairs, GO.align_many(pairs, mode, (match, mismatch), go, ge)):
+        assert GO.op_score(p, t, r["ops"], r["start"], (match, mismatch), go, ge) == r["score"]
         n_m = sum(1 for o in r["ops"] if o in (77, 68))
         assert r["start"][0] + n_m == r["end"][0]
 
@@ -59,7 +59,7 @@ def test_gap_open_zero_is_the_linear_mode(mode, sc):
     for _ in range(25):
         p, t = _rand(rng, rng.randint(1, 50)), _rand(rng, rng.randint(1, 70))
         want = O.align(mode, p, t, match, mismatch, gap)
-        got = GO.align(p, t, mode, match, mismatch, 0, gap)
+        got = GO.align(p, t, mode, (match, mismatch), 0, gap)
         assert got["score"] == want["score"]
         assert got["ops"] == want["ops"]
         assert got["end"] == tuple(want["end"])
@@ -72,7 +72,7 @@ def test_gap_open_zero_is_semiglobal(sc):
     for _ in range(25):
         p, t = _rand(rng, rng.randint(1, 40)), _rand(rng, rng.randint(1, 90))
         want = SG.align(p, t, match, mismatch, gap)
-        got = GO.align(p, t, "sg", match, mismatch, 0, gap)
+        got = GO.align(p, t, "sg", (match, mismatch), 0, gap)
         assert (got["score"], got["end"], got["start"], got["ops"]) == (want["score"], want["end"], want["start"], want["ops"])
 
 
@@ -81,8 +81,8 @@ def test_prefixes_equal_own_fills():
     p, t = _rand(rng, 30), _rand(rng, 80)
     for mode in ("nw", "sw", "sg"):
         ms = [0, 1, 17, 50, 80]
-        for m, r in zip(ms, GO.prefixes(p, t, ms, mode, 2, -3, -5, -2)):
-            assert r == GO.align(p, t[:m], mode, 2, -3, -5, -2)
+        for m, r in zip(ms, GO.prefixes(p, t, ms, mode, (2, -3), -5, -2)):
+            assert r == GO.align(p, t[:m], mode, (2, -3), -5, -2)
 
 
 def test_one_event_is_one_gap():
@@ -90,7 +90,7 @@ def test_one_event_is_one_gap():
     rng = random.Random(3)
     region = _rand(rng, 400)
     read = region[100:160] + region[172:250]   # 12 bases deleted
-    r = GO.align(read, region, "sg", 1, -4, -6, -1)
+    r = GO.align(read, region, "sg", (1, -4), -6, -1)
     ops = bytes(reversed(r["ops"]))
     assert b"I" * 12 in ops and ops.count(b"I") == 12 and b"D" not in ops
     assert r["score"] == len(read) - 6 - 12
@@ -100,7 +100,7 @@ def _rule_walk(p, t, mode, match, mismatch, go, ge):
     """pwalign.h's end cell and three-state walk, written from the stated rules over scalar_dp's H alone: E and F are recomputed
     from H, every choice is made from values (no source or open codes) -> (score, end, start, ops)"""
     n, m = len(p), len(t)
-    H = GO.scalar_dp(p, t, mode, match, mismatch, go, ge)[0]
+    H = GO.scalar_dp(p, t, mode, (match, mismatch), go, ge)[0]
     oe, inf = go + ge, float("-inf")
     E = [[inf] * (m + 1) for _ in range(n + 1)]
     F = [[inf] * (m + 1) for _ in range(n + 1)]
@@ -165,7 +165,7 @@ def test_walk_tie_breaks_follow_the_stated_rules(mode, sc):
     the rule walk above, field for field"""
     match, mismatch, go, ge = sc
     for p, t in _homopolymer_cases():
-        r = GO.align(p, t, mode, match, mismatch, go, ge)
+        r = GO.align(p, t, mode, (match, mismatch), go, ge)
         score, end, start, ops = _rule_walk(p, t, mode, match, mismatch, go, ge)
         assert (r["score"], r["end"], r["start"], r["ops"]) == (score, end, start, ops), (p, t)
 
@@ -174,7 +174,7 @@ def test_homopolymer_gap_sits_at_the_run_start():
     """the walk runs backwards and prefers the diagonal, so a gap in a run lands at its first base (forward order); global and
     semi-global (a local alignment of these drops the gap)"""
     for mode in ("nw", "sg"):
-        r = GO.align(b"ACGTTTTTCA", b"ACGTTTTTTTCA", mode, 1, -4, -6, -1)
+        r = GO.align(b"ACGTTTTTCA", b"ACGTTTTTTTCA", mode, (1, -4), -6, -1)
         assert bytes(reversed(r["ops"])) == b"MMMIIMMMMMMM", mode
-        r = GO.align(b"ACGTTTTTTTCA", b"ACGTTTTTCA", mode, 1, -4, -6, -1)
+        r = GO.align(b"ACGTTTTTTTCA", b"ACGTTTTTCA", mode, (1, -4), -6, -1)
         assert bytes(reversed(r["ops"])) == b"MMMDDMMMMMMM", mode

@@ -88,7 +88,7 @@ def hctx(request):
 @pytest.mark.parametrize("alpha,sc", [("dna", SCORINGS[0]), ("dna", SCORINGS[1]), ("bytes", SCORINGS[0])])
 def test_shapes_against_oracle(hctx, mode, alpha, sc):
     pairs, bands = _shape_cases(mode, HEIGHTS[hctx.rl], ALPHABETS[alpha], 7 * hctx.rl + len(alpha))
-    want = BO.align_many(pairs, bands, mode, *sc, group=24)
+    want = BO.align_many(pairs, bands, mode, sc[:2], *sc[2:], group=24)
     _check(_call(hctx, mode, pairs, bands, sc), _call(hctx, mode, pairs, bands, sc, cigar=True), want, pairs, bands, (mode, hctx.rl))
 
 
@@ -126,7 +126,7 @@ def path_cover_set():
         t = _text_for(rng, p, 1500, b"ACGT")
         pairs.append((p, t))
     sc = (1, -4, -6, -1)
-    return pairs, sc, {mode: GO.align_many(pairs, mode, *sc) for mode in ("nw", "sw", "sg")}
+    return pairs, sc, {mode: GO.align_many(pairs, mode, sc[:2], *sc[2:]) for mode in ("nw", "sw", "sg")}
 
 
 @pytest.mark.parametrize("mode", ["nw", "sw", "sg"])
@@ -144,11 +144,11 @@ def test_path_cover(ctx, path_cover_set, mode):
     assert len(ks) >= 16   # (how many bands can lose 3 diagonals a side and stay valid is a property of the data alone)
     sp, sb = [pairs[k] for k in ks], [(tight[k][0] + 3, tight[k][1] - 3) for k in ks]
     got = _call(ctx, mode, sp, sb, sc)
-    wantb = BO.align_many(sp, sb, mode, *sc)
+    wantb = BO.align_many(sp, sb, mode, sc[:2], *sc[2:])
     for x, k in enumerate(ks):
         g, (p, t) = got[x], sp[x]
         assert g["score"] <= want[k]["score"], (mode, k)
-        assert GO.op_score(p, t, g["ops"], g["start"], *sc) == g["score"], (mode, k)
+        assert GO.op_score(p, t, g["ops"], g["start"], sc[:2], *sc[2:]) == g["score"], (mode, k)
         assert mode == "sw" and not g["ops"] or BO.ops_in_band(g["ops"], g["start"], sb[x]), (mode, k)
         assert g == wantb[x], (mode, k, sb[x])
 
@@ -174,7 +174,7 @@ def test_stripe_and_edge_stress(hctx):
         pairs.append((p, t))
         bands.append((0, w))
         toks.append([b"%dI" % w, b"%dD" % w])
-    want = BO.align_many(pairs, bands, "nw", *sc)
+    want = BO.align_many(pairs, bands, "nw", sc[:2], *sc[2:])
     got, gc = _call(hctx, "nw", pairs, bands, sc), _call(hctx, "nw", pairs, bands, sc, cigar=True)
     _check(got, gc, want, pairs, bands, ("stress", hctx.rl))
     for c, tk in zip(gc, toks):
@@ -192,9 +192,9 @@ def test_widest_band(ctx):
     band = (-2100, MAX_WIDTH - 2101)
     assert band[1] - band[0] + 1 == MAX_WIDTH and -2200 <= band[0] and band[1] <= 2150
     sc = (1, -4, -6, -1)
-    want = BO.align(p, t, band, "nw", *sc)
+    want = BO.align(p, t, band, "nw", sc[:2], *sc[2:])
     assert _call(ctx, "nw", [(p, t)], [band], sc)[0] == want
-    assert _call(ctx, "sw", [(p, t)], [band], sc)[0] == BO.align(p, t, band, "sw", *sc)
+    assert _call(ctx, "sw", [(p, t)], [band], sc)[0] == BO.align(p, t, band, "sw", sc[:2], *sc[2:])
 
 
 def test_long_pair(ctx, pkg):
@@ -216,7 +216,7 @@ def test_long_pair(ctx, pkg):
     band = pkg.band_around(20000, 20000, 100)
     sc = (1, -4, -6, -1)
     got = _call(ctx, "nw", [(p, t)], [band], sc)[0]
-    assert got == BO.align(p, t, band, "nw", *sc)
+    assert got == BO.align(p, t, band, "nw", sc[:2], *sc[2:])
 
 
 def test_seeded_semiglobal_reads(ctx, pkg):
@@ -233,9 +233,9 @@ def test_seeded_semiglobal_reads(ctx, pkg):
         bands.append(pkg.band_around(len(read), 4000, 60, diag=d))
     got = _call(ctx, "sg", pairs, bands, sc)
     for k, g in enumerate(got):
-        assert GO.op_score(pairs[k][0], pairs[k][1], g["ops"], g["start"], *sc) == g["score"], k
+        assert GO.op_score(pairs[k][0], pairs[k][1], g["ops"], g["start"], sc[:2], *sc[2:]) == g["score"], k
     ks = list(range(0, 2048, 37))
-    want = BO.align_many([pairs[k] for k in ks], [bands[k] for k in ks], "sg", *sc)
+    want = BO.align_many([pairs[k] for k in ks], [bands[k] for k in ks], "sg", sc[:2], *sc[2:])
     for x, k in enumerate(ks):
         assert got[k] == want[x], (k, bands[k])
 
@@ -275,9 +275,9 @@ def test_mixed_batch(ctx, mode):
         p, t = pairs[k]
         if not (len(p) and len(t)):
             assert g == GO.result(None, mode, len(p), len(t), sc[2], sc[3]), k
-        assert GO.op_score(p, t, g["ops"], g["start"], *sc) == g["score"], (k, bands[k])
+        assert GO.op_score(p, t, g["ops"], g["start"], sc[:2], *sc[2:]) == g["score"], (k, bands[k])
     ks = list(range(1, 4096, 29))
-    want = BO.align_many([pairs[k] for k in ks], [bands[k] for k in ks], mode, *sc, group=16)
+    want = BO.align_many([pairs[k] for k in ks], [bands[k] for k in ks], mode, sc[:2], *sc[2:], group=16)
     for x, k in enumerate(ks):
         assert got[k] == want[x], (k, len(pairs[k][0]), len(pairs[k][1]), bands[k])
     st = ctx.align_banded_stats()
@@ -305,7 +305,7 @@ def test_errors(pkg, ctx):
     assert run("sw", (3, 5))[0]["score"] >= 0
     with pytest.raises(pkg.PwaError, match="wider"):
         run("nw", (-1, MAX_WIDTH - 1))
-    assert run("nw", (-1, MAX_WIDTH - 2))[0] == GO.align(A, Bq, "nw", 1, -1, -2, -1)
+    assert run("nw", (-1, MAX_WIDTH - 2))[0] == GO.align(A, Bq, "nw", (1, -1), -2, -1)
     with pytest.raises(pkg.PwaError, match="INVALID|invalid|gap"):
         run("nw", (-2, 4), sc=(1, -1, 1, -1))
     with pytest.raises(pkg.PwaError, match="range"):

@@ -38,6 +38,11 @@ def _scores(c, pairs, bands, sc, xdrop, want_end=True):
     return c.scores_extend_banded(seqs, pa, pb, *sc, bands, xdrop, want_end=want_end)
 
 
+def _whole(pairs, bands, sc, xdrop, **kw):
+    """the oracle's results as pwa_extend_banded_batch returns them: every key but the pattern end, which that call does not have"""
+    return [{k: v for k, v in w.items() if k != "pend"} for w in XO.extend_many(pairs, bands, sc[:2], *sc[2:], xdrop, **kw)]
+
+
 def _check(c, pairs, bands, sc, xdrop, want, tag):
     """test_gpu_banded._check with start = (0, 0) and rows: the op-list call, the string call and the scores call"""
     got, gc = _call(c, pairs, bands, sc, xdrop), _call(c, pairs, bands, sc, xdrop, cigar=True)
@@ -80,7 +85,7 @@ def _shape_cases(S, alpha, seed):
 @pytest.mark.parametrize("alpha,sc", [("dna", SCORINGS[0]), ("dna", SCORINGS[1]), ("bytes", SCORINGS[0])])
 def test_shapes_against_oracle(hctx, alpha, sc):
     pairs, bands = _shape_cases(HEIGHTS[hctx.rl], ALPHABETS[alpha], 11 * hctx.rl + len(alpha))
-    want = XO.extend_multi(pairs, bands, *sc, [-1, 30], group=24)
+    want = XO.extend_multi(pairs, bands, sc[:2], *sc[2:], [-1, 30], group=24)
     for xdrop in (-1, 30):
         _check(hctx, pairs, bands, sc, xdrop, want[xdrop], ("shapes", hctx.rl))
     assert any(w["rows"] < len(p) for w, (p, t) in zip(want[30], pairs))   # (the drop does stop some of them)
@@ -97,7 +102,7 @@ def test_stop_rows_at_the_stripe_edges(hctx):
         for tries in range(8):   # (a chance match at the seam can move the stop by a row: draw X again)
             x = _rand(rng, rows - 14, b"ACGT")
             pair, band = (x + b"A" * 600, x + b"C" * 600), (-32, 32)
-            w = XO.extend(*pair, band, *SC, 20)
+            w = XO.extend(*pair, band, SC[:2], *SC[2:], 20)
             if w["rows"] == rows:
                 break
         pairs.append(pair)
@@ -112,7 +117,7 @@ def test_the_drop_changes_the_answer(hctx):
     rng = random.Random(73)
     x, y = _rand(rng, 200, b"ACGT"), _rand(rng, 600, b"ACGT")
     pair, band = (x + _rand(rng, 60, b"AC") + y, x + _rand(rng, 60, b"GT") + y), (-40, 40)   # R1, R2 share no symbol
-    want = XO.extend_multi([pair], [band], *SC, [30, -1])
+    want = XO.extend_multi([pair], [band], SC[:2], *SC[2:], [30, -1])
     stop, free = want[30][0], want[-1][0]
     assert (stop["score"], stop["end"]) == (200, (200, 200)) and 200 < stop["rows"] < 260
     assert free["end"] == (860, 860) and free["score"] > 200 and free["rows"] == 860
@@ -129,10 +134,10 @@ def test_ties_and_the_anchor(hctx):
     pairs.append((b"G" + x, b"C" + x))
     bands.append((-5, 5))
     for xdrop in (-1, 3):
-        want = XO.extend_many(pairs[:1], bands[:1], *SC, xdrop)
+        want = XO.extend_many(pairs[:1], bands[:1], SC[:2], *SC[2:], xdrop)
         assert want[0]["end"] == (300, 300) and want[0]["score"] == 300
         _check(hctx, pairs[:1], bands[:1], SC, xdrop, want, ("ties", hctx.rl))
-    want = XO.extend_many(pairs[1:], bands[1:], *SC, 3)
+    want = XO.extend_many(pairs[1:], bands[1:], SC[:2], *SC[2:], 3)
     assert (want[0]["score"], want[0]["end"], want[0]["ops"]) == (0, (0, 0), b"")
     got = _check(hctx, pairs[1:], bands[1:], SC, 3, want, ("anchor", hctx.rl))
     assert _call(hctx, pairs[1:], bands[1:], SC, 3, cigar=True)[0]["cigar"] == b"" and got[0]["ops"] == b""
@@ -141,7 +146,7 @@ def test_ties_and_the_anchor(hctx):
     seqs, pa, pb = _seqs(pairs)
     sw = hctx.scores_banded("sw", seqs, pa, pb, *SC, bands)
     for xdrop in (-1, 30):
-        want = XO.extend_many(pairs, bands, *SC, xdrop)
+        want = XO.extend_many(pairs, bands, SC[:2], *SC[2:], xdrop)
         got = _check(hctx, pairs, bands, SC, xdrop, want, ("off-anchor", hctx.rl))
         assert got[0]["score"] < sw[0] == 300
 
@@ -162,7 +167,7 @@ def test_scores_equal_alignments(ctx, xdrop):
     assert [(g["score"], g["end"], g["rows"]) for g in got] == list(zip(s, zip(ei, ej), rw))
     assert _scores(ctx, pairs, bands, sc, xdrop, want_end=False) == s
     ks = list(range(0, 300, 13))
-    want = XO.extend_many([pairs[k] for k in ks], [bands[k] for k in ks], *sc, xdrop, group=8)
+    want = _whole([pairs[k] for k in ks], [bands[k] for k in ks], sc, xdrop, group=8)
     for x, k in enumerate(ks):
         assert got[k] == want[x], (k, len(pairs[k][0]), len(pairs[k][1]), bands[k])
 
@@ -174,7 +179,7 @@ def test_widest_band(ctx):
     t = _text_for(rng, p, 2150, b"ACGT")
     band = (-2100, MAX_WIDTH - 2101)
     assert band[1] - band[0] + 1 == MAX_WIDTH and band[0] <= 0 <= band[1]
-    want = XO.extend_multi([(p, t)], [band], *SC, [-1, 40])
+    want = XO.extend_multi([(p, t)], [band], SC[:2], *SC[2:], [-1, 40])
     for xdrop in (-1, 40):
         _check(ctx, [(p, t)], [band], SC, xdrop, want[xdrop], "widest")
 
@@ -185,7 +190,7 @@ def test_empty_sides_and_empty_list(ctx):
     bands = [(-3, 0), (0, 5), (0, 0), (-4, 4)]
     zero = dict(score=0, ops=b"", end=(0, 0), start=(0, 0), rows=0)
     for xdrop in (-1, 5):
-        want = XO.extend_many(pairs, bands, *sc, xdrop)
+        want = _whole(pairs, bands, sc, xdrop)
         assert want[:3] == [zero] * 3 and want[3]["score"] == 3
         got = _check(ctx, pairs, bands, sc, xdrop, want, "empty")
         assert got[:3] == [zero] * 3
@@ -203,7 +208,7 @@ def test_errors(pkg, ctx):
     def run(band, sc=(1, -1, -2, -1), xdrop=10, seqs=(A, Bq)):
         return ctx.extend_banded_batch(list(seqs), [0], [1], *sc, [band], xdrop)
     good = run((-2, 4))
-    assert good == XO.extend_many([(A, Bq)], [(-2, 4)], 1, -1, -2, -1, 10)
+    assert good == _whole([(A, Bq)], [(-2, 4)], (1, -1, -2, -1), 10)
     stats = ctx.extend_banded_stats()
     assert stats["rows_considered"] == good[0]["rows"] and stats["fill_ms"] > 0 and stats["walk_ms"] > 0
     with pytest.raises(pkg.PwaError, match="band_lo > band_hi"):
@@ -213,12 +218,12 @@ def test_errors(pkg, ctx):
             run(band)
     with pytest.raises(pkg.PwaError, match="wider"):
         run((-1, MAX_WIDTH - 1))
-    assert run((-1, MAX_WIDTH - 2)) == XO.extend_many([(A, Bq)], [(-1, MAX_WIDTH - 2)], 1, -1, -2, -1, 10)
+    assert run((-1, MAX_WIDTH - 2)) == _whole([(A, Bq)], [(-1, MAX_WIDTH - 2)], (1, -1, -2, -1), 10)
     with pytest.raises(pkg.PwaError, match="INVALID|invalid|gap"):
         run((-2, 4), sc=(1, -1, 1, -1))
     with pytest.raises(pkg.PwaError, match="xdrop"):
         run((-2, 4), xdrop=(1 << 27) + 1)
-    assert run((-2, 4), xdrop=1 << 27) == XO.extend_many([(A, Bq)], [(-2, 4)], 1, -1, -2, -1, 1 << 27)
+    assert run((-2, 4), xdrop=1 << 27) == _whole([(A, Bq)], [(-2, 4)], (1, -1, -2, -1), 1 << 27)
     # beyond EXT's 2^27 range rule, inside the banded rule's 2^28: 24 * 2^23 = 1.5 * 2^27
     with pytest.raises(pkg.PwaError, match="range"):
         run((-2, 4), sc=(1 << 23, -1, -2, -1))
@@ -246,7 +251,7 @@ def test_errors(pkg, ctx):
     assert raw_scores((-1, -1), (1, 1), score=None) == INV and raw_scores(None, (1, 1)) == INV and raw_scores((-1, -1), None) == INV
     assert raw_scores((-1, 1), (MAX_WIDTH - 1, 0)) == CAP and raw_scores((1, -1), (0, MAX_WIDTH - 1)) == INV
     assert ctx.extend_banded_stats() == stats            # unchanged by every call that failed validation
-    rows = sum(w["rows"] for w in XO.extend_many([(A, Bq)] * 2, [(-1, 1), (-2, 4)], 1, -1, -2, -1, 10))
+    rows = sum(w["rows"] for w in XO.extend_many([(A, Bq)] * 2, [(-1, 1), (-2, 4)], (1, -1), -2, -1, 10))
     assert raw((-1, -2), (1, 4)) == 0
     assert ctx.extend_banded_stats()["rows_considered"] == rows
     assert raw_scores((-1, -2), (1, 4)) == 0
@@ -269,7 +274,7 @@ def test_range_bytes(ctx):
     rows = sum(g["rows"] for g in got)
     assert ctx.extend_banded_stats()["rows_considered"] == rows and any(g["rows"] < 1500 for g in got)
     ks = list(range(0, 64, 9))
-    assert [got[k] for k in ks] == XO.extend_many([pairs[k] for k in ks], [bands[k] for k in ks], *SC, 40)
+    assert [got[k] for k in ks] == _whole([pairs[k] for k in ks], [bands[k] for k in ks], SC, 40)
     with switched_context(PWA_RANGE_BYTES="4096") as c:
         assert _call(c, pairs, bands, SC, 40) == got
         assert c.extend_banded_stats()["rows_considered"] == rows

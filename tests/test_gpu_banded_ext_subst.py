@@ -1,6 +1,6 @@
 """Banded X-drop extension under a substitution matrix on the device (pwa_extend_banded_subst_batch / _cigar,
 pwa_scores_extend_banded_subst; include/pwalign.h): scores, end cells, rows, the pattern-end result, op lists, CIGAR and MD:Z byte for
-byte against the numpy oracle banded_ext_subst_oracle.py (tied to a scalar DP, to banded_ext_oracle and to banded_subst_oracle by
+byte against the numpy oracle banded_ext_oracle.py under the table (tied to a scalar DP, to its byte compare and to banded_oracle by
 test_banded_ext_subst_oracle.py); the scores call against the alignment call; the byte-compare EXT calls under a match / mismatch
 table; and the error paths, all of which are host-side refusals.
 
@@ -13,7 +13,7 @@ import random
 import numpy as np
 import pytest
 
-import banded_ext_subst_oracle as XSO
+import banded_ext_oracle as XO
 from conftest import load_pkg, switched_context
 from test_gpu_banded import DELTAS, HEIGHTS, MAX_WIDTH, WIDTHS, _lengths, _mixed_pairs, _text_for
 from test_gpu_banded_subst import _table
@@ -100,7 +100,7 @@ def _shape_set(S):
             for w in widths:
                 pairs.append((p, t))
                 bands.append(pkg.band_around(n, m, w, diag=0))
-    return pairs, bands, XSO.extend_multi(pairs, bands, table, go, ge, [-1, 60], group=24)
+    return pairs, bands, XO.extend_multi(pairs, bands, table, go, ge, [-1, 60], group=24)
 
 
 def test_shapes_against_oracle(hctx):
@@ -134,7 +134,7 @@ def test_alphabet_sizes(pkg, hctx, n_sym):
         p = _rand(rng, n, alpha)
         pairs.append((p, _text_for(rng, p, n + d, alpha)))
         bands.append(pkg.band_around(n, n + d, w, diag=0))
-    want = XSO.extend_multi(pairs, bands, table, go, ge, [-1, 25])
+    want = XO.extend_multi(pairs, bands, table, go, ge, [-1, 25])
     for xdrop in (-1, 25):
         _check(hctx, pairs, bands, table, go, ge, xdrop, want[xdrop], ("n_sym", n_sym, hctx.rl))
 
@@ -152,7 +152,7 @@ def test_positive_off_diagonal_and_all_negative_tables(hctx, name):
         p = _rand(rng, n, b"ACGT")
         pairs.append((p, _text_for(rng, p, n + d, b"ACGT")))
         bands.append(pkg.band_around(n, n + d, w, diag=0))
-    want = XSO.extend_multi(pairs, bands, table, -4, -1, [-1, 15, 1 << 27])
+    want = XO.extend_multi(pairs, bands, table, -4, -1, [-1, 15, 1 << 27])
     for xdrop in (-1, 15, 1 << 27):
         got = _check(hctx, pairs, bands, table, -4, -1, xdrop, want[xdrop], (name, hctx.rl))
         if name == "neg":
@@ -168,7 +168,7 @@ def _stop_at(rng, table, go, ge, rows, tail):
     for tries in range(40):
         x = _rand(rng, rows - 14, b"ACGT")
         pair, band = (x + b"A" * tail, x + b"C" * 600), (-32, 32)
-        w = XSO.extend(*pair, band, table, go, ge, 20)
+        w = XO.extend(*pair, band, table, go, ge, 20)
         if w["rows"] == min(rows, len(pair[0])) and w["end"] == (rows - 14, rows - 14):
             return pair, band, w
     raise AssertionError("no X places the stop at row %d" % (rows + 1))
@@ -194,7 +194,7 @@ def test_the_drop_changes_the_answer_and_equal_maxima(hctx):
     rng = random.Random(73)
     x, y = _rand(rng, 200, b"ACGT"), _rand(rng, 600, b"ACGT")
     pair, band = (x + _rand(rng, 60, b"AC") + y, x + _rand(rng, 60, b"GT") + y), (-40, 40)
-    want = XSO.extend_multi([pair], [band], table, go, ge, [30, -1])
+    want = XO.extend_multi([pair], [band], table, go, ge, [30, -1])
     stop, free = want[30][0], want[-1][0]
     assert stop["end"][0] < 260 and stop["rows"] < 300 and stop["pend"] is None
     assert free["end"] == (860, 860) and free["score"] > stop["score"] and free["rows"] == 860 and free["pend"] == (free["score"], 860)
@@ -204,7 +204,7 @@ def test_the_drop_changes_the_answer_and_equal_maxima(hctx):
     # best cell and in the pattern end alike
     x, z = _rand(rng, 300, b"ACGT"), _rand(rng, 77, b"ACGT")
     for xdrop in (-1, 3):
-        want = XSO.extend_many([(x, x + z + x)], [(0, 377)], table, go, ge, xdrop)
+        want = XO.extend_many([(x, x + z + x)], [(0, 377)], table, go, ge, xdrop)
         assert want[0]["end"] == (300, 300) and want[0]["score"] == 900 and want[0]["pend"] == (900, 300)
         _check(hctx, [(x, x + z + x)], [(0, 377)], table, go, ge, xdrop, want, ("ties", hctx.rl))
 
@@ -221,7 +221,7 @@ def test_pattern_end_rows(hctx):
         p = _rand(rng, n, alpha)
         pairs.append((p, _text_for(rng, p, n + 40, alpha)))
         bands.append((-20, 20))
-    want = XSO.extend_multi(pairs, bands, table, go, ge, [-1, 1 << 27])
+    want = XO.extend_multi(pairs, bands, table, go, ge, [-1, 1 << 27])
     for xdrop in (-1, 1 << 27):   # (the largest drop: only a row without a cell would stop)
         assert all(w["pend"] is not None and w["rows"] == n for w, n in zip(want[xdrop], ns))
         _check(hctx, pairs, bands, table, go, ge, xdrop, want[xdrop], ("pend rows", hctx.rl))
@@ -255,7 +255,7 @@ def test_pattern_end_none_and_empty_sides(hctx):
     pairs += [(b"ACG", b""), (b"", b"ACGTN"), (b"", b""), (b"ACGT", b"ACGA")]
     bands += [(-3, 0), (0, 5), (0, 0), (-4, 4)]
     for xdrop in (-1, 50):   # (50: the ten rows below the text's end fall 16 at most; row S - 19 has no cell and stops)
-        want = XSO.extend_many(pairs, bands, table, go, ge, xdrop)
+        want = XO.extend_many(pairs, bands, table, go, ge, xdrop)
         assert want[0]["rows"] == S - 20 and want[0]["pend"] is None
         assert [w["pend"] for w in want[1:4]] == [None, (0, 0), (0, 0)] and all(w["rows"] == 0 and w["score"] == 0 for w in want[1:4])
         assert want[4]["pend"] is not None
@@ -300,7 +300,7 @@ def test_match_mismatch_table_equals_the_byte_compare_calls_and_nw_on_the_prefix
         qs, qa, qb = _seqs(prefix)
         assert ctx.scores_banded_subst("nw", qs, qa, qb, table, go, ge, [bands[k] for k in ks]) == [pend[k][0] for k in ks]
         ko = list(range(0, 300, 17))
-        want = XSO.extend_many([pairs[k] for k in ko], [bands[k] for k in ko], table, go, ge, xdrop, group=8)
+        want = XO.extend_many([pairs[k] for k in ko], [bands[k] for k in ko], table, go, ge, xdrop, group=8)
         for x, k in enumerate(ko):
             assert dict(got[k], pend=pend[k]) == want[x], (k, len(pairs[k][0]), len(pairs[k][1]), bands[k])
 
@@ -313,7 +313,7 @@ def test_widest_band(hctx):
     t = _text_for(rng, p, 2150, alpha)
     band = (-2100, MAX_WIDTH - 2101)
     assert band[1] - band[0] + 1 == MAX_WIDTH and band[0] <= 0 <= band[1]
-    want = XSO.extend_multi([(p, t)], [band], table, go, ge, [-1, 40], group=1)
+    want = XO.extend_multi([(p, t)], [band], table, go, ge, [-1, 40], group=1)
     for xdrop in (-1, 40):
         _check(hctx, [(p, t)], [band], table, go, ge, xdrop, want[xdrop], ("widest", hctx.rl))
 
@@ -321,7 +321,7 @@ def test_widest_band(hctx):
 def test_folded_case_is_a_match_that_mdz_reports_as_a_mismatch(ctx):
     table, go, ge, _ = _table("dna")
     p, t = b"ACGTACGTACGTACGTACGT", b"ACGTacgtACGTACGTACGTTT"
-    want = XSO.extend(p, t, (-3, 3), table, go, ge, 10)
+    want = XO.extend(p, t, (-3, 3), table, go, ge, 10)
     assert want["score"] == 60 and want["ops"] == b"M" * 20 and want["pend"] == (60, 20)
     got = _check(ctx, [(p, t)], [(-3, 3)], table, go, ge, 10, [want], "fold")
     cg = _call(ctx, [(p, t)], [(-3, 3)], table, go, ge, 10, cigar=True)[0]
@@ -344,7 +344,7 @@ def test_range_bytes(ctx):
     assert ctx.extend_banded_stats()["rows_considered"] == rows
     assert any(g["pend"] is None for g in got) and any(g["pend"] is not None for g in got)
     ks = list(range(0, 64, 9))
-    assert [got[k] for k in ks] == XSO.extend_many([pairs[k] for k in ks], [bands[k] for k in ks], table, go, ge, 60)
+    assert [got[k] for k in ks] == XO.extend_many([pairs[k] for k in ks], [bands[k] for k in ks], table, go, ge, 60)
     with switched_context(PWA_RANGE_BYTES="4096") as c:
         assert _call(c, pairs, bands, table, go, ge, 60) == got
         assert c.extend_banded_stats()["rows_considered"] == rows
@@ -358,7 +358,7 @@ def test_errors(pkg, ctx):
     A, Bq = b"ACGTACGTAC", b"ACGTTACGTACG"   # 10 x 12
     table, go, ge, _ = _table("dna")
     good = ctx.extend_banded_subst_batch([A, Bq], [0], [1], table, go, ge, [(-2, 4)], 10)
-    assert good == XSO.extend_many([(A, Bq)], [(-2, 4)], table, go, ge, 10)
+    assert good == XO.extend_many([(A, Bq)], [(-2, 4)], table, go, ge, 10)
     st = ctx.extend_banded_stats()
     assert st["rows_considered"] == good[0]["rows"] and st["fill_ms"] > 0 and st["walk_ms"] > 0
     blob, off, _ = pkg.pack_sequences([A, Bq])

@@ -7,9 +7,7 @@ import random
 import pytest
 
 import banded_ext_oracle as XO
-import banded_ext_subst_oracle as XSO
 import banded_oracle as BO
-import banded_subst_oracle as BSO
 from test_gpu_banded_ext import SC, _seqs
 from test_gpu_banded_subst import _table
 from test_gpu_cigar import fmt
@@ -51,8 +49,8 @@ def _call(c, form, out, pairs, bands):
 
 def _want(form, out, pairs, bands):
     table, go, ge, _alpha = _table("dna")
-    res = {"byte": lambda: BO.align_many(pairs, bands, "sw", *SC), "table": lambda: BSO.align_many(pairs, bands, "sw", table, go, ge),
-           "ext": lambda: XO.extend_many(pairs, bands, *SC, XDROP), "ext_table": lambda: XSO.extend_many(pairs, bands, table, go, ge, XDROP)}[form]()
+    res = {"byte": lambda: BO.align_many(pairs, bands, "sw", SC[:2], *SC[2:]), "table": lambda: BO.align_many(pairs, bands, "sw", table, go, ge),
+           "ext": lambda: XO.extend_many(pairs, bands, SC[:2], *SC[2:], XDROP), "ext_table": lambda: XO.extend_many(pairs, bands, table, go, ge, XDROP)}[form]()
     extra = {"byte": (), "table": (), "ext": ("rows",), "ext_table": ("rows", "pend")}[form]
     want = {}
     for o in out:

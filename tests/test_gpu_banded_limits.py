@@ -16,9 +16,8 @@ import random
 import numpy as np
 import pytest
 
-import banded_ext_subst_oracle as XSO
+import banded_ext_oracle as XO
 import banded_oracle as BO
-import banded_subst_oracle as BSO
 from conftest import load_pkg, switched_context
 from test_gpu_banded import HEIGHTS
 from test_gpu_cigar import fmt
@@ -116,7 +115,7 @@ def _case_a(S, mode):
     n = 2 * S + 1
     t = top(n, n, 28)
     sc = (t, -t, -(t // 3), -(t - t // 3))
-    return pairs, bands, sc, BO.align_many(pairs, bands, mode, *sc)
+    return pairs, bands, sc, BO.align_many(pairs, bands, mode, sc[:2], *sc[2:])
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -141,7 +140,7 @@ def _case_b(S, mode):
     pairs, bands = [(_rand(rng, n, b"AC"), _rand(rng, m, b"GT"))], [(0, 4000)]
     t = top(n, m, 28)
     sc = (1, -t, -1, -(t - 1))
-    return pairs, bands, sc, BO.align_many(pairs, bands, mode, *sc)
+    return pairs, bands, sc, BO.align_many(pairs, bands, mode, sc[:2], *sc[2:])
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -162,7 +161,7 @@ C_SCORINGS = {"open0": lambda t: (1, -t, 0, -t), "extend0": lambda t: (1, -t, -t
 def _case_c(shape, kind, mode):
     pair, band = {"wide": ((b"A", b"C" * 4000), (0, 3999)), "tall": (TALL, (-3997, 0))}[shape]
     sc = C_SCORINGS[kind](top(len(pair[0]), len(pair[1]), 28))
-    return [pair], [band], sc, BO.align_many([pair], [band], mode, *sc)
+    return [pair], [band], sc, BO.align_many([pair], [band], mode, sc[:2], *sc[2:])
 
 
 @pytest.mark.parametrize("shape,mode", [("wide", "nw"), ("wide", "sw"), ("wide", "sg"), ("tall", "nw"), ("tall", "sg")])
@@ -181,7 +180,7 @@ def _at_top_28(which, S, term, mode):
     """case d's pairs at A = top through one term -> pairs, bands, sc, tab and the two oracle results"""
     pairs, bands = _square_pairs(S) if which == "square" else ([TALL], [(-3997, 0)])
     sc, tab = _through(term, top(len(pairs[0][0]), len(pairs[0][1]), 28))
-    return pairs, bands, sc, tab, BO.align_many(pairs, bands, mode, *sc), BSO.align_many(pairs, bands, mode, *tab)
+    return pairs, bands, sc, tab, BO.align_many(pairs, bands, mode, sc[:2], *sc[2:]), BO.align_many(pairs, bands, mode, *tab)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -225,7 +224,7 @@ def test_d_one_step_over_is_refused(hctx, which):
 
 # ------------------------------------------------------------------ the X-drop extension calls: (n + m + 2) * A < 2^27
 def _check_ext(c, pairs, bands, xdrop, want, tag, sc=None, tab=None):
-    """want: banded_ext_subst_oracle's results (with pend); the byte-compare forms return everything but the pattern end"""
+    """want: banded_ext_oracle's results under the table (with pend); the byte-compare forms return everything but the pattern end"""
     seqs, pa, pb = _lists(pairs)
     if sc is not None:
         got, gc = c.extend_banded_batch(seqs, pa, pb, *sc, bands, xdrop), c.extend_banded_batch_cigar(seqs, pa, pb, *sc, bands, xdrop)
@@ -258,7 +257,7 @@ E_XDROPS = [-1, 1 << 27, 5]
 def _case_e():
     t = top(4000, 3, 27)
     tab = (load_pkg().subst_table(b"AC", np.full((2, 2), -t)), 0, -t)
-    return (1, -t, 0, -t), tab, XSO.extend_multi([TALL], [(-4000, 0)], *tab, E_XDROPS)
+    return (1, -t, 0, -t), tab, XO.extend_multi([TALL], [(-4000, 0)], *tab, E_XDROPS)
 
 
 @pytest.mark.parametrize("xdrop", E_XDROPS)
@@ -287,12 +286,12 @@ def _case_f(S):
     n = 2 * S + 1
     sc = _all_terms(top(n, n, 27))
     drops = [-1, 1 << 27, 3 * sc[0]]
-    ident = (pairs[:1], bands[:1], sc, drops, XSO.extend_multi(pairs[:1], bands[:1], _mm(sc[0], sc[1]), sc[2], sc[3], drops))
+    ident = (pairs[:1], bands[:1], sc, drops, XO.extend_multi(pairs[:1], bands[:1], _mm(sc[0], sc[1]), sc[2], sc[3], drops))
     x = _rand(random.Random(7 * S), S + 1, b"ACGT")
     pair, band = (x + b"A" * 40, x + b"C" * 40), (-32, 32)
     sc = _all_terms(top(S + 41, S + 41, 27))
     drops = [2 * sc[0], -1]
-    stop = ([pair], [band], sc, drops, XSO.extend_multi([pair], [band], _mm(sc[0], sc[1]), sc[2], sc[3], drops))
+    stop = ([pair], [band], sc, drops, XO.extend_multi([pair], [band], _mm(sc[0], sc[1]), sc[2], sc[3], drops))
     return ident, stop
 
 
@@ -320,7 +319,7 @@ def _at_top_27(S, term):
     n = 2 * S + 1
     sc, tab = _through(term, top(n, n, 27))
     drops = [-1, 1 << 27, 50]
-    return pairs, bands, sc, tab, drops, XSO.extend_multi(pairs, bands, _mm(sc[0], sc[1]), sc[2], sc[3], drops), XSO.extend_multi(pairs, bands, *tab, drops)
+    return pairs, bands, sc, tab, drops, XO.extend_multi(pairs, bands, _mm(sc[0], sc[1]), sc[2], sc[3], drops), XO.extend_multi(pairs, bands, *tab, drops)
 
 
 @pytest.mark.parametrize("term", TERMS)
@@ -355,5 +354,5 @@ def test_g_one_step_over_is_refused_and_the_2_28_rule_still_admits_it(hctx, whic
         seqs, pa, pb = _lists(pairs)
         got = (hctx.scores_banded("nw", seqs, pa, pb, *sc, bands), hctx.scores_banded_subst("nw", seqs, pa, pb, *tab, bands))
         if which == "square":
-            assert got == ([BO.align(*pairs[0], bands[0], "nw", *sc)["score"]], [BSO.align(*pairs[0], bands[0], "nw", *tab)["score"]])
+            assert got == ([BO.align(*pairs[0], bands[0], "nw", sc[:2], *sc[2:])["score"]], [BO.align(*pairs[0], bands[0], "nw", *tab)["score"]])
     assert hctx.extend_banded_stats() == before

@@ -51,7 +51,7 @@ def test_shapes_against_oracle(hctx, mode, alpha, sc):
     """n in {1, 2, 63, 64, 65, S - 1, S, S + 1, 2 S, 2 S + 1, 3001}, m = n + {-37, 0, 50}, half-widths {0, 1, 7, 64, 300}: stripe
     boundaries, the hand-off row, the 16-byte window start and the edge chunks, at both stripe heights"""
     pairs, bands = _shape_cases(mode, HEIGHTS[hctx.rl], ALPHABETS[alpha], 7 * hctx.rl + len(alpha))
-    want = _want(BO.align_many(pairs, bands, mode, *sc, group=24))
+    want = _want(BO.align_many(pairs, bands, mode, sc[:2], *sc[2:], group=24))
     got = _scores(hctx, mode, pairs, bands, sc)
     for k, (g, w) in enumerate(zip(got, want)):
         assert g == w, (mode, hctx.rl, k, len(pairs[k][0]), len(pairs[k][1]), bands[k])
@@ -87,7 +87,7 @@ def test_ties(hctx):
     for mode, p, t, band, want in cases:
         assert band[1] - band[0] + 1 <= MAX_WIDTH
         assert _scores(hctx, mode, [(p, t)], [band], sc) == [want], (mode, hctx.rl, band)
-        assert _want([BO.align(p, t, band, mode, *sc)]) == [want], (mode, band)
+        assert _want([BO.align(p, t, band, mode, sc[:2], *sc[2:])]) == [want], (mode, band)
 
 
 def test_widest_band(ctx):
@@ -99,7 +99,7 @@ def test_widest_band(ctx):
     assert band[1] - band[0] + 1 == MAX_WIDTH
     sc = (1, -4, -6, -1)
     for mode in ("nw", "sw"):
-        assert _scores(ctx, mode, [(p, t)], [band], sc) == _want([BO.align(p, t, band, mode, *sc)]), mode
+        assert _scores(ctx, mode, [(p, t)], [band], sc) == _want([BO.align(p, t, band, mode, sc[:2], *sc[2:])]), mode
 
 
 @pytest.mark.parametrize("mode", ["nw", "sw", "sg"])
@@ -158,7 +158,7 @@ def test_errors(pkg, ctx):
     assert L.pwa_scores_banded(h, 0, 1, -1, -2, -1, blob, off, 2, pa, pb, 2, sc, ei, ej, (C.c_int32 * 2)(-4, -4), None) == -1
     assert L.pwa_scores_banded(h, 0, 1, -1, -2, -1, blob, off, 2, pa, pb, 2, None, ei, ej, (C.c_int32 * 2)(-4, -4), four) == -1
     assert ctx.scores_banded_stats() == stats
-    assert run("nw", (-1, MAX_WIDTH - 2)) == (lambda w: (w["score"], tuple(w["end"])))(GO.align(A, Bq, "nw", 1, -1, -2, -1))
+    assert run("nw", (-1, MAX_WIDTH - 2)) == (lambda w: (w["score"], tuple(w["end"])))(GO.align(A, Bq, "nw", (1, -1), -2, -1))
     assert run("nw", (-3, 0), seqs=(b"ACG", b"")) == (lambda w: (w["score"], tuple(w["end"])))(GO.result(None, "nw", 3, 0, -2, -1))
 
 

@@ -1,6 +1,6 @@
 """Banded affine-gap alignments and scores under a substitution matrix on the device (pwa_align_banded_subst_batch / _cigar,
 pwa_scores_banded_subst, include/pwalign.h): scores, end and start cells, op lists and strings byte for byte against the numpy oracle
-banded_subst_oracle.py (tied to a scalar banded DP, to banded_oracle and to subst_oracle by test_banded_subst_oracle.py); against the
+banded_oracle.py under the table (tied to a scalar banded DP, to its byte compare and to gotoh_oracle by test_banded_subst_oracle.py); against the
 byte-compare banded calls under a match / mismatch table; against the unbanded table calls under a band that covers the matrix; and the
 error paths, all of which are host-side refusals.
 
@@ -14,7 +14,7 @@ import random
 import numpy as np
 import pytest
 
-import banded_subst_oracle as BSO
+import banded_oracle as BO
 import gotoh_oracle as GO
 from conftest import load_pkg, switched_context
 from test_gpu_banded import DELTAS, HEIGHTS, MAX_WIDTH, WIDTHS, _band, _random_valid_band
@@ -70,7 +70,7 @@ def _shape_set(mode, S, name):
             for w in widths:
                 pairs.append((p, t))
                 bands.append(_band(mode, n, m, w))
-    return pairs, bands, BSO.align_many(pairs, bands, mode, table, go, ge, group=24)
+    return pairs, bands, BO.align_many(pairs, bands, mode, table, go, ge, group=24)
 
 
 def _lists(pairs):
@@ -183,7 +183,7 @@ def test_alphabet_edges(pkg, hctx, mode, n_sym):
         t = _text_for(rng, p, n + d, alpha)
         pairs.append((p, t))
         bands.append(_band(mode, n, n + d, w))
-    want = BSO.align_many(pairs, bands, mode, table, -3, -1)
+    want = BO.align_many(pairs, bands, mode, table, -3, -1)
     _check_all(hctx, mode, pairs, bands, table, -3, -1, want, (mode, hctx.rl, n_sym))
 
 
@@ -200,7 +200,7 @@ def _widest_set(mode):
         q = _rand(rng, n, alpha)
         pairs.append((q, _text_for(rng, q, n + d, alpha)))
         bands.append(_band(mode, n, n + d, w))
-    return pairs, bands, BSO.align_many(pairs, bands, mode, table, go, ge, group=1)
+    return pairs, bands, BO.align_many(pairs, bands, mode, table, go, ge, group=1)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -228,7 +228,7 @@ def test_ties(pkg, hctx, mode):
         bands.append(_band(mode, n, m, w))
     for m, go, ge in [([[0, 0], [0, 0]], 0, 0), ([[2, 2], [2, 2]], 0, -2), ([[1, -1], [-1, 1]], -2, 0)]:
         table = pkg.subst_table(b"AC", m)
-        want = BSO.align_many(pairs, bands, mode, table, go, ge)
+        want = BO.align_many(pairs, bands, mode, table, go, ge)
         _check_all(hctx, mode, pairs, bands, table, go, ge, want, ("ties", mode, hctx.rl, go, ge))
 
 
@@ -254,7 +254,7 @@ def test_range_cut_keeps_the_table(ctx, mode):
         assert _call(c, mode, pairs, bands, table, go, ge, cigar=True) == gc
         assert c.align_banded_stats()["band_bytes"] == st["band_bytes"]
         assert _scores(c, mode, pairs, bands, table, go, ge) == [(g["score"], g["end"]) for g in got]
-    want = BSO.align_many(pairs[:8], bands[:8], mode, table, go, ge)
+    want = BO.align_many(pairs[:8], bands[:8], mode, table, go, ge)
     for k, w in enumerate(want):
         assert got[k] == dict(score=w["score"], ops=w["ops"], end=tuple(w["end"]), start=tuple(w["start"])), k
 
@@ -267,7 +267,7 @@ def test_empty_sides_and_the_empty_list(ctx, mode):
     assert ctx.scores_banded_subst(mode, [b"ACGT"], [], [], table, go, ge, [], want_end=True) == ([], [], [])
     pairs = [(b"ACG", b""), (b"", b"ACGTN"), (b"", b""), (b"ACGT", b"AGGT")]
     bands = [(-3, 0), (0, 5), (0, 0), (-1, 1)]
-    want = BSO.align_many(pairs, bands, mode, table, go, ge)
+    want = BO.align_many(pairs, bands, mode, table, go, ge)
     for k in range(3):
         assert want[k] == GO.result(None, mode, len(pairs[k][0]), len(pairs[k][1]), go, ge)
     _check_all(ctx, mode, pairs, bands, table, go, ge, want, ("empty", mode))

@@ -69,7 +69,7 @@ def test_shapes_against_oracle(ctx, mode, alpha, sc, long_text):
     gc = ctx.align_gotoh_batch_cigar(mode, seqs, pa, pb, match, mismatch, go, ge)
     k = 0
     for x, p in enumerate(pats):
-        want = GO.prefixes(p, texts[x], tl, mode, match, mismatch, go, ge)
+        want = GO.prefixes(p, texts[x], tl, mode, (match, mismatch), go, ge)
         for y, m in enumerate(tl):
             g, w, c = got[k], want[y], gc[k]
             t = texts[x][:m]
@@ -128,9 +128,9 @@ def test_large_mixed_batch(ctx, mode):
     got = ctx.align_gotoh_batch(mode, seqs, pa, pb, match, mismatch, go, ge)
     for k, g in enumerate(got):
         p, t = seqs[pa[k]], seqs[pb[k]]
-        assert GO.op_score(p, t, g["ops"], g["start"], match, mismatch, go, ge) == g["score"], k
+        assert GO.op_score(p, t, g["ops"], g["start"], (match, mismatch), go, ge) == g["score"], k
     for k in range(0, 8192, 61):
-        w = GO.align(seqs[pa[k]], seqs[pb[k]], mode, match, mismatch, go, ge)
+        w = GO.align(seqs[pa[k]], seqs[pb[k]], mode, (match, mismatch), go, ge)
         assert got[k] == w, k
     with switched_context(PWA_RANGE_BYTES="3145728") as c:
         assert c.align_gotoh_batch(mode, seqs, pa, pb, match, mismatch, go, ge) == got

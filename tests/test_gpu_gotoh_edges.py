@@ -78,7 +78,7 @@ def run_groups(c, mode, groups, sc, cigar=True, shuffle=None):
     match, mismatch, go, ge = sc
     pairs, want = [], []
     for p, t, ms in groups:
-        want += GO.prefixes(p, t[:max(ms)], ms, mode, match, mismatch, go, ge)
+        want += GO.prefixes(p, t[:max(ms)], ms, mode, (match, mismatch), go, ge)
         pairs += [(p, t[:m]) for m in ms]
     order = list(range(len(pairs)))
     if shuffle is not None:
@@ -213,7 +213,7 @@ def test_largest_admitted_scores_are_exact(ctx, mode, n):
     got = ctx.align_gotoh_batch(mode, *_batch(pairs), *sc)
     assert got[0]["score"] == n * mx and got[0]["ops"] == b"M" * n, mode
     for (a, b), g in zip(pairs, got):
-        w = GO.align(a, b, mode, *sc)
+        w = GO.align(a, b, mode, sc[:2], *sc[2:])
         assert (g["score"], g["end"], g["start"], g["ops"]) == (w["score"], w["end"], w["start"], w["ops"]), (mode, len(a), len(b))
 
 
@@ -231,7 +231,7 @@ def test_most_negative_keys_are_exact(ctx, mode, n):
     if mode == "nw":
         assert got[0]["score"] < -(1 << 28) * 0.85
     for (a, b), g in zip(pairs, got):
-        w = GO.align(a, b, mode, *sc)
+        w = GO.align(a, b, mode, sc[:2], *sc[2:])
         assert (g["score"], g["end"], g["start"], g["ops"]) == (w["score"], w["end"], w["start"], w["ops"]), (mode, n)
 
 
@@ -290,7 +290,7 @@ def test_homopolymer_indels_land_where_the_oracle_puts_them(ctx, mode, n):
         seqs, pa, pb = _batch(pairs)
         got = ctx.align_gotoh_batch(mode, seqs, pa, pb, *sc)
         for (p, t), g in zip(pairs, got):
-            w = GO.align(p, t, mode, *sc)
+            w = GO.align(p, t, mode, sc[:2], *sc[2:])
             assert (g["score"], g["end"], g["start"], g["ops"]) == (w["score"], w["end"], w["start"], w["ops"]), (mode, sc, p, t)
 
 
@@ -330,7 +330,7 @@ def test_sw_keeps_the_first_row_major_maximum(ctx, n):
         seqs, pa, pb = _batch(pairs)
         got = ctx.align_gotoh_batch("sw", seqs, pa, pb, *sc)
         for (a, b), g in zip(pairs, got):
-            w = GO.align(a, b, "sw", *sc)
+            w = GO.align(a, b, "sw", sc[:2], *sc[2:])
             assert (g["score"], g["end"], g["start"], g["ops"]) == (w["score"], w["end"], w["start"], w["ops"]), (n, sc, len(a), len(b))
 
 
@@ -349,7 +349,7 @@ def test_sg_keeps_the_smallest_end_column(ctx, n):
         seqs, pa, pb = _batch(pairs)
         got = ctx.align_gotoh_batch("sg", seqs, pa, pb, *sc)
         for (a, b), g in zip(pairs, got):
-            w = GO.align(a, b, "sg", *sc)
+            w = GO.align(a, b, "sg", sc[:2], *sc[2:])
             assert (g["score"], g["end"], g["start"], g["ops"]) == (w["score"], w["end"], w["start"], w["ops"]), (n, sc, len(a), len(b))
 
 
@@ -390,7 +390,7 @@ def test_op_region_layouts_are_byte_identical(pkg, ctx, mode):
         assert (s2, nops2, e2, st2) == (s0, nops0, e0, st0)
         assert [raw2[off2[k]:off2[k] + nops2[k]] for k in range(len(pairs))] == ops0
     for k in range(0, len(pairs), 11):
-        w = GO.align(*pairs[k], mode, *sc)
+        w = GO.align(*pairs[k], mode, sc[:2], *sc[2:])
         assert (s0[k], ops0[k], tuple(e0[2 * k:2 * k + 2]), tuple(st0[2 * k:2 * k + 2])) == (w["score"], w["ops"], w["end"], w["start"]), k
 
 

@@ -19,7 +19,7 @@ STRIP = "batch_gotoh_kernel"
 
 
 def _want(pairs, mode, sc):
-    w = GO.align_many(pairs, mode, *sc, want_ops=False)
+    w = GO.align_many(pairs, mode, sc[:2], *sc[2:], want_ops=False)
     return [x["score"] for x in w], [x["end"][0] for x in w], [x["end"][1] for x in w]
 
 
@@ -44,7 +44,7 @@ def test_shapes_against_oracle(ctx, mode, alpha, sc, long_text):
     s, ei, ej = ctx.scores_gotoh(mode, seqs, pa, pb, *sc, want_end=True)
     k = 0
     for x, p in enumerate(pats):
-        want = GO.prefixes(p, texts[x], tl, mode, *sc, want_ops=False)
+        want = GO.prefixes(p, texts[x], tl, mode, sc[:2], *sc[2:], want_ops=False)
         for y, m in enumerate(tl):
             key = (mode, len(p), m)
             assert plain[k] == want[y]["score"], key

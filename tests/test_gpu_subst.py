@@ -1,7 +1,7 @@
 """Substitution-matrix scoring of the affine-gap batch calls on the device (subst_fill.hip.h, include/pwalign.h): every pattern class on
 both sides of its row bounds, equivalence with the byte-compare gotoh calls under a match / mismatch matrix, the orientation of the
 table, the code map, ties, the scores entry points, several ranges, and the errors.  Every device result is compared field for field
-with the numpy oracle subst_oracle.py (tied to a scalar three-matrix DP and to gotoh_oracle by test_subst_oracle.py): score, end and
+with the numpy oracle gotoh_oracle.py under the table (tied to a scalar three-matrix DP and to its byte compare by test_subst_oracle.py): score, end and
 start cell, the op list byte for byte, CIGAR / MD:Z against pwa_format_alignment of those ops, and the ops re-scored under the matrix."""
 import ctypes as C
 import random
@@ -9,10 +9,10 @@ import random
 import numpy as np
 import pytest
 
-import subst_oracle as SO
+import gotoh_oracle as GO
 from conftest import load_pkg, switched_context
+from gotoh_oracle import random_table
 from test_gpu_cigar import fmt
-from test_subst_oracle import random_table
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +66,7 @@ def check(c, mode, pairs, want, table, go, ge, cigar=True):
         key = (mode, go, ge, len(p), len(t), k)
         assert (g["score"], g["end"], g["start"]) == (w["score"], w["end"], w["start"]), key
         assert g["ops"] == w["ops"], key
-        assert SO.op_score(p, t, g["ops"], g["start"], table, go, ge) == g["score"], key
+        assert GO.op_score(p, t, g["ops"], g["start"], table, go, ge) == g["score"], key
         if cigar:
             assert (gc[k]["score"], gc[k]["end"], gc[k]["start"]) == (w["score"], w["end"], w["start"]), key
             assert (gc[k]["cigar"], gc[k]["mdz"]) == strings(pkg, p, t, g["ops"], g["start"], g["end"]), key
@@ -97,7 +97,7 @@ def test_class_edges(ctx, edge_groups, mode, gaps):
     assert (submat.diagonal() > 0).all() and (submat - np.diag(submat.diagonal()) > 0).any() and not (submat == submat.T).all()
     pairs, want = [], []
     for p, t in edge_groups:
-        want += SO.prefixes(p, t, TEXT_LENS, mode, table, *gaps)
+        want += GO.prefixes(p, t, TEXT_LENS, mode, table, *gaps)
         pairs += [(p, t[:m]) for m in TEXT_LENS]
     check(ctx, mode, pairs, want, table, *gaps)
 
@@ -142,9 +142,9 @@ def test_table_orientation_and_alphabet_sizes(pkg, ctx, mode, n_sym):
     rng = random.Random(60 + n_sym)
     pairs = [(_rand(rng, n, alpha), _rand(rng, m, alpha)) for n, m in [(7, 9), (40, 33), (150, 170), (257, 120), (600, 40)]]
     go, ge = -5, -1
-    want = SO.align_many(pairs, mode, table, go, ge)
+    want = GO.align_many(pairs, mode, table, go, ge)
     if n_sym > 1:
-        other = SO.align_many(pairs, mode, transposed, go, ge)
+        other = GO.align_many(pairs, mode, transposed, go, ge)
         assert sum((w["score"], w["ops"]) != (o["score"], o["ops"]) for w, o in zip(want, other)) >= 4   # (of the five pairs)
     check(ctx, mode, pairs, want, table, go, ge)
 
@@ -161,7 +161,7 @@ def test_code_map_folds_case_and_wildcards(pkg, ctx, mode):
     soup = b"ACGTacgtN-\x00xZ"
     pairs = [(b"ACGTACGT", b"acgtacgt"), (b"AC-GT\x00AC", b"ACNGTxAC"), (b"acgtnACGT", b"ACGTNacgt")]
     pairs += [(_rand(rng, n, soup), _rand(rng, m_, soup)) for n, m_ in [(33, 50), (150, 140), (300, 280)]]
-    want = SO.align_many(pairs, mode, table, -6, -1)
+    want = GO.align_many(pairs, mode, table, -6, -1)
     got = check(ctx, mode, pairs, want, table, -6, -1)
     assert got[0]["score"] == 40 and got[0]["ops"] == b"M" * 8   # eight positively scored columns ...
     gc = ctx.align_subst_batch_cigar(mode, *_batch(pairs[:1]), table, -6, -1)[0]
@@ -187,10 +187,10 @@ def test_ties(pkg, ctx, mode):
     for s, go, ge in [(3, 0, -3), (0, 0, 0), (2, -2, 0), (1, 0, -1)]:
         one = pkg.subst_table(b"A", [[s]], unknown=0)
         pairs = [(b"A" * n, b"A" * m) for n, m in shapes]
-        check(ctx, mode, pairs, SO.align_many(pairs, mode, one, go, ge), one, go, ge, cigar=False)
+        check(ctx, mode, pairs, GO.align_many(pairs, mode, one, go, ge), one, go, ge, cigar=False)
         two = pkg.subst_table(b"AB", [[s, -s], [s, s]])
         pairs = [(_rand(rng, n, b"AB"), _rand(rng, m, b"AB")) for n, m in shapes]
-        check(ctx, mode, pairs, SO.align_many(pairs, mode, two, go, ge), two, go, ge, cigar=False)
+        check(ctx, mode, pairs, GO.align_many(pairs, mode, two, go, ge), two, go, ge, cigar=False)
 
 
 # ------------------------------------------------------------------ 6. scores
@@ -253,7 +253,7 @@ def test_several_ranges(ctx, mode):
         assert c.align_subst_batch(mode, seqs, pa, pb, table, -11, -1) == one
         assert c.align_subst_batch_cigar(mode, seqs, pa, pb, table, -11, -1) == one_c
     for k in range(0, len(pairs), 7):
-        w = SO.align(*pairs[k], mode, table, -11, -1)
+        w = GO.align(*pairs[k], mode, table, -11, -1)
         assert (one[k]["score"], one[k]["ops"], one[k]["end"], one[k]["start"]) == (w["score"], w["ops"], w["end"], w["start"]), k
 
 
@@ -322,7 +322,7 @@ def test_shape_and_range_limits(pkg, ctx, mode):
     for entry in (top, -top):
         sub = [3, entry, -2, 3]
         table = (np.array(code, np.uint8), 2, np.array(sub, np.int32))
-        check(ctx, mode, [(p, t)], [SO.align(p, t, mode, table, -2, -1)], table, -2, -1)
+        check(ctx, mode, [(p, t)], [GO.align(p, t, mode, table, -2, -1)], table, -2, -1)
         over = [3, entry + (1 if entry > 0 else -1), -2, 3]
         assert _rcs(_raw(pkg, ctx, mode, code, 2, over, -2, -1, [(p, t)])) == (PWA_E_CAPACITY,) * 4
         assert _rcs(_raw(pkg, ctx, mode, code, 2, over, -2, -1, [(b"\x00", b"\x01"), (p, t), (b"", b"\x01")])) == (PWA_E_CAPACITY,) * 4

@@ -1,4 +1,4 @@
-"""CPU checks of the substitution-matrix oracle (subst_oracle.py): it is gotoh_oracle when the matrix is match on the diagonal and
+"""CPU checks of gotoh_oracle.py under a substitution table: it is its own byte compare when the matrix is match on the diagonal and
 mismatch elsewhere, it equals a plain three-matrix DP on random asymmetric matrices in all three modes, the score of every op list
 under the matrix equals the returned score, and subst_table builds the map and matrix the oracle and the library take."""
 import random
@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import gotoh_oracle as GO
-import subst_oracle as SO
 from conftest import load_pkg
+from gotoh_oracle import random_table
 
 MODES = ["nw", "sw", "sg"]
 GAPS = [(-11, -1), (0, -3), (-6, -1), (-2, 0), (0, 0)]
@@ -18,15 +18,6 @@ def _rand(rng, n, alpha=b"ACGT"):
     return bytes(rng.choice(alpha) for _ in range(n))
 
 
-def random_table(seed, alphabet, lo=-9, hi=11, unknown=None, fold_case=False):
-    """an asymmetric matrix with entries in lo..hi, a positive diagonal and some positive off-diagonal entries"""
-    rng = np.random.RandomState(seed)
-    k = len(alphabet)
-    m = rng.randint(lo, hi + 1, size=(k, k))
-    m[np.arange(k), np.arange(k)] = rng.randint(1, hi + 1, size=k)
-    return load_pkg().subst_table(alphabet, m, unknown=unknown, fold_case=fold_case)
-
-
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("sc", [(1, -4, -6, -1), (5, -4, -16, -4), (2, 1, -3, -1), (0, 0, 0, 0), (1, -1, 0, -2)])
 def test_match_mismatch_matrix_is_the_gotoh_oracle(mode, sc):
@@ -34,7 +25,7 @@ def test_match_mismatch_matrix_is_the_gotoh_oracle(mode, sc):
     table = load_pkg().subst_table(b"ACGT", np.where(np.eye(4, dtype=bool), match, mismatch))
     rng = random.Random(3)
     pairs = [(_rand(rng, rng.randint(0, 40)), _rand(rng, rng.randint(0, 60))) for _ in range(30)]
-    assert SO.align_many(pairs, mode, table, go, ge) == GO.align_many(pairs, mode, match, mismatch, go, ge)
+    assert GO.align_many(pairs, mode, table, go, ge) == GO.align_many(pairs, mode, (match, mismatch), go, ge)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -47,8 +38,8 @@ def test_oracle_matches_scalar_dp(mode, gaps):
         table = random_table(trial, alpha, lo=-5, hi=6)
         n, m = rng.randint(1, 14), rng.randint(1, 14)
         p, t = _rand(rng, n, alpha), _rand(rng, m, alpha)
-        tab = SO.fill(SO._arr(p)[None, :], SO._arr(t)[None, :], mode, table, go, ge)
-        H, src, eop, fop = SO.scalar_dp(p, t, mode, table, go, ge)
+        tab = GO.fill(GO._arr(p)[None, :], GO._arr(t)[None, :], mode, table, go, ge)
+        H, src, eop, fop = GO.scalar_dp(p, t, mode, table, go, ge)
         assert tab["H"][0].tolist() == H
         for i in range(1, n + 1):
             for j in range(1, m + 1):
@@ -65,15 +56,15 @@ def test_op_scores_equal_scores(mode, gaps):
     table = random_table(5, alpha)
     rng = random.Random(9)
     pairs = [(_rand(rng, rng.randint(0, 40), alpha), _rand(rng, rng.randint(0, 60), alpha)) for _ in range(30)]
-    for (p, t), r in zip(pairs, SO.align_many(pairs, mode, table, go, ge)):
-        assert SO.op_score(p, t, r["ops"], r["start"], table, go, ge) == r["score"]
+    for (p, t), r in zip(pairs, GO.align_many(pairs, mode, table, go, ge)):
+        assert GO.op_score(p, t, r["ops"], r["start"], table, go, ge) == r["score"]
 
 
 def test_the_matrix_row_is_the_pattern():
     """s(a, b) != s(b, a): the oracle reads M[pattern code, text code], not the transpose"""
     table = load_pkg().subst_table(b"AB", [[1, 5], [-7, 1]])
-    assert SO.align(b"A", b"B", "nw", table, -20, -1)["score"] == 5
-    assert SO.align(b"B", b"A", "nw", table, -20, -1)["score"] == -7
+    assert GO.align(b"A", b"B", "nw", table, -20, -1)["score"] == 5
+    assert GO.align(b"B", b"A", "nw", table, -20, -1)["score"] == -7
 
 
 def test_subst_table():
