@@ -27,7 +27,7 @@ HW1_HOST_PATH = os.path.join(_HERE, "libhw1_host.so")   # hw1's reader and DOT w
 MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1, "sg": 2, "semiglobal": 2}   # sg: semi-global (pwalign.h, PWA_MODE_SG)
 
 EXPORTS = [
-    "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_scores",
+    "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_ctx_poison_stats", "pwa_scores",
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
@@ -187,6 +187,7 @@ def lib():
     L.pwa_last_error.argtypes = [vp]
     L.pwa_last_error.restype = C.c_char_p
     L.pwa_ctx_set_score_band.argtypes = [vp, C.c_int]
+    L.pwa_ctx_poison_stats.argtypes = [vp, u64p, u64p]
     batch_in = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u64p, C.c_uint32, u32p, u32p, C.c_uint64]
     L.pwa_scores.argtypes = batch_in + [i32p, u32p, u32p]
     L.pwa_batch_create.argtypes = batch_in + [C.c_int, C.POINTER(vp)]
@@ -460,6 +461,12 @@ class Context:
 
     def set_score_band(self, on):
         self._check(self._L.pwa_ctx_set_score_band(self._h, 1 if on else 0), "pwa_ctx_set_score_band")
+
+    def poison_stats(self):
+        """pwa_ctx_poison_stats: what PWA_POISON has filled on this context so far -> dict(buffers, bytes); zeros with the switch unset."""
+        n, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_ctx_poison_stats(self._h, C.byref(n), C.byref(b)), "pwa_ctx_poison_stats")
+        return dict(buffers=n.value, bytes=b.value)
 
     def _check(self, rc, what):
         if rc != 0:

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <string>
 
+#include "poison.h"
+
 struct pwa_ctx;
 
 namespace pwa {
@@ -25,6 +27,7 @@ struct ApproxCtxView {
     uint32_t chunk = 0;              // PWA_APPROX_CHUNK: most text columns a task reports
     uint64_t occ_chunk_hits = 0;     // PWA_OCC_CHUNK_HITS (0: the library's budget)
     std::string* err = nullptr;      // the context's last-error text
+    Poison* poison = nullptr;        // the context's PWA_POISON state: every device allocation of the unit goes through poison_device
     ApproxStats* stats = nullptr;
     ApproxStartsStats* starts_stats = nullptr;
 };

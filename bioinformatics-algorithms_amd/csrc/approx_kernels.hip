@@ -28,10 +28,12 @@ struct Dev {   // one device allocation, freed with its owner
     Dev(const Dev&) = delete;
     Dev& operator=(const Dev&) = delete;
     ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) {
+    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
         if (p) (void)hipFree(p);
         p = nullptr;
-        return hipMalloc(&p, std::max<size_t>(bytes, 16));
+        bytes = std::max<size_t>(bytes, 16);
+        const hipError_t e = hipMalloc(&p, bytes);
+        return e == hipSuccess ? pwa::poison_device(po, p, bytes) : e;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
@@ -144,10 +146,10 @@ void stage_inputs(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, u
     }
     (void)hipSetDevice(v.device);
     s.tbytes = (n + 15) / 16 * 16 + 16;
-    AP_CHECK(s.text.alloc(s.tbytes));
-    AP_CHECK(s.blob.alloc(bytes));
-    AP_CHECK(s.d_pats.alloc((size_t)n_pat * sizeof(Pat)));
-    AP_CHECK(s.peq.alloc(s.peq_words * 8));
+    AP_CHECK(s.text.alloc(v.poison, s.tbytes));
+    AP_CHECK(s.blob.alloc(v.poison, bytes));
+    AP_CHECK(s.d_pats.alloc(v.poison, (size_t)n_pat * sizeof(Pat)));
+    AP_CHECK(s.peq.alloc(v.poison, s.peq_words * 8));
     AP_CHECK(hipMemsetAsync(s.text.p, 0, s.tbytes, v.stream));
     AP_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
     AP_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
@@ -197,11 +199,11 @@ void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uin
     }
     s.first_wave[kMaxWords + 1] = (uint32_t)(lane_task.size() / 64);
 
-    AP_CHECK(s.tasks.alloc(nt * sizeof(Task)));
-    AP_CHECK(s.lane_task.alloc(lane_task.size() * 4));
-    AP_CHECK(s.task_cnt.alloc(nt * 4));
-    AP_CHECK(s.pat_cnt.alloc((size_t)n_pat * 4));
-    AP_CHECK(s.pat_best.alloc((size_t)n_pat * 8));
+    AP_CHECK(s.tasks.alloc(v.poison, nt * sizeof(Task)));
+    AP_CHECK(s.lane_task.alloc(v.poison, lane_task.size() * 4));
+    AP_CHECK(s.task_cnt.alloc(v.poison, nt * 4));
+    AP_CHECK(s.pat_cnt.alloc(v.poison, (size_t)n_pat * 4));
+    AP_CHECK(s.pat_best.alloc(v.poison, (size_t)n_pat * 8));
     Events ev;
     AP_CHECK(hipEventCreate(&ev.a));
     AP_CHECK(hipEventCreate(&ev.b));
@@ -254,9 +256,9 @@ void fill_pass(const pwa::ApproxCtxView& v, Search& s, uint64_t* occ) {
     }
     if (slices.empty()) return;
     Dev off, part, stage;
-    AP_CHECK(off.alloc((size_t)max_nt * 4));
-    AP_CHECK(part.alloc(pwa::scan_part_words(max_nt) * 4));
-    AP_CHECK(stage.alloc(max_hits * 8));
+    AP_CHECK(off.alloc(v.poison, (size_t)max_nt * 4));
+    AP_CHECK(part.alloc(v.poison, pwa::scan_part_words(max_nt) * 4));
+    AP_CHECK(stage.alloc(v.poison, max_hits * 8));
     Events ev;
     AP_CHECK(hipEventCreate(&ev.a));
     AP_CHECK(hipEventCreate(&ev.b));
@@ -313,8 +315,8 @@ void starts_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, ui
     const uint64_t budget = std::min(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultSliceHits, kMaxSliceHits);
     const uint64_t slice_cap = std::min(budget, total);
     Dev recs, starts;
-    AP_CHECK(recs.alloc(slice_cap * sizeof(Hit)));
-    AP_CHECK(starts.alloc(total * 4));
+    AP_CHECK(recs.alloc(v.poison, slice_cap * sizeof(Hit)));
+    AP_CHECK(starts.alloc(v.poison, total * 4));
     Events ev;
     AP_CHECK(hipEventCreate(&ev.a));
     AP_CHECK(hipEventCreate(&ev.b));

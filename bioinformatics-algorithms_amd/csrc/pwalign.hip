@@ -318,7 +318,7 @@ int upload_arena(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std::ve
     if (arena_bytes >= 0xffffffffull) return fail(ctx, PWA_E_CAPACITY, "sequence arena exceeds 4 GiB");
     uint8_t code8[256];
     for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)(al.code_of[v] >= 0 ? al.code_of[v] : 7);
-    HIPC(ctx, b->arena.alloc(arena_bytes));
+    HIPC(ctx, b->arena.alloc(ctx, arena_bytes));
     HIPC(ctx, build_arena(ctx, b->arena.p, arena_bytes, in.seq_bytes, in.seq_off, in.n_seq, is_used, aoff, f.coded ? code8 : nullptr,
                           !al.present[0] && !al.pattern_has[0]));
     return PWA_OK;
@@ -680,7 +680,7 @@ int upload_lane_rows(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Alp
     // The rows are built straight in the context's two page-locked arena buffers, in pieces of whole tasks (~32 MiB), by several host
     // threads, while the previous piece is on its way (copy stream) -- like build_arena.  (Until r03: one thread, byte by byte into a
     // heap buffer, then through the bounce buffer: 156 ms of a 159 ms call for 131 072 pairs 150 x 2000.)
-    HIPC(ctx, b->lane_text.alloc(total + 64));
+    HIPC(ctx, b->lane_text.alloc(ctx, total + 64));
     uint8_t code8[256];
     for (int v = 0; v < 256; ++v) code8[v] = (uint8_t)al.code_of[v];
     constexpr uint64_t kPiece = 32ull << 20;
@@ -798,19 +798,19 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
         if (rc != PWA_OK) return rc;
     }
     if (own_texts) {
-        HIPC(ctx, b->slot_toff.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, b->slot_toff.alloc(ctx, nt * kTaskLanes * 4));
         HIPC(ctx, hipMemcpy(b->slot_toff.p, stoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-        HIPC(ctx, b->slot_tlen.alloc(nt * kTaskLanes * 4));
+        HIPC(ctx, b->slot_tlen.alloc(ctx, nt * kTaskLanes * 4));
         HIPC(ctx, hipMemcpy(b->slot_tlen.p, stlen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
     }
     clock.mark("choose R + slot arrays");
-    HIPC(ctx, b->tasks.alloc(nt * sizeof(BatchTask)));
+    HIPC(ctx, b->tasks.alloc(ctx, nt * sizeof(BatchTask)));
     HIPC(ctx, hipMemcpy(b->tasks.p, tasks, nt * sizeof(BatchTask), hipMemcpyHostToDevice));
-    HIPC(ctx, b->slot_poff.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, b->slot_poff.alloc(ctx, nt * kTaskLanes * 4));
     HIPC(ctx, hipMemcpy(b->slot_poff.p, spoff, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-    HIPC(ctx, b->slot_plen.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, b->slot_plen.alloc(ctx, nt * kTaskLanes * 4));
     HIPC(ctx, hipMemcpy(b->slot_plen.p, splen, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
-    HIPC(ctx, b->slot_out.alloc(nt * kTaskLanes * 4));
+    HIPC(ctx, b->slot_out.alloc(ctx, nt * kTaskLanes * 4));
     HIPC(ctx, hipMemcpy(b->slot_out.p, sout, nt * kTaskLanes * 4, hipMemcpyHostToDevice));
 
     if (b->lanes) b->kernel_name = std::string(b->kernel_name).insert(b->kernel_name.size() - 1, ",LANES");
@@ -844,8 +844,9 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
             b->hand.bytes = ctx->hand_cache_bytes;
             ctx->hand_cache = nullptr;
             ctx->hand_cache_bytes = 0;
+            HIPC(ctx, poison_device(&ctx->poison, b->hand.p, b->hand.bytes));
         } else {
-            HIPC(ctx, b->hand.alloc(hand_bytes));
+            HIPC(ctx, b->hand.alloc(ctx, hand_bytes));
         }
     }
 
@@ -919,7 +920,7 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         mini_lists[c].second.push_back(k);
     }
     const size_t nl = pairs.size();
-    HIPC(ctx, b->pair_res.alloc(nl * sizeof(PairResult)));
+    HIPC(ctx, b->pair_res.alloc(ctx, nl * sizeof(PairResult)));
     HIPC(ctx, hipMemset(b->pair_res.p, 0, nl * sizeof(PairResult)));
     size_t q_next = 0;
     auto describe = [&](uint32_t k, size_t q) {
@@ -1018,7 +1019,7 @@ int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std
         if (c == classes.size()) classes.push_back({rl, ln, {}});
         classes[c].lst.push_back(k);
     }
-    HIPC(ctx, b->pair_res.alloc(pairs.size() * sizeof(PairResult)));
+    HIPC(ctx, b->pair_res.alloc(ctx, pairs.size() * sizeof(PairResult)));
     HIPC(ctx, hipMemset(b->pair_res.p, 0, pairs.size() * sizeof(PairResult)));
     static const char* const kModeName[3] = {"NW", "SW", "SG"};
     size_t q_next = 0;
@@ -1111,14 +1112,14 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
     int rc = scan_pairs(ctx, b, in, lp);
     if (rc != PWA_OK) return rc;
     b->n_live = lp.live.size();
-    HIPC(ctx, b->scores.alloc(std::max<uint64_t>(n_pairs, 1) * sizeof(int32_t)));
+    HIPC(ctx, b->scores.alloc(ctx, std::max<uint64_t>(n_pairs, 1) * sizeof(int32_t)));
     if (lp.any_trivial_score) HIPC(ctx, upload_via_bounce(ctx, b->scores.p, b->host_scores.data(), n_pairs * sizeof(int32_t)));
     else {   // (on the copy stream and waited for: a run may be enqueued on any stream afterwards -- and the context's own stream may be
              // busy with the previous batch's run, which preparing this one must not wait for)
         HIPC(ctx, hipMemsetAsync(b->scores.p, 0, std::max<uint64_t>(n_pairs, 1) * sizeof(int32_t), ctx->copy_stream));
         HIPC(ctx, hipStreamSynchronize(ctx->copy_stream));
     }
-    HIPC(ctx, b->queue.alloc(64));   // (the event ring of the runs is created run by run: pwa_batch_run)
+    HIPC(ctx, b->queue.alloc(ctx, 64));   // (the event ring of the runs is created run by run: pwa_batch_run)
     if (lp.live.empty()) {
         b->kernel_name = "none";
         guard.b = nullptr;

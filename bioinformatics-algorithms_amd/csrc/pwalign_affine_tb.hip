@@ -111,7 +111,7 @@ int build_raw_arena(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector<uint
     std::vector<uint8_t> host_arena(arena_bytes, 0);
     for (uint32_t s = 0; s < rq.n_seq; ++s)
         if (is_used[s] && rq.slen(s)) std::memcpy(host_arena.data() + ar.aoff[s], rq.seq_bytes + rq.seq_off[s], rq.slen(s));
-    HIPC(ctx, ar.arena.alloc(arena_bytes));
+    HIPC(ctx, ar.arena.alloc(ctx, arena_bytes));
     HIPC(ctx, upload_via_bounce(ctx, ar.arena.p, host_arena.data(), arena_bytes));
     return PWA_OK;
 }
@@ -228,18 +228,18 @@ std::vector<uint32_t> split_off_stripe_pairs(const pwa_ctx* ctx, const AffTbRequ
 
 // ---- the call's result buffers, the strips' queue word and (for n_strip_tasks > 0) their hand-off halves
 int take_result_buffers(pwa_ctx* ctx, const AffTbRequest& rq, const AffLive& lp, size_t n_strip_tasks, AffResults& rs) {
-    HIPC(ctx, rs.d_scores.alloc(rq.n_pairs * sizeof(int32_t)));
-    HIPC(ctx, rs.d_nops.alloc(rq.n_pairs * sizeof(uint32_t)));
-    HIPC(ctx, rs.d_queue.alloc(64));
+    HIPC(ctx, rs.d_scores.alloc(ctx, rq.n_pairs * sizeof(int32_t)));
+    HIPC(ctx, rs.d_nops.alloc(ctx, rq.n_pairs * sizeof(uint32_t)));
+    HIPC(ctx, rs.d_queue.alloc(ctx, 64));
     rs.dev_ops_off.assign(rq.n_pairs, 0);
     for (uint32_t k : lp.live) {
         rs.dev_ops_off[k] = rs.ops_total;
         rs.ops_total += align_up(rq.slen(rq.pair_a[k]) + rq.slen(rq.pair_b[k]) + 1, 16);
     }
-    HIPC(ctx, rs.d_ops.alloc(rs.ops_total));
+    HIPC(ctx, rs.d_ops.alloc(ctx, rs.ops_total));
     rs.half = ((lp.max_m + 3) / 4 + 1) * 192 * 4;   // int32 per half: three int4 per lane per 4-column block
     rs.grid_cap = (uint32_t)std::min<uint64_t>(n_strip_tasks, (uint64_t)ctx->num_cu * 2);
-    if (rs.grid_cap) HIPC(ctx, rs.d_hand.alloc((size_t)rs.grid_cap * 2 * rs.half * sizeof(int32_t)));
+    if (rs.grid_cap) HIPC(ctx, rs.d_hand.alloc(ctx, (size_t)rs.grid_cap * 2 * rs.half * sizeof(int32_t)));
     rs.h_nops.assign(rq.n_pairs, 0);
     return PWA_OK;
 }
@@ -270,8 +270,8 @@ int affine_tb_on_stripes(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector
                      (double)band_cap / 1e9, (double)cap / 1e9);
     DevBuf d_band, d_res_own;
     void *p_band = nullptr, *p_res = nullptr;
-    HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, band_cap + kWalkPad, d_band, &p_band));
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
+    HIPC(ctx, cached_workspace(ctx, ctx->band_cache, ctx->band_cache_bytes, band_cap + kWalkPad, d_band, &p_band));
+    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
     PairResult* const d_res = static_cast<PairResult*>(p_res);
     for (const auto& ch : chunks) {
         const size_t nc = ch.second - ch.first;
@@ -355,18 +355,18 @@ int run_strip_chunk(pwa_ctx* ctx, const AffTbRequest& rq, const AffArena& ar, co
         at += h.tb_dwords;
     }
     DevBuf d_tb, d_tasks, d_spoff, d_splen, d_sout, d_tboff, d_wp;
-    HIPC(ctx, d_tb.alloc(dw * 4));
-    HIPC(ctx, d_tasks.alloc(nt * sizeof(BatchTask)));
+    HIPC(ctx, d_tb.alloc(ctx, dw * 4));
+    HIPC(ctx, d_tasks.alloc(ctx, nt * sizeof(BatchTask)));
     HIPC(ctx, upload_via_bounce(ctx, d_tasks.p, tasks.data(), nt * sizeof(BatchTask)));
-    HIPC(ctx, d_spoff.alloc(nt * 64 * 4));
+    HIPC(ctx, d_spoff.alloc(ctx, nt * 64 * 4));
     HIPC(ctx, upload_via_bounce(ctx, d_spoff.p, spoff.data(), nt * 64 * 4));
-    HIPC(ctx, d_splen.alloc(nt * 64 * 4));
+    HIPC(ctx, d_splen.alloc(ctx, nt * 64 * 4));
     HIPC(ctx, upload_via_bounce(ctx, d_splen.p, splen.data(), nt * 64 * 4));
-    HIPC(ctx, d_sout.alloc(nt * 64 * 4));
+    HIPC(ctx, d_sout.alloc(ctx, nt * 64 * 4));
     HIPC(ctx, upload_via_bounce(ctx, d_sout.p, sout.data(), nt * 64 * 4));
-    HIPC(ctx, d_tboff.alloc(nt * sizeof(uint64_t)));
+    HIPC(ctx, d_tboff.alloc(ctx, nt * sizeof(uint64_t)));
     HIPC(ctx, upload_via_bounce(ctx, d_tboff.p, tboff.data(), nt * sizeof(uint64_t)));
-    HIPC(ctx, d_wp.alloc(wp.size() * sizeof(AffineWalkPair)));
+    HIPC(ctx, d_wp.alloc(ctx, wp.size() * sizeof(AffineWalkPair)));
     HIPC(ctx, upload_via_bounce(ctx, d_wp.p, wp.data(), wp.size() * sizeof(AffineWalkPair)));
 
     AffineTbParams T;

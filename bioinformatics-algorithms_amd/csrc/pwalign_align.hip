@@ -227,7 +227,7 @@ int build_align_arena(pwa_ctx* ctx, const AlignRequest& rq, AlignClock& clock, A
     ar.dash_sym = !dash_seen ? 0x100 : (ar.coded ? (int32_t)ar.code_of[(unsigned char)'-'] : (int32_t)'-');
     clock.mark("validate + alphabet scan");
     void* p_arena = nullptr;
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_ARENA], ctx->pool_bytes[pwa_ctx::POOL_ARENA], arena_bytes, ar.arena_own, &p_arena));
+    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_ARENA], ctx->pool_bytes[pwa_ctx::POOL_ARENA], arena_bytes, ar.arena_own, &p_arena));
     HIPC(ctx, build_arena(ctx, p_arena, arena_bytes, rq.seq_bytes, rq.seq_off, rq.n_seq, is_used, ar.aoff, ar.coded ? ar.code_of : nullptr, !nul_seen));
     ar.base = static_cast<uint8_t*>(p_arena);
     clock.mark("arena upload");
@@ -483,14 +483,14 @@ int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& pl
     ws.aux_part_at = ws.aux_len_at + align_up(len_words * 4, 256);
     if (rp.ranges.empty()) return PWA_OK;
     // + one traceback window: the walk stages whole windows
-    if (!rq.scores_only()) HIPC(ctx, cached_workspace(ctx->band_cache, ctx->band_cache_bytes, rp.band_cap + 32768, ws.d_band, &ws.p_band));
+    if (!rq.scores_only()) HIPC(ctx, cached_workspace(ctx, ctx->band_cache, ctx->band_cache_bytes, rp.band_cap + 32768, ws.d_band, &ws.p_band));
     if (plan.sband)
-        HIPC(ctx, cached_workspace(ctx->sband_cache, ctx->sband_cache_bytes, rp.band_cap * sizeof(int32_t), ws.d_sband, &ws.p_sband));
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
-    HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * rq.res_bytes(), ws.d_res_own, &ws.p_res));
+        HIPC(ctx, cached_workspace(ctx, ctx->sband_cache, ctx->sband_cache_bytes, rp.band_cap * sizeof(int32_t), ws.d_sband, &ws.p_sband));
+    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
+    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * rq.res_bytes(), ws.d_res_own, &ws.p_res));
     if (rq.want_str()) {
-        HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], rp.str_cap, ws.d_str_own, &ws.p_str));
-        HIPC(ctx, cached_workspace(ctx->pool[pwa_ctx::POOL_STR_AUX], ctx->pool_bytes[pwa_ctx::POOL_STR_AUX],
+        HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], rp.str_cap, ws.d_str_own, &ws.p_str));
+        HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_STR_AUX], ctx->pool_bytes[pwa_ctx::POOL_STR_AUX],
                                    ws.aux_part_at + pwa::scan_part_words(len_words) * 4, ws.d_aux_own, &ws.p_aux));
     }
     return PWA_OK;
@@ -1261,11 +1261,11 @@ int pwa_align_matrices(pwa_ctx* ctx, int mode, int match, int mismatch, int gap,
     const uint64_t kRL = (uint64_t)geom.rl;
     const uint64_t band = mini_rl ? (uint64_t)mini_band_steps(m) * 16 * kRL : tb_band_bytes(n, m, geom.rl);   // (wide: one 64 RL-row stripe)
     DevBuf d_pat, d_txt, d_band, d_sband, d_res;
-    HIPC(ctx, d_pat.alloc(n + 64));
-    HIPC(ctx, d_txt.alloc(m + 64));
-    HIPC(ctx, d_band.alloc((mini_rl ? 4 : 1) * band + 32768));
-    HIPC(ctx, d_sband.alloc((mini_rl ? 4 : 1) * band * sizeof(int32_t)));
-    HIPC(ctx, d_res.alloc(sizeof(PairResult)));
+    HIPC(ctx, d_pat.alloc(ctx, n + 64));
+    HIPC(ctx, d_txt.alloc(ctx, m + 64));
+    HIPC(ctx, d_band.alloc(ctx, (mini_rl ? 4 : 1) * band + 32768));
+    HIPC(ctx, d_sband.alloc(ctx, (mini_rl ? 4 : 1) * band * sizeof(int32_t)));
+    HIPC(ctx, d_res.alloc(ctx, sizeof(PairResult)));
     if (mini_rl || wide_rl) {
         std::vector<uint8_t> cp(n), ct(m);
         for (uint64_t o = 0; o < n; ++o) cp[o] = code_of[pattern[o]];

@@ -88,6 +88,7 @@ void Knobs::read() {
     prof16_int = num("PWA_PROF16_INT", -1);
     affine_tb_route = num("PWA_AFFINE_TB_ROUTE", -1);
     if (const char* e = std::getenv("PWA_OCC_CHUNK_HITS")) occ_chunk_hits = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    poison = parse_poison(std::getenv("PWA_POISON"));
     if (const char* e = std::getenv("PWA_APPROX_CHUNK")) approx_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)), 1u << 30);
 }
 
@@ -98,6 +99,7 @@ pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
     v.debug = c->knobs.debug;
     v.occ_chunk_hits = c->knobs.occ_chunk_hits;
     v.err = &c->err;
+    v.poison = &c->poison;
     return v;
 }
 
@@ -109,6 +111,7 @@ pwa::ApproxCtxView pwa::approx_ctx_view(pwa_ctx* c) {
     v.chunk = c->knobs.approx_chunk;
     v.occ_chunk_hits = c->knobs.occ_chunk_hits;
     v.err = &c->err;
+    v.poison = &c->poison;
     v.stats = &c->approx_stats;
     v.starts_stats = &c->approx_starts_stats;
     return v;
@@ -166,7 +169,40 @@ void DevBuf::release() {
     p = nullptr;
     bytes = 0;
 }
-hipError_t DevBuf::alloc(size_t n) {
+// PWA_POISON (poison.h).  The fill is a test mode: the device is drained before it, so that nothing enqueued earlier on any of the
+// context's (non-blocking) streams still uses the buffer, and after it, so that nothing enqueued later can overtake it.
+int parse_poison(const char* s) {
+    if (!s) return -1;
+    const bool hex = s[0] == '0' && (s[1] == 'x' || s[1] == 'X');
+    const char* d = hex ? s + 2 : s;
+    if (!*d) return -2;
+    unsigned v = 0;
+    for (; *d; ++d) {
+        const int c = (unsigned char)*d;
+        const int digit = c >= '0' && c <= '9' ? c - '0' : hex && c >= 'a' && c <= 'f' ? c - 'a' + 10 : hex && c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (digit < 0) return -2;
+        v = v * (hex ? 16u : 10u) + (unsigned)digit;
+        if (v > 255) return -2;
+    }
+    return (int)v;
+}
+hipError_t poison_device(Poison* po, void* p, size_t cap) {
+    if (!po || po->byte < 0) return hipSuccess;
+    if (!p || !cap) return hipSuccess;
+    hipError_t e = hipSetDevice(po->device);   // (hipDeviceSynchronize and hipMemset act on the current device)
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, po->byte, cap);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) ++po->buffers, po->bytes += cap;
+    return e;
+}
+void poison_host(Poison* po, void* p, size_t cap) {
+    if (!po || po->byte < 0 || !p || !cap) return;
+    std::memset(p, po->byte, cap);
+    ++po->buffers, po->bytes += cap;
+}
+
+hipError_t DevBuf::alloc(pwa_ctx* ctx, size_t n) {
     release();
     if (n == 0) n = 16;
     if (pool) {   // best fit among the kept buffers: at least n, at most 2 n + 1 MiB (a 5 GB block is not spent on a 1 KB request)
@@ -180,7 +216,7 @@ hipError_t DevBuf::alloc(size_t n) {
             bytes = pool->free_list[best].second;
             pool->free_list_bytes -= bytes;
             pool->free_list.erase(pool->free_list.begin() + (long)best);
-            return hipSuccess;
+            return poison_device(&ctx->poison, p, bytes);
         }
     }
     hipError_t e = hipMalloc(&p, n);
@@ -193,7 +229,7 @@ hipError_t DevBuf::alloc(size_t n) {
     }
     if (e == hipSuccess) bytes = n;
     else p = nullptr;
-    return e;
+    return e == hipSuccess ? poison_device(&ctx->poison, p, bytes) : e;
 }
 
 // Stable LSD radix sort of `idx` by 64-bit keys (16-bit digits; passes whose digit is constant are skipped).
@@ -285,9 +321,9 @@ int wide_rl_for(uint64_t n) { return n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12
 
 // A workspace of `bytes` from the context's cache slot (see pwa_ctx): reused when big enough, regrown otherwise;
 // requests beyond kBandCacheMax are served by `fallback` and freed with it.
-hipError_t cached_workspace(void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out) {
+hipError_t cached_workspace(pwa_ctx* ctx, void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out) {
     if (bytes > kBandCacheMax) {
-        const hipError_t e = fallback.alloc(bytes);
+        const hipError_t e = fallback.alloc(ctx, bytes);
         *out = fallback.p;
         return e;
     }
@@ -303,7 +339,7 @@ hipError_t cached_workspace(void*& slot, size_t& slot_bytes, size_t bytes, DevBu
         slot_bytes = bytes;
     }
     *out = slot;
-    return hipSuccess;
+    return poison_device(&ctx->poison, slot, slot_bytes);   // regrown or reused as it is: the whole slot
 }
 
 // pageable memory that the library does not own (or that is too large to mirror in page-locked memory): through a bounce buffer
@@ -593,7 +629,7 @@ int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, hipEvent_t after_fill) {
     } else {
         HIPC(ctx, hipMemsetAsync(p_progress, 0, progress_bytes, st));
         if (!ctx->knobs.stamps.empty()) {
-            HIPC(ctx, stamps.alloc(n_stripes * 32 + 4 * 8192 * 8));
+            HIPC(ctx, stamps.alloc(ctx, n_stripes * 32 + 4 * 8192 * 8));
             HIPC(ctx, hipMemsetAsync(stamps.p, 0, n_stripes * 32 + 4 * 8192 * 8, st));
             G.stamps = stamps.as<unsigned long long>();
             G.trace_base = (uint32_t)(n_stripes * 4);
@@ -707,7 +743,7 @@ int subst_prepare(pwa_ctx* ctx, const uint8_t* code, int n_sym, const int32_t* s
 }
 int subst_upload(pwa_ctx* ctx, SubstTable& t) {
     t.dev.pool = ctx;
-    HIPC(ctx, t.dev.alloc(t.blob.size() * sizeof(uint32_t)));
+    HIPC(ctx, t.dev.alloc(ctx, t.blob.size() * sizeof(uint32_t)));
     HIPC(ctx, upload_via_bounce(ctx, t.dev.p, t.blob.data(), t.blob.size() * sizeof(uint32_t)));
     return PWA_OK;
 }
@@ -924,6 +960,16 @@ int pwa_selftest_host(uint32_t seed) try {
             if (idx != want) return check;
         }
     }
+    {   // PWA_POISON's value: decimal or 0x.., 0 .. 255, nothing else; unset is not an error
+        ++check;
+        static const struct { const char* s; int want; } cases[] = {
+            {nullptr, -1}, {"0", 0}, {"1", 1}, {"255", 255}, {"0x00", 0}, {"0x80", 128}, {"0X7f", 127}, {"0xFF", 255}, {"0xff", 255}, {"007", 7},
+            {"", -2}, {"256", -2}, {"0x100", -2}, {"0x", -2}, {"-1", -2}, {"+1", -2}, {" 1", -2}, {"1 ", -2}, {"12a", -2}, {"ff", -2}, {"0xg", -2},
+            {"4294967297", -2}, {"0x100000001", -2}, {"1.0", -2}, {"true", -2},
+        };
+        for (const auto& c : cases)
+            if (parse_poison(c.s) != c.want) return check;
+    }
     if (const int rc = selftest_pair_forms()) return check + rc;
     if (const int rc = selftest_banded_forms()) return check + 2 + rc;
     return selftest_align_plan(x, check + 5);
@@ -957,6 +1003,13 @@ int pwa_ctx_create(int device, pwa_ctx** out) {
     pwa_ctx* c = new (std::nothrow) pwa_ctx();
     if (!c) return PWA_E_NOMEM;
     c->knobs.read();   // the only place the library's switches are read from the environment
+    if (c->knobs.poison == -2) {   // PWA_POISON set to something that is no byte: a run that poisons nothing must not look like one that does
+        delete c;
+        return PWA_E_INVALID;
+    }
+    c->poison.byte = c->knobs.poison;
+    c->poison.device = device;
+    for (PinnedBuf& pb : c->pin) pb.poison = &c->poison;
     c->device = device;
     c->num_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1000,6 +1053,13 @@ void pwa_ctx_destroy(pwa_ctx* c) {
 }
 
 const char* pwa_last_error(const pwa_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+int pwa_ctx_poison_stats(const pwa_ctx* c, uint64_t* buffers, uint64_t* bytes) {
+    if (!c) return PWA_E_INVALID;
+    if (buffers) *buffers = c->poison.buffers;
+    if (bytes) *bytes = c->poison.bytes;
+    return PWA_OK;
+}
 
 int pwa_ctx_set_score_band(pwa_ctx* c, int on) {
     if (!c) return PWA_E_INVALID;

@@ -17,6 +17,7 @@
 
 #include "approx_ctx.h"
 #include "kernel_table.h"
+#include "poison.h"
 #include "subst_table.h"
 
 // Host-side source / destination of the library's own host <-> device copies: page-locked, grow-only, kept in the context.
@@ -26,20 +27,26 @@
 struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;
+    pwa::Poison* poison = nullptr;   // the owning context's PWA_POISON state (pwa_ctx_create)
     PinnedBuf() = default;
     PinnedBuf(const PinnedBuf&) = delete;
     PinnedBuf& operator=(const PinnedBuf&) = delete;
     ~PinnedBuf() { if (p) (void)hipHostFree(p); }
     hipError_t reserve(size_t n) {   // contents are NOT kept
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        n = (n + (n >> 2) + 4095) & ~(size_t)4095;   // 25 % headroom: few regrowths
-        const hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
-        if (e == hipSuccess) cap = n;
-        else p = nullptr;
-        return e;
+        if (n > cap) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+            cap = 0;
+            n = (n + (n >> 2) + 4095) & ~(size_t)4095;   // 25 % headroom: few regrowths
+            const hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
+            if (e != hipSuccess) {
+                p = nullptr;
+                return e;
+            }
+            cap = n;
+        }
+        pwa::poison_host(poison, p, cap);   // PWA_POISON: every reserve, regrown or not
+        return hipSuccess;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
@@ -83,6 +90,8 @@ struct Knobs {
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count
     int banded_rl = 0;                          // PWA_BANDED_RL: 4 | 8 = every banded pair (alignments and scores) on stripes of 64 x 4 / 64 x 8 rows (tests), unset = by band width
+    int poison = -1;                            // PWA_POISON=<byte>: every buffer handed to a call reads as that byte until the call writes it (poison.h);
+                                                // -2: a value that does not parse, pwa_ctx_create fails
     void read();   // (pwalign_ctx.hip)
 };
 
@@ -103,6 +112,7 @@ struct AffineAlignStats {
 // ------------------------------------------------------------------------------------ context
 struct pwa_ctx {
     Knobs knobs;
+    pwa::Poison poison;   // PWA_POISON: the byte and the running totals of pwa_ctx_poison_stats; every acquisition site passes &poison
     int device = 0;
     int num_cu = 256;
     hipStream_t stream = nullptr;
@@ -164,7 +174,7 @@ struct DevBuf {   // RAII device allocation; with `pool` set, released buffers g
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
     void release();
-    hipError_t alloc(size_t n);
+    hipError_t alloc(pwa_ctx* ctx, size_t n);   // ctx: whose PWA_POISON applies (never null; `pool` only says where released buffers go)
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
@@ -190,7 +200,7 @@ bool gap0_ok(uint64_t n_plus_m, int match, int mismatch, int gap);
 bool code_alphabet(const bool seen[256], uint8_t code_of[256], int match, int mismatch, int gap, const Knobs& knobs);
 int mini_rl_for(uint64_t n);
 int wide_rl_for(uint64_t n);
-hipError_t cached_workspace(void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out);
+hipError_t cached_workspace(pwa_ctx* ctx, void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out);
 hipError_t upload_via_bounce(pwa_ctx* c, void* dst, const void* src, size_t bytes);
 hipError_t build_arena(pwa_ctx* c, void* d_arena, uint64_t arena_bytes, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
                        const std::vector<uint8_t>& is_used, const std::vector<uint64_t>& aoff, const uint8_t* table, bool nul_free = false);
@@ -355,8 +365,8 @@ struct PairLaunch {
     size_t progress_bytes = 0;
     hipError_t take(pwa_ctx* ctx, DevBuf& own, int slot, size_t bytes, void** out) {
         if (bytes == 0) bytes = 16;
-        if (from_pool) return cached_workspace(ctx->pool[slot], ctx->pool_bytes[slot], bytes, own, out);
-        const hipError_t e = own.alloc(bytes);
+        if (from_pool) return cached_workspace(ctx, ctx->pool[slot], ctx->pool_bytes[slot], bytes, own, out);
+        const hipError_t e = own.alloc(ctx, bytes);
         *out = own.p;
         return e;
     }

@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <string>
 
+#include "poison.h"
+
 struct pwa_ctx;
 
 namespace pwa {
@@ -15,6 +17,7 @@ struct SaCtxView {
     bool debug = false;              // PWA_DEBUG
     uint64_t occ_chunk_hits = 0;     // PWA_OCC_CHUNK_HITS (0: the library's budget)
     std::string* err = nullptr;      // the context's last-error text
+    Poison* poison = nullptr;        // the context's PWA_POISON state: every device allocation of the unit goes through poison_device
 };
 SaCtxView sa_ctx_view(pwa_ctx* c);
 // The suffix-array unit's reduce-then-scan over uint32 (sufarr_kernels.hip), enqueued on s: x[0 .. len) := its exclusive prefix

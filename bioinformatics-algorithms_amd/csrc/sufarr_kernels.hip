@@ -35,10 +35,12 @@ struct Dev {   // one device allocation, freed with its owner
     Dev(const Dev&) = delete;
     Dev& operator=(const Dev&) = delete;
     ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) {
+    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
         if (p) (void)hipFree(p);
         p = nullptr;
-        return hipMalloc(&p, std::max<size_t>(bytes, 16));
+        bytes = std::max<size_t>(bytes, 16);
+        const hipError_t e = hipMalloc(&p, bytes);
+        return e == hipSuccess ? pwa::poison_device(po, p, bytes) : e;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
@@ -81,11 +83,11 @@ struct SortBufs {
 // Scratch of radix_sort for up to n elements: the digit-major histogram, the scan's chunk sums, the key-bit partials.
 struct SortScratch {
     Dev hist, part, bits;
-    void alloc(size_t n) {
+    void alloc(pwa::Poison* po, size_t n) {
         const size_t tiles = std::max<size_t>(1, (n + kTile - 1) / kTile);
-        SA_CHECK(hist.alloc(tiles * kBuckets * 4));
-        SA_CHECK(part.alloc(((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
-        SA_CHECK(bits.alloc((2 * 1024 + 2) * 8));
+        SA_CHECK(hist.alloc(po, tiles * kBuckets * 4));
+        SA_CHECK(part.alloc(po, ((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
+        SA_CHECK(bits.alloc(po, (2 * 1024 + 2) * 8));
     }
 };
 
@@ -131,10 +133,10 @@ void search(pwa::SaCtxView& v, const pwa_sa_index* ix, const uint8_t* pb, const 
     const uint64_t base = poff[0], bytes = poff[n_pat] - base;
     std::vector<uint64_t> off(poff, poff + n_pat + 1);
     for (auto& o : off) o -= base;
-    SA_CHECK(r.blob.alloc((bytes + 7) / 8 * 8 + 16));
-    SA_CHECK(r.off.alloc(off.size() * 8));
-    SA_CHECK(r.lo.alloc((size_t)n_pat * 4));
-    SA_CHECK(r.cnt.alloc((size_t)n_pat * 4 + 4));
+    SA_CHECK(r.blob.alloc(v.poison, (bytes + 7) / 8 * 8 + 16));
+    SA_CHECK(r.off.alloc(v.poison, off.size() * 8));
+    SA_CHECK(r.lo.alloc(v.poison, (size_t)n_pat * 4));
+    SA_CHECK(r.cnt.alloc(v.poison, (size_t)n_pat * 4 + 4));
     SA_CHECK(hipMemsetAsync(r.blob.p, 0, (bytes + 7) / 8 * 8 + 16, v.stream));
     SA_CHECK(hipMemcpyAsync(r.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
     SA_CHECK(hipMemcpyAsync(r.off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, v.stream));
@@ -178,7 +180,9 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
         const auto t0 = std::chrono::steady_clock::now();
         const size_t tbytes = (n + 7) / 8 * 8 + 16;
         SA_CHECK(hipMalloc(&ix->d_text, tbytes));
+        SA_CHECK(pwa::poison_device(v.poison, ix->d_text, tbytes));
         SA_CHECK(hipMalloc(&ix->d_sa, std::max<size_t>(n, 1) * 4));
+        SA_CHECK(pwa::poison_device(v.poison, ix->d_sa, std::max<size_t>(n, 1) * 4));
         SA_CHECK(hipMemsetAsync(ix->d_text, 0, tbytes, v.stream));
         if (n) SA_CHECK(hipMemcpyAsync(ix->d_text, text, n, hipMemcpyHostToDevice, v.stream));
         // alphabet: codes 1 .. sigma in signed-char order, as few bits per code as sigma allows, as many codes per 64-bit key as fit
@@ -207,11 +211,11 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
         if (n) {
             Dev key2, val2, rank, head;
             SortScratch sc;
-            SA_CHECK(key2.alloc(n * 8 * 2));
-            SA_CHECK(val2.alloc(n * 4));
-            SA_CHECK(rank.alloc(n * 4));
-            SA_CHECK(head.alloc((n + 1) * 4));
-            sc.alloc(n);
+            SA_CHECK(key2.alloc(v.poison, n * 8 * 2));
+            SA_CHECK(val2.alloc(v.poison, n * 4));
+            SA_CHECK(rank.alloc(v.poison, n * 4));
+            SA_CHECK(head.alloc(v.poison, (n + 1) * 4));
+            sc.alloc(v.poison, n);
             SortBufs<uint64_t, uint32_t> b{{key2.as<uint64_t>(), key2.as<uint64_t>() + n}, {ix->d_sa, val2.as<uint32_t>()}, 0};
             const uint32_t nb = blocks_for(n, kThreads), nn = (uint32_t)n;
             sa_first_key_kernel<<<nb, kThreads, 0, v.stream>>>(ix->d_text, nn, tab, bits, k, b.k[0], b.v[0]);
@@ -311,14 +315,14 @@ int pwa_sa_occurrences(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_
         Dev d_ref, d_rank, key, pid, off;
         SortScratch sc;
         if (max_hits) {
-            SA_CHECK(d_ref.alloc(((size_t)n_ref + 1) * 4));
-            SA_CHECK(d_rank.alloc((size_t)n_ref * 4));
+            SA_CHECK(d_ref.alloc(v.poison, ((size_t)n_ref + 1) * 4));
+            SA_CHECK(d_rank.alloc(v.poison, (size_t)n_ref * 4));
             SA_CHECK(hipMemcpyAsync(d_ref.p, ref_start, ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, v.stream));
             if (n_ref) SA_CHECK(hipMemcpyAsync(d_rank.p, header_rank, (size_t)n_ref * 4, hipMemcpyHostToDevice, v.stream));
-            SA_CHECK(key.alloc(max_hits * 16));
-            SA_CHECK(pid.alloc(max_hits * 8));
-            SA_CHECK(off.alloc(((size_t)max_np + 1) * 4));
-            sc.alloc(std::max<uint64_t>(max_hits, (uint64_t)max_np + 1));   // (the offsets scan of a chunk of many hit-less patterns)
+            SA_CHECK(key.alloc(v.poison, max_hits * 16));
+            SA_CHECK(pid.alloc(v.poison, max_hits * 8));
+            SA_CHECK(off.alloc(v.poison, ((size_t)max_np + 1) * 4));
+            sc.alloc(v.poison, std::max<uint64_t>(max_hits, (uint64_t)max_np + 1));   // (the offsets scan of a chunk of many hit-less patterns)
         }
         std::vector<uint64_t> h_key;
         int n_chunks = 0;

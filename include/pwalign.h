@@ -58,6 +58,11 @@
  *   PWA_APPROX_CHUNK=N            pwa_approx_find / pwa_approx_occurrences: a task reports at most N text columns (default 4096)
  *   PWA_AFFINE_TB_ROUTE=0|1       pwa_align_affine_batch: 0 every pair on the strips, 1 every wave task of a list the stripe engine
  *                                 takes on the stripes (default: by estimated cost, and tasks whose strip band does not fit)
+ *   PWA_POISON=<byte>             decimal or 0x.., 0 .. 255: every buffer the context hands to a call -- a new or regrown device
+ *                                 allocation, a kept one that is reused, a page-locked staging buffer -- is filled with that byte over its
+ *                                 whole capacity first (a blocking hipMemset between two device synchronises: slow, a test mode), so a
+ *                                 call that reads what it did not write reads that byte, not zeros or the last call's values; a value
+ *                                 that does not parse makes pwa_ctx_create fail with PWA_E_INVALID; pwa_ctx_poison_stats counts the fills
  *   PWA_NO_PAIR_TABLE, PWA_NO_KEYED_TB, PWA_NO_GAP_SHIFT, PWA_NO_TILED_OPS, PWA_NO_PACKED_DIST, PWA_FORCE_LANES,
  *   PWA_FORCE_R, PWA_FORCE_MODE, PWA_FORCE_RL, PWA_FORCE_W, PWA_WG_PER_CU, PWA_MINI_PER_CU, PWA_NO_LDS_PAD, PWA_STAMPS,
  *   PWA_TRACE_STRIPE
@@ -101,7 +106,8 @@ const char *pwa_strerror(int code);
 /* Test hook, no GPU involved: runs the host scheduler's sorting helpers (stable counting sort, its multi-threaded form, the length
  * sort, the radix sort) on pseudo-random lists against std::stable_sort, and the range planner of the alignment batches (classes,
  * ranges, wave tasks, band layout) on pseudo-random length lists with made-up free-memory figures against the properties every plan
- * must have.  Returns 0, or the number of the first check that failed. */
+ * must have; the parser of PWA_POISON's value on a list of good and bad spellings.  Returns 0, or the number of the first check
+ * that failed. */
 int pwa_selftest_host(uint32_t seed);
 
 /* Context = one GPU (HIP device ordinal) + its streams and workspaces. */
@@ -113,6 +119,10 @@ const char *pwa_last_error(const pwa_ctx *ctx);
  * one coalesced 64*RL*4-byte wave store per anti-diagonal step.  The walk does not need it; it exists
  * for inspection (pwa_align_matrices returns it) and for the 5 B/cell roofline accounting. */
 int pwa_ctx_set_score_band(pwa_ctx *ctx, int on);
+/* What PWA_POISON has filled on this context so far, as running totals: buffers, and their bytes (whole capacities).  The buffers
+ * of a pwa_sa_index and of batch objects count on the context they were created on.  Zeros with the switch unset; a pointer may be
+ * NULL.  PWA_E_INVALID on a NULL context. */
+int pwa_ctx_poison_stats(const pwa_ctx *ctx, uint64_t *buffers, uint64_t *bytes);
 
 /*
  * Scores of many pairs (the scores-only pass over hw2.cpp's pair loop 328-338; for -l the
