@@ -43,10 +43,12 @@ EXPORTS = [
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
+    "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_wfa_last_stats",
 ]
 
 
 APPROX_NO_START = 0xffffffff   # PWA_APPROX_NO_START
+WFA_NONE = -(1 << 31)          # PWA_WFA_NONE: score_out of a pair the bound leaves out
 
 
 class PwaError(RuntimeError):
@@ -70,6 +72,31 @@ def approx_plan(n, pat_len, max_dist, chunk):
     if rc != 0:
         raise PwaError("pwa_approx_plan: %s" % L.pwa_strerror(rc).decode())
     return [(tp[t], ts[t], tl[t], th[t]) for t in range(cap)]
+
+
+def _min_scores(min_score, n):
+    """min_score of the wavefront calls: None, one int, or one per pair -> an int32 array or None"""
+    if min_score is None:
+        return None
+    ms = [min_score] * n if isinstance(min_score, int) else [int(x) for x in min_score]
+    if len(ms) != n:
+        raise ValueError("min_score: one value, or one per pair")
+    return (C.c_int32 * max(n, 1))(*ms)
+
+
+def wfa_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
+    """pwa_wfa_plan (host only): the penalties and, for every (n, m) of `lengths`, the sweep bound and the planned wavefront cells ->
+    dict(pen=(x, o, e, g), p_max=[...], cells=[...]); p_max is None and cells 0 for a pair the bound already rules out."""
+    L = lib()
+    k = len(lengths)
+    ns = (C.c_uint64 * max(k, 1))(*[int(a) for a, _ in lengths])
+    ms = (C.c_uint64 * max(k, 1))(*[int(b) for _, b in lengths])
+    pen = (C.c_int32 * 4)()
+    pm, ce = (C.c_uint64 * max(k, 1))(), (C.c_uint64 * max(k, 1))()
+    rc = L.pwa_wfa_plan(match, mismatch, gap_open, gap_extend, ns, ms, _min_scores(min_score, k), k, pen, pm, ce)
+    if rc != 0:
+        raise PwaError("pwa_wfa_plan: %s" % L.pwa_strerror(rc).decode())
+    return dict(pen=tuple(pen), p_max=[None if pm[i] == (1 << 64) - 1 else pm[i] for i in range(k)], cells=list(ce[:k]))
 
 
 def approx_minima(hits, pat_len, k, n):
@@ -281,6 +308,12 @@ def lib():
     L.pwa_approx_starts.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u64p, u64p, u32p]
     L.pwa_approx_starts_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p, u64p]
     L.pwa_approx_minima.argtypes = [C.c_uint64, u32p, u32p, C.c_uint32, u64p, u64p]
+    wfa_in = [vp] + gotoh_in[2:]   # ctx, match, mismatch, gap_open, gap_extend, sequences, pairs
+    L.pwa_wfa_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u64p, u64p, i32p, C.c_uint64, i32p, u64p, u64p]
+    L.pwa_scores_wfa.argtypes = wfa_in + [i32p, i32p, u32p]   # ..., min_score, score, penalty
+    L.pwa_align_wfa_batch.argtypes = wfa_in + [i32p, vp, u64p, u64p, i32p]   # ..., score, ops, ops_off, n_ops, min_score
+    L.pwa_align_wfa_batch_cigar.argtypes = wfa_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, i32p]
+    L.pwa_wfa_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
     _lib = L
     return L
 
@@ -730,6 +763,70 @@ class Context:
         [dict(score, cigar, mdz, end, start)] as align_batch_cigar returns them."""
         return self._align_strings(self._L.pwa_align_gotoh_batch_cigar, "pwa_align_gotoh_batch_cigar",
                                    (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b)
+
+    # -- wavefront (WFA) affine-gap global alignments of long pairs: exact, no band (include/pwalign.h, "Wavefront alignments")
+    def scores_wfa(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, want_penalty=False):
+        """pwa_scores_wfa: the global affine-gap score of every pair, None for a pair whose optimum lies below min_score (None, one
+        int, or one per pair) -> scores, or with want_penalty (scores, penalties)."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        pen = (C.c_uint32 * max(n, 1))()
+        rc = self._L.pwa_scores_wfa(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, _min_scores(min_score, n), sc, pen)
+        self._check(rc, "pwa_scores_wfa")
+        scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
+        return (scores, [None if scores[k] is None else pen[k] for k in range(n)]) if want_penalty else scores
+
+    def align_wfa_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
+        """pwa_align_wfa_batch -> [dict(score, ops, end, start)] as align_gotoh_batch returns them (end = (n, m), start = (0, 0));
+        score None and ops b"" for a pair not found."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ooff = (C.c_uint64 * max(n, 1))()
+        tot = 0
+        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
+        for k in range(n):
+            ooff[k] = tot
+            tot += ln(pair_a[k]) + ln(pair_b[k])
+        ops = C.create_string_buffer(tot + 1)
+        nops = (C.c_uint64 * max(n, 1))()
+        rc = self._L.pwa_align_wfa_batch(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops,
+                                         _min_scores(min_score, n))
+        self._check(rc, "pwa_align_wfa_batch")
+        raw = memoryview(ops)
+        return [dict(score=None if sc[k] == WFA_NONE else sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]),
+                     end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
+
+    def align_wfa_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
+        """pwa_align_wfa_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_gotoh_batch_cigar returns them; score None and two
+        empty strings for a pair not found."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
+        nm = [ln(pair_a[k]) + ln(pair_b[k]) for k in range(n)]
+        cap_c, cap_m = sum(2 * v + 24 for v in nm), sum(3 * v + 24 for v in nm)   # pwa_cigar_bound / pwa_mdz_bound
+        cg, md = C.create_string_buffer(cap_c + 1), C.create_string_buffer(cap_m + 1)
+        co, mo = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
+        rc = self._L.pwa_align_wfa_batch_cigar(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
+                                               md, cap_m, mo, None, _min_scores(min_score, n))
+        self._check(rc, "pwa_align_wfa_batch_cigar")
+        cgb, mdb = cg.raw, md.raw
+        return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
+                     end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
+
+    def align_wfa_stats(self):
+        """The last scores_wfa / align_wfa_batch(_cigar): device ms of the sweeps and walks, wavefront cells swept, workspace bytes."""
+        f, w, c, b = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_wfa_last_stats(self._h, C.byref(f), C.byref(w), C.byref(c), C.byref(b)), "pwa_wfa_last_stats")
+        return {"sweep_ms": f.value, "walk_ms": w.value, "cells": c.value, "workspace_bytes": b.value}
 
     # -- banded affine-gap alignments of long pairs: the gotoh calls inside a diagonal band per pair (include/pwalign.h)
     @staticmethod

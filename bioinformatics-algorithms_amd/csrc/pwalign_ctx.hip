@@ -119,6 +119,19 @@ pwa::ApproxCtxView pwa::approx_ctx_view(pwa_ctx* c) {
 const pwa::ApproxStats& pwa::approx_stats_of(const pwa_ctx* c) { return c->approx_stats; }
 const pwa::ApproxStartsStats& pwa::approx_starts_stats_of(const pwa_ctx* c) { return c->approx_starts_stats; }
 
+pwa::WfaCtxView pwa::wfa_ctx_view(pwa_ctx* c) {
+    WfaCtxView v;
+    v.device = c->device;
+    v.stream = c->stream;
+    v.debug = c->knobs.debug;
+    v.range_bytes = c->knobs.range_bytes;
+    v.err = &c->err;
+    v.poison = &c->poison;
+    v.stats = &c->wfa_stats;
+    return v;
+}
+const pwa::WfaStats& pwa::wfa_stats_of(const pwa_ctx* c) { return c->wfa_stats; }
+
 hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_t* table) {
     if (!n16) return hipSuccess;
     RecodeTable rt;

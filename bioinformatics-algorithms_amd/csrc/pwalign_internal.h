@@ -19,6 +19,7 @@
 #include "kernel_table.h"
 #include "poison.h"
 #include "subst_table.h"
+#include "wfa_ctx.h"
 
 // Host-side source / destination of the library's own host <-> device copies: page-locked, grow-only, kept in the context.
 // hipMemcpy from a short-lived pageable vector works, but the runtime registers its pages with the driver for the DMA, and
@@ -126,6 +127,7 @@ struct pwa_ctx {
     AffineAlignStats aff_stats;            // the last pwa_align_affine_batch
     pwa::ApproxStats approx_stats;         // the last pwa_approx_find / pwa_approx_occurrences
     pwa::ApproxStartsStats approx_starts_stats;   // the last pwa_approx_starts
+    pwa::WfaStats wfa_stats;               // the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
     // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the

@@ -1,0 +1,303 @@
+// wfa.hip.h -- wavefront (WFA, Marco-Sola et al. 2021) affine-gap global alignment of long pairs (gfx950 / MI355X): the sweep by
+// penalty and the backtrace over the stored wavefronts.  Semantics: include/pwalign.h ("Wavefront alignments"); DESIGN.md §3.21.
+//
+// One wave per pair, four waves per workgroup, nothing between waves: no flags, no spin-waits, every loop bounded by the host's plan
+// (the sweep by P_max, an extend by the two lengths, the walk by the op region).  Lanes are diagonals, in chunks of 64.  A pair's
+// wavefronts live in its own workspace in global memory; what a lane reads was stored by lanes of the SAME wave at an earlier score,
+// so a workgroup-scope release / acquire (wait counts only, the CU's own L1) orders it -- no agent-scope fence anywhere.
+//
+// Layout of wavefront s with the planned span [lo, hi] (w = hi - lo + 1 cells): M[w], I[w], D[w] as int32 offsets, kNull for none,
+// at cell offset cum(s) of the workspace (alignment form: every wavefront up to P_max, 12 bytes per planned cell) or in slot
+// s mod R of a ring of R = max(x, o + e) + 1 wavefronts of the widest span (score form).  A score whose three source wavefronts are
+// all empty is skipped in O(1): its first M cell takes kEmpty, which no computed cell ever holds, and that is the whole per-score
+// bookkeeping -- a non-empty wavefront is computed over its planned span.  While R <= 64 the sweep keeps the emptiness of the last 64
+// scores in a register and reads no marker.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace pwa {
+namespace wfa {
+
+constexpr int kWaves = 4;                       // pairs per 256-thread workgroup
+constexpr int32_t kNull = -(1 << 30);           // no offset: stays negative under + 1, and every negative offset is trimmed
+constexpr int32_t kEmpty = INT32_MIN;           // first M cell of a skipped wavefront
+constexpr uint32_t kNotFound = 0xffffffffu;     // penalty of a pair whose sweep reached P_max without ending
+constexpr uint32_t kPad = 16;                   // zero bytes behind the sequence blob: an 8-byte extend load never leaves it
+
+struct Pen {
+    uint32_t x, o, e;   // reduced penalties of a mismatch, a gap open, a gap extend
+};
+
+struct Pair {            // one pair of a range (host-built), in launch order: longest plan first
+    uint64_t pat, txt;   // blob offsets of the pattern (i) and the text (j)
+    uint64_t ws;         // first int32 of its wavefront workspace
+    uint64_t ops;        // first byte of its op region in the range's op buffer (alignment form)
+    uint32_t n, m;
+    uint32_t p_max;      // the sweep's last score
+    uint32_t out;        // its place in the range's result arrays
+};
+
+struct Span {
+    int32_t lo, hi;
+};
+
+__host__ __device__ inline uint32_t khi(uint32_t s, const Pen& p) { return s < p.o + p.e ? 0u : (s - p.o) / p.e; }
+
+__host__ __device__ inline Span span_of(uint32_t s, uint32_t n, uint32_t m, const Pen& p) {
+    const uint32_t h = khi(s, p);
+    return Span{-(int32_t)(n < h ? n : h), (int32_t)(m < h ? m : h)};
+}
+
+__host__ __device__ inline uint64_t tri(uint64_t c, uint64_t K) {   // sum of min(c, q) over q = 1 .. K
+    return K <= c ? K * (K + 1) / 2 : c * (c + 1) / 2 + (K - c) * c;
+}
+
+// Cells of the wavefronts 0 .. s - 1: sum of 1 + min(n, khi) + min(m, khi).  khi is q on the e scores from o + q e on
+__host__ __device__ inline uint64_t cum(uint32_t s, uint32_t n, uint32_t m, const Pen& p) {
+    uint64_t r = s;
+    if (s > p.o + p.e) {
+        const uint32_t t = s - p.o, Q = (t - 1) / p.e;   // Q = khi(s - 1) >= 1
+        const uint64_t last = t - (uint64_t)Q * p.e;     // scores with khi = Q among them
+        r += (uint64_t)p.e * (tri(m, Q - 1) + tri(n, Q - 1)) + ((m < Q ? m : Q) + (uint64_t)(n < Q ? n : Q)) * last;
+    }
+    return r;
+}
+
+__device__ __forceinline__ int32_t trim(int32_t j, int32_t k, int32_t n, int32_t m) {
+    const int32_t i = j - k;
+    return (j >= 0 && j <= m && i >= 0 && i <= n) ? j : kNull;
+}
+
+__device__ __forceinline__ uint64_t load8(const uint8_t* p) {   // any byte address
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+
+struct SweepParams {
+    const uint8_t* blob;    // the sequences, kPad zero bytes behind them
+    const Pair* pairs;
+    uint32_t n_pairs;
+    Pen pen;
+    int32_t* ws;
+    uint32_t* penalty;      // [out]: P, or kNotFound
+};
+
+template <bool RING>
+__global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
+    const uint32_t q = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    if (q >= a.n_pairs) return;   // whole waves
+    const int lane = threadIdx.x & 63;
+    const Pair P = a.pairs[q];
+    const Pen pen = a.pen;
+    const uint32_t n = P.n, m = P.m, oe = pen.o + pen.e;
+    const uint8_t* const pat = a.blob + P.pat;
+    const uint8_t* const txt = a.blob + P.txt;
+    int32_t* const w = a.ws + P.ws;
+    const uint32_t R = (pen.x > oe ? pen.x : oe) + 1;
+    const bool use_hist = R <= 64;
+    const Span widest = span_of(P.p_max, n, m, pen);
+    const uint64_t stride = 3ull * (uint32_t)(widest.hi - widest.lo + 1);   // of a ring slot
+    const int32_t kend = (int32_t)m - (int32_t)n;
+
+    uint64_t hist = 0;     // bit b: wavefront s - 1 - b is not empty
+    uint32_t slot = 0;     // s mod R
+    uint32_t found = kNotFound;
+    // wavefront s - d
+    auto wf = [&](uint32_t s, uint32_t d) -> int32_t* {
+        if (RING) return w + (uint64_t)(slot >= d ? slot - d : slot + R - d) * stride;
+        return w + 3 * cum(s - d, n, m, pen);
+    };
+    auto filled = [&](uint32_t s, uint32_t d) -> bool {
+        if (d > s) return false;
+        if (use_hist) return (hist >> (d - 1)) & 1;
+        return *wf(s, d) != kEmpty;
+    };
+    for (uint32_t s = 0; s <= P.p_max; ++s) {
+        if (!use_hist) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the markers below
+        const bool ex = filled(s, pen.x), eo = filled(s, oe), ee = filled(s, pen.e);
+        int32_t* const cur = wf(s, 0);
+        if (s && !(ex || eo || ee)) {
+            if (!(RING && use_hist) && lane == 0) cur[0] = kEmpty;
+            hist <<= 1;
+            slot = slot + 1 == R ? 0 : slot + 1;
+            continue;
+        }
+        if (use_hist) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // earlier scores' stores before this score's loads
+        const Span sp = span_of(s, n, m, pen);
+        const uint32_t wd = (uint32_t)(sp.hi - sp.lo + 1);
+        Span sx = {0, -1}, so = {0, -1}, se = {0, -1};
+        const int32_t *bx = w, *bo = w, *be = w;
+        uint32_t wde = 0;
+        if (ex) {
+            sx = span_of(s - pen.x, n, m, pen);
+            bx = wf(s, pen.x);
+        }
+        if (eo) {
+            so = span_of(s - oe, n, m, pen);
+            bo = wf(s, oe);
+        }
+        if (ee) {
+            se = span_of(s - pen.e, n, m, pen);
+            be = wf(s, pen.e);
+            wde = (uint32_t)(se.hi - se.lo + 1);
+        }
+        bool done = false;
+        for (uint32_t c0 = 0; c0 < wd; c0 += 64) {
+            const uint32_t c = c0 + lane;
+            const bool valid = c < wd;
+            const int32_t k = sp.lo + (int32_t)c;
+            int32_t mx = kNull, ml = kNull, mr = kNull, il = kNull, dr = kNull;
+            if (valid) {
+                if (k >= sx.lo && k <= sx.hi) mx = bx[k - sx.lo];
+                if (k - 1 >= so.lo && k - 1 <= so.hi) ml = bo[k - 1 - so.lo];
+                if (k + 1 >= so.lo && k + 1 <= so.hi) mr = bo[k + 1 - so.lo];
+                if (k - 1 >= se.lo && k - 1 <= se.hi) il = be[wde + (uint32_t)(k - 1 - se.lo)];
+                if (k + 1 >= se.lo && k + 1 <= se.hi) dr = be[2 * wde + (uint32_t)(k + 1 - se.lo)];
+            }
+            const int32_t vi = trim((ml > il ? ml : il) + 1, k, (int32_t)n, (int32_t)m);
+            const int32_t vd = trim(mr > dr ? mr : dr, k, (int32_t)n, (int32_t)m);
+            const int32_t vx = trim(mx + 1, k, (int32_t)n, (int32_t)m);
+            int32_t j = vx > vi ? vx : vi;
+            j = j > vd ? j : vd;
+            if (s == 0) j = 0;
+            if (valid && j >= 0) {   // extend: 8 bytes per step, ended by the clamp to the two lengths
+                const uint32_t i = (uint32_t)(j - k);
+                const uint32_t rem = n - i < m - (uint32_t)j ? n - i : m - (uint32_t)j;
+                const uint8_t* const pa = pat + i;
+                const uint8_t* const pb = txt + j;
+                uint32_t run = 0;
+                while (run < rem) {
+                    const uint64_t d = load8(pa + run) ^ load8(pb + run);
+                    if (d) {
+                        run += (uint32_t)__builtin_ctzll(d) >> 3;
+                        break;
+                    }
+                    run += 8;
+                }
+                j += (int32_t)(run < rem ? run : rem);
+            }
+            if (valid) {
+                cur[c] = j;
+                cur[wd + c] = vi;
+                cur[2 * wd + c] = vd;
+            }
+            done |= __ballot(valid && k == kend && j == (int32_t)m) != 0;
+        }
+        hist = hist << 1 | 1;
+        slot = slot + 1 == R ? 0 : slot + 1;
+        if (done) {
+            found = s;
+            break;
+        }
+    }
+    if (lane == 0) a.penalty[P.out] = found;
+}
+
+struct WalkParams {
+    const Pair* pairs;
+    uint32_t n_pairs;
+    Pen pen;
+    const int32_t* ws;
+    const uint32_t* penalty;   // [out] of the sweep
+    uint8_t* ops;
+    uint32_t* n_ops;           // [out]
+    uint32_t* fault;           // one word: set when a walk met a wavefront it cannot follow
+};
+
+// The backtrace over the stored wavefronts of the alignment form.  Every value it reads sits at a wave-uniform address, so the wave
+// walks as one; its lanes share the writing of an 'M' run.
+__global__ __launch_bounds__(256) void wfa_walk_kernel(const WalkParams a) {
+    const uint32_t q = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    if (q >= a.n_pairs) return;   // whole waves
+    const uint32_t lane = threadIdx.x & 63;
+    const Pair P = a.pairs[q];
+    const Pen pen = a.pen;
+    const uint32_t n = P.n, m = P.m, oe = pen.o + pen.e;
+    const int32_t* const w = a.ws + P.ws;
+    uint8_t* const ops = a.ops + P.ops;
+    const uint32_t cap = n + m;
+    const uint32_t pnl = a.penalty[P.out];
+    if (pnl == kNotFound) {
+        if (lane == 0) a.n_ops[P.out] = 0;
+        return;
+    }
+    // which: 0 M, 1 I, 2 D of wavefront s at diagonal k; kNull outside the sweep, outside the span, on a skipped wavefront
+    auto get = [&](int64_t s, uint32_t which, int32_t k) -> int32_t {
+        if (s < 0) return kNull;
+        const Span sp = span_of((uint32_t)s, n, m, pen);
+        if (k < sp.lo || k > sp.hi) return kNull;
+        const int32_t* const b = w + 3 * cum((uint32_t)s, n, m, pen);
+        if (b[0] == kEmpty) return kNull;
+        return b[which * (uint32_t)(sp.hi - sp.lo + 1) + (uint32_t)(k - sp.lo)];
+    };
+    uint32_t cnt = 0;
+    bool fault = false, finished = false;
+    auto put_m = [&](uint32_t len) {
+        if (len > cap - cnt) {
+            fault = true;
+            return;
+        }
+        for (uint32_t c = lane; c < len; c += 64) ops[cnt + c] = 'M';
+        cnt += len;
+    };
+    int64_t s = pnl;
+    int32_t k = (int32_t)m - (int32_t)n, j = (int32_t)m;
+    int st = 0;   // 0: M, 1: I, 2: D
+    for (uint64_t it = 0; it <= 2ull * cap + 2 && !fault; ++it) {
+        if (st == 0) {
+            if (s == 0) {
+                if (k != 0 || j < 0) break;
+                put_m((uint32_t)j);
+                finished = !fault;
+                break;
+            }
+            const int32_t vx = trim(get(s - pen.x, 0, k) + 1, k, (int32_t)n, (int32_t)m);
+            const int32_t vi = get(s, 1, k), vd = get(s, 2, k);
+            int32_t v = vx > vi ? vx : vi;
+            v = v > vd ? v : vd;
+            if (v < 0 || v > j) {
+                fault = true;
+                break;
+            }
+            put_m((uint32_t)(j - v) + (vx == v ? 1u : 0u));   // ties: mismatch >= I >= D
+            if (vx == v) {
+                s -= pen.x;
+                j = v - 1;
+            } else {
+                st = vi == v ? 1 : 2;
+                j = v;
+            }
+        } else {
+            if (cnt >= cap) {   // cannot happen (every op moves i or j): never spin on the GPU
+                fault = true;
+                break;
+            }
+            const bool ins = st == 1;
+            const int32_t ks = ins ? k - 1 : k + 1;
+            if (lane == 0) ops[cnt] = ins ? 'I' : 'D';
+            ++cnt;
+            const int32_t vm = get(s - oe, 0, ks), vg = get(s - pen.e, (uint32_t)st, ks);
+            if (vm < 0 && vg < 0) {
+                fault = true;
+                break;
+            }
+            if (vm >= vg) {   // a tie opens
+                s -= oe;
+                st = 0;
+            } else {
+                s -= pen.e;
+            }
+            k = ks;
+            if (ins) --j;
+        }
+    }
+    if (lane == 0) {
+        a.n_ops[P.out] = finished ? cnt : 0u;
+        if (!finished) *a.fault = 1u;
+    }
+}
+
+}  // namespace wfa
+}  // namespace pwa

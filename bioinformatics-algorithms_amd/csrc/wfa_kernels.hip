@@ -1,0 +1,503 @@
+// wfa_kernels.hip -- the wavefront-alignment entries of include/pwalign.h (pwa_wfa_plan, pwa_scores_wfa, pwa_align_wfa_batch(_cigar),
+// pwa_wfa_last_stats): validation, the conversion to penalties, the per-pair plan and bound, ranges of consecutive pairs under the
+// PWA_RANGE_BYTES budget, the sweep and the walk of each range, the CIGAR / MD:Z strings.  Kernels: wfa.hip.h.
+#include "../../include/pwalign.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "wfa.hip.h"
+#include "wfa_ctx.h"
+
+using namespace pwa::wfa;
+
+namespace {
+
+struct Dev {   // one device allocation, freed with its owner
+    void* p = nullptr;
+    size_t cap = 0;
+    Dev() = default;
+    Dev(const Dev&) = delete;
+    Dev& operator=(const Dev&) = delete;
+    ~Dev() { if (p) (void)hipFree(p); }
+    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = std::max<size_t>(bytes, 16);
+        const hipError_t e = hipMalloc(&p, cap);
+        return e == hipSuccess ? pwa::poison_device(po, p, cap) : e;
+    }
+    hipError_t again(pwa::Poison* po) { return pwa::poison_device(po, p, cap); }   // the same buffer handed to the next range
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+struct Fail {   // an error on the way: the code and what to say about it
+    int code;
+    std::string what;
+};
+void check(hipError_t e, const char* what) {
+    if (e != hipSuccess) throw Fail{e == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
+}
+#define WF_CHECK(call) check((call), #call)
+
+struct Scoring {
+    int match = 0, mismatch = 0, go = 0, ge = 0;
+    Pen pen{};
+    uint32_t g = 1;
+};
+
+int64_t gcd64(int64_t a, int64_t b) {
+    while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// The scoring as penalties; PWA_E_INVALID where no penalty form exists
+int convert(int match, int mismatch, int go, int ge, Scoring& sc) {
+    const int64_t x0 = 2 * ((int64_t)match - mismatch), o0 = -2 * (int64_t)go, e0 = (int64_t)match - 2 * (int64_t)ge;
+    if (go > 0 || ge > 0 || x0 <= 0 || e0 <= 0) return PWA_E_INVALID;
+    const int64_t g = gcd64(gcd64(x0, o0), e0);
+    if (x0 / g > 0x3fffffff || o0 / g > 0x3fffffff || e0 / g > 0x3fffffff) return PWA_E_CAPACITY;   // (no pair passes the range rule then)
+    sc.match = match;
+    sc.mismatch = mismatch;
+    sc.go = go;
+    sc.ge = ge;
+    sc.pen = Pen{(uint32_t)(x0 / g), (uint32_t)(o0 / g), (uint32_t)(e0 / g)};
+    sc.g = (uint32_t)g;
+    return PWA_OK;
+}
+
+bool in_range(const Scoring& sc, uint64_t n, uint64_t m) {
+    const uint64_t big = std::max<uint64_t>({(uint64_t)std::llabs(sc.match), (uint64_t)std::llabs(sc.mismatch), (uint64_t)std::llabs(sc.go) + (uint64_t)std::llabs(sc.ge)});
+    return n + m + 2 < (1ull << 28) && (n + m + 2) * big < (1ull << 28);
+}
+
+struct Plan {
+    uint32_t n = 0, m = 0;
+    bool none = false;      // not found, decided here
+    uint32_t p_max = 0;
+    uint64_t cells = 0;     // of the wavefronts 0 .. p_max
+};
+
+// The bound and the planning unit of one pair inside the range rule
+Plan plan_pair(const Scoring& sc, uint64_t n, uint64_t m, const int32_t* min_score) {
+    Plan p;
+    p.n = (uint32_t)n;
+    p.m = (uint32_t)m;
+    const int64_t o = sc.pen.o, e = sc.pen.e;
+    int64_t p_max = (n ? o + (int64_t)n * e : 0) + (m ? o + (int64_t)m * e : 0);
+    if (min_score) {
+        const int64_t num = (int64_t)sc.match * (int64_t)(n + m) - 2 * (int64_t)*min_score, g = sc.g;
+        const int64_t fl = num >= 0 ? num / g : -((-num + g - 1) / g);
+        p_max = std::min(p_max, fl);
+    }
+    const int64_t gap = n == m ? 0 : o + (int64_t)(n > m ? n - m : m - n) * e;
+    if (p_max < 0 || p_max < gap) {
+        p.none = true;
+        return p;
+    }
+    p.p_max = (uint32_t)p_max;
+    p.cells = cum(p.p_max + 1, p.n, p.m, sc.pen);
+    return p;
+}
+
+int32_t score_of(const Scoring& sc, const Plan& p, uint32_t pen) {
+    return (int32_t)(((int64_t)sc.match * ((int64_t)p.n + p.m) - (int64_t)sc.g * pen) / 2);
+}
+
+// CIGAR and MD:Z of an op list in traceback order from (n, m) down to (0, 0), as pwa_format_alignment writes them, appended to the
+// two strings (any byte value may appear)
+void put_uint(std::string& s, uint64_t v) {
+    char buf[24];
+    int k = 0;
+    do {
+        buf[k++] = (char)('0' + v % 10);
+        v /= 10;
+    } while (v);
+    while (k) s.push_back(buf[--k]);
+}
+void format_ops(const uint8_t* pat, const uint8_t* txt, const uint8_t* ops, uint64_t n_ops, std::string& cg, std::string& md) {
+    uint64_t i = 0, j = 0, matches = 0;
+    for (uint64_t c = 0; c < n_ops;) {
+        const uint8_t op = ops[n_ops - 1 - c];
+        uint64_t run = 1;
+        while (c + run < n_ops && ops[n_ops - 1 - (c + run)] == op) ++run;
+        put_uint(cg, run);
+        cg.push_back((char)op);
+        if (op == 'M') {
+            for (uint64_t r = 0; r < run; ++r, ++i, ++j) {
+                if (pat[i] == txt[j]) {
+                    ++matches;
+                } else {
+                    put_uint(md, matches);
+                    md.push_back((char)txt[j]);
+                    matches = 0;
+                }
+            }
+        } else if (op == 'D') {
+            put_uint(md, matches);
+            md.push_back('^');
+            matches = 0;
+            md.append(reinterpret_cast<const char*>(pat + i), run);
+            i += run;
+        } else {
+            j += run;
+        }
+        c += run;
+    }
+    put_uint(md, matches);
+}
+
+struct Range {
+    uint64_t k0 = 0, k1 = 0;
+    uint64_t ws_bytes = 0, op_bytes = 0;
+};
+
+struct Call {
+    pwa::WfaCtxView v;
+    Scoring sc;
+    const uint8_t* blob = nullptr;
+    const uint64_t* seq_off = nullptr;
+    uint32_t n_seq = 0;
+    const uint32_t *pair_a = nullptr, *pair_b = nullptr;
+    uint64_t n_pairs = 0;
+    std::vector<Plan> plans;
+};
+
+// Scoring, required pointers (by the caller), indices and the range rule, in pair order; fills c.plans
+int validate(Call& c, int match, int mismatch, int go, int ge, const int32_t* min_score, const char* who) {
+    if (const int rc = convert(match, mismatch, go, ge, c.sc)) {
+        *c.v.err = std::string(who) + ": the scoring has no penalty form (gap_open <= 0, gap_extend <= 0, match > mismatch, match - 2 gap_extend > 0)";
+        return rc;
+    }
+    c.plans.resize(c.n_pairs);
+    for (uint64_t k = 0; k < c.n_pairs; ++k) {
+        const uint32_t a = c.pair_a[k], b = c.pair_b[k];
+        if (a >= c.n_seq || b >= c.n_seq || c.seq_off[a + 1] < c.seq_off[a] || c.seq_off[b + 1] < c.seq_off[b] || c.seq_off[a + 1] > c.seq_off[c.n_seq] ||
+            c.seq_off[b + 1] > c.seq_off[c.n_seq]) {
+            *c.v.err = std::string(who) + ": pair " + std::to_string(k) + " names a sequence outside the list";
+            return PWA_E_INVALID;
+        }
+        const uint64_t n = c.seq_off[a + 1] - c.seq_off[a], m = c.seq_off[b + 1] - c.seq_off[b];
+        if (!in_range(c.sc, n, m)) {
+            *c.v.err = std::string(who) + ": pair " + std::to_string(k) + " (" + std::to_string(n) + " x " + std::to_string(m) + ") exceeds the score range";
+            return PWA_E_CAPACITY;
+        }
+        c.plans[k] = plan_pair(c.sc, n, m, min_score ? min_score + k : nullptr);
+    }
+    return PWA_OK;
+}
+
+// The sweep (and, with want_ops, the walk) of every pair: penalty[k] = P or kNotFound; op lists packed pair after pair into `ops`
+// (pair k at op_at[k], n + m bytes of room, n_ops[k] of them written)
+void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uint8_t>& ops, std::vector<uint64_t>& op_at, std::vector<uint32_t>& n_ops) {
+    const pwa::WfaCtxView& v = c.v;
+    const uint64_t np = c.n_pairs;
+    penalty.assign(np, kNotFound);
+    n_ops.assign(np, 0);
+    op_at.assign(np + 1, 0);
+    pwa::WfaStats st;
+    if (want_ops) {
+        for (uint64_t k = 0; k < np; ++k) op_at[k + 1] = op_at[k] + c.plans[k].n + c.plans[k].m;
+        ops.resize(op_at[np]);
+    }
+    const Pen pen = c.sc.pen;
+    const uint64_t R = (uint64_t)std::max(pen.x, pen.o + pen.e) + 1;
+    auto ws_bytes = [&](const Plan& p) -> uint64_t {
+        if (p.none) return 0;
+        if (want_ops) return 12 * p.cells;
+        const Span sp = span_of(p.p_max, p.n, p.m, pen);
+        return 12 * std::min<uint64_t>(R, (uint64_t)p.p_max + 1) * (uint64_t)(sp.hi - sp.lo + 1);
+    };
+    bool any = false;
+    for (const Plan& p : c.plans) any = any || !p.none;
+    if (!any) {
+        *v.stats = st;
+        return;
+    }
+    (void)hipSetDevice(v.device);
+    uint64_t budget = v.range_bytes;
+    if (!budget) {
+        size_t free_b = 0, total_b = 0;
+        WF_CHECK(hipMemGetInfo(&free_b, &total_b));
+        budget = std::min<uint64_t>((uint64_t)(free_b * 0.6), 48ull << 30);
+    }
+    // ranges of consecutive pairs; one pair alone may exceed the budget
+    std::vector<Range> ranges;
+    uint64_t max_ws = 0, max_ops = 0, max_n = 0;
+    for (uint64_t k = 0; k < np;) {
+        Range r;
+        r.k0 = k;
+        do {
+            r.ws_bytes += ws_bytes(c.plans[k]);
+            r.op_bytes += want_ops ? c.plans[k].n + c.plans[k].m : 0;
+            ++k;
+        } while (k < np && r.ws_bytes + r.op_bytes + ws_bytes(c.plans[k]) + (want_ops ? c.plans[k].n + c.plans[k].m : 0) <= budget);
+        r.k1 = k;
+        ranges.push_back(r);
+        max_ws = std::max(max_ws, r.ws_bytes);
+        max_ops = std::max(max_ops, r.op_bytes);
+        max_n = std::max(max_n, r.k1 - r.k0);
+    }
+    const uint64_t blob_bytes = c.seq_off[c.n_seq];
+    Dev d_blob, d_ws, d_pairs, d_pen, d_nops, d_ops, d_fault;
+    WF_CHECK(d_blob.alloc(v.poison, blob_bytes + kPad));
+    WF_CHECK(d_ws.alloc(v.poison, max_ws));
+    WF_CHECK(d_pairs.alloc(v.poison, max_n * sizeof(Pair)));
+    WF_CHECK(d_pen.alloc(v.poison, max_n * 4));
+    if (want_ops) {
+        WF_CHECK(d_nops.alloc(v.poison, max_n * 4));
+        WF_CHECK(d_ops.alloc(v.poison, max_ops));
+        WF_CHECK(d_fault.alloc(v.poison, 4));
+    }
+    if (blob_bytes) WF_CHECK(hipMemcpyAsync(d_blob.p, c.blob, blob_bytes, hipMemcpyHostToDevice, v.stream));
+    WF_CHECK(hipMemsetAsync(d_blob.as<uint8_t>() + blob_bytes, 0, kPad, v.stream));
+    if (want_ops) WF_CHECK(hipMemsetAsync(d_fault.p, 0, 4, v.stream));
+    Events ev;
+    for (hipEvent_t& e : ev.e) WF_CHECK(hipEventCreate(&e));
+    std::vector<Pair> pairs;
+    std::vector<uint32_t> h_pen, h_nops;
+    std::vector<uint64_t> order;
+    bool first = true;
+    for (const Range& r : ranges) {
+        const uint64_t cnt = r.k1 - r.k0;
+        // launch order: longest plan first; pairs the host decided are left out
+        order.clear();
+        for (uint64_t k = r.k0; k < r.k1; ++k)
+            if (!c.plans[k].none) order.push_back(k);
+        if (order.empty()) continue;
+        std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return c.plans[a].cells > c.plans[b].cells; });
+        std::vector<uint64_t> ws_at(cnt + 1, 0);
+        for (uint64_t k = r.k0; k < r.k1; ++k) ws_at[k - r.k0 + 1] = ws_at[k - r.k0] + ws_bytes(c.plans[k]) / 4;
+        pairs.clear();
+        for (uint64_t k : order) {
+            const Plan& p = c.plans[k];
+            pairs.push_back(Pair{c.seq_off[c.pair_a[k]], c.seq_off[c.pair_b[k]], ws_at[k - r.k0], want_ops ? op_at[k] - op_at[r.k0] : 0, p.n, p.m, p.p_max,
+                                 (uint32_t)(k - r.k0)});
+        }
+        if (!first) {   // the buffers of the range before, handed out again
+            WF_CHECK(hipStreamSynchronize(v.stream));
+            WF_CHECK(d_ws.again(v.poison));
+            WF_CHECK(d_pairs.again(v.poison));
+            WF_CHECK(d_pen.again(v.poison));
+            if (want_ops) {
+                WF_CHECK(d_nops.again(v.poison));
+                WF_CHECK(d_ops.again(v.poison));
+            }
+        }
+        first = false;
+        const uint32_t nl = (uint32_t)pairs.size(), blocks = (nl + kWaves - 1) / kWaves;
+        WF_CHECK(hipMemcpyAsync(d_pairs.p, pairs.data(), nl * sizeof(Pair), hipMemcpyHostToDevice, v.stream));
+        const SweepParams sp{d_blob.as<uint8_t>(), d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>()};
+        WF_CHECK(hipEventRecord(ev.e[0], v.stream));
+        if (want_ops)
+            hipLaunchKernelGGL(wfa_sweep_kernel<false>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
+        else
+            hipLaunchKernelGGL(wfa_sweep_kernel<true>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
+        WF_CHECK(hipGetLastError());
+        WF_CHECK(hipEventRecord(ev.e[1], v.stream));
+        if (want_ops) {
+            const WalkParams wp{d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>(), d_ops.as<uint8_t>(), d_nops.as<uint32_t>(), d_fault.as<uint32_t>()};
+            hipLaunchKernelGGL(wfa_walk_kernel, dim3(blocks), dim3(64 * kWaves), 0, v.stream, wp);
+            WF_CHECK(hipGetLastError());
+        }
+        WF_CHECK(hipEventRecord(ev.e[2], v.stream));
+        h_pen.assign(cnt, kNotFound);
+        h_nops.assign(cnt, 0);
+        WF_CHECK(hipMemcpyAsync(h_pen.data(), d_pen.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
+        if (want_ops) {
+            WF_CHECK(hipMemcpyAsync(h_nops.data(), d_nops.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
+            if (r.op_bytes) WF_CHECK(hipMemcpyAsync(ops.data() + op_at[r.k0], d_ops.p, r.op_bytes, hipMemcpyDeviceToHost, v.stream));
+        }
+        WF_CHECK(hipStreamSynchronize(v.stream));
+        float a = 0.f, b = 0.f;
+        WF_CHECK(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+        WF_CHECK(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+        st.sweep_ms += a;
+        st.walk_ms += b;
+        for (uint64_t k : order) {   // (a pair left out of the launch keeps kNotFound and no ops; its slots were never written)
+            penalty[k] = h_pen[k - r.k0];
+            n_ops[k] = want_ops ? h_nops[k - r.k0] : 0;
+            const Plan& p = c.plans[k];
+            st.cells += cum((penalty[k] == kNotFound ? p.p_max : penalty[k]) + 1, p.n, p.m, pen);
+        }
+    }
+    st.workspace_bytes = max_ws;
+    if (want_ops) {
+        uint32_t fault = 0;
+        WF_CHECK(hipMemcpy(&fault, d_fault.p, 4, hipMemcpyDeviceToHost));
+        if (fault) throw Fail{PWA_E_HIP, "pwa_align_wfa: a walk left its wavefronts (internal error)"};
+    }
+    *v.stats = st;
+    if (v.debug)
+        std::fprintf(stderr, "[pwa] wfa %s: %llu pairs, %zu ranges, x=%u o=%u e=%u, %llu cells, workspace %llu B, sweep %.3f ms, walk %.3f ms\n",
+                     want_ops ? "align" : "scores", (unsigned long long)np, ranges.size(), pen.x, pen.o, pen.e, (unsigned long long)st.cells,
+                     (unsigned long long)st.workspace_bytes, st.sweep_ms, st.walk_ms);
+}
+
+int fail(pwa::WfaCtxView& v, const Fail& f) {
+    *v.err = f.what;
+    return f.code;
+}
+
+Call begin(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs) {
+    Call c;
+    c.v = pwa::wfa_ctx_view(ctx);
+    c.blob = seq_bytes;
+    c.seq_off = seq_off;
+    c.n_seq = n_seq;
+    c.pair_a = pair_a;
+    c.pair_b = pair_b;
+    c.n_pairs = n_pairs;
+    return c;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pwa_wfa_plan(int match, int mismatch, int gap_open, int gap_extend, const uint64_t* n, const uint64_t* m, const int32_t* min_score,
+                 uint64_t n_pairs, int32_t pen[4], uint64_t* p_max, uint64_t* cells) {
+    if (!pen || ((!n || !m) && n_pairs)) return PWA_E_INVALID;
+    Scoring sc;
+    if (const int rc = convert(match, mismatch, gap_open, gap_extend, sc)) return rc;
+    for (uint64_t k = 0; k < n_pairs; ++k)
+        if (!in_range(sc, n[k], m[k])) return PWA_E_CAPACITY;
+    pen[0] = (int32_t)sc.pen.x;
+    pen[1] = (int32_t)sc.pen.o;
+    pen[2] = (int32_t)sc.pen.e;
+    pen[3] = (int32_t)sc.g;
+    for (uint64_t k = 0; k < n_pairs; ++k) {
+        const Plan p = plan_pair(sc, n[k], m[k], min_score ? min_score + k : nullptr);
+        if (p_max) p_max[k] = p.none ? UINT64_MAX : p.p_max;
+        if (cells) cells[k] = p.none ? 0 : p.cells;
+    }
+    return PWA_OK;
+}
+
+int pwa_scores_wfa(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                   const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, const int32_t* min_score, int32_t* score_out, uint32_t* penalty_out) {
+    if (!ctx || !seq_off || (!seq_bytes && n_seq && seq_off[n_seq]) || ((!pair_a || !pair_b || !score_out) && n_pairs)) return PWA_E_INVALID;
+    Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
+    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_scores_wfa")) return rc;
+    try {
+        std::vector<uint32_t> penalty, n_ops;
+        std::vector<uint8_t> ops;
+        std::vector<uint64_t> op_at;
+        run(c, false, penalty, ops, op_at, n_ops);
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const bool hit = penalty[k] != kNotFound;
+            score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
+            if (penalty_out) penalty_out[k] = penalty[k];
+        }
+    } catch (const Fail& f) {
+        return fail(c.v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                        const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off,
+                        uint64_t* n_ops, const int32_t* min_score) {
+    if (!ctx || !seq_off || (!seq_bytes && n_seq && seq_off[n_seq]) || ((!pair_a || !pair_b || !score_out || !ops || !ops_off || !n_ops) && n_pairs))
+        return PWA_E_INVALID;
+    Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
+    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch")) return rc;
+    try {
+        std::vector<uint32_t> penalty, cnt;
+        std::vector<uint8_t> h_ops;
+        std::vector<uint64_t> op_at;
+        run(c, true, penalty, h_ops, op_at, cnt);
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const bool hit = penalty[k] != kNotFound;
+            score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
+            n_ops[k] = hit ? cnt[k] : 0;
+            if (n_ops[k]) std::memcpy(ops + ops_off[k], h_ops.data() + op_at[k], n_ops[k]);
+        }
+    } catch (const Fail& f) {
+        return fail(c.v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
+                              uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
+                              uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t needed[2],
+                              const int32_t* min_score) {
+    if (!ctx || !seq_off || !cigar_off || !mdz_off || (!seq_bytes && n_seq && seq_off[n_seq]) || (!cigar && cigar_cap) || (!mdz && mdz_cap) ||
+        ((!pair_a || !pair_b || !score_out) && n_pairs))
+        return PWA_E_INVALID;
+    Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
+    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch_cigar")) return rc;
+    try {
+        std::vector<uint32_t> penalty, cnt;
+        std::vector<uint8_t> h_ops;
+        std::vector<uint64_t> op_at;
+        run(c, true, penalty, h_ops, op_at, cnt);
+        // the strings are formatted here, on the host, from the op lists (a pair not found has no strings at all, which
+        // the device pass of cigar.hip.h cannot express)
+        uint64_t at_c = 0, at_m = 0;
+        std::string cg, md;
+        for (uint64_t k = 0; k < n_pairs; ++k) {
+            const bool hit = penalty[k] != kNotFound;
+            score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
+            cigar_off[k] = at_c;
+            mdz_off[k] = at_m;
+            if (!hit) continue;
+            cg.clear();
+            md.clear();
+            format_ops(seq_bytes + seq_off[pair_a[k]], seq_bytes + seq_off[pair_b[k]], h_ops.data() + op_at[k], cnt[k], cg, md);
+            if (at_c + cg.size() <= cigar_cap && cg.size()) std::memcpy(cigar + at_c, cg.data(), cg.size());
+            if (at_m + md.size() <= mdz_cap && md.size()) std::memcpy(mdz + at_m, md.data(), md.size());
+            at_c += cg.size();
+            at_m += md.size();
+        }
+        cigar_off[n_pairs] = at_c;
+        mdz_off[n_pairs] = at_m;
+        if (needed) {
+            needed[0] = at_c;
+            needed[1] = at_m;
+        }
+        if (at_c > cigar_cap || at_m > mdz_cap) {
+            *c.v.err = "pwa_align_wfa_batch_cigar: the strings need " + std::to_string(at_c) + " + " + std::to_string(at_m) + " bytes";
+            return PWA_E_CAPACITY;
+        }
+    } catch (const Fail& f) {
+        return fail(c.v, f);
+    } catch (const std::bad_alloc&) {
+        return PWA_E_NOMEM;
+    }
+    return PWA_OK;
+}
+
+int pwa_wfa_last_stats(const pwa_ctx* ctx, float* sweep_ms, float* walk_ms, uint64_t* cells, uint64_t* workspace_bytes) {
+    if (!ctx) return PWA_E_INVALID;
+    const pwa::WfaStats& st = pwa::wfa_stats_of(ctx);
+    if (sweep_ms) *sweep_ms = st.sweep_ms;
+    if (walk_ms) *walk_ms = st.walk_ms;
+    if (cells) *cells = st.cells;
+    if (workspace_bytes) *workspace_bytes = st.workspace_bytes;
+    return PWA_OK;
+}
+
+}  // extern "C"

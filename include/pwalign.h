@@ -50,7 +50,8 @@
  *   PWA_NO_PIPELINE, PWA_PIPE_RUNS=N  one-shot score calls: runs strictly one after the other / a list that fits one arena cut into N runs
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
- *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs
+ *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs; wavefront + op bytes per range of
+ *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
  *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
@@ -796,6 +797,73 @@ int pwa_approx_starts(pwa_ctx *ctx, const uint8_t *text, uint64_t n, const uint8
 int pwa_approx_starts_last_stats(const pwa_ctx *ctx, float *ms, uint64_t *hits, uint64_t *columns);
 int pwa_approx_minima(uint64_t n, const uint32_t *pat_len, const uint32_t *max_dist, uint32_t n_pat,
                       uint64_t *occ_off /* in: n_pat + 1; out: of the kept hits */, uint64_t *occ /* compacted in place */);
+
+/* ---- Wavefront alignments: exact affine-gap GLOBAL alignments of long pairs without a band (WFA, Marco-Sola et al. 2021)
+ *
+ * The gotoh block's scoring and conventions (match, mismatch, gap_open, gap_extend; a gap of length L scores gap_open + L * gap_extend;
+ * equality on raw bytes, NUL and '-' included), mode NW only: from (0, 0) to (n, m), pattern = pair_a (rows, i), text = pair_b (j).
+ * The sweep is by PENALTY, not by cell, so work and memory grow with how much a pair differs, not with its size: no limit on the
+ * pattern length, no band to guess.  Penalties:
+ *   x0 = 2 (match - mismatch)   o0 = -2 gap_open   e0 = match - 2 gap_extend
+ *   g = gcd(x0, o0, e0) (gcd with 0 is the other value)   x, o, e = x0 / g, o0 / g, e0 / g
+ * PWA_E_INVALID unless gap_open <= 0, gap_extend <= 0, match > mismatch and match - 2 gap_extend > 0.  An alignment with penalty P
+ * scores (match (n + m) - g P) / 2; the division is exact.  Range rule as for gotoh: (n + m + 2) * max(|match|, |mismatch|,
+ * |gap_open| + |gap_extend|) < 2^28, else PWA_E_CAPACITY.
+ * Wavefronts: the offset is the text index j, the diagonal k = j - i, NULL is -inf; an offset is kept only when 0 <= j <= m and
+ * 0 <= j - k <= n, otherwise it is NULL, and that holds for every term below before a max is taken.
+ *   I[s][k] = max(M[s-o-e][k-1], I[s-e][k-1]) + 1          ('I': text symbol against a gap)
+ *   D[s][k] = max(M[s-o-e][k+1], D[s-e][k+1])              ('D': pattern symbol against a gap)
+ *   M[s][k] = extend(max(M[s-x][k] + 1, I[s][k], D[s][k]))  extend: j++ while i < n, j < m, p[i] == t[j]
+ *   M[0][0] = extend(0); the sweep ends at the first s with M[s][m-n] == m; that s is the pair's penalty P
+ * Wavefront s spans the diagonals [max(-n, -khi(s)), min(m, khi(s))], khi(s) = 0 for s < o + e, else (s - o) div e; width(s) is the
+ * number of those diagonals.  A score whose wavefronts s - x, s - o - e and s - e are all empty (or below 0) is empty.
+ * Backtrace: from state M at (P, m - n, m); ops in traceback order, as every other call writes them.  In M at s > 0: v = the max of the
+ * three sources (the value before the extend); emit j - v 'M'; on ties mismatch >= I >= D (mirrors diag >= E >= F); a mismatch emits
+ * one more 'M' and goes to (s - x, k, v - 1); I or D switch state on the same (s, k) with j = v.  In I: emit 'I', go to (k - 1, j - 1);
+ * a tie OPENS: M[s-o-e][k-1] >= I[s-e][k-1] goes to M at s - o - e, otherwise stay in I at s - e.  D likewise with 'D', k + 1 and j
+ * unchanged.  At s = 0: emit j 'M' and stop.  The op list is an optimal alignment; between ties it is chosen by these rules, not by
+ * the DP walk's, so it need not equal pwa_align_gotoh_batch's byte for byte.
+ * Bound: min_score[k] (the pointer may be NULL: no bound) is the lowest score worth finding for pair k.  With P_worst the penalty of
+ * "n 'D' then m 'I'", (o + n e if n > 0) + (o + m e if m > 0),  P_max = min(P_worst, floor((match (n + m) - 2 min_score) / g)), and
+ * the sweep never goes beyond P_max.  A pair whose optimum scores below min_score[k] is NOT FOUND: P_max < 0, or P_max < o + |n - m| e
+ * for n != m (both decided on the host, no device work for the pair), or the sweep reaches P_max without ending.  Then
+ * score_out[k] = PWA_WFA_NONE, penalty_out[k] = 0xffffffff, n_ops[k] = 0, and CIGAR and MD:Z are both of length 0.  A found pair with
+ * an empty side follows the gotoh NW conventions ("nD" / "0^<pattern>0", "mI" / "0", "" / "0").
+ * cells(k) = the sum of width(s) over s = 0 .. P_max is the planning unit: the alignment calls keep every wavefront, 12 bytes of
+ * device workspace per planned cell; the score call keeps a ring of max(x, o + e) + 1 wavefronts per pair.  The workspace is processed
+ * in ranges of consecutive pairs under the PWA_RANGE_BYTES budget (default min(0.6 free, 48 GiB)); a range holds at least one pair, and
+ * PWA_E_NOMEM when that pair cannot be allocated.  Give a bound for long pairs: without one the plan reaches P_worst.
+ *   pwa_wfa_plan             host only, no context: validation, the conversion (pen = x, o, e, g) and per pair P_max and cells (either
+ *                            may be NULL); a pair not found on the host gets cells = 0 and p_max = UINT64_MAX.
+ *   pwa_scores_wfa           score_out[k], and penalty_out[k] = P (penalty_out may be NULL).
+ *   pwa_align_wfa_batch      score_out, and the op lists with pwa_align_gotoh_batch's op-region layout (ops_off, n_ops).
+ *   pwa_align_wfa_batch_cigar  the same alignments as CIGAR and MD:Z strings with pwa_align_gotoh_batch_cigar's string buffers and
+ *                            PWA_E_CAPACITY / needed protocol; the strings equal pwa_format_alignment of the op list byte for byte
+ *                            (formatted on the host from the op lists).  No end or start cells: always (n, m) and (0, 0).
+ *   pwa_wfa_last_stats       of the last of the three calls on ctx: device ms of the sweeps and the walks (events), cells = the sum over
+ *                            the pairs of width(s) for s = 0 .. P (P_max for a pair the sweep did not find, nothing for one decided on
+ *                            the host), and the bytes of the largest range's wavefront workspace.  A call that fails validation
+ *                            leaves them unchanged.
+ * Validation runs before any device work, in pair order: a null context, a null required pointer, an index >= n_seq PWA_E_INVALID;
+ * the scoring first.  An empty pair list is PWA_OK. */
+#define PWA_WFA_NONE INT32_MIN
+int pwa_wfa_plan(int match, int mismatch, int gap_open, int gap_extend, const uint64_t *n, const uint64_t *m,
+                 const int32_t *min_score /* or NULL */, uint64_t n_pairs, int32_t pen[4] /* x, o, e, g */,
+                 uint64_t *p_max /* or NULL */, uint64_t *cells /* or NULL */);
+int pwa_scores_wfa(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                   const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs,
+                   const int32_t *min_score /* or NULL */, int32_t *score_out, uint32_t *penalty_out /* or NULL */);
+int pwa_align_wfa_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                        const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs,
+                        int32_t *score_out, uint8_t *ops, const uint64_t *ops_off, uint64_t *n_ops,
+                        const int32_t *min_score /* or NULL */);
+int pwa_align_wfa_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                              const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                              uint64_t n_pairs, int32_t *score_out,
+                              char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                              char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                              uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
+int pwa_wfa_last_stats(const pwa_ctx *ctx, float *sweep_ms, float *walk_ms, uint64_t *cells, uint64_t *workspace_bytes);
 
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
