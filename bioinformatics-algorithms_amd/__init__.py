@@ -28,7 +28,7 @@ MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1, "sg": 2, "semiglobal": 2}   #
 
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_ctx_poison_stats", "pwa_scores",
-    "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int",
+    "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int", "pwa_profile_plan",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
@@ -233,6 +233,7 @@ def lib():
     L.pwa_batch_cell_bits.argtypes = [vp]
     L.pwa_batch_profile_form.argtypes = [vp]
     L.pwa_batch_profile_int.argtypes = [vp]
+    L.pwa_profile_plan.argtypes = [C.c_uint32, C.c_uint32, u32p, u32p]
     L.pwa_batch_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.pwa_batch_run_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.pwa_batch_destroy.argtypes = [vp]

@@ -385,6 +385,90 @@ __device__ __forceinline__ void scores16_body(const BatchParams& P) {
 // that tool's row "... int nomove" (DESIGN.md r05, r06).  Neither row runs the pad rows past the pattern's length rounded up to a pair of rows.
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
+// The integer row's asm text in pieces (scores16p_body, INT = true).  P16I_ADDS: a row's profile offset and its 8 indexed adds, DIAG
+// the first column's diagonal; P16I_CHAIN: its maxima and subtracts, LEFT the row's left neighbour and UPL the last column's "up";
+// the forms ending in 0 are row 0's, whose diagonal and "up" operands are the boundary's constant 0 (it writes u0..u6 and pd without
+// reading them); P16I_ROW1: the second row of a pair, whole.
+#define P16I_ADDS(IDX, FLD, DIAG)                        \
+    "s_bfe_u32 %[" IDX "], %[pw], %[" FLD "]\n\t"         \
+    "s_set_gpr_idx_on %[" IDX "], gpr_idx(SRC1)\n\t"     \
+    "v_add_u32 %[t0], " DIAG ", v216\n\t"                \
+    "v_add_u32 %[t1], %[u0], v217\n\t"                   \
+    "v_add_u32 %[t2], %[u1], v218\n\t"                   \
+    "v_add_u32 %[t3], %[u2], v219\n\t"                   \
+    "v_add_u32 %[t4], %[u3], v220\n\t"                   \
+    "v_add_u32 %[t5], %[u4], v221\n\t"                   \
+    "v_add_u32 %[t6], %[u5], v222\n\t"                   \
+    "v_add_u32 %[t7], %[u6], v223\n\t"                   \
+    "s_set_gpr_idx_off"
+#define P16I_ADDS0(IDX, FLD)                             \
+    "s_bfe_u32 %[" IDX "], %[pw], %[" FLD "]\n\t"         \
+    "s_set_gpr_idx_on %[" IDX "], gpr_idx(SRC1)\n\t"     \
+    "v_add_u32 %[t0], 0, v216\n\t"                       \
+    "v_add_u32 %[t1], 0, v217\n\t"                       \
+    "v_add_u32 %[t2], 0, v218\n\t"                       \
+    "v_add_u32 %[t3], 0, v219\n\t"                       \
+    "v_add_u32 %[t4], 0, v220\n\t"                       \
+    "v_add_u32 %[t5], 0, v221\n\t"                       \
+    "v_add_u32 %[t6], 0, v222\n\t"                       \
+    "v_add_u32 %[t7], 0, v223\n\t"                       \
+    "s_set_gpr_idx_off"
+#define P16I_CHAIN(LEFT, UPL)                                    \
+    "v_pk_maximum3_f16 %[t0], %[t0], %[u0], " LEFT "\n\t"        \
+    "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"           \
+    "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"           \
+    "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"           \
+    "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"           \
+    "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"           \
+    "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"           \
+    "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"           \
+    "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"           \
+    "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"           \
+    "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[pd], %[t7], " UPL ", %[u6]\n\t"         \
+    "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]"
+#define P16I_CHAIN0                                              \
+    "v_pk_maximum3_f16 %[t0], %[t0], 0, %[c0]\n\t"               \
+    "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t1], %[t1], 0, %[u0]\n\t"               \
+    "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"           \
+    "v_pk_maximum3_f16 %[t2], %[t2], 0, %[u1]\n\t"               \
+    "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t3], %[t3], 0, %[u2]\n\t"               \
+    "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"           \
+    "v_pk_maximum3_f16 %[t4], %[t4], 0, %[u3]\n\t"               \
+    "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[t5], %[t5], 0, %[u4]\n\t"               \
+    "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"           \
+    "v_pk_maximum3_f16 %[t6], %[t6], 0, %[u5]\n\t"               \
+    "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"                  \
+    "v_pk_maximum3_f16 %[pd], %[t7], 0, %[u6]\n\t"               \
+    "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]"
+#define P16I_ROW1 P16I_ADDS("i1", "f1", "%[c0]") "\n\t" "v_pk_sub_u16 %[c0], %[pd], %[g] clamp\n\t" P16I_CHAIN("%[l1]", "%[c0]")
+// ... and its operands (r, t, i0, i1, u, best, col, pw, g and the profile registers p0..p3, pz of the body)
+#define P16I_TMPS                                                                                                                \
+    [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]), [t6] "=&v"(t[6]), \
+        [t7] "=&v"(t[7]), [i0] "=&s"(i0), [i1] "=&s"(i1)
+#define P16I_UPS(CON) \
+    [u0] CON(u[0]), [u1] CON(u[1]), [u2] CON(u[2]), [u3] CON(u[3]), [u4] CON(u[4]), [u5] CON(u[5]), [u6] CON(u[6])
+#define P16I_BEST [b0] "+v"(best[0]), [b1] "+v"(best[1]), [b2] "+v"(best[2]), [b3] "+v"(best[3])
+#define P16I_INS                                                                                                                    \
+    [l1] "v"(col[r + 1 < R ? r + 1 : r]), [pw] "s"(pw[r >> 2]), [f0] "i"((8 * (r & 3)) | (8 << 16)), [f1] "i"((8 * ((r + 1) & 3)) | (8 << 16)), \
+        [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
+
+// The leading column blocks of a PROF16 task that load their texts without word()'s clamp and pad merge: block jb prefetches bytes
+// 8 jb + 8 .. 8 jb + 15 of every lane's two texts, which are whole words inside every text while 8 jb + 16 <= the task's shortest
+__host__ __device__ constexpr int prof16_interior_blocks(int min_len) { return min_len >= 16 ? min_len / 8 - 1 : 0; }
+
 template <int R, bool INT>
 __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
     constexpr int C = 8, NW = (R + 3) / 4;
@@ -438,6 +522,18 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
             return (v & keep) | (0x0c0c0c0cu & ~keep);
         };
 
+        // The leading column blocks whose prefetch needs neither the clamp nor the pad merge of word(): block jb loads bytes 8 jb + 8
+        // .. 8 jb + 15 of both texts, whole words inside every text of the task up to its shortest one (the host gives an empty slot
+        // the task's shortest text, pwalign.hip).  Wave-uniform, so the choice below is a scalar branch around the loads alone: both
+        // kinds of block run the one copy of the row code.
+        // (The f16 row keeps word() for every block: its register allocation is tight enough that the second kind of load moves it.)
+        int nint = 0;
+        if constexpr (INT) {
+            int mn = min(ma, mb);
+            for (int o = 32; o; o >>= 1) mn = min(mn, __shfl_xor(mn, o));
+            nint = prof16_interior_blocks(__builtin_amdgcn_readfirstlane(mn));
+        }
+
         // G of the left boundary column (H = 0): g in every row (INT: H = 0)
         const uint32_t edge = INT ? 0u : g;
         uint32_t col[R];
@@ -449,27 +545,47 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
         uint32_t nb0 = word(toff_b, mb, 0), nb1 = word(toff_b, mb, 1);
         for (int jb = 0; jb < nblk; ++jb) {
             const uint32_t wa[2] = {na0, na1}, wb[2] = {nb0, nb1};
-            na0 = word(toff_a, ma, 2 * jb + 2);
-            na1 = word(toff_a, ma, 2 * jb + 3);
-            nb0 = word(toff_b, mb, 2 * jb + 2);
-            nb1 = word(toff_b, mb, 2 * jb + 3);
+            if (INT && jb < nint) {
+                const uint32_t* const qa = reinterpret_cast<const uint32_t*>(P.arena + (toff_a + 8u * (uint32_t)jb + 8u));
+                const uint32_t* const qb = reinterpret_cast<const uint32_t*>(P.arena + (toff_b + 8u * (uint32_t)jb + 8u));
+                na0 = qa[0];
+                na1 = qa[1];
+                nb0 = qb[0];
+                nb1 = qb[1];
+            } else {
+                na0 = word(toff_a, ma, 2 * jb + 2);
+                na1 = word(toff_a, ma, 2 * jb + 3);
+                nb0 = word(toff_b, mb, 2 * jb + 2);
+                nb1 = word(toff_b, mb, 2 * jb + 3);
+            }
             // the block's profile: selector (cA, cA | 4, cB, cB | 4) per column, then one v_perm per code
-            // (INT: selector (cA, 12, cB, 12) -- byte 12 selects 0x00 -- into the one table)
+            // (INT: selector (cA, 12, cB, 12) -- byte 12 selects 0x00 -- into the one table.  The 12 has to be a source byte of the
+            // perm that makes the selector, and the two text words fill both sources: so one perm gathers two columns' codes
+            // (cA, cA', cB, cB'), and each column's perm takes its two of them and the low byte of the inline constant 12: three
+            // perms per two columns, no v_or)
             u32x8 p0, p1, p2, p3;
 #pragma unroll
             for (int k = 0; k < C; ++k) {
                 const uint32_t kk = (uint32_t)(k & 3);
-                const uint32_t sel = INT ? __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk + ((4u + kk) << 16) + 0x0c000c00u) | 0x0c000c00u
-                                         : __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk * 0x00000101u + (4u + kk) * 0x01010000u) | 0x04000400u;
+                uint32_t sel;
+                if constexpr (INT) {
+                    const uint32_t two = __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk < 2 ? 0x05040100u : 0x07060302u);
+                    sel = __builtin_amdgcn_perm(12u, two, 0x04020400u + (kk & 1u) * 0x00010001u);
+                } else {
+                    sel = __builtin_amdgcn_perm(wb[k >> 2], wa[k >> 2], kk * 0x00000101u + (4u + kk) * 0x01010000u) | 0x04000400u;
+                }
                 p0[k] = __builtin_amdgcn_perm(thi[0], tlo[0], sel);
                 p1[k] = __builtin_amdgcn_perm(thi[1], tlo[1], sel);
                 p2[k] = __builtin_amdgcn_perm(thi[2], tlo[2], sel);
                 p3[k] = __builtin_amdgcn_perm(thi[3], tlo[3], sel);
             }
-            // row -1 (H = 0): G_up = g in every column, and the diagonal of row 0's first column
+            // row -1 (H = 0): G_up = g in every column, and the diagonal of row 0's first column (INT: row 0's text takes the
+            // constant 0 for them and writes u[])
             uint32_t u[C];
+            if constexpr (!INT) {
 #pragma unroll
-            for (int k = 0; k < C; ++k) u[k] = edge;
+                for (int k = 0; k < C; ++k) u[k] = edge;
+            }
             if constexpr (INT) {
                 // The move-free row, two rows to an asm text.  The last column's subtract of a row is deferred into the next row's
                 // step (pend = its m, still due): row r first reads the OLD col[r - 1] as its diagonal, then the deferred subtract
@@ -483,154 +599,25 @@ __device__ __forceinline__ void scores16p_body(const BatchParams& P) {
                 // (each costs 9 VALU and a taken branch instead of 56).  A branch in the C++ loop instead (an exit per pair) makes
                 // the compiler copy u[] and best[] at every exit: 11 v_mov per pair.
                 static_assert(R % 2 == 0, "the integer row runs its rows in pairs");
-                uint32_t pend = 0;
+                uint32_t pend;
 #pragma unroll
                 for (int r = 0; r < R; r += 2) {
                     uint32_t t[C], i0, i1;
                     if (r == 0) {
-                        asm volatile(
-                            "s_bfe_u32 %[i0], %[pw], %[f0]\n\t"
-                            "s_set_gpr_idx_on %[i0], gpr_idx(SRC1)\n\t"
-                            "v_add_u32 %[t0], 0, v216\n\t"
-                            "v_add_u32 %[t1], %[u0], v217\n\t"
-                            "v_add_u32 %[t2], %[u1], v218\n\t"
-                            "v_add_u32 %[t3], %[u2], v219\n\t"
-                            "v_add_u32 %[t4], %[u3], v220\n\t"
-                            "v_add_u32 %[t5], %[u4], v221\n\t"
-                            "v_add_u32 %[t6], %[u5], v222\n\t"
-                            "v_add_u32 %[t7], %[u6], v223\n\t"
-                            "s_set_gpr_idx_off\n\t"
-                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[c0]\n\t"
-                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[pd], %[t7], 0, %[u6]\n\t"
-                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n\t"
-                            "s_bfe_u32 %[i1], %[pw], %[f1]\n\t"
-                            "s_set_gpr_idx_on %[i1], gpr_idx(SRC1)\n\t"
-                            "v_add_u32 %[t0], %[c0], v216\n\t"
-                            "v_add_u32 %[t1], %[u0], v217\n\t"
-                            "v_add_u32 %[t2], %[u1], v218\n\t"
-                            "v_add_u32 %[t3], %[u2], v219\n\t"
-                            "v_add_u32 %[t4], %[u3], v220\n\t"
-                            "v_add_u32 %[t5], %[u4], v221\n\t"
-                            "v_add_u32 %[t6], %[u5], v222\n\t"
-                            "v_add_u32 %[t7], %[u6], v223\n\t"
-                            "s_set_gpr_idx_off\n\t"
-                            "v_pk_sub_u16 %[c0], %[pd], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l1]\n\t"
-                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[pd], %[t7], %[c0], %[u6]\n\t"
-                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]"
-                            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
-                              [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [i0] "=&s"(i0), [i1] "=&s"(i1), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]),
-                              [u3] "+v"(u[3]), [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
-                              [b2] "+v"(best[2]), [b3] "+v"(best[3]), [pd] "+v"(pend), [c0] "+v"(col[r])
-                            : [l1] "v"(col[r + 1 < R ? r + 1 : r]), [pw] "s"(pw[r >> 2]), [f0] "i"((8 * (r & 3)) | (8 << 16)), [f1] "i"((8 * ((r + 1) & 3)) | (8 << 16)),
-                              [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
-                            : "m0", "scc");
+                        asm volatile(P16I_ADDS0("i0", "f0") "\n\t" P16I_CHAIN0 "\n\t" P16I_ROW1
+                                     : P16I_TMPS, P16I_UPS("=&v"), P16I_BEST, [pd] "=&v"(pend), [c0] "+v"(col[r])
+                                     : P16I_INS
+                                     : "m0", "scc");
                     } else {
-                        asm volatile(
-                            "s_bfe_u32 %[i0], %[pw], %[f0]\n\t"
-                            "s_set_gpr_idx_on %[i0], gpr_idx(SRC1)\n\t"
-                            "v_add_u32 %[t0], %[cp], v216\n\t"
-                            "v_add_u32 %[t1], %[u0], v217\n\t"
-                            "v_add_u32 %[t2], %[u1], v218\n\t"
-                            "v_add_u32 %[t3], %[u2], v219\n\t"
-                            "v_add_u32 %[t4], %[u3], v220\n\t"
-                            "v_add_u32 %[t5], %[u4], v221\n\t"
-                            "v_add_u32 %[t6], %[u5], v222\n\t"
-                            "v_add_u32 %[t7], %[u6], v223\n\t"
-                            "s_set_gpr_idx_off\n\t"
-                            "v_pk_sub_u16 %[cp], %[pd], %[g] clamp\n\t"
-                            "s_cmp_eq_u32 %[i0], 32\n\t"
-                            "s_cbranch_scc1 .Lpad%=\n\t"
-                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[c0]\n\t"
-                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[pd], %[t7], %[cp], %[u6]\n\t"
-                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n\t"
-                            "s_bfe_u32 %[i1], %[pw], %[f1]\n\t"
-                            "s_set_gpr_idx_on %[i1], gpr_idx(SRC1)\n\t"
-                            "v_add_u32 %[t0], %[c0], v216\n\t"
-                            "v_add_u32 %[t1], %[u0], v217\n\t"
-                            "v_add_u32 %[t2], %[u1], v218\n\t"
-                            "v_add_u32 %[t3], %[u2], v219\n\t"
-                            "v_add_u32 %[t4], %[u3], v220\n\t"
-                            "v_add_u32 %[t5], %[u4], v221\n\t"
-                            "v_add_u32 %[t6], %[u5], v222\n\t"
-                            "v_add_u32 %[t7], %[u6], v223\n\t"
-                            "s_set_gpr_idx_off\n\t"
-                            "v_pk_sub_u16 %[c0], %[pd], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t0], %[t0], %[u0], %[l1]\n\t"
-                            "v_pk_sub_u16 %[u0], %[t0], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t1], %[t1], %[u1], %[u0]\n\t"
-                            "v_pk_sub_u16 %[u1], %[t1], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b0], %[b0], %[t0], %[t1]\n\t"
-                            "v_pk_maximum3_f16 %[t2], %[t2], %[u2], %[u1]\n\t"
-                            "v_pk_sub_u16 %[u2], %[t2], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t3], %[t3], %[u3], %[u2]\n\t"
-                            "v_pk_sub_u16 %[u3], %[t3], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b1], %[b1], %[t2], %[t3]\n\t"
-                            "v_pk_maximum3_f16 %[t4], %[t4], %[u4], %[u3]\n\t"
-                            "v_pk_sub_u16 %[u4], %[t4], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[t5], %[t5], %[u5], %[u4]\n\t"
-                            "v_pk_sub_u16 %[u5], %[t5], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[b2], %[b2], %[t4], %[t5]\n\t"
-                            "v_pk_maximum3_f16 %[t6], %[t6], %[u6], %[u5]\n\t"
-                            "v_pk_sub_u16 %[u6], %[t6], %[g] clamp\n\t"
-                            "v_pk_maximum3_f16 %[pd], %[t7], %[c0], %[u6]\n\t"
-                            "v_pk_maximum3_f16 %[b3], %[b3], %[t6], %[pd]\n"
-                            ".Lpad%=:"
-                            : [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]),
-                              [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [i0] "=&s"(i0), [i1] "=&s"(i1), [u0] "+v"(u[0]), [u1] "+v"(u[1]), [u2] "+v"(u[2]),
-                              [u3] "+v"(u[3]), [u4] "+v"(u[4]), [u5] "+v"(u[5]), [u6] "+v"(u[6]), [b0] "+v"(best[0]), [b1] "+v"(best[1]),
-                              [b2] "+v"(best[2]), [b3] "+v"(best[3]), [pd] "+v"(pend), [c0] "+v"(col[r]), [cp] "+v"(col[r > 0 ? r - 1 : 0])
-                            : [l1] "v"(col[r + 1 < R ? r + 1 : r]), [pw] "s"(pw[r >> 2]), [f0] "i"((8 * (r & 3)) | (8 << 16)), [f1] "i"((8 * ((r + 1) & 3)) | (8 << 16)),
-                              [g] "s"(g), "{v[216:223]}"(p0), "{v[224:231]}"(p1), "{v[232:239]}"(p2), "{v[240:247]}"(p3), "{v[248:255]}"(pz)
-                            : "m0", "scc");
+                        asm volatile(P16I_ADDS("i0", "f0", "%[cp]") "\n\t"
+                                     "v_pk_sub_u16 %[cp], %[pd], %[g] clamp\n\t"
+                                     "s_cmp_eq_u32 %[i0], 32\n\t"
+                                     "s_cbranch_scc1 .Lpad%=\n\t"
+                                     P16I_CHAIN("%[c0]", "%[cp]") "\n\t" P16I_ROW1 "\n"
+                                     ".Lpad%=:"
+                                     : P16I_TMPS, P16I_UPS("+v"), P16I_BEST, [pd] "+v"(pend), [c0] "+v"(col[r]), [cp] "+v"(col[r > 0 ? r - 1 : 0])
+                                     : P16I_INS
+                                     : "m0", "scc");
                     }
                 }
                 // the last row's pending subtract, when no pair was skipped (otherwise col[R - 1] is a pad row's)

@@ -785,6 +785,12 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
                         stlen[t * kTaskLanes + l] = (uint32_t)in.len(in.pair_b[k]);
                     }
                 }
+                // PROF16: an empty slot streams the task's shortest text (its last: group_by_pattern), so that the kernel's unmasked
+                // loads, which go by the shortest text of all 128 slots, stay inside a text in every lane
+                for (uint32_t l = ht[t].count; b->prof16 && ht[t].count > 0 && l < kTaskLanes; ++l) {
+                    stoff[t * kTaskLanes + l] = stoff[t * kTaskLanes + ht[t].count - 1];
+                    stlen[t * kTaskLanes + l] = stlen[t * kTaskLanes + ht[t].count - 1];
+                }
             }
         };
         std::vector<std::thread> pool;
@@ -1476,6 +1482,13 @@ int pwa_batch_profile_form(const pwa_batch* b) {
 int pwa_batch_profile_int(const pwa_batch* b) {
     if (!b) return PWA_E_INVALID;
     return b->use_strips && b->prof16 && b->prof16_int ? 1 : 0;
+}
+
+int pwa_profile_plan(uint32_t min_text_len, uint32_t max_text_len, uint32_t* interior_blocks, uint32_t* blocks) {
+    if (!interior_blocks || !blocks || min_text_len > max_text_len || max_text_len > 0x7fffffffu) return PWA_E_INVALID;
+    *blocks = (max_text_len + 7) / 8;
+    *interior_blocks = std::min<uint32_t>((uint32_t)prof16_interior_blocks((int)min_text_len), *blocks);
+    return PWA_OK;
 }
 
 int pwa_batch_cell_bits(const pwa_batch* b) {

@@ -182,6 +182,11 @@ int pwa_batch_profile_form(const pwa_batch *b);
 /* 1 when that profile form runs its integer-coded row step (scores stored as integers, one 32-bit add per two cells; taken when
  * mismatch - gap >= 0 and match - gap >= 0 unless PWA_PROF16_INT=0), 0 otherwise.  Scores are the same either way. */
 int pwa_batch_profile_int(const pwa_batch *b);
+/* Host only, no context: the column-block loop of the profile form's integer row for one wave task.  blocks: the 8-column blocks
+ * of a task whose longest text has max_text_len columns; interior_blocks: how many of them, from the first, prefetch their texts
+ * with plain loads (whole words inside every text of the task, the shortest having min_text_len columns) -- the rest clamp the
+ * word index and merge the pad code.  Scores do not depend on it. */
+int pwa_profile_plan(uint32_t min_text_len, uint32_t max_text_len, uint32_t *interior_blocks, uint32_t *blocks);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);
