@@ -1,13 +1,6 @@
 // approx_ctx.h -- what the approximate-search unit (approx_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign_internal.h.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "poison.h"
-
-struct pwa_ctx;
+#include "side_unit.h"
 
 namespace pwa {
 // the last pwa_approx_find / pwa_approx_occurrences: device ms of the count and the fill pass (events), tasks, text columns scanned
@@ -20,14 +13,9 @@ struct ApproxStartsStats {
     float ms = 0.f;
     uint64_t hits = 0, columns = 0;
 };
-struct ApproxCtxView {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool debug = false;              // PWA_DEBUG
+struct ApproxCtxView : UnitCtx {
     uint32_t chunk = 0;              // PWA_APPROX_CHUNK: most text columns a task reports
     uint64_t occ_chunk_hits = 0;     // PWA_OCC_CHUNK_HITS (0: the library's budget)
-    std::string* err = nullptr;      // the context's last-error text
-    Poison* poison = nullptr;        // the context's PWA_POISON state: every device allocation of the unit goes through poison_device
     ApproxStats* stats = nullptr;
     ApproxStartsStats* starts_stats = nullptr;
 };

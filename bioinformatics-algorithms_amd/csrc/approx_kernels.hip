@@ -16,43 +16,13 @@
 #include "sufarr_ctx.h"
 
 using namespace pwa::approx;
+using pwa::Dev;
+using pwa::Fail;
 
 namespace {
 
 constexpr uint64_t kDefaultSliceHits = 1ull << 27;   // 8 B of staging per hit: 1 GB per slice at most
 constexpr uint64_t kMaxSliceHits = 1ull << 31;       // offsets within a slice are uint32
-
-struct Dev {   // one device allocation, freed with its owner
-    void* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = std::max<size_t>(bytes, 16);
-        const hipError_t e = hipMalloc(&p, bytes);
-        return e == hipSuccess ? pwa::poison_device(po, p, bytes) : e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-};
-
-struct Fail {   // an error on the way: the code and what to say about it
-    int code;
-    std::string what;
-};
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Fail{e == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define AP_CHECK(call) check((call), #call)
 
 using scan_kernel_t = decltype(&approx_scan_kernel<1, false>);
 template <bool FILL>
@@ -88,11 +58,11 @@ void launch_scan(const pwa::ApproxCtxView& v, Search& s, bool fill, uint32_t t0,
         if (!waves) continue;
         scan_kernel_t kern = fill ? scan_kernel_for<true>(W) : scan_kernel_for<false>(W);
         const size_t lds = (size_t)s.rows * W * 64 * 8;
-        if (lds > 64 * 1024) AP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (lds > 64 * 1024) UNIT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(waves), dim3(64), lds, v.stream, s.text.as<uint8_t>(), s.peq.as<uint64_t>(), s.d_pats.as<Pat>(), s.tasks.as<Task>(),
                            s.lane_task.as<uint32_t>() + (size_t)64 * s.first_wave[W], s.rows, s.task_cnt.as<uint32_t>(), s.pat_cnt.as<uint32_t>(),
                            s.pat_best.as<unsigned long long>(), t0, t1, d_off, d_out, out_cap);
-        AP_CHECK(hipGetLastError());
+        UNIT_CHECK(hipGetLastError());
     }
 }
 
@@ -146,14 +116,14 @@ void stage_inputs(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, u
     }
     (void)hipSetDevice(v.device);
     s.tbytes = (n + 15) / 16 * 16 + 16;
-    AP_CHECK(s.text.alloc(v.poison, s.tbytes));
-    AP_CHECK(s.blob.alloc(v.poison, bytes));
-    AP_CHECK(s.d_pats.alloc(v.poison, (size_t)n_pat * sizeof(Pat)));
-    AP_CHECK(s.peq.alloc(v.poison, s.peq_words * 8));
-    AP_CHECK(hipMemsetAsync(s.text.p, 0, s.tbytes, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.d_pats.p, s.pats.data(), (size_t)n_pat * sizeof(Pat), hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(s.text.alloc(v.poison, s.tbytes));
+    UNIT_CHECK(s.blob.alloc(v.poison, bytes));
+    UNIT_CHECK(s.d_pats.alloc(v.poison, (size_t)n_pat * sizeof(Pat)));
+    UNIT_CHECK(s.peq.alloc(v.poison, s.peq_words * 8));
+    UNIT_CHECK(hipMemsetAsync(s.text.p, 0, s.tbytes, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.text.p, text, n, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.d_pats.p, s.pats.data(), (size_t)n_pat * sizeof(Pat), hipMemcpyHostToDevice, v.stream));
 }
 
 // Uploads, codes the text, builds the masks, runs the count pass; fills s.h_cnt / s.h_best and the stats of v
@@ -199,29 +169,28 @@ void count_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, uin
     }
     s.first_wave[kMaxWords + 1] = (uint32_t)(lane_task.size() / 64);
 
-    AP_CHECK(s.tasks.alloc(v.poison, nt * sizeof(Task)));
-    AP_CHECK(s.lane_task.alloc(v.poison, lane_task.size() * 4));
-    AP_CHECK(s.task_cnt.alloc(v.poison, nt * 4));
-    AP_CHECK(s.pat_cnt.alloc(v.poison, (size_t)n_pat * 4));
-    AP_CHECK(s.pat_best.alloc(v.poison, (size_t)n_pat * 8));
-    Events ev;
-    AP_CHECK(hipEventCreate(&ev.a));
-    AP_CHECK(hipEventCreate(&ev.b));
-    AP_CHECK(hipMemcpyAsync(s.tasks.p, tasks.data(), nt * sizeof(Task), hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.lane_task.p, lane_task.data(), lane_task.size() * 4, hipMemcpyHostToDevice, v.stream));
-    AP_CHECK(hipMemsetAsync(s.pat_cnt.p, 0, (size_t)n_pat * 4, v.stream));
-    AP_CHECK(hipMemsetAsync(s.pat_best.p, 0xff, (size_t)n_pat * 8, v.stream));
-    AP_CHECK(hipEventRecord(ev.a, v.stream));
-    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
+    UNIT_CHECK(s.tasks.alloc(v.poison, nt * sizeof(Task)));
+    UNIT_CHECK(s.lane_task.alloc(v.poison, lane_task.size() * 4));
+    UNIT_CHECK(s.task_cnt.alloc(v.poison, nt * 4));
+    UNIT_CHECK(s.pat_cnt.alloc(v.poison, (size_t)n_pat * 4));
+    UNIT_CHECK(s.pat_best.alloc(v.poison, (size_t)n_pat * 8));
+    pwa::Events<2> ev;
+    UNIT_CHECK(ev.create());
+    UNIT_CHECK(hipMemcpyAsync(s.tasks.p, tasks.data(), nt * sizeof(Task), hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.lane_task.p, lane_task.data(), lane_task.size() * 4, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemsetAsync(s.pat_cnt.p, 0, (size_t)n_pat * 4, v.stream));
+    UNIT_CHECK(hipMemsetAsync(s.pat_best.p, 0xff, (size_t)n_pat * 8, v.stream));
+    UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
+    UNIT_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
     const uint64_t mask_threads = (uint64_t)n_pat * s.rows * kMaxWords;
     approx_masks_kernel<<<(uint32_t)((mask_threads + 255) / 256), 256, 0, v.stream>>>(s.blob.as<uint8_t>(), s.d_pats.as<Pat>(), n_pat, s.rows, tab, s.peq.as<uint64_t>());
-    AP_CHECK(hipGetLastError());
+    UNIT_CHECK(hipGetLastError());
     launch_scan(v, s, false, 0, 0, nullptr, nullptr, 0);
-    AP_CHECK(hipEventRecord(ev.b, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.h_cnt.data(), s.pat_cnt.p, (size_t)n_pat * 4, hipMemcpyDeviceToHost, v.stream));
-    AP_CHECK(hipMemcpyAsync(s.h_best.data(), s.pat_best.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, v.stream));
-    AP_CHECK(hipStreamSynchronize(v.stream));
-    AP_CHECK(hipEventElapsedTime(&v.stats->count_ms, ev.a, ev.b));
+    UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.h_cnt.data(), s.pat_cnt.p, (size_t)n_pat * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(s.h_best.data(), s.pat_best.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    UNIT_CHECK(hipEventElapsedTime(&v.stats->count_ms, ev.e[0], ev.e[1]));
     v.stats->tasks = nt;
     v.stats->columns = s.columns;
     if (v.debug)
@@ -234,49 +203,39 @@ void fill_pass(const pwa::ApproxCtxView& v, Search& s, uint64_t* occ) {
     if (!s.n_tasks) return;
     const uint64_t budget = std::min(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultSliceHits, kMaxSliceHits);
     std::vector<uint32_t> cnt(s.n_tasks);
-    AP_CHECK(hipMemcpyAsync(cnt.data(), s.task_cnt.p, s.n_tasks * 4, hipMemcpyDeviceToHost, v.stream));
-    AP_CHECK(hipStreamSynchronize(v.stream));
-    struct Slice {
-        uint32_t t0, t1;
-        uint64_t hits;
-    };
-    std::vector<Slice> slices;
+    UNIT_CHECK(hipMemcpyAsync(cnt.data(), s.task_cnt.p, s.n_tasks * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    std::vector<pwa::Run> slices = pwa::cut_runs(s.n_tasks, budget, [&](uint64_t t) { return (uint64_t)cnt[t]; });
+    slices.erase(std::remove_if(slices.begin(), slices.end(), [](const pwa::Run& sl) { return !sl.weight; }), slices.end());   // (nothing to fill)
+    if (slices.empty()) return;
     uint64_t max_hits = 0;
     uint32_t max_nt = 0;
-    for (uint32_t t0 = 0; t0 < s.n_tasks;) {
-        uint64_t hits = cnt[t0];
-        uint32_t t1 = t0 + 1;
-        while (t1 < s.n_tasks && hits + cnt[t1] <= budget) hits += cnt[t1++];
-        if (hits) {
-            slices.push_back({t0, t1, hits});
-            max_hits = std::max(max_hits, hits);
-            max_nt = std::max(max_nt, t1 - t0);
-        }
-        t0 = t1;
+    for (const pwa::Run& sl : slices) {
+        max_hits = std::max(max_hits, sl.weight);
+        max_nt = std::max(max_nt, (uint32_t)(sl.k1 - sl.k0));
     }
-    if (slices.empty()) return;
     Dev off, part, stage;
-    AP_CHECK(off.alloc(v.poison, (size_t)max_nt * 4));
-    AP_CHECK(part.alloc(v.poison, pwa::scan_part_words(max_nt) * 4));
-    AP_CHECK(stage.alloc(v.poison, max_hits * 8));
-    Events ev;
-    AP_CHECK(hipEventCreate(&ev.a));
-    AP_CHECK(hipEventCreate(&ev.b));
+    UNIT_CHECK(off.alloc(v.poison, (size_t)max_nt * 4));
+    UNIT_CHECK(part.alloc(v.poison, pwa::scan_part_words(max_nt) * 4));
+    UNIT_CHECK(stage.alloc(v.poison, max_hits * 8));
+    pwa::Events<2> ev;
+    UNIT_CHECK(ev.create());
     uint64_t kept = 0;
-    for (const Slice& sl : slices) {
-        const uint32_t nt = sl.t1 - sl.t0;
-        AP_CHECK(hipEventRecord(ev.a, v.stream));
-        AP_CHECK(hipMemcpyAsync(off.p, s.task_cnt.as<uint32_t>() + sl.t0, (size_t)nt * 4, hipMemcpyDeviceToDevice, v.stream));
+    for (const pwa::Run& sl : slices) {
+        const uint32_t t0 = (uint32_t)sl.k0, t1 = (uint32_t)sl.k1, nt = t1 - t0;
+        const uint64_t hits = sl.weight;
+        UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
+        UNIT_CHECK(hipMemcpyAsync(off.p, s.task_cnt.as<uint32_t>() + t0, (size_t)nt * 4, hipMemcpyDeviceToDevice, v.stream));
         pwa::scan_excl(v.stream, off.as<uint32_t>(), nt, part.as<uint32_t>());
-        AP_CHECK(hipGetLastError());
-        launch_scan(v, s, true, sl.t0, sl.t1, off.as<uint32_t>(), stage.as<uint64_t>(), (uint32_t)sl.hits);
-        AP_CHECK(hipEventRecord(ev.b, v.stream));
-        AP_CHECK(hipMemcpyAsync(occ + kept, stage.p, sl.hits * 8, hipMemcpyDeviceToHost, v.stream));
-        AP_CHECK(hipStreamSynchronize(v.stream));
+        UNIT_CHECK(hipGetLastError());
+        launch_scan(v, s, true, t0, t1, off.as<uint32_t>(), stage.as<uint64_t>(), (uint32_t)hits);
+        UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+        UNIT_CHECK(hipMemcpyAsync(occ + kept, stage.p, hits * 8, hipMemcpyDeviceToHost, v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
         float ms = 0.f;
-        AP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+        UNIT_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
         v.stats->fill_ms += ms;
-        kept += sl.hits;
+        kept += hits;
     }
     if (v.debug) std::fprintf(stderr, "[pwa] approx fill: %zu slices, %llu hits, device %.3f ms\n", slices.size(), (unsigned long long)kept, v.stats->fill_ms);
 }
@@ -315,54 +274,48 @@ void starts_pass(const pwa::ApproxCtxView& v, Search& s, const uint8_t* text, ui
     const uint64_t budget = std::min(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultSliceHits, kMaxSliceHits);
     const uint64_t slice_cap = std::min(budget, total);
     Dev recs, starts;
-    AP_CHECK(recs.alloc(v.poison, slice_cap * sizeof(Hit)));
-    AP_CHECK(starts.alloc(v.poison, total * 4));
-    Events ev;
-    AP_CHECK(hipEventCreate(&ev.a));
-    AP_CHECK(hipEventCreate(&ev.b));
+    UNIT_CHECK(recs.alloc(v.poison, slice_cap * sizeof(Hit)));
+    UNIT_CHECK(starts.alloc(v.poison, total * 4));
+    pwa::Events<2> ev;
+    UNIT_CHECK(ev.create());
     float ms = 0.f, part = 0.f;
-    AP_CHECK(hipEventRecord(ev.a, v.stream));
-    AP_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
+    UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
+    UNIT_CHECK(pwa::recode_bytes(v.stream, s.text.as<uint8_t>(), s.tbytes / 16, tab.t));
     const uint64_t mask_threads = (uint64_t)n_pat * s.rows * kMaxWords;
     approx_masks_rev_kernel<<<(uint32_t)((mask_threads + 255) / 256), 256, 0, v.stream>>>(s.blob.as<uint8_t>(), s.d_pats.as<Pat>(), n_pat, s.rows, tab,
                                                                                           s.peq.as<uint64_t>());
-    AP_CHECK(hipGetLastError());
-    AP_CHECK(hipEventRecord(ev.b, v.stream));
-    AP_CHECK(hipStreamSynchronize(v.stream));
-    AP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+    UNIT_CHECK(hipGetLastError());
+    UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    UNIT_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     uint64_t slices = 0;
     for (uint64_t h0 = 0; h0 < total; h0 += slice_cap, ++slices) {
         const uint64_t h1 = std::min(h0 + slice_cap, total);
-        AP_CHECK(hipMemcpyAsync(recs.p, sorted.data() + h0, (h1 - h0) * sizeof(Hit), hipMemcpyHostToDevice, v.stream));
-        AP_CHECK(hipEventRecord(ev.a, v.stream));
+        UNIT_CHECK(hipMemcpyAsync(recs.p, sorted.data() + h0, (h1 - h0) * sizeof(Hit), hipMemcpyHostToDevice, v.stream));
+        UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
         for (int W = 1; W <= kMaxWords; ++W) {
             const uint64_t c0 = std::max(h0, class_at[W]), c1 = std::min(h1, class_at[W + 1]);
             if (c0 >= c1) continue;
             start_kernel_t kern = start_kernel_for(W);
             const size_t lds = (size_t)s.rows * W * 64 * 8;
-            if (lds > 64 * 1024) AP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            if (lds > 64 * 1024) UNIT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(kern, dim3((uint32_t)((c1 - c0 + 63) / 64)), dim3(64), lds, v.stream, s.text.as<uint8_t>(), s.peq.as<uint64_t>(), s.d_pats.as<Pat>(),
                                recs.as<Hit>() + (c0 - h0), (uint32_t)(c1 - c0), s.rows, starts.as<uint32_t>());
-            AP_CHECK(hipGetLastError());
+            UNIT_CHECK(hipGetLastError());
         }
-        AP_CHECK(hipEventRecord(ev.b, v.stream));
-        AP_CHECK(hipStreamSynchronize(v.stream));   // the records of the next slice go into the same buffer
-        AP_CHECK(hipEventElapsedTime(&part, ev.a, ev.b));
+        UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));   // the records of the next slice go into the same buffer
+        UNIT_CHECK(hipEventElapsedTime(&part, ev.e[0], ev.e[1]));
         ms += part;
     }
-    AP_CHECK(hipMemcpyAsync(start_out, starts.p, total * 4, hipMemcpyDeviceToHost, v.stream));
-    AP_CHECK(hipStreamSynchronize(v.stream));
+    UNIT_CHECK(hipMemcpyAsync(start_out, starts.p, total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
     uint64_t columns = 0;   // what the lanes scanned, read off their answers: e - start, or the whole bound where there is none
     for (const Hit& h : sorted) columns += start_out[h.out] == kNoStart ? std::min<uint64_t>(h.end, (uint64_t)s.pats[h.pat].m + h.dist) : h.end - start_out[h.out];
     *v.starts_stats = pwa::ApproxStartsStats{ms, total, columns};
     if (v.debug)
         std::fprintf(stderr, "[pwa] approx starts: %llu hits, %llu slices, %llu columns, device %.3f ms\n", (unsigned long long)total, (unsigned long long)slices,
                      (unsigned long long)columns, ms);
-}
-
-int fail(pwa::ApproxCtxView& v, const Fail& f) {
-    *v.err = f.what;
-    return f.code;
 }
 
 }  // namespace
@@ -398,7 +351,7 @@ int pwa_approx_find(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t
     CodeTable tab;
     uint32_t sigma = 0;
     if (const int rc = validate(v, "pwa_approx_find", n, pat_bytes, pat_off, n_pat, tab, sigma)) return rc;
-    try {
+    return pwa::guarded(v, [&] {
         Search s;
         count_pass(v, s, text, n, pat_bytes, pat_off, n_pat, max_dist, tab, sigma);
         for (uint32_t q = 0; q < n_pat; ++q) {
@@ -407,12 +360,7 @@ int pwa_approx_find(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t
             if (best_dist_out) best_dist_out[q] = hit ? (int32_t)(s.h_best[q] >> 32) : -1;
             if (best_end_out) best_end_out[q] = hit ? (uint32_t)s.h_best[q] : 0;
         }
-    } catch (const Fail& f) {
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+    });
 }
 
 int pwa_approx_occurrences(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat,
@@ -423,7 +371,7 @@ int pwa_approx_occurrences(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const 
     CodeTable tab;
     uint32_t sigma = 0;
     if (const int rc = validate(v, "pwa_approx_occurrences", n, pat_bytes, pat_off, n_pat, tab, sigma)) return rc;
-    try {
+    return pwa::guarded(v, [&] {
         Search s;
         count_pass(v, s, text, n, pat_bytes, pat_off, n_pat, max_dist, tab, sigma);
         uint64_t total = 0;
@@ -433,17 +381,9 @@ int pwa_approx_occurrences(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const 
         }
         occ_off[n_pat] = total;
         if (needed) *needed = total;
-        if (total > cap) {
-            *v.err = "pwa_approx_occurrences: " + std::to_string(total) + " hits, capacity " + std::to_string(cap);
-            return PWA_E_CAPACITY;
-        }
+        if (total > cap) throw Fail{PWA_E_CAPACITY, "pwa_approx_occurrences: " + std::to_string(total) + " hits, capacity " + std::to_string(cap)};
         if (total) fill_pass(v, s, occ);
-    } catch (const Fail& f) {
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+    });
 }
 
 int pwa_approx_starts(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat,
@@ -470,17 +410,12 @@ int pwa_approx_starts(pwa_ctx* ctx, const uint8_t* text, uint64_t n, const uint8
         *v.err = "pwa_approx_starts: more than 2^32 - 1 hits in one call";
         return PWA_E_CAPACITY;
     }
-    try {
+    return pwa::guarded(v, [&] {
         *v.starts_stats = pwa::ApproxStartsStats{};
-        if (!n_pat || occ_off[n_pat] == occ_off[0]) return PWA_OK;
+        if (!n_pat || occ_off[n_pat] == occ_off[0]) return;
         Search s;
         starts_pass(v, s, text, n, pat_bytes, pat_off, n_pat, occ_off, occ, tab, sigma, start_out);
-    } catch (const Fail& f) {
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+    });
 }
 
 int pwa_approx_starts_last_stats(const pwa_ctx* ctx, float* ms, uint64_t* hits, uint64_t* columns) {

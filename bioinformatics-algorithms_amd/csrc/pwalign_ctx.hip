@@ -8,7 +8,6 @@
 #include <cstring>
 #include <new>
 
-#include "approx_ctx.h"
 #include "banded_fill.hip.h"
 #include "sufarr_ctx.h"
 
@@ -92,26 +91,26 @@ void Knobs::read() {
     if (const char* e = std::getenv("PWA_APPROX_CHUNK")) approx_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)), 1u << 30);
 }
 
-pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
-    SaCtxView v;
+pwa::UnitCtx pwa::unit_ctx(pwa_ctx* c) {
+    UnitCtx v;
     v.device = c->device;
     v.stream = c->stream;
     v.debug = c->knobs.debug;
-    v.occ_chunk_hits = c->knobs.occ_chunk_hits;
     v.err = &c->err;
     v.poison = &c->poison;
     return v;
 }
 
+pwa::SaCtxView pwa::sa_ctx_view(pwa_ctx* c) {
+    SaCtxView v{unit_ctx(c)};
+    v.occ_chunk_hits = c->knobs.occ_chunk_hits;
+    return v;
+}
+
 pwa::ApproxCtxView pwa::approx_ctx_view(pwa_ctx* c) {
-    ApproxCtxView v;
-    v.device = c->device;
-    v.stream = c->stream;
-    v.debug = c->knobs.debug;
+    ApproxCtxView v{unit_ctx(c)};
     v.chunk = c->knobs.approx_chunk;
     v.occ_chunk_hits = c->knobs.occ_chunk_hits;
-    v.err = &c->err;
-    v.poison = &c->poison;
     v.stats = &c->approx_stats;
     v.starts_stats = &c->approx_starts_stats;
     return v;
@@ -120,13 +119,8 @@ const pwa::ApproxStats& pwa::approx_stats_of(const pwa_ctx* c) { return c->appro
 const pwa::ApproxStartsStats& pwa::approx_starts_stats_of(const pwa_ctx* c) { return c->approx_starts_stats; }
 
 pwa::WfaCtxView pwa::wfa_ctx_view(pwa_ctx* c) {
-    WfaCtxView v;
-    v.device = c->device;
-    v.stream = c->stream;
-    v.debug = c->knobs.debug;
+    WfaCtxView v{unit_ctx(c)};
     v.range_bytes = c->knobs.range_bytes;
-    v.err = &c->err;
-    v.poison = &c->poison;
     v.stats = &c->wfa_stats;
     return v;
 }
@@ -982,6 +976,41 @@ int pwa_selftest_host(uint32_t seed) try {
         };
         for (const auto& c : cases)
             if (parse_poison(c.s) != c.want) return check;
+    }
+    {   // cut_runs (side_unit.h): the edge cases by hand, then random lists against what defines the cut -- the runs tile 0 .. n in order,
+        // a run's weight is its items' sum, a run of several items fits the budget, and the item after a run would not have fitted
+        ++check;
+        static const struct {
+            uint64_t n, budget, w[5], runs, want[3][3];
+        } cases[] = {
+            {0, 5, {}, 0, {}},                                               // nothing to cut
+            {3, 5, {10, 1, 1}, 2, {{0, 1, 10}, {1, 3, 2}}},                  // a first item that alone exceeds the budget
+            {1, 5, {9}, 1, {{0, 1, 9}}},
+            {3, 0, {0, 0, 0}, 1, {{0, 3, 0}}},                               // zero weights
+            {5, 4, {0, 0, 5, 0, 0}, 3, {{0, 2, 0}, {2, 3, 5}, {3, 5, 0}}},
+            {5, 5, {1, 0, 4, 0, 1}, 2, {{0, 4, 5}, {4, 5, 1}}},
+            {3, 4, {2, 2, 2}, 2, {{0, 2, 4}, {2, 3, 2}}},                    // an exact fit
+        };
+        for (const auto& c : cases) {
+            const std::vector<Run> got = cut_runs(c.n, c.budget, [&](uint64_t k) { return c.w[k]; });
+            if (got.size() != c.runs) return check;
+            for (size_t r = 0; r < got.size(); ++r)
+                if (got[r].k0 != c.want[r][0] || got[r].k1 != c.want[r][1] || got[r].weight != c.want[r][2]) return check;
+        }
+        for (int rep = 0; rep < 200; ++rep) {
+            const uint64_t budget = rnd() % 40;
+            std::vector<uint64_t> w(rnd() % 30);
+            for (uint64_t& e : w) e = rnd() % 4 ? rnd() % 25 : 0;
+            uint64_t at = 0;
+            for (const Run& r : cut_runs(w.size(), budget, [&](uint64_t k) { return w[k]; })) {
+                uint64_t sum = 0;
+                for (uint64_t k = r.k0; k < r.k1; ++k) sum += w[k];
+                if (r.k0 != at || r.k1 <= r.k0 || r.k1 > w.size() || r.weight != sum || (r.k1 - r.k0 > 1 && sum > budget) || (r.k1 < w.size() && sum + w[r.k1] <= budget))
+                    return check;
+                at = r.k1;
+            }
+            if (at != w.size()) return check;
+        }
     }
     if (const int rc = selftest_pair_forms()) return check + rc;
     if (const int rc = selftest_banded_forms()) return check + 2 + rc;

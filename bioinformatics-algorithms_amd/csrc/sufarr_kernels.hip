@@ -15,49 +15,20 @@
 #include "sufarr_ctx.h"
 
 using namespace pwa::sufarr;
+using pwa::blocks_for;
+using pwa::Dev;
+using pwa::Fail;
 
 struct pwa_sa_index {
     pwa_ctx* ctx = nullptr;
     uint32_t n = 0;
-    uint8_t* d_text = nullptr;   // round_up(n, 8) + 16 bytes, zero past n (sufarr::load8)
-    uint32_t* d_sa = nullptr;
+    Dev d_text;   // round_up(n, 8) + 16 bytes, zero past n (sufarr::load8)
+    Dev d_sa;     // n positions (one where n == 0)
     uint32_t rounds = 0;
     float build_ms = 0.f, search_ms = 0.f;
 };
 
-namespace {
-
 constexpr uint64_t kDefaultChunkHits = 1ull << 27;   // 24 B of device buffers per raw hit: 3.2 GB per chunk at most
-
-struct Dev {   // one device allocation, freed with its owner
-    void* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = std::max<size_t>(bytes, 16);
-        const hipError_t e = hipMalloc(&p, bytes);
-        return e == hipSuccess ? pwa::poison_device(po, p, bytes) : e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-struct Fail {   // a HIP error on the way: the code and the call that returned it
-    int code;
-    std::string what;
-};
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Fail{e == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define SA_CHECK(call) check((call), #call)
-
-inline uint32_t blocks_for(size_t n, size_t per) { return (uint32_t)((n + per - 1) / per); }
-
-}  // namespace
 
 // x[0 .. len) := exclusive prefix sums, in place (reduce, scan of the chunk sums, apply); part: scan_part_words(len) words.
 // Also the scan of pwa_align_batch_cigar's string lengths (pwalign_align.hip), hence outside this unit's anonymous namespace.
@@ -85,9 +56,9 @@ struct SortScratch {
     Dev hist, part, bits;
     void alloc(pwa::Poison* po, size_t n) {
         const size_t tiles = std::max<size_t>(1, (n + kTile - 1) / kTile);
-        SA_CHECK(hist.alloc(po, tiles * kBuckets * 4));
-        SA_CHECK(part.alloc(po, ((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
-        SA_CHECK(bits.alloc(po, (2 * 1024 + 2) * 8));
+        UNIT_CHECK(hist.alloc(po, tiles * kBuckets * 4));
+        UNIT_CHECK(part.alloc(po, ((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
+        UNIT_CHECK(bits.alloc(po, (2 * 1024 + 2) * 8));
     }
 };
 
@@ -101,8 +72,8 @@ int radix_sort(hipStream_t s, SortBufs<K, V>& b, size_t n, SortScratch& sc) {
     key_bits_kernel<K><<<g, kThreads, 0, s>>>(b.k[b.cur], b.k[b.cur], n, bits, bits + g);
     key_bits_kernel<K><<<1, kThreads, 0, s>>>(bits, bits + g, g, bits + 2 * g, bits + 2 * g + 1);
     K h[2];
-    SA_CHECK(hipMemcpyAsync(h, bits + 2 * g, sizeof h, hipMemcpyDeviceToHost, s));
-    SA_CHECK(hipStreamSynchronize(s));
+    UNIT_CHECK(hipMemcpyAsync(h, bits + 2 * g, sizeof h, hipMemcpyDeviceToHost, s));
+    UNIT_CHECK(hipStreamSynchronize(s));
     const K vary = h[0] ^ h[1];
     int passes = 0;
     for (int sh = 0; sh < (int)(8 * sizeof(K)); sh += kRadixBits) {
@@ -114,13 +85,8 @@ int radix_sort(hipStream_t s, SortBufs<K, V>& b, size_t n, SortScratch& sc) {
         b.cur ^= 1;
         ++passes;
     }
-    SA_CHECK(hipGetLastError());
+    UNIT_CHECK(hipGetLastError());
     return passes;
-}
-
-int fail(pwa::SaCtxView& v, const Fail& f) {
-    *v.err = f.what;
-    return f.code;
 }
 
 // Patterns on the device (blob padded for sufarr::load8, offsets rebased to 0) and their SA ranges.
@@ -133,19 +99,19 @@ void search(pwa::SaCtxView& v, const pwa_sa_index* ix, const uint8_t* pb, const 
     const uint64_t base = poff[0], bytes = poff[n_pat] - base;
     std::vector<uint64_t> off(poff, poff + n_pat + 1);
     for (auto& o : off) o -= base;
-    SA_CHECK(r.blob.alloc(v.poison, (bytes + 7) / 8 * 8 + 16));
-    SA_CHECK(r.off.alloc(v.poison, off.size() * 8));
-    SA_CHECK(r.lo.alloc(v.poison, (size_t)n_pat * 4));
-    SA_CHECK(r.cnt.alloc(v.poison, (size_t)n_pat * 4 + 4));
-    SA_CHECK(hipMemsetAsync(r.blob.p, 0, (bytes + 7) / 8 * 8 + 16, v.stream));
-    SA_CHECK(hipMemcpyAsync(r.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
-    SA_CHECK(hipMemcpyAsync(r.off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, v.stream));
-    if (n_pat) sa_search_kernel<<<blocks_for(n_pat, kThreads), kThreads, 0, v.stream>>>(ix->d_text, ix->n, ix->d_sa, r.blob.as<uint8_t>(),
+    UNIT_CHECK(r.blob.alloc(v.poison, (bytes + 7) / 8 * 8 + 16));
+    UNIT_CHECK(r.off.alloc(v.poison, off.size() * 8));
+    UNIT_CHECK(r.lo.alloc(v.poison, (size_t)n_pat * 4));
+    UNIT_CHECK(r.cnt.alloc(v.poison, (size_t)n_pat * 4 + 4));
+    UNIT_CHECK(hipMemsetAsync(r.blob.p, 0, (bytes + 7) / 8 * 8 + 16, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(r.blob.p, pb + base, bytes, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(r.off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, v.stream));
+    if (n_pat) sa_search_kernel<<<blocks_for(n_pat, kThreads), kThreads, 0, v.stream>>>(ix->d_text.as<uint8_t>(), ix->n, ix->d_sa.as<uint32_t>(), r.blob.as<uint8_t>(),
                                                                                         r.off.as<uint64_t>(), n_pat, r.lo.as<uint32_t>(), r.cnt.as<uint32_t>());
-    SA_CHECK(hipGetLastError());
+    UNIT_CHECK(hipGetLastError());
     r.h_cnt.resize(n_pat);
-    SA_CHECK(hipMemcpyAsync(r.h_cnt.data(), r.cnt.p, (size_t)n_pat * 4, hipMemcpyDeviceToHost, v.stream));
-    SA_CHECK(hipStreamSynchronize(v.stream));
+    UNIT_CHECK(hipMemcpyAsync(r.h_cnt.data(), r.cnt.p, (size_t)n_pat * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
 }
 
 bool patterns_ok(const uint8_t* pb, const uint64_t* poff, uint32_t n_pat) {
@@ -175,16 +141,16 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
     if (!ix) return PWA_E_NOMEM;
     ix->ctx = ctx;
     ix->n = (uint32_t)n;
-    try {
+    const int rc = pwa::guarded(v, [&] {
         (void)hipSetDevice(v.device);
         const auto t0 = std::chrono::steady_clock::now();
         const size_t tbytes = (n + 7) / 8 * 8 + 16;
-        SA_CHECK(hipMalloc(&ix->d_text, tbytes));
-        SA_CHECK(pwa::poison_device(v.poison, ix->d_text, tbytes));
-        SA_CHECK(hipMalloc(&ix->d_sa, std::max<size_t>(n, 1) * 4));
-        SA_CHECK(pwa::poison_device(v.poison, ix->d_sa, std::max<size_t>(n, 1) * 4));
-        SA_CHECK(hipMemsetAsync(ix->d_text, 0, tbytes, v.stream));
-        if (n) SA_CHECK(hipMemcpyAsync(ix->d_text, text, n, hipMemcpyHostToDevice, v.stream));
+        UNIT_CHECK(ix->d_text.alloc(v.poison, tbytes));
+        UNIT_CHECK(ix->d_sa.alloc(v.poison, std::max<size_t>(n, 1) * 4));
+        uint8_t* d_text = ix->d_text.as<uint8_t>();
+        uint32_t* d_sa = ix->d_sa.as<uint32_t>();
+        UNIT_CHECK(hipMemsetAsync(d_text, 0, tbytes, v.stream));
+        if (n) UNIT_CHECK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, v.stream));
         // alphabet: codes 1 .. sigma in signed-char order, as few bits per code as sigma allows, as many codes per 64-bit key as fit
         std::vector<uint64_t> seen(256, 0);
         for (uint64_t i = 0; i < n; ++i) seen[text[i]] = 1;
@@ -195,31 +161,22 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
         int bits = 1;
         while ((1 << bits) <= sigma) ++bits;
         const int k = 64 / bits;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        SA_CHECK(hipEventCreate(&e0));
-        SA_CHECK(hipEventCreate(&e1));
-        struct Ev {
-            hipEvent_t& a;
-            hipEvent_t& b;
-            ~Ev() {
-                if (a) (void)hipEventDestroy(a);
-                if (b) (void)hipEventDestroy(b);
-            }
-        } ev{e0, e1};
-        SA_CHECK(hipEventRecord(e0, v.stream));
+        pwa::Events<2> ev;
+        UNIT_CHECK(ev.create());
+        UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
         int passes = 0;
         if (n) {
             Dev key2, val2, rank, head;
             SortScratch sc;
-            SA_CHECK(key2.alloc(v.poison, n * 8 * 2));
-            SA_CHECK(val2.alloc(v.poison, n * 4));
-            SA_CHECK(rank.alloc(v.poison, n * 4));
-            SA_CHECK(head.alloc(v.poison, (n + 1) * 4));
+            UNIT_CHECK(key2.alloc(v.poison, n * 8 * 2));
+            UNIT_CHECK(val2.alloc(v.poison, n * 4));
+            UNIT_CHECK(rank.alloc(v.poison, n * 4));
+            UNIT_CHECK(head.alloc(v.poison, (n + 1) * 4));
             sc.alloc(v.poison, n);
-            SortBufs<uint64_t, uint32_t> b{{key2.as<uint64_t>(), key2.as<uint64_t>() + n}, {ix->d_sa, val2.as<uint32_t>()}, 0};
+            SortBufs<uint64_t, uint32_t> b{{key2.as<uint64_t>(), key2.as<uint64_t>() + n}, {d_sa, val2.as<uint32_t>()}, 0};
             const uint32_t nb = blocks_for(n, kThreads), nn = (uint32_t)n;
-            sa_first_key_kernel<<<nb, kThreads, 0, v.stream>>>(ix->d_text, nn, tab, bits, k, b.k[0], b.v[0]);
-            SA_CHECK(hipGetLastError());
+            sa_first_key_kernel<<<nb, kThreads, 0, v.stream>>>(d_text, nn, tab, bits, k, b.k[0], b.v[0]);
+            UNIT_CHECK(hipGetLastError());
             passes += radix_sort(v.stream, b, n, sc);
             ix->rounds = 1;
             uint32_t h = (uint32_t)k;
@@ -227,63 +184,53 @@ int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** 
                 sa_heads_kernel<<<blocks_for(n + 1, kThreads), kThreads, 0, v.stream>>>(b.k[b.cur], nn, head.as<uint32_t>());
                 pwa::scan_excl(v.stream, head.as<uint32_t>(), n + 1, sc.part.as<uint32_t>());
                 uint32_t groups = 0;
-                SA_CHECK(hipMemcpyAsync(&groups, head.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, v.stream));
-                SA_CHECK(hipStreamSynchronize(v.stream));
+                UNIT_CHECK(hipMemcpyAsync(&groups, head.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, v.stream));
+                UNIT_CHECK(hipStreamSynchronize(v.stream));
                 if (groups == nn) break;
                 if (h >= nn || ix->rounds >= 40) throw Fail{PWA_E_HIP, "pwa_sa_create: prefix doubling did not separate the suffixes"};
                 sa_rank_kernel<<<nb, kThreads, 0, v.stream>>>(b.k[b.cur], b.v[b.cur], head.as<uint32_t>(), nn, rank.as<uint32_t>());
                 sa_pair_key_kernel<<<nb, kThreads, 0, v.stream>>>(rank.as<uint32_t>(), nn, h, b.k[b.cur], b.v[b.cur]);
-                SA_CHECK(hipGetLastError());
+                UNIT_CHECK(hipGetLastError());
                 passes += radix_sort(v.stream, b, n, sc);
                 ++ix->rounds;
                 h = h > (1u << 30) ? nn : 2 * h;
             }
-            if (b.v[b.cur] != ix->d_sa) SA_CHECK(hipMemcpyAsync(ix->d_sa, b.v[b.cur], n * 4, hipMemcpyDeviceToDevice, v.stream));
+            if (b.v[b.cur] != d_sa) UNIT_CHECK(hipMemcpyAsync(d_sa, b.v[b.cur], n * 4, hipMemcpyDeviceToDevice, v.stream));
         }
-        SA_CHECK(hipEventRecord(e1, v.stream));
-        SA_CHECK(hipStreamSynchronize(v.stream));
-        SA_CHECK(hipEventElapsedTime(&ix->build_ms, e0, e1));
+        UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
+        UNIT_CHECK(hipEventElapsedTime(&ix->build_ms, ev.e[0], ev.e[1]));
         if (v.debug)
             std::fprintf(stderr, "[pwa] sa build: n=%llu sigma=%d codes/key=%d rounds=%u passes=%d device %.3f ms, call %.3f ms\n",
                          (unsigned long long)n, sigma, k, ix->rounds, passes, ix->build_ms, ms_since(t0));
-    } catch (const Fail& f) {
-        pwa_sa_destroy(ix);
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        pwa_sa_destroy(ix);
-        return PWA_E_NOMEM;
-    }
-    *out = ix;
-    return PWA_OK;
+    });
+    if (rc == PWA_OK)
+        *out = ix;
+    else
+        delete ix;   // (half built)
+    return rc;
 }
 
 int pwa_sa_fetch(pwa_sa_index* ix, uint32_t* sa_out) {
     if (!ix || (!sa_out && ix->n)) return PWA_E_INVALID;
     pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
-    try {
-        if (ix->n) SA_CHECK(hipMemcpyAsync(sa_out, ix->d_sa, (size_t)ix->n * 4, hipMemcpyDeviceToHost, v.stream));
-        SA_CHECK(hipStreamSynchronize(v.stream));
-    } catch (const Fail& f) {
-        return fail(v, f);
-    }
-    return PWA_OK;
+    return pwa::guarded(v, [&] {
+        if (ix->n) UNIT_CHECK(hipMemcpyAsync(sa_out, ix->d_sa.p, (size_t)ix->n * 4, hipMemcpyDeviceToHost, v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
+    });
 }
 
 int pwa_sa_find(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat, uint32_t* counts_out) {
     if (!ix || (!counts_out && n_pat) || !patterns_ok(pat_bytes, pat_off, n_pat)) return PWA_E_INVALID;
     pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
     const auto t0 = std::chrono::steady_clock::now();
-    try {
+    const int rc = pwa::guarded(v, [&] {
         Ranges r;
         search(v, ix, pat_bytes, pat_off, n_pat, r);
         std::copy(r.h_cnt.begin(), r.h_cnt.end(), counts_out);
-    } catch (const Fail& f) {
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    ix->search_ms = (float)ms_since(t0);
-    return PWA_OK;
+    });
+    if (rc == PWA_OK) ix->search_ms = (float)ms_since(t0);
+    return rc;
 }
 
 int pwa_sa_occurrences(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_t* pat_off, uint32_t n_pat, const uint32_t* ref_start,
@@ -295,60 +242,54 @@ int pwa_sa_occurrences(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_
     pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t kept = 0;
-    try {
+    const int rc = pwa::guarded(v, [&] {
         Ranges r;
         search(v, ix, pat_bytes, pat_off, n_pat, r);
         const uint64_t budget = v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultChunkHits;
         // chunks of consecutive patterns: raw hits within the budget, or one pattern that alone exceeds it (at most n hits)
-        std::vector<std::pair<uint32_t, uint32_t>> chunks;
+        const std::vector<pwa::Run> chunks = pwa::cut_runs(n_pat, budget, [&](uint64_t p) { return (uint64_t)r.h_cnt[p]; });
         uint64_t max_hits = 0;
         uint32_t max_np = 0;
-        for (uint32_t p0 = 0; p0 < n_pat;) {
-            uint64_t hits = r.h_cnt[p0];
-            uint32_t p1 = p0 + 1;
-            while (p1 < n_pat && hits + r.h_cnt[p1] <= budget) hits += r.h_cnt[p1++];
-            chunks.emplace_back(p0, p1);
-            max_hits = std::max(max_hits, hits);
-            max_np = std::max(max_np, p1 - p0);
-            p0 = p1;
+        for (const pwa::Run& c : chunks) {
+            max_hits = std::max(max_hits, c.weight);
+            max_np = std::max(max_np, (uint32_t)(c.k1 - c.k0));
         }
         Dev d_ref, d_rank, key, pid, off;
         SortScratch sc;
         if (max_hits) {
-            SA_CHECK(d_ref.alloc(v.poison, ((size_t)n_ref + 1) * 4));
-            SA_CHECK(d_rank.alloc(v.poison, (size_t)n_ref * 4));
-            SA_CHECK(hipMemcpyAsync(d_ref.p, ref_start, ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, v.stream));
-            if (n_ref) SA_CHECK(hipMemcpyAsync(d_rank.p, header_rank, (size_t)n_ref * 4, hipMemcpyHostToDevice, v.stream));
-            SA_CHECK(key.alloc(v.poison, max_hits * 16));
-            SA_CHECK(pid.alloc(v.poison, max_hits * 8));
-            SA_CHECK(off.alloc(v.poison, ((size_t)max_np + 1) * 4));
+            UNIT_CHECK(d_ref.alloc(v.poison, ((size_t)n_ref + 1) * 4));
+            UNIT_CHECK(d_rank.alloc(v.poison, (size_t)n_ref * 4));
+            UNIT_CHECK(hipMemcpyAsync(d_ref.p, ref_start, ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, v.stream));
+            if (n_ref) UNIT_CHECK(hipMemcpyAsync(d_rank.p, header_rank, (size_t)n_ref * 4, hipMemcpyHostToDevice, v.stream));
+            UNIT_CHECK(key.alloc(v.poison, max_hits * 16));
+            UNIT_CHECK(pid.alloc(v.poison, max_hits * 8));
+            UNIT_CHECK(off.alloc(v.poison, ((size_t)max_np + 1) * 4));
             sc.alloc(v.poison, std::max<uint64_t>(max_hits, (uint64_t)max_np + 1));   // (the offsets scan of a chunk of many hit-less patterns)
         }
         std::vector<uint64_t> h_key;
         int n_chunks = 0;
-        for (const auto& c : chunks) {
-            const uint32_t p0 = c.first, np = c.second - c.first;
-            uint64_t total = 0;
-            for (uint32_t p = p0; p < c.second; ++p) total += r.h_cnt[p];
+        for (const pwa::Run& c : chunks) {
+            const uint32_t p0 = (uint32_t)c.k0, p1 = (uint32_t)c.k1, np = p1 - p0;
+            const uint64_t total = c.weight;
             if (total) {
                 ++n_chunks;
                 uint32_t* d_off = off.as<uint32_t>();
-                SA_CHECK(hipMemcpyAsync(d_off, r.cnt.as<uint32_t>() + p0, (size_t)np * 4, hipMemcpyDeviceToDevice, v.stream));
-                SA_CHECK(hipMemsetAsync(d_off + np, 0, 4, v.stream));
+                UNIT_CHECK(hipMemcpyAsync(d_off, r.cnt.as<uint32_t>() + p0, (size_t)np * 4, hipMemcpyDeviceToDevice, v.stream));
+                UNIT_CHECK(hipMemsetAsync(d_off + np, 0, 4, v.stream));
                 pwa::scan_excl(v.stream, d_off, (size_t)np + 1, sc.part.as<uint32_t>());
                 SortBufs<uint64_t, uint32_t> s1{{key.as<uint64_t>(), key.as<uint64_t>() + max_hits}, {pid.as<uint32_t>(), pid.as<uint32_t>() + max_hits}, 0};
-                occ_gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->d_sa, r.lo.as<uint32_t>() + p0, d_off, np, (uint32_t)total,
+                occ_gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->d_sa.as<uint32_t>(), r.lo.as<uint32_t>() + p0, d_off, np, (uint32_t)total,
                                                                                           d_ref.as<uint32_t>(), n_ref, d_rank.as<uint32_t>(), s1.k[0], s1.v[0]);
-                SA_CHECK(hipGetLastError());
+                UNIT_CHECK(hipGetLastError());
                 radix_sort(v.stream, s1, total, sc);   // by key ...
                 SortBufs<uint32_t, uint64_t> s2{{s1.v[0], s1.v[1]}, {s1.k[0], s1.k[1]}, s1.cur};
                 radix_sort(v.stream, s2, total, sc);   // ... then, stably, by pattern
                 h_key.resize(total);
-                SA_CHECK(hipMemcpyAsync(h_key.data(), s2.v[s2.cur], total * 8, hipMemcpyDeviceToHost, v.stream));
-                SA_CHECK(hipStreamSynchronize(v.stream));
+                UNIT_CHECK(hipMemcpyAsync(h_key.data(), s2.v[s2.cur], total * 8, hipMemcpyDeviceToHost, v.stream));
+                UNIT_CHECK(hipStreamSynchronize(v.stream));
             }
             uint64_t at = 0;
-            for (uint32_t p = p0; p < c.second; ++p) {
+            for (uint32_t p = p0; p < p1; ++p) {
                 occ_off[p] = kept;
                 for (const uint64_t e = at + r.h_cnt[p]; at < e; ++at)
                     if (h_key[at] != ~0ull) {   // (hits on a terminator)
@@ -361,11 +302,8 @@ int pwa_sa_occurrences(pwa_sa_index* ix, const uint8_t* pat_bytes, const uint64_
         if (v.debug)
             std::fprintf(stderr, "[pwa] sa occurrences: %u patterns, %zu chunks (%d with hits), %llu hits kept, %.3f ms\n", n_pat, chunks.size(),
                          n_chunks, (unsigned long long)kept, ms_since(t0));
-    } catch (const Fail& f) {
-        return fail(v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
+    });
+    if (rc != PWA_OK) return rc;
     ix->search_ms = (float)ms_since(t0);
     if (needed) *needed = kept;
     if (kept > cap) {
@@ -383,11 +321,6 @@ int pwa_sa_last_stats(const pwa_sa_index* ix, uint32_t* rounds, float* build_ms,
     return PWA_OK;
 }
 
-void pwa_sa_destroy(pwa_sa_index* ix) {
-    if (!ix) return;
-    if (ix->d_text) (void)hipFree(ix->d_text);
-    if (ix->d_sa) (void)hipFree(ix->d_sa);
-    delete ix;
-}
+void pwa_sa_destroy(pwa_sa_index* ix) { delete ix; }
 
 }  // extern "C"

@@ -1,13 +1,6 @@
 // wfa_ctx.h -- what the wavefront-alignment unit (wfa_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign_internal.h.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "poison.h"
-
-struct pwa_ctx;
+#include "side_unit.h"
 
 namespace pwa {
 // the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar): device ms of the sweeps and of the walks (events, summed over the ranges), the
@@ -16,13 +9,8 @@ struct WfaStats {
     float sweep_ms = 0.f, walk_ms = 0.f;
     uint64_t cells = 0, workspace_bytes = 0;
 };
-struct WfaCtxView {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool debug = false;              // PWA_DEBUG
+struct WfaCtxView : UnitCtx {
     uint64_t range_bytes = 0;        // PWA_RANGE_BYTES (0: the library's budget)
-    std::string* err = nullptr;      // the context's last-error text
-    Poison* poison = nullptr;        // the context's PWA_POISON state: every device allocation of the unit goes through poison_device
     WfaStats* stats = nullptr;
 };
 WfaCtxView wfa_ctx_view(pwa_ctx* c);

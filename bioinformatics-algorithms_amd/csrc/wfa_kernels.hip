@@ -12,46 +12,15 @@
 #include <string>
 #include <vector>
 
+#include "../host/format_ops.h"
 #include "wfa.hip.h"
 #include "wfa_ctx.h"
 
 using namespace pwa::wfa;
+using pwa::Dev;
+using pwa::Fail;
 
 namespace {
-
-struct Dev {   // one device allocation, freed with its owner
-    void* p = nullptr;
-    size_t cap = 0;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(pwa::Poison* po, size_t bytes) {   // po: the context's PWA_POISON state (the unit's view of the context)
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = std::max<size_t>(bytes, 16);
-        const hipError_t e = hipMalloc(&p, cap);
-        return e == hipSuccess ? pwa::poison_device(po, p, cap) : e;
-    }
-    hipError_t again(pwa::Poison* po) { return pwa::poison_device(po, p, cap); }   // the same buffer handed to the next range
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-struct Fail {   // an error on the way: the code and what to say about it
-    int code;
-    std::string what;
-};
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Fail{e == hipErrorOutOfMemory ? PWA_E_NOMEM : PWA_E_HIP, std::string(what) + ": " + hipGetErrorString(e)};
-}
-#define WF_CHECK(call) check((call), #call)
 
 struct Scoring {
     int match = 0, mismatch = 0, go = 0, ge = 0;
@@ -119,49 +88,6 @@ Plan plan_pair(const Scoring& sc, uint64_t n, uint64_t m, const int32_t* min_sco
 
 int32_t score_of(const Scoring& sc, const Plan& p, uint32_t pen) {
     return (int32_t)(((int64_t)sc.match * ((int64_t)p.n + p.m) - (int64_t)sc.g * pen) / 2);
-}
-
-// CIGAR and MD:Z of an op list in traceback order from (n, m) down to (0, 0), as pwa_format_alignment writes them, appended to the
-// two strings (any byte value may appear)
-void put_uint(std::string& s, uint64_t v) {
-    char buf[24];
-    int k = 0;
-    do {
-        buf[k++] = (char)('0' + v % 10);
-        v /= 10;
-    } while (v);
-    while (k) s.push_back(buf[--k]);
-}
-void format_ops(const uint8_t* pat, const uint8_t* txt, const uint8_t* ops, uint64_t n_ops, std::string& cg, std::string& md) {
-    uint64_t i = 0, j = 0, matches = 0;
-    for (uint64_t c = 0; c < n_ops;) {
-        const uint8_t op = ops[n_ops - 1 - c];
-        uint64_t run = 1;
-        while (c + run < n_ops && ops[n_ops - 1 - (c + run)] == op) ++run;
-        put_uint(cg, run);
-        cg.push_back((char)op);
-        if (op == 'M') {
-            for (uint64_t r = 0; r < run; ++r, ++i, ++j) {
-                if (pat[i] == txt[j]) {
-                    ++matches;
-                } else {
-                    put_uint(md, matches);
-                    md.push_back((char)txt[j]);
-                    matches = 0;
-                }
-            }
-        } else if (op == 'D') {
-            put_uint(md, matches);
-            md.push_back('^');
-            matches = 0;
-            md.append(reinterpret_cast<const char*>(pat + i), run);
-            i += run;
-        } else {
-            j += run;
-        }
-        c += run;
-    }
-    put_uint(md, matches);
 }
 
 struct Range {
@@ -235,21 +161,19 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
     uint64_t budget = v.range_bytes;
     if (!budget) {
         size_t free_b = 0, total_b = 0;
-        WF_CHECK(hipMemGetInfo(&free_b, &total_b));
+        UNIT_CHECK(hipMemGetInfo(&free_b, &total_b));
         budget = std::min<uint64_t>((uint64_t)(free_b * 0.6), 48ull << 30);
     }
-    // ranges of consecutive pairs; one pair alone may exceed the budget
+    // ranges of consecutive pairs, by workspace and op bytes together; one pair alone may exceed the budget
+    auto op_bytes = [&](const Plan& p) -> uint64_t { return want_ops ? p.n + p.m : 0; };
     std::vector<Range> ranges;
     uint64_t max_ws = 0, max_ops = 0, max_n = 0;
-    for (uint64_t k = 0; k < np;) {
-        Range r;
-        r.k0 = k;
-        do {
+    for (const pwa::Run& cut : pwa::cut_runs(np, budget, [&](uint64_t k) { return ws_bytes(c.plans[k]) + op_bytes(c.plans[k]); })) {
+        Range r{cut.k0, cut.k1};
+        for (uint64_t k = r.k0; k < r.k1; ++k) {
             r.ws_bytes += ws_bytes(c.plans[k]);
-            r.op_bytes += want_ops ? c.plans[k].n + c.plans[k].m : 0;
-            ++k;
-        } while (k < np && r.ws_bytes + r.op_bytes + ws_bytes(c.plans[k]) + (want_ops ? c.plans[k].n + c.plans[k].m : 0) <= budget);
-        r.k1 = k;
+            r.op_bytes += op_bytes(c.plans[k]);
+        }
         ranges.push_back(r);
         max_ws = std::max(max_ws, r.ws_bytes);
         max_ops = std::max(max_ops, r.op_bytes);
@@ -257,20 +181,20 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
     }
     const uint64_t blob_bytes = c.seq_off[c.n_seq];
     Dev d_blob, d_ws, d_pairs, d_pen, d_nops, d_ops, d_fault;
-    WF_CHECK(d_blob.alloc(v.poison, blob_bytes + kPad));
-    WF_CHECK(d_ws.alloc(v.poison, max_ws));
-    WF_CHECK(d_pairs.alloc(v.poison, max_n * sizeof(Pair)));
-    WF_CHECK(d_pen.alloc(v.poison, max_n * 4));
+    UNIT_CHECK(d_blob.alloc(v.poison, blob_bytes + kPad));
+    UNIT_CHECK(d_ws.alloc(v.poison, max_ws));
+    UNIT_CHECK(d_pairs.alloc(v.poison, max_n * sizeof(Pair)));
+    UNIT_CHECK(d_pen.alloc(v.poison, max_n * 4));
     if (want_ops) {
-        WF_CHECK(d_nops.alloc(v.poison, max_n * 4));
-        WF_CHECK(d_ops.alloc(v.poison, max_ops));
-        WF_CHECK(d_fault.alloc(v.poison, 4));
+        UNIT_CHECK(d_nops.alloc(v.poison, max_n * 4));
+        UNIT_CHECK(d_ops.alloc(v.poison, max_ops));
+        UNIT_CHECK(d_fault.alloc(v.poison, 4));
     }
-    if (blob_bytes) WF_CHECK(hipMemcpyAsync(d_blob.p, c.blob, blob_bytes, hipMemcpyHostToDevice, v.stream));
-    WF_CHECK(hipMemsetAsync(d_blob.as<uint8_t>() + blob_bytes, 0, kPad, v.stream));
-    if (want_ops) WF_CHECK(hipMemsetAsync(d_fault.p, 0, 4, v.stream));
-    Events ev;
-    for (hipEvent_t& e : ev.e) WF_CHECK(hipEventCreate(&e));
+    if (blob_bytes) UNIT_CHECK(hipMemcpyAsync(d_blob.p, c.blob, blob_bytes, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemsetAsync(d_blob.as<uint8_t>() + blob_bytes, 0, kPad, v.stream));
+    if (want_ops) UNIT_CHECK(hipMemsetAsync(d_fault.p, 0, 4, v.stream));
+    pwa::Events<3> ev;
+    UNIT_CHECK(ev.create());
     std::vector<Pair> pairs;
     std::vector<uint32_t> h_pen, h_nops;
     std::vector<uint64_t> order;
@@ -292,43 +216,43 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
                                  (uint32_t)(k - r.k0)});
         }
         if (!first) {   // the buffers of the range before, handed out again
-            WF_CHECK(hipStreamSynchronize(v.stream));
-            WF_CHECK(d_ws.again(v.poison));
-            WF_CHECK(d_pairs.again(v.poison));
-            WF_CHECK(d_pen.again(v.poison));
+            UNIT_CHECK(hipStreamSynchronize(v.stream));
+            UNIT_CHECK(d_ws.again(v.poison));
+            UNIT_CHECK(d_pairs.again(v.poison));
+            UNIT_CHECK(d_pen.again(v.poison));
             if (want_ops) {
-                WF_CHECK(d_nops.again(v.poison));
-                WF_CHECK(d_ops.again(v.poison));
+                UNIT_CHECK(d_nops.again(v.poison));
+                UNIT_CHECK(d_ops.again(v.poison));
             }
         }
         first = false;
         const uint32_t nl = (uint32_t)pairs.size(), blocks = (nl + kWaves - 1) / kWaves;
-        WF_CHECK(hipMemcpyAsync(d_pairs.p, pairs.data(), nl * sizeof(Pair), hipMemcpyHostToDevice, v.stream));
+        UNIT_CHECK(hipMemcpyAsync(d_pairs.p, pairs.data(), nl * sizeof(Pair), hipMemcpyHostToDevice, v.stream));
         const SweepParams sp{d_blob.as<uint8_t>(), d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>()};
-        WF_CHECK(hipEventRecord(ev.e[0], v.stream));
+        UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
         if (want_ops)
             hipLaunchKernelGGL(wfa_sweep_kernel<false>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
         else
             hipLaunchKernelGGL(wfa_sweep_kernel<true>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
-        WF_CHECK(hipGetLastError());
-        WF_CHECK(hipEventRecord(ev.e[1], v.stream));
+        UNIT_CHECK(hipGetLastError());
+        UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
         if (want_ops) {
             const WalkParams wp{d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>(), d_ops.as<uint8_t>(), d_nops.as<uint32_t>(), d_fault.as<uint32_t>()};
             hipLaunchKernelGGL(wfa_walk_kernel, dim3(blocks), dim3(64 * kWaves), 0, v.stream, wp);
-            WF_CHECK(hipGetLastError());
+            UNIT_CHECK(hipGetLastError());
         }
-        WF_CHECK(hipEventRecord(ev.e[2], v.stream));
+        UNIT_CHECK(hipEventRecord(ev.e[2], v.stream));
         h_pen.assign(cnt, kNotFound);
         h_nops.assign(cnt, 0);
-        WF_CHECK(hipMemcpyAsync(h_pen.data(), d_pen.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
+        UNIT_CHECK(hipMemcpyAsync(h_pen.data(), d_pen.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
         if (want_ops) {
-            WF_CHECK(hipMemcpyAsync(h_nops.data(), d_nops.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
-            if (r.op_bytes) WF_CHECK(hipMemcpyAsync(ops.data() + op_at[r.k0], d_ops.p, r.op_bytes, hipMemcpyDeviceToHost, v.stream));
+            UNIT_CHECK(hipMemcpyAsync(h_nops.data(), d_nops.p, cnt * 4, hipMemcpyDeviceToHost, v.stream));
+            if (r.op_bytes) UNIT_CHECK(hipMemcpyAsync(ops.data() + op_at[r.k0], d_ops.p, r.op_bytes, hipMemcpyDeviceToHost, v.stream));
         }
-        WF_CHECK(hipStreamSynchronize(v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
         float a = 0.f, b = 0.f;
-        WF_CHECK(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        WF_CHECK(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+        UNIT_CHECK(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+        UNIT_CHECK(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
         st.sweep_ms += a;
         st.walk_ms += b;
         for (uint64_t k : order) {   // (a pair left out of the launch keeps kNotFound and no ops; its slots were never written)
@@ -341,7 +265,7 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
     st.workspace_bytes = max_ws;
     if (want_ops) {
         uint32_t fault = 0;
-        WF_CHECK(hipMemcpy(&fault, d_fault.p, 4, hipMemcpyDeviceToHost));
+        UNIT_CHECK(hipMemcpy(&fault, d_fault.p, 4, hipMemcpyDeviceToHost));
         if (fault) throw Fail{PWA_E_HIP, "pwa_align_wfa: a walk left its wavefronts (internal error)"};
     }
     *v.stats = st;
@@ -349,11 +273,6 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
         std::fprintf(stderr, "[pwa] wfa %s: %llu pairs, %zu ranges, x=%u o=%u e=%u, %llu cells, workspace %llu B, sweep %.3f ms, walk %.3f ms\n",
                      want_ops ? "align" : "scores", (unsigned long long)np, ranges.size(), pen.x, pen.o, pen.e, (unsigned long long)st.cells,
                      (unsigned long long)st.workspace_bytes, st.sweep_ms, st.walk_ms);
-}
-
-int fail(pwa::WfaCtxView& v, const Fail& f) {
-    *v.err = f.what;
-    return f.code;
 }
 
 Call begin(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs) {
@@ -396,7 +315,7 @@ int pwa_scores_wfa(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_
     if (!ctx || !seq_off || (!seq_bytes && n_seq && seq_off[n_seq]) || ((!pair_a || !pair_b || !score_out) && n_pairs)) return PWA_E_INVALID;
     Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
     if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_scores_wfa")) return rc;
-    try {
+    return pwa::guarded(c.v, [&] {
         std::vector<uint32_t> penalty, n_ops;
         std::vector<uint8_t> ops;
         std::vector<uint64_t> op_at;
@@ -406,12 +325,7 @@ int pwa_scores_wfa(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_
             score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
             if (penalty_out) penalty_out[k] = penalty[k];
         }
-    } catch (const Fail& f) {
-        return fail(c.v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+    });
 }
 
 int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
@@ -421,7 +335,7 @@ int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int
         return PWA_E_INVALID;
     Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
     if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch")) return rc;
-    try {
+    return pwa::guarded(c.v, [&] {
         std::vector<uint32_t> penalty, cnt;
         std::vector<uint8_t> h_ops;
         std::vector<uint64_t> op_at;
@@ -432,12 +346,7 @@ int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int
             n_ops[k] = hit ? cnt[k] : 0;
             if (n_ops[k]) std::memcpy(ops + ops_off[k], h_ops.data() + op_at[k], n_ops[k]);
         }
-    } catch (const Fail& f) {
-        return fail(c.v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+    });
 }
 
 int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
@@ -449,7 +358,7 @@ int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_ope
         return PWA_E_INVALID;
     Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
     if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch_cigar")) return rc;
-    try {
+    return pwa::guarded(c.v, [&] {
         std::vector<uint32_t> penalty, cnt;
         std::vector<uint8_t> h_ops;
         std::vector<uint64_t> op_at;
@@ -457,20 +366,20 @@ int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_ope
         // the strings are formatted here, on the host, from the op lists (a pair not found has no strings at all, which
         // the device pass of cigar.hip.h cannot express)
         uint64_t at_c = 0, at_m = 0;
-        std::string cg, md;
+        std::vector<char> cg, md;
         for (uint64_t k = 0; k < n_pairs; ++k) {
             const bool hit = penalty[k] != kNotFound;
             score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
             cigar_off[k] = at_c;
             mdz_off[k] = at_m;
             if (!hit) continue;
-            cg.clear();
-            md.clear();
-            format_ops(seq_bytes + seq_off[pair_a[k]], seq_bytes + seq_off[pair_b[k]], h_ops.data() + op_at[k], cnt[k], cg, md);
-            if (at_c + cg.size() <= cigar_cap && cg.size()) std::memcpy(cigar + at_c, cg.data(), cg.size());
-            if (at_m + md.size() <= mdz_cap && md.size()) std::memcpy(mdz + at_m, md.data(), md.size());
-            at_c += cg.size();
-            at_m += md.size();
+            cg.resize(pwa_cigar_bound(cnt[k]));
+            md.resize(pwa_mdz_bound(cnt[k]));
+            const pwa::FormatLen len = pwa::format_ops(seq_bytes + seq_off[pair_a[k]], seq_bytes + seq_off[pair_b[k]], h_ops.data() + op_at[k], cnt[k], cg.data(), md.data());
+            if (at_c + len.cigar <= cigar_cap && len.cigar) std::memcpy(cigar + at_c, cg.data(), len.cigar);
+            if (at_m + len.mdz <= mdz_cap && len.mdz) std::memcpy(mdz + at_m, md.data(), len.mdz);
+            at_c += len.cigar;
+            at_m += len.mdz;
         }
         cigar_off[n_pairs] = at_c;
         mdz_off[n_pairs] = at_m;
@@ -478,16 +387,9 @@ int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_ope
             needed[0] = at_c;
             needed[1] = at_m;
         }
-        if (at_c > cigar_cap || at_m > mdz_cap) {
-            *c.v.err = "pwa_align_wfa_batch_cigar: the strings need " + std::to_string(at_c) + " + " + std::to_string(at_m) + " bytes";
-            return PWA_E_CAPACITY;
-        }
-    } catch (const Fail& f) {
-        return fail(c.v, f);
-    } catch (const std::bad_alloc&) {
-        return PWA_E_NOMEM;
-    }
-    return PWA_OK;
+        if (at_c > cigar_cap || at_m > mdz_cap)
+            throw Fail{PWA_E_CAPACITY, "pwa_align_wfa_batch_cigar: the strings need " + std::to_string(at_c) + " + " + std::to_string(at_m) + " bytes"};
+    });
 }
 
 int pwa_wfa_last_stats(const pwa_ctx* ctx, float* sweep_ms, float* walk_ms, uint64_t* cells, uint64_t* workspace_bytes) {

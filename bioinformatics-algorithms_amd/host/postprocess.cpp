@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/pwalign.h"
+#include "format_ops.h"
 
 namespace {
 
@@ -23,6 +24,57 @@ inline char* put_uint(char* out, uint64_t v) {   // std::to_string of a non-nega
 }
 
 }  // namespace
+
+pwa::FormatLen pwa::format_ops(const uint8_t* pattern, const uint8_t* text, const uint8_t* ops, uint64_t n_ops, char* cigar, char* mdz) {
+    pwa::FormatLen len{0, 0};
+    // ---- CIGAR: run-length encoding in forward order (hw2.cpp:59-78)
+    if (cigar) {
+        char* o = cigar;
+        uint64_t k = n_ops;
+        while (k > 0) {
+            const uint8_t cur = ops[k - 1];
+            uint64_t run = 0;
+            while (k > 0 && ops[k - 1] == cur) {
+                ++run;
+                --k;
+            }
+            o = put_uint(o, run);
+            *o++ = (char)cur;
+        }
+        len.cigar = (uint64_t)(o - cigar);
+    }
+    // ---- MD:Z (hw2.cpp:80-116)
+    if (mdz) {
+        char* o = mdz;
+        uint64_t matches = 0, c = 0, i = 0, j = 0;
+        while (c < n_ops) {
+            const uint8_t op = ops[n_ops - 1 - c];   // forward order
+            if (op == 'M') {
+                if (pattern[i] == text[j]) {
+                    ++matches;
+                } else {
+                    o = put_uint(o, matches);
+                    *o++ = (char)text[j];
+                    matches = 0;
+                }
+                ++i;
+                ++j;
+                ++c;
+            } else if (op == 'D') {
+                o = put_uint(o, matches);
+                *o++ = '^';
+                matches = 0;
+                for (; c < n_ops && ops[n_ops - 1 - c] == 'D'; ++c) *o++ = (char)pattern[i++];
+            } else {
+                ++j;   // 'I': skipped, the match counter keeps running
+                ++c;
+            }
+        }
+        o = put_uint(o, matches);
+        len.mdz = (uint64_t)(o - mdz);
+    }
+    return len;
+}
 
 extern "C" {
 
@@ -100,50 +152,10 @@ int pwa_format_alignment(const uint8_t* pattern, uint64_t n, const uint8_t* text
     aligned_pattern[n_ops] = 0;
     aligned_reference[n_ops] = 0;
 
-    // ---- CIGAR: run-length encoding in forward order (hw2.cpp:59-78)
-    if (cigar) {
-        char* o = cigar;
-        uint64_t k = n_ops;
-        while (k > 0) {
-            const uint8_t cur = ops[k - 1];
-            uint64_t run = 0;
-            while (k > 0 && ops[k - 1] == cur) {
-                ++run;
-                --k;
-            }
-            o = put_uint(o, run);
-            *o++ = (char)cur;
-        }
-        *o = 0;
-    }
-
-    // ---- MD:Z (hw2.cpp:80-116)
-    if (mdz) {
-        char* o = mdz;
-        uint64_t matches = 0, c = 0;
-        while (c < n_ops) {
-            const uint8_t op = ops[n_ops - 1 - c];   // forward order
-            if (op == 'M') {
-                if (aligned_pattern[c] == aligned_reference[c]) {
-                    ++matches;
-                } else {
-                    o = put_uint(o, matches);
-                    *o++ = aligned_reference[c];
-                    matches = 0;
-                }
-                ++c;
-            } else if (op == 'D') {
-                o = put_uint(o, matches);
-                *o++ = '^';
-                matches = 0;
-                while (c < n_ops && ops[n_ops - 1 - c] == 'D') *o++ = aligned_pattern[c++];
-            } else {
-                ++c;   // 'I': skipped, the match counter keeps running
-            }
-        }
-        o = put_uint(o, matches);
-        *o = 0;
-    }
+    // ---- CIGAR and MD:Z: (i, j) is the alignment's start cell now
+    const pwa::FormatLen len = pwa::format_ops(pattern + i, text + j, ops, n_ops, cigar, mdz);
+    if (cigar) cigar[len.cigar] = 0;
+    if (mdz) mdz[len.mdz] = 0;
 
     // ---- longest run of identical, non-gap columns (hw2.cpp:267-278)
     if (overlap) {

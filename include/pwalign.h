@@ -107,8 +107,9 @@ const char *pwa_strerror(int code);
 /* Test hook, no GPU involved: runs the host scheduler's sorting helpers (stable counting sort, its multi-threaded form, the length
  * sort, the radix sort) on pseudo-random lists against std::stable_sort, and the range planner of the alignment batches (classes,
  * ranges, wave tasks, band layout) on pseudo-random length lists with made-up free-memory figures against the properties every plan
- * must have; the parser of PWA_POISON's value on a list of good and bad spellings.  Returns 0, or the number of the first check
- * that failed. */
+ * must have; the parser of PWA_POISON's value on a list of good and bad spellings; the cutting of a list into runs under a budget
+ * (chunks of patterns, slices of tasks, ranges of WFA pairs) on its edge cases and on random lists.  Returns 0, or the number of the
+ * first check that failed. */
 int pwa_selftest_host(uint32_t seed);
 
 /* Context = one GPU (HIP device ordinal) + its streams and workspaces. */
