@@ -28,7 +28,7 @@ MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1, "sg": 2, "semiglobal": 2}   #
 
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_ctx_poison_stats", "pwa_scores",
-    "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int", "pwa_profile_plan",
+    "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int", "pwa_profile_plan", "pwa_strip_table",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
@@ -234,6 +234,7 @@ def lib():
     L.pwa_batch_profile_form.argtypes = [vp]
     L.pwa_batch_profile_int.argtypes = [vp]
     L.pwa_profile_plan.argtypes = [C.c_uint32, C.c_uint32, u32p, u32p]
+    L.pwa_strip_table.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), u32p, u32p]
     L.pwa_batch_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.pwa_batch_run_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.pwa_batch_destroy.argtypes = [vp]
@@ -317,6 +318,26 @@ def lib():
     L.pwa_wfa_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
     _lib = L
     return L
+
+
+STRIP_VARIANTS = ("single", "lanes", "lanes_single", "cell16", "cell16_single", "prof16", "prof16_int")   # PWA_STRIP_* bits 0..6
+
+
+def strip_table():
+    """pwa_strip_table (host only): the instantiated register-strip kernels as dicts -- name (the entry's part of info()["kernel"]), R, mode
+    and score (pwalign.h's numbers), variants (the STRIP_VARIANTS the entry carries beside its multi-strip kernel)."""
+    L = lib()
+    count = C.c_uint32(0)
+    L.pwa_strip_table(0xffffffff, None, None, None, None, None, C.byref(count))
+    out = []
+    for i in range(count.value):
+        name, rows, mode, score, var = C.c_char_p(), C.c_int(0), C.c_int(0), C.c_int(0), C.c_uint32(0)
+        rc = L.pwa_strip_table(i, C.byref(name), C.byref(rows), C.byref(mode), C.byref(score), C.byref(var), None)
+        if rc != 0:
+            raise PwaError("pwa_strip_table: %s" % L.pwa_strerror(rc).decode())
+        out.append(dict(name=name.value.decode(), R=rows.value, mode=mode.value, score=score.value,
+                        variants=tuple(v for k, v in enumerate(STRIP_VARIANTS) if var.value >> k & 1)))
+    return out
 
 
 def _b(x):

@@ -1491,6 +1491,23 @@ int pwa_profile_plan(uint32_t min_text_len, uint32_t max_text_len, uint32_t* int
     return PWA_OK;
 }
 
+int pwa_strip_table(uint32_t index, const char** name, int* rows, int* mode, int* score_path, uint32_t* variants, uint32_t* count) {
+    size_t n = 0;
+    const BatchKernelEntry* const t = batch_kernel_table(&n);
+    if (count) *count = (uint32_t)n;
+    if (index >= n) return PWA_E_INVALID;
+    const BatchKernelEntry& e = t[index];
+    if (name) *name = e.name;
+    if (rows) *rows = e.R;
+    if (mode) *mode = e.mode;
+    if (score_path) *score_path = e.score;
+    if (variants)
+        *variants = (e.fn_single ? PWA_STRIP_SINGLE : 0u) | (e.fn_lanes ? PWA_STRIP_LANES : 0u) | (e.fn_lanes_single ? PWA_STRIP_LANES_SINGLE : 0u) |
+                    (e.fn_cell16 ? PWA_STRIP_CELL16 : 0u) | (e.fn_cell16_single ? PWA_STRIP_CELL16_SINGLE : 0u) | (e.fn_prof16 ? PWA_STRIP_PROF16 : 0u) |
+                    (e.fn_prof16_int ? PWA_STRIP_PROF16_INT : 0u);
+    return PWA_OK;
+}
+
 int pwa_batch_cell_bits(const pwa_batch* b) {
     if (!b) return PWA_E_INVALID;
     return b->use_strips ? (b->cell16 ? 16 : 32) : 0;

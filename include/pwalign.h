@@ -188,6 +188,20 @@ int pwa_batch_profile_int(const pwa_batch *b);
  * with plain loads (whole words inside every text of the task, the shortest having min_text_len columns) -- the rest clamp the
  * word index and merge the pad code.  Scores do not depend on it. */
 int pwa_profile_plan(uint32_t min_text_len, uint32_t max_text_len, uint32_t *interior_blocks, uint32_t *blocks);
+/* Host only, no context: entry `index` of the table of instantiated register-strip kernels the scheduler picks from, and the number
+ * of entries in *count (written whatever the index; any output pointer may be NULL).  name: the entry's part of pwa_batch_info's
+ * kernel_name; rows: the strip height R; mode: its cell form (0 SW, 1 NW, 2 gap-shifted NW, 3 / 4 hw3 affine plain / shifted,
+ * 5 / 7 hw4 distance plain / packed key, 6 saturating SW, 8 / 9 / 10 gotoh NW plain / shifted / SW); score_path: 0 coded symbols
+ * with a byte table, 1 raw bytes compared; variants: which further kernels the entry carries beside its multi-strip one, as
+ * PWA_STRIP_* bits.  PWA_E_INVALID when index >= *count.  For tests that want to reach every instantiation by name. */
+#define PWA_STRIP_SINGLE 1u        /* every task a single strip: no hand-off rows */
+#define PWA_STRIP_LANES 2u         /* every lane its own text (index-paired lists) */
+#define PWA_STRIP_LANES_SINGLE 4u
+#define PWA_STRIP_CELL16 8u        /* two pairs per lane in packed f16 cells */
+#define PWA_STRIP_CELL16_SINGLE 16u
+#define PWA_STRIP_PROF16 32u       /* ... their profile form */
+#define PWA_STRIP_PROF16_INT 64u   /* ... with the integer-coded row */
+int pwa_strip_table(uint32_t index, const char **name, int *rows, int *mode, int *score_path, uint32_t *variants, uint32_t *count);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);
