@@ -43,7 +43,8 @@ EXPORTS = [
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
-    "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_wfa_last_stats",
+    "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
+    "pwa_align_wfa_codes_batch_cigar", "pwa_wfa_last_stats",
 ]
 
 
@@ -315,6 +316,8 @@ def lib():
     L.pwa_scores_wfa.argtypes = wfa_in + [i32p, i32p, u32p]   # ..., min_score, score, penalty
     L.pwa_align_wfa_batch.argtypes = wfa_in + [i32p, vp, u64p, u64p, i32p]   # ..., score, ops, ops_off, n_ops, min_score
     L.pwa_align_wfa_batch_cigar.argtypes = wfa_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, i32p]
+    L.pwa_align_wfa_codes_batch.argtypes = L.pwa_align_wfa_batch.argtypes
+    L.pwa_align_wfa_codes_batch_cigar.argtypes = L.pwa_align_wfa_batch_cigar.argtypes
     L.pwa_wfa_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
     _lib = L
     return L
@@ -801,9 +804,20 @@ class Context:
         scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
         return (scores, [None if scores[k] is None else pen[k] for k in range(n)]) if want_penalty else scores
 
-    def align_wfa_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
-        """pwa_align_wfa_batch -> [dict(score, ops, end, start)] as align_gotoh_batch returns them (end = (n, m), start = (0, 0));
-        score None and ops b"" for a pair not found."""
+    @staticmethod
+    def _wfa_form(form, name):
+        """the C call of a form of the WFA alignments: "offsets" keeps every wavefront (12 bytes per planned cell), "codes" a ring and
+        one code byte per planned cell; the results are the same"""
+        if form == "offsets":
+            return name
+        if form == "codes":
+            return name.replace("pwa_align_wfa_", "pwa_align_wfa_codes_")
+        raise ValueError('form: "offsets" or "codes", not %r' % (form,))
+
+    def align_wfa_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, form="offsets"):
+        """pwa_align_wfa_batch (form="offsets") or pwa_align_wfa_codes_batch (form="codes") -> [dict(score, ops, end, start)] as
+        align_gotoh_batch returns them (end = (n, m), start = (0, 0)); score None and ops b"" for a pair not found."""
+        name = self._wfa_form(form, "pwa_align_wfa_batch")
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -817,16 +831,17 @@ class Context:
             tot += ln(pair_a[k]) + ln(pair_b[k])
         ops = C.create_string_buffer(tot + 1)
         nops = (C.c_uint64 * max(n, 1))()
-        rc = self._L.pwa_align_wfa_batch(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops,
-                                         _min_scores(min_score, n))
-        self._check(rc, "pwa_align_wfa_batch")
+        rc = getattr(self._L, name)(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops,
+                                    _min_scores(min_score, n))
+        self._check(rc, name)
         raw = memoryview(ops)
         return [dict(score=None if sc[k] == WFA_NONE else sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]),
                      end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
 
-    def align_wfa_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
-        """pwa_align_wfa_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_gotoh_batch_cigar returns them; score None and two
-        empty strings for a pair not found."""
+    def align_wfa_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, form="offsets"):
+        """pwa_align_wfa_batch_cigar (form="offsets") or pwa_align_wfa_codes_batch_cigar (form="codes") -> [dict(score, cigar, mdz, end,
+        start)] as align_gotoh_batch_cigar returns them; score None and two empty strings for a pair not found."""
+        name = self._wfa_form(form, "pwa_align_wfa_batch_cigar")
         blob, off, seqs = pack_sequences(seqs)
         n = len(pair_a)
         pa = (C.c_uint32 * max(n, 1))(*pair_a)
@@ -837,9 +852,9 @@ class Context:
         cap_c, cap_m = sum(2 * v + 24 for v in nm), sum(3 * v + 24 for v in nm)   # pwa_cigar_bound / pwa_mdz_bound
         cg, md = C.create_string_buffer(cap_c + 1), C.create_string_buffer(cap_m + 1)
         co, mo = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
-        rc = self._L.pwa_align_wfa_batch_cigar(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
-                                               md, cap_m, mo, None, _min_scores(min_score, n))
-        self._check(rc, "pwa_align_wfa_batch_cigar")
+        rc = getattr(self._L, name)(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
+                                    md, cap_m, mo, None, _min_scores(min_score, n))
+        self._check(rc, name)
         cgb, mdb = cg.raw, md.raw
         return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
                      end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]

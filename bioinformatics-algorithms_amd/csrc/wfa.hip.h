@@ -8,10 +8,11 @@
 //
 // Layout of wavefront s with the planned span [lo, hi] (w = hi - lo + 1 cells): M[w], I[w], D[w] as int32 offsets, kNull for none,
 // at cell offset cum(s) of the workspace (alignment form: every wavefront up to P_max, 12 bytes per planned cell) or in slot
-// s mod R of a ring of R = max(x, o + e) + 1 wavefronts of the widest span (score form).  A score whose three source wavefronts are
-// all empty is skipped in O(1): its first M cell takes kEmpty, which no computed cell ever holds, and that is the whole per-score
-// bookkeeping -- a non-empty wavefront is computed over its planned span.  While R <= 64 the sweep keeps the emptiness of the last 64
-// scores in a register and reads no marker.
+// s mod R of a ring of R = max(x, o + e) + 1 wavefronts of the widest span (score form; the codes form too, which adds one code byte
+// per planned cell behind the ring and backtraces over those: wfa_codes_sweep_kernel, wfa_codes_walk_kernel).  A score whose three
+// source wavefronts are all empty is skipped in O(1): its first M cell takes kEmpty, which no computed cell ever holds, and that is
+// the whole per-score bookkeeping -- a non-empty wavefront is computed over its planned span.  While R <= 64 the sweep keeps the
+// emptiness of the last 64 scores in a register and reads no marker.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,8 +85,22 @@ struct SweepParams {
     uint32_t* penalty;      // [out]: P, or kNotFound
 };
 
-template <bool RING>
-__global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
+// The int32 of a pair's ring in the score and the codes form: min(R, P_max + 1) slots of the widest span's three planes.  In the codes
+// form the code plane (one byte per planned cell, wavefront s at byte cum(s)) lies right behind it in the pair's workspace.
+__host__ __device__ inline uint64_t ring_words(uint32_t p_max, uint32_t n, uint32_t m, const Pen& p) {
+    const uint64_t R = (uint64_t)(p.x > p.o + p.e ? p.x : p.o + p.e) + 1;
+    const Span sp = span_of(p_max, n, m, p);
+    return 3 * (R < (uint64_t)p_max + 1 ? R : (uint64_t)p_max + 1) * (uint64_t)(sp.hi - sp.lo + 1);
+}
+
+// Code byte of a cell (codes form): all the backtrace ever asks of it
+constexpr uint32_t kSrcX = 0, kSrcI = 1, kSrcD = 2, kSrcNone = 3;   // bits 0-1: where M came from (none: the cell is NULL, or s == 0)
+constexpr uint32_t kOpenI = 4, kOpenD = 8;                           // bit 2: I opened (ml >= il); bit 3: D opened (mr >= dr)
+
+// RING: the wavefronts live in the ring; CODES (with RING only): one code byte per valid cell goes to the pair's code plane as well
+template <bool RING, bool CODES>
+__device__ __forceinline__ void sweep(const SweepParams& a) {
+    static_assert(RING || !CODES, "the code plane goes with the ring");
     const uint32_t q = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
     if (q >= a.n_pairs) return;   // whole waves
     const int lane = threadIdx.x & 63;
@@ -100,6 +115,8 @@ __global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
     const Span widest = span_of(P.p_max, n, m, pen);
     const uint64_t stride = 3ull * (uint32_t)(widest.hi - widest.lo + 1);   // of a ring slot
     const int32_t kend = (int32_t)m - (int32_t)n;
+    uint8_t* codes = nullptr;
+    if constexpr (CODES) codes = reinterpret_cast<uint8_t*>(w + ring_words(P.p_max, n, m, pen));
 
     uint64_t hist = 0;     // bit b: wavefront s - 1 - b is not empty
     uint32_t slot = 0;     // s mod R
@@ -143,6 +160,8 @@ __global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
             be = wf(s, pen.e);
             wde = (uint32_t)(se.hi - se.lo + 1);
         }
+        uint8_t* cd = nullptr;   // a skipped wavefront (above) writes no codes: no walk is ever led to one
+        if constexpr (CODES) cd = codes + cum(s, n, m, pen);
         bool done = false;
         for (uint32_t c0 = 0; c0 < wd; c0 += 64) {
             const uint32_t c = c0 + lane;
@@ -161,6 +180,10 @@ __global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
             const int32_t vx = trim(mx + 1, k, (int32_t)n, (int32_t)m);
             int32_t j = vx > vi ? vx : vi;
             j = j > vd ? j : vd;
+            if constexpr (CODES) {   // the comparisons of wfa_walk_kernel, on the values it would read back
+                const uint32_t src = (s == 0 || j < 0) ? kSrcNone : vx == j ? kSrcX : vi == j ? kSrcI : kSrcD;
+                if (valid) cd[c] = (uint8_t)(src | (ml >= il ? kOpenI : 0u) | (mr >= dr ? kOpenD : 0u));
+            }
             if (s == 0) j = 0;
             if (valid && j >= 0) {   // extend: 8 bytes per step, ended by the clamp to the two lengths
                 const uint32_t i = (uint32_t)(j - k);
@@ -193,6 +216,16 @@ __global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
         }
     }
     if (lane == 0) a.penalty[P.out] = found;
+}
+
+template <bool RING>
+__global__ __launch_bounds__(256) void wfa_sweep_kernel(const SweepParams a) {
+    sweep<RING, false>(a);
+}
+
+// The ring sweep of the codes form: wfa_sweep_kernel<true> plus one byte store per valid cell
+__global__ __launch_bounds__(256) void wfa_codes_sweep_kernel(const SweepParams a) {
+    sweep<true, true>(a);
 }
 
 struct WalkParams {
@@ -293,6 +326,139 @@ __global__ __launch_bounds__(256) void wfa_walk_kernel(const WalkParams a) {
             if (ins) --j;
         }
     }
+    if (lane == 0) {
+        a.n_ops[P.out] = finished ? cnt : 0u;
+        if (!finished) *a.fault = 1u;
+    }
+}
+
+struct CodesWalkParams {
+    const uint8_t* blob;       // the sequences: pass B extends over them again
+    const Pair* pairs;
+    uint32_t n_pairs;
+    Pen pen;
+    const int32_t* ws;         // per pair: the ring (not read here), then the code plane
+    const uint32_t* penalty;   // [out] of the sweep
+    uint8_t* ops;
+    uint32_t* n_ops;           // [out]
+    uint32_t* fault;           // one word: set when a walk met a code it cannot follow
+};
+
+constexpr uint32_t kToM = 0x80;   // in an edit record: the walk is in state M after it, so a match run may stand there
+
+// The backtrace of the codes form, in two passes, every address wave-uniform (the values are held in scalar registers).
+// Pass A walks the codes from (P, m - n, state M) down to score 0 and leaves one record per edit ('M' for a mismatch, 'I', 'D', with
+// kToM) at the front of the pair's op region, in traceback order.  Pass B replays them from (0, 0), last record first: a greedy
+// extend over the lanes wherever the walk was in state M, then the edit, and writes the op list from its end downwards.  With t + 1
+// records unread and `wr` slots unwritten, wr - (t + 1) is the number of matches still to come, so a write never lands on an
+// unread record; record t is read before the op that may take its place.
+__global__ __launch_bounds__(256) void wfa_codes_walk_kernel(const CodesWalkParams a) {
+    const uint32_t q = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6));
+    if (q >= a.n_pairs) return;   // whole waves
+    const uint32_t lane = threadIdx.x & 63;
+    const Pair P = a.pairs[q];
+    const Pen pen = a.pen;
+    const uint32_t n = P.n, m = P.m, oe = pen.o + pen.e;
+    const uint8_t* const pat = a.blob + P.pat;
+    const uint8_t* const txt = a.blob + P.txt;
+    const uint8_t* const codes = reinterpret_cast<const uint8_t*>(a.ws + P.ws + ring_words(P.p_max, n, m, pen));
+    uint8_t* const ops = a.ops + P.ops;
+    const uint32_t cap = n + m;
+    const uint32_t pnl = __builtin_amdgcn_readfirstlane(a.penalty[P.out]);
+    if (pnl == kNotFound) {
+        if (lane == 0) a.n_ops[P.out] = 0;
+        return;
+    }
+    // ---- pass A
+    uint32_t E = 0, ui = 0, uj = 0;   // records; pattern and text symbols their edits consume
+    bool fault = false, ended = false;
+    int64_t s = pnl;
+    int32_t k = (int32_t)m - (int32_t)n;
+    uint32_t st = 0;   // 0: M, 1: I, 2: D
+    for (uint64_t it = 0; it <= 2ull * cap + 2; ++it) {
+        if (st == 0 && s == 0) {
+            ended = k == 0;
+            break;
+        }
+        if (s < 0 || E >= cap) break;   // (every record moves i or j: more than n + m of them cannot be)
+        const Span sp = span_of((uint32_t)s, n, m, pen);
+        if (k < sp.lo || k > sp.hi) break;
+        const uint32_t code = __builtin_amdgcn_readfirstlane(codes[cum((uint32_t)s, n, m, pen) + (uint32_t)(k - sp.lo)]);
+        if (st == 0) {
+            const uint32_t src = code & 3u;
+            if (src == kSrcNone) break;
+            if (src == kSrcX) {
+                if (lane == 0) ops[E] = (uint8_t)('M' | kToM);
+                ++E;
+                ++ui;
+                ++uj;
+                s -= pen.x;
+            } else {
+                st = src;   // kSrcI, kSrcD: the same cell in state I, D
+            }
+        } else {
+            const bool ins = st == 1;
+            const bool opened = (code & (ins ? kOpenI : kOpenD)) != 0;
+            if (lane == 0) ops[E] = (uint8_t)((ins ? 'I' : 'D') | (opened ? kToM : 0u));
+            ++E;
+            if (ins) {
+                ++uj;
+                --k;
+            } else {
+                ++ui;
+                ++k;
+            }
+            s -= opened ? oe : pen.e;
+            if (opened) st = 0;
+        }
+    }
+    fault = !ended || ui > n || uj > m || n - ui != m - uj;
+    const uint32_t cnt = fault ? 0u : E + (n - ui);   // <= n + m: E - ui is the number of 'I', at most uj <= m
+    fault = fault || cnt > cap;
+    // ---- pass B
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // lane 0's records before every lane's loads of them
+    uint32_t i = 0, j = 0, wr = cnt;   // ops[0 .. wr) not written yet
+    // the match run from (i, j), at most `room` long, into the slots below wr
+    auto extend = [&](uint32_t room) {
+        const uint32_t rem = n - i < m - j ? n - i : m - j;
+        uint32_t run = rem;
+        for (uint32_t base = 0; base < rem; base += 512) {
+            const uint32_t off = base + 8 * lane;
+            uint32_t pos = off;   // a lane beyond the clamp ends the run where it stands
+            bool stop = true;
+            if (off < rem) {
+                const uint64_t d = load8(pat + i + off) ^ load8(txt + j + off);
+                stop = d != 0;
+                if (stop) pos += (uint32_t)__builtin_ctzll(d) >> 3;
+            }
+            const uint64_t b = __ballot(stop);
+            if (b) {
+                run = (uint32_t)__builtin_amdgcn_readlane((int)pos, (int)__builtin_ctzll(b));
+                break;
+            }
+        }
+        run = run < rem ? run : rem;
+        if (run > room) {
+            fault = true;
+            return;
+        }
+        for (uint32_t c = lane; c < run; c += 64) ops[wr - run + c] = 'M';
+        wr -= run;
+        i += run;
+        j += run;
+    };
+    for (uint32_t t = E; !fault && t-- > 0;) {
+        const uint32_t rec = __builtin_amdgcn_readfirstlane(ops[t]);
+        if (rec & kToM) extend(wr - (t + 1));
+        if (fault) break;
+        const uint32_t op = rec & 0x7fu;
+        i += op != 'I';
+        j += op != 'D';
+        if (lane == 0) ops[wr - 1] = (uint8_t)op;   // wr - 1 >= t
+        --wr;
+    }
+    if (!fault) extend(wr);
+    const bool finished = !fault && wr == 0 && i == n && j == m;
     if (lane == 0) {
         a.n_ops[P.out] = finished ? cnt : 0u;
         if (!finished) *a.fault = 1u;

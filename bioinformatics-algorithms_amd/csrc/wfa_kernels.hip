@@ -1,5 +1,5 @@
 // wfa_kernels.hip -- the wavefront-alignment entries of include/pwalign.h (pwa_wfa_plan, pwa_scores_wfa, pwa_align_wfa_batch(_cigar),
-// pwa_wfa_last_stats): validation, the conversion to penalties, the per-pair plan and bound, ranges of consecutive pairs under the
+// pwa_align_wfa_codes_batch(_cigar), pwa_wfa_last_stats): validation, the conversion to penalties, the per-pair plan and bound, ranges of consecutive pairs under the
 // PWA_RANGE_BYTES budget, the sweep and the walk of each range, the CIGAR / MD:Z strings.  Kernels: wfa.hip.h.
 #include "../../include/pwalign.h"
 
@@ -130,15 +130,20 @@ int validate(Call& c, int match, int mismatch, int go, int ge, const int32_t* mi
     return PWA_OK;
 }
 
-// The sweep (and, with want_ops, the walk) of every pair: penalty[k] = P or kNotFound; op lists packed pair after pair into `ops`
-// (pair k at op_at[k], n + m bytes of room, n_ops[k] of them written)
-void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uint8_t>& ops, std::vector<uint64_t>& op_at, std::vector<uint32_t>& n_ops) {
+// What a call keeps of the wavefronts: a ring and nothing else (scores), every wavefront (alignments from the stored offsets), or a
+// ring and one code byte per planned cell (alignments from the codes)
+enum class Form { Scores, Offsets, Codes };
+
+// The sweep (and, for the alignment forms, the walk) of every pair: penalty[k] = P or kNotFound; op lists packed pair after pair into
+// `ops` (pair k at op_at[k], n + m bytes of room, n_ops[k] of them written)
+void run(Call& c, Form form, std::vector<uint32_t>& penalty, std::vector<uint8_t>& ops, std::vector<uint64_t>& op_at, std::vector<uint32_t>& n_ops) {
     const pwa::WfaCtxView& v = c.v;
     const uint64_t np = c.n_pairs;
     penalty.assign(np, kNotFound);
     n_ops.assign(np, 0);
     op_at.assign(np + 1, 0);
     pwa::WfaStats st;
+    const bool want_ops = form != Form::Scores;
     if (want_ops) {
         for (uint64_t k = 0; k < np; ++k) op_at[k + 1] = op_at[k] + c.plans[k].n + c.plans[k].m;
         ops.resize(op_at[np]);
@@ -147,9 +152,10 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
     const uint64_t R = (uint64_t)std::max(pen.x, pen.o + pen.e) + 1;
     auto ws_bytes = [&](const Plan& p) -> uint64_t {
         if (p.none) return 0;
-        if (want_ops) return 12 * p.cells;
+        if (form == Form::Offsets) return 12 * p.cells;
         const Span sp = span_of(p.p_max, p.n, p.m, pen);
-        return 12 * std::min<uint64_t>(R, (uint64_t)p.p_max + 1) * (uint64_t)(sp.hi - sp.lo + 1);
+        const uint64_t ring = 12 * std::min<uint64_t>(R, (uint64_t)p.p_max + 1) * (uint64_t)(sp.hi - sp.lo + 1);
+        return form == Form::Codes ? ring + ((p.cells + 3) & ~3ull) : ring;   // the code plane behind the ring, up to the next int32
     };
     bool any = false;
     for (const Plan& p : c.plans) any = any || !p.none;
@@ -230,13 +236,20 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
         UNIT_CHECK(hipMemcpyAsync(d_pairs.p, pairs.data(), nl * sizeof(Pair), hipMemcpyHostToDevice, v.stream));
         const SweepParams sp{d_blob.as<uint8_t>(), d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>()};
         UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
-        if (want_ops)
+        if (form == Form::Offsets)
             hipLaunchKernelGGL(wfa_sweep_kernel<false>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
+        else if (form == Form::Codes)
+            hipLaunchKernelGGL(wfa_codes_sweep_kernel, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
         else
             hipLaunchKernelGGL(wfa_sweep_kernel<true>, dim3(blocks), dim3(64 * kWaves), 0, v.stream, sp);
         UNIT_CHECK(hipGetLastError());
         UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
-        if (want_ops) {
+        if (form == Form::Codes) {
+            const CodesWalkParams wp{d_blob.as<uint8_t>(), d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>(), d_ops.as<uint8_t>(),
+                                     d_nops.as<uint32_t>(), d_fault.as<uint32_t>()};
+            hipLaunchKernelGGL(wfa_codes_walk_kernel, dim3(blocks), dim3(64 * kWaves), 0, v.stream, wp);
+            UNIT_CHECK(hipGetLastError());
+        } else if (want_ops) {
             const WalkParams wp{d_pairs.as<Pair>(), nl, pen, d_ws.as<int32_t>(), d_pen.as<uint32_t>(), d_ops.as<uint8_t>(), d_nops.as<uint32_t>(), d_fault.as<uint32_t>()};
             hipLaunchKernelGGL(wfa_walk_kernel, dim3(blocks), dim3(64 * kWaves), 0, v.stream, wp);
             UNIT_CHECK(hipGetLastError());
@@ -271,7 +284,7 @@ void run(Call& c, bool want_ops, std::vector<uint32_t>& penalty, std::vector<uin
     *v.stats = st;
     if (v.debug)
         std::fprintf(stderr, "[pwa] wfa %s: %llu pairs, %zu ranges, x=%u o=%u e=%u, %llu cells, workspace %llu B, sweep %.3f ms, walk %.3f ms\n",
-                     want_ops ? "align" : "scores", (unsigned long long)np, ranges.size(), pen.x, pen.o, pen.e, (unsigned long long)st.cells,
+                     form == Form::Codes ? "align (codes)" : want_ops ? "align" : "scores", (unsigned long long)np, ranges.size(), pen.x, pen.o, pen.e, (unsigned long long)st.cells,
                      (unsigned long long)st.workspace_bytes, st.sweep_ms, st.walk_ms);
 }
 
@@ -319,7 +332,7 @@ int pwa_scores_wfa(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_
         std::vector<uint32_t> penalty, n_ops;
         std::vector<uint8_t> ops;
         std::vector<uint64_t> op_at;
-        run(c, false, penalty, ops, op_at, n_ops);
+        run(c, Form::Scores, penalty, ops, op_at, n_ops);
         for (uint64_t k = 0; k < n_pairs; ++k) {
             const bool hit = penalty[k] != kNotFound;
             score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
@@ -328,18 +341,23 @@ int pwa_scores_wfa(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_
     });
 }
 
-int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
-                        const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off,
-                        uint64_t* n_ops, const int32_t* min_score) {
+}  // extern "C"
+
+namespace {
+
+// pwa_align_wfa_batch and pwa_align_wfa_codes_batch: one body, two forms of the workspace
+int align_ops(Form form, const char* who, pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
+              uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off,
+              uint64_t* n_ops, const int32_t* min_score) {
     if (!ctx || !seq_off || (!seq_bytes && n_seq && seq_off[n_seq]) || ((!pair_a || !pair_b || !score_out || !ops || !ops_off || !n_ops) && n_pairs))
         return PWA_E_INVALID;
     Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
-    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch")) return rc;
+    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, who)) return rc;
     return pwa::guarded(c.v, [&] {
         std::vector<uint32_t> penalty, cnt;
         std::vector<uint8_t> h_ops;
         std::vector<uint64_t> op_at;
-        run(c, true, penalty, h_ops, op_at, cnt);
+        run(c, form, penalty, h_ops, op_at, cnt);
         for (uint64_t k = 0; k < n_pairs; ++k) {
             const bool hit = penalty[k] != kNotFound;
             score_out[k] = hit ? score_of(c.sc, c.plans[k], penalty[k]) : PWA_WFA_NONE;
@@ -349,20 +367,20 @@ int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int
     });
 }
 
-int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
-                              uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
-                              uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t needed[2],
-                              const int32_t* min_score) {
+// pwa_align_wfa_batch_cigar and pwa_align_wfa_codes_batch_cigar
+int align_strings(Form form, const char* who, pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes,
+                  const uint64_t* seq_off, uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
+                  uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t needed[2], const int32_t* min_score) {
     if (!ctx || !seq_off || !cigar_off || !mdz_off || (!seq_bytes && n_seq && seq_off[n_seq]) || (!cigar && cigar_cap) || (!mdz && mdz_cap) ||
         ((!pair_a || !pair_b || !score_out) && n_pairs))
         return PWA_E_INVALID;
     Call c = begin(ctx, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs);
-    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, "pwa_align_wfa_batch_cigar")) return rc;
+    if (const int rc = validate(c, match, mismatch, gap_open, gap_extend, min_score, who)) return rc;
     return pwa::guarded(c.v, [&] {
         std::vector<uint32_t> penalty, cnt;
         std::vector<uint8_t> h_ops;
         std::vector<uint64_t> op_at;
-        run(c, true, penalty, h_ops, op_at, cnt);
+        run(c, form, penalty, h_ops, op_at, cnt);
         // the strings are formatted here, on the host, from the op lists (a pair not found has no strings at all, which
         // the device pass of cigar.hip.h cannot express)
         uint64_t at_c = 0, at_m = 0;
@@ -388,8 +406,42 @@ int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_ope
             needed[1] = at_m;
         }
         if (at_c > cigar_cap || at_m > mdz_cap)
-            throw Fail{PWA_E_CAPACITY, "pwa_align_wfa_batch_cigar: the strings need " + std::to_string(at_c) + " + " + std::to_string(at_m) + " bytes"};
+            throw Fail{PWA_E_CAPACITY, std::string(who) + ": the strings need " + std::to_string(at_c) + " + " + std::to_string(at_m) + " bytes"};
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int pwa_align_wfa_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                        const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off,
+                        uint64_t* n_ops, const int32_t* min_score) {
+    return align_ops(Form::Offsets, "pwa_align_wfa_batch", ctx, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs, score_out,
+                     ops, ops_off, n_ops, min_score);
+}
+
+int pwa_align_wfa_codes_batch(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
+                              const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, uint8_t* ops, const uint64_t* ops_off,
+                              uint64_t* n_ops, const int32_t* min_score) {
+    return align_ops(Form::Codes, "pwa_align_wfa_codes_batch", ctx, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                     score_out, ops, ops_off, n_ops, min_score);
+}
+
+int pwa_align_wfa_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
+                              uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
+                              uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t needed[2],
+                              const int32_t* min_score) {
+    return align_strings(Form::Offsets, "pwa_align_wfa_batch_cigar", ctx, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b, n_pairs,
+                         score_out, cigar, cigar_cap, cigar_off, mdz, mdz_cap, mdz_off, needed, min_score);
+}
+
+int pwa_align_wfa_codes_batch_cigar(pwa_ctx* ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t* seq_bytes, const uint64_t* seq_off,
+                                    uint32_t n_seq, const uint32_t* pair_a, const uint32_t* pair_b, uint64_t n_pairs, int32_t* score_out, char* cigar,
+                                    uint64_t cigar_cap, uint64_t* cigar_off, char* mdz, uint64_t mdz_cap, uint64_t* mdz_off, uint64_t needed[2],
+                                    const int32_t* min_score) {
+    return align_strings(Form::Codes, "pwa_align_wfa_codes_batch_cigar", ctx, match, mismatch, gap_open, gap_extend, seq_bytes, seq_off, n_seq, pair_a, pair_b,
+                         n_pairs, score_out, cigar, cigar_cap, cigar_off, mdz, mdz_cap, mdz_off, needed, min_score);
 }
 
 int pwa_wfa_last_stats(const pwa_ctx* ctx, float* sweep_ms, float* walk_ms, uint64_t* cells, uint64_t* workspace_bytes) {

@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs; wavefront + op bytes per range of
- *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
+ *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar) / pwa_align_wfa_codes_batch(_cigar)
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
  *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
@@ -860,12 +860,31 @@ int pwa_approx_minima(uint64_t n, const uint32_t *pat_len, const uint32_t *max_d
  *   pwa_align_wfa_batch_cigar  the same alignments as CIGAR and MD:Z strings with pwa_align_gotoh_batch_cigar's string buffers and
  *                            PWA_E_CAPACITY / needed protocol; the strings equal pwa_format_alignment of the op list byte for byte
  *                            (formatted on the host from the op lists).  No end or start cells: always (n, m) and (0, 0).
- *   pwa_wfa_last_stats       of the last of the three calls on ctx: device ms of the sweeps and the walks (events), cells = the sum over
+ *   pwa_align_wfa_codes_batch, pwa_align_wfa_codes_batch_cigar   the same two calls in the low-memory form below: parameters, validation,
+ *                            bound, results, op lists, strings and the capacity protocol are pwa_align_wfa_batch(_cigar)'s, and the op
+ *                            list equals pwa_align_wfa_batch's byte for byte; only the device workspace differs.
+ *   pwa_wfa_last_stats       of the last of these calls on ctx: device ms of the sweeps and the walks (events), cells = the sum over
  *                            the pairs of width(s) for s = 0 .. P (P_max for a pair the sweep did not find, nothing for one decided on
  *                            the host), and the bytes of the largest range's wavefront workspace.  A call that fails validation
  *                            leaves them unchanged.
  * Validation runs before any device work, in pair order: a null context, a null required pointer, an index >= n_seq PWA_E_INVALID;
- * the scoring first.  An empty pair list is PWA_OK. */
+ * the scoring first.  An empty pair list is PWA_OK.
+ * The codes form.  The backtrace above asks three things of a cell, and the sweep knows all three when it computes the cell, so the
+ * codes calls keep one byte per planned cell instead of three offsets and run the sweep on the score call's ring:
+ *   bits 0-1  where M[s][k] came from: 0 mismatch, 1 I, 2 D (the first of M[s-x][k] + 1, I[s][k], D[s][k], in this order, that equals
+ *             their max), 3 none (the cell is NULL, or s = 0)
+ *   bit 2     I[s][k] opened: M[s-o-e][k-1] >= I[s-e][k-1]          bit 3     D[s][k] opened: M[s-o-e][k+1] >= D[s-e][k+1]
+ * The length of a match run is not stored: extend() depends on the offset before it alone, so the run is found again from the
+ * sequences.  The walk has two passes.  Pass A follows the state machine of the backtrace over the codes alone, from (P, m - n, M) to
+ * s = 0 (where k must be 0), and notes one record per edit -- 'M' for a mismatch, 'I', 'D' -- in traceback order, each with a flag:
+ * the walk is in state M after it (a mismatch, or a gap's open).  That gives the op count: the records plus n minus the pattern
+ * symbols they consume.  Pass B replays the records from (0, 0), last record first: where the flag is set it extends greedily and
+ * writes the run, then it writes the edit; after the last record it extends once more and must stand on (n, m) with every op slot
+ * written.  It fills the op list from its end downwards, so the list is in traceback order; the records lie at the front of the
+ * pair's own op region and are each read before an op can take their place.
+ * Workspace of a device pair: a ring of min(max(x, o + e) + 1, P_max + 1) wavefronts of 3 width(P_max) int32 (what pwa_scores_wfa
+ * keeps), then cells(k) code bytes, wavefront s at byte offset width(0) + .. + width(s - 1), padded to the next multiple of 4:
+ * ring + cells <= bytes <= ring + cells + 3, against 12 cells.  A range's weight is ring + codes + op bytes. */
 #define PWA_WFA_NONE INT32_MIN
 int pwa_wfa_plan(int match, int mismatch, int gap_open, int gap_extend, const uint64_t *n, const uint64_t *m,
                  const int32_t *min_score /* or NULL */, uint64_t n_pairs, int32_t pen[4] /* x, o, e, g */,
@@ -883,6 +902,16 @@ int pwa_align_wfa_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_ope
                               char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
                               char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
                               uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
+int pwa_align_wfa_codes_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                              const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                              uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off, uint64_t *n_ops,
+                              const int32_t *min_score /* or NULL */);
+int pwa_align_wfa_codes_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend,
+                                    const uint8_t *seq_bytes, const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a,
+                                    const uint32_t *pair_b, uint64_t n_pairs, int32_t *score_out,
+                                    char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                    char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                    uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
 int pwa_wfa_last_stats(const pwa_ctx *ctx, float *sweep_ms, float *walk_ms, uint64_t *cells, uint64_t *workspace_bytes);
 
 /*

@@ -15,10 +15,15 @@ medians over --reps repetitions after one warm-up call; the cells the call compu
 in-band cells); the WFA workspace; and whether the banded score equals the exact one for every pair.  Nothing is asserted about which
 is faster: the lines say what was measured.
 
+--legs codes runs the WFA calls alone -- pwa_scores_wfa, pwa_align_wfa_batch and pwa_align_wfa_codes_batch (the ring sweep with one code
+byte per planned cell) with the same bound, in one process, so that the three stand next to each other -- and appends
+to profiles/wfa_codes_batch.jsonl; the codes line also says whether every op list equals the offsets form's.  --legs all (the default)
+runs every call, the codes form included.
+
 One GPU process at a time: the parent never touches the GPU; it runs every shape in a child of its own under a time limit, one after
 the other, stops at the first that fails, and appends the children's JSON lines to --out (profiles/wfa_batch.jsonl).
 
-    python tools/wfa_batch.py [--reps 3] [--shapes d1,d3,k30] [--limit 420] [--out FILE]
+    python tools/wfa_batch.py [--reps 3] [--shapes d1,d3,k30] [--legs all|codes] [--limit 420] [--out FILE]
 """
 import argparse
 import json
@@ -35,6 +40,7 @@ sys.path.insert(0, ROOT)
 
 SC = (1, -4, -6, -1)
 OUT = os.path.join(ROOT, "profiles", "wfa_batch.jsonl")
+OUT_CODES = os.path.join(ROOT, "profiles", "wfa_codes_batch.jsonl")
 SHAPES = dict(d1=(10000, 4096, 0.01), d3=(10000, 4096, 0.03), k30=(30000, 1024, 0.01))
 HALF_WIDTH = 128
 
@@ -78,7 +84,7 @@ def timed(reps, call, stats):
     return res, wall, rows
 
 
-def run_shape(shape, reps):
+def run_shape(shape, reps, legs):
     import __graft_entry__ as G
     pkg = G.load_pkg()
     ctx = pkg.Context(0)
@@ -106,7 +112,20 @@ def run_shape(shape, reps):
                     device_ms=statistics.median(r["sweep_ms"] + r["walk_ms"] for r in rows), cells=rows[-1]["cells"],
                     workspace_bytes=rows[-1]["workspace_bytes"], found=sum(found),
                     scores_equal_the_score_call=[a["score"] for a in al if a["score"] is not None] == [s for s, f in zip(scores, found) if f]))
+    ops = [a["ops"] for a in al]
     del al
+    al, wall, rows = timed(reps, lambda: ctx.align_wfa_batch(seqs, pa, pb, *SC, min_score=bound, form="codes"), ctx.align_wfa_stats)
+    out.append(dict(head, call="align_wfa_codes_batch", min_score=bound, p_max=plan["p_max"][0], planned_cells_per_pair=plan["cells"][0], call_ms=stat(wall),
+                    sweep_ms=stat([r["sweep_ms"] for r in rows]), walk_ms=stat([r["walk_ms"] for r in rows]),
+                    device_ms=statistics.median(r["sweep_ms"] + r["walk_ms"] for r in rows), cells=rows[-1]["cells"],
+                    workspace_bytes=rows[-1]["workspace_bytes"], found=sum(a["score"] is not None for a in al),
+                    ops_equal_the_offsets_form=[a["ops"] for a in al] == ops))
+    del al, ops
+    if legs == "codes":
+        ctx.close()
+        for r in out:
+            print(json.dumps(r), flush=True)
+        return 0
     band = pkg.band_around(n, n, HALF_WIDTH)
     cells = count * band_cells(n, n, *band)
     bal, wall, rows = timed(reps, lambda: ctx.align_banded_batch("nw", seqs, pa, pb, *SC, [band] * count), ctx.align_banded_stats)
@@ -130,14 +149,16 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--shapes", default="d1,d3,k30")
     ap.add_argument("--limit", type=int, default=420, help="seconds per shape")
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--legs", default="all", choices=["all", "codes"])
+    ap.add_argument("--out", default=None, help="default: profiles/wfa_batch.jsonl, or profiles/wfa_codes_batch.jsonl with --legs codes")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return run_shape(a.child, a.reps)
+        return run_shape(a.child, a.reps, a.legs)
+    a.out = a.out or (OUT_CODES if a.legs == "codes" else OUT)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     for shape in a.shapes.split(","):
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", shape, "--reps", str(a.reps)]
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", shape, "--reps", str(a.reps), "--legs", a.legs]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         with open(a.out, "a") as f:
             for x in r.stdout.splitlines():
