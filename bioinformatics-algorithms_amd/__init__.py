@@ -45,6 +45,7 @@ EXPORTS = [
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
     "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
     "pwa_align_wfa_codes_batch_cigar", "pwa_wfa_last_stats",
+    "pwa_wfa_sg_plan", "pwa_scores_wfa_sg", "pwa_align_wfa_sg_batch", "pwa_align_wfa_sg_batch_cigar",
 ]
 
 
@@ -85,19 +86,28 @@ def _min_scores(min_score, n):
     return (C.c_int32 * max(n, 1))(*ms)
 
 
-def wfa_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
-    """pwa_wfa_plan (host only): the penalties and, for every (n, m) of `lengths`, the sweep bound and the planned wavefront cells ->
-    dict(pen=(x, o, e, g), p_max=[...], cells=[...]); p_max is None and cells 0 for a pair the bound already rules out."""
+def _wfa_plan(name, n_pen, match, mismatch, gap_open, gap_extend, lengths, min_score):
     L = lib()
     k = len(lengths)
     ns = (C.c_uint64 * max(k, 1))(*[int(a) for a, _ in lengths])
     ms = (C.c_uint64 * max(k, 1))(*[int(b) for _, b in lengths])
-    pen = (C.c_int32 * 4)()
+    pen = (C.c_int32 * n_pen)()
     pm, ce = (C.c_uint64 * max(k, 1))(), (C.c_uint64 * max(k, 1))()
-    rc = L.pwa_wfa_plan(match, mismatch, gap_open, gap_extend, ns, ms, _min_scores(min_score, k), k, pen, pm, ce)
+    rc = getattr(L, name)(match, mismatch, gap_open, gap_extend, ns, ms, _min_scores(min_score, k), k, pen, pm, ce)
     if rc != 0:
-        raise PwaError("pwa_wfa_plan: %s" % L.pwa_strerror(rc).decode())
+        raise PwaError("%s: %s" % (name, L.pwa_strerror(rc).decode()))
     return dict(pen=tuple(pen), p_max=[None if pm[i] == (1 << 64) - 1 else pm[i] for i in range(k)], cells=list(ce[:k]))
+
+
+def wfa_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
+    """pwa_wfa_plan (host only): the penalties and, for every (n, m) of `lengths`, the sweep bound and the planned wavefront cells ->
+    dict(pen=(x, o, e, g), p_max=[...], cells=[...]); p_max is None and cells 0 for a pair the bound already rules out."""
+    return _wfa_plan("pwa_wfa_plan", 4, match, mismatch, gap_open, gap_extend, lengths, min_score)
+
+
+def wfa_sg_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
+    """pwa_wfa_sg_plan (host only): wfa_plan for the semi-global form -> dict(pen=(x, o, eI, eD, g), p_max=[...], cells=[...])."""
+    return _wfa_plan("pwa_wfa_sg_plan", 5, match, mismatch, gap_open, gap_extend, lengths, min_score)
 
 
 def approx_minima(hits, pat_len, k, n):
@@ -319,6 +329,10 @@ def lib():
     L.pwa_align_wfa_codes_batch.argtypes = L.pwa_align_wfa_batch.argtypes
     L.pwa_align_wfa_codes_batch_cigar.argtypes = L.pwa_align_wfa_batch_cigar.argtypes
     L.pwa_wfa_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
+    L.pwa_wfa_sg_plan.argtypes = L.pwa_wfa_plan.argtypes
+    L.pwa_scores_wfa_sg.argtypes = wfa_in + [i32p, i32p, u32p, u64p]   # ..., min_score, score, penalty, end_j
+    L.pwa_align_wfa_sg_batch.argtypes = wfa_in + [i32p, vp, u64p, u64p, u64p, u64p, i32p]   # ..., score, ops, ops_off, n_ops, end, start, min_score
+    L.pwa_align_wfa_sg_batch_cigar.argtypes = wfa_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p, i32p]
     _lib = L
     return L
 
@@ -859,8 +873,76 @@ class Context:
         return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
                      end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
 
+    # -- the semi-global form: the whole pattern against any substring of the text (include/pwalign.h, "Semi-global wavefront alignments")
+    def scores_wfa_sg(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, want_penalty=False, want_end=False):
+        """pwa_scores_wfa_sg: the semi-global affine-gap score of every pair (pattern = pair_a, whole; text = pair_b, ends free), None for
+        a pair whose optimum lies below min_score (None, one int, or one per pair) -> scores, or a tuple of scores, then with
+        want_penalty the penalties (None where not found), then with want_end the end cells (i, j) ((0, 0) where not found)."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        pen = (C.c_uint32 * max(n, 1))()
+        ej = (C.c_uint64 * max(n, 1))()
+        rc = self._L.pwa_scores_wfa_sg(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, _min_scores(min_score, n), sc, pen, ej)
+        self._check(rc, "pwa_scores_wfa_sg")
+        scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
+        out = [scores]
+        if want_penalty:
+            out.append([None if scores[k] is None else pen[k] for k in range(n)])
+        if want_end:
+            out.append([(0, 0) if scores[k] is None else (len(seqs[pair_a[k]]), ej[k]) for k in range(n)])
+        return scores if len(out) == 1 else tuple(out)
+
+    def align_wfa_sg_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
+        """pwa_align_wfa_sg_batch -> [dict(score, ops, end, start)] as align_gotoh_batch("sg", ...) returns them (end = (n, j), start =
+        (0, j0)); score None, ops b"" and both cells (0, 0) for a pair not found."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ooff = (C.c_uint64 * max(n, 1))()
+        tot = 0
+        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
+        for k in range(n):
+            ooff[k] = tot
+            tot += ln(pair_a[k]) + ln(pair_b[k])
+        ops = C.create_string_buffer(tot + 1)
+        nops = (C.c_uint64 * max(n, 1))()
+        end, start = (C.c_uint64 * max(2 * n, 1))(), (C.c_uint64 * max(2 * n, 1))()
+        rc = self._L.pwa_align_wfa_sg_batch(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, end, start,
+                                            _min_scores(min_score, n))
+        self._check(rc, "pwa_align_wfa_sg_batch")
+        raw = memoryview(ops)
+        return [dict(score=None if sc[k] == WFA_NONE else sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]),
+                     end=(end[2 * k], end[2 * k + 1]), start=(start[2 * k], start[2 * k + 1])) for k in range(n)]
+
+    def align_wfa_sg_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
+        """pwa_align_wfa_sg_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_gotoh_batch_cigar("sg", ...) returns them;
+        score None, two empty strings and both cells (0, 0) for a pair not found."""
+        blob, off, seqs = pack_sequences(seqs)
+        n = len(pair_a)
+        pa = (C.c_uint32 * max(n, 1))(*pair_a)
+        pb = (C.c_uint32 * max(n, 1))(*pair_b)
+        sc = (C.c_int32 * max(n, 1))()
+        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
+        nm = [ln(pair_a[k]) + ln(pair_b[k]) for k in range(n)]
+        cap_c, cap_m = sum(2 * v + 24 for v in nm), sum(3 * v + 24 for v in nm)   # pwa_cigar_bound / pwa_mdz_bound
+        cg, md = C.create_string_buffer(cap_c + 1), C.create_string_buffer(cap_m + 1)
+        co, mo = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
+        end, start = (C.c_uint64 * max(2 * n, 1))(), (C.c_uint64 * max(2 * n, 1))()
+        rc = self._L.pwa_align_wfa_sg_batch_cigar(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
+                                                  md, cap_m, mo, end, start, None, _min_scores(min_score, n))
+        self._check(rc, "pwa_align_wfa_sg_batch_cigar")
+        cgb, mdb = cg.raw, md.raw
+        return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
+                     end=(end[2 * k], end[2 * k + 1]), start=(start[2 * k], start[2 * k + 1])) for k in range(n)]
+
     def align_wfa_stats(self):
-        """The last scores_wfa / align_wfa_batch(_cigar): device ms of the sweeps and walks, wavefront cells swept, workspace bytes."""
+        """The last scores_wfa / align_wfa_batch(_cigar) / scores_wfa_sg / align_wfa_sg_batch(_cigar): device ms of the sweeps and walks,
+        wavefront cells swept, workspace bytes."""
         f, w, c, b = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0)
         self._check(self._L.pwa_wfa_last_stats(self._h, C.byref(f), C.byref(w), C.byref(c), C.byref(b)), "pwa_wfa_last_stats")
         return {"sweep_ms": f.value, "walk_ms": w.value, "cells": c.value, "workspace_bytes": b.value}

@@ -3,7 +3,7 @@
 #include "side_unit.h"
 
 namespace pwa {
-// the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar): device ms of the sweeps and of the walks (events, summed over the ranges), the
+// the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar) or one of their codes and semi-global forms: device ms of the sweeps and of the walks (events, summed over the ranges), the
 // wavefront cells of its pairs up to each pair's penalty (or bound), the bytes of the largest range's wavefront workspace
 struct WfaStats {
     float sweep_ms = 0.f, walk_ms = 0.f;

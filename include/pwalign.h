@@ -51,7 +51,7 @@
  *   PWA_ARENA_LIMIT, PWA_LANE_ROWS_LIMIT   bytes per run of the one-shot calls / per-lane text rows per batch (force the multi-run paths)
  *   PWA_RANGE_BYTES               band + op bytes per range of pwa_align_batch / pwa_overlaps (forces several ranges on a small list);
  *                                 band bytes per chunk of pwa_align_affine_batch's stripe-engine pairs; wavefront + op bytes per range of
- *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar) / pwa_align_wfa_codes_batch(_cigar)
+ *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar) / pwa_align_wfa_codes_batch(_cigar) and the pwa_*_wfa_sg calls
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
  *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
@@ -913,6 +913,69 @@ int pwa_align_wfa_codes_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int g
                                     char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
                                     uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
 int pwa_wfa_last_stats(const pwa_ctx *ctx, float *sweep_ms, float *walk_ms, uint64_t *cells, uint64_t *workspace_bytes);
+
+/* ---- Semi-global wavefront alignments: the WHOLE pattern against any substring of the text, both text ends free, exact, for patterns
+ * of any length and without a band.  What PWA_MODE_SG of the gotoh block computes (score, end cell = the first
+ * maximum of row n), by the sweep of the block above; scoring, sequences, pairs, bytes and the range rule are that block's.
+ * The global conversion does not carry over: its 2x scale rests on n + m being fixed, and here the consumed text length varies.
+ * Penalties are counted per PATTERN symbol instead -- every one is consumed, so n = matches + mismatches + 'D':
+ *   x0 = match - mismatch   o0 = -gap_open   eI0 = -gap_extend   eD0 = match - gap_extend
+ *   g = gcd(x0, o0, eI0, eD0) (gcd with 0 is the other value)   x, o, eI, eD = the four divided by g     score = match n - g P
+ * P is the sum of the reduced penalties of the alignment's mismatches and gaps: a run of L 'I' (text symbol against a gap) costs
+ * o + L eI, a run of L 'D' (pattern symbol against a gap) o + L eD, a skipped text prefix or suffix nothing; minimal P is maximal
+ * semi-global score.  PWA_E_INVALID unless gap_open <= 0, gap_extend < 0, match > mismatch and match - gap_extend > 0 (gap_extend = 0
+ * would give eI = 0, a dependency between diagonals of one wavefront).
+ * Wavefronts, on the definitions above (offset = text index j, k = j - i, the trim on every term):
+ *   I[s][k] = max(M[s-o-eI][k-1], I[s-eI][k-1]) + 1
+ *   D[s][k] = max(M[s-o-eD][k+1], D[s-eD][k+1])
+ *   M[s][k] = extend(max(M[s-x][k] + 1, I[s][k], D[s][k]))
+ *   M[0][k] = extend(k) for every k = 0 .. m: a start at cell (0, k); I[0] and D[0] are NULL
+ * A score is empty when its five source wavefronts (s - x, s - o - eI, s - eI, s - o - eD, s - eD) are all empty or below 0.
+ * Wavefront s spans the diagonals [max(-n, -khD(s)), m], khD(s) = 0 for s < o + eD, else (s - o) div eD; width(s) = m + 1 +
+ * min(n, khD(s)), and cells(k) = the sum of width(s) over s = 0 .. P_max as above.
+ * End: the sweep ends at the first s at which some diagonal holds an offset with j - k = n; that s is P, and the end cell is
+ * (n, n + k_end) with k_end the LOWEST such diagonal -- the first maximum of row n, so end cells equal the DP calls' exactly.  Op
+ * lists need not: between ties the path is chosen by the wavefront rules.
+ * Backtrace: from state M at (P, k_end, n + k_end) with the rules above (ties mismatch >= I >= D, a tie opens); I reads s - o - eI and
+ * s - eI at k - 1, D reads s - o - eD and s - eD at k + 1.  At s = 0 it stands on a diagonal 0 <= k <= m, emits j - k 'M' and stops:
+ * the start cell is (0, k).
+ * Bound: P_worst = o + n eD for n > 0 (all 'D'), else 0; for m >= n the smaller of that and n x (all mismatches).
+ * P_max = min(P_worst, floor((match n - min_score) / g)).  NOT FOUND on the host: P_max < 0, or n > m and P_max < o + (n - m) eD; on
+ * the device: the sweep reaches P_max without ending.  A pair not found gets PWA_WFA_NONE, penalty 0xffffffff, n_ops = 0, empty
+ * strings, and end and start cells (0, 0).  Empty sides as PWA_MODE_SG: n = 0 scores 0 with end = start = (0, 0) and no ops; m = 0
+ * gives n 'D'.
+ *   pwa_wfa_sg_plan          pwa_wfa_plan for this form: pen = x, o, eI, eD, g.
+ *   pwa_scores_wfa_sg        score_out[k], penalty_out[k] = P and end_j_out[k] = the end cell's text index (0 for a pair not found);
+ *                            the last two may be NULL.  Workspace: a ring of min(max(x, o + eI, o + eD) + 1, P_max + 1) wavefronts of
+ *                            3 width(P_max) int32 per pair.
+ *   pwa_align_wfa_sg_batch   op lists with pwa_align_wfa_codes_batch's op regions (n + m bytes of room per pair), and per pair the end
+ *                            cell (i, j) in end_cells[2k], [2k + 1] and the start cell in start_cells (either may be NULL).
+ *   pwa_align_wfa_sg_batch_cigar  the same alignments as CIGAR and MD:Z with pwa_align_wfa_codes_batch_cigar's buffers and
+ *                            PWA_E_CAPACITY / needed protocol; the strings equal pwa_format_alignment of the op list with the returned
+ *                            end cell byte for byte.
+ * The alignment calls exist in the codes form only: the ring above, then cells(k) code bytes with the same bit layout, written by
+ * the same sweep; pass A starts at (P, k_end), accepts any 0 <= k <= m at s = 0 and notes it as the start; pass B replays from
+ * (0, k_start) and must end on (n, n + k_end) with every op slot written.  Validation, its order, the ranges under PWA_RANGE_BYTES
+ * (weight = ring + codes + op bytes) are those of pwa_align_wfa_codes_batch(_cigar); pwa_wfa_last_stats reports these calls too. */
+int pwa_wfa_sg_plan(int match, int mismatch, int gap_open, int gap_extend, const uint64_t *n, const uint64_t *m,
+                    const int32_t *min_score /* or NULL */, uint64_t n_pairs, int32_t pen[5] /* x, o, eI, eD, g */,
+                    uint64_t *p_max /* or NULL */, uint64_t *cells /* or NULL */);
+int pwa_scores_wfa_sg(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                      const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b, uint64_t n_pairs,
+                      const int32_t *min_score /* or NULL */, int32_t *score_out, uint32_t *penalty_out /* or NULL */,
+                      uint64_t *end_j_out /* or NULL */);
+int pwa_align_wfa_sg_batch(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                           const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                           uint64_t n_pairs, int32_t *score_out, uint8_t *ops, const uint64_t *ops_off, uint64_t *n_ops,
+                           uint64_t *end_cells /* 2 * n_pairs or NULL */, uint64_t *start_cells /* 2 * n_pairs or NULL */,
+                           const int32_t *min_score /* or NULL */);
+int pwa_align_wfa_sg_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend, const uint8_t *seq_bytes,
+                                 const uint64_t *seq_off, uint32_t n_seq, const uint32_t *pair_a, const uint32_t *pair_b,
+                                 uint64_t n_pairs, int32_t *score_out,
+                                 char *cigar, uint64_t cigar_cap, uint64_t *cigar_off /* n_pairs + 1 */,
+                                 char *mdz, uint64_t mdz_cap, uint64_t *mdz_off /* n_pairs + 1 */,
+                                 uint64_t *end_cells /* 2 * n_pairs or NULL */, uint64_t *start_cells /* 2 * n_pairs or NULL */,
+                                 uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
 
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
