@@ -740,8 +740,19 @@ class Context:
         return blob, off, seqs, n, pa, pb, sc, endc, startc, pe
 
     @staticmethod
-    def _align_results(n, own, sc, endc, startc, pe, ext):
-        """... and end with: own(k) = the keys of pair k that only the one call has, between score and end"""
+    def _pair_lens(seqs, pair_a, pair_b, lax):
+        """(n, m) of every pair; lax: 0 for an index outside the list, which is then the library's to refuse (a PwaError, not an IndexError)"""
+        ln = (lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0) if lax else (lambda i: len(seqs[i]))
+        return [(ln(a), ln(b)) for a, b in zip(pair_a, pair_b)]
+
+    @staticmethod
+    def _align_results(n, own, sc, endc, startc, pe, ext, none=None, ends=None):
+        """... and end with: own(k) = the keys of pair k that only the one call has, between score and end; none: the score that stands
+        for "no alignment" and is returned as None; ends: the end cells of a call without cell outputs, whose start cells are (0, 0)"""
+        if none is not None:
+            sc = [None if v == none else v for v in sc[:n]]
+        if ends is not None:
+            return [dict(score=sc[k], **own(k), end=ends[k], start=(0, 0)) for k in range(n)]
         if not ext:
             return [dict(score=sc[k], **own(k), end=(endc[2 * k], endc[2 * k + 1]), start=(startc[2 * k], startc[2 * k + 1])) for k in range(n)]
         out = [dict(score=sc[k], **own(k), end=(endc[2 * k], endc[2 * k + 1]), start=(0, 0), rows=startc[k]) for k in range(n)]
@@ -749,29 +760,31 @@ class Context:
             out[k]["pend"] = _pend(pe[0][k], pe[1][k])
         return out
 
-    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
+    def _align_ops(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False, none=None, cells=True, lax=False):
         """an op-list alignment call whose arguments are `head` (context .. scoring), the sequences, the pairs, the outputs (and `tail`);
         ext: an extension call -- rows_out where the others take start_cells, start = (0, 0) and a `rows` key in the result;
-        pend: ... with pend_score_out and pend_j_out behind rows_out, and a `pend` key"""
+        pend: ... with pend_score_out and pend_j_out behind rows_out, and a `pend` key;
+        none, cells, lax (the wavefront calls): see _align_results and _pair_lens; cells=False: no end_cells and start_cells, end = (n, m)"""
         blob, off, seqs, n, pa, pb, sc, endc, startc, pe = self._align_begin(seqs, pair_a, pair_b, ext, pend)
+        lens = self._pair_lens(seqs, pair_a, pair_b, lax)
         ooff = (C.c_uint64 * max(n, 1))()
         tot = 0
         for k in range(n):
             ooff[k] = tot
-            tot += len(seqs[pair_a[k]]) + len(seqs[pair_b[k]])
+            tot += lens[k][0] + lens[k][1]
         ops = C.create_string_buffer(tot + 1)
         nops = (C.c_uint64 * max(n, 1))()
-        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, endc, startc, *pe, *tail)
+        rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, *((endc, startc) if cells else ()), *pe, *tail)
         self._check(rc, name)
         raw = memoryview(ops)
-        return self._align_results(n, lambda k: dict(ops=bytes(raw[ooff[k]:ooff[k] + nops[k]])), sc, endc, startc, pe, ext)
+        return self._align_results(n, lambda k: dict(ops=bytes(raw[ooff[k]:ooff[k] + nops[k]])), sc, endc, startc, pe, ext, none, None if cells else lens)
 
-    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False):
-        """... and one that returns CIGAR and MD:Z strings built on the device"""
+    def _align_strings(self, fn, name, head, seqs, pair_a, pair_b, tail=(), ext=False, pend=False, none=None, cells=True, lax=False):
+        """... and one that returns CIGAR and MD:Z strings (built on the device; the wavefront calls' on the host)"""
         import numpy as np
         blob, off, seqs, n, pa, pb, sc, endc, startc, pe = self._align_begin(seqs, pair_a, pair_b, ext, pend)
-        lens = np.array([len(x) for x in seqs] or [0], dtype=np.uint64)
-        nm = lens[np.asarray(pair_a, dtype=np.int64)] + lens[np.asarray(pair_b, dtype=np.int64)] if n else np.zeros(0, np.uint64)
+        lens = self._pair_lens(seqs, pair_a, pair_b, lax)
+        nm = np.array([a + b for a, b in lens], dtype=np.uint64)
         cap_c, cap_m = int((2 * nm + 24).sum()), int((3 * nm + 24).sum())   # pwa_cigar_bound / pwa_mdz_bound
         cg = np.empty(max(cap_c, 1), dtype=np.uint8)
         md = np.empty(max(cap_m, 1), dtype=np.uint8)
@@ -779,11 +792,12 @@ class Context:
         md_off = np.zeros(n + 1, dtype=np.uint64)
         u64p = C.POINTER(C.c_uint64)
         rc = fn(*head, blob, off, len(seqs), pa, pb, n, sc, cg.ctypes.data_as(C.c_void_p), cap_c, cg_off.ctypes.data_as(u64p),
-                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), endc, startc, *pe, None, *tail)
+                md.ctypes.data_as(C.c_void_p), cap_m, md_off.ctypes.data_as(u64p), *((endc, startc) if cells else ()), *pe, None, *tail)
         self._check(rc, name)
         co, mo = cg_off.tolist(), md_off.tolist()
         cgb, mdb = cg[:co[n]].tobytes(), md[:mo[n]].tobytes()
-        return self._align_results(n, lambda k: dict(cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]]), sc, endc, startc, pe, ext)
+        return self._align_results(n, lambda k: dict(cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]]), sc, endc, startc, pe, ext, none,
+                                   None if cells else lens)
 
     def _stats3(self, fn, name, third):
         """a last-stats call of three values: device ms of the fills and of the walks, and a count under the key `third`"""
@@ -804,19 +818,21 @@ class Context:
                                    (self._h, MODE[mode], match, mismatch, gap_open, gap_extend), seqs, pair_a, pair_b)
 
     # -- wavefront (WFA) affine-gap global alignments of long pairs: exact, no band (include/pwalign.h, "Wavefront alignments")
+    def _wfa_scores(self, name, seqs, pair_a, pair_b, scoring, min_score, end_j=False):
+        """a WFA score pass: min_score before score_out and penalty_out, with end_j an end_j_out behind them
+        -> scores and penalties (None for a pair not found), the sequences, end_j_out"""
+        blob, off, seqs, n, pa, pb, sc, _, _, _ = self._align_begin(seqs, pair_a, pair_b, False, False)
+        pen = (C.c_uint32 * max(n, 1))()
+        ej = (C.c_uint64 * max(n, 1))() if end_j else None
+        self._check(getattr(self._L, name)(self._h, *scoring, blob, off, len(seqs), pa, pb, n, _min_scores(min_score, n), sc, pen, *([ej] if end_j else [])), name)
+        scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
+        return scores, [None if scores[k] is None else pen[k] for k in range(n)], seqs, ej
+
     def scores_wfa(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, want_penalty=False):
         """pwa_scores_wfa: the global affine-gap score of every pair, None for a pair whose optimum lies below min_score (None, one
         int, or one per pair) -> scores, or with want_penalty (scores, penalties)."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        pen = (C.c_uint32 * max(n, 1))()
-        rc = self._L.pwa_scores_wfa(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, _min_scores(min_score, n), sc, pen)
-        self._check(rc, "pwa_scores_wfa")
-        scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
-        return (scores, [None if scores[k] is None else pen[k] for k in range(n)]) if want_penalty else scores
+        scores, pens, _, _ = self._wfa_scores("pwa_scores_wfa", seqs, pair_a, pair_b, (match, mismatch, gap_open, gap_extend), min_score)
+        return (scores, pens) if want_penalty else scores
 
     @staticmethod
     def _wfa_form(form, name):
@@ -828,117 +844,46 @@ class Context:
             return name.replace("pwa_align_wfa_", "pwa_align_wfa_codes_")
         raise ValueError('form: "offsets" or "codes", not %r' % (form,))
 
+    def _wfa_align(self, helper, name, cells, seqs, pair_a, pair_b, scoring, min_score):
+        """a WFA alignment call through _align_ops or _align_strings: min_score in the tail, PWA_WFA_NONE as None, a pair index outside
+        the list left to the library; cells: the call has end and start cells (the semi-global form)"""
+        return helper(getattr(self._L, name), name, (self._h,) + scoring, seqs, pair_a, pair_b, tail=(_min_scores(min_score, len(pair_a)),),
+                      none=WFA_NONE, cells=cells, lax=True)
+
     def align_wfa_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, form="offsets"):
         """pwa_align_wfa_batch (form="offsets") or pwa_align_wfa_codes_batch (form="codes") -> [dict(score, ops, end, start)] as
         align_gotoh_batch returns them (end = (n, m), start = (0, 0)); score None and ops b"" for a pair not found."""
-        name = self._wfa_form(form, "pwa_align_wfa_batch")
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ooff = (C.c_uint64 * max(n, 1))()
-        tot = 0
-        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
-        for k in range(n):
-            ooff[k] = tot
-            tot += ln(pair_a[k]) + ln(pair_b[k])
-        ops = C.create_string_buffer(tot + 1)
-        nops = (C.c_uint64 * max(n, 1))()
-        rc = getattr(self._L, name)(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops,
-                                    _min_scores(min_score, n))
-        self._check(rc, name)
-        raw = memoryview(ops)
-        return [dict(score=None if sc[k] == WFA_NONE else sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]),
-                     end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
+        return self._wfa_align(self._align_ops, self._wfa_form(form, "pwa_align_wfa_batch"), False, seqs, pair_a, pair_b,
+                               (match, mismatch, gap_open, gap_extend), min_score)
 
     def align_wfa_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, form="offsets"):
         """pwa_align_wfa_batch_cigar (form="offsets") or pwa_align_wfa_codes_batch_cigar (form="codes") -> [dict(score, cigar, mdz, end,
         start)] as align_gotoh_batch_cigar returns them; score None and two empty strings for a pair not found."""
-        name = self._wfa_form(form, "pwa_align_wfa_batch_cigar")
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
-        nm = [ln(pair_a[k]) + ln(pair_b[k]) for k in range(n)]
-        cap_c, cap_m = sum(2 * v + 24 for v in nm), sum(3 * v + 24 for v in nm)   # pwa_cigar_bound / pwa_mdz_bound
-        cg, md = C.create_string_buffer(cap_c + 1), C.create_string_buffer(cap_m + 1)
-        co, mo = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
-        rc = getattr(self._L, name)(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
-                                    md, cap_m, mo, None, _min_scores(min_score, n))
-        self._check(rc, name)
-        cgb, mdb = cg.raw, md.raw
-        return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
-                     end=(ln(pair_a[k]), ln(pair_b[k])), start=(0, 0)) for k in range(n)]
+        return self._wfa_align(self._align_strings, self._wfa_form(form, "pwa_align_wfa_batch_cigar"), False, seqs, pair_a, pair_b,
+                               (match, mismatch, gap_open, gap_extend), min_score)
 
     # -- the semi-global form: the whole pattern against any substring of the text (include/pwalign.h, "Semi-global wavefront alignments")
     def scores_wfa_sg(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None, want_penalty=False, want_end=False):
         """pwa_scores_wfa_sg: the semi-global affine-gap score of every pair (pattern = pair_a, whole; text = pair_b, ends free), None for
         a pair whose optimum lies below min_score (None, one int, or one per pair) -> scores, or a tuple of scores, then with
         want_penalty the penalties (None where not found), then with want_end the end cells (i, j) ((0, 0) where not found)."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        pen = (C.c_uint32 * max(n, 1))()
-        ej = (C.c_uint64 * max(n, 1))()
-        rc = self._L.pwa_scores_wfa_sg(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, _min_scores(min_score, n), sc, pen, ej)
-        self._check(rc, "pwa_scores_wfa_sg")
-        scores = [None if sc[k] == WFA_NONE else sc[k] for k in range(n)]
+        scores, pens, seqs, ej = self._wfa_scores("pwa_scores_wfa_sg", seqs, pair_a, pair_b, (match, mismatch, gap_open, gap_extend), min_score, end_j=True)
         out = [scores]
         if want_penalty:
-            out.append([None if scores[k] is None else pen[k] for k in range(n)])
+            out.append(pens)
         if want_end:
-            out.append([(0, 0) if scores[k] is None else (len(seqs[pair_a[k]]), ej[k]) for k in range(n)])
+            out.append([(0, 0) if s is None else (len(seqs[pair_a[k]]), ej[k]) for k, s in enumerate(scores)])
         return scores if len(out) == 1 else tuple(out)
 
     def align_wfa_sg_batch(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
         """pwa_align_wfa_sg_batch -> [dict(score, ops, end, start)] as align_gotoh_batch("sg", ...) returns them (end = (n, j), start =
         (0, j0)); score None, ops b"" and both cells (0, 0) for a pair not found."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ooff = (C.c_uint64 * max(n, 1))()
-        tot = 0
-        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
-        for k in range(n):
-            ooff[k] = tot
-            tot += ln(pair_a[k]) + ln(pair_b[k])
-        ops = C.create_string_buffer(tot + 1)
-        nops = (C.c_uint64 * max(n, 1))()
-        end, start = (C.c_uint64 * max(2 * n, 1))(), (C.c_uint64 * max(2 * n, 1))()
-        rc = self._L.pwa_align_wfa_sg_batch(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, ops, ooff, nops, end, start,
-                                            _min_scores(min_score, n))
-        self._check(rc, "pwa_align_wfa_sg_batch")
-        raw = memoryview(ops)
-        return [dict(score=None if sc[k] == WFA_NONE else sc[k], ops=bytes(raw[ooff[k]:ooff[k] + nops[k]]),
-                     end=(end[2 * k], end[2 * k + 1]), start=(start[2 * k], start[2 * k + 1])) for k in range(n)]
+        return self._wfa_align(self._align_ops, "pwa_align_wfa_sg_batch", True, seqs, pair_a, pair_b, (match, mismatch, gap_open, gap_extend), min_score)
 
     def align_wfa_sg_batch_cigar(self, seqs, pair_a, pair_b, match, mismatch, gap_open, gap_extend, min_score=None):
         """pwa_align_wfa_sg_batch_cigar -> [dict(score, cigar, mdz, end, start)] as align_gotoh_batch_cigar("sg", ...) returns them;
         score None, two empty strings and both cells (0, 0) for a pair not found."""
-        blob, off, seqs = pack_sequences(seqs)
-        n = len(pair_a)
-        pa = (C.c_uint32 * max(n, 1))(*pair_a)
-        pb = (C.c_uint32 * max(n, 1))(*pair_b)
-        sc = (C.c_int32 * max(n, 1))()
-        ln = lambda i: len(seqs[i]) if 0 <= i < len(seqs) else 0   # (an index outside the list is the library's to refuse)
-        nm = [ln(pair_a[k]) + ln(pair_b[k]) for k in range(n)]
-        cap_c, cap_m = sum(2 * v + 24 for v in nm), sum(3 * v + 24 for v in nm)   # pwa_cigar_bound / pwa_mdz_bound
-        cg, md = C.create_string_buffer(cap_c + 1), C.create_string_buffer(cap_m + 1)
-        co, mo = (C.c_uint64 * (n + 1))(), (C.c_uint64 * (n + 1))()
-        end, start = (C.c_uint64 * max(2 * n, 1))(), (C.c_uint64 * max(2 * n, 1))()
-        rc = self._L.pwa_align_wfa_sg_batch_cigar(self._h, match, mismatch, gap_open, gap_extend, blob, off, len(seqs), pa, pb, n, sc, cg, cap_c, co,
-                                                  md, cap_m, mo, end, start, None, _min_scores(min_score, n))
-        self._check(rc, "pwa_align_wfa_sg_batch_cigar")
-        cgb, mdb = cg.raw, md.raw
-        return [dict(score=None if sc[k] == WFA_NONE else sc[k], cigar=cgb[co[k]:co[k + 1]], mdz=mdb[mo[k]:mo[k + 1]],
-                     end=(end[2 * k], end[2 * k + 1]), start=(start[2 * k], start[2 * k + 1])) for k in range(n)]
+        return self._wfa_align(self._align_strings, "pwa_align_wfa_sg_batch_cigar", True, seqs, pair_a, pair_b, (match, mismatch, gap_open, gap_extend), min_score)
 
     def align_wfa_stats(self):
         """The last scores_wfa / align_wfa_batch(_cigar) / scores_wfa_sg / align_wfa_sg_batch(_cigar): device ms of the sweeps and walks,

@@ -915,8 +915,8 @@ extern "C" {
 
 const char* pwa_version(void) { return "pwalign 0.1 gfx950"; }
 
-// Host-only checks of the scheduler's sorting helpers and of the alignment batches' range planner (include/pwalign.h): tests call this on
-// machines without a GPU.
+// Host-only checks of the scheduler's sorting helpers, of the alignment batches' range planner (include/pwalign.h) and of the wavefront
+// unit's: tests call this on machines without a GPU.
 int pwa_selftest_host(uint32_t seed) try {
     uint64_t x = 0x9e3779b97f4a7c15ull ^ seed;
     auto rnd = [&]() {
@@ -1014,7 +1014,8 @@ int pwa_selftest_host(uint32_t seed) try {
     }
     if (const int rc = selftest_pair_forms()) return check + rc;
     if (const int rc = selftest_banded_forms()) return check + 2 + rc;
-    return selftest_align_plan(x, check + 5);
+    if (const int rc = selftest_align_plan(x, check + 5)) return rc;
+    return selftest_wfa_plan(x, check + 11);
 } catch (...) {
     return -1;
 }

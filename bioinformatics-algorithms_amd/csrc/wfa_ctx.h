@@ -16,3 +16,10 @@ struct WfaCtxView : UnitCtx {
 WfaCtxView wfa_ctx_view(pwa_ctx* c);
 const WfaStats& wfa_stats_of(const pwa_ctx* c);
 }  // namespace pwa
+
+#pragma GCC visibility push(hidden)
+namespace pwa {
+// defined in wfa_kernels.hip, behind the range planner it checks; pwa_selftest_host ends with it
+int selftest_wfa_plan(uint64_t x, int check);
+}  // namespace pwa
+#pragma GCC visibility pop

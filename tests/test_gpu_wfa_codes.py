@@ -211,6 +211,50 @@ def test_ranges_and_poisoned_buffers_change_nothing(ctx, pkg):
             assert both(c, pairs, SC, bounds, want)[0] == plain
 
 
+def test_ranges_without_a_live_pair_change_nothing(ctx, pkg):
+    """the first pair and a run of four in the middle carry a bound above any score, so the host rules them out; under a budget of
+    about two pairs' op bytes they form ranges of their own in the alignment forms -- the first range among them --, which launch
+    nothing, and every result and the cell count stay the uncut call's"""
+    rng = random.Random(27)
+    dead = {0, 5, 6, 7, 8}
+    pairs = []
+    for k in range(12):
+        p = rand_seq(rng, 60 + 5 * k)
+        t = mutate(rng, p, 0.05 + 0.005 * k)
+        pairs.append((p, t + rand_seq(rng, max(0, len(p) - len(t)))))   # m >= n: the bound below is above the semi-global scores too
+    bounds = [SC[0] * (len(p) + len(t)) // 2 + 1 if k in dead else -(1 << 30) for k, (p, t) in enumerate(pairs)]
+    nm = [len(p) + len(t) for p, t in pairs]
+    budget = 2 * max(nm)
+    # the ranges, on the CPU: a live pair alone exceeds the budget in every form, a pair ruled out weighs its op bytes
+    cells = pkg.wfa_plan(*SC, [(len(p), len(t)) for p, t in pairs], bounds)["cells"]
+    sg_cells = pkg.wfa_sg_plan(*SC, [(len(p), len(t)) for p, t in pairs], bounds)["cells"]
+    by_form = dict(offsets=[12 * c + s for c, s in zip(cells, nm)],
+                   codes=[ring + (c + 3) // 4 * 4 + s for (ring, c), s in zip(codes_sizes(pkg, pairs, SC, bounds), nm)],
+                   sg=[c + s for c, s in zip(sg_cells, nm)])   # (a lower bound: the ring comes on top)
+    for form, sizes in by_form.items():
+        assert all((sizes[k] == nm[k]) == (k in dead) for k in range(12)) and min(sizes[k] for k in range(12) if k not in dead) > budget, form
+        ranges = TW.split(sizes, budget)
+        assert ranges[0] == (0, 1) and sum(all(k in dead for k in range(k0, k1)) for k0, k1 in ranges) >= 3, (form, ranges)
+    seqs, pa, pb = flatten(pairs)
+
+    def everything(c):
+        out = []
+        for call in (lambda: c.align_wfa_batch(seqs, pa, pb, *SC, min_score=bounds), lambda: c.align_wfa_batch(seqs, pa, pb, *SC, min_score=bounds, form="codes"),
+                     lambda: c.align_wfa_batch_cigar(seqs, pa, pb, *SC, min_score=bounds), lambda: c.align_wfa_batch_cigar(seqs, pa, pb, *SC, min_score=bounds, form="codes"),
+                     lambda: c.align_wfa_sg_batch(seqs, pa, pb, *SC, min_score=bounds), lambda: c.align_wfa_sg_batch_cigar(seqs, pa, pb, *SC, min_score=bounds),
+                     lambda: c.scores_wfa(seqs, pa, pb, *SC, min_score=bounds, want_penalty=True),
+                     lambda: c.scores_wfa_sg(seqs, pa, pb, *SC, min_score=bounds, want_penalty=True, want_end=True)):
+            out.append((call(), c.align_wfa_stats()["cells"]))
+        return out
+
+    plain = everything(ctx)
+    for res, n_cells in plain[:6]:
+        assert [a["score"] is None for a in res] == [k in dead for k in range(12)] and n_cells > 0
+    assert plain[1] == plain[0] and [(a["score"], a["ops"]) for a in plain[0][0]] == [(w["score"], w["ops"]) for w in TW.oracle(pairs, SC, bounds)]
+    with switched_context(PWA_RANGE_BYTES=budget) as c:
+        assert everything(c) == plain
+
+
 def test_workspace_is_a_ring_and_one_byte_per_planned_cell(ctx, pkg):
     pairs, bounds, want = TW.mixed()
     sizes = codes_sizes(pkg, pairs, SC, bounds)

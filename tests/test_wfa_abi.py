@@ -50,6 +50,21 @@ def test_null_context_and_null_pointers_are_invalid():
     assert L.pwa_wfa_plan(1, -4, -6, -1, None, None, None, 0, p4, None, None) == 0
 
 
+def test_range_planner_selftest():
+    """pwa_selftest_host ends with the wavefront unit's range planner (pwa::selftest_wfa_plan), host only: every one of the five forms
+    under scorings with a shallow and a deep ring, a few hundred pairs of 0 .. some thousand symbols on either side, without bounds, with
+    loose ones and with runs of pairs the host rules out, budgets from "one range" down to less than any pair.  It checks that the ranges
+    tile the list and are the greedy cut; that every pair not ruled out stands once in its range's launch list, longest plan first,
+    with its own lengths, blob offsets and result slot; that the workspace slices of a range are disjoint, lie inside the range's
+    workspace and hold what the kernels address by their own formulas; that the op slices tile the range's op bytes in pair order (none
+    for a score form); and that the buffer capacities cover every range"""
+    L = load_pkg().lib()
+    L.pwa_selftest_host.argtypes = [C.c_uint32]
+    L.pwa_selftest_host.restype = C.c_int
+    for seed in (0, 0x5eed, 0xffffffff):
+        assert L.pwa_selftest_host(seed) == 0, seed
+
+
 @pytest.mark.parametrize("bad", [(1, 1, -1, -1), (2, 3, -1, -1), (0, -1, -1, 0), (-2, -3, 0, -1), (1, 0, 1, -1), (1, 0, -1, 1)])
 def test_plan_refuses_a_scoring_without_a_penalty_form(bad):
     """match == mismatch, match < mismatch, match - 2 gap_extend == 0 (twice), a positive gap open, a positive gap extend"""
