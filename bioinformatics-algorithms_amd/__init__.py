@@ -29,6 +29,7 @@ MODE = {"nw": 0, "sw": 1, "global": 0, "local": 1, "sg": 2, "semiglobal": 2}   #
 EXPORTS = [
     "pwa_version", "pwa_strerror", "pwa_selftest_host", "pwa_ctx_create", "pwa_ctx_destroy", "pwa_last_error", "pwa_ctx_set_score_band", "pwa_ctx_poison_stats", "pwa_scores",
     "pwa_batch_create", "pwa_affine_batch_create", "pwa_scores_affine", "pwa_align_affine_batch", "pwa_nwdist_batch_create", "pwa_distances", "pwa_upgma_newick", "pwa_batch_run", "pwa_batch_d_scores", "pwa_batch_set_d_scores", "pwa_batch_fetch", "pwa_batch_info", "pwa_batch_cell_bits", "pwa_batch_profile_form", "pwa_batch_profile_int", "pwa_profile_plan", "pwa_strip_table",
+    "pwa_pair_form_table", "pwa_pair_forms", "pwa_pair_forms_reset",
     "pwa_batch_last_ms", "pwa_batch_run_times", "pwa_batch_destroy", "pwa_align", "pwa_align_matrices", "pwa_align_last_stats", "pwa_align_affine_last_stats", "pwa_align_batch", "pwa_align_batch_cigar", "pwa_overlaps",
     "pwa_align_gotoh_batch", "pwa_align_gotoh_batch_cigar", "pwa_align_gotoh_last_stats",
     "pwa_gotoh_batch_create", "pwa_scores_gotoh",
@@ -246,6 +247,9 @@ def lib():
     L.pwa_batch_profile_int.argtypes = [vp]
     L.pwa_profile_plan.argtypes = [C.c_uint32, C.c_uint32, u32p, u32p]
     L.pwa_strip_table.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), u32p, u32p]
+    L.pwa_pair_form_table.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), u32p]
+    L.pwa_pair_forms.argtypes = [vp, vp, C.c_uint64, u64p]
+    L.pwa_pair_forms_reset.argtypes = [vp]
     L.pwa_batch_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.pwa_batch_run_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.pwa_batch_destroy.argtypes = [vp]
@@ -354,6 +358,21 @@ def strip_table():
             raise PwaError("pwa_strip_table: %s" % L.pwa_strerror(rc).decode())
         out.append(dict(name=name.value.decode(), R=rows.value, mode=mode.value, score=score.value,
                         variants=tuple(v for k, v in enumerate(STRIP_VARIANTS) if var.value >> k & 1)))
+    return out
+
+
+def pair_form_table():
+    """pwa_pair_form_table (host only): the names of the pair-engine forms the library's call sites can build, in the listing's order."""
+    L = lib()
+    count = C.c_uint32(0)
+    L.pwa_pair_form_table(0xffffffff, None, C.byref(count))
+    out = []
+    for i in range(count.value):
+        name = C.c_char_p()
+        rc = L.pwa_pair_form_table(i, C.byref(name), None)
+        if rc != 0:
+            raise PwaError("pwa_pair_form_table: %s" % L.pwa_strerror(rc).decode())
+        out.append(name.value.decode())
     return out
 
 
@@ -533,6 +552,20 @@ class Context:
 
     def set_score_band(self, on):
         self._check(self._L.pwa_ctx_set_score_band(self._h, 1 if on else 0), "pwa_ctx_set_score_band")
+
+    def pair_forms(self):
+        """pwa_pair_forms: the names (pair_form_table's) of the pair-engine forms this context has prepared launches of since the last
+        reset_pair_forms(), distinct, in first-seen order."""
+        need = C.c_uint64(0)
+        rc = self._L.pwa_pair_forms(self._h, None, 0, C.byref(need))
+        if rc != -5:
+            self._check(rc, "pwa_pair_forms")
+        buf = C.create_string_buffer(need.value)
+        self._check(self._L.pwa_pair_forms(self._h, buf, need.value, C.byref(need)), "pwa_pair_forms")
+        return buf.value.decode().split("\n") if buf.value else []
+
+    def reset_pair_forms(self):
+        self._check(self._L.pwa_pair_forms_reset(self._h), "pwa_pair_forms_reset")
 
     def poison_stats(self):
         """pwa_ctx_poison_stats: what PWA_POISON has filled on this context so far -> dict(buffers, bytes); zeros with the switch unset."""

@@ -513,6 +513,83 @@ static bool resolve_pair_form(const PairForm& f, PairKernels& k) {   // false: n
     return (k.fill || k.sfill) && (k.walk || !k.walks);
 }
 
+std::string pair_form_name(const PairForm& f) {
+    static const char* const kFamily[] = {"stripe_fill", "stripe_dist", "stripe_affine", "stripe_affine_tb", "mini_fill", "mini_gotoh", "mini_subst"};
+    static const char* const kMode[] = {"NW", "SW", "SG"}, * const kBand[] = {"none", "tb", "tb+scores"}, * const kWalk[] = {"none", "ops", "overlap"};
+    static const char* const kCells[] = {"plain", "keyed", "coded", "gap0"};
+    auto of = [](const char* const* t, size_t n, int v) { return v >= 0 && (size_t)v < n ? t[v] : "?"; };
+    return std::string(of(kFamily, 7, f.family)) + "/" + of(kMode, 3, f.mode) + "/" + of(kBand, 3, f.band) + "/" + of(kWalk, 3, f.walk) + "/" + of(kCells, 4, f.cells) +
+           "/rl" + std::to_string(f.rl) + (f.mini() ? "/ln" : "/w") + std::to_string(f.w);
+}
+
+// What the call sites can build, one loop nest per site, each condition the site's own (DESIGN.md 3.23 quotes the expressions):
+//   run_launch (pwalign_align.hip)            walk = OPS | OVERLAP (no SG overlap: validate_align), band = TB | TB_SCORES; stripes: PLAIN at
+//                                             RL = 4, KEYED, CODED, GAP0 (NW, BAND_TB); mini classes (16 lanes x kMiniRL, 64 lanes x
+//                                             wide_rl_for): CODED, GAP0; gotoh / subst: BAND_TB, OPS, KEYED on TbPlan::class_of's gotoh classes
+//   pwa_align_matrices                        BAND_TB_SCORES, WALK_NONE; stripes KEYED | PLAIN (RL = 4), mini classes CODED
+//   setup_off_strips (pwalign.hip)            BAND_NONE, WALK_NONE; stripes PLAIN | CODED | GAP0 (NW), hw4's and hw3's families; mini (16 lanes)
+//                                             CODED | GAP0 (NW)
+//   setup_gotoh_mini                          BAND_NONE, WALK_NONE, KEYED on the gotoh classes
+//   affine_tb_on_stripes (pwalign_affine_tb.hip)   RL = 4, W = 1 | 4
+const std::vector<PairForm>& pair_form_listing() {
+    static const uint32_t tab_word = 0;
+    static const std::vector<PairForm> listing = [] {
+        const SubstRef tab{&tab_word, 1, 1};
+        const std::vector<PairGeom> stripe = {{2, 1}, {2, 4}, {4, 1}, {4, 4}};
+        std::vector<PairGeom> mini16, mini, gotoh;
+        for (const int rl : kMiniRL) mini16.push_back({rl, 16});
+        mini = gotoh = mini16;
+        for (const int rl : {6, 8, 12, 16}) mini.push_back({rl, 64});   // (wide_rl_for)
+        for (const int rl : {8, 16}) gotoh.push_back({rl, 64});         // (TbPlan::class_of, setup_gotoh_mini)
+        std::vector<PairForm> v;
+        auto add = [&](PairFamily fam, int mode, PairBand band, int walk, PairCells cells, PairGeom g) {
+            v.push_back(PairForm{fam, mode, band, walk, cells, g.rl, g.w, fam == PF_MINI_SUBST ? tab : SubstRef{}});
+        };
+        for (const int mode : {PWA_MODE_NW, PWA_MODE_SW, PWA_MODE_SG}) {
+            const bool nw = mode == PWA_MODE_NW;
+            for (const PairGeom g : stripe)   // setup_off_strips
+                for (const PairCells c : {CELLS_PLAIN, CELLS_CODED, CELLS_GAP0})
+                    if (c != CELLS_GAP0 || nw) add(PF_STRIPE_FILL, mode, BAND_NONE, WALK_NONE, c, g);
+            for (const PairGeom g : mini16)
+                for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
+                    if (c != CELLS_GAP0 || nw) add(PF_MINI_FILL, mode, BAND_NONE, WALK_NONE, c, g);
+            for (const PairBand band : {BAND_TB, BAND_TB_SCORES})   // run_launch
+                for (const int walk : {WALK_OPS, WALK_OVERLAP}) {
+                    if (walk == WALK_OVERLAP && mode == PWA_MODE_SG) continue;
+                    for (const PairGeom g : stripe)
+                        for (const PairCells c : {CELLS_PLAIN, CELLS_KEYED, CELLS_CODED, CELLS_GAP0})
+                            if ((c != CELLS_PLAIN || g.rl == 4) && (c != CELLS_GAP0 || (nw && band == BAND_TB))) add(PF_STRIPE_FILL, mode, band, walk, c, g);
+                    for (const PairGeom g : mini)
+                        for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
+                            if (c != CELLS_GAP0 || (nw && band == BAND_TB)) add(PF_MINI_FILL, mode, band, walk, c, g);
+                }
+            for (const PairGeom g : stripe)   // pwa_align_matrices
+                for (const PairCells c : {CELLS_PLAIN, CELLS_KEYED})
+                    if (c != CELLS_PLAIN || g.rl == 4) add(PF_STRIPE_FILL, mode, BAND_TB_SCORES, WALK_NONE, c, g);
+            for (const PairGeom g : mini) add(PF_MINI_FILL, mode, BAND_TB_SCORES, WALK_NONE, CELLS_CODED, g);
+            for (const PairGeom g : gotoh)   // setup_gotoh_mini, run_launch
+                for (const PairFamily fam : {PF_MINI_GOTOH, PF_MINI_SUBST}) {
+                    add(fam, mode, BAND_NONE, WALK_NONE, CELLS_KEYED, g);
+                    add(fam, mode, BAND_TB, WALK_OPS, CELLS_KEYED, g);
+                }
+        }
+        for (const PairGeom g : stripe) {   // setup_off_strips (hw4, hw3), affine_tb_on_stripes
+            add(PF_STRIPE_DIST, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
+            add(PF_STRIPE_AFFINE, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
+            if (g.rl == 4) add(PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, g);
+        }
+        return v;
+    }();
+    return listing;
+}
+
+// build() / build_mini(): the resolved form into the context's record (pwa_pair_forms)
+static void note_pair_form(pwa_ctx* ctx, const PairForm& f) {
+    std::string name = pair_form_name(f);
+    if (std::find(ctx->pair_forms.begin(), ctx->pair_forms.end(), name) != ctx->pair_forms.end()) return;
+    if (ctx->pair_forms.size() < pair_form_listing().size()) ctx->pair_forms.push_back(std::move(name));   // (bounded by the listing's size)
+}
+
 // ---- PairLaunch (pwalign_internal.h)
 int PairLaunch::upload_desc(pwa_ctx* ctx, const std::vector<PairDesc>& pd) {
     const size_t bytes = pd.size() * sizeof(PairDesc);
@@ -541,6 +618,7 @@ void PairLaunch::set_params(uint32_t n_pairs, uint32_t n_tasks, int match, int m
 int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, const PairForm& f, int match, int mismatch, int gap, int gap_extend) {
     if (f.mini() || !resolve_pair_form(f, k)) return fail(ctx, PWA_E_INVALID, "internal: no stripe kernel for this form");
     form = f;
+    note_pair_form(ctx, f);
     const uint64_t vals = f.family == PF_STRIPE_FILL ? 1 : 2;   // int32 values per hand-off column
     const uint64_t rows_per_stripe = 64ull * f.rl;
     std::vector<StripeTask> tl;
@@ -593,6 +671,7 @@ int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, const PairForm& f
 int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_real, const PairForm& f, int match, int mismatch, int gap) {
     if (!f.mini() || !resolve_pair_form(f, k)) return fail(ctx, PWA_E_INVALID, "internal: no mini-stripe kernel for this form");
     form = f;
+    note_pair_form(ctx, f);
     const size_t ppw = (size_t)(64 / f.w);   // pairs per wave: 4, or 1 (one pair per wave: 512- / 1024-row single stripes)
     if (pd.empty() || pd.size() % ppw || pd.size() >= 0xffffffffull || n_real > pd.size() || n_real + ppw - 1 < pd.size())
         return fail(ctx, PWA_E_INVALID, "internal: mini-stripe task list");
@@ -778,54 +857,31 @@ uint64_t layout_arena(const uint64_t* seq_off, uint32_t n_seq, const std::vector
 
 }  // namespace pwa
 
-// pwa_selftest_host: every form the seven call sites of PairLaunch can build resolves to kernels -- each family at every geometry its
-// planner chooses, in every mode, band and walk it combines them with -- and a list of forms that mean nothing is refused.  (Kernel host
-// stubs have addresses without a device.)
+// pwa_selftest_host: every form the seven call sites of PairLaunch can build (pair_form_listing) resolves to kernels; so do the forms
+// with a band and no walk that no call site asks for (pwa_align_matrices builds a few of them: those are listed); and a list of forms
+// that mean nothing is refused.  (Kernel host stubs have addresses without a device.)
 static int selftest_pair_forms() {
     static const uint32_t tab_word = 0;
     const SubstRef tab{&tab_word, 1, 1};
-    const std::vector<PairGeom> stripe = {{2, 1}, {2, 4}, {4, 1}, {4, 4}}, wide = {{6, 64}, {8, 64}, {12, 64}, {16, 64}};
-    std::vector<PairGeom> mini16, mini, gotoh;
-    for (const int rl : kMiniRL) mini16.push_back({rl, 16});
-    mini = gotoh = mini16;
-    mini.insert(mini.end(), wide.begin(), wide.end());   // (wide_rl_for)
-    gotoh.insert(gotoh.end(), {{8, 64}, {16, 64}});      // (TbPlan::class_of, setup_gotoh_mini)
+    const std::vector<PairGeom> stripe = {{2, 1}, {2, 4}, {4, 1}, {4, 4}};
+    std::vector<PairGeom> mini;
+    for (const int rl : kMiniRL) mini.push_back({rl, 16});
+    for (const int rl : {6, 8, 12, 16}) mini.push_back({rl, 64});   // (wide_rl_for)
     int bad = 0;
     PairKernels k;
+    for (const PairForm& f : pair_form_listing()) bad += !resolve_pair_form(f, k);
     auto must = [&](PairFamily fam, int mode, PairBand band, int walk, PairCells cells, PairGeom g) {
-        bad += !resolve_pair_form(PairForm{fam, mode, band, walk, cells, g.rl, g.w, fam == PF_MINI_SUBST ? tab : SubstRef{}}, k);
+        bad += !resolve_pair_form(PairForm{fam, mode, band, walk, cells, g.rl, g.w}, k);
     };
-    for (const int mode : {PWA_MODE_NW, PWA_MODE_SW, PWA_MODE_SG}) {
-        const bool nw = mode == PWA_MODE_NW;
-        // score batches (setup_off_strips, setup_gotoh_mini): no band, the end-cell pick
-        for (const PairGeom g : stripe)
-            for (const PairCells c : {CELLS_PLAIN, CELLS_CODED, CELLS_GAP0})
-                if (c != CELLS_GAP0 || nw) must(PF_STRIPE_FILL, mode, BAND_NONE, WALK_NONE, c, g);
-        for (const PairGeom g : mini16)
-            for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
-                if (c != CELLS_GAP0 || nw) must(PF_MINI_FILL, mode, BAND_NONE, WALK_NONE, c, g);
-        // alignment batches (run_launch: op or overlap walks; pwa_align_matrices: both bands, no walk)
-        for (const PairBand band : {BAND_TB, BAND_TB_SCORES})
-            for (const int walk : {WALK_NONE, WALK_OPS, WALK_OVERLAP}) {
-                if (walk == WALK_OVERLAP && mode == PWA_MODE_SG) continue;   // (validate_align)
-                for (const PairGeom g : stripe)
-                    for (const PairCells c : {CELLS_PLAIN, CELLS_KEYED, CELLS_CODED, CELLS_GAP0})
-                        if ((c != CELLS_PLAIN || g.rl == 4) && (c != CELLS_GAP0 || (nw && band == BAND_TB))) must(PF_STRIPE_FILL, mode, band, walk, c, g);
-                for (const PairGeom g : mini)
-                    for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
-                        if (c != CELLS_GAP0 || (nw && band == BAND_TB)) must(PF_MINI_FILL, mode, band, walk, c, g);
-            }
-        for (const PairGeom g : gotoh)
-            for (const PairFamily fam : {PF_MINI_GOTOH, PF_MINI_SUBST}) {
-                must(fam, mode, BAND_NONE, WALK_NONE, CELLS_KEYED, g);
-                must(fam, mode, BAND_TB, WALK_OPS, CELLS_KEYED, g);
-            }
-    }
-    for (const PairGeom g : stripe) {   // hw4 / hw3 (setup_off_strips; pwalign_affine_tb.hip: RL = 4)
-        must(PF_STRIPE_DIST, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
-        must(PF_STRIPE_AFFINE, PWA_MODE_NW, BAND_NONE, WALK_NONE, CELLS_PLAIN, g);
-        if (g.rl == 4) must(PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, g);
-    }
+    for (const int mode : {PWA_MODE_NW, PWA_MODE_SW, PWA_MODE_SG})   // a band, the end-cell pick only: every cell form, either band
+        for (const PairBand band : {BAND_TB, BAND_TB_SCORES}) {
+            for (const PairGeom g : stripe)
+                for (const PairCells c : {CELLS_PLAIN, CELLS_KEYED, CELLS_CODED, CELLS_GAP0})
+                    if ((c != CELLS_PLAIN || g.rl == 4) && (c != CELLS_GAP0 || (mode == PWA_MODE_NW && band == BAND_TB))) must(PF_STRIPE_FILL, mode, band, WALK_NONE, c, g);
+            for (const PairGeom g : mini)
+                for (const PairCells c : {CELLS_CODED, CELLS_GAP0})
+                    if (c != CELLS_GAP0 || (mode == PWA_MODE_NW && band == BAND_TB)) must(PF_MINI_FILL, mode, band, WALK_NONE, c, g);
+        }
     if (bad) return 1;
     const PairForm none[] = {
         {PF_MINI_GOTOH, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_KEYED, 4, 4},             // a gotoh family with stripe geometry
@@ -869,6 +925,44 @@ static int selftest_pair_forms() {
     };
     for (const PairForm& f : none)
         if (resolve_pair_form(f, k)) return 2;
+    return 0;
+}
+
+// ... and that the listing's forms resolve to the RIGHT number of kernels: no form twice (1); two forms that differ in a field the fill
+// depends on -- anything but the walk -- have different fills (2); the walk is a function of (engine class, rl, lanes, mode, walk)
+// alone (3) and differs whenever one of the five does (4).  Engine class: the stripe fills, hw3's alignment, the mini-stripe fills, the
+// gotoh kernels (whose walk the subst family shares); a stripe walk is one wave per pair whatever W is: 64 lanes.
+static int selftest_pair_listing() {
+    struct Key {
+        int a[6];
+        bool operator<(const Key& o) const { return std::lexicographical_compare(a, a + 6, o.a, o.a + 6); }
+        bool operator==(const Key& o) const { return std::equal(a, a + 6, o.a); }
+    };
+    std::vector<std::pair<Key, const void*>> fills, walks;
+    std::vector<std::string> names;
+    PairKernels k;
+    for (const PairForm& f : pair_form_listing()) {
+        if (!resolve_pair_form(f, k)) return 1;
+        names.push_back(pair_form_name(f));
+        fills.push_back({Key{{f.family, f.mode, f.band, f.cells, f.rl, f.w}}, k.sfill ? reinterpret_cast<const void*>(k.sfill) : reinterpret_cast<const void*>(k.fill)});
+        if (!k.walks) continue;
+        const int cls = f.family == PF_STRIPE_FILL ? 0 : f.family == PF_STRIPE_AFFINE_TB ? 1 : f.family == PF_MINI_FILL ? 2 : 3;
+        walks.push_back({Key{{cls, f.rl, f.mini() ? f.w : 64, f.mode, f.walk, 0}}, reinterpret_cast<const void*>(k.walk)});
+    }
+    std::sort(names.begin(), names.end());
+    if (names.empty() || std::adjacent_find(names.begin(), names.end()) != names.end()) return 1;
+    // sorted by key, then by pointer: equal keys are neighbours; sorted by pointer: equal pointers are
+    int at = 2;
+    for (auto* v : {&fills, &walks}) {
+        std::sort(v->begin(), v->end());
+        for (size_t i = 1; i < v->size(); ++i)
+            if ((*v)[i].first == (*v)[i - 1].first && (*v)[i].second != (*v)[i - 1].second) return v == &fills ? 1 : 3;   // (a fill key twice is a form twice)
+        v->erase(std::unique(v->begin(), v->end()), v->end());
+        std::sort(v->begin(), v->end(), [](const auto& x, const auto& y) { return x.second < y.second; });
+        for (size_t i = 1; i < v->size(); ++i)
+            if ((*v)[i].second == (*v)[i - 1].second) return at;
+        at = 4;
+    }
     return 0;
 }
 
@@ -1015,9 +1109,43 @@ int pwa_selftest_host(uint32_t seed) try {
     if (const int rc = selftest_pair_forms()) return check + rc;
     if (const int rc = selftest_banded_forms()) return check + 2 + rc;
     if (const int rc = selftest_align_plan(x, check + 5)) return rc;
-    return selftest_wfa_plan(x, check + 11);
+    if (const int rc = selftest_wfa_plan(x, check + 11)) return rc;
+    if (const int rc = selftest_pair_listing()) return check + 16 + rc;   // (the wavefront planner's checks end at check + 16)
+    return 0;
 } catch (...) {
     return -1;
+}
+
+int pwa_pair_form_table(uint32_t index, const char** name, uint32_t* count) try {
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v;
+        for (const PairForm& f : pair_form_listing()) v.push_back(pair_form_name(f));
+        return v;
+    }();
+    if (count) *count = (uint32_t)names.size();
+    if (index >= names.size()) return PWA_E_INVALID;
+    if (name) *name = names[index].c_str();
+    return PWA_OK;
+} catch (...) {
+    return PWA_E_NOMEM;
+}
+
+int pwa_pair_forms(const pwa_ctx* ctx, char* buf, uint64_t cap, uint64_t* needed) try {
+    if (!ctx) return PWA_E_INVALID;
+    std::string s;
+    for (const std::string& n : ctx->pair_forms) s += (s.empty() ? "" : "\n") + n;
+    if (needed) *needed = s.size() + 1;
+    if (!buf || cap < s.size() + 1) return PWA_E_CAPACITY;
+    std::memcpy(buf, s.c_str(), s.size() + 1);
+    return PWA_OK;
+} catch (...) {
+    return PWA_E_NOMEM;
+}
+
+int pwa_pair_forms_reset(pwa_ctx* ctx) {
+    if (!ctx) return PWA_E_INVALID;
+    ctx->pair_forms.clear();
+    return PWA_OK;
 }
 
 const char* pwa_strerror(int code) {

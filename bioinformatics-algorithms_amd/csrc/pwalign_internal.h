@@ -129,6 +129,9 @@ struct pwa_ctx {
     pwa::ApproxStartsStats approx_starts_stats;   // the last pwa_approx_starts
     pwa::WfaStats wfa_stats;               // the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
+    // pwa_pair_forms: pair_form_name of every form PairLaunch::build / build_mini resolved on this context (a batch object's launches:
+    // on the context that created it), distinct, in first-seen order; only pwa_pair_forms_reset empties it
+    std::vector<std::string> pair_forms;
     // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
     // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the
     // device's memory, and a caller that aligns batch after batch should pay it once.
@@ -333,6 +336,12 @@ struct PairForm {
     SubstRef subst = {};   // PF_MINI_SUBST only
     bool mini() const { return family >= PF_MINI_FILL; }
 };
+// family/mode/band/walk/cells/rl<n>/w<n> (mini families: ln<n>), e.g. stripe_fill/NW/tb/ops/coded/rl2/w4: the only place a form becomes a
+// name (pwa_pair_forms, pwa_pair_form_table); a field outside its enum reads "?"
+std::string pair_form_name(const PairForm& f);
+// The forms the seven call sites of PairLaunch can build, each once (DESIGN.md 3.23 derives the list from their expressions); the
+// PF_MINI_SUBST entries carry a one-word host table, enough for resolve_pair_form.  pwa_selftest_host and pwa_pair_form_table walk it.
+const std::vector<PairForm>& pair_form_listing();
 typedef void (*subst_kernel_t)(const PairParams, const uint32_t*, int, int);
 struct PairKernels {
     pair_kernel_t fill = nullptr, walk = nullptr;   // the fill, `block` threads per workgroup; the walk, one wave per pair, when `walks`

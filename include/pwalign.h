@@ -108,8 +108,9 @@ const char *pwa_strerror(int code);
  * sort, the radix sort) on pseudo-random lists against std::stable_sort, and the range planner of the alignment batches (classes,
  * ranges, wave tasks, band layout) on pseudo-random length lists with made-up free-memory figures against the properties every plan
  * must have; the parser of PWA_POISON's value on a list of good and bad spellings; the cutting of a list into runs under a budget
- * (chunks of patterns, slices of tasks, ranges of WFA pairs) on its edge cases and on random lists.  Returns 0, or the number of the
- * first check that failed. */
+ * (chunks of patterns, slices of tasks, ranges of WFA pairs) on its edge cases and on random lists; that every form of
+ * pwa_pair_form_table resolves to kernels, to a fill of its own wherever a field the fill depends on differs, and to a walk that
+ * follows from engine class, rows per lane, lanes, mode and walk alone.  Returns 0, or the number of the first check that failed. */
 int pwa_selftest_host(uint32_t seed);
 
 /* Context = one GPU (HIP device ordinal) + its streams and workspaces. */
@@ -202,6 +203,22 @@ int pwa_profile_plan(uint32_t min_text_len, uint32_t max_text_len, uint32_t *int
 #define PWA_STRIP_PROF16 32u       /* ... their profile form */
 #define PWA_STRIP_PROF16_INT 64u   /* ... with the integer-coded row */
 int pwa_strip_table(uint32_t index, const char **name, int *rows, int *mode, int *score_path, uint32_t *variants, uint32_t *count);
+/* The stripe and mini-stripe ("pair") engine's launches by name.  A launch of that engine is one value -- family, mode, band, walk,
+ * cell form, rows per lane, compute waves (stripe families) or lanes per pair (mini families) -- and its name spells the seven fields:
+ *   family/mode/band/walk/cells/rl<n>/w<n>      stripe_fill | stripe_dist | stripe_affine | stripe_affine_tb
+ *   family/mode/band/walk/cells/rl<n>/ln<n>     mini_fill | mini_gotoh | mini_subst
+ * with mode NW | SW | SG, band none | tb | tb+scores, walk none | ops | overlap, cells plain | keyed | coded | gap0; for example
+ * stripe_fill/NW/tb/ops/coded/rl2/w4 or mini_subst/SG/none/none/keyed/rl16/ln64.
+ * pwa_pair_form_table (host only, no context): entry `index` of the list of forms the library's call sites can build, and the number
+ * of entries in *count (written whatever the index; any output pointer may be NULL).  PWA_E_INVALID when index >= *count.
+ * pwa_pair_forms: the names of the forms this context has prepared launches of since the last pwa_pair_forms_reset -- distinct, in
+ * first-seen order, joined by '\n', NUL-terminated.  A batch object's launches are prepared by its create call and count on the
+ * context that created it.  *needed receives the size required (PWA_E_CAPACITY when cap is too small; call with cap = 0 to size the
+ * buffer).  Nothing but pwa_pair_forms_reset empties the record, so a test brackets exactly the call it means; it never holds more
+ * names than the table has entries.  For tests that want to reach every instantiation by name. */
+int pwa_pair_form_table(uint32_t index, const char **name, uint32_t *count);
+int pwa_pair_forms(const pwa_ctx *ctx, char *buf, uint64_t cap, uint64_t *needed);
+int pwa_pair_forms_reset(pwa_ctx *ctx);
 /* Device time of the most recent pwa_batch_run in ms (HIP events on the run's stream); the call
  * synchronises the run. */
 int pwa_batch_last_ms(pwa_batch *b, float *ms);
