@@ -47,11 +47,13 @@ EXPORTS = [
     "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
     "pwa_align_wfa_codes_batch_cigar", "pwa_wfa_last_stats",
     "pwa_wfa_sg_plan", "pwa_scores_wfa_sg", "pwa_align_wfa_sg_batch", "pwa_align_wfa_sg_batch_cigar",
+    "pwa_chain_plan", "pwa_chain_anchors", "pwa_chain_last_stats",
 ]
 
 
 APPROX_NO_START = 0xffffffff   # PWA_APPROX_NO_START
 WFA_NONE = -(1 << 31)          # PWA_WFA_NONE: score_out of a pair the bound leaves out
+CHAIN_NO_READ = 0xffffffff     # last_out of a read without anchors; pwa_chain_plan's bad_read when no read is at fault
 
 
 class PwaError(RuntimeError):
@@ -109,6 +111,46 @@ def wfa_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
 def wfa_sg_plan(match, mismatch, gap_open, gap_extend, lengths, min_score=None):
     """pwa_wfa_sg_plan (host only): wfa_plan for the semi-global form -> dict(pen=(x, o, eI, eD, g), p_max=[...], cells=[...])."""
     return _wfa_plan("pwa_wfa_sg_plan", 5, match, mismatch, gap_open, gap_extend, lengths, min_score)
+
+
+def _anchor_arrays(anchors):
+    """anchors per read ((t, q, len) triples: lists of tuples, or arrays of shape (n, 3)) -> the uint32 arrays t, q, len and the uint64
+    offsets of the chain calls, C-contiguous"""
+    import numpy as np
+    per = [np.asarray(a, dtype=np.int64).reshape(-1, 3) for a in anchors]
+    off = np.zeros(len(per) + 1, dtype=np.uint64)
+    if per:
+        off[1:] = np.cumsum([len(a) for a in per])
+    flat = np.concatenate(per) if per else np.zeros((0, 3), dtype=np.int64)
+    if flat.size and (flat.min() < 0 or flat.max() > 0xffffffff):
+        raise ValueError("anchors: t, q and len are uint32 values")
+    cols = [np.ascontiguousarray(flat[:, c], dtype=np.uint32) for c in range(3)]
+    cols = [c if c.size else np.zeros(1, dtype=np.uint32) for c in cols]
+    return cols[0], cols[1], cols[2], off
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def chain_plan(anchors, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38, budget=0):
+    """pwa_chain_plan (host only): what Context.chain would answer to these anchors and parameters before any device work ->
+    dict(code, bad_read, ranges): the validation code (0, or a negative PWA_E_* value), the first offending read (None: none, or a
+    parameter was at fault), the ranges of reads the call would run under `budget` bytes (0: no limit)."""
+    L = lib()
+    t, q, ln, off = _anchor_arrays(anchors)
+    bad, nr = C.c_uint32(0), C.c_uint64(0)
+    rc = L.pwa_chain_plan(_u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), len(off) - 1, lookback, max_dist, bandwidth,
+                          gap_scale, budget, C.byref(bad), C.byref(nr))
+    return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, ranges=nr.value)
+
+
+_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def revcomp(seq):
+    """The reverse complement of a sequence: A <-> T and C <-> G in either case, every other byte unchanged."""
+    return _b(seq).translate(_COMPLEMENT)[::-1]
 
 
 def approx_minima(hits, pat_len, k, n):
@@ -337,6 +379,10 @@ def lib():
     L.pwa_scores_wfa_sg.argtypes = wfa_in + [i32p, i32p, u32p, u64p]   # ..., min_score, score, penalty, end_j
     L.pwa_align_wfa_sg_batch.argtypes = wfa_in + [i32p, vp, u64p, u64p, u64p, u64p, i32p]   # ..., score, ops, ops_off, n_ops, end, start, min_score
     L.pwa_align_wfa_sg_batch_cigar.argtypes = wfa_in + [i32p, vp, C.c_uint64, u64p, vp, C.c_uint64, u64p, u64p, u64p, u64p, i32p]
+    chain_in = [u32p, u32p, u32p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]   # anchors, offsets, reads, the four parameters
+    L.pwa_chain_plan.argtypes = chain_in + [C.c_uint64, u32p, u64p]
+    L.pwa_chain_anchors.argtypes = [vp] + chain_in + [i32p, u32p, u32p, u32p, i32p, i32p, i32p]
+    L.pwa_chain_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p, u64p]
     _lib = L
     return L
 
@@ -1294,6 +1340,142 @@ class Context:
         for pl in placed:
             out.append([dict(start=s, end=e, dist=d, score=a["score"], cigar=a["cigar"], mdz=a["mdz"]) for (s, e, d), a in zip(pl, al[at:at + len(pl)])])
             at += len(pl)
+        return out
+
+    # -- from seeds to placements: seeding on the suffix array, collinear chaining (include/pwalign.h, pwa_chain_*), banded alignment
+    def chain(self, anchors, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38, want_dp=False):
+        """pwa_chain_anchors: the best collinear chain of every read's anchors.  anchors: per read its (t, q, len) triples in
+        non-decreasing order of (t + len, q + len) -> per read dict(score, count, last, q_begin, q_end, t_begin, t_end, diag_lo,
+        diag_hi), and with want_dp the whole DP as lists f and pred (local indices).  A read without anchors: score 0, count 0,
+        last None.  Sets chain_stats = dict(chain_ms, anchors, ranges)."""
+        import numpy as np
+        t, q, ln, off = _anchor_arrays(anchors)
+        n = len(off) - 1
+        sc = np.zeros(max(n, 1), dtype=np.int32)
+        cnt, last, span = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(4 * max(n, 1), dtype=np.uint32)
+        diag = np.zeros(2 * max(n, 1), dtype=np.int32)
+        tot = int(off[n])
+        f = np.zeros(max(tot, 1), dtype=np.int32) if want_dp else None
+        pr = np.zeros(max(tot, 1), dtype=np.int32) if want_dp else None
+        i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self._L.pwa_chain_anchors(self._h, _u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), n, lookback, max_dist,
+                                       bandwidth, gap_scale, i32(sc), _u32p(cnt), _u32p(last), _u32p(span), i32(diag), i32(f), i32(pr))
+        self._check(rc, "pwa_chain_anchors")
+        ms, na, nr = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_chain_last_stats(self._h, C.byref(ms), C.byref(na), C.byref(nr)), "pwa_chain_last_stats")
+        self.chain_stats = dict(chain_ms=ms.value, anchors=na.value, ranges=nr.value)
+        sc, cnt, last, span, diag, o = sc.tolist(), cnt.tolist(), last.tolist(), span.tolist(), diag.tolist(), off.tolist()
+        out = []
+        for r in range(n):
+            d = dict(score=sc[r], count=cnt[r], last=None if last[r] == CHAIN_NO_READ else last[r], q_begin=span[4 * r], q_end=span[4 * r + 1],
+                     t_begin=span[4 * r + 2], t_end=span[4 * r + 3], diag_lo=diag[2 * r], diag_hi=diag[2 * r + 1])
+            if want_dp:
+                d["f"] = f[o[r]:o[r + 1]].tolist()
+                d["pred"] = pr[o[r]:o[r + 1]].tolist()
+            out.append(d)
+        return out
+
+    def seed(self, text, reads, k, step=1, max_occ=64, as_arrays=False):
+        """Exact k-mer anchors of every read in the text: one suffix-array index of the text per call, the k-mers read[q:q + k] at
+        q = 0, step, 2 step, ... through pwa_sa_find and pwa_sa_occurrences; a k-mer with more than max_occ occurrences is dropped.
+        -> per read its anchors (t, q, k) in the order chain() requires (by t, then q), as a list of tuples, or with as_arrays as a
+        uint32 array of shape (n, 3)."""
+        import numpy as np
+        if k < 1 or step < 1 or max_occ < 1:
+            raise ValueError("seed: k, step and max_occ are at least 1")
+        text = _b(text)
+        reads = [_b(r) for r in reads]
+        n = len(text)
+        qs = [np.arange(0, len(r) - k + 1, step, dtype=np.int64) if len(r) >= k else np.zeros(0, dtype=np.int64) for r in reads]
+        n_pat = int(sum(len(a) for a in qs))
+        empty = np.zeros((0, 3), dtype=np.uint32)
+        if not n_pat or n < k:
+            return [empty.copy() if as_arrays else [] for _ in reads]
+        pat_read = np.repeat(np.arange(len(reads), dtype=np.int64), [len(a) for a in qs])
+        pat_q = np.concatenate(qs)
+        kmers = np.concatenate([np.lib.stride_tricks.sliding_window_view(np.frombuffer(r, dtype=np.uint8), k)[::step].reshape(-1)
+                                for r in reads if len(r) >= k])
+        u64p = C.POINTER(C.c_uint64)
+        # the index takes a text whose last byte is its terminator: one is appended, and a hit that runs into it is dropped below
+        ix = self._sa_index(text + b"\0")
+        try:
+            off = np.arange(n_pat + 1, dtype=np.uint64) * np.uint64(k)
+            cnt = np.zeros(n_pat, dtype=np.uint32)
+            self._check(self._L.pwa_sa_find(ix, kmers.ctypes.data_as(C.c_void_p), off.ctypes.data_as(u64p), n_pat, _u32p(cnt)), "pwa_sa_find")
+            keep = np.flatnonzero((cnt > 0) & (cnt <= max_occ + 1))   # + 1: the one hit the terminator can add
+            if not keep.size:
+                return [empty.copy() if as_arrays else [] for _ in reads]
+            sub = np.ascontiguousarray(kmers.reshape(n_pat, k)[keep]).reshape(-1)
+            sub_off = np.arange(keep.size + 1, dtype=np.uint64) * np.uint64(k)
+            cap = int(cnt[keep].sum())
+            occ_off = np.zeros(keep.size + 1, dtype=np.uint64)
+            occ = np.zeros(max(cap, 1), dtype=np.uint64)
+            rs, hr, need = (C.c_uint32 * 2)(0, n + 1), (C.c_uint32 * 1)(0), C.c_uint64(0)
+            self._check(self._L.pwa_sa_occurrences(ix, sub.ctypes.data_as(C.c_void_p), sub_off.ctypes.data_as(u64p), keep.size, rs, 1, hr,
+                                                   occ_off.ctypes.data_as(u64p), occ.ctypes.data_as(u64p), cap, C.byref(need)), "pwa_sa_occurrences")
+            self._sa_stats(ix)
+        finally:
+            self._L.pwa_sa_destroy(ix)
+        per = np.diff(occ_off.astype(np.int64))
+        hit_pat = np.repeat(np.arange(keep.size, dtype=np.int64), per)
+        t = (occ[:int(occ_off[-1])] & np.uint64(0xffffffff)).astype(np.int64)
+        inside = t + k <= n
+        hit_pat, t = hit_pat[inside], t[inside]
+        few = np.bincount(hit_pat, minlength=keep.size) <= max_occ
+        sel = few[hit_pat]
+        hit_pat, t = keep[hit_pat[sel]], t[sel]
+        r, q = pat_read[hit_pat], pat_q[hit_pat]
+        order = np.lexsort((q, t, r))
+        r, q, t = r[order], q[order], t[order]
+        trip = np.stack([t, q, np.full(t.size, k, dtype=np.int64)], axis=1).astype(np.uint32)
+        cut = np.searchsorted(r, np.arange(len(reads) + 1))
+        if as_arrays:
+            return [trip[cut[i]:cut[i + 1]] for i in range(len(reads))]
+        rows = trip.tolist()
+        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(len(reads))]
+
+    def map_reads(self, text, reads, k, match, mismatch, gap_open, gap_extend, w=100, step=1, max_occ=64, both_strands=False, lookback=64,
+                  max_dist=5000, bandwidth=500, gap_scale=38):
+        """Seed, chain, align: seed() of every read (with both_strands also of its reverse complement; the strand with the higher
+        chain score is kept, ties go forward), chain() of the anchors, then align_banded_batch_cigar("sg", ...) of the read against
+        the text window [max(0, t_begin - q_begin - w), min(len(text), t_end + (n - q_end) + w)) in the band (diag_lo - window start -
+        w, diag_hi - window start + w).  -> per read dict(pos, end, score, cigar, mdz, strand, chain_score) in text coordinates
+        (strand '+' or '-'; cigar and mdz are of the aligned strand), or None for a read without a chain, or whose band is wider than
+        the banded call's 4096 or fails its semi-global validity rule.  Sets map_stats = dict(seed_s, chain_s, align_s): wall seconds."""
+        import time
+        text = _b(text)
+        fw = [_b(r) for r in reads]
+        nr = len(fw)
+        strands = [fw, [revcomp(r) for r in fw]] if both_strands else [fw]
+        t0 = time.perf_counter()
+        anchors = self.seed(text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+        t1 = time.perf_counter()
+        chains = self.chain(anchors, lookback, max_dist, bandwidth, gap_scale)
+        t2 = time.perf_counter()
+        pats, wins, bands, placed = [], [], [], []   # placed: (read, strand, window start, chain score)
+        for i in range(nr):
+            s = 1 if both_strands and chains[nr + i]["score"] > chains[i]["score"] else 0
+            c = chains[s * nr + i]
+            if not c["count"]:
+                continue
+            n = len(fw[i])
+            ws = max(0, c["t_begin"] - c["q_begin"] - w)
+            we = min(len(text), c["t_end"] + (n - c["q_end"]) + w)
+            lo, hi = c["diag_lo"] - ws - w, c["diag_hi"] - ws + w
+            if hi - lo + 1 > 4096 or hi < 0 or n + lo > we - ws:
+                continue
+            pats.append(strands[s][i])
+            wins.append(text[ws:we])
+            bands.append((lo, hi))
+            placed.append((i, "+-"[s], ws, c["score"]))
+        np_ = len(pats)
+        al = self.align_banded_batch_cigar("sg", pats + wins, list(range(np_)), list(range(np_, 2 * np_)), match, mismatch, gap_open, gap_extend,
+                                           bands) if np_ else []
+        t3 = time.perf_counter()
+        self.map_stats = dict(seed_s=t1 - t0, chain_s=t2 - t1, align_s=t3 - t2)
+        out = [None] * nr
+        for (i, strand, ws, cs), a in zip(placed, al):
+            out[i] = dict(pos=ws + a["start"][1], end=ws + a["end"][1], score=a["score"], cigar=a["cigar"], mdz=a["mdz"], strand=strand, chain_score=cs)
         return out
 
 

@@ -126,6 +126,14 @@ pwa::WfaCtxView pwa::wfa_ctx_view(pwa_ctx* c) {
 }
 const pwa::WfaStats& pwa::wfa_stats_of(const pwa_ctx* c) { return c->wfa_stats; }
 
+pwa::ChainCtxView pwa::chain_ctx_view(pwa_ctx* c) {
+    ChainCtxView v{unit_ctx(c)};
+    v.range_bytes = c->knobs.range_bytes;
+    v.stats = &c->chain_stats;
+    return v;
+}
+const pwa::ChainStats& pwa::chain_stats_of(const pwa_ctx* c) { return c->chain_stats; }
+
 hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_t* table) {
     if (!n16) return hipSuccess;
     RecodeTable rt;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "approx_ctx.h"
+#include "chain_ctx.h"
 #include "kernel_table.h"
 #include "poison.h"
 #include "subst_table.h"
@@ -128,6 +129,7 @@ struct pwa_ctx {
     pwa::ApproxStats approx_stats;         // the last pwa_approx_find / pwa_approx_occurrences
     pwa::ApproxStartsStats approx_starts_stats;   // the last pwa_approx_starts
     pwa::WfaStats wfa_stats;               // the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
+    pwa::ChainStats chain_stats;           // the last pwa_chain_anchors
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // pwa_pair_forms: pair_form_name of every form PairLaunch::build / build_mini resolved on this context (a batch object's launches:
     // on the context that created it), distinct, in first-seen order; only pwa_pair_forms_reset empties it

@@ -1,5 +1,5 @@
 // side_unit.h -- the host kit of the units that stay away from pwalign_internal.h (sufarr_kernels.hip, approx_kernels.hip,
-// wfa_kernels.hip): what each needs of a pwa_ctx, an owned device allocation, timing events, the error path from a HIP call to the
+// wfa_kernels.hip, chain_kernels.hip): what each needs of a pwa_ctx, an owned device allocation, timing events, the error path from a HIP call to the
 // entry point's return code, and the cutting of a list into runs under a budget.  Nothing here is exported.  DESIGN.md §3.21 ("The side units' host kit").
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@
 
 #pragma GCC visibility push(hidden)
 namespace pwa {
-// What every side unit reads of a context; a unit's own view (sufarr_ctx.h, approx_ctx.h, wfa_ctx.h) adds its knobs and stats
+// What every side unit reads of a context; a unit's own view (sufarr_ctx.h, approx_ctx.h, wfa_ctx.h, chain_ctx.h) adds its knobs and stats
 struct UnitCtx {
     int device = 0;
     hipStream_t stream = nullptr;

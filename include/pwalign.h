@@ -994,6 +994,49 @@ int pwa_align_wfa_sg_batch_cigar(pwa_ctx *ctx, int match, int mismatch, int gap_
                                  uint64_t *end_cells /* 2 * n_pairs or NULL */, uint64_t *start_cells /* 2 * n_pairs or NULL */,
                                  uint64_t needed[2] /* or NULL */, const int32_t *min_score /* or NULL */);
 
+/* ---- Collinear chaining of anchors: the DP between seeding and extension of a read mapper
+ *
+ * Anchors.  An anchor of read r is (t, q, len) with len >= 1 and claims read[q .. q + len) == text[t .. t + len); the call never looks
+ * at sequences, an anchor may come from anywhere.  Read r's anchors are entries anc_off[r] .. anc_off[r + 1]) of the three parallel
+ * arrays anc_t, anc_q, anc_len.  x = t + len and y = q + len are the exclusive ends.  Within a read the anchors are in non-decreasing
+ * lexicographic order of (x, y); equal anchors are legal.  Indices below are local to the read.
+ * Parameters: lookback H 1 .. 512, max_dist 1 .. 2^30, bandwidth 0 .. 2^20, gap_scale 0 .. 1024.
+ * Recurrence.  For anchor i, over the predecessors j in [max(0, i - H), i) -- every one of them, no skip heuristic:
+ *   dx = x_i - x_j, dy = y_i - y_j, dd = |dx - dy|
+ *   j is admissible iff 0 < dx <= max_dist, 0 < dy <= max_dist and dd <= bandwidth
+ *   cand(j) = f(j) + min(len_i, dx, dy) - beta(dd)
+ *   beta(0) = 0; for dd >= 1, beta(dd) = ((gap_scale * dd) >> 8) + (floor(log2 dd) >> 1)
+ *   f(i) = max(len_i, max_j cand(j))
+ *   pred(i) = -1 unless some admissible cand(j) > len_i strictly; otherwise the largest j among the admissible j of maximal cand.
+ * All arithmetic is int32; the limits below keep every intermediate inside it.
+ * Result per read.  The chain's last anchor e is the smallest index with maximal f; the chain is e, pred(e), ... down to b with
+ * pred(b) = -1.  score_out[r] = f(e), count_out[r] = the number of chain anchors, last_out[r] = e, span_out[4 r ..] = (q_b, y_e, t_b,
+ * x_e), diag_out[2 r ..] = (min, max) of t - q over the chain's anchors: the j - i diagonals that band_lo / band_hi of the banded
+ * calls use.  A read without anchors gives score 0, count 0, last 0xFFFFFFFF and zeros elsewhere, and never reaches the device.
+ * f_out and pred_out (one int32 per anchor, local indices, each may be NULL) return the whole DP: a caller derives secondary chains
+ * from them.
+ * Validation runs before any device work.  First a null ctx or null required pointer and a parameter outside its range, PWA_E_INVALID;
+ * then in read order, the first offending read decides, and within a read: anc_off not non-decreasing PWA_E_INVALID; more than 2^24
+ * anchors PWA_E_CAPACITY; then anchor by anchor a len of 0 PWA_E_INVALID, t + len or q + len >= 2^31 PWA_E_CAPACITY, the order
+ * violated PWA_E_INVALID; then a sum of len >= 2^30 PWA_E_CAPACITY.  n_reads = 0 is PWA_OK.
+ * Ranges.  Consecutive reads run together as long as their device bytes -- 20 bytes per anchor (t, q, len, f, pred) plus a 40-byte
+ * result record per read -- fit PWA_RANGE_BYTES, else the library's budget; one read alone may exceed it.  A range whose reads are
+ * all empty launches nothing and is not counted.
+ *   pwa_chain_plan        host only, no context, no GPU: the validation code of the same inputs, *bad_read = the first offending read
+ *                         (0xFFFFFFFF: none, or a pointer or parameter was at fault), *n_ranges = the ranges the call would run
+ *                         under budget_bytes (0: no limit).  bad_read and n_ranges may be NULL.
+ *   pwa_chain_last_stats  of the last pwa_chain_anchors on ctx: device ms of the chain kernel (events, summed over the ranges), the
+ *                         anchors it chained, the ranges it ran.  Any pointer may be NULL; a call that fails validation leaves them. */
+int pwa_chain_plan(const uint32_t *anc_t, const uint32_t *anc_q, const uint32_t *anc_len, const uint64_t *anc_off /* n_reads + 1 */,
+                   uint32_t n_reads, uint32_t lookback, uint32_t max_dist, uint32_t bandwidth, uint32_t gap_scale,
+                   uint64_t budget_bytes, uint32_t *bad_read /* or NULL */, uint64_t *n_ranges /* or NULL */);
+int pwa_chain_anchors(pwa_ctx *ctx, const uint32_t *anc_t, const uint32_t *anc_q, const uint32_t *anc_len,
+                      const uint64_t *anc_off /* n_reads + 1 */, uint32_t n_reads, uint32_t lookback, uint32_t max_dist,
+                      uint32_t bandwidth, uint32_t gap_scale, int32_t *score_out, uint32_t *count_out, uint32_t *last_out,
+                      uint32_t *span_out /* 4 * n_reads */, int32_t *diag_out /* 2 * n_reads */, int32_t *f_out /* or NULL */,
+                      int32_t *pred_out /* or NULL */);
+int pwa_chain_last_stats(const pwa_ctx *ctx, float *chain_ms, uint64_t *anchors, uint64_t *ranges);
+
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
  * the walk -- the gapped strings (hw2.cpp:164-184 / 240-259), prepareCigarString (59-78),
