@@ -1,6 +1,6 @@
 // poison.h -- PWA_POISON=<byte> (include/pwalign.h, "Environment switches"): a test mode in which every buffer the context
 // hands to a call reads as that byte until the call first writes to it.  Every acquisition site of the host units -- a fresh or regrown
-// allocation, a buffer from the free list or the hand-off cache, a retained slot reused as it is, a page-locked staging buffer -- calls
+// allocation, a buffer from the free list, the parked hand-off buffer, a retained slot reused as it is, a page-locked staging buffer -- calls
 // poison_device / poison_host on the buffer's whole capacity; with the switch unset that is one branch.  No kernel knows about it.
 #pragma once
 #include <hip/hip_runtime.h>

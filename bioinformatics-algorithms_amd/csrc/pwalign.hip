@@ -843,18 +843,7 @@ int setup_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const CellFor
         b->grid = (uint32_t)std::min<uint64_t>(b->grid, fit);
         b->grid = (b->grid + 3u) & ~3u;   // whole four-wave workgroups (pwa_batch_run): every wave has a hand-off region of its own
     }
-    {
-        const size_t hand_bytes = (size_t)b->grid * (half + second) * sizeof(int32_t);
-        if (ctx->hand_cache && ctx->hand_cache_bytes >= hand_bytes) {   // left behind by an earlier batch of this context
-            b->hand.p = ctx->hand_cache;
-            b->hand.bytes = ctx->hand_cache_bytes;
-            ctx->hand_cache = nullptr;
-            ctx->hand_cache_bytes = 0;
-            HIPC(ctx, poison_device(&ctx->poison, b->hand.p, b->hand.bytes));
-        } else {
-            HIPC(ctx, b->hand.alloc(ctx, hand_bytes));
-        }
-    }
+    HIPC(ctx, b->hand.alloc_hand(ctx, (size_t)b->grid * (half + second) * sizeof(int32_t)));   // (the one an earlier batch of this context left behind, if it is big enough)
 
     clock.mark("uploads + workspace");
     BatchParams& P = b->bp;
@@ -997,7 +986,7 @@ int setup_off_strips(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const Cel
         }
         b->mini.emplace_back(new PairLaunch());
         PairLaunch& ml = *b->mini.back();
-        for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
+        ml.mem = PairLaunch::MEM_FREE_LIST;
         const PairForm form{PF_MINI_FILL, b->mode, BAND_NONE, WALK_NONE, mini_gap0 ? CELLS_GAP0 : CELLS_CODED, rl, 16};
         const int rc = ml.build_mini(ctx, pd, n_real, form, mini_gap0 ? match - 2 * gap : match, mini_gap0 ? mismatch - 2 * gap : mismatch, mini_gap0 ? 0 : gap);
         if (rc != PWA_OK) return rc;
@@ -1056,7 +1045,7 @@ int setup_gotoh_mini(pwa_ctx* ctx, pwa_batch* b, const BatchInput& in, const std
         }
         b->mini.emplace_back(new PairLaunch());
         PairLaunch& ml = *b->mini.back();
-        for (DevBuf* d : {&ml.desc, &ml.tasks, &ml.rows, &ml.progress, &ml.best, &ml.queue}) d->pool = ctx;
+        ml.mem = PairLaunch::MEM_FREE_LIST;
         PairForm form{in.subst ? PF_MINI_SUBST : PF_MINI_GOTOH, b->mode, BAND_NONE, WALK_NONE, CELLS_KEYED, cls.rl, cls.ln};
         if (in.subst) form.subst = SubstRef{b->subst.dev.as<uint32_t>(), b->subst.n_sym, b->subst.stride};
         const int rc = ml.build_mini(ctx, pd, n_real, form, in.match, in.mismatch, in.gap);
@@ -1098,8 +1087,9 @@ int batch_create_impl(pwa_ctx* ctx, int mode, int match, int mismatch, int gap, 
     } guard{b};
     b->ctx = ctx;
     for (DevBuf* d : {&b->arena, &b->tasks, &b->slot_poff, &b->slot_plen, &b->slot_out, &b->slot_toff, &b->slot_tlen, &b->lane_text, &b->hand, &b->queue,
-                      &b->scores, &b->pair_res, &b->pl.desc, &b->pl.tasks, &b->pl.rows, &b->pl.progress, &b->pl.best, &b->pl.queue})
+                      &b->scores, &b->pair_res})
         d->pool = ctx;   // released buffers are kept for the next batch of this context
+    b->pl.mem = PairLaunch::MEM_FREE_LIST;   // (and those of its launches)
     b->mode = mode;
     b->n_pairs = n_pairs;
     b->want_end = in.want_end;
@@ -1565,15 +1555,7 @@ void pwa_batch_destroy(pwa_batch* b) {
         if (b->ev0[e]) (void)hipEventDestroy(b->ev0[e]);
         if (b->ev1[e]) (void)hipEventDestroy(b->ev1[e]);
     }
-    // the hand-off workspace goes back to the context if it is the larger one (and not outrageous): the next batch of
-    // the same shape then skips a multi-GB hipMalloc
-    if (b->ctx && b->hand.p && b->hand.bytes > b->ctx->hand_cache_bytes && b->hand.bytes <= kBandCacheMax) {
-        if (b->ctx->hand_cache) (void)hipFree(b->ctx->hand_cache);
-        b->ctx->hand_cache = b->hand.p;
-        b->ctx->hand_cache_bytes = b->hand.bytes;
-        b->hand.p = nullptr;
-        b->hand.bytes = 0;
-    }
+    b->hand.park_hand();   // the hand-off workspace stays the context's parked one if it is the larger one (DevMem::park_hand)
     delete b;
 }
 

@@ -268,11 +268,10 @@ int affine_tb_on_stripes(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector
     if (ctx->knobs.debug)
         std::fprintf(stderr, "[pwa] align_affine stripes: %zu pairs in %zu chunk(s) of <= %.2f GB of band (cap %.2f GB)\n", pairs.size(), chunks.size(),
                      (double)band_cap / 1e9, (double)cap / 1e9);
-    DevBuf d_band, d_res_own;
-    void *p_band = nullptr, *p_res = nullptr;
-    HIPC(ctx, cached_workspace(ctx, ctx->band_cache, ctx->band_cache_bytes, band_cap + kWalkPad, d_band, &p_band));
-    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], nc_cap * sizeof(PairResult), d_res_own, &p_res));
-    PairResult* const d_res = static_cast<PairResult*>(p_res);
+    Lease l_band, l_res;
+    HIPC(ctx, workspace(ctx, DevMem::BAND, band_cap + kWalkPad, l_band));
+    HIPC(ctx, workspace(ctx, DevMem::RES, nc_cap * sizeof(PairResult), l_res));
+    PairResult* const d_res = l_res.as<PairResult>();
     for (const auto& ch : chunks) {
         const size_t nc = ch.second - ch.first;
         std::vector<PairDesc> pd(nc);
@@ -285,7 +284,7 @@ int affine_tb_on_stripes(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector
             d.txt = ar.arena.as<uint8_t>() + ar.aoff[rq.pair_b[k]];
             d.n = (int32_t)rq.slen(rq.pair_a[k]);
             d.m = (int32_t)rq.slen(rq.pair_b[k]);
-            d.tb = static_cast<uint8_t*>(p_band) + bo;
+            d.tb = l_band.as<uint8_t>() + bo;
             d.res = d_res + q;
             d.ops = rs.d_ops.as<uint8_t>() + rs.dev_ops_off[k];
             d.ops_cap = (uint32_t)(d.n + d.m);
@@ -296,7 +295,7 @@ int affine_tb_on_stripes(pwa_ctx* ctx, const AffTbRequest& rq, const std::vector
         }
         HIPC(ctx, hipMemsetAsync(d_res, 0, nc * sizeof(PairResult), ctx->stream));
         PairLaunch pl;
-        pl.from_pool = true;
+        pl.mem = PairLaunch::MEM_SLOTS;
         const PairForm form{PF_STRIPE_AFFINE_TB, PWA_MODE_NW, BAND_TB, WALK_OPS, CELLS_PLAIN, 4, max_n <= 256 ? 1 : 4};
         int rc = pl.build(ctx, pd, form, rq.match, rq.mismatch, rq.gap_open, rq.gap_extend);
         if (rc != PWA_OK) return rc;

@@ -211,8 +211,8 @@ struct AlignArena {
     uint8_t code_of[256];
     bool coded = false;
     int32_t dash_sym = 0x100;
-    DevBuf arena_own;
-    uint8_t* base = nullptr;
+    Lease arena;
+    uint8_t* base() const { return arena.as<uint8_t>(); }
 };
 int build_align_arena(pwa_ctx* ctx, const AlignRequest& rq, AlignClock& clock, AlignArena& ar) {
     std::vector<uint8_t> is_used(rq.n_seq, 0);
@@ -226,10 +226,8 @@ int build_align_arena(pwa_ctx* ctx, const AlignRequest& rq, AlignClock& clock, A
     // of the input sequence itself: the walk needs the arena's value for that byte
     ar.dash_sym = !dash_seen ? 0x100 : (ar.coded ? (int32_t)ar.code_of[(unsigned char)'-'] : (int32_t)'-');
     clock.mark("validate + alphabet scan");
-    void* p_arena = nullptr;
-    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_ARENA], ctx->pool_bytes[pwa_ctx::POOL_ARENA], arena_bytes, ar.arena_own, &p_arena));
-    HIPC(ctx, build_arena(ctx, p_arena, arena_bytes, rq.seq_bytes, rq.seq_off, rq.n_seq, is_used, ar.aoff, ar.coded ? ar.code_of : nullptr, !nul_seen));
-    ar.base = static_cast<uint8_t*>(p_arena);
+    HIPC(ctx, workspace(ctx, DevMem::ARENA, arena_bytes, ar.arena));
+    HIPC(ctx, build_arena(ctx, ar.base(), arena_bytes, rq.seq_bytes, rq.seq_off, rq.n_seq, is_used, ar.aoff, ar.coded ? ar.code_of : nullptr, !nul_seen));
     clock.mark("arena upload");
     return PWA_OK;
 }
@@ -470,12 +468,11 @@ RangePlan plan_ranges(const AlignRequest& rq, const TbPlan& plan, const RangeTar
 
 // The device workspaces of a call, sized for its largest range and kept in the context between calls
 struct AlignWorkspaces {
-    DevBuf d_band, d_sband, d_ops_own, d_res_own, d_str_own, d_aux_own;   // (requests beyond what the context keeps)
-    void *p_band = nullptr, *p_sband = nullptr, *p_ops = nullptr, *p_res = nullptr, *p_str = nullptr, *p_aux = nullptr;
-    // pwa_align_batch_cigar's device side per range (p_aux): the pair list, the 2 nc + 2 string lengths (then offsets), the scan's partials
+    Lease band, sband, d_ops, d_res, str, aux;
+    // pwa_align_batch_cigar's device side per range (aux): the pair list, the 2 nc + 2 string lengths (then offsets), the scan's partials
     uint64_t aux_len_at = 0, aux_part_at = 0;
-    uint8_t* ops() const { return static_cast<uint8_t*>(p_ops); }
-    PairResult* res() const { return static_cast<PairResult*>(p_res); }
+    uint8_t* ops() const { return d_ops.as<uint8_t>(); }
+    PairResult* res() const { return d_res.as<PairResult>(); }
 };
 int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& plan, const RangePlan& rp, AlignWorkspaces& ws) {
     const uint64_t len_words = 2 * rp.nc_cap + 2;
@@ -483,15 +480,13 @@ int take_align_workspaces(pwa_ctx* ctx, const AlignRequest& rq, const TbPlan& pl
     ws.aux_part_at = ws.aux_len_at + align_up(len_words * 4, 256);
     if (rp.ranges.empty()) return PWA_OK;
     // + one traceback window: the walk stages whole windows
-    if (!rq.scores_only()) HIPC(ctx, cached_workspace(ctx, ctx->band_cache, ctx->band_cache_bytes, rp.band_cap + 32768, ws.d_band, &ws.p_band));
-    if (plan.sband)
-        HIPC(ctx, cached_workspace(ctx, ctx->sband_cache, ctx->sband_cache_bytes, rp.band_cap * sizeof(int32_t), ws.d_sband, &ws.p_sband));
-    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_OPS], ctx->pool_bytes[pwa_ctx::POOL_OPS], rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops_own, &ws.p_ops));
-    HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_RES], ctx->pool_bytes[pwa_ctx::POOL_RES], rp.nc_cap * rq.res_bytes(), ws.d_res_own, &ws.p_res));
+    if (!rq.scores_only()) HIPC(ctx, workspace(ctx, DevMem::BAND, rp.band_cap + 32768, ws.band));
+    if (plan.sband) HIPC(ctx, workspace(ctx, DevMem::SBAND, rp.band_cap * sizeof(int32_t), ws.sband));
+    HIPC(ctx, workspace(ctx, DevMem::OPS, rq.walk_ops() && !rq.scores_only() ? rp.ops_cap_b : 16, ws.d_ops));
+    HIPC(ctx, workspace(ctx, DevMem::RES, rp.nc_cap * rq.res_bytes(), ws.d_res));
     if (rq.want_str()) {
-        HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_STR], ctx->pool_bytes[pwa_ctx::POOL_STR], rp.str_cap, ws.d_str_own, &ws.p_str));
-        HIPC(ctx, cached_workspace(ctx, ctx->pool[pwa_ctx::POOL_STR_AUX], ctx->pool_bytes[pwa_ctx::POOL_STR_AUX],
-                                   ws.aux_part_at + pwa::scan_part_words(len_words) * 4, ws.d_aux_own, &ws.p_aux));
+        HIPC(ctx, workspace(ctx, DevMem::STR, rp.str_cap, ws.str));
+        HIPC(ctx, workspace(ctx, DevMem::STR_AUX, ws.aux_part_at + pwa::scan_part_words(len_words) * 4, ws.aux));
     }
     return PWA_OK;
 }
@@ -547,7 +542,7 @@ int init_range_results(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& a
         oo += align_up(n + m + 1, 16);
     }
     HIPC(ctx, hipMemcpy(ws.res(), res, nc * rq.res_bytes(), hipMemcpyHostToDevice));
-    if (want_str) HIPC(ctx, hipMemcpyAsync(ws.p_aux, rh.cpairs, nc * sizeof(CigarPair), hipMemcpyHostToDevice, ctx->stream));
+    if (want_str) HIPC(ctx, hipMemcpyAsync(ws.aux.get(), rh.cpairs, nc * sizeof(CigarPair), hipMemcpyHostToDevice, ctx->stream));
     return PWA_OK;
 }
 
@@ -575,11 +570,11 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
         const int64_t lo = rq.bd->lo_in(k, n, m), hi = rq.bd->hi_in(k, n, m);
         PairDesc& d = pd[p];
         std::memset(&d, 0, sizeof d);
-        d.pat = ar.base + ar.aoff[rq.pair_a[k]];
-        d.txt = ar.base + ar.aoff[rq.pair_b[k]];
+        d.pat = ar.base() + ar.aoff[rq.pair_a[k]];
+        d.txt = ar.base() + ar.aoff[rq.pair_b[k]];
         d.n = (int32_t)n;
         d.m = (int32_t)m;
-        d.tb = scores ? nullptr : static_cast<uint8_t*>(ws.p_band) + L.bo[p];
+        d.tb = scores ? nullptr : ws.band.as<uint8_t>() + L.bo[p];
         d.res = ws.res() + q;
         if (rq.pend()) d.rows = reinterpret_cast<int32_t*>(ws.res() + (rg.k1 - rg.k0)) + 2 * q;
         d.ops = scores ? nullptr : ws.ops() + rh.ooff[q];
@@ -593,7 +588,7 @@ int run_banded_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar
         for (int64_t s = 0; !scores && s < (int64_t)d.n_stripes; ++s) stats.band_bytes += (uint64_t)(banded_chunks(s * S + 1, S, lo, hi, (int64_t)m) * 16 * S);   // what the fill stores
     }
     PairLaunch pl;
-    pl.from_pool = true;
+    pl.mem = PairLaunch::MEM_SLOTS;
     if (const int rc = pl.upload_desc(ctx, pd)) return rc;
     // (a table launch: match / mismatch = +- max |submat| -- banded_body places its sentinel by them; the range rule keeps them below 2^27)
     const int k_match = rq.sb ? (int)rq.sb->max_abs : rq.match, k_mismatch = rq.sb ? -(int)rq.sb->max_abs : rq.mismatch;
@@ -627,12 +622,12 @@ int run_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const
         const uint64_t q = L.q[p], k = rg.k0 + q, n = rq.slen(rq.pair_a[k]), m = rq.slen(rq.pair_b[k]);
         PairDesc d;
         std::memset(&d, 0, sizeof d);
-        d.pat = ar.base + ar.aoff[rq.pair_a[k]];
-        d.txt = ar.base + ar.aoff[rq.pair_b[k]];
+        d.pat = ar.base() + ar.aoff[rq.pair_a[k]];
+        d.txt = ar.base() + ar.aoff[rq.pair_b[k]];
         d.n = (int32_t)n;
         d.m = (int32_t)m;
-        d.tb = static_cast<uint8_t*>(ws.p_band) + L.bo[p];
-        if (plan.sband) d.sband = static_cast<int32_t*>(ws.p_sband) + L.bo[p];
+        d.tb = ws.band.as<uint8_t>() + L.bo[p];
+        if (plan.sband) d.sband = ws.sband.as<int32_t>() + L.bo[p];
         d.res = ws.res() + q;
         d.ops = walk_ops ? ws.ops() + rh.ooff[q] : ws.ops();   // WALK_OVERLAP never writes ops
         d.ops_cap = (uint32_t)std::min<uint64_t>(n + m, 0xffffffffu);
@@ -643,12 +638,12 @@ int run_launch(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena& ar, const
     for (uint32_t dmy = 0; dmy < L.n_dummy; ++dmy) {   // empty patterns that fill the last task: every cell of theirs is padding
         PairDesc d = pd[np - 1];
         d.n = 0;
-        d.tb = static_cast<uint8_t*>(ws.p_band) + L.dummy_bo[dmy];
-        if (plan.sband) d.sband = static_cast<int32_t*>(ws.p_sband) + L.dummy_bo[dmy];
+        d.tb = ws.band.as<uint8_t>() + L.dummy_bo[dmy];
+        if (plan.sband) d.sband = ws.sband.as<int32_t>() + L.dummy_bo[dmy];
         pd.push_back(d);
     }
     PairLaunch pl;
-    pl.from_pool = true;
+    pl.mem = PairLaunch::MEM_SLOTS;
     const PairCells cells = plan.gap0 ? CELLS_GAP0 : ar.coded && plan.keyed ? CELLS_CODED : plan.keyed ? CELLS_KEYED : CELLS_PLAIN;
     PairForm form{L.cls.mini ? PF_MINI_FILL : PF_STRIPE_FILL, rq.mode, plan.sband ? BAND_TB_SCORES : BAND_TB, walk_ops ? WALK_OPS : WALK_OVERLAP, cells, L.cls.rl, L.cls.w};
     if (rq.gt) form.family = rq.sb ? PF_MINI_SUBST : PF_MINI_GOTOH, form.cells = CELLS_KEYED;   // (raw bytes, compared; always a mini class)
@@ -685,12 +680,12 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
     const StrOut& str = rq.out.str;
     uint32_t* const clen = rh.clen;
     CigarParams cp;
-    cp.arena = ar.base;
+    cp.arena = ar.base();
     cp.ops = ws.ops();
     cp.res = ws.res();
-    cp.pairs = static_cast<const CigarPair*>(ws.p_aux);
-    cp.len = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws.p_aux) + ws.aux_len_at);
-    cp.out = static_cast<uint8_t*>(ws.p_str);
+    cp.pairs = ws.aux.as<const CigarPair>();
+    cp.len = reinterpret_cast<uint32_t*>(ws.aux.as<uint8_t>() + ws.aux_len_at);
+    cp.out = ws.str.as<uint8_t>();
     cp.decode = 0;
     if (ar.coded)
         for (int v = 255; v >= 0; --v)
@@ -701,7 +696,7 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
     cp.semi = rq.semi();
     HIPC(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     HIPC(ctx, pwa::cigar_launch(cp, false, ctx->stream));
-    pwa::scan_excl(ctx->stream, cp.len, 2 * nc + 2, reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws.p_aux) + ws.aux_part_at));
+    pwa::scan_excl(ctx->stream, cp.len, 2 * nc + 2, reinterpret_cast<uint32_t*>(ws.aux.as<uint8_t>() + ws.aux_part_at));
     HIPC(ctx, hipGetLastError());
     HIPC(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIPC(ctx, pwa::cigar_launch(cp, true, ctx->stream));
@@ -718,9 +713,9 @@ int format_range_strings(pwa_ctx* ctx, const AlignRequest& rq, const AlignArena&
         str.cigar_off[k0 + q] = rh.str_at[0] + clen[q];
         str.mdz_off[k0 + q] = rh.str_at[1] + (clen[nc + 1 + q] - tot_c);
     }
-    if (tot_c && rh.str_at[0] + tot_c <= str.cigar_cap) HIPC(ctx, hipMemcpy(str.cigar + rh.str_at[0], ws.p_str, tot_c, hipMemcpyDeviceToHost));
+    if (tot_c && rh.str_at[0] + tot_c <= str.cigar_cap) HIPC(ctx, hipMemcpy(str.cigar + rh.str_at[0], ws.str.get(), tot_c, hipMemcpyDeviceToHost));
     if (tot_m && rh.str_at[1] + tot_m <= str.mdz_cap)
-        HIPC(ctx, hipMemcpy(str.mdz + rh.str_at[1], static_cast<uint8_t*>(ws.p_str) + tot_c, tot_m, hipMemcpyDeviceToHost));
+        HIPC(ctx, hipMemcpy(str.mdz + rh.str_at[1], ws.str.as<uint8_t>() + tot_c, tot_m, hipMemcpyDeviceToHost));
     rh.str_at[0] += tot_c;
     rh.str_at[1] += tot_m;
     return PWA_OK;
@@ -804,7 +799,7 @@ int align_batch_impl(pwa_ctx* ctx, const AlignRequest& rq, AlignStats& stats) tr
     AlignWorkspaces ws;
     if ((rc = take_align_workspaces(ctx, rq, plan, rp, ws)) != PWA_OK) return rc;
     clock.mark("band / ops allocation");
-    if (clock.on) std::fprintf(stderr, "[pwa] bands at %p (codes, %.2f GB) %p (scores)\n", ws.p_band, (double)rp.band_cap / 1e9, ws.p_sband);
+    if (clock.on) std::fprintf(stderr, "[pwa] bands at %p (codes, %.2f GB) %p (scores)\n", ws.band.get(), (double)rp.band_cap / 1e9, ws.sband.get());
     RangeHost rh;
     for (const Range& rg : rp.ranges) {
         if ((rc = init_range_results(ctx, rq, arena, ws, rg, rh)) != PWA_OK) return rc;

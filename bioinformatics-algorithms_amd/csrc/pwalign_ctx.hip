@@ -144,7 +144,6 @@ hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_
 
 namespace {
 
-constexpr size_t kFreeListMaxBytes = 24ull << 30, kFreeListMaxCount = 64;   // (DevBuf)
 bool key_byte(int64_t k) { return k <= 127 && k >= -126; }   // (diag_keys_fit, gap0_ok)
 
 // Runs fn(first_seq, last_seq, thread) over the sequences, split into byte-balanced contiguous ranges, on up to
@@ -173,14 +172,8 @@ void for_seq_ranges(const uint64_t* seq_off, uint32_t n_seq, F&& fn, int* n_thre
 namespace pwa {
 
 void DevBuf::release() {
-    if (p) {
-        if (pool && pool->free_list.size() < kFreeListMaxCount && pool->free_list_bytes + bytes <= kFreeListMaxBytes) {
-            pool->free_list.emplace_back(p, bytes);
-            pool->free_list_bytes += bytes;
-        } else {
-            (void)hipFree(p);
-        }
-    }
+    if (pool) pool->mem.keep(p, bytes);
+    else if (p) (void)hipFree(p);
     p = nullptr;
     bytes = 0;
 }
@@ -219,32 +212,19 @@ void poison_host(Poison* po, void* p, size_t cap) {
 
 hipError_t DevBuf::alloc(pwa_ctx* ctx, size_t n) {
     release();
-    if (n == 0) n = 16;
-    if (pool) {   // best fit among the kept buffers: at least n, at most 2 n + 1 MiB (a 5 GB block is not spent on a 1 KB request)
-        size_t best = pool->free_list.size();
-        for (size_t i = 0; i < pool->free_list.size(); ++i) {
-            const size_t have = pool->free_list[i].second;
-            if (have >= n && have <= 2 * n + (1u << 20) && (best == pool->free_list.size() || have < pool->free_list[best].second)) best = i;
-        }
-        if (best < pool->free_list.size()) {
-            p = pool->free_list[best].first;
-            bytes = pool->free_list[best].second;
-            pool->free_list_bytes -= bytes;
-            pool->free_list.erase(pool->free_list.begin() + (long)best);
-            return poison_device(&ctx->poison, p, bytes);
-        }
-    }
-    hipError_t e = hipMalloc(&p, n);
-    if (e != hipSuccess && pool && !pool->free_list.empty()) {   // out of memory with buffers parked: give them back and try again
-        for (auto& f : pool->free_list) (void)hipFree(f.first);
-        pool->free_list.clear();
-        pool->free_list_bytes = 0;
-        (void)hipGetLastError();
-        e = hipMalloc(&p, n);
-    }
-    if (e == hipSuccess) bytes = n;
-    else p = nullptr;
+    const hipError_t e = ctx->mem.buffer(n ? n : 16, pool != nullptr, &p, &bytes);
     return e == hipSuccess ? poison_device(&ctx->poison, p, bytes) : e;
+}
+hipError_t DevBuf::alloc_hand(pwa_ctx* ctx, size_t n) {
+    release();
+    if (!ctx->mem.take_hand(n, &p, &bytes)) return alloc(ctx, n);
+    return poison_device(&ctx->poison, p, bytes);
+}
+void DevBuf::park_hand() {
+    if (!pool) return;
+    pool->mem.park_hand(p, bytes);
+    p = nullptr;
+    bytes = 0;
 }
 
 // Stable LSD radix sort of `idx` by 64-bit keys (16-bit digits; passes whose digit is constant are skipped).
@@ -334,27 +314,11 @@ int mini_rl_for(uint64_t n) {
 // ... and of the one-pair-per-wave class (64 lanes) for 257 .. 1024 rows
 int wide_rl_for(uint64_t n) { return n <= 384 ? 6 : n <= 512 ? 8 : n <= 768 ? 12 : 16; }
 
-// A workspace of `bytes` from the context's cache slot (see pwa_ctx): reused when big enough, regrown otherwise;
-// requests beyond kBandCacheMax are served by `fallback` and freed with it.
-hipError_t cached_workspace(pwa_ctx* ctx, void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out) {
-    if (bytes > kBandCacheMax) {
-        const hipError_t e = fallback.alloc(ctx, bytes);
-        *out = fallback.p;
-        return e;
-    }
-    if (slot_bytes < bytes) {
-        if (slot) (void)hipFree(slot);
-        slot = nullptr;
-        slot_bytes = 0;
-        const hipError_t e = hipMalloc(&slot, bytes);
-        if (e != hipSuccess) {
-            slot = nullptr;
-            return e;
-        }
-        slot_bytes = bytes;
-    }
-    *out = slot;
-    return poison_device(&ctx->poison, slot, slot_bytes);   // regrown or reused as it is: the whole slot
+// `bytes` of the context's slot (DevMem::workspace: reused when big enough, regrown otherwise, a buffer of the lease's own beyond
+// kBandCacheMax), PWA_POISON over the whole capacity on every acquisition
+hipError_t workspace(pwa_ctx* ctx, DevMem::Slot slot, size_t bytes, Lease& out) {
+    const hipError_t e = ctx->mem.workspace(slot, bytes, out);
+    return e == hipSuccess ? poison_device(&ctx->poison, out.get(), out.cap()) : e;
 }
 
 // pageable memory that the library does not own (or that is too large to mirror in page-locked memory): through a bounce buffer
@@ -599,22 +563,29 @@ static void note_pair_form(pwa_ctx* ctx, const PairForm& f) {
 }
 
 // ---- PairLaunch (pwalign_internal.h)
+// one of a launch's six buffers, from where PairLaunch::mem says
+static hipError_t take(pwa_ctx* ctx, const PairLaunch& pl, Lease& out, DevMem::Slot slot, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (pl.mem == PairLaunch::MEM_SLOTS) return workspace(ctx, slot, bytes, out);
+    const hipError_t e = ctx->mem.lease(bytes, pl.mem == PairLaunch::MEM_FREE_LIST, out);
+    return e == hipSuccess ? poison_device(&ctx->poison, out.get(), out.cap()) : e;
+}
 int PairLaunch::upload_desc(pwa_ctx* ctx, const std::vector<PairDesc>& pd) {
     const size_t bytes = pd.size() * sizeof(PairDesc);
-    HIPC(ctx, take(ctx, desc, pwa_ctx::POOL_DESC, bytes, &p_desc));
+    HIPC(ctx, take(ctx, *this, desc, DevMem::DESC, bytes));
     HIPC(ctx, ctx->pin[pwa_ctx::PIN_DESC].reserve(bytes));
     std::memcpy(ctx->pin[pwa_ctx::PIN_DESC].p, pd.data(), bytes);
-    HIPC(ctx, hipMemcpy(p_desc, ctx->pin[pwa_ctx::PIN_DESC].p, bytes, hipMemcpyHostToDevice));
+    HIPC(ctx, hipMemcpy(desc.get(), ctx->pin[pwa_ctx::PIN_DESC].p, bytes, hipMemcpyHostToDevice));
     return PWA_OK;
 }
 // the fields of G that every launch sets (the callers add scores_out, dash, gap_extend of the gotoh families)
 void PairLaunch::set_params(uint32_t n_pairs, uint32_t n_tasks, int match, int mismatch, int gap, int gap_extend) {
     G = PairParams{};
-    G.pairs = static_cast<PairDesc*>(p_desc);
+    G.pairs = desc.as<PairDesc>();
     G.n_pairs = n_pairs;
     G.n_tasks = n_tasks;
-    G.queue = static_cast<uint32_t*>(p_queue);
-    G.best = static_cast<StripeBest*>(p_best);
+    G.queue = queue.as<uint32_t>();
+    G.best = best.as<StripeBest>();
     G.match = match;
     G.mismatch = mismatch;
     G.gap = gap;
@@ -645,25 +616,25 @@ int PairLaunch::build(pwa_ctx* ctx, std::vector<PairDesc>& pd, const PairForm& f
         n_stripes_total += ns;
     }
     row_bytes = rows_i32 * sizeof(int32_t);
-    HIPC(ctx, take(ctx, rows, pwa_ctx::POOL_ROWS, row_bytes, &p_rows));
+    HIPC(ctx, take(ctx, *this, rows, DevMem::ROWS, row_bytes));
     uint64_t ro = 0;
     for (auto& d : pd) {
-        d.rows = static_cast<int32_t*>(p_rows) + ro;
+        d.rows = rows.as<int32_t>() + ro;
         const uint64_t nsup = ((uint64_t)d.n_stripes + f.w - 1) / f.w;
         ro += (nsup - 1) * d.row_stride * vals;
     }
     if (const int rc = upload_desc(ctx, pd)) return rc;
-    HIPC(ctx, take(ctx, tasks, pwa_ctx::POOL_TASKS, tl.size() * sizeof(StripeTask), &p_tasks));
+    HIPC(ctx, take(ctx, *this, tasks, DevMem::TASKS, tl.size() * sizeof(StripeTask)));
     HIPC(ctx, ctx->pin[pwa_ctx::PIN_TL].reserve(tl.size() * sizeof(StripeTask)));
     std::memcpy(ctx->pin[pwa_ctx::PIN_TL].p, tl.data(), tl.size() * sizeof(StripeTask));
-    HIPC(ctx, hipMemcpy(p_tasks, ctx->pin[pwa_ctx::PIN_TL].p, tl.size() * sizeof(StripeTask), hipMemcpyHostToDevice));
+    HIPC(ctx, hipMemcpy(tasks.get(), ctx->pin[pwa_ctx::PIN_TL].p, tl.size() * sizeof(StripeTask), hipMemcpyHostToDevice));
     progress_bytes = align_up(tl.size() * sizeof(uint32_t), 16);
-    HIPC(ctx, take(ctx, progress, pwa_ctx::POOL_PROGRESS, progress_bytes, &p_progress));
-    HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, std::max<uint64_t>(n_stripes_total, 1) * sizeof(StripeBest), &p_best));
-    HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
+    HIPC(ctx, take(ctx, *this, progress, DevMem::PROGRESS, progress_bytes));
+    HIPC(ctx, take(ctx, *this, best, DevMem::BEST, std::max<uint64_t>(n_stripes_total, 1) * sizeof(StripeBest)));
+    HIPC(ctx, take(ctx, *this, queue, DevMem::QUEUE, 64));
     set_params((uint32_t)pd.size(), (uint32_t)tl.size(), match, mismatch, gap, gap_extend);
-    G.tasks = static_cast<StripeTask*>(p_tasks);
-    G.progress = static_cast<uint32_t*>(p_progress);
+    G.tasks = tasks.as<StripeTask>();
+    G.progress = progress.as<uint32_t>();
     n_stripes = n_stripes_total;
     // Tasks come off the queue in global order, so correctness does not depend on how many workgroups
     // are resident.  One workgroup = W compute waves + 1 helper wave.
@@ -691,8 +662,8 @@ int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_r
         pd[q].rows = nullptr;
     }
     if (const int rc = upload_desc(ctx, pd)) return rc;
-    HIPC(ctx, take(ctx, best, pwa_ctx::POOL_BEST, pd.size() * sizeof(StripeBest), &p_best));
-    HIPC(ctx, take(ctx, queue, pwa_ctx::POOL_QUEUE, 64, &p_queue));
+    HIPC(ctx, take(ctx, *this, best, DevMem::BEST, pd.size() * sizeof(StripeBest)));
+    HIPC(ctx, take(ctx, *this, queue, DevMem::QUEUE, 64));
     progress_bytes = 0;
     row_bytes = 0;
     set_params(n_real, (uint32_t)(pd.size() / ppw), match, mismatch, gap, 0);
@@ -702,7 +673,7 @@ int PairLaunch::build_mini(pwa_ctx* ctx, std::vector<PairDesc>& pd, uint32_t n_r
 }
 // enqueue: zero the queue / progress words, fill, then the walk (or only the end-cell pick)
 int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, hipEvent_t after_fill) {
-    HIPC(ctx, hipMemsetAsync(p_queue, 0, 16, st));
+    HIPC(ctx, hipMemsetAsync(queue.get(), 0, 16, st));
     const void* const fill_fn = k.sfill ? reinterpret_cast<const void*>(k.sfill) : reinterpret_cast<const void*>(k.fill);
     uint32_t g = grid;
     size_t pad_lds = 0;
@@ -721,7 +692,7 @@ int PairLaunch::launch(pwa_ctx* ctx, hipStream_t st, hipEvent_t after_fill) {
         g = std::min<uint32_t>(n_wg, (uint32_t)ctx->num_cu * per_cu);
         if (ctx->knobs.debug) std::fprintf(stderr, "[pwa] mini fill: %u tasks, %u workgroups of %d waves, %u per CU (%zu KiB of LDS each)\n", G.n_tasks, g, kMiniWaves, per_cu, pad_lds >> 10);
     } else {
-        HIPC(ctx, hipMemsetAsync(p_progress, 0, progress_bytes, st));
+        HIPC(ctx, hipMemsetAsync(progress.get(), 0, progress_bytes, st));
         if (!ctx->knobs.stamps.empty()) {
             HIPC(ctx, stamps.alloc(ctx, n_stripes * 32 + 4 * 8192 * 8));
             HIPC(ctx, hipMemsetAsync(stamps.p, 0, n_stripes * 32 + 4 * 8192 * 8, st));
@@ -766,7 +737,7 @@ int PairLaunch::check(pwa_ctx* ctx) {
         }
     }
     uint32_t q[2] = {0, 0};
-    HIPC(ctx, hipMemcpy(q, p_queue, sizeof q, hipMemcpyDeviceToHost));
+    HIPC(ctx, hipMemcpy(q, queue.get(), sizeof q, hipMemcpyDeviceToHost));
     if (q[1] != 0) return fail(ctx, PWA_E_HIP, "stripe pipeline timed out waiting for the stripe above");
     return PWA_OK;
 }
@@ -1013,6 +984,141 @@ static int selftest_banded_forms() {
     return 0;
 }
 
+// ... and DevMem's policy (dev_mem.h; DESIGN.md 3.20, "The allocation rule") over a fake device: a byte budget, addresses that are
+// never dereferenced, every call counted, every free checked against what is live.  The return value names the rule that broke:
+// 1 a slot big enough is reused without a call; 2 it is regrown with one free and one malloc; 3 a request beyond kBandCacheMax leaves
+// the slot alone and its buffer goes with the lease; 4 best fit takes the smallest admissible buffer of the free list; 5 none larger
+// than 2 n + 1 MiB; 6 the list's count and byte caps; 7 parking a larger hand-off buffer moves the displaced one to the list without a
+// free; 8 a parked buffer that is too small stays parked; 9 out of memory frees the list and the parked buffer and the second try
+// succeeds; 10 a leased slot survives that; 11 with nothing idle the failure comes back after exactly one retry; 12 the destructor
+// frees every slot, the parked buffer and the list once each; 13 nothing is left live and nothing was freed twice.
+namespace {
+struct FakeDev {
+    std::vector<std::pair<void*, size_t>> live;
+    size_t budget = ~size_t(0), used = 0, mallocs = 0, frees = 0, bad_frees = 0;
+    uintptr_t next = 0x1000;
+    bool is_live(const void* p) const {
+        return std::any_of(live.begin(), live.end(), [&](const auto& b) { return b.first == p; });
+    }
+};
+thread_local FakeDev fake;   // (DevMem's allocator is a plain function pointer)
+hipError_t fake_malloc(void** p, size_t n) {
+    ++fake.mallocs;
+    *p = nullptr;
+    if (n > fake.budget - fake.used) return hipErrorOutOfMemory;
+    *p = reinterpret_cast<void*>(fake.next);
+    fake.next += 0x1000;
+    fake.used += n;
+    fake.live.emplace_back(*p, n);
+    return hipSuccess;
+}
+hipError_t fake_free(void* p) {
+    ++fake.frees;
+    for (size_t i = 0; i < fake.live.size(); ++i)
+        if (fake.live[i].first == p) {
+            fake.used -= fake.live[i].second;
+            fake.live.erase(fake.live.begin() + (long)i);
+            return hipSuccess;
+        }
+    ++fake.bad_frees;
+    return hipErrorInvalidValue;
+}
+}  // namespace
+static int selftest_dev_mem() {
+    constexpr size_t MiB = 1u << 20;
+    FakeDev& f = fake;
+    auto calls = [&](size_t mallocs, size_t frees) { return f.mallocs == mallocs && f.frees == frees; };
+    auto fresh = [&](DevMem& m, size_t n, void** p) {   // a buffer of exactly n bytes, not from the list
+        size_t got = 0;
+        return m.buffer(n, false, p, &got) == hipSuccess && *p && got == n;
+    };
+    void *p = nullptr, *q[3] = {};
+    size_t got = 0;
+    f = FakeDev{};
+    {   // slots
+        DevMem m(fake_malloc, fake_free);
+        Lease a, b;
+        if (m.workspace(DevMem::RES, 1000, a) != hipSuccess || !a.get() || a.cap() != 1000 || !calls(1, 0)) return 1;
+        void* const p0 = a.get();
+        if (m.workspace(DevMem::RES, 600, a) != hipSuccess || a.get() != p0 || a.cap() != 1000 || !calls(1, 0)) return 1;
+        if (m.workspace(DevMem::RES, 1001, a) != hipSuccess || a.cap() != 1001 || !calls(2, 1) || f.is_live(p0) || f.used != 1001) return 2;
+        if (m.workspace(DevMem::RES, kBandCacheMax + 1, b) != hipSuccess || b.get() == a.get() || b.cap() != kBandCacheMax + 1 || !calls(3, 1)) return 3;
+        void* const big = b.get();
+        b.release();
+        if (!calls(3, 2) || f.is_live(big) || m.workspace(DevMem::RES, 1001, b) != hipSuccess || b.get() != a.get() || !calls(3, 2)) return 3;
+        // the free list: 3, 2 and 8 MiB kept
+        const size_t sizes[3] = {3 * MiB, 2 * MiB, 8 * MiB};
+        for (int i = 0; i < 3; ++i) {
+            if (!fresh(m, sizes[i], &q[i])) return 4;
+            m.keep(q[i], sizes[i]);
+        }
+        if (!calls(6, 2)) return 4;
+        if (m.buffer(3 * MiB / 2, true, &p, &got) != hipSuccess || p != q[1] || got != 2 * MiB || !calls(6, 2)) return 4;   // 2 and 3 MiB are admissible
+        m.keep(p, got);
+        if (!fresh(m, 2 * MiB, &p) || p == q[1] || !calls(7, 2)) return 4;   // an un-pooled request never takes from the list
+        m.drop(p);
+        if (m.buffer(7 * MiB / 2 - 1, true, &p, &got) != hipSuccess || p == q[2] || got != 7 * MiB / 2 - 1 || !calls(8, 3)) return 5;   // 8 MiB > 2 n + 1 MiB
+        m.drop(p);
+        if (m.buffer(7 * MiB / 2, true, &p, &got) != hipSuccess || p != q[2] || got != 8 * MiB || !calls(8, 4)) return 5;   // ... = 2 n + 1 MiB
+        m.drop(p);
+    }
+    if (!calls(8, 8) || !f.live.empty() || f.bad_frees) return 12;   // (the slot and the two kept buffers)
+    f = FakeDev{};
+    {   // the list's caps
+        DevMem m(fake_malloc, fake_free);
+        for (size_t i = 0; i <= DevMem::kListMaxCount; ++i) {
+            if (!fresh(m, 16, &p)) return 6;
+            m.keep(p, 16);
+            if (f.frees != (i == DevMem::kListMaxCount ? 1u : 0u)) return 6;
+        }
+    }
+    if (!f.live.empty() || f.bad_frees) return 12;
+    f = FakeDev{};
+    {
+        DevMem m(fake_malloc, fake_free);
+        for (int i = 0; i < 4; ++i) {   // three buffers fill the list's bytes exactly; 16 bytes more are refused
+            const size_t n = i < 3 ? DevMem::kListMaxBytes / 3 : 16;
+            if (!fresh(m, n, &p)) return 6;
+            m.keep(p, n);
+            if (f.frees != (i < 3 ? 0u : 1u)) return 6;
+        }
+    }
+    if (!f.live.empty() || f.bad_frees) return 12;
+    f = FakeDev{};
+    {   // the hand-off buffer
+        DevMem m(fake_malloc, fake_free);
+        if (!fresh(m, 1000, &q[0]) || !fresh(m, 2000, &q[1])) return 7;
+        m.park_hand(q[0], 1000);
+        m.park_hand(q[1], 2000);   // displaces the first one ...
+        if (!calls(2, 0) || m.buffer(1000, true, &p, &got) != hipSuccess || p != q[0] || got != 1000 || !calls(2, 0)) return 7;   // ... onto the list
+        m.park_hand(q[0], 1000);   // the smaller one is refused: the list again
+        if (!calls(2, 0) || m.buffer(1000, true, &p, &got) != hipSuccess || p != q[0] || !calls(2, 0)) return 7;
+        m.drop(p);
+        if (m.take_hand(2001, &p, &got) || !m.take_hand(2000, &p, &got) || p != q[1] || got != 2000 || m.take_hand(1, &p, &got) || !calls(2, 1)) return 8;
+        m.drop(q[1]);
+    }
+    if (!calls(2, 2) || !f.live.empty() || f.bad_frees) return 12;
+    f = FakeDev{};
+    f.budget = 10000;
+    {   // out of memory
+        DevMem m(fake_malloc, fake_free);
+        Lease res, band, ops;
+        if (m.workspace(DevMem::RES, 3000, res) != hipSuccess || !fresh(m, 3000, &q[0]) || !fresh(m, 3000, &q[1])) return 9;
+        m.keep(q[0], 3000);
+        m.park_hand(q[1], 3000);
+        if (m.workspace(DevMem::BAND, 4000, band) != hipSuccess || !band.get() || f.mallocs != 5 || f.is_live(q[0]) || f.is_live(q[1])) return 9;
+        if (!f.is_live(res.get()) || !calls(5, 2) || m.workspace(DevMem::RES, 3000, ops) != hipSuccess || ops.get() != res.get() || !calls(5, 2)) return 10;
+        if (m.workspace(DevMem::OPS, 5000, ops) != hipErrorOutOfMemory || ops.get() || !calls(7, 2) || !f.is_live(res.get()) || !f.is_live(band.get())) return 11;
+        if (m.buffer(5000, true, &p, &got) != hipErrorOutOfMemory || p || got || !calls(9, 2)) return 11;
+        if (!fresh(m, 1000, &q[0]) || !fresh(m, 1000, &q[1])) return 12;
+        m.keep(q[0], 1000);
+        m.park_hand(q[1], 1000);
+        if (!calls(11, 2) || f.live.size() != 4) return 12;
+    }
+    if (!calls(11, 6) || f.bad_frees) return 12;   // two slots, the parked buffer, the list
+    return f.live.empty() && f.used == 0 ? 0 : 13;
+}
+
 extern "C" {
 
 const char* pwa_version(void) { return "pwalign 0.1 gfx950"; }
@@ -1119,6 +1225,7 @@ int pwa_selftest_host(uint32_t seed) try {
     if (const int rc = selftest_align_plan(x, check + 5)) return rc;
     if (const int rc = selftest_wfa_plan(x, check + 11)) return rc;
     if (const int rc = selftest_pair_listing()) return check + 16 + rc;   // (the wavefront planner's checks end at check + 16)
+    if (const int rc = selftest_dev_mem()) return check + 20 + rc;
     return 0;
 } catch (...) {
     return -1;
@@ -1222,12 +1329,6 @@ void pwa_ctx_destroy(pwa_ctx* c) {
     for (auto& e : c->aux_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->band_cache) (void)hipFree(c->band_cache);
-    if (c->sband_cache) (void)hipFree(c->sband_cache);
-    if (c->hand_cache) (void)hipFree(c->hand_cache);
-    for (void* q : c->pool)
-        if (q) (void)hipFree(q);
-    for (auto& f : c->free_list) (void)hipFree(f.first);
     delete c;
 }
 

@@ -17,6 +17,7 @@
 
 #include "approx_ctx.h"
 #include "chain_ctx.h"
+#include "dev_mem.h"
 #include "kernel_table.h"
 #include "poison.h"
 #include "subst_table.h"
@@ -134,45 +135,24 @@ struct pwa_ctx {
     // pwa_pair_forms: pair_form_name of every form PairLaunch::build / build_mini resolved on this context (a batch object's launches:
     // on the context that created it), distinct, in first-seen order; only pwa_pair_forms_reset empties it
     std::vector<std::string> pair_forms;
-    // Traceback / score band workspaces of pwa_align*, kept between calls (grow-only, at most kBandCacheMax each):
-    // hipMalloc of several GiB is sometimes fast (0.3 ms) and sometimes not (0.2 - 1.5 s) depending on the state of the
-    // device's memory, and a caller that aligns batch after batch should pay it once.
-    void* band_cache = nullptr;
-    size_t band_cache_bytes = 0;
-    void* sband_cache = nullptr;
-    size_t sband_cache_bytes = 0;
-    // the strip hand-off workspace of the last destroyed batch (5.2 GB for C3): the next batch takes it over
-    void* hand_cache = nullptr;
-    size_t hand_cache_bytes = 0;
-    // pwa_align* work buffers (sequence arena, op lists, results, pair descriptors, task list, hand-off rows, progress words,
-    // per-stripe bests, queue): grow-only, reused by the next call -- a call that aligns a batch costs no hipMalloc / hipFree
-    // (each of which also synchronises the device) once the context has seen a batch of that size; pwa_align_batch_cigar's
-    // strings and their pair list / lengths / scan partials
-    enum { POOL_ARENA, POOL_OPS, POOL_RES, POOL_DESC, POOL_TASKS, POOL_ROWS, POOL_PROGRESS, POOL_BEST, POOL_QUEUE, POOL_STR, POOL_STR_AUX, POOL_N };
-    void* pool[POOL_N] = {};
-    size_t pool_bytes[POOL_N] = {};
-    // page-locked staging of everything the library itself uploads or reads back (see PinnedBuf)
+    pwa::DevMem mem;   // every device buffer the context keeps between calls: the pwa_align* slots, the parked hand-off buffer, the free list
     hipStream_t aux_stream = nullptr;                  // pwa_batch_run: the mini-stripe launches of a split batch run next to its stripe launch
     hipEvent_t aux_ev[2] = {nullptr, nullptr};         // fork / join of that
     hipStream_t copy_stream = nullptr;                 // uploads that overlap host work (build_arena)
     hipEvent_t copy_ev[2] = {nullptr, nullptr};
-    // Device buffers of destroyed batch objects, kept for the next one (DevBuf below): a steady stream of batches -- the runs of a
-    // one-shot call over a large list, a caller that builds batch after batch -- costs no hipMalloc and, more to the point, no
-    // hipFree: hipFree waits for ALL work on the device, i.e. for the kernels of the batch that is still running, and with it the
-    // overlap of preparing run k + 1 with computing run k would be gone (scores_in_arena_chunks).
-    std::vector<std::pair<void*, size_t>> free_list;
-    size_t free_list_bytes = 0;
+    // page-locked staging of everything the library itself uploads or reads back (see PinnedBuf)
     enum { PIN_ARENA, PIN_ARENA2, PIN_TASKS, PIN_SLOT0, PIN_SLOT1, PIN_SLOT2, PIN_SLOT3, PIN_SLOT4, PIN_DESC, PIN_TL, PIN_RES, PIN_BOUNCE, PIN_STR, PIN_N };
     PinnedBuf pin[PIN_N];
 };
-constexpr size_t kBandCacheMax = 64ull << 30;   // (288 GB of HBM per GPU: a 4096-pair batch with both bands is 33 GB)
 
 __global__ void pwa_nop_kernel(int* p);   // (pwalign_ctx.hip; PWA_PROBE / PWA_DEBUG launch it to time a submission)
 
 #pragma GCC visibility push(hidden)
 namespace pwa {
 
-struct DevBuf {   // RAII device allocation; with `pool` set, released buffers go to the context's free list and come back from it
+// RAII device buffer of a batch object or of one call, from ctx->mem; with `pool` set, released buffers go to the context's free list
+// and come back from it
+struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     pwa_ctx* pool = nullptr;
@@ -181,7 +161,10 @@ struct DevBuf {   // RAII device allocation; with `pool` set, released buffers g
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
     void release();
-    hipError_t alloc(pwa_ctx* ctx, size_t n);   // ctx: whose PWA_POISON applies (never null; `pool` only says where released buffers go)
+    hipError_t alloc(pwa_ctx* ctx, size_t n);   // ctx: whose memory and PWA_POISON (never null; `pool` only says where released buffers go)
+    // the strip hand-off workspace: the one an earlier batch of ctx parked if it holds n bytes, else alloc; and parking it (pooled buffers only)
+    hipError_t alloc_hand(pwa_ctx* ctx, size_t n);
+    void park_hand();
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
@@ -207,7 +190,7 @@ bool gap0_ok(uint64_t n_plus_m, int match, int mismatch, int gap);
 bool code_alphabet(const bool seen[256], uint8_t code_of[256], int match, int mismatch, int gap, const Knobs& knobs);
 int mini_rl_for(uint64_t n);
 int wide_rl_for(uint64_t n);
-hipError_t cached_workspace(pwa_ctx* ctx, void*& slot, size_t& slot_bytes, size_t bytes, DevBuf& fallback, void** out);
+hipError_t workspace(pwa_ctx* ctx, DevMem::Slot slot, size_t bytes, Lease& out);
 hipError_t upload_via_bounce(pwa_ctx* c, void* dst, const void* src, size_t bytes);
 hipError_t build_arena(pwa_ctx* c, void* d_arena, uint64_t arena_bytes, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seq,
                        const std::vector<uint8_t>& is_used, const std::vector<uint64_t>& aoff, const uint8_t* table, bool nul_free = false);
@@ -372,17 +355,11 @@ hipError_t banded_launch(const BandedForm& f, const PairParams& G, int row_cap, 
 // Device-side state of one launch of the wavefront (pair) engine: pair descriptors, the global
 // stripe-task list, hand-off rows, progress counters, per-stripe bests.
 struct PairLaunch {
-    DevBuf desc, tasks, rows, progress, best, queue;
-    bool from_pool = false;   // take the six buffers from the context's pool (one launch at a time per context: pwa_align*)
-    void *p_desc = nullptr, *p_tasks = nullptr, *p_rows = nullptr, *p_progress = nullptr, *p_best = nullptr, *p_queue = nullptr;
+    Lease desc, tasks, rows, progress, best, queue;
+    // where the six come from, said once before build(): buffers of the launch's own (pwa_align_matrices), the context's slots (one
+    // launch at a time per context: the other pwa_align* calls), or the free list (a batch object's launches)
+    enum { MEM_OWN, MEM_SLOTS, MEM_FREE_LIST } mem = MEM_OWN;
     size_t progress_bytes = 0;
-    hipError_t take(pwa_ctx* ctx, DevBuf& own, int slot, size_t bytes, void** out) {
-        if (bytes == 0) bytes = 16;
-        if (from_pool) return cached_workspace(ctx, ctx->pool[slot], ctx->pool_bytes[slot], bytes, own, out);
-        const hipError_t e = own.alloc(ctx, bytes);
-        *out = own.p;
-        return e;
-    }
     PairParams G{};
     PairForm form{};   // set and resolved by build() / build_mini()
     PairKernels k;

@@ -110,7 +110,9 @@ const char *pwa_strerror(int code);
  * must have; the parser of PWA_POISON's value on a list of good and bad spellings; the cutting of a list into runs under a budget
  * (chunks of patterns, slices of tasks, ranges of WFA pairs) on its edge cases and on random lists; that every form of
  * pwa_pair_form_table resolves to kernels, to a fill of its own wherever a field the fill depends on differs, and to a walk that
- * follows from engine class, rows per lane, lanes, mode and walk alone.  Returns 0, or the number of the first check that failed. */
+ * follows from engine class, rows per lane, lanes, mode and walk alone; and the context's device-memory policy (slot reuse and
+ * regrowth, the free list's best fit and caps, the parked hand-off buffer, the one retry after a failed allocation, teardown) over a
+ * counting fake allocator.  Returns 0, or the number of the first check that failed. */
 int pwa_selftest_host(uint32_t seed);
 
 /* Context = one GPU (HIP device ordinal) + its streams and workspaces. */

@@ -1,11 +1,12 @@
 """Every call on a context whose buffers start full of junk (PWA_POISON, include/pwalign.h; the audit table is in DESIGN.md 3.20).
 
-The library keeps device memory between calls (band caches, the eleven pool slots, the free list of batch buffers, the hand-off cache,
-page-locked staging) and never clears it on acquisition.  With PWA_POISON=<byte> every buffer a call is handed reads as that byte
-until the call writes it.  Each family below runs a list of probes twice in ONE poisoned context -- ascending size, then descending,
-so that small calls meet oversized retained buffers -- and compares every specified output, field for field, with the same probe on
-a fresh unpoisoned context with the same other switches.  The control's outputs are checked against the existing oracles on a seeded
-sample of at most 8 items per probe.  After every probe the context's poison counters must have grown: a run that poisons nothing
+The library keeps device memory between calls (the context's DevMem, dev_mem.h: the thirteen slots of the pwa_align* calls, the parked
+hand-off buffer, the free list of batch buffers; and the page-locked staging buffers) and never clears it on acquisition.  With
+PWA_POISON=<byte> every buffer a call is handed reads as that byte until the call writes it.  Each family below runs a list of probes
+twice in ONE poisoned context -- ascending size, then descending, so that small calls meet oversized retained buffers -- and compares
+every specified output, field for field, with the same probe on a fresh unpoisoned context with the same other switches; the mixed
+family does so across entry points, which share slots, the free list and the parked buffer.  The control's outputs are checked
+against the existing oracles on a seeded sample of at most 8 items per probe.  After every probe the context's poison counters must have grown: a run that poisons nothing
 cannot pass.  Everything is integer or byte exact."""
 import functools
 import random
@@ -700,6 +701,65 @@ def test_banded_class(name, byte):
             rows = [_banded_ext("gotoh", *pt, bd, 30)["rows"] for pt, bd in live]
             assert any(r < len(pt[0]) for r, (pt, bd) in zip(rows, live)) and any(r == len(pt[0]) for r, (pt, bd) in zip(rows, live)), size
     poisoned(("banded", name), BANDED_SETS[name], _banded_probes_once(), byte)
+
+
+# ====================================================================================== 5b. mixed: one context across entry points
+def _ends(probes, prefix=""):
+    """of the probes whose name starts with prefix: the first of the smallest size and the last of the largest"""
+    ps = [p for p in probes if p.name.startswith(prefix)]
+    lo, hi = min(p.size for p in ps), max(p.size for p in ps)
+    return [next(p for p in ps if p.size == lo), next(p for p in reversed(ps) if p.size == hi)]
+
+
+def _batch_probe(name, size, make, n, expect, kernel):
+    """one score batch without end cells: created, run, fetched, destroyed; it must have run on the strip kernel `kernel`, the only
+    user of the hand-off workspace"""
+    def run(c):
+        b = make(c)
+        try:
+            b.run()
+            return (b.fetch(), b.info()["kernel"])
+        finally:
+            b.close()
+
+    def check(out):
+        assert out[1].startswith(kernel), out[1]
+    return Probe(name, size, run, n, lambda out, k: out[0][k], expect, check)
+
+
+def _hand_off_batches():
+    """Three score batches that stay on the strips under the default route, with hand-off workspaces of 8 KiB, 16 KiB and 64 KiB or
+    more: the small strip list (one wave task, a text of 5 columns) as NW, one strip per task, and as SW, two; the large gotoh list
+    as NW, which the gotoh rule keeps on the strips -- 14 texts, so 14 tasks and 16 workgroups with 4 KiB and more each.  (The two
+    linear sizes are what a library that prints them reported; the bound of the third follows from setup_strips' formula.)  A
+    probe's size here is that figure in KiB: it only orders the probes."""
+    seqs, pa, pb = _strip_lists()[0][1]
+    pr = _gotoh_lists()[2][1]
+    gs, ga, gb = _seqs(pr)
+    lin = lambda mode: (lambda c: c.batch(mode, seqs, pa, pb, *LIN))
+    return [_batch_probe("batch/nw/small", 8, lin("nw"), len(pa), lambda k: _lin_score("nw", seqs[pa[k]], seqs[pb[k]])[0], "batch_scores_kernel<"),
+            _batch_probe("batch/sw/small", 16, lin("sw"), len(pa), lambda k: _lin_score("sw", seqs[pa[k]], seqs[pb[k]])[0], "batch_scores_kernel<"),
+            _batch_probe("batch/gotoh/nw/large", 64, lambda c: c.batch_gotoh("nw", gs, ga, gb, *AFF), len(pr),
+                         lambda k: _gotoh_align("gotoh", "nw", *pr[k])["score"], "batch_gotoh_kernel<")]
+
+
+@functools.lru_cache(maxsize=None)
+def _mixed_probes():
+    """The families above run in a context each; here ONE context, default switches, serves the two ends of five of them in turn --
+    the results slot and the traceback band are shared by the linear, gotoh, banded and hw3 alignment calls, the free list by every
+    score batch -- and three score batches whose strip hand-off workspaces grow from one to the next, so that the ascending pass
+    parks a larger buffer each time (the displaced one goes to the free list) and the descending pass takes over an oversized
+    one.  (The score probes are the first and the last of the strip lists': NW and SG, whose form checks are none -- the route is
+    the default one here.)"""
+    probes = (_ends(_score_probes("strips_int32")) + _ends(_family_probes(), "align_affine_batch/") + _ends(_align_probes_once(), "align_batch_cigar/") +
+              _ends(_gotoh_probes_once()) + _ends(_banded_probes_once()))
+    assert all(p.check is None for p in probes) and len({p.name for p in probes}) == 10
+    return probes + _hand_off_batches()
+
+
+@pytest.mark.parametrize("byte", POISON, ids=BYTE_IDS)
+def test_mixed_entry_points_in_one_context(byte):
+    poisoned(("mixed", "default"), {}, _mixed_probes(), byte)
 
 
 # ====================================================================================== 6. hw1: suffix arrays and exact search
