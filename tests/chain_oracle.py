@@ -274,3 +274,115 @@ def random_anchors(rng, n, span=400, max_len=20):
     if n > 2 and rng.random() < 0.5:
         out[rng.randrange(n)] = out[rng.randrange(n)]
     return sorted(out, key=lambda a: (a[0] + a[2], a[1] + a[2]))
+
+
+# ---- inputs where one far predecessor decides: every chunk of the kernel's window, every tie of its key maximum, every walk hop
+
+def far_predecessor(d):
+    """d + 1 anchors whose last one has exactly one admissible predecessor, anchor 0, d back: the d - 1 anchors between them end at
+    the last anchor's text position (dx = 0), far off its diagonal, and have no predecessor themselves.  Under the default
+    parameters (any bandwidth, any gap_scale) pred[-1] == 0 and f[-1] == 20 when d <= lookback, pred[-1] == -1 and f[-1] == 10
+    otherwise, and every other pred is -1"""
+    return [(100, 100, 10)] + [(129, 0, 1)] * (d - 1) + [(120, 120, 10)]
+
+
+def equal_predecessor(d):
+    """far_predecessor(d) with a last anchor that starts where anchor 0 starts and is twice as long: dx == dy == 10, so cand is
+    10 + 10 == len of the last anchor, which is not enough: every pred is -1, f[-1] == 20 and the chain is the last anchor alone,
+    whatever the lookback.  (A kernel that takes cand >= len would answer pred[-1] == 0 when d <= lookback)"""
+    return [(100, 100, 10)] + [(119, 0, 1)] * (d - 1) + [(100, 100, 20)]
+
+
+def ladder(d, n, bw=3, step=7, ln=5):
+    """n anchors on d diagonals bw + 1 apart, taken in turn: anchor i is on diagonal 4000 - (i % d) * (bw + 1), text ends `step` apart.
+    With bandwidth <= bw and gap_scale 0 the admissible predecessors of i are i - d, i - 2 d, ..., and i - d has the largest cand, so
+    pred[i] == i - d and f[i] == ln * (i // d + 1) for every i >= d when d <= lookback, and every pred is -1 when d > lookback.  The
+    chain of d <= lookback hops by exactly d on one diagonal: last == d * ((n - 1) // d), the smallest index of maximal f, and
+    count == (n - 1) // d + 1; with n == 2 * d + 70 and d >= 70 that is last == 2 * d, the first of 70 equal f, and count == 3"""
+    assert d >= 1 and (d - 1) * (bw + 1) < 4000 and step >= ln
+    return [(step * i + 4000, step * i + (i % d) * (bw + 1), ln) for i in range(n)]
+
+
+def two_way_tie(o1, o2, far_len=10):
+    """o2 + 2 anchors whose last one, i, has exactly two admissible predecessors, i - 1 - o1 and i - 1 - o2 (o1 < o2), under
+    bandwidth 1, gap_scale 0, max_dist 10000 and any lookback > o2.  The last anchor is on diagonal D, the two on D + 1 and D - 1,
+    every other anchor alone on a diagonal 10 * (offset + 2) above D; text ends are 12 apart and len is 10, so alpha is len.  The
+    nearer one has len 10, the farther one far_len: with 10 the two cand are equal and pred[-1] is the nearer one, n - 2 - o1, with
+    f[-1] == 20; with 11 the farther one wins, pred[-1] == n - 2 - o2 == 0 and f[-1] == 21.  Every other pred is -1"""
+    assert 0 <= o1 < o2 <= 511 and far_len >= 1
+    n, D, out = o2 + 2, 100, []
+    for k in range(n):
+        o = n - 2 - k   # the offset in the last anchor's window; -1: the last anchor itself
+        diag, ln = (D, 10) if o < 0 else (D + 1, 10) if o == o1 else (D - 1, far_len) if o == o2 else (D + 10 * (o + 2), 10)
+        x = 6000 + 12 * k
+        out.append((x - ln, x - diag - ln, ln))
+    return out
+
+
+EDGE_LOOKBACKS = [1, 63, 64, 65, 127, 128, 129, 192, 255, 256, 257, 448, 511, 512]   # both sides of every kernel_for threshold
+EDGE_PARAMS = dict(bandwidth=3, gap_scale=0)
+WALK_HOPS = [64, 65, 200, 512]
+TIE_OFFSETS = [(0, 1), (1, 2), (2, 3), (3, 4), (7, 8), (15, 16), (31, 32), (47, 48), (63, 64), (64, 127), (127, 128), (5, 300), (255, 256),
+               (510, 511), (0, 511)]   # the two lanes in one quad, two quads, two halves of a row, two rows, two chunks
+TIE_PARAMS = dict(bandwidth=1, gap_scale=0, max_dist=10000)   # every builder above keeps its promise under these, too
+_far = {}
+
+
+def chunks_of(lookback):
+    """the C of the chain_kernel<C> that kernel_for(lookback) picks"""
+    return 1 if lookback <= 64 else 2 if lookback <= 128 else 4 if lookback <= 256 else 8
+
+
+def ladder_with_tail():
+    """ladder(512, 1100) and then 100 anchors in a row on a far diagonal: the best chain is the tail, whole, and never enters the ladder"""
+    return ladder(512, 1100) + [(30000 + 5 * k, 5 * k, 5) for k in range(100)]
+
+
+def repeat_reads():
+    """60 planted reads of 300 .. 2000 symbols at 5 % on a 40 kb text that holds a 500-base unit 8 times, seeded with k = 12, step 1,
+    max_occ 64: where a read meets the unit its anchors come in eights, and predecessors far back in the window compete"""
+    if "repeat" not in _far:
+        import random
+        rng = random.Random(41)
+        text = random_text(rng, 40000, repeat=500, copies=8)
+        index = kmer_index(text, 12)
+        _far["repeat"] = [seed(index, read, 12, 1, 64) for read, _, _ in planted_reads(rng, text, 60, (300, 2000), 0.05)]
+    return _far["repeat"]
+
+
+def far_cases():
+    """the calls of test_gpu_chain.py's far-window tests, built without a GPU: [dict(name, params, reads, labels)], labels[r] naming
+    the builder and the arguments of reads[r] -- ("far", d), ("ladder", d, n), ("equal", d), ("tie", o1, o2, far_len), ("tail",),
+    ("seeded",), ("few",) -- so that a test can hold the call's result to what the builder promises (test_chain_oracle.py holds the list itself
+    to the oracle and shows which mistakes in the recurrence it catches)"""
+    if "cases" in _far:
+        return _far["cases"]
+    cases = []
+    for H in EDGE_LOOKBACKS:
+        ds = [d for d in sorted({1, H - 1, H, H + 1}) if d >= 1]
+        cases.append(dict(name="edges-%d" % H, params=dict(EDGE_PARAMS, lookback=H),
+                          reads=[r for d in ds for r in (far_predecessor(d), ladder(d, 2 * d + 70), equal_predecessor(d))],
+                          labels=[l for d in ds for l in (("far", d), ("ladder", d, 2 * d + 70), ("equal", d))]))
+    cases.append(dict(name="walk", params=dict(EDGE_PARAMS, lookback=512), reads=[ladder(d, 5 * d + 3) for d in WALK_HOPS] + [ladder_with_tail()],
+                      labels=[("ladder", d, 5 * d + 3) for d in WALK_HOPS] + [("tail",)]))
+    ties = [(o1, o2, fl) for o1, o2 in TIE_OFFSETS for fl in (10, 11)]
+    cases.append(dict(name="ties", params=dict(TIE_PARAMS, lookback=512), reads=[two_way_tie(*t) for t in ties], labels=[("tie",) + t for t in ties]))
+    for C in (1, 2, 4, 8):   # the farther candidate in the window's last slot: one call per lookback, in the order of the kernels
+        for H in sorted({o2 + 1 for _, o2 in TIE_OFFSETS if chunks_of(o2 + 1) == C}):
+            own = [t for t in ties if t[1] + 1 == H]
+            cases.append(dict(name="ties-%d" % H, params=dict(TIE_PARAMS, lookback=H), reads=[two_way_tie(*t) for t in own], labels=[("tie",) + t for t in own]))
+    import random
+    seen, mixed = set(), []
+    for c in cases:   # every read above, once
+        for a, l in zip(c["reads"], c["labels"]):
+            if l not in seen:
+                seen.add(l)
+                mixed.append((a, l))
+    random.Random(7).shuffle(mixed)
+    few = [[], [(7, 3, 5)], [], [(0, 0, 1)]]
+    mixed = [p for i, m in enumerate(mixed) for p in ([m, (few[i // 3 % 4], ("few",))] if i % 3 == 0 else [m])]
+    cases.append(dict(name="mixed", params=dict(TIE_PARAMS, lookback=512), reads=[a for a, _ in mixed], labels=[l for _, l in mixed]))
+    for H in (200, 512):
+        cases.append(dict(name="seeded-%d" % H, params=dict(lookback=H), reads=repeat_reads(), labels=[("seeded",)] * len(repeat_reads())))
+    _far["cases"] = cases
+    return cases

@@ -98,6 +98,93 @@ def test_planted_reads_on_a_text_with_a_repeat():
         assert c["diag_lo"] <= c["t_begin"] - c["q_begin"] <= c["diag_hi"]
 
 
+MUTANTS = ["win+1", "win-1", "dead64", "dead128", "dead192", "dead256", "dead448", "stale64", "stale128", "stale256", "tie_small_j", "nonstrict"]
+
+
+def dp_mutant(reads, mut=None, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38):
+    """chain_oracle.dp of every read with one named mistake (None: none), the way a kernel that keeps its window in chunks of 64 lanes
+    could be wrong -> [(f, pred)].  Written per anchor over numpy arrays of the window, j descending (offset 0 first):
+        win+1 / win-1   the window is one longer / one shorter
+        deadK           a predecessor at offset >= K (offset: i - 1 - j) is never admissible
+        staleK          a predecessor at offset >= K is read one lane stale: x, y and f are those of j + 1
+        tie_small_j     the smallest j among equal cand
+        nonstrict       cand >= len_i takes the link"""
+    import numpy as np
+    H = lookback + (mut == "win+1") - (mut == "win-1")
+    dead = int(mut[4:]) if mut and mut.startswith("dead") else 1 << 30
+    stale = int(mut[5:]) if mut and mut.startswith("stale") else 1 << 30
+    out = []
+    for anchors in reads:
+        n = len(anchors)
+        A = np.asarray(anchors, dtype=np.int64).reshape(-1, 3)
+        X, Y, L = A[:, 0] + A[:, 2], A[:, 1] + A[:, 2], A[:, 2]
+        F, P = np.zeros(n, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+        for i in range(n):
+            off = np.arange(min(i, H))
+            j = i - 1 - off
+            src = np.where(off >= stale, j + 1, j)
+            dx, dy = X[i] - X[src], Y[i] - Y[src]
+            dd = np.abs(dx - dy)
+            adm = (dx > 0) & (dx <= max_dist) & (dy > 0) & (dy <= max_dist) & (dd <= bandwidth) & (off < dead)
+            F[i] = L[i]
+            if not adm.any():
+                continue
+            dx, dy, dd, ja = dx[adm], dy[adm], dd[adm], j[adm]
+            bt = np.where(dd > 0, ((gap_scale * dd) >> 8) + ((np.frexp(np.maximum(dd, 1).astype(np.float64))[1] - 1) >> 1), 0)   # CO.beta
+            cand = F[src[adm]] + np.minimum(L[i], np.minimum(dx, dy)) - bt
+            best = cand.max()
+            if best >= L[i] if mut == "nonstrict" else best > L[i]:
+                F[i] = best
+                P[i] = ja[cand == best].min() if mut == "tie_small_j" else ja[cand == best].max()
+        out.append((F.tolist(), P.tolist()))
+    return out
+
+
+def noticed(case, mut):
+    """the reads of a case whose (f, pred) change under a mistake"""
+    if mut.startswith(("dead", "stale")) and int(mut.lstrip("adelst")) >= case["params"]["lookback"]:
+        return []   # no offset of this window is that large
+    return [r for r, (a, b) in enumerate(zip(case["dp"], dp_mutant(case["reads"], mut, **case["params"]))) if a != b]
+
+
+def test_the_far_window_cases_tell_a_wrong_recurrence_from_the_right_one():
+    """every call of the GPU suite's far-window tests is valid input; dp_mutant without a mistake is the oracle's dp; and each
+    mistake changes (f, pred) of at least one read -- of the edge, walk and tie cases for the window, the chunks and the ties, and
+    of the seeded list for dead128, which is what that list is there for.  This is the proof that those GPU tests would notice a
+    kernel with a dead or shifted chunk; no broken kernel is ever run"""
+    cases = CO.far_cases()
+    assert {c["params"]["lookback"] for c in cases} >= set(CO.EDGE_LOOKBACKS)
+    assert {CO.chunks_of(c["params"]["lookback"]) for c in cases} == {1, 2, 4, 8}
+    for c in cases:
+        assert len(c["reads"]) == len(c["labels"]) > 0
+        assert CO.validate(c["reads"], **c["params"]) == (0, None), c["name"]
+        c["dp"] = [(w["f"], w["pred"]) for w in CO.chain_many_fast(c["reads"], **c["params"])]
+        if not c["name"].startswith("seeded") and c["name"] != "mixed":   # those two: the lockstep form, held to dp() above
+            assert c["dp"] == [CO.dp(a, **c["params"]) for a in c["reads"]], c["name"]
+        assert dp_mutant(c["reads"], None, **c["params"]) == c["dp"], c["name"]
+    built = [c for c in cases if not c["name"].startswith("seeded") and c["name"] != "mixed"]   # mixed repeats their reads
+    for mut in MUTANTS:
+        hits = sum(len(noticed(c, mut)) for c in built)
+        print(mut, hits)
+        assert hits >= 1, mut
+    for c in cases:
+        if c["name"].startswith("seeded"):
+            assert noticed(c, "dead128"), c["name"]
+            assert max(len(a) for a in c["reads"]) > 2000
+
+
+def test_the_earlier_inputs_do_not_reach_beyond_offset_127():
+    """why the far-window cases exist: on the inputs of test_anchor_counts_around_the_block_and_the_window a window that is dead, or one
+    lane stale, from offset 128 on changes nothing"""
+    from test_gpu_chain import block_and_window_inputs
+    for lookback in (1, 63, 64, 65, 128, 512):
+        reads, params = block_and_window_inputs(lookback)
+        want = [CO.dp(a, **params) for a in reads]
+        assert dp_mutant(reads, None, **params) == want
+        for mut in ("dead128", "stale128"):
+            assert dp_mutant(reads, mut, **params) == want, (lookback, mut)
+
+
 def test_ranges_and_validation_of_the_oracle():
     assert CO.ranges([], 0) == [] and CO.ranges([0, 0], 0) == []
     assert CO.ranges([3, 0, 2], 0) == [(0, 3)]

@@ -37,14 +37,20 @@ def test_the_empty_list_and_reads_with_few_anchors(ctx):
     assert ctx.chain_stats["anchors"] == 6 and ctx.chain_stats["ranges"] == 1
 
 
+def block_and_window_inputs(lookback):
+    """-> (reads, parameters) of the test below (test_chain_oracle.py shows what these inputs do not reach)"""
+    rng = random.Random(lookback)
+    reads = [CO.random_anchors(rng, n, span=rng.choice([60, 400]), max_len=12) for n in COUNTS]
+    reads += [[(100 + 3 * i, 3 * i, 2) for i in range(n)] for n in (64, 513)]   # every predecessor admissible, f grows along the window
+    return reads, dict(lookback=lookback, max_dist=rng.choice([50, 5000]))
+
+
 @pytest.mark.parametrize("lookback", [1, 63, 64, 65, 128, 512])
 def test_anchor_counts_around_the_block_and_the_window(ctx, lookback):
     """63 .. 513 anchors (a block of the kernel is 64) against windows of 1 .. 512 (a chunk is 64), n < H included; the anchors sit
     densely around one diagonal, so that every window is full of admissible predecessors"""
-    rng = random.Random(lookback)
-    reads = [CO.random_anchors(rng, n, span=rng.choice([60, 400]), max_len=12) for n in COUNTS]
-    reads += [[(100 + 3 * i, 3 * i, 2) for i in range(n)] for n in (64, 513)]   # every predecessor admissible, f grows along the window
-    got = check(ctx, reads, lookback=lookback, max_dist=rng.choice([50, 5000]))
+    reads, params = block_and_window_inputs(lookback)
+    got = check(ctx, reads, **params)
     assert max(g["count"] for g in got) > 20
 
 
@@ -136,6 +142,113 @@ def test_a_ragged_list_in_ranges_and_over_poisoned_buffers(ctx):
         with switched_context(PWA_POISON=byte, PWA_RANGE_BYTES=budget) as c:
             assert c.chain(reads, want_dp=True) == plain
             assert c.chain_stats["ranges"] == n_ranges
+
+
+def far_case(name):
+    return next(c for c in CO.far_cases() if c["name"] == name)
+
+
+def hold(label, g, H):
+    """what the builder of a far-window read promises (chain_oracle.py), asserted on the call's own result: a mistake that the kernel
+    and the oracle share would still show here"""
+    kind, n = label[0], len(g["pred"])
+    top = (g["score"], g["count"], g["last"])
+    if kind == "far":
+        d = label[1]
+        assert g["pred"] == [-1] * d + [0 if d <= H else -1], label
+        assert g["f"] == [10] + [1] * (d - 1) + [20 if d <= H else 10], label
+        assert top == ((20, 2, d) if d <= H else (10, 1, 0)), label
+    elif kind == "equal":
+        d = label[1]
+        assert g["pred"] == [-1] * (d + 1) and g["f"][-1] == 20 and top == (20, 1, d), label
+    elif kind == "ladder":
+        d = label[1]
+        assert n == label[2]
+        if d <= H:
+            assert g["pred"] == [i - d if i >= d else -1 for i in range(n)], label
+            assert g["f"] == [5 * (i // d + 1) for i in range(n)], label
+            assert top == (5 * ((n - 1) // d + 1), (n - 1) // d + 1, d * ((n - 1) // d)), label
+            if n == 2 * d + 70 and d >= 70:
+                assert top == (15, 3, 2 * d), label
+        else:
+            assert g["pred"] == [-1] * n and top == (5, 1, 0), label
+        assert g["diag_lo"] == g["diag_hi"] == 4000, label   # one rung is one diagonal, and every chain found ends on rung 0
+    elif kind == "tie":
+        o1, o2, far_len = label[1:]
+        assert n == o2 + 2 and H > o2
+        assert g["pred"] == [-1] * (n - 1) + [n - 2 - (o1 if far_len == 10 else o2)], label
+        assert g["f"][-1] == 10 + far_len and top == (10 + far_len, 2, n - 1), label
+    elif kind == "tail":
+        assert top == (500, 100, 1199) and g["pred"][1100] == -1 and g["diag_lo"] == g["diag_hi"] == 30000, label
+    else:
+        assert kind == "few" and n <= 1
+
+
+def run_case(ctx, c):
+    got = check(ctx, c["reads"], fast=True, **c["params"])
+    for label, g in zip(c["labels"], got):
+        hold(label, g, c["params"]["lookback"])
+    return got
+
+
+@pytest.mark.parametrize("lookback", CO.EDGE_LOOKBACKS)
+def test_the_deciding_predecessor_at_both_edges_of_the_window(ctx, lookback):
+    """the one predecessor that counts at offset 0, H - 2, H - 1 (the window's last slot) and H (one beyond it), for H on both sides of
+    every threshold between chain_kernel<1>, <2>, <4> and <8>: as a single link (far), along a whole read (ladder, whose walk then
+    hops by that distance), and with a cand that only equals len (equal)"""
+    c = far_case("edges-%d" % lookback)
+    assert {l[1] for l in c["labels"]} == {d for d in (1, lookback - 1, lookback, lookback + 1) if d >= 1}
+    run_case(ctx, c)
+
+
+def test_walks_that_skip_whole_blocks_and_one_that_stays_in_its_tail(ctx):
+    """hops of 64, 65, 200 and 512 anchors, five in a row: the walk leaves its block of 64 pred words with every hop and lands in an
+    earlier one at lane 0, 63, 62, ... of it; and a read whose best chain is its last 100 anchors, behind a ladder it must not enter"""
+    c = far_case("walk")
+    got = run_case(ctx, c)
+    assert [g["count"] for g in got[:-1]] == [6, 6, 6, 6] and all(g["count"] >= 5 for g in got)
+    assert [g["last"] for g in got[:-1]] == [5 * d for d in CO.WALK_HOPS]
+
+
+def test_ties_between_two_lanes_of_the_key_maximum(ctx):
+    """two admissible predecessors and no third, in one quad, in two quads of a row, in two rows, in two chunks: equal cand (the
+    nearer, the larger j, wins) and the farther better by one; at lookback 512, and with the farther one in the window's last slot"""
+    run_case(ctx, far_case("ties"))
+    kernels = []
+    for c in CO.far_cases():
+        if c["name"].startswith("ties-"):
+            assert {o2 + 1 for _, _, o2, _ in c["labels"]} == {c["params"]["lookback"]}
+            kernels.append(CO.chunks_of(c["params"]["lookback"]))
+            run_case(ctx, c)
+    assert kernels == sorted(kernels) and set(kernels) == {1, 2, 4, 8}
+
+
+def test_the_far_window_reads_in_mixed_order_in_ranges_and_over_poisoned_buffers(ctx):
+    """every read of the three tests above in one call, shuffled among empty and one-anchor reads; again with a budget that the
+    longest read alone exceeds (the planner's arm "one read that alone exceeds it"), and again over poisoned buffers"""
+    c = far_case("mixed")
+    reads, params = c["reads"], c["params"]
+    counts = [len(a) for a in reads]
+    assert counts.count(0) > 10 and counts.count(1) > 10 and len(reads) - c["labels"].count(("few",)) == len(set(c["labels"])) - 1
+    plain = run_case(ctx, c)
+    weight = lambda r: CO.ANCHOR_BYTES * counts[r] + CO.RECORD_BYTES
+    budget = max(weight(r) for r in range(len(reads))) // 2
+    cut = CO.ranges(counts, budget)
+    assert budget >= 4096 and any(k1 - k0 == 1 and weight(k0) > budget for k0, k1 in cut) and len(cut) > 10
+    with switched_context(PWA_RANGE_BYTES=budget) as k:
+        assert k.chain(reads, want_dp=True, **params) == plain
+        assert k.chain_stats["ranges"] == len(cut) and k.chain_stats["anchors"] == sum(counts)
+    with switched_context(PWA_POISON="0xA5") as k:
+        assert k.chain(reads, want_dp=True, **params) == plain
+        assert k.poison_stats()["buffers"] > 0
+
+
+@pytest.mark.parametrize("lookback", [200, 512])
+def test_seeded_reads_on_a_text_with_eight_copies_of_a_unit(ctx, lookback):
+    """a real seeded list whose anchors are dense enough that predecessors beyond offset 127 win (test_chain_oracle.py: ignoring them
+    changes this list's result), through chain_kernel<4> and <8>"""
+    got = check(ctx, CO.repeat_reads(), fast=True, lookback=lookback)
+    assert max(i - p for g in got for i, p in enumerate(g["pred"]) if p >= 0) > 128
 
 
 def test_validation_matches_the_plan(ctx, pkg):
