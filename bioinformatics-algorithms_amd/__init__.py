@@ -42,6 +42,7 @@ EXPORTS = [
     "pwa_cigar_bound", "pwa_mdz_bound", "pwa_format_alignment", "pwa_alignment_overlap",
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
+    "pwa_seed_plan", "pwa_sa_seed", "pwa_sa_seed_fetch", "pwa_sa_seed_last_stats",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
     "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
@@ -143,6 +144,22 @@ def chain_plan(anchors, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38,
     rc = L.pwa_chain_plan(_u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), len(off) - 1, lookback, max_dist, bandwidth,
                           gap_scale, budget, C.byref(bad), C.byref(nr))
     return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, ranges=nr.value)
+
+
+def seed_plan(text_len, read_lens, k, step=1, max_occ=64, budget=0):
+    """pwa_seed_plan (host only): what TextIndex.seed would answer to reads of these lengths on a text of text_len bytes before any
+    device work -> dict(code, bad_read, slots, ranges): the validation code (0, or a negative PWA_E_* value), the first offending
+    read (None: none, or a parameter or the total was at fault), the list's slots, the ranges of reads the call would run under a
+    budget of `budget` worst-case hits (0: the library's)."""
+    import numpy as np
+    L = lib()
+    off = np.zeros(len(read_lens) + 1, dtype=np.uint64)
+    if len(read_lens):
+        off[1:] = np.cumsum(np.asarray(read_lens, dtype=np.uint64), dtype=np.uint64)
+    bad, ns, nr = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.pwa_seed_plan(text_len, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(read_lens), k, step, max_occ, budget, C.byref(bad), C.byref(ns),
+                         C.byref(nr))
+    return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, slots=ns.value, ranges=nr.value)
 
 
 _COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
@@ -360,6 +377,10 @@ def lib():
     L.pwa_sa_last_stats.argtypes = [vp, u32p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.pwa_sa_destroy.argtypes = [vp]
     L.pwa_sa_destroy.restype = None
+    L.pwa_seed_plan.argtypes = [C.c_uint64, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u64p, u64p]
+    L.pwa_sa_seed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p]
+    L.pwa_sa_seed_fetch.argtypes = [vp, u32p, u32p, C.c_uint64]
+    L.pwa_sa_seed_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p, u64p]
     L.pwa_approx_find.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u32p, i32p, u32p]
     L.pwa_approx_occurrences.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
     L.pwa_approx_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
@@ -1375,80 +1396,38 @@ class Context:
             out.append(d)
         return out
 
+    def index(self, text):
+        """A TextIndex of text: its suffix array, built once on the device and kept for any number of seed() / map_reads() calls."""
+        return TextIndex(self, text)
+
     def seed(self, text, reads, k, step=1, max_occ=64, as_arrays=False):
-        """Exact k-mer anchors of every read in the text: one suffix-array index of the text per call, the k-mers read[q:q + k] at
-        q = 0, step, 2 step, ... through pwa_sa_find and pwa_sa_occurrences; a k-mer with more than max_occ occurrences is dropped.
-        -> per read its anchors (t, q, k) in the order chain() requires (by t, then q), as a list of tuples, or with as_arrays as a
-        uint32 array of shape (n, 3)."""
-        import numpy as np
+        """Exact k-mer anchors of every read in the text (bytes: a temporary index of it is built; or a TextIndex), pwa_sa_seed: the
+        k-mers read[q:q + k] at q = 0, step, 2 step, ... are cut, searched, gathered and sorted on the device; a k-mer with more than
+        max_occ occurrences is dropped.  -> per read its anchors (t, q, k) in the order chain() requires (by t, then q), as a list of
+        tuples, or with as_arrays as a uint32 array of shape (n, 3).  Sets seed_stats = dict(search_ms, sort_ms, slots, hits, ranges)."""
+        if isinstance(text, TextIndex):
+            return text.seed(reads, k, step, max_occ, as_arrays)
         if k < 1 or step < 1 or max_occ < 1:
             raise ValueError("seed: k, step and max_occ are at least 1")
-        text = _b(text)
-        reads = [_b(r) for r in reads]
-        n = len(text)
-        qs = [np.arange(0, len(r) - k + 1, step, dtype=np.int64) if len(r) >= k else np.zeros(0, dtype=np.int64) for r in reads]
-        n_pat = int(sum(len(a) for a in qs))
-        empty = np.zeros((0, 3), dtype=np.uint32)
-        if not n_pat or n < k:
-            return [empty.copy() if as_arrays else [] for _ in reads]
-        pat_read = np.repeat(np.arange(len(reads), dtype=np.int64), [len(a) for a in qs])
-        pat_q = np.concatenate(qs)
-        kmers = np.concatenate([np.lib.stride_tricks.sliding_window_view(np.frombuffer(r, dtype=np.uint8), k)[::step].reshape(-1)
-                                for r in reads if len(r) >= k])
-        u64p = C.POINTER(C.c_uint64)
-        # the index takes a text whose last byte is its terminator: one is appended, and a hit that runs into it is dropped below
-        ix = self._sa_index(text + b"\0")
-        try:
-            off = np.arange(n_pat + 1, dtype=np.uint64) * np.uint64(k)
-            cnt = np.zeros(n_pat, dtype=np.uint32)
-            self._check(self._L.pwa_sa_find(ix, kmers.ctypes.data_as(C.c_void_p), off.ctypes.data_as(u64p), n_pat, _u32p(cnt)), "pwa_sa_find")
-            keep = np.flatnonzero((cnt > 0) & (cnt <= max_occ + 1))   # + 1: the one hit the terminator can add
-            if not keep.size:
-                return [empty.copy() if as_arrays else [] for _ in reads]
-            sub = np.ascontiguousarray(kmers.reshape(n_pat, k)[keep]).reshape(-1)
-            sub_off = np.arange(keep.size + 1, dtype=np.uint64) * np.uint64(k)
-            cap = int(cnt[keep].sum())
-            occ_off = np.zeros(keep.size + 1, dtype=np.uint64)
-            occ = np.zeros(max(cap, 1), dtype=np.uint64)
-            rs, hr, need = (C.c_uint32 * 2)(0, n + 1), (C.c_uint32 * 1)(0), C.c_uint64(0)
-            self._check(self._L.pwa_sa_occurrences(ix, sub.ctypes.data_as(C.c_void_p), sub_off.ctypes.data_as(u64p), keep.size, rs, 1, hr,
-                                                   occ_off.ctypes.data_as(u64p), occ.ctypes.data_as(u64p), cap, C.byref(need)), "pwa_sa_occurrences")
-            self._sa_stats(ix)
-        finally:
-            self._L.pwa_sa_destroy(ix)
-        per = np.diff(occ_off.astype(np.int64))
-        hit_pat = np.repeat(np.arange(keep.size, dtype=np.int64), per)
-        t = (occ[:int(occ_off[-1])] & np.uint64(0xffffffff)).astype(np.int64)
-        inside = t + k <= n
-        hit_pat, t = hit_pat[inside], t[inside]
-        few = np.bincount(hit_pat, minlength=keep.size) <= max_occ
-        sel = few[hit_pat]
-        hit_pat, t = keep[hit_pat[sel]], t[sel]
-        r, q = pat_read[hit_pat], pat_q[hit_pat]
-        order = np.lexsort((q, t, r))
-        r, q, t = r[order], q[order], t[order]
-        trip = np.stack([t, q, np.full(t.size, k, dtype=np.int64)], axis=1).astype(np.uint32)
-        cut = np.searchsorted(r, np.arange(len(reads) + 1))
-        if as_arrays:
-            return [trip[cut[i]:cut[i + 1]] for i in range(len(reads))]
-        rows = trip.tolist()
-        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(len(reads))]
+        with TextIndex(self, text) as ix:
+            return ix.seed(reads, k, step, max_occ, as_arrays)
 
     def map_reads(self, text, reads, k, match, mismatch, gap_open, gap_extend, w=100, step=1, max_occ=64, both_strands=False, lookback=64,
                   max_dist=5000, bandwidth=500, gap_scale=38):
-        """Seed, chain, align: seed() of every read (with both_strands also of its reverse complement; the strand with the higher
+        """Seed, chain, align (text: bytes, or a TextIndex kept across calls): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
         chain score is kept, ties go forward), chain() of the anchors, then align_banded_batch_cigar("sg", ...) of the read against
         the text window [max(0, t_begin - q_begin - w), min(len(text), t_end + (n - q_end) + w)) in the band (diag_lo - window start -
         w, diag_hi - window start + w).  -> per read dict(pos, end, score, cigar, mdz, strand, chain_score) in text coordinates
         (strand '+' or '-'; cigar and mdz are of the aligned strand), or None for a read without a chain, or whose band is wider than
         the banded call's 4096 or fails its semi-global validity rule.  Sets map_stats = dict(seed_s, chain_s, align_s): wall seconds."""
         import time
-        text = _b(text)
+        index = text if isinstance(text, TextIndex) else None   # bytes: seed() builds a temporary index, inside seed_s
+        text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
         nr = len(fw)
         strands = [fw, [revcomp(r) for r in fw]] if both_strands else [fw]
         t0 = time.perf_counter()
-        anchors = self.seed(text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+        anchors = self.seed(index or text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
         t1 = time.perf_counter()
         chains = self.chain(anchors, lookback, max_dist, bandwidth, gap_scale)
         t2 = time.perf_counter()
@@ -1477,6 +1456,64 @@ class Context:
         for (i, strand, ws, cs), a in zip(placed, al):
             out[i] = dict(pos=ws + a["start"][1], end=ws + a["end"][1], score=a["score"], cigar=a["cigar"], mdz=a["mdz"], strand=strand, chain_score=cs)
         return out
+
+
+class TextIndex:
+    """The suffix-array index of one text, resident on the context's GPU (pwa_sa_create): built once, then seeded against by any number
+    of read lists (pwa_sa_seed).  Keeps the text bytes (map_reads cuts its windows from them).  stats = dict(rounds, build_ms) of the
+    build; close() frees it, and it works as a context manager.  Close it before its context."""
+
+    def __init__(self, ctx, text):
+        self._ctx, self._L = ctx, ctx._L
+        self.text = _b(text)
+        self._ix = ctx._sa_index(self.text)
+        ctx._sa_stats(self._ix)
+        self.stats = dict(rounds=ctx.sa_stats["rounds"], build_ms=ctx.sa_stats["build_ms"])
+        self.seed_stats = None
+
+    def close(self):
+        if getattr(self, "_ix", None):
+            self._L.pwa_sa_destroy(self._ix)
+            self._ix = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def seed(self, reads, k, step=1, max_occ=64, as_arrays=False):
+        """pwa_sa_seed + pwa_sa_seed_fetch: Context.seed on this index -> per read its anchors (t, q, k) by t, then q, as a list of
+        tuples or, with as_arrays, a uint32 array of shape (n, 3).  Sets seed_stats = dict(search_ms, sort_ms, slots, hits, ranges)
+        here and on the context: device ms of the search kernel and of gather + sort + split, the list's k-mers, the hits kept, the
+        ranges of reads the call ran."""
+        import numpy as np
+        if k < 1 or step < 1 or max_occ < 1:
+            raise ValueError("seed: k, step and max_occ are at least 1")
+        if not self._ix:
+            raise PwaError("TextIndex.seed: the index is closed")
+        reads = [_b(r) for r in reads]
+        n = len(reads)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(r) for r in reads])
+        u64p = C.POINTER(C.c_uint64)
+        anc_off = np.zeros(n + 1, dtype=np.uint64)
+        ck = self._ctx._check
+        ck(self._L.pwa_sa_seed(self._ix, b"".join(reads), off.ctypes.data_as(u64p), n, k, step, max_occ, anc_off.ctypes.data_as(u64p)), "pwa_sa_seed")
+        total = int(anc_off[n])
+        trip = np.empty((total, 3), dtype=np.uint32)
+        t, q = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.uint32)
+        ck(self._L.pwa_sa_seed_fetch(self._ix, _u32p(t), _u32p(q), total), "pwa_sa_seed_fetch")
+        trip[:, 0], trip[:, 1], trip[:, 2] = t[:total], q[:total], k
+        sm, om, ns, nh, nr = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ck(self._L.pwa_sa_seed_last_stats(self._ix, C.byref(sm), C.byref(om), C.byref(ns), C.byref(nh), C.byref(nr)), "pwa_sa_seed_last_stats")
+        self.seed_stats = self._ctx.seed_stats = dict(search_ms=sm.value, sort_ms=om.value, slots=ns.value, hits=nh.value, ranges=nr.value)
+        cut = anc_off.astype(np.int64).tolist()
+        if as_arrays:
+            return [trip[cut[i]:cut[i + 1]] for i in range(n)]
+        rows = trip.tolist()
+        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(n)]
 
 
 class Batch:

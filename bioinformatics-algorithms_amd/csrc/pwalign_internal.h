@@ -88,7 +88,8 @@ struct Knobs {
     int prof16_int = -1;                        // PWA_PROF16_INT: 0 = never the profile form's integer-coded row, 1 or unset = wherever the
                                                 // scoring admits it (mismatch >= gap and match >= gap)
     uint64_t occ_chunk_hits = 0;                // PWA_OCC_CHUNK_HITS: most raw hits per chunk of pwa_sa_occurrences, most staged hits per slice
-                                                // of tasks of pwa_approx_occurrences (tests: several chunks)
+                                                // of tasks of pwa_approx_occurrences, most worst-case hits per range of reads of pwa_sa_seed
+                                                // (tests: several chunks)
     uint32_t approx_chunk = 4096;               // PWA_APPROX_CHUNK: most text columns one task of pwa_approx_* reports
     int tb_engine = -1;                         // PWA_TB_ENGINE: 0 = stripe engine only, 2 = mini-stripe kernels wherever they exist (also one
                                                 // pair per wave for 257 .. 1024 rows, however few such pairs), unset = by pattern length and count

@@ -1,5 +1,6 @@
-// sufarr_kernels.hip -- the suffix-array entries of include/pwalign.h (pwa_sa_*): device buffers, the prefix-doubling
-// rounds, the radix-sort passes and the chunked occurrence lists.  Kernels: sufarr.hip.h.  DESIGN.md §3.8.
+// sufarr_kernels.hip -- the suffix-array entries of include/pwalign.h (pwa_sa_*, pwa_seed_plan): device buffers, the prefix-doubling
+// rounds, the radix-sort passes, the chunked occurrence lists, and the seeding of read lists against a kept index.  Kernels:
+// sufarr.hip.h, seed.hip.h.  DESIGN.md §3.8, §3.25.
 #include "../../include/pwalign.h"
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "seed.hip.h"
 #include "sufarr.hip.h"
 #include "sufarr_ctx.h"
 
@@ -26,6 +28,11 @@ struct pwa_sa_index {
     Dev d_sa;     // n positions (one where n == 0)
     uint32_t rounds = 0;
     float build_ms = 0.f, search_ms = 0.f;
+    // the last pwa_sa_seed: its anchors (all reads, in the call's order) until the next one, and its stats
+    bool seeded = false;
+    std::vector<uint32_t> anc_t, anc_q;
+    float seed_search_ms = 0.f, seed_sort_ms = 0.f;
+    uint64_t seed_slots = 0, seed_hits = 0, seed_ranges = 0;
 };
 
 constexpr uint64_t kDefaultChunkHits = 1ull << 27;   // 24 B of device buffers per raw hit: 3.2 GB per chunk at most
@@ -125,9 +132,253 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// ---- seeding: validation and the host-only planner, then the stages of one range
+
+constexpr uint32_t kNoRead = 0xFFFFFFFFu;
+
+struct SeedCall {
+    uint64_t n = 0;                  // text bytes
+    const uint64_t* off = nullptr;   // n_reads + 1 byte offsets of the reads
+    uint32_t n_reads = 0, k = 0, step = 0, max_occ = 0;
+
+    uint64_t slots(uint64_t r) const {
+        const uint64_t len = off[r + 1] - off[r];
+        return len < k ? 0 : (len - k) / step + 1;
+    }
+    uint64_t hits_per_slot() const { return n < k ? 0 : std::min<uint64_t>(max_occ, n - k + 1); }
+    uint64_t worst_hits(uint64_t r) const { return slots(r) * hits_per_slot(); }   // both factors below 2^32
+};
+
+// Pointers and parameters, then the reads in order, then the list's slots: the code, the first offending read in `bad`, the slots
+int seed_validate(const SeedCall& c, uint32_t& bad, uint64_t& n_slots, std::string& what) {
+    bad = kNoRead;
+    n_slots = 0;
+    if (c.n_reads && !c.off) {
+        what = "a required pointer is null";
+        return PWA_E_INVALID;
+    }
+    if (!c.k || !c.step || !c.max_occ) {
+        what = "k, step and max_occ are at least 1";
+        return PWA_E_INVALID;
+    }
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < c.n_reads; ++r) {
+        const auto fail = [&](int code, const char* why) {
+            bad = r;
+            what = "read " + std::to_string(r) + ": " + why;
+            return code;
+        };
+        if (c.off[r + 1] < c.off[r]) return fail(PWA_E_INVALID, "read_off decreases");
+        if (c.off[r + 1] - c.off[r] >= (1ull << 31)) return fail(PWA_E_CAPACITY, "2^31 bytes or more");
+        if (c.worst_hits(r) >= (1ull << 32)) return fail(PWA_E_CAPACITY, "its slots times min(max_occ, n - k + 1) reach 2^32");
+        total += c.slots(r);   // below 2^31 each, 2^32 of them at most: no overflow
+    }
+    if (total >= (1ull << 32)) {
+        what = std::to_string(total) + " slots; at most 2^32 - 1";
+        return PWA_E_CAPACITY;
+    }
+    n_slots = total;
+    return PWA_OK;
+}
+
+// Consecutive reads whose worst-case hits fit the budget (or one read that alone exceeds it); a range without a slot is left out.
+// Every range's slots and hits fit uint32: a read's worst case is below 2^32, and so is the budget.
+std::vector<pwa::Run> seed_ranges(const SeedCall& c, uint64_t budget) {
+    budget = std::min<uint64_t>(budget ? budget : kDefaultChunkHits, 0xFFFFFFFFull);
+    std::vector<pwa::Run> out;
+    if (!c.hits_per_slot()) return out;   // n < k: no k-mer of any read occurs
+    for (const pwa::Run& g : pwa::cut_runs(c.n_reads, budget, [&](uint64_t r) { return c.worst_hits(r); }))
+        if (g.weight) out.push_back(g);
+    return out;
+}
+
+// Grow-only: the buffer handed out again (and poisoned again) where it is large enough
+void fit(pwa::Poison* po, Dev& d, size_t bytes) {
+    if (d.p && d.cap >= bytes) UNIT_CHECK(d.again(po));
+    else UNIT_CHECK(d.alloc(po, bytes));
+}
+
+struct SeedBuffers {
+    Dev blob, read_off, slot_off, lo, cnt, slot_part, anc_off;   // by the range's bytes, reads and slots
+    Dev key, val;                                                // by the range's hits, as the scan reports them
+    SortScratch sc;
+    size_t sc_n = 0;
+    std::vector<uint64_t> h_read_off;
+    std::vector<uint32_t> h_slot_off, h_anc_off;
+
+    void fit_sort(pwa::Poison* po, size_t n) {
+        if (n > sc_n) {
+            sc.alloc(po, n);
+            sc_n = n;
+        } else {
+            for (Dev* d : {&sc.hist, &sc.part, &sc.bits}) UNIT_CHECK(d->again(po));
+        }
+    }
+};
+
+// One range: reads g.k0 .. g.k1 searched, their hits sorted and appended to the index's kept anchors, their offsets into anc_off_out
+void seed_range(pwa::SaCtxView& v, pwa_sa_index* ix, const SeedCall& c, const uint8_t* bytes, const pwa::Run& g, SeedBuffers& b, pwa::Events<4>& ev,
+                uint64_t* anc_off_out) {
+    const uint32_t nr = (uint32_t)(g.k1 - g.k0);
+    const uint64_t base = c.off[g.k0], n_bytes = c.off[g.k1] - base;
+    b.h_read_off.resize((size_t)nr + 1);
+    b.h_slot_off.resize((size_t)nr + 1);
+    uint64_t ns64 = 0;
+    for (uint64_t i = 0; i <= nr; ++i) {
+        b.h_read_off[i] = c.off[g.k0 + i] - base;
+        b.h_slot_off[i] = (uint32_t)ns64;
+        if (i < nr) ns64 += c.slots(g.k0 + i);
+    }
+    const uint32_t ns = (uint32_t)ns64;   // <= the range's worst-case hits
+    const size_t blob_bytes = (n_bytes + 7) / 8 * 8 + 16;
+    fit(v.poison, b.blob, blob_bytes);
+    fit(v.poison, b.read_off, ((size_t)nr + 1) * 8);
+    fit(v.poison, b.slot_off, ((size_t)nr + 1) * 4);
+    fit(v.poison, b.anc_off, ((size_t)nr + 1) * 4);
+    fit(v.poison, b.lo, (size_t)ns * 4);
+    fit(v.poison, b.cnt, ((size_t)ns + 1) * 4);
+    fit(v.poison, b.slot_part, pwa::scan_part_words((size_t)ns + 1) * 4);
+    UNIT_CHECK(hipMemcpyAsync(b.blob.p, bytes + base, n_bytes, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemsetAsync(b.blob.as<uint8_t>() + n_bytes, 0, blob_bytes - n_bytes, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(b.read_off.p, b.h_read_off.data(), ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(b.slot_off.p, b.h_slot_off.data(), ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, v.stream));
+    uint32_t* hit_off = b.cnt.as<uint32_t>();   // the counts, then, scanned, where each slot's hits start; the total last
+    UNIT_CHECK(hipMemsetAsync(hit_off + ns, 0, 4, v.stream));
+    UNIT_CHECK(hipEventRecord(ev.e[0], v.stream));
+    seed_search_kernel<<<blocks_for(ns, kThreads), kThreads, 0, v.stream>>>(ix->d_text.as<uint8_t>(), ix->n, ix->d_sa.as<uint32_t>(), b.blob.as<uint8_t>(),
+                                                                            b.read_off.as<uint64_t>(), b.slot_off.as<uint32_t>(), nr, ns, c.k, c.step,
+                                                                            c.max_occ, b.lo.as<uint32_t>(), hit_off);
+    UNIT_CHECK(hipGetLastError());
+    UNIT_CHECK(hipEventRecord(ev.e[1], v.stream));
+    pwa::scan_excl(v.stream, hit_off, (size_t)ns + 1, b.slot_part.as<uint32_t>());
+    seed_read_offsets_kernel<<<blocks_for((size_t)nr + 1, kThreads), kThreads, 0, v.stream>>>(hit_off, b.slot_off.as<uint32_t>(), nr, b.anc_off.as<uint32_t>());
+    UNIT_CHECK(hipGetLastError());
+    b.h_anc_off.resize((size_t)nr + 1);
+    UNIT_CHECK(hipMemcpyAsync(b.h_anc_off.data(), b.anc_off.p, ((size_t)nr + 1) * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    const uint32_t total = b.h_anc_off[nr];
+    const size_t kept = ix->anc_t.size();
+    for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept + b.h_anc_off[i];
+    float ms = 0.f;
+    UNIT_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    ix->seed_search_ms += ms;
+    ix->seed_hits += total;
+    ix->seed_ranges += 1;
+    if (!total) return;
+    fit(v.poison, b.key, (size_t)total * 16);
+    fit(v.poison, b.val, (size_t)total * 8);
+    b.fit_sort(v.poison, total);
+    SortBufs<uint64_t, uint32_t> s{{b.key.as<uint64_t>(), b.key.as<uint64_t>() + total}, {b.val.as<uint32_t>(), b.val.as<uint32_t>() + total}, 0};
+    UNIT_CHECK(hipEventRecord(ev.e[2], v.stream));
+    seed_gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->d_sa.as<uint32_t>(), b.lo.as<uint32_t>(), hit_off, ns, total,
+                                                                               b.slot_off.as<uint32_t>(), nr, c.step, s.k[0], s.v[0]);
+    UNIT_CHECK(hipGetLastError());
+    radix_sort(v.stream, s, total, b.sc);
+    uint32_t* d_t = reinterpret_cast<uint32_t*>(s.k[s.cur ^ 1]);   // the sort's other key buffer is free now
+    seed_split_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], total, d_t);
+    UNIT_CHECK(hipGetLastError());
+    UNIT_CHECK(hipEventRecord(ev.e[3], v.stream));
+    ix->anc_t.resize(kept + total);
+    ix->anc_q.resize(kept + total);
+    UNIT_CHECK(hipMemcpyAsync(ix->anc_t.data() + kept, d_t, (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(ix->anc_q.data() + kept, s.v[s.cur], (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    UNIT_CHECK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+    ix->seed_sort_ms += ms;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pwa_seed_plan(uint64_t text_n, const uint64_t* read_off, uint32_t n_reads, uint32_t k, uint32_t step, uint32_t max_occ, uint64_t budget_hits,
+                  uint32_t* bad_read, uint64_t* n_slots, uint64_t* n_ranges) {
+    const SeedCall c{text_n, read_off, n_reads, k, step, max_occ};
+    uint32_t bad = kNoRead;
+    uint64_t slots = 0, count = 0;
+    std::string what;
+    int rc = PWA_E_NOMEM;
+    try {
+        rc = seed_validate(c, bad, slots, what);
+        if (rc == PWA_OK) count = seed_ranges(c, budget_hits).size();
+    } catch (const std::bad_alloc&) {
+        rc = PWA_E_NOMEM;
+    }
+    if (bad_read) *bad_read = bad;
+    if (n_slots) *n_slots = slots;
+    if (n_ranges) *n_ranges = count;
+    return rc;
+}
+
+int pwa_sa_seed(pwa_sa_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads, uint32_t k, uint32_t step,
+                uint32_t max_occ, uint64_t* anc_off_out) {
+    if (!ix) return PWA_E_INVALID;
+    pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
+    const SeedCall c{ix->n, read_off, n_reads, k, step, max_occ};
+    if (!anc_off_out || (!read_bytes && n_reads && read_off && read_off[n_reads] != read_off[0])) {
+        *v.err = "pwa_sa_seed: a required pointer is null";
+        return PWA_E_INVALID;
+    }
+    uint32_t bad = kNoRead;
+    uint64_t slots = 0;
+    std::string what;
+    if (const int rc = seed_validate(c, bad, slots, what)) {
+        *v.err = "pwa_sa_seed: " + what;
+        return rc;
+    }
+    ix->seeded = false;
+    ix->anc_t.clear();
+    ix->anc_q.clear();
+    ix->seed_search_ms = ix->seed_sort_ms = 0.f;
+    ix->seed_slots = slots;
+    ix->seed_hits = ix->seed_ranges = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = pwa::guarded(v, [&] {
+        std::fill_n(anc_off_out, (size_t)n_reads + 1, 0ull);
+        const std::vector<pwa::Run> ranges = seed_ranges(c, v.occ_chunk_hits);
+        if (ranges.empty()) return;   // no read, no slot, or a text shorter than k: nothing for the device to do
+        UNIT_CHECK(hipSetDevice(v.device));
+        SeedBuffers b;
+        pwa::Events<4> ev;
+        UNIT_CHECK(ev.create());
+        uint64_t done = 0;   // reads whose offsets are written
+        for (const pwa::Run& g : ranges) {
+            for (; done < g.k0; ++done) anc_off_out[done] = ix->anc_t.size();   // the reads of a range without a slot
+            seed_range(v, ix, c, read_bytes, g, b, ev, anc_off_out);
+            done = g.k1;
+        }
+        for (; done <= n_reads; ++done) anc_off_out[done] = ix->anc_t.size();
+        if (v.debug)
+            std::fprintf(stderr, "[pwa] sa seed: %u reads, k=%u step=%u max_occ=%u: %llu slots, %llu hits, %llu ranges, search %.3f ms, sort %.3f ms, call %.3f ms\n",
+                         n_reads, k, step, max_occ, (unsigned long long)ix->seed_slots, (unsigned long long)ix->seed_hits,
+                         (unsigned long long)ix->seed_ranges, ix->seed_search_ms, ix->seed_sort_ms, ms_since(t0));
+    });
+    ix->seeded = rc == PWA_OK;
+    return rc;
+}
+
+int pwa_sa_seed_fetch(const pwa_sa_index* ix, uint32_t* anc_t, uint32_t* anc_q, uint64_t cap) {
+    if (!ix || !ix->seeded) return PWA_E_INVALID;
+    const uint64_t total = ix->anc_t.size();
+    if (cap < total) {
+        *pwa::sa_ctx_view(ix->ctx).err = "pwa_sa_seed_fetch: " + std::to_string(total) + " anchors, capacity " + std::to_string(cap);
+        return PWA_E_CAPACITY;
+    }
+    if (total && (!anc_t || !anc_q)) return PWA_E_INVALID;
+    std::copy(ix->anc_t.begin(), ix->anc_t.end(), anc_t);
+    std::copy(ix->anc_q.begin(), ix->anc_q.end(), anc_q);
+    return PWA_OK;
+}
+
+int pwa_sa_seed_last_stats(const pwa_sa_index* ix, float* search_ms, float* sort_ms, uint64_t* slots, uint64_t* hits, uint64_t* ranges) {
+    if (!ix) return PWA_E_INVALID;
+    if (search_ms) *search_ms = ix->seed_search_ms;
+    if (sort_ms) *sort_ms = ix->seed_sort_ms;
+    if (slots) *slots = ix->seed_slots;
+    if (hits) *hits = ix->seed_hits;
+    if (ranges) *ranges = ix->seed_ranges;
+    return PWA_OK;
+}
 
 int pwa_sa_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, pwa_sa_index** out) {
     if (!ctx || !out || (!text && n)) return PWA_E_INVALID;

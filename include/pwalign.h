@@ -54,6 +54,7 @@
  *                                 pwa_scores_wfa / pwa_align_wfa_batch(_cigar) / pwa_align_wfa_codes_batch(_cigar) and the pwa_*_wfa_sg calls
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
+ *                                 pwa_sa_seed: at most N worst-case hits per range of reads (forces several ranges on a small list);
  *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
  *                                 pwa_approx_starts: at most N hit records on the device per slice
  *   PWA_APPROX_CHUNK=N            pwa_approx_find / pwa_approx_occurrences: a task reports at most N text columns (default 4096)
@@ -762,6 +763,45 @@ int pwa_sa_occurrences(pwa_sa_index *ix, const uint8_t *pat_bytes, const uint64_
                        uint32_t n_ref, const uint32_t *header_rank, uint64_t *occ_off, uint64_t *occ, uint64_t cap, uint64_t *needed);
 int pwa_sa_last_stats(const pwa_sa_index *ix, uint32_t *rounds, float *build_ms, float *search_ms);
 void pwa_sa_destroy(pwa_sa_index *ix);
+
+/* ---- Seeding a list of reads against a kept index: the exact k-mer anchors that pwa_chain_anchors takes
+ *
+ * The index is a pwa_sa_index of the text as given -- no terminator is appended -- created once and used for any number of calls.
+ * Reads.  Read r is read_bytes[read_off[r] .. read_off[r + 1]).  Its slots are q = 0, step, 2 step, ... while q + k <= len: that is
+ * (len - k) / step + 1 slots, or 0 when len < k.
+ * Hits.  A slot's hits are every t with t + k <= n and text[t .. t + k) == read[q .. q + k) as raw bytes; any byte value is legal, NUL
+ * and >= 0x80 included.  The search treats a suffix shorter than k as smaller, so no hit runs past n.  A slot with more than max_occ hits
+ * contributes none.
+ * Anchors.  Read r's anchors are its slots' hits in ascending (t, q).  Every anchor has len = k, so this is the (t + len, q + len)
+ * order of the chaining call.  Read r's anchors are entries anc_off_out[r] .. anc_off_out[r + 1]) of anc_t and anc_q.
+ * On the device: the k-mers are cut out of the read blob by the search kernel, each k-mer is searched once, the hits are gathered and
+ * sorted there; nothing per k-mer is built on the host.
+ * Validation runs before any device work.  First a null required pointer, or k, step or max_occ equal to 0, PWA_E_INVALID; then in
+ * read order, the first offending read decides: read_off decreasing PWA_E_INVALID; a read of 2^31 bytes or more PWA_E_CAPACITY (the
+ * chaining call needs q + k < 2^31); a read whose worst-case hits, slots x min(max_occ, max(n - k + 1, 0)), reach 2^32
+ * PWA_E_CAPACITY; then a total of 2^32 slots or more PWA_E_CAPACITY.  n_reads = 0, n < k and a list without a slot are valid calls:
+ * they do no device work, and anc_off_out is all zeros.
+ * Ranges.  Consecutive reads run together as long as the sum of their worst-case hits stays within PWA_OCC_CHUNK_HITS, else the
+ * library's budget (2^27); one read alone may exceed it.  A range without a slot launches nothing and is not counted.  The device
+ * buffers of a range's hits are sized from the hits it has, not from the worst case.
+ *   pwa_seed_plan           host only, no context, no GPU: the validation code of the same inputs for a text of text_n bytes,
+ *                           *bad_read = the first offending read (0xFFFFFFFF: none, or a pointer, a parameter or the total was at
+ *                           fault), *n_slots = the list's slots, *n_ranges = the ranges the call would run under budget_hits (0: the
+ *                           library's budget); both are 0 with an error.  bad_read, n_slots and n_ranges may be NULL.
+ *   pwa_sa_seed             runs the seeding, writes anc_off_out[n_reads + 1], and keeps the call's anchors with the index until the
+ *                           next pwa_sa_seed on it or pwa_sa_destroy (sizing with cap = 0 and calling again would search twice).
+ *   pwa_sa_seed_fetch       copies the kept anchors out; PWA_E_CAPACITY when cap < anc_off_out[n_reads], PWA_E_INVALID when no
+ *                           seeding has run on the index (or the last one failed on the device).
+ *   pwa_sa_seed_last_stats  of the last pwa_sa_seed on ix: device ms of the search kernel and of gather + sort + split (events,
+ *                           summed over the ranges), the list's slots, the hits kept, the ranges run.  Any pointer may be NULL; a
+ *                           call that fails validation leaves them, and the kept anchors, unchanged. */
+int pwa_seed_plan(uint64_t text_n, const uint64_t *read_off /* n_reads + 1 */, uint32_t n_reads, uint32_t k, uint32_t step,
+                  uint32_t max_occ, uint64_t budget_hits, uint32_t *bad_read /* or NULL */, uint64_t *n_slots /* or NULL */,
+                  uint64_t *n_ranges /* or NULL */);
+int pwa_sa_seed(pwa_sa_index *ix, const uint8_t *read_bytes, const uint64_t *read_off /* n_reads + 1 */, uint32_t n_reads, uint32_t k,
+                uint32_t step, uint32_t max_occ, uint64_t *anc_off_out /* n_reads + 1 */);
+int pwa_sa_seed_fetch(const pwa_sa_index *ix, uint32_t *anc_t, uint32_t *anc_q, uint64_t cap);
+int pwa_sa_seed_last_stats(const pwa_sa_index *ix, float *search_ms, float *sort_ms, uint64_t *slots, uint64_t *hits, uint64_t *ranges);
 
 /* ---- k-edit approximate pattern search (Sellers' DP on bit-parallel columns, Myers 1999)
  *
