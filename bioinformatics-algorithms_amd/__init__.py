@@ -49,12 +49,14 @@ EXPORTS = [
     "pwa_align_wfa_codes_batch_cigar", "pwa_wfa_last_stats",
     "pwa_wfa_sg_plan", "pwa_scores_wfa_sg", "pwa_align_wfa_sg_batch", "pwa_align_wfa_sg_batch_cigar",
     "pwa_chain_plan", "pwa_chain_anchors", "pwa_chain_last_stats",
+    "pwa_chain_top_plan", "pwa_chain_top", "pwa_chain_top_last_stats", "pwa_mapq",
 ]
 
 
 APPROX_NO_START = 0xffffffff   # PWA_APPROX_NO_START
 WFA_NONE = -(1 << 31)          # PWA_WFA_NONE: score_out of a pair the bound leaves out
 CHAIN_NO_READ = 0xffffffff     # last_out of a read without anchors; pwa_chain_plan's bad_read when no read is at fault
+CHAIN_ROOTED = 1               # PWA_CHAIN_ROOTED: pwa_chain_top keeps only walks that end at an anchor without a predecessor
 
 
 class PwaError(RuntimeError):
@@ -144,6 +146,24 @@ def chain_plan(anchors, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38,
     rc = L.pwa_chain_plan(_u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), len(off) - 1, lookback, max_dist, bandwidth,
                           gap_scale, budget, C.byref(bad), C.byref(nr))
     return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, ranges=nr.value)
+
+
+def chain_top_plan(anchors, max_chains=4, min_score=40, min_count=3, rooted=False, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38, budget=0,
+                   flags=None):
+    """pwa_chain_top_plan (host only): chain_plan for Context.chain_top, with that call's parameters and device bytes ->
+    dict(code, bad_read, ranges).  flags, where given, is passed as it is in place of rooted."""
+    L = lib()
+    t, q, ln, off = _anchor_arrays(anchors)
+    bad, nr = C.c_uint32(0), C.c_uint64(0)
+    rc = L.pwa_chain_top_plan(_u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), len(off) - 1, lookback, max_dist, bandwidth,
+                              gap_scale, max_chains, min_score, min_count, (CHAIN_ROOTED if rooted else 0) if flags is None else flags, budget,
+                              C.byref(bad), C.byref(nr))
+    return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, ranges=nr.value)
+
+
+def mapq(s1, s2, c1):
+    """pwa_mapq (host only): the mapping quality 0 .. 60 of a best chain of score s1 and c1 anchors beside a second-best score s2."""
+    return lib().pwa_mapq(s1, s2, c1)
 
 
 def seed_plan(text_len, read_lens, k, step=1, max_occ=64, budget=0):
@@ -404,6 +424,11 @@ def lib():
     L.pwa_chain_plan.argtypes = chain_in + [C.c_uint64, u32p, u64p]
     L.pwa_chain_anchors.argtypes = [vp] + chain_in + [i32p, u32p, u32p, u32p, i32p, i32p, i32p]
     L.pwa_chain_last_stats.argtypes = [vp, C.POINTER(C.c_float), u64p, u64p]
+    top_in = chain_in + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]   # ..., max_chains, min_score, min_count, flags
+    L.pwa_chain_top_plan.argtypes = top_in + [C.c_uint64, u32p, u64p]
+    L.pwa_chain_top.argtypes = [vp] + top_in + [u32p, i32p, u32p, u32p, u32p, i32p, i32p, u32p, i32p, i32p, i32p]
+    L.pwa_chain_top_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p, u64p]
+    L.pwa_mapq.argtypes = [C.c_int32, C.c_int32, C.c_uint32]
     _lib = L
     return L
 
@@ -1396,6 +1421,47 @@ class Context:
             out.append(d)
         return out
 
+    def chain_top(self, anchors, max_chains=4, min_score=40, min_count=3, rooted=False, lookback=64, max_dist=5000, bandwidth=500, gap_scale=38,
+                  want_dp=False, want_ids=False):
+        """pwa_chain_top: up to max_chains chains of every read's anchors, best first, selected on the device by marked back-walks
+        over chain()'s DP (a walk that runs into an anchor of an earlier walk stops there and scores what it adds; with rooted such a
+        walk is not kept), and the read's mapping quality.  anchors as for chain() -> per read dict(chains=[dict(chain()'s keys plus
+        branch: the anchor the walk stopped before, or -1)], mapq), with want_dp the lists f and pred, with want_ids the list chain_id
+        (per anchor its kept chain's index, or -1).  Sets chain_top_stats = dict(chain_ms, top_ms, anchors, rounds, ranges)."""
+        import numpy as np
+        t, q, ln, off = _anchor_arrays(anchors)
+        n, N = len(off) - 1, max(int(max_chains), 1)
+        slots = max(n, 1) * N
+        nch, mq = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        sc, br = np.zeros(slots, dtype=np.int32), np.zeros(slots, dtype=np.int32)
+        cnt, last, span = np.zeros(slots, dtype=np.uint32), np.zeros(slots, dtype=np.uint32), np.zeros(4 * slots, dtype=np.uint32)
+        diag = np.zeros(2 * slots, dtype=np.int32)
+        tot = int(off[n])
+        f = np.zeros(max(tot, 1), dtype=np.int32) if want_dp else None
+        pr = np.zeros(max(tot, 1), dtype=np.int32) if want_dp else None
+        ids = np.zeros(max(tot, 1), dtype=np.int32) if want_ids else None
+        i32 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        rc = self._L.pwa_chain_top(self._h, _u32p(t), _u32p(q), _u32p(ln), off.ctypes.data_as(C.POINTER(C.c_uint64)), n, lookback, max_dist, bandwidth,
+                                   gap_scale, max_chains, min_score, min_count, CHAIN_ROOTED if rooted else 0, _u32p(nch), i32(sc), _u32p(cnt), _u32p(last),
+                                   _u32p(span), i32(diag), i32(br), _u32p(mq), i32(f), i32(pr), i32(ids))
+        self._check(rc, "pwa_chain_top")
+        cm, tm, na, nro, nr = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pwa_chain_top_last_stats(self._h, C.byref(cm), C.byref(tm), C.byref(na), C.byref(nro), C.byref(nr)), "pwa_chain_top_last_stats")
+        self.chain_top_stats = dict(chain_ms=cm.value, top_ms=tm.value, anchors=na.value, rounds=nro.value, ranges=nr.value)
+        nch, mq, sc, br, cnt, last, span, diag, o = (a.tolist() for a in (nch, mq, sc, br, cnt, last, span, diag, off))
+        out = []
+        for r in range(n):
+            d = dict(chains=[dict(score=sc[s], count=cnt[s], last=last[s], q_begin=span[4 * s], q_end=span[4 * s + 1], t_begin=span[4 * s + 2],
+                                  t_end=span[4 * s + 3], diag_lo=diag[2 * s], diag_hi=diag[2 * s + 1], branch=br[s]) for s in range(r * N, r * N + nch[r])],
+                     mapq=mq[r])
+            if want_dp:
+                d["f"] = f[o[r]:o[r + 1]].tolist()
+                d["pred"] = pr[o[r]:o[r + 1]].tolist()
+            if want_ids:
+                d["chain_id"] = ids[o[r]:o[r + 1]].tolist()
+            out.append(d)
+        return out
+
     def index(self, text):
         """A TextIndex of text: its suffix array, built once on the device and kept for any number of seed() / map_reads() calls."""
         return TextIndex(self, text)
@@ -1413,14 +1479,24 @@ class Context:
             return ix.seed(reads, k, step, max_occ, as_arrays)
 
     def map_reads(self, text, reads, k, match, mismatch, gap_open, gap_extend, w=100, step=1, max_occ=64, both_strands=False, lookback=64,
-                  max_dist=5000, bandwidth=500, gap_scale=38):
+                  max_dist=5000, bandwidth=500, gap_scale=38, secondary=0, min_chain_score=40, min_chain_count=3):
         """Seed, chain, align (text: bytes, or a TextIndex kept across calls): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
         chain score is kept, ties go forward), chain() of the anchors, then align_banded_batch_cigar("sg", ...) of the read against
         the text window [max(0, t_begin - q_begin - w), min(len(text), t_end + (n - q_end) + w)) in the band (diag_lo - window start -
         w, diag_hi - window start + w).  -> per read dict(pos, end, score, cigar, mdz, strand, chain_score) in text coordinates
         (strand '+' or '-'; cigar and mdz are of the aligned strand), or None for a read without a chain, or whose band is wider than
-        the banded call's 4096 or fails its semi-global validity rule.  Sets map_stats = dict(seed_s, chain_s, align_s): wall seconds."""
+        the banded call's 4096 or fails its semi-global validity rule.  Sets map_stats = dict(seed_s, chain_s, align_s): wall seconds.
+        With secondary = S in 1 .. 15 the chains come from chain_top(max_chains=S + 1, min_chain_score, min_chain_count, rooted) of
+        every strand's anchors: a read's kept chains of both strands are pooled and ordered by score descending, then forward strand
+        first, then chain index; the first is the primary, the next up to S the secondaries, all aligned in the one banded call.  The
+        primary's dict gains mapq = mapq(its chain score, the second pooled score or 0, its chain count) and secondary: a list of
+        dicts with the keys above (a secondary whose band fails is left out; a primary whose band fails makes the read None)."""
         import time
+        if secondary:
+            if not 1 <= secondary <= 15:
+                raise ValueError("map_reads: secondary is 0 .. 15")
+            return self._map_reads_secondary(text, reads, k, match, mismatch, gap_open, gap_extend, w, step, max_occ, both_strands, lookback, max_dist,
+                                             bandwidth, gap_scale, secondary, min_chain_score, min_chain_count)
         index = text if isinstance(text, TextIndex) else None   # bytes: seed() builds a temporary index, inside seed_s
         text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
@@ -1455,6 +1531,55 @@ class Context:
         out = [None] * nr
         for (i, strand, ws, cs), a in zip(placed, al):
             out[i] = dict(pos=ws + a["start"][1], end=ws + a["end"][1], score=a["score"], cigar=a["cigar"], mdz=a["mdz"], strand=strand, chain_score=cs)
+        return out
+
+    def _map_reads_secondary(self, text, reads, k, match, mismatch, gap_open, gap_extend, w, step, max_occ, both_strands, lookback, max_dist, bandwidth,
+                             gap_scale, secondary, min_chain_score, min_chain_count):
+        """map_reads with secondary >= 1: the top chains of every strand pooled per read, one banded call for all their windows"""
+        import time
+        index = text if isinstance(text, TextIndex) else None
+        text = index.text if index else _b(text)
+        fw = [_b(r) for r in reads]
+        nr = len(fw)
+        strands = [fw, [revcomp(r) for r in fw]] if both_strands else [fw]
+        t0 = time.perf_counter()
+        anchors = self.seed(index or text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+        t1 = time.perf_counter()
+        tops = self.chain_top(anchors, secondary + 1, min_chain_score, min_chain_count, True, lookback, max_dist, bandwidth, gap_scale)
+        t2 = time.perf_counter()
+        pats, wins, bands, placed = [], [], [], []   # placed: (read, rank in its pool, strand, window start, chain)
+        second = [0] * nr
+        for i in range(nr):
+            pool = sorted(((s, ci, c) for s in range(len(strands)) for ci, c in enumerate(tops[s * nr + i]["chains"])),
+                          key=lambda e: (-e[2]["score"], e[0], e[1]))[:secondary + 1]
+            second[i] = pool[1][2]["score"] if len(pool) > 1 else 0
+            n = len(fw[i])
+            for rank, (s, _, c) in enumerate(pool):
+                ws = max(0, c["t_begin"] - c["q_begin"] - w)
+                we = min(len(text), c["t_end"] + (n - c["q_end"]) + w)
+                lo, hi = c["diag_lo"] - ws - w, c["diag_hi"] - ws + w
+                if hi - lo + 1 > 4096 or hi < 0 or n + lo > we - ws:
+                    if rank == 0:
+                        break    # no primary: the read is None
+                    continue
+                pats.append(strands[s][i])
+                wins.append(text[ws:we])
+                bands.append((lo, hi))
+                placed.append((i, rank, "+-"[s], ws, c))
+        np_ = len(pats)
+        al = self.align_banded_batch_cigar("sg", pats + wins, list(range(np_)), list(range(np_, 2 * np_)), match, mismatch, gap_open, gap_extend,
+                                           bands) if np_ else []
+        t3 = time.perf_counter()
+        self.map_stats = dict(seed_s=t1 - t0, chain_s=t2 - t1, align_s=t3 - t2)
+        out = [None] * nr
+        for (i, rank, strand, ws, c), a in zip(placed, al):
+            d = dict(pos=ws + a["start"][1], end=ws + a["end"][1], score=a["score"], cigar=a["cigar"], mdz=a["mdz"], strand=strand, chain_score=c["score"])
+            if rank == 0:
+                d["mapq"] = mapq(c["score"], second[i], c["count"])
+                d["secondary"] = []
+                out[i] = d
+            else:
+                out[i]["secondary"].append(d)
         return out
 
 

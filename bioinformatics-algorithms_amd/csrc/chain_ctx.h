@@ -8,10 +8,17 @@ struct ChainStats {
     float chain_ms = 0.f;
     uint64_t anchors = 0, ranges = 0;
 };
+// the last pwa_chain_top: device ms of its chain kernel and of what follows it (keys, sort, selection), the anchors, the rounds of
+// the selection (walks begun), the ranges
+struct ChainTopStats {
+    float chain_ms = 0.f, top_ms = 0.f;
+    uint64_t anchors = 0, rounds = 0, ranges = 0;
+};
 struct ChainCtxView : UnitCtx {
     uint64_t range_bytes = 0;        // PWA_RANGE_BYTES (0: the library's budget)
     ChainStats* stats = nullptr;
 };
 ChainCtxView chain_ctx_view(pwa_ctx* c);
 const ChainStats& chain_stats_of(const pwa_ctx* c);
+ChainTopStats* chain_top_stats_of(pwa_ctx* c);
 }  // namespace pwa

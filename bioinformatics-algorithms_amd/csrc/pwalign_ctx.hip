@@ -133,6 +133,7 @@ pwa::ChainCtxView pwa::chain_ctx_view(pwa_ctx* c) {
     return v;
 }
 const pwa::ChainStats& pwa::chain_stats_of(const pwa_ctx* c) { return c->chain_stats; }
+pwa::ChainTopStats* pwa::chain_top_stats_of(pwa_ctx* c) { return &c->chain_top_stats; }
 
 hipError_t pwa::recode_bytes(hipStream_t s, uint8_t* p, size_t n16, const uint8_t* table) {
     if (!n16) return hipSuccess;

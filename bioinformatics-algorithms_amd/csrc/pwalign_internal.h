@@ -132,6 +132,7 @@ struct pwa_ctx {
     pwa::ApproxStartsStats approx_starts_stats;   // the last pwa_approx_starts
     pwa::WfaStats wfa_stats;               // the last pwa_scores_wfa / pwa_align_wfa_batch(_cigar)
     pwa::ChainStats chain_stats;           // the last pwa_chain_anchors
+    pwa::ChainTopStats chain_top_stats;    // the last pwa_chain_top
     bool score_band = false;   // pwa_ctx_set_score_band: also materialise the int32 score band in HBM
     // pwa_pair_forms: pair_form_name of every form PairLaunch::build / build_mini resolved on this context (a batch object's launches:
     // on the context that created it), distinct, in first-seen order; only pwa_pair_forms_reset empties it

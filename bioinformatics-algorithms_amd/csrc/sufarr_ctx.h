@@ -1,5 +1,5 @@
-// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign_internal.h, and the
-// scan of that unit that pwalign_align.hip borrows.
+// sufarr_ctx.h -- what the suffix-array unit (sufarr_kernels.hip) needs of a pwa_ctx, whose layout lives in pwalign_internal.h, the
+// scan of that unit that pwalign_align.hip borrows, and its radix sort of (uint64 key, uint32 value) pairs that chain_kernels.hip borrows.
 #pragma once
 #include "side_unit.h"
 
@@ -12,4 +12,13 @@ SaCtxView sa_ctx_view(pwa_ctx* c);
 // sums, in place; part is a device workspace of scan_part_words(len) words.
 void scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part);
 size_t scan_part_words(size_t len);
+// Scratch of the unit's radix sort for up to n elements: the digit-major histogram, the scan's chunk sums, the key-bit partials.
+struct SortScratch {
+    Dev hist, part, bits;
+    void alloc(Poison* po, size_t n);
+};
+// The suffix-array unit's stable LSD radix sort (sufarr_kernels.hip) of n (uint64 key, uint32 value) pairs by key, enqueued on s (it
+// waits once on s for the key bits that decide which 8-bit passes run).  key2 and val2 hold 2 n entries each: the input in the first
+// n, the other n a workspace.  Returns which half (0 or 1) holds the sorted pairs.
+int sort_pairs(hipStream_t s, uint64_t* key2, uint32_t* val2, size_t n, SortScratch& sc);
 }  // namespace pwa

@@ -48,6 +48,13 @@ void pwa::scan_excl(hipStream_t s, uint32_t* x, size_t len, uint32_t* part) {
     scan_apply_kernel<<<nb, kThreads, 0, s>>>(x, len, part);
 }
 
+void pwa::SortScratch::alloc(pwa::Poison* po, size_t n) {
+    const size_t tiles = std::max<size_t>(1, (n + kTile - 1) / kTile);
+    UNIT_CHECK(hist.alloc(po, tiles * kBuckets * 4));
+    UNIT_CHECK(part.alloc(po, ((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
+    UNIT_CHECK(bits.alloc(po, (2 * 1024 + 2) * 8));
+}
+
 namespace {
 
 // Buffers of a stable LSD radix sort of n (key, value) pairs: k[cur] / v[cur] hold the input and, afterwards, the result.
@@ -58,16 +65,8 @@ struct SortBufs {
     int cur = 0;
 };
 
-// Scratch of radix_sort for up to n elements: the digit-major histogram, the scan's chunk sums, the key-bit partials.
-struct SortScratch {
-    Dev hist, part, bits;
-    void alloc(pwa::Poison* po, size_t n) {
-        const size_t tiles = std::max<size_t>(1, (n + kTile - 1) / kTile);
-        UNIT_CHECK(hist.alloc(po, tiles * kBuckets * 4));
-        UNIT_CHECK(part.alloc(po, ((std::max(tiles * kBuckets, n + 1) + kTile - 1) / kTile + 1) * 4));
-        UNIT_CHECK(bits.alloc(po, (2 * 1024 + 2) * 8));
-    }
-};
+// Scratch of radix_sort for up to n elements (sufarr_ctx.h)
+using pwa::SortScratch;
 
 // Stable sort by key.  Digits (8 bits) that are the same in every key are skipped: one OR / AND reduction and a 16-byte
 // read-back decide which passes run.  Returns the number of passes.
@@ -288,6 +287,13 @@ void seed_range(pwa::SaCtxView& v, pwa_sa_index* ix, const SeedCall& c, const ui
 }
 
 }  // namespace
+
+// The sort above for another unit (sufarr_ctx.h): the chaining unit's candidate order
+int pwa::sort_pairs(hipStream_t s, uint64_t* key2, uint32_t* val2, size_t n, SortScratch& sc) {
+    SortBufs<uint64_t, uint32_t> b{{key2, key2 + n}, {val2, val2 + n}, 0};
+    radix_sort(s, b, n, sc);
+    return b.cur;
+}
 
 extern "C" {
 

@@ -1079,6 +1079,55 @@ int pwa_chain_anchors(pwa_ctx *ctx, const uint32_t *anc_t, const uint32_t *anc_q
                       int32_t *pred_out /* or NULL */);
 int pwa_chain_last_stats(const pwa_ctx *ctx, float *chain_ms, uint64_t *anchors, uint64_t *ranges);
 
+/* ---- Top-N chains of a read, mapping quality: the alternative placements behind the best chain
+ *
+ * Anchors, their order, lookback / max_dist / bandwidth / gap_scale, f and pred are those of pwa_chain_anchors above, unchanged.
+ * New parameters: max_chains N 1 .. 16, min_score 1 .. 2^30, min_count 1 .. 2^24, flags 0 or PWA_CHAIN_ROOTED.
+ * Selection.  Per read, every anchor carries a mark, initially "free".  Candidates are the anchors in order of descending f, the
+ * smaller index first among equal f.  For each candidate e, in that order:
+ *   1. stop the read when N chains are kept, or when f(e) < min_score (no later walk can score min_score);
+ *   2. skip e if it is marked;
+ *   3. otherwise this is a round: walk cur = e, pred(cur), ...; every anchor visited is part of the walk.  The walk ends at the
+ *      anchor b whose pred is -1 (base = 0, branch = -1), or at the anchor b whose pred p is already marked (base = f(p), branch = p);
+ *   4. score = f(e) - base, count = the number of anchors of the walk;
+ *   5. the walk is kept iff score >= min_score and count >= min_count and (PWA_CHAIN_ROOTED is not set or branch = -1);
+ *   6. its anchors are marked in either case: with the kept chain's index c = 0, 1, ... when kept, with "dropped" otherwise.
+ *      A dropped walk still claims its anchors: a later walk that runs into one of them stops there.
+ * A kept chain's record: score, count, last = e, (q_b, y_e, t_b, x_e), (min, max) of t - q over the walk's anchors, branch.  With
+ * min_score = 1 and min_count = 1, chain 0 is pwa_chain_anchors' result field by field, with branch = -1.
+ * Outputs.  n_chains_out[r] = the chains kept for read r; read r's chain c is slot r * max_chains + c of score_out, count_out,
+ * last_out, branch_out, and, laid out as in pwa_chain_anchors by slot, of span_out (4 per slot) and diag_out (2 per slot).  Unused
+ * slots hold score 0, count 0, last 0xFFFFFFFF, branch -1 and zeros elsewhere.  mapq_out (one per read), f_out, pred_out and
+ * chain_id_out (one per anchor: c for an anchor of kept chain c, else -1) may each be NULL.  A read without anchors is answered on
+ * the host; n_reads = 0 is PWA_OK.
+ * Mapping quality, integers only: pwa_mapq(s1, s2, c1) = min(60, (60 * (s1 - s2) * min(c1, 10)) div (10 * s1)) in 64-bit arithmetic,
+ * 0 when s1 <= 0, s2 clamped to [0, s1].  mapq_out[r] = pwa_mapq(score of chain 0, the best score among the chains 1 .. with
+ * branch = -1 or 0 if there is none, count of chain 0), and 0 for a read without a kept chain.
+ * Validation is pwa_chain_plan's, in its order; the four new parameters are checked in its "parameter outside its range" step.
+ * Ranges.  As above, with this call's device bytes: 48 per anchor (t, q, len, f, pred, the mark, two sort keys of 8 and two sort
+ * values of 4) plus 40 * max_chains + 16 per read (its chain slots and a head of 4 words).
+ * The DP runs on the device with pwa_chain_anchors' kernel and stays there; the candidates are ordered by one stable radix sort per
+ * range and selected by one wave per read; nothing per anchor is copied back unless f_out, pred_out or chain_id_out asks for it.
+ *   pwa_chain_top_plan        host only: the validation code, *bad_read and *n_ranges as pwa_chain_plan gives them.
+ *   pwa_chain_top_last_stats  of the last pwa_chain_top on ctx: device ms of the chain kernel and of the selection (keys, sort and
+ *                             walks), the anchors, the rounds (step 3) summed over the reads, the ranges.  Any pointer may be NULL.
+ *                             pwa_chain_last_stats keeps reporting pwa_chain_anchors only.
+ *   pwa_mapq                  host only; returns the value. */
+#define PWA_CHAIN_ROOTED 1u /* flags: keep only walks that end at an anchor without a predecessor */
+int pwa_chain_top_plan(const uint32_t *anc_t, const uint32_t *anc_q, const uint32_t *anc_len, const uint64_t *anc_off /* n_reads + 1 */,
+                       uint32_t n_reads, uint32_t lookback, uint32_t max_dist, uint32_t bandwidth, uint32_t gap_scale,
+                       uint32_t max_chains, uint32_t min_score, uint32_t min_count, uint32_t flags, uint64_t budget_bytes,
+                       uint32_t *bad_read /* or NULL */, uint64_t *n_ranges /* or NULL */);
+int pwa_chain_top(pwa_ctx *ctx, const uint32_t *anc_t, const uint32_t *anc_q, const uint32_t *anc_len,
+                  const uint64_t *anc_off /* n_reads + 1 */, uint32_t n_reads, uint32_t lookback, uint32_t max_dist, uint32_t bandwidth,
+                  uint32_t gap_scale, uint32_t max_chains, uint32_t min_score, uint32_t min_count, uint32_t flags,
+                  uint32_t *n_chains_out /* n_reads */, int32_t *score_out /* n_reads * max_chains, as count, last, branch */,
+                  uint32_t *count_out, uint32_t *last_out, uint32_t *span_out /* 4 * n_reads * max_chains */,
+                  int32_t *diag_out /* 2 * n_reads * max_chains */, int32_t *branch_out, uint32_t *mapq_out /* n_reads or NULL */,
+                  int32_t *f_out /* or NULL */, int32_t *pred_out /* or NULL */, int32_t *chain_id_out /* or NULL */);
+int pwa_chain_top_last_stats(const pwa_ctx *ctx, float *chain_ms, float *top_ms, uint64_t *anchors, uint64_t *rounds, uint64_t *ranges);
+int pwa_mapq(int32_t s1, int32_t s2, uint32_t c1);
+
 /*
  * Host-side post-processing of one alignment (no GPU work): everything hw2.cpp derives from
  * the walk -- the gapped strings (hw2.cpp:164-184 / 240-259), prepareCigarString (59-78),
