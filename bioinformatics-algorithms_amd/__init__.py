@@ -43,6 +43,8 @@ EXPORTS = [
     "pwa_fasta_read", "pwa_fasta_n_seq", "pwa_fasta_bytes", "pwa_fasta_offsets", "pwa_fasta_first_seq", "pwa_fasta_free",
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
     "pwa_seed_plan", "pwa_sa_seed", "pwa_sa_seed_fetch", "pwa_sa_seed_last_stats",
+    "pwa_mm_create", "pwa_mm_destroy", "pwa_mm_fetch", "pwa_mm_last_stats", "pwa_mm_sketch", "pwa_mm_plan", "pwa_mm_seed", "pwa_mm_seed_fetch",
+    "pwa_mm_seed_last_stats",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
     "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
@@ -179,6 +181,19 @@ def seed_plan(text_len, read_lens, k, step=1, max_occ=64, budget=0):
     bad, ns, nr = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
     rc = L.pwa_seed_plan(text_len, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(read_lens), k, step, max_occ, budget, C.byref(bad), C.byref(ns),
                          C.byref(nr))
+    return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, slots=ns.value, ranges=nr.value)
+
+
+def minimizer_plan(n_min, read_lens, k, max_occ=64, budget=0):
+    """pwa_mm_plan (host only): seed_plan for a MinimizerIndex of n_min entries -- what MinimizerIndex.seed would answer to reads of
+    these lengths before any device work -> dict(code, bad_read, slots, ranges), slots being the list's k-mers."""
+    import numpy as np
+    L = lib()
+    off = np.zeros(len(read_lens) + 1, dtype=np.uint64)
+    if len(read_lens):
+        off[1:] = np.cumsum(np.asarray(read_lens, dtype=np.uint64), dtype=np.uint64)
+    bad, ns, nr = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.pwa_mm_plan(n_min, off.ctypes.data_as(C.POINTER(C.c_uint64)), len(read_lens), k, max_occ, budget, C.byref(bad), C.byref(ns), C.byref(nr))
     return dict(code=rc, bad_read=None if bad.value == CHAIN_NO_READ else bad.value, slots=ns.value, ranges=nr.value)
 
 
@@ -401,6 +416,17 @@ def lib():
     L.pwa_sa_seed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p]
     L.pwa_sa_seed_fetch.argtypes = [vp, u32p, u32p, C.c_uint64]
     L.pwa_sa_seed_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p, u64p]
+    f32p = C.POINTER(C.c_float)
+    L.pwa_mm_create.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.pwa_mm_destroy.argtypes = [vp]
+    L.pwa_mm_destroy.restype = None
+    L.pwa_mm_fetch.argtypes = [vp, u64p, u32p, C.c_uint64]
+    L.pwa_mm_last_stats.argtypes = [vp, u64p, f32p]
+    L.pwa_mm_sketch.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, u64p, C.c_uint64, u64p]
+    L.pwa_mm_plan.argtypes = [C.c_uint64, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u64p, u64p]
+    L.pwa_mm_seed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, u64p]
+    L.pwa_mm_seed_fetch.argtypes = [vp, u32p, u32p, C.c_uint64]
+    L.pwa_mm_seed_last_stats.argtypes = [vp, f32p, f32p, f32p, u64p, u64p, u64p, u64p]
     L.pwa_approx_find.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u32p, i32p, u32p]
     L.pwa_approx_occurrences.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
     L.pwa_approx_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
@@ -1462,15 +1488,52 @@ class Context:
             out.append(d)
         return out
 
-    def index(self, text):
-        """A TextIndex of text: its suffix array, built once on the device and kept for any number of seed() / map_reads() calls."""
+    def index(self, text, minimizers=None):
+        """A TextIndex of text: its suffix array, built once on the device and kept for any number of seed() / map_reads() calls.
+        With minimizers=(k, w) a MinimizerIndex instead: the text's (w, k)-minimizer sketch sorted by hash, for the same calls."""
+        if minimizers is not None:
+            k, w = minimizers
+            return MinimizerIndex(self, text, k, w)
         return TextIndex(self, text)
+
+    def sketch(self, seqs, k, w, as_arrays=False):
+        """pwa_mm_sketch: the (w, k)-minimizer sketch of every sequence -> per sequence a list of (pos, hash) in ascending pos, or
+        with as_arrays a pair of arrays (pos uint32, hash uint64)."""
+        import numpy as np
+        if not (1 <= k <= 31 and 1 <= w <= 128):
+            raise ValueError("sketch: k is 1 .. 31 and w is 1 .. 128")
+        seqs = [_b(s) for s in seqs]
+        n = len(seqs)
+        u64p = C.POINTER(C.c_uint64)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in seqs])
+        cap = sum(max(len(s) - k + 1, 0) for s in seqs)
+        min_off = np.zeros(n + 1, dtype=np.uint64)
+        pos, hsh = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64)
+        need = C.c_uint64(0)
+        self._check(self._L.pwa_mm_sketch(self._h, b"".join(seqs), off.ctypes.data_as(u64p), n, k, w, min_off.ctypes.data_as(u64p), _u32p(pos),
+                                          hsh.ctypes.data_as(u64p), cap, C.byref(need)), "pwa_mm_sketch")
+        cut = min_off.astype(np.int64).tolist()
+        if as_arrays:
+            return [(pos[cut[i]:cut[i + 1]], hsh[cut[i]:cut[i + 1]]) for i in range(n)]
+        pairs = list(zip(pos[:cut[n]].tolist(), hsh[:cut[n]].tolist()))
+        return [pairs[cut[i]:cut[i + 1]] for i in range(n)]
+
+    @staticmethod
+    def _on_minimizers(index, k, step):
+        if k != index.k or step != 1:
+            raise ValueError("a MinimizerIndex seeds with its own k (%d) and step 1" % index.k)
 
     def seed(self, text, reads, k, step=1, max_occ=64, as_arrays=False):
         """Exact k-mer anchors of every read in the text (bytes: a temporary index of it is built; or a TextIndex), pwa_sa_seed: the
         k-mers read[q:q + k] at q = 0, step, 2 step, ... are cut, searched, gathered and sorted on the device; a k-mer with more than
         max_occ occurrences is dropped.  -> per read its anchors (t, q, k) in the order chain() requires (by t, then q), as a list of
-        tuples, or with as_arrays as a uint32 array of shape (n, 3).  Sets seed_stats = dict(search_ms, sort_ms, slots, hits, ranges)."""
+        tuples, or with as_arrays as a uint32 array of shape (n, 3).  Sets seed_stats = dict(search_ms, sort_ms, slots, hits, ranges).
+        On a MinimizerIndex (k its own, step 1, else ValueError) the anchors are those of MinimizerIndex.seed."""
+        if isinstance(text, MinimizerIndex):
+            self._on_minimizers(text, k, step)
+            return text.seed(reads, max_occ, as_arrays)
         if isinstance(text, TextIndex):
             return text.seed(reads, k, step, max_occ, as_arrays)
         if k < 1 or step < 1 or max_occ < 1:
@@ -1480,7 +1543,7 @@ class Context:
 
     def map_reads(self, text, reads, k, match, mismatch, gap_open, gap_extend, w=100, step=1, max_occ=64, both_strands=False, lookback=64,
                   max_dist=5000, bandwidth=500, gap_scale=38, secondary=0, min_chain_score=40, min_chain_count=3):
-        """Seed, chain, align (text: bytes, or a TextIndex kept across calls): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
+        """Seed, chain, align (text: bytes, or a TextIndex or MinimizerIndex kept across calls; the latter with its own k and step 1): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
         chain score is kept, ties go forward), chain() of the anchors, then align_banded_batch_cigar("sg", ...) of the read against
         the text window [max(0, t_begin - q_begin - w), min(len(text), t_end + (n - q_end) + w)) in the band (diag_lo - window start -
         w, diag_hi - window start + w).  -> per read dict(pos, end, score, cigar, mdz, strand, chain_score) in text coordinates
@@ -1497,7 +1560,7 @@ class Context:
                 raise ValueError("map_reads: secondary is 0 .. 15")
             return self._map_reads_secondary(text, reads, k, match, mismatch, gap_open, gap_extend, w, step, max_occ, both_strands, lookback, max_dist,
                                              bandwidth, gap_scale, secondary, min_chain_score, min_chain_count)
-        index = text if isinstance(text, TextIndex) else None   # bytes: seed() builds a temporary index, inside seed_s
+        index = text if isinstance(text, (TextIndex, MinimizerIndex)) else None   # bytes: seed() builds a temporary index, inside seed_s
         text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
         nr = len(fw)
@@ -1537,7 +1600,7 @@ class Context:
                              gap_scale, secondary, min_chain_score, min_chain_count):
         """map_reads with secondary >= 1: the top chains of every strand pooled per read, one banded call for all their windows"""
         import time
-        index = text if isinstance(text, TextIndex) else None
+        index = text if isinstance(text, (TextIndex, MinimizerIndex)) else None
         text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
         nr = len(fw)
@@ -1634,6 +1697,84 @@ class TextIndex:
         sm, om, ns, nh, nr = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         ck(self._L.pwa_sa_seed_last_stats(self._ix, C.byref(sm), C.byref(om), C.byref(ns), C.byref(nh), C.byref(nr)), "pwa_sa_seed_last_stats")
         self.seed_stats = self._ctx.seed_stats = dict(search_ms=sm.value, sort_ms=om.value, slots=ns.value, hits=nh.value, ranges=nr.value)
+        cut = anc_off.astype(np.int64).tolist()
+        if as_arrays:
+            return [trip[cut[i]:cut[i + 1]] for i in range(n)]
+        rows = trip.tolist()
+        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(n)]
+
+
+class MinimizerIndex:
+    """The (w, k)-minimizer index of one text, resident on the context's GPU (pwa_mm_create): the text's sketch as (hash, pos) pairs in
+    that order, built once, then seeded against by any number of read lists (pwa_mm_seed).  Keeps the text bytes (map_reads cuts its
+    windows from them).  k, w; stats = dict(minimizers, build_ms) of the build; close() frees it, and it works as a context manager.
+    Close it before its context."""
+
+    def __init__(self, ctx, text, k, w):
+        if not (1 <= k <= 31 and 1 <= w <= 128):
+            raise ValueError("MinimizerIndex: k is 1 .. 31 and w is 1 .. 128")
+        self._ctx, self._L = ctx, ctx._L
+        self.text = _b(text)
+        self.k, self.w = k, w
+        ix = C.c_void_p()
+        ctx._check(self._L.pwa_mm_create(ctx._h, self.text, len(self.text), k, w, C.byref(ix)), "pwa_mm_create")
+        self._ix = ix
+        n, ms = C.c_uint64(0), C.c_float(0)
+        ctx._check(self._L.pwa_mm_last_stats(ix, C.byref(n), C.byref(ms)), "pwa_mm_last_stats")
+        self.stats = dict(minimizers=n.value, build_ms=ms.value)
+        self.seed_stats = None
+
+    def close(self):
+        if getattr(self, "_ix", None):
+            self._L.pwa_mm_destroy(self._ix)
+            self._ix = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def entries(self):
+        """pwa_mm_fetch -> (hash uint64 array, pos uint32 array), in ascending (hash, pos)"""
+        import numpy as np
+        if not self._ix:
+            raise PwaError("MinimizerIndex.entries: the index is closed")
+        n = self.stats["minimizers"]
+        h, p = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+        self._ctx._check(self._L.pwa_mm_fetch(self._ix, h.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(p), n), "pwa_mm_fetch")
+        return h[:n], p[:n]
+
+    def seed(self, reads, max_occ=64, as_arrays=False):
+        """pwa_mm_seed + pwa_mm_seed_fetch: every read's minimizers looked up among the text's -> what TextIndex.seed returns, per read
+        its anchors (t, q, k) by t, then q.  Sets seed_stats = dict(sketch_ms, search_ms, sort_ms, slots, minimizers, hits, ranges)
+        here and on the context: device ms of the sketch passes, the lookup kernel and gather + sort + split, the list's k-mers, the
+        read minimizers looked up, the hits kept, the ranges of reads the call ran."""
+        import numpy as np
+        if max_occ < 1:
+            raise ValueError("seed: max_occ is at least 1")
+        if not self._ix:
+            raise PwaError("MinimizerIndex.seed: the index is closed")
+        reads = [_b(r) for r in reads]
+        n = len(reads)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(r) for r in reads])
+        u64p = C.POINTER(C.c_uint64)
+        anc_off = np.zeros(n + 1, dtype=np.uint64)
+        ck = self._ctx._check
+        ck(self._L.pwa_mm_seed(self._ix, b"".join(reads), off.ctypes.data_as(u64p), n, max_occ, anc_off.ctypes.data_as(u64p)), "pwa_mm_seed")
+        total = int(anc_off[n])
+        trip = np.empty((total, 3), dtype=np.uint32)
+        t, q = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.uint32)
+        ck(self._L.pwa_mm_seed_fetch(self._ix, _u32p(t), _u32p(q), total), "pwa_mm_seed_fetch")
+        trip[:, 0], trip[:, 1], trip[:, 2] = t[:total], q[:total], self.k
+        km, sm, om = C.c_float(0), C.c_float(0), C.c_float(0)
+        ns, nm, nh, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ck(self._L.pwa_mm_seed_last_stats(self._ix, C.byref(km), C.byref(sm), C.byref(om), C.byref(ns), C.byref(nm), C.byref(nh), C.byref(nr)),
+           "pwa_mm_seed_last_stats")
+        self.seed_stats = self._ctx.seed_stats = dict(sketch_ms=km.value, search_ms=sm.value, sort_ms=om.value, slots=ns.value, minimizers=nm.value,
+                                                      hits=nh.value, ranges=nr.value)
         cut = anc_off.astype(np.int64).tolist()
         if as_arrays:
             return [trip[cut[i]:cut[i + 1]] for i in range(n)]

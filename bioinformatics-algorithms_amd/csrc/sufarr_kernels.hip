@@ -1,6 +1,7 @@
 // sufarr_kernels.hip -- the suffix-array entries of include/pwalign.h (pwa_sa_*, pwa_seed_plan): device buffers, the prefix-doubling
-// rounds, the radix-sort passes, the chunked occurrence lists, and the seeding of read lists against a kept index.  Kernels:
-// sufarr.hip.h, seed.hip.h.  DESIGN.md §3.8, §3.25.
+// rounds, the radix-sort passes, the chunked occurrence lists, and the seeding of read lists against a kept index; and the minimizer
+// entries (pwa_mm_*), which share the seeding's planner, scan, sort and split.  Kernels: sufarr.hip.h, seed.hip.h, minim.hip.h.
+// DESIGN.md §3.8, §3.25, §3.27.
 #include "../../include/pwalign.h"
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "minim.hip.h"
 #include "seed.hip.h"
 #include "sufarr.hip.h"
 #include "sufarr_ctx.h"
@@ -33,6 +35,22 @@ struct pwa_sa_index {
     std::vector<uint32_t> anc_t, anc_q;
     float seed_search_ms = 0.f, seed_sort_ms = 0.f;
     uint64_t seed_slots = 0, seed_hits = 0, seed_ranges = 0;
+};
+
+struct pwa_mm_index {
+    pwa_ctx* ctx = nullptr;
+    uint32_t k = 0, w = 0, n_min = 0;
+    Dev d_hash, d_pos;   // 2 n_min entries each, as sort_pairs takes them; half `half` holds the pairs in (hash, t) order
+    int half = 0;
+    float build_ms = 0.f;
+    // the last pwa_mm_seed: its anchors (all reads, in the call's order) until the next one, and its stats
+    bool seeded = false;
+    std::vector<uint32_t> anc_t, anc_q;
+    float sketch_ms = 0.f, search_ms = 0.f, sort_ms = 0.f;
+    uint64_t slots = 0, minimizers = 0, hits = 0, ranges = 0;
+
+    const uint64_t* hashes() const { return d_hash.as<uint64_t>() + (size_t)half * n_min; }
+    const uint32_t* positions() const { return d_pos.as<uint32_t>() + (size_t)half * n_min; }
 };
 
 constexpr uint64_t kDefaultChunkHits = 1ull << 27;   // 24 B of device buffers per raw hit: 3.2 GB per chunk at most
@@ -284,6 +302,186 @@ void seed_range(pwa::SaCtxView& v, pwa_sa_index* ix, const SeedCall& c, const ui
     UNIT_CHECK(hipStreamSynchronize(v.stream));
     UNIT_CHECK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
     ix->seed_sort_ms += ms;
+}
+
+// ---- minimizers: the sketch of a range of sequences in two passes, then the index build and the stages of one seeded range
+
+namespace mm = pwa::minim;
+
+bool mm_params_ok(uint32_t k, uint32_t w) { return k >= 1 && k <= mm::kMaxK && w >= 1 && w <= mm::kMaxW; }
+
+uint64_t kmers_of(uint64_t len, uint32_t k) { return len < k ? 0 : len - k + 1; }
+
+// The reads of a minimizer seeding as a SeedCall: step 1, and a text that has n_min k-mers (only min(max_occ, that) enters the plan)
+SeedCall mm_call(uint64_t n_min, const uint64_t* off, uint32_t n_reads, uint32_t k, uint32_t max_occ) {
+    return SeedCall{std::min<uint64_t>(n_min, 1ull << 32) + k - 1, off, n_reads, k, 1, max_occ};
+}
+
+// Pointers aside: k and w, then the sequences in order -- offsets decreasing, 2^31 bytes or more
+int sketch_validate(const uint64_t* off, uint32_t n_seqs, uint32_t k, uint32_t w, std::string& what) {
+    if (!mm_params_ok(k, w)) {
+        what = "k is 1 .. 31 and w is 1 .. 128";
+        return PWA_E_INVALID;
+    }
+    for (uint32_t r = 0; r < n_seqs; ++r) {
+        if (off[r + 1] < off[r]) {
+            what = "sequence " + std::to_string(r) + ": seq_off decreases";
+            return PWA_E_INVALID;
+        }
+        if (off[r + 1] - off[r] >= (1ull << 31)) {
+            what = "sequence " + std::to_string(r) + ": 2^31 bytes or more";
+            return PWA_E_CAPACITY;
+        }
+    }
+    return PWA_OK;
+}
+
+// A range of sequences on the device and its sketch: the per-tile counts (scanned in place, the total last), then the sketch itself
+// in slot order -- hash, position in the sequence, flattened slot -- and where each sequence's minimizers start among them
+struct SketchBuffers {
+    Dev blob, seq_off, slot_off, tile, part, hash, pos, flat, min_off, fault;
+    std::vector<uint64_t> h_seq_off;
+    std::vector<uint32_t> h_slot_off, h_min_off;
+    mm::SketchArgs args{};
+    uint32_t n_tiles = 0, total = 0;
+
+    void start(pwa::SaCtxView& v) {   // once per call: the fault word of all its launches
+        UNIT_CHECK(fault.alloc(v.poison, 4));
+        UNIT_CHECK(hipMemsetAsync(fault.p, 0, 4, v.stream));
+    }
+    void check_fault(const char* who) {   // after a wait on the stream
+        uint32_t f = 0;
+        UNIT_CHECK(hipMemcpy(&f, fault.p, 4, hipMemcpyDeviceToHost));
+        if (f) throw Fail{PWA_E_HIP, std::string(who) + ": a kernel left its bounds (internal error)"};
+    }
+};
+
+// Sequences k0 .. k1 of the list uploaded, their slots laid out, and the count pass: b.total minimizers (waits for it).
+// ev: two events around the device work, or null.
+void sketch_count(pwa::SaCtxView& v, const uint8_t* bytes, const uint64_t* off, uint64_t k0, uint64_t k1, uint32_t k, uint32_t w, SketchBuffers& b,
+                  hipEvent_t* ev) {
+    const uint32_t nr = (uint32_t)(k1 - k0);
+    const uint64_t base = off[k0], n_bytes = off[k1] - base;
+    b.h_seq_off.resize((size_t)nr + 1);
+    b.h_slot_off.resize((size_t)nr + 1);
+    uint64_t ns64 = 0;
+    for (uint64_t i = 0; i <= nr; ++i) {
+        b.h_seq_off[i] = off[k0 + i] - base;
+        b.h_slot_off[i] = (uint32_t)ns64;
+        if (i < nr) ns64 += kmers_of(off[k0 + i + 1] - off[k0 + i], k);
+    }
+    const uint32_t ns = (uint32_t)ns64;   // the caller's ranges hold fewer than 2^32 slots
+    b.n_tiles = blocks_for(ns, kThreads);
+    const size_t blob_bytes = (n_bytes + 7) / 8 * 8 + 16;
+    fit(v.poison, b.blob, blob_bytes);
+    fit(v.poison, b.seq_off, ((size_t)nr + 1) * 8);
+    fit(v.poison, b.slot_off, ((size_t)nr + 1) * 4);
+    fit(v.poison, b.tile, ((size_t)b.n_tiles + 1) * 4);
+    fit(v.poison, b.part, pwa::scan_part_words((size_t)b.n_tiles + 1) * 4);
+    if (n_bytes) UNIT_CHECK(hipMemcpyAsync(b.blob.p, bytes + base, n_bytes, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemsetAsync(b.blob.as<uint8_t>() + n_bytes, 0, blob_bytes - n_bytes, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(b.seq_off.p, b.h_seq_off.data(), ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(b.slot_off.p, b.h_slot_off.data(), ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, v.stream));
+    UNIT_CHECK(hipMemsetAsync(b.tile.as<uint32_t>() + b.n_tiles, 0, 4, v.stream));
+    b.args = mm::SketchArgs{b.blob.as<uint8_t>(), b.seq_off.as<uint64_t>(), b.slot_off.as<uint32_t>(), nr, ns, k, w};
+    b.total = 0;
+    if (ev) UNIT_CHECK(hipEventRecord(ev[0], v.stream));
+    if (ns) {
+        mm::sketch_kernel<false><<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), nullptr, nullptr, nullptr, 0, b.fault.as<uint32_t>());
+        UNIT_CHECK(hipGetLastError());
+        pwa::scan_excl(v.stream, b.tile.as<uint32_t>(), (size_t)b.n_tiles + 1, b.part.as<uint32_t>());
+    }
+    if (ev) UNIT_CHECK(hipEventRecord(ev[1], v.stream));
+    UNIT_CHECK(hipMemcpyAsync(&b.total, b.tile.as<uint32_t>() + b.n_tiles, 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+}
+
+// The write pass of the range counted last, into hash_out / pos_out (b.total entries each); with offsets also b.flat and b.min_off.
+// Enqueued only.
+void sketch_write(pwa::SaCtxView& v, SketchBuffers& b, uint64_t* hash_out, uint32_t* pos_out, bool offsets) {
+    if (offsets) {
+        fit(v.poison, b.flat, (size_t)b.total * 4);
+        fit(v.poison, b.min_off, ((size_t)b.args.n_seqs + 1) * 4);
+    }
+    if (b.total) {
+        mm::sketch_kernel<true><<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), hash_out, pos_out,
+                                                                      offsets ? b.flat.as<uint32_t>() : nullptr, b.total, b.fault.as<uint32_t>());
+        UNIT_CHECK(hipGetLastError());
+    }
+    if (offsets) {
+        mm::sketch_offsets_kernel<<<blocks_for((size_t)b.args.n_seqs + 1, kThreads), kThreads, 0, v.stream>>>(b.flat.as<uint32_t>(), b.total, b.slot_off.as<uint32_t>(),
+                                                                                                              b.args.n_seqs, b.min_off.as<uint32_t>());
+        UNIT_CHECK(hipGetLastError());
+    }
+}
+
+float span_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    UNIT_CHECK(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+
+// One range: reads g.k0 .. g.k1 sketched, their minimizers looked up, the hits sorted and appended to the index's kept anchors
+void mm_seed_range(pwa::SaCtxView& v, pwa_mm_index* ix, const SeedCall& c, const uint8_t* bytes, const pwa::Run& g, SketchBuffers& sb, SeedBuffers& b,
+                   pwa::Events<8>& ev, uint64_t* anc_off_out) {
+    const uint32_t nr = (uint32_t)(g.k1 - g.k0);
+    const size_t kept = ix->anc_t.size();
+    sketch_count(v, bytes, c.off, g.k0, g.k1, ix->k, ix->w, sb, &ev.e[0]);
+    ix->sketch_ms += span_ms(ev.e[0], ev.e[1]);
+    ix->ranges += 1;
+    const uint32_t nm = sb.total;
+    ix->minimizers += nm;
+    for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept;
+    if (!nm) return;   // (every k-mer of the range holds a byte that is not ACGT)
+    fit(v.poison, sb.hash, (size_t)nm * 8);
+    fit(v.poison, sb.pos, (size_t)nm * 4);
+    fit(v.poison, b.lo, (size_t)nm * 4);
+    fit(v.poison, b.cnt, ((size_t)nm + 1) * 4);
+    fit(v.poison, b.slot_part, pwa::scan_part_words((size_t)nm + 1) * 4);
+    fit(v.poison, b.anc_off, ((size_t)nr + 1) * 4);
+    uint32_t* hit_off = b.cnt.as<uint32_t>();   // the counts, then, scanned, where each minimizer's hits start; the total last
+    UNIT_CHECK(hipMemsetAsync(hit_off + nm, 0, 4, v.stream));
+    UNIT_CHECK(hipEventRecord(ev.e[2], v.stream));
+    sketch_write(v, sb, sb.hash.as<uint64_t>(), sb.pos.as<uint32_t>(), true);
+    UNIT_CHECK(hipEventRecord(ev.e[3], v.stream));
+    mm::lookup_kernel<<<blocks_for(nm, kThreads), kThreads, 0, v.stream>>>(ix->hashes(), ix->n_min, sb.hash.as<uint64_t>(), nm, c.max_occ, b.lo.as<uint32_t>(),
+                                                                          hit_off);
+    UNIT_CHECK(hipGetLastError());
+    UNIT_CHECK(hipEventRecord(ev.e[4], v.stream));
+    pwa::scan_excl(v.stream, hit_off, (size_t)nm + 1, b.slot_part.as<uint32_t>());
+    seed_read_offsets_kernel<<<blocks_for((size_t)nr + 1, kThreads), kThreads, 0, v.stream>>>(hit_off, sb.min_off.as<uint32_t>(), nr, b.anc_off.as<uint32_t>());
+    UNIT_CHECK(hipGetLastError());
+    b.h_anc_off.resize((size_t)nr + 1);
+    UNIT_CHECK(hipMemcpyAsync(b.h_anc_off.data(), b.anc_off.p, ((size_t)nr + 1) * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    sb.check_fault("pwa_mm_seed");
+    const uint32_t total = b.h_anc_off[nr];
+    for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept + b.h_anc_off[i];
+    ix->sketch_ms += span_ms(ev.e[2], ev.e[3]);
+    ix->search_ms += span_ms(ev.e[3], ev.e[4]);
+    ix->hits += total;
+    if (!total) return;
+    fit(v.poison, b.key, (size_t)total * 16);
+    fit(v.poison, b.val, (size_t)total * 8);
+    b.fit_sort(v.poison, total);
+    SortBufs<uint64_t, uint32_t> s{{b.key.as<uint64_t>(), b.key.as<uint64_t>() + total}, {b.val.as<uint32_t>(), b.val.as<uint32_t>() + total}, 0};
+    UNIT_CHECK(hipEventRecord(ev.e[5], v.stream));
+    mm::gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->positions(), ix->n_min, b.lo.as<uint32_t>(), hit_off, nm, total,
+                                                                             sb.min_off.as<uint32_t>(), nr, sb.pos.as<uint32_t>(), s.k[0], s.v[0],
+                                                                             sb.fault.as<uint32_t>());
+    UNIT_CHECK(hipGetLastError());
+    radix_sort(v.stream, s, total, b.sc);
+    uint32_t* d_t = reinterpret_cast<uint32_t*>(s.k[s.cur ^ 1]);   // the sort's other key buffer is free now
+    seed_split_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], total, d_t);
+    UNIT_CHECK(hipGetLastError());
+    UNIT_CHECK(hipEventRecord(ev.e[6], v.stream));
+    ix->anc_t.resize(kept + total);
+    ix->anc_q.resize(kept + total);
+    UNIT_CHECK(hipMemcpyAsync(ix->anc_t.data() + kept, d_t, (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(ix->anc_q.data() + kept, s.v[s.cur], (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipStreamSynchronize(v.stream));
+    sb.check_fault("pwa_mm_seed");
+    ix->sort_ms += span_ms(ev.e[5], ev.e[6]);
 }
 
 }  // namespace
@@ -579,5 +777,235 @@ int pwa_sa_last_stats(const pwa_sa_index* ix, uint32_t* rounds, float* build_ms,
 }
 
 void pwa_sa_destroy(pwa_sa_index* ix) { delete ix; }
+
+// ---- minimizer sketches, the minimizer index, seeding against it
+
+int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index** out) {
+    if (!ctx || !out || (!text && n)) return PWA_E_INVALID;
+    *out = nullptr;
+    pwa::SaCtxView v = pwa::sa_ctx_view(ctx);
+    if (!mm_params_ok(k, w)) {
+        *v.err = "pwa_mm_create: k is 1 .. 31 and w is 1 .. 128";
+        return PWA_E_INVALID;
+    }
+    if (n >= (1ull << 31)) {
+        *v.err = "pwa_mm_create: a text of " + std::to_string(n) + " bytes; at most 2^31 - 1";
+        return PWA_E_CAPACITY;
+    }
+    pwa_mm_index* ix = new (std::nothrow) pwa_mm_index();
+    if (!ix) return PWA_E_NOMEM;
+    ix->ctx = ctx;
+    ix->k = k;
+    ix->w = w;
+    const int rc = pwa::guarded(v, [&] {
+        if (!kmers_of(n, k)) return;   // n < k: a valid, empty index
+        UNIT_CHECK(hipSetDevice(v.device));
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint64_t off[2] = {0, n};
+        SketchBuffers b;
+        pwa::Events<4> ev;
+        UNIT_CHECK(ev.create());
+        b.start(v);
+        sketch_count(v, text, off, 0, 1, k, w, b, &ev.e[0]);
+        ix->n_min = b.total;
+        ix->build_ms = span_ms(ev.e[0], ev.e[1]);
+        if (!b.total) return;   // no k-mer of the text is over ACGT alone
+        SortScratch sc;
+        UNIT_CHECK(ix->d_hash.alloc(v.poison, (size_t)b.total * 16));
+        UNIT_CHECK(ix->d_pos.alloc(v.poison, (size_t)b.total * 8));
+        sc.alloc(v.poison, b.total);
+        UNIT_CHECK(hipEventRecord(ev.e[2], v.stream));
+        sketch_write(v, b, ix->d_hash.as<uint64_t>(), ix->d_pos.as<uint32_t>(), false);
+        ix->half = pwa::sort_pairs(v.stream, ix->d_hash.as<uint64_t>(), ix->d_pos.as<uint32_t>(), b.total, sc);   // stable: (hash, t) order
+        UNIT_CHECK(hipEventRecord(ev.e[3], v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
+        b.check_fault("pwa_mm_create");
+        ix->build_ms += span_ms(ev.e[2], ev.e[3]);
+        if (v.debug)
+            std::fprintf(stderr, "[pwa] mm build: n=%llu k=%u w=%u: %u minimizers, device %.3f ms, call %.3f ms\n", (unsigned long long)n, k, w, ix->n_min,
+                         ix->build_ms, ms_since(t0));
+    });
+    if (rc == PWA_OK)
+        *out = ix;
+    else
+        delete ix;   // (half built)
+    return rc;
+}
+
+void pwa_mm_destroy(pwa_mm_index* ix) { delete ix; }
+
+int pwa_mm_fetch(pwa_mm_index* ix, uint64_t* hash_out, uint32_t* pos_out, uint64_t cap) {
+    if (!ix) return PWA_E_INVALID;
+    pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
+    if (cap < ix->n_min) {
+        *v.err = "pwa_mm_fetch: " + std::to_string(ix->n_min) + " minimizers, capacity " + std::to_string(cap);
+        return PWA_E_CAPACITY;
+    }
+    if (ix->n_min && (!hash_out || !pos_out)) return PWA_E_INVALID;
+    return pwa::guarded(v, [&] {
+        if (!ix->n_min) return;
+        UNIT_CHECK(hipMemcpyAsync(hash_out, ix->hashes(), (size_t)ix->n_min * 8, hipMemcpyDeviceToHost, v.stream));
+        UNIT_CHECK(hipMemcpyAsync(pos_out, ix->positions(), (size_t)ix->n_min * 4, hipMemcpyDeviceToHost, v.stream));
+        UNIT_CHECK(hipStreamSynchronize(v.stream));
+    });
+}
+
+int pwa_mm_last_stats(const pwa_mm_index* ix, uint64_t* n_min, float* build_ms) {
+    if (!ix) return PWA_E_INVALID;
+    if (n_min) *n_min = ix->n_min;
+    if (build_ms) *build_ms = ix->build_ms;
+    return PWA_OK;
+}
+
+int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k, uint32_t w, uint64_t* min_off_out,
+                  uint32_t* pos_out, uint64_t* hash_out, uint64_t cap, uint64_t* needed) {
+    if (!ctx || !min_off_out || (n_seqs && !seq_off) || (cap && (!pos_out || !hash_out))) return PWA_E_INVALID;
+    pwa::SaCtxView v = pwa::sa_ctx_view(ctx);
+    if (!seq_bytes && n_seqs && seq_off[n_seqs] != seq_off[0]) {
+        *v.err = "pwa_mm_sketch: a required pointer is null";
+        return PWA_E_INVALID;
+    }
+    std::string what;
+    if (const int rc = sketch_validate(seq_off, n_seqs, k, w, what)) {
+        *v.err = "pwa_mm_sketch: " + what;
+        return rc;
+    }
+    uint64_t kept = 0;
+    const int rc = pwa::guarded(v, [&] {
+        std::fill_n(min_off_out, (size_t)n_seqs + 1, 0ull);
+        const uint64_t budget = std::min<uint64_t>(v.occ_chunk_hits ? v.occ_chunk_hits : kDefaultChunkHits, 0xFFFFFFFFull);
+        // consecutive sequences whose k-mers fit the budget, or one that alone exceeds it (below 2^31 k-mers)
+        const std::vector<pwa::Run> runs = pwa::cut_runs(n_seqs, budget, [&](uint64_t r) { return kmers_of(seq_off[r + 1] - seq_off[r], k); });
+        SketchBuffers b;
+        bool started = false;
+        uint64_t done = 0;   // sequences whose offsets are written
+        for (const pwa::Run& g : runs) {
+            if (!g.weight) continue;
+            if (!started) {
+                UNIT_CHECK(hipSetDevice(v.device));
+                b.start(v);
+                started = true;
+            }
+            for (; done < g.k0; ++done) min_off_out[done] = kept;
+            sketch_count(v, seq_bytes, seq_off, g.k0, g.k1, k, w, b, nullptr);
+            const uint32_t nr = (uint32_t)(g.k1 - g.k0);
+            fit(v.poison, b.hash, (size_t)b.total * 8);
+            fit(v.poison, b.pos, (size_t)b.total * 4);
+            sketch_write(v, b, b.hash.as<uint64_t>(), b.pos.as<uint32_t>(), true);
+            b.h_min_off.resize((size_t)nr + 1);
+            UNIT_CHECK(hipMemcpyAsync(b.h_min_off.data(), b.min_off.p, ((size_t)nr + 1) * 4, hipMemcpyDeviceToHost, v.stream));
+            if (b.total && kept + b.total <= cap) {
+                UNIT_CHECK(hipMemcpyAsync(hash_out + kept, b.hash.p, (size_t)b.total * 8, hipMemcpyDeviceToHost, v.stream));
+                UNIT_CHECK(hipMemcpyAsync(pos_out + kept, b.pos.p, (size_t)b.total * 4, hipMemcpyDeviceToHost, v.stream));
+            }
+            UNIT_CHECK(hipStreamSynchronize(v.stream));
+            b.check_fault("pwa_mm_sketch");
+            for (uint32_t i = 0; i < nr; ++i) min_off_out[g.k0 + i] = kept + b.h_min_off[i];
+            kept += b.total;
+            done = g.k1;
+        }
+        for (; done <= n_seqs; ++done) min_off_out[done] = kept;
+    });
+    if (rc != PWA_OK) return rc;
+    if (needed) *needed = kept;
+    if (kept > cap) {
+        *v.err = "pwa_mm_sketch: " + std::to_string(kept) + " minimizers, capacity " + std::to_string(cap);
+        return PWA_E_CAPACITY;
+    }
+    return PWA_OK;
+}
+
+int pwa_mm_plan(uint64_t n_min, const uint64_t* read_off, uint32_t n_reads, uint32_t k, uint32_t max_occ, uint64_t budget_hits, uint32_t* bad_read,
+                uint64_t* n_slots, uint64_t* n_ranges) {
+    const SeedCall c = mm_call(n_min, read_off, n_reads, k, max_occ);
+    uint32_t bad = kNoRead;
+    uint64_t slots = 0, count = 0;
+    std::string what;
+    int rc = PWA_E_NOMEM;
+    try {
+        rc = k > mm::kMaxK ? PWA_E_INVALID : seed_validate(c, bad, slots, what);
+        if (rc == PWA_OK) count = seed_ranges(c, budget_hits).size();
+    } catch (const std::bad_alloc&) {
+        rc = PWA_E_NOMEM;
+    }
+    if (bad_read) *bad_read = bad;
+    if (n_slots) *n_slots = slots;
+    if (n_ranges) *n_ranges = count;
+    return rc;
+}
+
+int pwa_mm_seed(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads, uint32_t max_occ, uint64_t* anc_off_out) {
+    if (!ix) return PWA_E_INVALID;
+    pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
+    const SeedCall c = mm_call(ix->n_min, read_off, n_reads, ix->k, max_occ);
+    if (!anc_off_out || (!read_bytes && n_reads && read_off && read_off[n_reads] != read_off[0])) {
+        *v.err = "pwa_mm_seed: a required pointer is null";
+        return PWA_E_INVALID;
+    }
+    uint32_t bad = kNoRead;
+    uint64_t slots = 0;
+    std::string what;
+    if (const int rc = seed_validate(c, bad, slots, what)) {
+        *v.err = "pwa_mm_seed (the text's k-mers being the index's minimizers): " + what;
+        return rc;
+    }
+    ix->seeded = false;
+    ix->anc_t.clear();
+    ix->anc_q.clear();
+    ix->sketch_ms = ix->search_ms = ix->sort_ms = 0.f;
+    ix->slots = slots;
+    ix->minimizers = ix->hits = ix->ranges = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = pwa::guarded(v, [&] {
+        std::fill_n(anc_off_out, (size_t)n_reads + 1, 0ull);
+        const std::vector<pwa::Run> ranges = seed_ranges(c, v.occ_chunk_hits);
+        if (ranges.empty()) return;   // no read, no k-mer, or an empty index: nothing for the device to do
+        UNIT_CHECK(hipSetDevice(v.device));
+        SketchBuffers sb;
+        SeedBuffers b;
+        pwa::Events<8> ev;
+        UNIT_CHECK(ev.create());
+        sb.start(v);
+        uint64_t done = 0;   // reads whose offsets are written
+        for (const pwa::Run& g : ranges) {
+            for (; done < g.k0; ++done) anc_off_out[done] = ix->anc_t.size();   // the reads of a range without a k-mer
+            mm_seed_range(v, ix, c, read_bytes, g, sb, b, ev, anc_off_out);
+            done = g.k1;
+        }
+        for (; done <= n_reads; ++done) anc_off_out[done] = ix->anc_t.size();
+        if (v.debug)
+            std::fprintf(stderr, "[pwa] mm seed: %u reads, k=%u w=%u max_occ=%u: %llu slots, %llu minimizers, %llu hits, %llu ranges, sketch %.3f ms, search %.3f ms, sort %.3f ms, call %.3f ms\n",
+                         n_reads, ix->k, ix->w, max_occ, (unsigned long long)ix->slots, (unsigned long long)ix->minimizers, (unsigned long long)ix->hits,
+                         (unsigned long long)ix->ranges, ix->sketch_ms, ix->search_ms, ix->sort_ms, ms_since(t0));
+    });
+    ix->seeded = rc == PWA_OK;
+    return rc;
+}
+
+int pwa_mm_seed_fetch(const pwa_mm_index* ix, uint32_t* anc_t, uint32_t* anc_q, uint64_t cap) {
+    if (!ix || !ix->seeded) return PWA_E_INVALID;
+    const uint64_t total = ix->anc_t.size();
+    if (cap < total) {
+        *pwa::sa_ctx_view(ix->ctx).err = "pwa_mm_seed_fetch: " + std::to_string(total) + " anchors, capacity " + std::to_string(cap);
+        return PWA_E_CAPACITY;
+    }
+    if (total && (!anc_t || !anc_q)) return PWA_E_INVALID;
+    std::copy(ix->anc_t.begin(), ix->anc_t.end(), anc_t);
+    std::copy(ix->anc_q.begin(), ix->anc_q.end(), anc_q);
+    return PWA_OK;
+}
+
+int pwa_mm_seed_last_stats(const pwa_mm_index* ix, float* sketch_ms, float* search_ms, float* sort_ms, uint64_t* slots, uint64_t* minimizers,
+                           uint64_t* hits, uint64_t* ranges) {
+    if (!ix) return PWA_E_INVALID;
+    if (sketch_ms) *sketch_ms = ix->sketch_ms;
+    if (search_ms) *search_ms = ix->search_ms;
+    if (sort_ms) *sort_ms = ix->sort_ms;
+    if (slots) *slots = ix->slots;
+    if (minimizers) *minimizers = ix->minimizers;
+    if (hits) *hits = ix->hits;
+    if (ranges) *ranges = ix->ranges;
+    return PWA_OK;
+}
 
 }  // extern "C"

@@ -55,6 +55,7 @@
  *   PWA_BANDED_RL=4|8             pwa_align_banded_batch(_cigar), pwa_scores_banded, their _subst forms and the pwa_extend_banded calls (with or without a table): every pair on stripes of 256 / 512 rows (default: by the pair's band width)
  *   PWA_OCC_CHUNK_HITS=N          pwa_sa_occurrences: at most N raw hits per chunk of patterns (forces several chunks on a small list);
  *                                 pwa_sa_seed: at most N worst-case hits per range of reads (forces several ranges on a small list);
+ *                                 pwa_mm_seed: the same over the index's minimizers; pwa_mm_sketch: at most N k-mers per range of sequences;
  *                                 pwa_approx_occurrences: at most N hits staged on the device per slice of whole tasks;
  *                                 pwa_approx_starts: at most N hit records on the device per slice
  *   PWA_APPROX_CHUNK=N            pwa_approx_find / pwa_approx_occurrences: a task reports at most N text columns (default 4096)
@@ -802,6 +803,71 @@ int pwa_sa_seed(pwa_sa_index *ix, const uint8_t *read_bytes, const uint64_t *rea
                 uint32_t step, uint32_t max_occ, uint64_t *anc_off_out /* n_reads + 1 */);
 int pwa_sa_seed_fetch(const pwa_sa_index *ix, uint32_t *anc_t, uint32_t *anc_q, uint64_t cap);
 int pwa_sa_seed_last_stats(const pwa_sa_index *ix, float *search_ms, float *sort_ms, uint64_t *slots, uint64_t *hits, uint64_t *ranges);
+
+/* ---- Minimizer sketches, a minimizer index, seeding against it
+ *
+ * Codes.  Byte 'A' is 0, 'C' 1, 'G' 2, 'T' 3, uppercase only.  Every other byte value -- lowercase, 'N', NUL, >= 0x80 -- makes each
+ * k-mer that covers it invalid.  An anchor therefore always means text[t .. t + k) == read[q .. q + k) as raw bytes, as in pwa_sa_seed.
+ * k-mer value and hash.  1 <= k <= 31.  v(p) = sum of code(s[p + i]) * 4^(k - 1 - i), the first symbol most significant;
+ * h(p) = mix(v(p), 2^(2k) - 1), where mix(key, mask) is, in this order,
+ *   key = (~key + (key << 21)) & mask;  key ^= key >> 24;  key = (key + (key << 3) + (key << 8)) & mask;  key ^= key >> 14;
+ *   key = (key + (key << 2) + (key << 4)) & mask;  key ^= key >> 28;  key = (key + (key << 31)) & mask.
+ * It is a bijection on 2k bits: equal hashes mean equal k-mers, so a lookup by hash is exact.  An invalid k-mer compares as
+ * +infinity, above every valid hash (those are below 2^62).
+ * Windows.  1 <= w <= 128.  A sequence of L bytes has K = L - k + 1 k-mers (0 when L < k) at starts 0 .. K - 1.  If K >= w the
+ * windows are [s, s + w) for s = 0 .. K - w; if 1 <= K < w there is one window, [0, K).  A window selects its valid k-mer of smallest
+ * hash, the leftmost one among equals; a window with no valid k-mer selects nothing.  The sketch is the set of distinct selected
+ * starts in ascending order, each with its hash.  With w = 1 the sketch is every valid k-mer.  Equivalently, start p is selected iff
+ * it is valid and some window W that holds p has h(j) > h(p) for all j < p in W and h(j) >= h(p) for all j > p in W.
+ * Index.  The sketch of the text as given, n < 2^31 bytes, stored as pairs (hash, t) in ascending (hash, t); n_min is its size.
+ * n < k gives a valid, empty index.  Its size and build cost scale with the sketch: nothing per text position is kept.
+ * Seeding.  Each sketch entry (q, h) of read r hits every index entry with hash h; an entry with more than max_occ hits contributes
+ * none (occurrences are counted among the text's minimizers, not among all text positions).  Read r's anchors are (t, q) with
+ * len = k in ascending (t, q), the order pwa_chain_anchors requires, entries anc_off_out[r] .. anc_off_out[r + 1]) of anc_t and anc_q.
+ * On the device: one lane per k-mer start hashes it from the blob, a workgroup stages a tile's hashes with a halo of w - 1 in LDS,
+ * each lane decides by the local form among the neighbours of its own sequence, and the selected starts are compacted in position
+ * order; the read minimizers are looked up by binary search over the sorted hashes; the hits are gathered and sorted there.
+ * Validation runs before any device work; the first offending item decides the code.  pwa_mm_create and pwa_mm_sketch: a null
+ * required pointer PWA_E_INVALID; k outside 1 .. 31 or w outside 1 .. 128 PWA_E_INVALID; then in sequence order, offsets decreasing
+ * PWA_E_INVALID, a text or sequence of 2^31 bytes or more PWA_E_CAPACITY.  pwa_mm_seed and pwa_mm_plan follow pwa_seed_plan's rule
+ * with step = 1 and the text's k-mer count replaced by n_min: a null pointer or max_occ = 0 (for the plan also k outside 1 .. 31)
+ * PWA_E_INVALID; then in read order read_off decreasing PWA_E_INVALID, a read of 2^31 bytes or more PWA_E_CAPACITY, worst-case hits
+ * (len - k + 1) x min(max_occ, n_min) of 2^32 or more PWA_E_CAPACITY; then a total of 2^32 k-mers or more PWA_E_CAPACITY.
+ * n_reads = 0, an empty index and reads shorter than k are valid calls with all-zero offsets.
+ * Ranges.  The same greedy cut over worst-case hits as pwa_sa_seed, under PWA_OCC_CHUNK_HITS or else 2^27; one read alone may exceed
+ * it.  A range without a k-mer is not run or counted.  pwa_mm_sketch cuts its list the same way by k-mers under the same budget.
+ *   pwa_mm_create           uploads text[0 .. n), sketches it and sorts the pairs on the context's GPU; the text is not kept.
+ *   pwa_mm_fetch            copies the sorted entries out: hash_out[n_min], pos_out[n_min]; PWA_E_CAPACITY when cap < n_min.
+ *   pwa_mm_last_stats       n_min, and the device ms of sketch + sort (events).  Either pointer may be NULL.
+ *   pwa_mm_sketch           the sketches of a sequence list: sequence r's entries are min_off_out[r] .. min_off_out[r + 1]) of
+ *                           pos_out and hash_out, in ascending position.  PWA_E_CAPACITY with *needed set (needed may be NULL) and
+ *                           min_off_out complete when cap is too small; the total k-mer count always suffices as cap.
+ *   pwa_mm_plan             host only, no context, no GPU: pwa_seed_plan for an index of n_min entries -- the validation code,
+ *                           *bad_read (0xFFFFFFFF: none, or a pointer, a parameter or the total was at fault), *n_slots = the
+ *                           list's k-mers, *n_ranges under budget_hits (0: the library's budget); the last three may be NULL.
+ *   pwa_mm_seed             runs the seeding, writes anc_off_out[n_reads + 1], and keeps the call's anchors with the index until the
+ *                           next pwa_mm_seed on it or pwa_mm_destroy.
+ *   pwa_mm_seed_fetch       copies the kept anchors out; PWA_E_CAPACITY when cap < anc_off_out[n_reads], PWA_E_INVALID when no
+ *                           seeding has run on the index (or the last one failed on the device).
+ *   pwa_mm_seed_last_stats  of the last pwa_mm_seed on ix: device ms of the sketch passes, of the lookup kernel and of gather + sort
+ *                           + split (events, summed over the ranges); slots = the k-mers examined, minimizers = the read minimizers
+ *                           looked up, the hits kept, the ranges run.  Any pointer may be NULL; a call that fails validation leaves
+ *                           them, and the kept anchors, unchanged.
+ * A kernel that finds one of its bounds violated sets the call's fault word; the call then returns PWA_E_HIP. */
+typedef struct pwa_mm_index pwa_mm_index;
+int pwa_mm_create(pwa_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index **out);
+void pwa_mm_destroy(pwa_mm_index *ix);
+int pwa_mm_fetch(pwa_mm_index *ix, uint64_t *hash_out, uint32_t *pos_out, uint64_t cap);
+int pwa_mm_last_stats(const pwa_mm_index *ix, uint64_t *n_min, float *build_ms);
+int pwa_mm_sketch(pwa_ctx *ctx, const uint8_t *seq_bytes, const uint64_t *seq_off /* n_seqs + 1 */, uint32_t n_seqs, uint32_t k, uint32_t w,
+                  uint64_t *min_off_out /* n_seqs + 1 */, uint32_t *pos_out, uint64_t *hash_out, uint64_t cap, uint64_t *needed /* or NULL */);
+int pwa_mm_plan(uint64_t n_min, const uint64_t *read_off /* n_reads + 1 */, uint32_t n_reads, uint32_t k, uint32_t max_occ,
+                uint64_t budget_hits, uint32_t *bad_read /* or NULL */, uint64_t *n_slots /* or NULL */, uint64_t *n_ranges /* or NULL */);
+int pwa_mm_seed(pwa_mm_index *ix, const uint8_t *read_bytes, const uint64_t *read_off /* n_reads + 1 */, uint32_t n_reads, uint32_t max_occ,
+                uint64_t *anc_off_out /* n_reads + 1 */);
+int pwa_mm_seed_fetch(const pwa_mm_index *ix, uint32_t *anc_t, uint32_t *anc_q, uint64_t cap);
+int pwa_mm_seed_last_stats(const pwa_mm_index *ix, float *sketch_ms, float *search_ms, float *sort_ms, uint64_t *slots, uint64_t *minimizers,
+                           uint64_t *hits, uint64_t *ranges);
 
 /* ---- k-edit approximate pattern search (Sellers' DP on bit-parallel columns, Myers 1999)
  *
