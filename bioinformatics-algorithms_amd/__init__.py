@@ -44,7 +44,7 @@ EXPORTS = [
     "pwa_sa_create", "pwa_sa_fetch", "pwa_sa_find", "pwa_sa_occurrences", "pwa_sa_last_stats", "pwa_sa_destroy",
     "pwa_seed_plan", "pwa_sa_seed", "pwa_sa_seed_fetch", "pwa_sa_seed_last_stats",
     "pwa_mm_create", "pwa_mm_destroy", "pwa_mm_fetch", "pwa_mm_last_stats", "pwa_mm_sketch", "pwa_mm_plan", "pwa_mm_seed", "pwa_mm_seed_fetch",
-    "pwa_mm_seed_last_stats",
+    "pwa_mm_seed_last_stats", "pwa_mm_create_canonical", "pwa_mm_fetch_canonical", "pwa_mm_sketch_canonical", "pwa_mm_seed_strands",
     "pwa_approx_find", "pwa_approx_occurrences", "pwa_approx_last_stats", "pwa_approx_plan",
     "pwa_approx_starts", "pwa_approx_starts_last_stats", "pwa_approx_minima",
     "pwa_wfa_plan", "pwa_scores_wfa", "pwa_align_wfa_batch", "pwa_align_wfa_batch_cigar", "pwa_align_wfa_codes_batch",
@@ -427,6 +427,11 @@ def lib():
     L.pwa_mm_seed.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, u64p]
     L.pwa_mm_seed_fetch.argtypes = [vp, u32p, u32p, C.c_uint64]
     L.pwa_mm_seed_last_stats.argtypes = [vp, f32p, f32p, f32p, u64p, u64p, u64p, u64p]
+    u8p = C.POINTER(C.c_uint8)
+    L.pwa_mm_create_canonical.argtypes = L.pwa_mm_create.argtypes
+    L.pwa_mm_fetch_canonical.argtypes = [vp, u64p, u32p, u8p, C.c_uint64]
+    L.pwa_mm_sketch_canonical.argtypes = [vp, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, u64p, u8p, C.c_uint64, u64p]
+    L.pwa_mm_seed_strands.argtypes = L.pwa_mm_seed.argtypes
     L.pwa_approx_find.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u32p, i32p, u32p]
     L.pwa_approx_occurrences.argtypes = [vp, vp, C.c_uint64, vp, u64p, C.c_uint32, u32p, u64p, u64p, C.c_uint64, u64p]
     L.pwa_approx_last_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u64p, u64p]
@@ -1488,17 +1493,22 @@ class Context:
             out.append(d)
         return out
 
-    def index(self, text, minimizers=None):
+    def index(self, text, minimizers=None, canonical=False):
         """A TextIndex of text: its suffix array, built once on the device and kept for any number of seed() / map_reads() calls.
-        With minimizers=(k, w) a MinimizerIndex instead: the text's (w, k)-minimizer sketch sorted by hash, for the same calls."""
+        With minimizers=(k, w) a MinimizerIndex instead: the text's (w, k)-minimizer sketch sorted by hash, for the same calls; with
+        canonical=True its canonical form (pwa_mm_create_canonical), which seed_strands() and map_reads() seed on both strands from
+        one sketch of every read."""
         if minimizers is not None:
             k, w = minimizers
-            return MinimizerIndex(self, text, k, w)
+            return MinimizerIndex(self, text, k, w, canonical)
+        if canonical:
+            raise ValueError("index: canonical=True goes with minimizers=(k, w)")
         return TextIndex(self, text)
 
-    def sketch(self, seqs, k, w, as_arrays=False):
+    def sketch(self, seqs, k, w, as_arrays=False, canonical=False):
         """pwa_mm_sketch: the (w, k)-minimizer sketch of every sequence -> per sequence a list of (pos, hash) in ascending pos, or
-        with as_arrays a pair of arrays (pos uint32, hash uint64)."""
+        with as_arrays a pair of arrays (pos uint32, hash uint64).  With canonical=True pwa_mm_sketch_canonical: (pos, hash, strand),
+        the hash that of the smaller of the k-mer and its reverse complement, strand 1 where that is the reverse complement (uint8)."""
         import numpy as np
         if not (1 <= k <= 31 and 1 <= w <= 128):
             raise ValueError("sketch: k is 1 .. 31 and w is 1 .. 128")
@@ -1512,6 +1522,16 @@ class Context:
         min_off = np.zeros(n + 1, dtype=np.uint64)
         pos, hsh = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64)
         need = C.c_uint64(0)
+        if canonical:
+            std = np.zeros(max(cap, 1), dtype=np.uint8)
+            self._check(self._L.pwa_mm_sketch_canonical(self._h, b"".join(seqs), off.ctypes.data_as(u64p), n, k, w, min_off.ctypes.data_as(u64p), _u32p(pos),
+                                                        hsh.ctypes.data_as(u64p), std.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(need)),
+                        "pwa_mm_sketch_canonical")
+            cut = min_off.astype(np.int64).tolist()
+            if as_arrays:
+                return [(pos[cut[i]:cut[i + 1]], hsh[cut[i]:cut[i + 1]], std[cut[i]:cut[i + 1]]) for i in range(n)]
+            rows = list(zip(pos[:cut[n]].tolist(), hsh[:cut[n]].tolist(), std[:cut[n]].tolist()))
+            return [rows[cut[i]:cut[i + 1]] for i in range(n)]
         self._check(self._L.pwa_mm_sketch(self._h, b"".join(seqs), off.ctypes.data_as(u64p), n, k, w, min_off.ctypes.data_as(u64p), _u32p(pos),
                                           hsh.ctypes.data_as(u64p), cap, C.byref(need)), "pwa_mm_sketch")
         cut = min_off.astype(np.int64).tolist()
@@ -1530,7 +1550,8 @@ class Context:
         k-mers read[q:q + k] at q = 0, step, 2 step, ... are cut, searched, gathered and sorted on the device; a k-mer with more than
         max_occ occurrences is dropped.  -> per read its anchors (t, q, k) in the order chain() requires (by t, then q), as a list of
         tuples, or with as_arrays as a uint32 array of shape (n, 3).  Sets seed_stats = dict(search_ms, sort_ms, slots, hits, ranges).
-        On a MinimizerIndex (k its own, step 1, else ValueError) the anchors are those of MinimizerIndex.seed."""
+        On a MinimizerIndex (k its own, step 1, else ValueError) the anchors are those of MinimizerIndex.seed; a canonical one is
+        seeded by its seed_strands() instead (ValueError here)."""
         if isinstance(text, MinimizerIndex):
             self._on_minimizers(text, k, step)
             return text.seed(reads, max_occ, as_arrays)
@@ -1543,7 +1564,7 @@ class Context:
 
     def map_reads(self, text, reads, k, match, mismatch, gap_open, gap_extend, w=100, step=1, max_occ=64, both_strands=False, lookback=64,
                   max_dist=5000, bandwidth=500, gap_scale=38, secondary=0, min_chain_score=40, min_chain_count=3):
-        """Seed, chain, align (text: bytes, or a TextIndex or MinimizerIndex kept across calls; the latter with its own k and step 1): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
+        """Seed, chain, align (text: bytes, or a TextIndex or MinimizerIndex kept across calls; the latter with its own k and step 1; a canonical MinimizerIndex is seeded by seed_strands() of the reads as given, no reverse complement is built but that of a read placed on '-'): seed() of every read (with both_strands also of its reverse complement; the strand with the higher
         chain score is kept, ties go forward), chain() of the anchors, then align_banded_batch_cigar("sg", ...) of the read against
         the text window [max(0, t_begin - q_begin - w), min(len(text), t_end + (n - q_end) + w)) in the band (diag_lo - window start -
         w, diag_hi - window start + w).  -> per read dict(pos, end, score, cigar, mdz, strand, chain_score) in text coordinates
@@ -1564,9 +1585,9 @@ class Context:
         text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
         nr = len(fw)
-        strands = [fw, [revcomp(r) for r in fw]] if both_strands else [fw]
+        strands = self._strand_lists(index, fw, both_strands)
         t0 = time.perf_counter()
-        anchors = self.seed(index or text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+        anchors = self._seed_strand_lists(index, text, strands, k, step, max_occ)
         t1 = time.perf_counter()
         chains = self.chain(anchors, lookback, max_dist, bandwidth, gap_scale)
         t2 = time.perf_counter()
@@ -1582,7 +1603,7 @@ class Context:
             lo, hi = c["diag_lo"] - ws - w, c["diag_hi"] - ws + w
             if hi - lo + 1 > 4096 or hi < 0 or n + lo > we - ws:
                 continue
-            pats.append(strands[s][i])
+            pats.append(self._strand_read(strands, s, i))
             wins.append(text[ws:we])
             bands.append((lo, hi))
             placed.append((i, "+-"[s], ws, c["score"]))
@@ -1596,6 +1617,31 @@ class Context:
             out[i] = dict(pos=ws + a["start"][1], end=ws + a["end"][1], score=a["score"], cigar=a["cigar"], mdz=a["mdz"], strand=strand, chain_score=cs)
         return out
 
+    @staticmethod
+    def _strand_lists(index, fw, both_strands):
+        """map_reads' strands: strands[s][i] = read i as strand s is aligned.  Under a canonical MinimizerIndex the reverse strand
+        starts as None entries, which _strand_read fills for the reads placed there."""
+        if not both_strands:
+            return [fw]
+        if isinstance(index, MinimizerIndex) and index.canonical:
+            return [fw, [None] * len(fw)]
+        return [fw, [revcomp(r) for r in fw]]
+
+    def _seed_strand_lists(self, index, text, strands, k, step, max_occ):
+        """map_reads' seeding: anchors[s * n + i] = the anchor list of strands[s][i].  A canonical MinimizerIndex seeds both
+        strands from the reads as given."""
+        if isinstance(index, MinimizerIndex) and index.canonical:
+            self._on_minimizers(index, k, step)
+            anchors = index.seed_strands(strands[0], max_occ, as_arrays=True)
+            return anchors[:len(strands) * len(strands[0])]
+        return self.seed(index or text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+
+    @staticmethod
+    def _strand_read(strands, s, i):
+        if strands[s][i] is None:
+            strands[s][i] = revcomp(strands[0][i])
+        return strands[s][i]
+
     def _map_reads_secondary(self, text, reads, k, match, mismatch, gap_open, gap_extend, w, step, max_occ, both_strands, lookback, max_dist, bandwidth,
                              gap_scale, secondary, min_chain_score, min_chain_count):
         """map_reads with secondary >= 1: the top chains of every strand pooled per read, one banded call for all their windows"""
@@ -1604,9 +1650,9 @@ class Context:
         text = index.text if index else _b(text)
         fw = [_b(r) for r in reads]
         nr = len(fw)
-        strands = [fw, [revcomp(r) for r in fw]] if both_strands else [fw]
+        strands = self._strand_lists(index, fw, both_strands)
         t0 = time.perf_counter()
-        anchors = self.seed(index or text, [r for s in strands for r in s], k, step, max_occ, as_arrays=True)
+        anchors = self._seed_strand_lists(index, text, strands, k, step, max_occ)
         t1 = time.perf_counter()
         tops = self.chain_top(anchors, secondary + 1, min_chain_score, min_chain_count, True, lookback, max_dist, bandwidth, gap_scale)
         t2 = time.perf_counter()
@@ -1625,7 +1671,7 @@ class Context:
                     if rank == 0:
                         break    # no primary: the read is None
                     continue
-                pats.append(strands[s][i])
+                pats.append(self._strand_read(strands, s, i))
                 wins.append(text[ws:we])
                 bands.append((lo, hi))
                 placed.append((i, rank, "+-"[s], ws, c))
@@ -1708,16 +1754,19 @@ class MinimizerIndex:
     """The (w, k)-minimizer index of one text, resident on the context's GPU (pwa_mm_create): the text's sketch as (hash, pos) pairs in
     that order, built once, then seeded against by any number of read lists (pwa_mm_seed).  Keeps the text bytes (map_reads cuts its
     windows from them).  k, w; stats = dict(minimizers, build_ms) of the build; close() frees it, and it works as a context manager.
-    Close it before its context."""
+    Close it before its context.  With canonical=True (pwa_mm_create_canonical) a k-mer and its reverse complement share one hash
+    and every entry has a strand bit: seed_strands() then finds a read's anchors on both strands from one sketch of the read, and
+    seed() is refused; on a plain index it is the other way round."""
 
-    def __init__(self, ctx, text, k, w):
+    def __init__(self, ctx, text, k, w, canonical=False):
         if not (1 <= k <= 31 and 1 <= w <= 128):
             raise ValueError("MinimizerIndex: k is 1 .. 31 and w is 1 .. 128")
         self._ctx, self._L = ctx, ctx._L
         self.text = _b(text)
-        self.k, self.w = k, w
+        self.k, self.w, self.canonical = k, w, bool(canonical)
         ix = C.c_void_p()
-        ctx._check(self._L.pwa_mm_create(ctx._h, self.text, len(self.text), k, w, C.byref(ix)), "pwa_mm_create")
+        create = "pwa_mm_create_canonical" if self.canonical else "pwa_mm_create"
+        ctx._check(getattr(self._L, create)(ctx._h, self.text, len(self.text), k, w, C.byref(ix)), create)
         self._ix = ix
         n, ms = C.c_uint64(0), C.c_float(0)
         ctx._check(self._L.pwa_mm_last_stats(ix, C.byref(n), C.byref(ms)), "pwa_mm_last_stats")
@@ -1736,12 +1785,18 @@ class MinimizerIndex:
         self.close()
 
     def entries(self):
-        """pwa_mm_fetch -> (hash uint64 array, pos uint32 array), in ascending (hash, pos)"""
+        """pwa_mm_fetch -> (hash uint64 array, pos uint32 array), in ascending (hash, pos); on a canonical index
+        pwa_mm_fetch_canonical -> (hash, pos, strand uint8 array)"""
         import numpy as np
         if not self._ix:
             raise PwaError("MinimizerIndex.entries: the index is closed")
         n = self.stats["minimizers"]
         h, p = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+        if self.canonical:
+            s = np.zeros(max(n, 1), dtype=np.uint8)
+            self._ctx._check(self._L.pwa_mm_fetch_canonical(self._ix, h.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(p),
+                                                            s.ctypes.data_as(C.POINTER(C.c_uint8)), n), "pwa_mm_fetch_canonical")
+            return h[:n], p[:n], s[:n]
         self._ctx._check(self._L.pwa_mm_fetch(self._ix, h.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(p), n), "pwa_mm_fetch")
         return h[:n], p[:n]
 
@@ -1749,7 +1804,24 @@ class MinimizerIndex:
         """pwa_mm_seed + pwa_mm_seed_fetch: every read's minimizers looked up among the text's -> what TextIndex.seed returns, per read
         its anchors (t, q, k) by t, then q.  Sets seed_stats = dict(sketch_ms, search_ms, sort_ms, slots, minimizers, hits, ranges)
         here and on the context: device ms of the sketch passes, the lookup kernel and gather + sort + split, the list's k-mers, the
-        read minimizers looked up, the hits kept, the ranges of reads the call ran."""
+        read minimizers looked up, the hits kept, the ranges of reads the call ran.  ValueError on a canonical index."""
+        if self.canonical:
+            raise ValueError("MinimizerIndex.seed: the index is canonical; seed_strands() seeds it")
+        return self._seed(reads, max_occ, as_arrays, 1)
+
+    def seed_strands(self, reads, max_occ=64, as_arrays=False):
+        """pwa_mm_seed_strands + pwa_mm_seed_fetch on a canonical index (ValueError on a plain one): every read sketched once, as
+        given, its hits split by strand -> a list of 2 n anchor lists in seed()'s form, entry i read i forward, anchors (t, q, k),
+        entry n + i read i reverse, anchors (t, q', k) in the coordinates of revcomp(read i) -- the shape of
+        seed(reads + [revcomp(r) for r in reads]) on a plain index, so chain() and chain_top() take it unchanged.  Sets seed_stats as
+        seed() does; minimizers counts each read minimizer once, and max_occ counts a minimizer's hits over both strands."""
+        if not self.canonical:
+            raise ValueError("MinimizerIndex.seed_strands: the index is not canonical; seed() seeds it")
+        lists = self._seed(reads, max_occ, as_arrays, 2)
+        return lists[0::2] + lists[1::2]
+
+    def _seed(self, reads, max_occ, as_arrays, per):
+        """the seeding call with `per` lists per read, in the call's order"""
         import numpy as np
         if max_occ < 1:
             raise ValueError("seed: max_occ is at least 1")
@@ -1761,10 +1833,11 @@ class MinimizerIndex:
         if n:
             off[1:] = np.cumsum([len(r) for r in reads])
         u64p = C.POINTER(C.c_uint64)
-        anc_off = np.zeros(n + 1, dtype=np.uint64)
+        anc_off = np.zeros(per * n + 1, dtype=np.uint64)
         ck = self._ctx._check
-        ck(self._L.pwa_mm_seed(self._ix, b"".join(reads), off.ctypes.data_as(u64p), n, max_occ, anc_off.ctypes.data_as(u64p)), "pwa_mm_seed")
-        total = int(anc_off[n])
+        call = "pwa_mm_seed_strands" if per == 2 else "pwa_mm_seed"
+        ck(getattr(self._L, call)(self._ix, b"".join(reads), off.ctypes.data_as(u64p), n, max_occ, anc_off.ctypes.data_as(u64p)), call)
+        total = int(anc_off[per * n])
         trip = np.empty((total, 3), dtype=np.uint32)
         t, q = np.zeros(max(total, 1), dtype=np.uint32), np.zeros(max(total, 1), dtype=np.uint32)
         ck(self._L.pwa_mm_seed_fetch(self._ix, _u32p(t), _u32p(q), total), "pwa_mm_seed_fetch")
@@ -1777,9 +1850,9 @@ class MinimizerIndex:
                                                       hits=nh.value, ranges=nr.value)
         cut = anc_off.astype(np.int64).tolist()
         if as_arrays:
-            return [trip[cut[i]:cut[i + 1]] for i in range(n)]
+            return [trip[cut[i]:cut[i + 1]] for i in range(per * n)]
         rows = trip.tolist()
-        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(n)]
+        return [[tuple(x) for x in rows[cut[i]:cut[i + 1]]] for i in range(per * n)]
 
 
 class Batch:

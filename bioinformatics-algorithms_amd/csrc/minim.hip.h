@@ -1,5 +1,6 @@
 // minim.hip.h -- (w, k)-minimizer sketches of a sequence list, and the lookup of read minimizers in a sorted minimizer index
-// (the definitions are in include/pwalign.h, "Minimizer sketches, a minimizer index, seeding against it").  Like
+// (DESIGN.md §3.27, and §3.28 for the canonical form; the definitions are in include/pwalign.h, "Minimizer sketches, a minimizer index,
+// seeding against it" and "Canonical minimizers: one sketch, both strands").  Like
 // seed.hip.h these are plain data-parallel passes of the suffix-array unit: the flattened slot order, owner_of and load8 are its own,
 // and so are the scan, the sort and the split that the host code runs around them.
 //
@@ -49,6 +50,30 @@ __device__ inline uint64_t kmer_hash(const uint8_t* blob, uint64_t po, uint32_t 
     return (seen & 4u) ? kInvalid : mix(v, mask);
 }
 
+// The canonical form: f = the k-mer's value, r = its reverse complement's, both out of the same load8 loop -- every
+// symbol enters f at the bottom and, complemented, r at the top.  The smaller of the two is hashed and strand = 1 where that is r;
+// f == r (a reverse palindrome, even k only) is kInvalid like a k-mer over N.
+__device__ inline uint64_t kmer_hash_canonical(const uint8_t* blob, uint64_t po, uint32_t k, uint64_t mask, uint32_t& strand) {
+    uint64_t f = 0, r = 0;
+    uint32_t seen = 0;
+    const uint32_t top = 2 * (k - 1);
+    for (uint32_t o = 0; o < k; o += 8) {
+        uint64_t word = load8(blob, po + o);
+        const uint32_t m = k - o < 8 ? k - o : 8;
+        for (uint32_t j = 0; j < m; ++j, word >>= 8) {
+            const uint32_t b = (uint32_t)word & 0xffu;
+            const uint32_t c = b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u;
+            seen |= c;
+            f = f << 2 | (c & 3u);
+            r = r >> 2 | (uint64_t)(3u - (c & 3u)) << top;
+        }
+    }
+    strand = r < f ? 1u : 0u;
+    return ((seen & 4u) || f == r) ? kInvalid : mix(r < f ? r : f, mask);
+}
+
+constexpr uint32_t kStrandBit = 0x80000000u;   // of a canonical sketch's position word on the device (positions are below 2^31)
+
 struct SketchArgs {
     const uint8_t* blob;
     const uint64_t* seq_off;
@@ -63,7 +88,9 @@ struct SketchArgs {
 // a + b >= min(w, K) - 1: some window holds it with only larger hashes before and no smaller one after (the leftmost minimum).
 // COUNT form: tile_cnt[tile] = the tile's selected starts.  WRITE form: tile_cnt holds their exclusive scan; the in-tile rank is
 // the wave's ballot below the lane plus the counts of the waves before, so the output is in slot order without an atomic.
-template <bool WRITE>
+// CANON: the hashes are canonical ones; LDS still holds hashes only, a lane keeps the strand bit of its own k-mer in a register and
+// a selected one writes it as bit 31 of its position word.
+template <bool WRITE, bool CANON = false>
 __global__ __launch_bounds__(kThreads) void sketch_kernel(const SketchArgs a, uint32_t* tile_cnt, uint64_t* hash_out, uint32_t* pos_out,
                                                           uint32_t* flat_out, uint32_t cap, uint32_t* fault) {
     __shared__ uint64_t sh[kStage];
@@ -73,19 +100,21 @@ __global__ __launch_bounds__(kThreads) void sketch_kernel(const SketchArgs a, ui
     const uint64_t t0 = (uint64_t)blockIdx.x * kThreads;   // staged index i holds slot t0 - halo + i
     const uint64_t s = t0 + tid;
     const bool live = s < a.n_slots;
-    uint32_t p = 0, K = 0;
+    uint32_t p = 0, K = 0, strand = 0;
     if (live) {
         const uint32_t r = owner_of(a.slot_off, a.n_seqs, (uint32_t)s);
         p = (uint32_t)s - a.slot_off[r];
         K = a.slot_off[r + 1] - a.slot_off[r];
-        sh[halo + tid] = kmer_hash(a.blob, a.seq_off[r] + p, a.k, mask);
+        sh[halo + tid] = CANON ? kmer_hash_canonical(a.blob, a.seq_off[r] + p, a.k, mask, strand) : kmer_hash(a.blob, a.seq_off[r] + p, a.k, mask);
     }
     if (tid < 2 * halo) {
         const uint32_t i = tid < halo ? tid : kThreads + tid;
         const uint64_t at = t0 + i;   // the slot + halo
         if (at >= halo && at - halo < a.n_slots) {
             const uint32_t x = (uint32_t)(at - halo), r = owner_of(a.slot_off, a.n_seqs, x);
-            sh[i] = kmer_hash(a.blob, a.seq_off[r] + (x - a.slot_off[r]), a.k, mask);
+            uint32_t other;
+            sh[i] = CANON ? kmer_hash_canonical(a.blob, a.seq_off[r] + (x - a.slot_off[r]), a.k, mask, other)
+                          : kmer_hash(a.blob, a.seq_off[r] + (x - a.slot_off[r]), a.k, mask);
         }
     }
     __syncthreads();
@@ -120,7 +149,7 @@ __global__ __launch_bounds__(kThreads) void sketch_kernel(const SketchArgs a, ui
         return;
     }
     hash_out[rank] = h;
-    pos_out[rank] = p;
+    pos_out[rank] = CANON ? p | (strand ? kStrandBit : 0u) : p;
     if (flat_out) flat_out[rank] = (uint32_t)s;
 }
 
@@ -183,6 +212,95 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const uint32_t* ix_pos
     else *fault = 1u;   // (a range past the index: internal error)
     key[h] = (uint64_t)r << 32 | t;
     val[h] = q_pos[m];
+}
+
+// The gather of a canonical seeding, one lane per hit: t and s_t from the index's position word, q and s_q from the
+// read sketch's, L from seq_off.  key = (2 local read + (s_q ^ s_t)) << 32 | t; val = q in a forward list (s_q == s_t) and the mirrored
+// start L - k - q in a reverse one, which descends where q ascends: split_strands_kernel turns those runs round after the sort.
+__global__ __launch_bounds__(kThreads) void gather_strands_kernel(const uint32_t* ix_pos, uint32_t n_min, const uint32_t* lo, const uint32_t* hit_off,
+                                                                  uint32_t n_q, uint32_t total, const uint32_t* min_off, uint32_t n_reads,
+                                                                  const uint32_t* q_pos, const uint64_t* seq_off, uint32_t k, uint64_t* key,
+                                                                  uint32_t* val, uint32_t* fault) {
+    const uint32_t h = blockIdx.x * kThreads + threadIdx.x;
+    if (h >= total) return;
+    const uint32_t m = owner_of(hit_off, n_q, h);
+    const uint32_t r = owner_of(min_off, n_reads, m);
+    const uint64_t at = (uint64_t)lo[m] + (h - hit_off[m]);
+    uint32_t tw = 0;
+    if (at < n_min) tw = ix_pos[at];
+    else *fault = 1u;   // (a range past the index: internal error)
+    const uint32_t qw = q_pos[m], q = qw & ~kStrandBit, flip = (qw ^ tw) >> 31;
+    const uint64_t len = seq_off[r + 1] - seq_off[r];
+    uint32_t v = q;
+    if (flip) {
+        if ((uint64_t)q + k <= len) v = (uint32_t)(len - k - q);
+        else *fault = 1u;   // (a minimizer past its read's end: internal error)
+    }
+    key[h] = (uint64_t)(2u * r + flip) << 32 | (tw & ~kStrandBit);
+    val[h] = v;
+}
+
+// list_off[i] = how many of the `total` sorted keys belong to a list below i, i = 0 .. n_lists: a hit's list is known only once it is
+// gathered, so the cuts come from the sorted keys, one lower bound per boundary as in sketch_offsets_kernel.
+__global__ __launch_bounds__(kThreads) void list_offsets_kernel(const uint64_t* key, uint32_t total, uint32_t n_lists, uint32_t* list_off) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i > n_lists) return;
+    const uint64_t x = (uint64_t)i << 32;
+    uint32_t lo = 0, hi = total;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (key[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    list_off[i] = lo;
+}
+
+// The first (DIR = -1) or last (+1) index of the run of keys equal to key[h] = kk in the sorted key[0 .. total): doubling steps away
+// from h, then a binary search in the last step -- two loads where the run is h alone, log of the run otherwise.
+template <int DIR>
+__device__ inline uint32_t run_edge(const uint64_t* key, uint32_t total, uint32_t h, uint64_t kk) {
+    uint32_t in = h, out, step = 1;   // key[in] == kk; out: one past the edge at the earliest
+    for (;;) {
+        const uint32_t room = DIR < 0 ? in : total - 1u - in;
+        if (room < step) {
+            out = DIR < 0 ? 0u : total - 1u;
+            break;
+        }
+        const uint32_t at = DIR < 0 ? in - step : in + step;
+        if (key[at] != kk) {
+            out = DIR < 0 ? at + 1u : at - 1u;
+            break;
+        }
+        in = at;
+        step <<= 1;
+    }
+    uint32_t lo = DIR < 0 ? out : in, hi = DIR < 0 ? in : out;   // the edge lies in [lo, hi]
+    while (lo < hi) {
+        if (DIR < 0) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (key[mid] == kk) hi = mid;
+            else lo = mid + 1u;
+        } else {
+            const uint32_t mid = lo + (hi - lo + 1u) / 2;
+            if (key[mid] == kk) lo = mid;
+            else hi = mid - 1u;
+        }
+    }
+    return lo;
+}
+
+// seed_split_kernel for the two lists per read, one lane per sorted hit: t_out = the key's low word, and the values move to val_out --
+// in place in a forward (even) list; in a reverse (odd) list the hits of one (list, t) arrived in ascending q, that is in descending
+// mirrored start, so hit h of the run [a, b] goes to a + b - h and every list leaves in ascending (t, q').
+__global__ __launch_bounds__(kThreads) void split_strands_kernel(const uint64_t* key, const uint32_t* val, uint32_t total, uint32_t* t_out,
+                                                                 uint32_t* val_out) {
+    const uint32_t h = blockIdx.x * kThreads + threadIdx.x;
+    if (h >= total) return;
+    const uint64_t kk = key[h];
+    t_out[h] = (uint32_t)kk;
+    uint32_t dst = h;
+    if ((kk >> 32) & 1u) dst = run_edge<-1>(key, total, h, kk) + (run_edge<1>(key, total, h, kk) - h);
+    val_out[dst] = val[h];
 }
 
 }  // namespace minim

@@ -1,7 +1,7 @@
 // sufarr_kernels.hip -- the suffix-array entries of include/pwalign.h (pwa_sa_*, pwa_seed_plan): device buffers, the prefix-doubling
 // rounds, the radix-sort passes, the chunked occurrence lists, and the seeding of read lists against a kept index; and the minimizer
 // entries (pwa_mm_*), which share the seeding's planner, scan, sort and split.  Kernels: sufarr.hip.h, seed.hip.h, minim.hip.h.
-// DESIGN.md §3.8, §3.25, §3.27.
+// DESIGN.md §3.8, §3.25, §3.27, §3.28.
 #include "../../include/pwalign.h"
 
 #include <hip/hip_runtime.h>
@@ -40,6 +40,7 @@ struct pwa_sa_index {
 struct pwa_mm_index {
     pwa_ctx* ctx = nullptr;
     uint32_t k = 0, w = 0, n_min = 0;
+    bool canonical = false;   // canonical hashes, and the strand of every entry in bit 31 of its position word
     Dev d_hash, d_pos;   // 2 n_min entries each, as sort_pairs takes them; half `half` holds the pairs in (hash, t) order
     int half = 0;
     float build_ms = 0.f;
@@ -344,8 +345,10 @@ struct SketchBuffers {
     std::vector<uint32_t> h_slot_off, h_min_off;
     mm::SketchArgs args{};
     uint32_t n_tiles = 0, total = 0;
+    bool canonical = false;   // the canonical kernels: pos then carries the strand in bit 31
 
-    void start(pwa::SaCtxView& v) {   // once per call: the fault word of all its launches
+    void start(pwa::SaCtxView& v, bool canon = false) {   // once per call: the fault word of all its launches
+        canonical = canon;
         UNIT_CHECK(fault.alloc(v.poison, 4));
         UNIT_CHECK(hipMemsetAsync(fault.p, 0, 4, v.stream));
     }
@@ -387,7 +390,8 @@ void sketch_count(pwa::SaCtxView& v, const uint8_t* bytes, const uint64_t* off, 
     b.total = 0;
     if (ev) UNIT_CHECK(hipEventRecord(ev[0], v.stream));
     if (ns) {
-        mm::sketch_kernel<false><<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), nullptr, nullptr, nullptr, 0, b.fault.as<uint32_t>());
+        const auto count = b.canonical ? mm::sketch_kernel<false, true> : mm::sketch_kernel<false, false>;
+        count<<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), nullptr, nullptr, nullptr, 0, b.fault.as<uint32_t>());
         UNIT_CHECK(hipGetLastError());
         pwa::scan_excl(v.stream, b.tile.as<uint32_t>(), (size_t)b.n_tiles + 1, b.part.as<uint32_t>());
     }
@@ -404,8 +408,9 @@ void sketch_write(pwa::SaCtxView& v, SketchBuffers& b, uint64_t* hash_out, uint3
         fit(v.poison, b.min_off, ((size_t)b.args.n_seqs + 1) * 4);
     }
     if (b.total) {
-        mm::sketch_kernel<true><<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), hash_out, pos_out,
-                                                                      offsets ? b.flat.as<uint32_t>() : nullptr, b.total, b.fault.as<uint32_t>());
+        const auto write = b.canonical ? mm::sketch_kernel<true, true> : mm::sketch_kernel<true, false>;
+        write<<<b.n_tiles, kThreads, 0, v.stream>>>(b.args, b.tile.as<uint32_t>(), hash_out, pos_out, offsets ? b.flat.as<uint32_t>() : nullptr, b.total,
+                                                    b.fault.as<uint32_t>());
         UNIT_CHECK(hipGetLastError());
     }
     if (offsets) {
@@ -421,24 +426,28 @@ float span_ms(hipEvent_t a, hipEvent_t b) {
     return ms;
 }
 
-// One range: reads g.k0 .. g.k1 sketched, their minimizers looked up, the hits sorted and appended to the index's kept anchors
+// One range: reads g.k0 .. g.k1 sketched, their minimizers looked up, the hits sorted and appended to the index's kept anchors.
+// On a canonical index (pwa_mm_seed_strands) a read has two lists, whose cuts are known only once the hits are gathered and sorted:
+// the total comes from the scan, the 2 nr + 1 offsets from the sorted keys, and the split turns the reverse lists' tied runs round.
 void mm_seed_range(pwa::SaCtxView& v, pwa_mm_index* ix, const SeedCall& c, const uint8_t* bytes, const pwa::Run& g, SketchBuffers& sb, SeedBuffers& b,
-                   pwa::Events<8>& ev, uint64_t* anc_off_out) {
+                   pwa::Events<8>& ev, uint64_t* anc_off_out, const char* who) {
     const uint32_t nr = (uint32_t)(g.k1 - g.k0);
+    const bool two = ix->canonical;
+    const size_t lists = (size_t)nr * (two ? 2 : 1), first = (size_t)g.k0 * (two ? 2 : 1);
     const size_t kept = ix->anc_t.size();
     sketch_count(v, bytes, c.off, g.k0, g.k1, ix->k, ix->w, sb, &ev.e[0]);
     ix->sketch_ms += span_ms(ev.e[0], ev.e[1]);
     ix->ranges += 1;
     const uint32_t nm = sb.total;
     ix->minimizers += nm;
-    for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept;
-    if (!nm) return;   // (every k-mer of the range holds a byte that is not ACGT)
+    for (size_t i = 0; i < lists; ++i) anc_off_out[first + i] = kept;
+    if (!nm) return;   // (every k-mer of the range holds a byte that is not ACGT, or is a reverse palindrome)
     fit(v.poison, sb.hash, (size_t)nm * 8);
     fit(v.poison, sb.pos, (size_t)nm * 4);
     fit(v.poison, b.lo, (size_t)nm * 4);
     fit(v.poison, b.cnt, ((size_t)nm + 1) * 4);
     fit(v.poison, b.slot_part, pwa::scan_part_words((size_t)nm + 1) * 4);
-    fit(v.poison, b.anc_off, ((size_t)nr + 1) * 4);
+    fit(v.poison, b.anc_off, (lists + 1) * 4);
     uint32_t* hit_off = b.cnt.as<uint32_t>();   // the counts, then, scanned, where each minimizer's hits start; the total last
     UNIT_CHECK(hipMemsetAsync(hit_off + nm, 0, 4, v.stream));
     UNIT_CHECK(hipEventRecord(ev.e[2], v.stream));
@@ -449,14 +458,19 @@ void mm_seed_range(pwa::SaCtxView& v, pwa_mm_index* ix, const SeedCall& c, const
     UNIT_CHECK(hipGetLastError());
     UNIT_CHECK(hipEventRecord(ev.e[4], v.stream));
     pwa::scan_excl(v.stream, hit_off, (size_t)nm + 1, b.slot_part.as<uint32_t>());
-    seed_read_offsets_kernel<<<blocks_for((size_t)nr + 1, kThreads), kThreads, 0, v.stream>>>(hit_off, sb.min_off.as<uint32_t>(), nr, b.anc_off.as<uint32_t>());
-    UNIT_CHECK(hipGetLastError());
-    b.h_anc_off.resize((size_t)nr + 1);
-    UNIT_CHECK(hipMemcpyAsync(b.h_anc_off.data(), b.anc_off.p, ((size_t)nr + 1) * 4, hipMemcpyDeviceToHost, v.stream));
+    b.h_anc_off.resize(lists + 1);
+    if (two) {
+        UNIT_CHECK(hipMemcpyAsync(&b.h_anc_off[lists], hit_off + nm, 4, hipMemcpyDeviceToHost, v.stream));
+    } else {
+        seed_read_offsets_kernel<<<blocks_for((size_t)nr + 1, kThreads), kThreads, 0, v.stream>>>(hit_off, sb.min_off.as<uint32_t>(), nr, b.anc_off.as<uint32_t>());
+        UNIT_CHECK(hipGetLastError());
+        UNIT_CHECK(hipMemcpyAsync(b.h_anc_off.data(), b.anc_off.p, ((size_t)nr + 1) * 4, hipMemcpyDeviceToHost, v.stream));
+    }
     UNIT_CHECK(hipStreamSynchronize(v.stream));
-    sb.check_fault("pwa_mm_seed");
-    const uint32_t total = b.h_anc_off[nr];
-    for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept + b.h_anc_off[i];
+    sb.check_fault(who);
+    const uint32_t total = b.h_anc_off[lists];
+    if (!two)
+        for (uint32_t i = 0; i < nr; ++i) anc_off_out[g.k0 + i] = kept + b.h_anc_off[i];
     ix->sketch_ms += span_ms(ev.e[2], ev.e[3]);
     ix->search_ms += span_ms(ev.e[3], ev.e[4]);
     ix->hits += total;
@@ -466,21 +480,37 @@ void mm_seed_range(pwa::SaCtxView& v, pwa_mm_index* ix, const SeedCall& c, const
     b.fit_sort(v.poison, total);
     SortBufs<uint64_t, uint32_t> s{{b.key.as<uint64_t>(), b.key.as<uint64_t>() + total}, {b.val.as<uint32_t>(), b.val.as<uint32_t>() + total}, 0};
     UNIT_CHECK(hipEventRecord(ev.e[5], v.stream));
-    mm::gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->positions(), ix->n_min, b.lo.as<uint32_t>(), hit_off, nm, total,
-                                                                             sb.min_off.as<uint32_t>(), nr, sb.pos.as<uint32_t>(), s.k[0], s.v[0],
-                                                                             sb.fault.as<uint32_t>());
+    if (two)
+        mm::gather_strands_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->positions(), ix->n_min, b.lo.as<uint32_t>(), hit_off, nm, total,
+                                                                                         sb.min_off.as<uint32_t>(), nr, sb.pos.as<uint32_t>(),
+                                                                                         sb.seq_off.as<uint64_t>(), ix->k, s.k[0], s.v[0],
+                                                                                         sb.fault.as<uint32_t>());
+    else
+        mm::gather_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(ix->positions(), ix->n_min, b.lo.as<uint32_t>(), hit_off, nm, total,
+                                                                                 sb.min_off.as<uint32_t>(), nr, sb.pos.as<uint32_t>(), s.k[0], s.v[0],
+                                                                                 sb.fault.as<uint32_t>());
     UNIT_CHECK(hipGetLastError());
     radix_sort(v.stream, s, total, b.sc);
     uint32_t* d_t = reinterpret_cast<uint32_t*>(s.k[s.cur ^ 1]);   // the sort's other key buffer is free now
-    seed_split_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], total, d_t);
+    const uint32_t* d_q = s.v[s.cur];
+    if (two) {   // ... and so is its other value buffer
+        mm::list_offsets_kernel<<<blocks_for(lists + 1, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], total, (uint32_t)lists, b.anc_off.as<uint32_t>());
+        mm::split_strands_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], s.v[s.cur], total, d_t, s.v[s.cur ^ 1]);
+        d_q = s.v[s.cur ^ 1];
+    } else {
+        seed_split_kernel<<<blocks_for(total, kThreads), kThreads, 0, v.stream>>>(s.k[s.cur], total, d_t);
+    }
     UNIT_CHECK(hipGetLastError());
     UNIT_CHECK(hipEventRecord(ev.e[6], v.stream));
     ix->anc_t.resize(kept + total);
     ix->anc_q.resize(kept + total);
     UNIT_CHECK(hipMemcpyAsync(ix->anc_t.data() + kept, d_t, (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
-    UNIT_CHECK(hipMemcpyAsync(ix->anc_q.data() + kept, s.v[s.cur], (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    UNIT_CHECK(hipMemcpyAsync(ix->anc_q.data() + kept, d_q, (size_t)total * 4, hipMemcpyDeviceToHost, v.stream));
+    if (two) UNIT_CHECK(hipMemcpyAsync(b.h_anc_off.data(), b.anc_off.p, (lists + 1) * 4, hipMemcpyDeviceToHost, v.stream));
     UNIT_CHECK(hipStreamSynchronize(v.stream));
-    sb.check_fault("pwa_mm_seed");
+    sb.check_fault(who);
+    if (two)
+        for (size_t i = 0; i < lists; ++i) anc_off_out[first + i] = kept + b.h_anc_off[i];
     ix->sort_ms += span_ms(ev.e[5], ev.e[6]);
 }
 
@@ -780,16 +810,17 @@ void pwa_sa_destroy(pwa_sa_index* ix) { delete ix; }
 
 // ---- minimizer sketches, the minimizer index, seeding against it
 
-int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index** out) {
+// pwa_mm_create and pwa_mm_create_canonical
+static int mm_create(const char* who, pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uint32_t w, bool canonical, pwa_mm_index** out) {
     if (!ctx || !out || (!text && n)) return PWA_E_INVALID;
     *out = nullptr;
     pwa::SaCtxView v = pwa::sa_ctx_view(ctx);
     if (!mm_params_ok(k, w)) {
-        *v.err = "pwa_mm_create: k is 1 .. 31 and w is 1 .. 128";
+        *v.err = std::string(who) + ": k is 1 .. 31 and w is 1 .. 128";
         return PWA_E_INVALID;
     }
     if (n >= (1ull << 31)) {
-        *v.err = "pwa_mm_create: a text of " + std::to_string(n) + " bytes; at most 2^31 - 1";
+        *v.err = std::string(who) + ": a text of " + std::to_string(n) + " bytes; at most 2^31 - 1";
         return PWA_E_CAPACITY;
     }
     pwa_mm_index* ix = new (std::nothrow) pwa_mm_index();
@@ -797,6 +828,7 @@ int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uin
     ix->ctx = ctx;
     ix->k = k;
     ix->w = w;
+    ix->canonical = canonical;
     const int rc = pwa::guarded(v, [&] {
         if (!kmers_of(n, k)) return;   // n < k: a valid, empty index
         UNIT_CHECK(hipSetDevice(v.device));
@@ -805,7 +837,7 @@ int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uin
         SketchBuffers b;
         pwa::Events<4> ev;
         UNIT_CHECK(ev.create());
-        b.start(v);
+        b.start(v, canonical);
         sketch_count(v, text, off, 0, 1, k, w, b, &ev.e[0]);
         ix->n_min = b.total;
         ix->build_ms = span_ms(ev.e[0], ev.e[1]);
@@ -819,11 +851,11 @@ int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uin
         ix->half = pwa::sort_pairs(v.stream, ix->d_hash.as<uint64_t>(), ix->d_pos.as<uint32_t>(), b.total, sc);   // stable: (hash, t) order
         UNIT_CHECK(hipEventRecord(ev.e[3], v.stream));
         UNIT_CHECK(hipStreamSynchronize(v.stream));
-        b.check_fault("pwa_mm_create");
+        b.check_fault(who);
         ix->build_ms += span_ms(ev.e[2], ev.e[3]);
         if (v.debug)
-            std::fprintf(stderr, "[pwa] mm build: n=%llu k=%u w=%u: %u minimizers, device %.3f ms, call %.3f ms\n", (unsigned long long)n, k, w, ix->n_min,
-                         ix->build_ms, ms_since(t0));
+            std::fprintf(stderr, "[pwa] mm build%s: n=%llu k=%u w=%u: %u minimizers, device %.3f ms, call %.3f ms\n", canonical ? " (canonical)" : "",
+                         (unsigned long long)n, k, w, ix->n_min, ix->build_ms, ms_since(t0));
     });
     if (rc == PWA_OK)
         *out = ix;
@@ -832,22 +864,52 @@ int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uin
     return rc;
 }
 
+int pwa_mm_create(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index** out) {
+    return mm_create("pwa_mm_create", ctx, text, n, k, w, false, out);
+}
+
+int pwa_mm_create_canonical(pwa_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index** out) {
+    return mm_create("pwa_mm_create_canonical", ctx, text, n, k, w, true, out);
+}
+
 void pwa_mm_destroy(pwa_mm_index* ix) { delete ix; }
 
-int pwa_mm_fetch(pwa_mm_index* ix, uint64_t* hash_out, uint32_t* pos_out, uint64_t cap) {
+// Position words as the canonical kernels leave them, taken apart on the host: bit 31 into strand_out (where wanted), the rest stays
+static void split_strand_words(uint32_t* pos, uint8_t* strand_out, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
+        if (strand_out) strand_out[i] = (uint8_t)(pos[i] >> 31);
+        pos[i] &= ~mm::kStrandBit;
+    }
+}
+
+// pwa_mm_fetch and, with want_strand, pwa_mm_fetch_canonical
+static int mm_fetch(const char* who, pwa_mm_index* ix, uint64_t* hash_out, uint32_t* pos_out, uint8_t* strand_out, bool want_strand, uint64_t cap) {
     if (!ix) return PWA_E_INVALID;
     pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
+    if (want_strand && !ix->canonical) {
+        *v.err = std::string(who) + ": the index is not canonical (pwa_mm_create_canonical builds one)";
+        return PWA_E_INVALID;
+    }
     if (cap < ix->n_min) {
-        *v.err = "pwa_mm_fetch: " + std::to_string(ix->n_min) + " minimizers, capacity " + std::to_string(cap);
+        *v.err = std::string(who) + ": " + std::to_string(ix->n_min) + " minimizers, capacity " + std::to_string(cap);
         return PWA_E_CAPACITY;
     }
-    if (ix->n_min && (!hash_out || !pos_out)) return PWA_E_INVALID;
+    if (ix->n_min && (!hash_out || !pos_out || (want_strand && !strand_out))) return PWA_E_INVALID;
     return pwa::guarded(v, [&] {
         if (!ix->n_min) return;
         UNIT_CHECK(hipMemcpyAsync(hash_out, ix->hashes(), (size_t)ix->n_min * 8, hipMemcpyDeviceToHost, v.stream));
         UNIT_CHECK(hipMemcpyAsync(pos_out, ix->positions(), (size_t)ix->n_min * 4, hipMemcpyDeviceToHost, v.stream));
         UNIT_CHECK(hipStreamSynchronize(v.stream));
+        if (ix->canonical) split_strand_words(pos_out, strand_out, ix->n_min);
     });
+}
+
+int pwa_mm_fetch(pwa_mm_index* ix, uint64_t* hash_out, uint32_t* pos_out, uint64_t cap) {
+    return mm_fetch("pwa_mm_fetch", ix, hash_out, pos_out, nullptr, false, cap);
+}
+
+int pwa_mm_fetch_canonical(pwa_mm_index* ix, uint64_t* hash_out, uint32_t* pos_out, uint8_t* strand_out, uint64_t cap) {
+    return mm_fetch("pwa_mm_fetch_canonical", ix, hash_out, pos_out, strand_out, true, cap);
 }
 
 int pwa_mm_last_stats(const pwa_mm_index* ix, uint64_t* n_min, float* build_ms) {
@@ -857,17 +919,18 @@ int pwa_mm_last_stats(const pwa_mm_index* ix, uint64_t* n_min, float* build_ms) 
     return PWA_OK;
 }
 
-int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k, uint32_t w, uint64_t* min_off_out,
-                  uint32_t* pos_out, uint64_t* hash_out, uint64_t cap, uint64_t* needed) {
-    if (!ctx || !min_off_out || (n_seqs && !seq_off) || (cap && (!pos_out || !hash_out))) return PWA_E_INVALID;
+// pwa_mm_sketch and, with canonical, pwa_mm_sketch_canonical (strand_out beside pos_out)
+static int mm_sketch(const std::string& who, pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k, uint32_t w,
+                     bool canonical, uint64_t* min_off_out, uint32_t* pos_out, uint64_t* hash_out, uint8_t* strand_out, uint64_t cap, uint64_t* needed) {
+    if (!ctx || !min_off_out || (n_seqs && !seq_off) || (cap && (!pos_out || !hash_out || (canonical && !strand_out)))) return PWA_E_INVALID;
     pwa::SaCtxView v = pwa::sa_ctx_view(ctx);
     if (!seq_bytes && n_seqs && seq_off[n_seqs] != seq_off[0]) {
-        *v.err = "pwa_mm_sketch: a required pointer is null";
+        *v.err = who + ": a required pointer is null";
         return PWA_E_INVALID;
     }
     std::string what;
     if (const int rc = sketch_validate(seq_off, n_seqs, k, w, what)) {
-        *v.err = "pwa_mm_sketch: " + what;
+        *v.err = who + ": " + what;
         return rc;
     }
     uint64_t kept = 0;
@@ -883,7 +946,7 @@ int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_of
             if (!g.weight) continue;
             if (!started) {
                 UNIT_CHECK(hipSetDevice(v.device));
-                b.start(v);
+                b.start(v, canonical);
                 started = true;
             }
             for (; done < g.k0; ++done) min_off_out[done] = kept;
@@ -899,7 +962,8 @@ int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_of
                 UNIT_CHECK(hipMemcpyAsync(pos_out + kept, b.pos.p, (size_t)b.total * 4, hipMemcpyDeviceToHost, v.stream));
             }
             UNIT_CHECK(hipStreamSynchronize(v.stream));
-            b.check_fault("pwa_mm_sketch");
+            b.check_fault(who.c_str());
+            if (canonical && b.total && kept + b.total <= cap) split_strand_words(pos_out + kept, strand_out + kept, b.total);
             for (uint32_t i = 0; i < nr; ++i) min_off_out[g.k0 + i] = kept + b.h_min_off[i];
             kept += b.total;
             done = g.k1;
@@ -909,10 +973,20 @@ int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_of
     if (rc != PWA_OK) return rc;
     if (needed) *needed = kept;
     if (kept > cap) {
-        *v.err = "pwa_mm_sketch: " + std::to_string(kept) + " minimizers, capacity " + std::to_string(cap);
+        *v.err = who + ": " + std::to_string(kept) + " minimizers, capacity " + std::to_string(cap);
         return PWA_E_CAPACITY;
     }
     return PWA_OK;
+}
+
+int pwa_mm_sketch(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k, uint32_t w, uint64_t* min_off_out,
+                  uint32_t* pos_out, uint64_t* hash_out, uint64_t cap, uint64_t* needed) {
+    return mm_sketch("pwa_mm_sketch", ctx, seq_bytes, seq_off, n_seqs, k, w, false, min_off_out, pos_out, hash_out, nullptr, cap, needed);
+}
+
+int pwa_mm_sketch_canonical(pwa_ctx* ctx, const uint8_t* seq_bytes, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k, uint32_t w,
+                            uint64_t* min_off_out, uint32_t* pos_out, uint64_t* hash_out, uint8_t* strand_out, uint64_t cap, uint64_t* needed) {
+    return mm_sketch("pwa_mm_sketch_canonical", ctx, seq_bytes, seq_off, n_seqs, k, w, true, min_off_out, pos_out, hash_out, strand_out, cap, needed);
 }
 
 int pwa_mm_plan(uint64_t n_min, const uint64_t* read_off, uint32_t n_reads, uint32_t k, uint32_t max_occ, uint64_t budget_hits, uint32_t* bad_read,
@@ -934,19 +1008,29 @@ int pwa_mm_plan(uint64_t n_min, const uint64_t* read_off, uint32_t n_reads, uint
     return rc;
 }
 
-int pwa_mm_seed(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads, uint32_t max_occ, uint64_t* anc_off_out) {
+// pwa_mm_seed (a plain index, one list per read) and pwa_mm_seed_strands (a canonical one, two)
+static int mm_seed(const std::string& who, bool strands, pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads,
+                   uint32_t max_occ, uint64_t* anc_off_out) {
     if (!ix) return PWA_E_INVALID;
     pwa::SaCtxView v = pwa::sa_ctx_view(ix->ctx);
     const SeedCall c = mm_call(ix->n_min, read_off, n_reads, ix->k, max_occ);
     if (!anc_off_out || (!read_bytes && n_reads && read_off && read_off[n_reads] != read_off[0])) {
-        *v.err = "pwa_mm_seed: a required pointer is null";
+        *v.err = who + ": a required pointer is null";
         return PWA_E_INVALID;
+    }
+    if (strands != ix->canonical) {
+        *v.err = who + (strands ? ": the index is not canonical; pwa_mm_seed seeds a plain index" : ": the index is canonical; pwa_mm_seed_strands seeds it");
+        return PWA_E_INVALID;
+    }
+    if (strands && n_reads > 0x7FFFFFFFu) {
+        *v.err = who + ": " + std::to_string(n_reads) + " reads; at most 2^31 - 1, two lists each";
+        return PWA_E_CAPACITY;
     }
     uint32_t bad = kNoRead;
     uint64_t slots = 0;
     std::string what;
     if (const int rc = seed_validate(c, bad, slots, what)) {
-        *v.err = "pwa_mm_seed (the text's k-mers being the index's minimizers): " + what;
+        *v.err = who + " (the text's k-mers being the index's minimizers): " + what;
         return rc;
     }
     ix->seeded = false;
@@ -956,8 +1040,9 @@ int pwa_mm_seed(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* rea
     ix->slots = slots;
     ix->minimizers = ix->hits = ix->ranges = 0;
     const auto t0 = std::chrono::steady_clock::now();
+    const size_t per = strands ? 2 : 1;   // lists per read
     const int rc = pwa::guarded(v, [&] {
-        std::fill_n(anc_off_out, (size_t)n_reads + 1, 0ull);
+        std::fill_n(anc_off_out, per * n_reads + 1, 0ull);
         const std::vector<pwa::Run> ranges = seed_ranges(c, v.occ_chunk_hits);
         if (ranges.empty()) return;   // no read, no k-mer, or an empty index: nothing for the device to do
         UNIT_CHECK(hipSetDevice(v.device));
@@ -965,21 +1050,30 @@ int pwa_mm_seed(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* rea
         SeedBuffers b;
         pwa::Events<8> ev;
         UNIT_CHECK(ev.create());
-        sb.start(v);
-        uint64_t done = 0;   // reads whose offsets are written
+        sb.start(v, strands);
+        size_t done = 0;   // lists whose offsets are written
         for (const pwa::Run& g : ranges) {
-            for (; done < g.k0; ++done) anc_off_out[done] = ix->anc_t.size();   // the reads of a range without a k-mer
-            mm_seed_range(v, ix, c, read_bytes, g, sb, b, ev, anc_off_out);
-            done = g.k1;
+            for (; done < per * g.k0; ++done) anc_off_out[done] = ix->anc_t.size();   // the reads of a range without a k-mer
+            mm_seed_range(v, ix, c, read_bytes, g, sb, b, ev, anc_off_out, who.c_str());
+            done = per * g.k1;
         }
-        for (; done <= n_reads; ++done) anc_off_out[done] = ix->anc_t.size();
+        for (; done <= per * n_reads; ++done) anc_off_out[done] = ix->anc_t.size();
         if (v.debug)
-            std::fprintf(stderr, "[pwa] mm seed: %u reads, k=%u w=%u max_occ=%u: %llu slots, %llu minimizers, %llu hits, %llu ranges, sketch %.3f ms, search %.3f ms, sort %.3f ms, call %.3f ms\n",
-                         n_reads, ix->k, ix->w, max_occ, (unsigned long long)ix->slots, (unsigned long long)ix->minimizers, (unsigned long long)ix->hits,
+            std::fprintf(stderr, "[pwa] mm seed%s: %u reads, k=%u w=%u max_occ=%u: %llu slots, %llu minimizers, %llu hits, %llu ranges, sketch %.3f ms, search %.3f ms, sort %.3f ms, call %.3f ms\n",
+                         strands ? " (strands)" : "", n_reads, ix->k, ix->w, max_occ, (unsigned long long)ix->slots, (unsigned long long)ix->minimizers, (unsigned long long)ix->hits,
                          (unsigned long long)ix->ranges, ix->sketch_ms, ix->search_ms, ix->sort_ms, ms_since(t0));
     });
     ix->seeded = rc == PWA_OK;
     return rc;
+}
+
+int pwa_mm_seed(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads, uint32_t max_occ, uint64_t* anc_off_out) {
+    return mm_seed("pwa_mm_seed", false, ix, read_bytes, read_off, n_reads, max_occ, anc_off_out);
+}
+
+int pwa_mm_seed_strands(pwa_mm_index* ix, const uint8_t* read_bytes, const uint64_t* read_off, uint32_t n_reads, uint32_t max_occ,
+                        uint64_t* anc_off_out) {
+    return mm_seed("pwa_mm_seed_strands", true, ix, read_bytes, read_off, n_reads, max_occ, anc_off_out);
 }
 
 int pwa_mm_seed_fetch(const pwa_mm_index* ix, uint32_t* anc_t, uint32_t* anc_q, uint64_t cap) {

@@ -869,6 +869,47 @@ int pwa_mm_seed_fetch(const pwa_mm_index *ix, uint32_t *anc_t, uint32_t *anc_q, 
 int pwa_mm_seed_last_stats(const pwa_mm_index *ix, float *sketch_ms, float *search_ms, float *sort_ms, uint64_t *slots, uint64_t *minimizers,
                            uint64_t *hits, uint64_t *ranges);
 
+/* ---- Canonical minimizers: one sketch, both strands
+ *
+ * Codes, mix, the windows, the leftmost tie, the invalid bytes and the limits on k and w are those of the minimizer block above.
+ * Canonical value and strand.  A k-mer at start p with codes c_0 .. c_(k-1) has the forward value f(p) = sum of c_i * 4^(k - 1 - i)
+ * and the reverse-complement value r(p) = sum of (3 - c_i) * 4^i, the value of the k-mer read off the other strand.  If f < r the
+ * strand bit s(p) = 0 and h(p) = mix(f); if r < f then s(p) = 1 and h(p) = mix(r); if f = r (a reverse palindrome, possible only for
+ * even k) the k-mer is invalid: +infinity, never selected, like a k-mer over 'N'.  A k-mer and its reverse complement so have the
+ * same hash and opposite strand bits.  Window selection runs over h exactly as above.
+ * Sketch.  The selected starts in ascending order, each with its hash and its strand bit.
+ * Index.  The text's canonical sketch as (hash, t, strand) in ascending (hash, t).
+ * Seeding.  Read r of L bytes is sketched once, as given.  A sketch entry (q, h, s_q) hits every index entry (h, t, s_t); an entry
+ * with more than max_occ hits contributes none, the count being over both strands together.  A hit with s_q = s_t goes to list 2r
+ * as the forward anchor (t, q): text[t .. t + k) == read[q .. q + k).  A hit with s_q != s_t goes to list 2r + 1 as the reverse
+ * anchor (t, L - k - q): text[t .. t + k) == revcomp(read)[q' .. q' + k) with q' = L - k - q.  Each list is in ascending (t, q), the
+ * order pwa_chain_anchors requires, in the coordinates of the sequence that list would be aligned as.  Lists 2r and 2r + 1 are
+ * consecutive in the kept anchors: list i is entries anc_off_out[i] .. anc_off_out[i + 1]), i = 0 .. 2 n_reads - 1.
+ * Not promised: the sketch of revcomp(x) is not always the mirror of the sketch of x (the leftmost tie is not symmetric), so the
+ * two lists of a read are not always what two plain seedings of the read and of its reverse complement would give.
+ * The type stays pwa_mm_index; an index is plain (pwa_mm_create) or canonical (pwa_mm_create_canonical) for its lifetime, and each
+ * wrong pairing of a call and an index kind is PWA_E_INVALID with a message that names the other call.  Validation order and codes
+ * are those of the siblings above.
+ *   pwa_mm_create_canonical  pwa_mm_create with canonical hashes; the strand bits are kept with the positions.
+ *   pwa_mm_fetch_canonical   pwa_mm_fetch plus strand_out[n_min] (0 or 1).  On a plain index PWA_E_INVALID.  pwa_mm_fetch on a
+ *                            canonical index gives hash and t alone.
+ *   pwa_mm_sketch_canonical  pwa_mm_sketch plus strand_out, one byte (0 or 1) beside every pos_out entry.
+ *   pwa_mm_seed_strands      the seeding above: writes anc_off_out[2 n_reads + 1] and keeps the anchors as pwa_mm_seed does;
+ *                            pwa_mm_seed_fetch and pwa_mm_seed_last_stats serve it unchanged, minimizers counting each read
+ *                            minimizer once.  On a plain index PWA_E_INVALID, as pwa_mm_seed is on a canonical one.  n_reads is at
+ *                            most 2^31 - 1 so that list numbers fit 32 bits; above that PWA_E_CAPACITY.
+ *   pwa_mm_plan              is the plan of pwa_mm_seed_strands as it stands: a read minimizer still has at most
+ *                            min(max_occ, n_min) hits, now summed over the two lists of its read, so the worst case per read, the
+ *                            ranges and the codes are the same.
+ * On the device the strand bit travels as bit 31 of the position word (positions are below 2^31); nothing per text position is kept. */
+int pwa_mm_create_canonical(pwa_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t w, pwa_mm_index **out);
+int pwa_mm_fetch_canonical(pwa_mm_index *ix, uint64_t *hash_out, uint32_t *pos_out, uint8_t *strand_out, uint64_t cap);
+int pwa_mm_sketch_canonical(pwa_ctx *ctx, const uint8_t *seq_bytes, const uint64_t *seq_off /* n_seqs + 1 */, uint32_t n_seqs, uint32_t k,
+                            uint32_t w, uint64_t *min_off_out /* n_seqs + 1 */, uint32_t *pos_out, uint64_t *hash_out, uint8_t *strand_out,
+                            uint64_t cap, uint64_t *needed /* or NULL */);
+int pwa_mm_seed_strands(pwa_mm_index *ix, const uint8_t *read_bytes, const uint64_t *read_off /* n_reads + 1 */, uint32_t n_reads,
+                        uint32_t max_occ, uint64_t *anc_off_out /* 2 n_reads + 1 */);
+
 /* ---- k-edit approximate pattern search (Sellers' DP on bit-parallel columns, Myers 1999)
  *
  * For a pattern p of m >= 1 bytes and a text t of n bytes:  D[0][j] = 0, D[i][0] = i,
