@@ -49,8 +49,22 @@ def index(text, k, w, **mistake):
     return sorted((h, t, s) for t, h, s in sketch(text, k, w, **mistake))
 
 
+def swap_pairs_in_runs(rv):
+    """the mistake of turning a run of equal t round by swapping its neighbouring pairs: right for runs of one and two hits, wrong
+    from three on.  rv: one reverse list's (t, q', k, q) as they arrive, in ascending (t, q)"""
+    out, i = list(rv), 0
+    while i < len(out):
+        j = i
+        while j < len(out) and out[j][0] == out[i][0]:
+            j += 1
+        for p in range(i, j - 1, 2):
+            out[p], out[p + 1] = out[p + 1], out[p]
+        i = j
+    return out
+
+
 def seed(text, reads, k, w, max_occ=64, entries=None, strand_from_read=False, no_mirror=False, reverse_by_q=False, occ_per_strand=False,
-         palindrome_valid=False):
+         palindrome_valid=False, reverse_pairs_only=False, probe_at_end_dropped=False):
     """-> (lists, read minimizers looked up): lists[2 r] = read r's forward anchors (t, q, k), lists[2 r + 1] its reverse anchors
     (t, L - k - q, k), each in ascending (t, q); none looked up in an empty index, whose calls do no device work"""
     entries = index(text, k, w, palindrome_valid=palindrome_valid) if entries is None else entries
@@ -63,6 +77,8 @@ def seed(text, reads, k, w, max_occ=64, entries=None, strand_from_read=False, no
         for q, h, sq in sketch(r, k, w, palindrome_valid=palindrome_valid):
             looked += 1 if entries else 0
             hits = by_hash.get(h, [])
+            if probe_at_end_dropped and hits and len(hits) == max_occ and h == entries[-1][0]:
+                continue    # the probe at lo + max_occ read one past the index's last entry, and taken for one more of the same hash
             for t, st in hits:
                 flip = sq if strand_from_read else sq ^ st
                 if occ_per_strand:
@@ -75,7 +91,11 @@ def seed(text, reads, k, w, max_occ=64, entries=None, strand_from_read=False, no
                 else:
                     fw.append((t, q, k, q))
         out.append(sorted(a[:3] for a in fw))
-        out.append([a[:3] for a in sorted(rv, key=lambda a: (a[0], a[3]))] if reverse_by_q else sorted(a[:3] for a in rv))
+        if reverse_by_q or reverse_pairs_only:
+            arrived = sorted(rv, key=lambda a: (a[0], a[3]))
+            out.append([a[:3] for a in (swap_pairs_in_runs(arrived) if reverse_pairs_only else arrived)])
+        else:
+            out.append(sorted(a[:3] for a in rv))
     return out, looked
 
 

@@ -95,9 +95,10 @@ def index(text, k, w):
     return sorted((h, t) for t, h in sketch(text, k, w))
 
 
-def seed(text, reads, k, w, max_occ=64, entries=None):
+def seed(text, reads, k, w, max_occ=64, entries=None, probe_at_end_dropped=False):
     """per read its anchors (t, q, k) in ascending (t, q); -> (anchors, read minimizers looked up: none in an empty index, whose
-    calls do no device work)"""
+    calls do no device work).  probe_at_end_dropped is a deliberate mistake: the probe at lo + max_occ read one past the index's last
+    entry and taken for one more of the same hash, so a minimizer whose exactly max_occ occurrences end the index is dropped"""
     entries = index(text, k, w) if entries is None else entries
     by_hash = {}
     for h, t in entries:
@@ -108,6 +109,8 @@ def seed(text, reads, k, w, max_occ=64, entries=None):
         for q, h in sketch(r, k, w):
             looked += 1 if entries else 0
             ts = by_hash.get(h, [])
+            if probe_at_end_dropped and ts and len(ts) == max_occ and h == entries[-1][0]:
+                continue
             if len(ts) <= max_occ:
                 anchors += [(t, q, k) for t in ts]
         out.append(sorted(anchors))

@@ -1,7 +1,8 @@
 """canonical_oracle.py held to the definitions it restates, without a GPU: anchors are byte-for-byte matches on their strand, the hash
 ignores direction, reverse palindromes are invalid, a shared stretch on either strand shares a selected k-mer, each deliberate mistake
-changes a built case, the planted reads of test_gpu_map_reads.py chain to their strand and place from one sketch each, and the
-both-strand text of test_gpu_map_secondary.py gives its two chains."""
+changes a built case (those of the stages behind the sketch change a case of seed_stage_cases.py), the planted reads of
+test_gpu_map_reads.py chain to their strand and place from one sketch each, and the both-strand text of test_gpu_map_secondary.py
+gives its two chains."""
 import random
 
 import canonical_oracle as KO
@@ -127,6 +128,66 @@ def test_each_mistake_changes_a_built_case():
     assert sizes[4] == [0, 0] and sizes[5] == sizes[6] == [3, 2]
     assert [len(lst) for lst in KO.seed(rep, [b"N" + x + b"N"], k, w, max_occ=4, occ_per_strand=True)[0]] == [3, 2]
     assert [len(lst) for lst in KO.seed(rep, [b"N" + x + b"N"], k, w, max_occ=2, occ_per_strand=True)[0]] == [0, 2] and sizes[2] == [0, 0]
+
+
+def several_t_per_q(seed=25):
+    """order_trap()'s x at three places forward and two reverse, each between N: a minimizer of five hits over both strands"""
+    rng = random.Random(seed)
+    x = order_trap()[2]
+    fill = lambda m: bytes(rng.choice(b"ACGT") for _ in range(m))
+    return b"N".join([fill(50), x, fill(60), x, fill(70), CO.revcomp(x), fill(40), x, fill(30), CO.revcomp(x), fill(20)])
+
+
+def test_the_stage_cases_catch_what_the_older_cases_let_through():
+    """seed_stage_cases.py: each mistake of the stages behind the sketch changes a built case there -- and the two new ones change
+    nothing in the cases test_gpu_canonical.py had before, which is why they are there"""
+    import seed_stage_cases as SC
+    text, read, x, w, t, _ = order_trap()
+    k = len(x)
+    older = [(text, [read, CO.revcomp(read), x], 64), (several_t_per_q(), [read, b"N" + x + b"N"], 64)]
+    older += [(several_t_per_q(), [b"N" + x + b"N"], m) for m in (4, 5, 6)]
+    assert max(e - s for tx, reads, m in older for _, _, s, e in SC.runs_of(KO.seed(tx, reads, k, w, m)[0])) == 2   # no run beyond two hits
+    for tx, reads, m in older:
+        want = KO.seed(tx, reads, k, w, m)
+        assert KO.seed(tx, reads, k, w, m, reverse_pairs_only=True) == want
+        assert KO.seed(tx, reads, k, w, m, probe_at_end_dropped=True) == want
+    # runs turned round by swapping pairs: right up to two hits, wrong from three on, and chain()'s order rule refuses the list
+    for variant, runs in [("reverse", None), ("swapped", [1, 2, 3, 4, 5]), ("both", [1, 2, 3, 4, 5, 6])]:
+        case = SC.tied_runs(variant, runs)
+        want, looked = KO.seed(case["text"], case["reads"], SC.K, 8)
+        assert want == case["lists"] and looked == sum(case["runs"]) and CO.validate(want) == (0, None)
+        wrong, _ = KO.seed(case["text"], case["reads"], SC.K, 8, reverse_pairs_only=True)
+        assert [i for i in range(len(want)) if wrong[i] != want[i]] == [2 * i + 1 for i, r in enumerate(case["runs"]) if r >= 3]
+        assert all(sorted(a) == b for a, b in zip(wrong, want)) and CO.validate(wrong)[0] != 0
+    # the four pairings of the strand bits, and the mirror: each mistake changes the variant that has them all
+    case = SC.tied_runs("both", [1, 2, 3, 4, 5, 6])
+    assert SC.four_pairings(case) == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    assert SC.four_pairings(SC.tied_runs("reverse", [1, 2])) | SC.four_pairings(SC.tied_runs("swapped", [1, 2])) == {(0, 1), (1, 0)}
+    want, _ = KO.seed(case["text"], case["reads"], SC.K, 8)
+    for mistake in ("no_mirror", "strand_from_read"):
+        wrong, _ = KO.seed(case["text"], case["reads"], SC.K, 8, **{mistake: True})
+        assert wrong != want and (mistake == "strand_from_read" or wrong[0::2] == want[0::2])
+    sym = SC.tied_runs("reverse", [1, 2, 3])         # (where a read is nothing but its units the mirror maps its starts onto themselves)
+    assert KO.seed(sym["text"], sym["reads"], SC.K, 8, no_mirror=True) == KO.seed(sym["text"], sym["reads"], SC.K, 8)
+    # ... and the reads whose one reverse hit is their first k-mer (q' = L - k) and their last (q' = 0)
+    shapes = SC.list_shapes(True, 127)
+    reads, kinds = shapes["shapes"]["reverse_only"]
+    ends = SC.end_anchors(shapes, reads, kinds)
+    want, _ = KO.seed(shapes["text"], reads, shapes["k"], shapes["w"])
+    assert [bool(lst) for lst in want] == SC.filled(kinds, True) and all(want[i] == a for i, a in ends.items())
+    assert {a[0][1] for a in ends.values() if a} == {0, 31}                    # q' = 0, and q' = L - k of L = 15 + 1 + 30
+    for mistake in ("no_mirror", "strand_from_read"):
+        wrong, _ = KO.seed(shapes["text"], reads, shapes["k"], shapes["w"], **{mistake: True})
+        assert all(wrong[i] != want[i] for i, a in ends.items() if a), mistake
+    # the probe one past the index's last entry: a minimizer whose exactly max_occ occurrences end the index
+    p = SC.probe_cases(True)
+    for m in p["max_occs"]:
+        want, _ = KO.seed(p["text"], p["reads"], p["k"], 1, m, entries=p["entries"])
+        assert [len(want[2 * i]) + len(want[2 * i + 1]) for i in range(len(p["reads"]))] == p["hits"][m], m
+        wrong, _ = KO.seed(p["text"], p["reads"], p["k"], 1, m, entries=p["entries"], probe_at_end_dropped=True)
+        assert (wrong != want) == (m == p["c"]), m
+    top = p["names"].index("top")
+    assert want[2 * top] and want[2 * top + 1]                                 # counted over both strands
 
 
 def test_the_two_lists_are_not_two_plain_seedings():

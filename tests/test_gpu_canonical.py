@@ -42,9 +42,10 @@ def check_entries(ix, want):
     assert list(zip(h.tolist(), p.tolist(), s.tolist())) == want and ix.stats["minimizers"] == len(want)
 
 
-def check_seed(ctx, ix, reads, max_occ=64, entries=None):
-    """ix.seed_strands against the oracle, whole, with the call's stats, the byte-for-byte meaning of every anchor and chain()'s
-    verdict on every list; -> the oracle's lists in the call's order (2 r, 2 r + 1)"""
+def check_seed(ctx, ix, reads, max_occ=64, entries=None, budget=0):
+    """ix.seed_strands against the oracle, whole, with the call's stats (budget: the context's PWA_OCC_CHUNK_HITS, where it has
+    one), the byte-for-byte meaning of every anchor and chain()'s verdict on every list; -> the oracle's lists in the call's order
+    (2 r, 2 r + 1)"""
     want, looked = KO.seed(ix.text, reads, ix.k, ix.w, max_occ, entries=entries)
     got = ix.seed_strands(reads, max_occ)
     assert got == KO.by_strand(want), (ix.k, ix.w, max_occ)
@@ -58,7 +59,7 @@ def check_seed(ctx, ix, reads, max_occ=64, entries=None):
     assert set(st) == {"sketch_ms", "search_ms", "sort_ms", "slots", "minimizers", "hits", "ranges"}
     assert st["hits"] == sum(len(a) for a in want) and st["minimizers"] == looked
     assert st["slots"] == sum(max(len(r) - ix.k + 1, 0) for r in reads)
-    assert st["ranges"] == len(MO.ranges(ix.stats["minimizers"], [len(r) for r in reads], ix.k, max_occ))
+    assert st["ranges"] == len(MO.ranges(ix.stats["minimizers"], [len(r) for r in reads], ix.k, max_occ, budget))
     return want
 
 

@@ -138,8 +138,8 @@ def test_sketch_validation_and_capacity(ctx, pkg):
     assert L.pwa_mm_create(ctx._h, None, 20, 5, 5, C.byref(ix)) == INVALID and L.pwa_mm_create(ctx._h, seq, 20, 5, 5, None) == INVALID
 
 
-def check_seed(ix, reads, max_occ=64, entries=None):
-    """ix.seed against the oracle, whole, with the call's stats; -> the anchors"""
+def check_seed(ix, reads, max_occ=64, entries=None, budget=0):
+    """ix.seed against the oracle, whole, with the call's stats (budget: the context's PWA_OCC_CHUNK_HITS, where it has one); -> the anchors"""
     want, looked = MO.seed(ix.text, reads, ix.k, ix.w, max_occ, entries=entries)
     got = ix.seed(reads, max_occ)
     assert got == want, (ix.k, ix.w, max_occ)
@@ -148,7 +148,7 @@ def check_seed(ix, reads, max_occ=64, entries=None):
     assert set(st) == {"sketch_ms", "search_ms", "sort_ms", "slots", "minimizers", "hits", "ranges"}
     assert st["hits"] == sum(len(a) for a in want) and st["minimizers"] == looked
     assert st["slots"] == sum(max(len(r) - ix.k + 1, 0) for r in reads)
-    assert st["ranges"] == len(MO.ranges(ix.stats["minimizers"], [len(r) for r in reads], ix.k, max_occ))
+    assert st["ranges"] == len(MO.ranges(ix.stats["minimizers"], [len(r) for r in reads], ix.k, max_occ, budget))
     return got
 
 
@@ -174,16 +174,20 @@ def test_index_entries_and_small_texts(ctx, pkg):
         assert ix.stats["minimizers"] == 0 and check_seed(ix, [b"ACGTACGT"]) == [[]]
 
 
-def test_max_occ_at_and_around_a_minimizers_count(ctx):
+def max_occ_inputs():
+    """the text, its entries and the reads of test_max_occ_at_and_around_a_minimizers_count"""
     text, _ = repeat_text()
-    entries = MO.index(text, K, W)
+    rng = random.Random(7)
+    return text, MO.index(text, K, W), [text[0:400], text[100:900], text[29000:], CO.mutate(rng, text[0:400], 0.03), text[7300:7900]]
+
+
+def test_max_occ_at_and_around_a_minimizers_count(ctx):
+    text, entries, reads = max_occ_inputs()
     count = {}
     for h, _ in entries:
         count[h] = count.get(h, 0) + 1
     unit = sorted(count[h] for _, h in MO.sketch(text[0:400], K, W) if h in count)
     assert unit.count(5) > 20 and unit[-1] >= 5
-    rng = random.Random(7)
-    reads = [text[0:400], text[100:900], text[29000:], CO.mutate(rng, text[0:400], 0.03), text[7300:7900]]
     with ctx.index(text, minimizers=(K, W)) as ix:
         sizes = {m: len(check_seed(ix, reads, m, entries)[0]) for m in (1, 4, 5, 6, 64, 0xffffffff)}
     assert sizes[4] < sizes[5] <= sizes[6] <= sizes[64] == sizes[0xffffffff] and sizes[5] - sizes[4] == 5 * unit.count(5)

@@ -85,6 +85,28 @@ def test_each_mistake_changes_a_built_case():
     assert differ >= 15
 
 
+def test_the_probe_case_catches_what_the_max_occ_test_lets_through():
+    """seed_stage_cases.probe_cases: the lookup's probe at lo + max_occ, read one past the index's last entry, changes the built case
+    at max_occ = c alone -- and nothing in the inputs of test_gpu_minimizer.py's max_occ test, which never looks up the index's top"""
+    import seed_stage_cases as SC
+    from test_gpu_minimizer import K, W, max_occ_inputs
+    text, entries, reads = max_occ_inputs()
+    for m in (1, 4, 5, 6, 64, 0xffffffff):
+        assert MO.seed(text, reads, K, W, m, entries=entries, probe_at_end_dropped=True) == MO.seed(text, reads, K, W, m, entries=entries)
+    p = SC.probe_cases(False)
+    assert p["entries"] == MO.index(p["text"], p["k"], 1)
+    for m in p["max_occs"]:
+        want, looked = MO.seed(p["text"], p["reads"], p["k"], 1, m, entries=p["entries"])
+        assert [len(a) for a in want] == p["hits"][m] and looked == len(p["reads"]), m
+        wrong, _ = MO.seed(p["text"], p["reads"], p["k"], 1, m, entries=p["entries"], probe_at_end_dropped=True)
+        assert (wrong != want) == (m == p["c"]), m
+    # the tied runs in their forward form: the plain calls' q order within 4097 equal (read, t) keys
+    case = SC.tied_runs("forward")
+    assert MO.seed(case["text"], case["reads"], SC.K, 8)[0] == case["lists"]
+    sa = SC.tied_runs("forward", sep=b"R")
+    assert SO.seed(sa["text"], sa["reads"], SC.K) == sa["lists"] == case["lists"]
+
+
 def test_the_plan_is_the_seed_plan_of_a_text_with_n_min_kmers():
     assert MO.validate(100, [0, 50], 0, 64)[0] == MO.INVALID and MO.validate(100, [0, 50], 32, 64)[0] == MO.INVALID
     assert MO.validate(100, [0, 50], 31, 64) == (0, None, 20) and MO.validate(0, [0, 50, 40], 5, 64) == (MO.INVALID, 1, 0)
